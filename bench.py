@@ -12,6 +12,8 @@ OS_CNN + Simplified_NF_WaveGlow + C_DAN (+CPC, GradNorm), synthetic univariate L
 A "step" is one pass of train_and_test.py:539-766 over one batch of 256 (target, source) pairs per GPU:
 forward of every module, the GradNorm partial backward passes, one full backward, all optimiser updates.
 Inputs are resident in HBM before the timed region.  One JSON line is printed by rank 0.
+--dump-outputs DIR: rank 0 also writes what the last timed step returned (losses, logits, features, GradNorm weights and
+norms) as DIR/<name>.npy; inputs and weights are seeded, so two builds run with the same arguments can be compared.
 """
 from __future__ import annotations
 
@@ -263,6 +265,36 @@ def north_star_extras(fst, ops, trainer, x_t, B: int, L: int):
     return out
 
 
+DUMP_BUDGET_BYTES = 64_000_000                     # --dump-outputs: all files together, .npy headers included
+
+
+def dump_outputs(out_dir: str, reports, budget: int = DUMP_BUDGET_BYTES) -> dict:
+    """Write what the timed step returned to its caller (one report per pipeline: losses, logits, features, GradNorm
+    weights and norms) as ``out_dir/<name>.npy`` — float64 and integer tensors as float64, everything else as float32.
+    If the set exceeds ``budget`` bytes, every array keeps the same fraction of its flattened elements, at positions drawn
+    by a fixed seed from its size alone, so two builds run with the same arguments write the same positions."""
+    import numpy as np
+    arrays = {}
+    for k, rep in enumerate(reports):
+        prefix = "" if len(reports) == 1 else f"src{k}."
+        for key, v in rep.items():
+            if isinstance(v, torch.Tensor):
+                v = v.detach().cpu()
+                arrays[prefix + key] = v.double() if v.dtype == torch.float64 or not v.is_floating_point() else v.float()
+    total = sum(v.numel() * v.element_size() for v in arrays.values())
+    frac = min(1.0, (budget - 1024 * len(arrays)) / max(total, 1))             # 1 KB per file for its .npy header
+    os.makedirs(out_dir, exist_ok=True)
+    written = 0
+    for name, v in arrays.items():
+        if frac < 1.0:
+            flat = v.reshape(-1)
+            keep = max(1, int(flat.numel() * frac))
+            v = flat[torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values]
+        np.save(os.path.join(out_dir, name + ".npy"), v.numpy())
+        written += v.numel() * v.element_size()
+    return {"dir": out_dir, "arrays": len(arrays), "bytes": written, "sampled": frac < 1.0}
+
+
 def kernel_peak(key: str) -> float:
     """Dense MFMA peak (algorithmic TFLOP/s) of the instruction a conv-engine kernel is built on."""
     bf3 = "bf3" in key or key.startswith(("wn_layer_", "wn_stack_")) or (key.startswith("conv_wgrad_kernel") and key.rstrip(">").endswith("true"))
@@ -288,6 +320,9 @@ def main() -> None:
     ap.add_argument("--mode", choices=["graph", "eager", "auto"], default="graph",
                     help="graph: the whole step is one captured hipGraph replayed per step — a failed capture is an error "
                          "(default); eager: launch by launch; auto: graph, falling back to eager with a note on stderr")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (every pipeline's report) as "
+                         "DIR/<name>.npy, float32/float64, at most 64 MB in all (a fixed, seeded sample beyond that)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -356,13 +391,13 @@ def main() -> None:
             torch.cuda.synchronize()
 
     def one_step():
-        rep = None
+        reps = []
         for tr, (xs, ys) in zip(trainers, src):
             if mode == "graph":
-                rep = tr.replay(x_t, y_t, xs, ys, draw_t())
+                reps.append(tr.replay(x_t, y_t, xs, ys, draw_t()))
             else:
-                rep = tr.step(x_t, y_t, xs, ys, epoch=0, t_samples=draw_t())
-        return rep
+                reps.append(tr.step(x_t, y_t, xs, ys, epoch=0, t_samples=draw_t()))
+        return reps
 
     for i in range(args.warmup):
         one_step()
@@ -372,7 +407,7 @@ def main() -> None:
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        rep = one_step()
+        reps = one_step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -381,7 +416,11 @@ def main() -> None:
         t = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    rep = {k: v.clone() for k, v in rep.items()}
+    rep = {k: v.clone() for k, v in reps[-1].items()}
+    dumped = None
+    if args.dump_outputs and rank == 0:                                       # before the extra eager step below moves state
+        dumped = dump_outputs(args.dump_outputs, reps)
+    del reps
     # per-kernel durations for the roofline leg: HIP events around every conv-engine launch of ONE extra eager step
     # (same kernels, same shapes as the timed steps; a captured graph cannot carry timing events)
     timer = ops.KernelTimer()
@@ -453,6 +492,7 @@ def main() -> None:
                                "cross-Gram; everything pointwise in f32") if ops.MATH == "bf16x3" else
                               "f32 MFMA (v_mfma_f32_32x32x2_f32, exact fp32 FMA chains) for every GEMM-shaped product",
                 "losses": {k: float(rep[k]) for k in ("nf_t", "nf_s", "ce_t", "ce_s", "sl_t", "cdan")},
+                "dumped_outputs": dumped,
                 "roofline": roofline}
         default_shape = args.c_in == 1 and args.sources == 1
         if world == 1 and not args.plain and default_shape:

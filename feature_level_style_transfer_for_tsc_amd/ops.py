@@ -145,6 +145,8 @@ def _gate_numel(acts: Tensor, *pairs: Tensor) -> int:
 
 
 def _wsrc(t: Optional[Tensor], off0: int, sm: int, sc: int, st: int) -> WSrc:
+    if t is not None:
+        _lib.require_gpu_tensor(t, "weight")                                 # the pack kernels read it on the device
     return WSrc(ptr(t) if t is not None else None, off0, sm, sc, st)
 
 

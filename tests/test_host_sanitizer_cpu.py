@@ -1,9 +1,10 @@
 """Host side of libfst_hip.so under AddressSanitizer + UndefinedBehaviorSanitizer (race / memory checking).
 
 GPU ASan is not available on this pool; what CAN be sanitized is everything the launchers do on the host — argument and extent
-checks, plan walking, pointer tables, launch geometry.  `hipcc --cuda-host-only -fsanitize=address,undefined` builds that half
-of every csrc/*.hip (the device code objects are replaced by empty stand-ins: nothing is launched), and
-tests/host_sanitize/driver.py drives every entry point up to its launch."""
+checks, plan walking, pointer tables, launch geometry.
+`hipcc --cuda-host-only -fsanitize=address,undefined -fno-gpu-sanitize` builds that half of every csrc/*.hip (the device code
+objects are replaced by empty stand-ins: nothing is launched), and tests/host_sanitize/driver.py drives every entry point up
+to its launch."""
 import glob
 import os
 import shutil
@@ -32,8 +33,9 @@ def _asan_runtime():
 @pytest.mark.skipif(not os.path.exists(_hipcc()) or _asan_runtime() is None, reason="needs hipcc and clang's ASan runtime")
 def test_host_code_under_asan_and_ubsan():
     os.makedirs(OUT, exist_ok=True)
-    flags = ["--cuda-host-only", "-O1", "-g", "-std=c++17", "-fPIC", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-             "-fno-omit-frame-pointer", "--offload-arch=gfx950", "-w"]
+    # host code only: --cuda-host-only builds no device code, and -fno-gpu-sanitize keeps the sanitizers off the device side
+    flags = ["--cuda-host-only", "-O1", "-g", "-std=c++17", "-fPIC", "-fsanitize=address,undefined", "-fno-gpu-sanitize",
+             "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "--offload-arch=gfx950", "-w"]
     srcs = sorted(glob.glob(os.path.join(CSRC, "*.hip")))
 
     def cc(src):
@@ -44,7 +46,8 @@ def test_host_code_under_asan_and_ubsan():
     with ThreadPoolExecutor(4) as ex:
         objs = list(ex.map(cc, srcs))
     lib = os.path.join(OUT, "libfst_hip_san.so")
-    subprocess.run([_hipcc(), "-shared", "-fPIC", "-fsanitize=address,undefined", *objs, "-o", lib], check=True, capture_output=True)
+    subprocess.run([_hipcc(), "-shared", "-fPIC", "-fsanitize=address,undefined", "-fno-gpu-sanitize", *objs, "-o", lib], check=True,
+                   capture_output=True)
     # the host-only objects still reference their device code objects (__hip_fatbin_<hash>): empty stand-ins
     undefined = subprocess.run(["nm", "-u", lib], check=True, capture_output=True, text=True).stdout
     syms = [l.split()[-1] for l in undefined.splitlines() if "__hip_fatbin_" in l]
@@ -54,8 +57,8 @@ def test_host_code_under_asan_and_ubsan():
         f.write("// empty stand-ins for the device code objects of the host-only sanitizer build: nothing is ever launched from it\n")
         f.writelines(f'extern "C" const char {s}[64] = {{0}};\n' for s in syms)
     subprocess.run(["g++", "-c", "-fPIC", stub, "-o", stub[:-4] + ".o"], check=True)
-    subprocess.run([_hipcc(), "-shared", "-fPIC", "-fsanitize=address,undefined", *objs, stub[:-4] + ".o", "-o", lib], check=True,
-                   capture_output=True)
+    subprocess.run([_hipcc(), "-shared", "-fPIC", "-fsanitize=address,undefined", "-fno-gpu-sanitize", *objs, stub[:-4] + ".o", "-o", lib],
+                   check=True, capture_output=True)
     env = dict(os.environ, LD_PRELOAD=_asan_runtime(), FST_HIP_LIB=lib, PYTHONPATH=ROOT,
                ASAN_OPTIONS="detect_leaks=0:halt_on_error=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "host_sanitize", "driver.py")], env=env, capture_output=True,
