@@ -581,12 +581,6 @@ __device__ __forceinline__ void wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// Diagnostic builds only (tools/build_exp.sh): FST_EXP is a bit mask that removes one cost at a time from the
-// bf3 kernel (wrong results, timing only): 1 no MFMAs, 2 no B loads, 8 no hi/lo split, 16 no A loads.
-#ifndef FST_EXP
-#define FST_EXP 0
-#endif
-
 template <int MB, int NB>
 __global__ __launch_bounds__(256, 2) void conv_gemm_bf3_kernel(ConvGemmParams p, const int32_t* __restrict__ plan) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -634,8 +628,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_bf3_kernel(ConvGemmParams p,
       const int idx = wave_s + 4 * i;
       if (idx >= NI) break;                            // wave-uniform
       if (idx < NA) {
-        const char* src = (FST_EXP & 16) ? zero16 : asrc + idx * 1024 + lane * 16;
-        __builtin_amdgcn_global_load_lds(FST_GLOBAL_PTR(src), FST_LDS_VOID(sl + idx * 1024), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds(FST_GLOBAL_PTR(asrc + idx * 1024 + lane * 16), FST_LDS_VOID(sl + idx * 1024), 16, 0, 0);
       } else {
         const int bi = idx - NA;
         const int gq = bi >= NBLK ? 1 : 0, m = bi - gq * NBLK;
@@ -643,7 +636,6 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_bf3_kernel(ConvGemmParams p,
         const int t = t4 + 32 * m + 4 * (lane & 7);
         bool ok = row < c_count && t >= 0 && t < L;
         if (m == NBLK - 1) ok = ok && spill && (lane & 7) == 0;
-        if (FST_EXP & 2) ok = false;
         const char* src = ok ? reinterpret_cast<const char*>(xb + ((long long)row * L + t)) : zero16;
         __builtin_amdgcn_global_load_lds(FST_GLOBAL_PTR(src), FST_LDS_VOID(sl + A_BYTES + gq * GS + m * 1024), 16, 0, 0);
       }
@@ -701,8 +693,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_bf3_kernel(ConvGemmParams p,
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         unsigned hh, ll;
-        if (FST_EXP & 8) { hh = __float_as_uint(v[2 * j]); ll = __float_as_uint(v[2 * j + 1]); }
-        else split_bf16_pair(v[2 * j], v[2 * j + 1], hh, ll);
+        split_bf16_pair(v[2 * j], v[2 * j + 1], hh, ll);
         h[j] = hh; l[j] = ll;
       }
       bh[nb] = __builtin_bit_cast(bf16x8, h);
@@ -719,7 +710,6 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_bf3_kernel(ConvGemmParams p,
       const bf16x8 al = *reinterpret_cast<const bf16x8*>(base + mb * 2048 + 1024 + lane * 16);
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb) {
-        if (FST_EXP & 1) { asm volatile("" ::"v"(al), "v"(ah), "v"(bh[nb]), "v"(bl[nb])); continue; }
         acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[nb], acc[mb][nb], 0, 0, 0);
         acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[nb], acc[mb][nb], 0, 0, 0);
         acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[nb], acc[mb][nb], 0, 0, 0);
@@ -1271,9 +1261,8 @@ extern "C" int fst_conv_gemm(const float* x0, int64_t x0_bs, const float* x1, in
     lds_bytes = (size_t)p.epi_lds_off * sizeof(float) + epi_bytes;       // the epilogue's transpose tiles (vec or not)
     // 32-row M-groups on 256-sample tiles with resident windows: the waves split over the M-groups instead of over time
     // (conv_win_rows_kernel: a weight fragment is fetched by one wave, not by all four)
-    static const bool rows_off = getenv("FST_WIN_ROWS") && atoi(getenv("FST_WIN_ROWS")) == 0;     // diagnostics
     if (resident && pv.MB == 1 && nb_cfg == 2 && pv.n_mgroups >= 4 && res == nullptr &&
-        !(flags & (FST_EPI_ATOMIC | FST_EPI_ACC1 | FST_EPI_ACC2)) && !rows_off)
+        !(flags & (FST_EPI_ATOMIC | FST_EPI_ACC1 | FST_EPI_ACC2)))
       fn = conv_win_rows_kernel;
   } else {
     p.epi_lds_off = (int)((lds_bytes / sizeof(float) + 3) / 4 * 4);   // after the staged window (reused across M-groups)
@@ -1308,11 +1297,6 @@ struct WgradParams {
 };
 
 #define WG_ITEMS 4   // row-blocks (32 packed K-rows each) per workgroup
-// Diagnostic builds only (tools/build_wg_exp.sh): WG_EXP removes one cost at a time from the split-bf16 weight-gradient
-// kernel (wrong results, timing only): 1 no atomics, 2 no MFMAs, 4 no dy fetch, 8 no x fetch, 16 no LDS commit.
-#ifndef WG_EXP
-#define WG_EXP 0
-#endif
 
 // CB: output-channel blocks per wave (M tile = 4*CB*32).  WIDE=false: every chunk is a single tap of ≤ 32
 // channels (window = TW columns, up to WG_ITEMS windows per workgroup); WIDE=true: one windowed chunk of
@@ -1606,12 +1590,12 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradParams p, const
     }
   };
 
-  if (tile_begin < tile_end && !(WG_EXP & 12)) fetch(tile_begin);
+  if (tile_begin < tile_end) fetch(tile_begin);
   for (int tile = tile_begin; tile < tile_end; ++tile) {
     __syncthreads();   // previous tile's readers are done
-    if (!(WG_EXP & 16)) commit();
+    commit();
     __syncthreads();
-    if (tile + 1 < tile_end && !(WG_EXP & 12)) fetch(tile + 1);
+    if (tile + 1 < tile_end) fetch(tile + 1);
 
     if (BF3) {
       // wave w multiplies item w: rows = its 32 packed K-rows (lane's row: rowoff_w), columns = every LIVE output block
@@ -1643,7 +1627,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradParams p, const
               if (blk >= nblk_live) continue;            // output-channel blocks beyond M (M = 25: three of four) hold zeros
             const bf16x8 bh = *reinterpret_cast<const bf16x8*>(dyh + blk * 32 * DYB + boff);
             const bf16x8 bl = *reinterpret_cast<const bf16x8*>(dyl + blk * 32 * DYB + boff);
-            if (WG_EXP & 2) { asm volatile("" ::"v"(al), "v"(ah), "v"(bh), "v"(bl)); continue; }
             acc[i][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[i][cb], 0, 0, 0);
             acc[i][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[i][cb], 0, 0, 0);
             acc[i][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[i][cb], 0, 0, 0);
@@ -1688,7 +1671,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradParams p, const
       for (int i = 0; i < WG_ITEMS; ++i)
 #pragma unroll
         for (int cb = 0; cb < CB; ++cb) {
-          if (WG_EXP & 1) { if (acc[i][cb][r] == 12345.678f) p.da[0] = 1.f; continue; }
           float* dst = p.da + (long long)blockIdx.x * p.slab_floats + (rec * MBW + i * CB + cb) * 64 + (c & 1) * 32 + l31;
           if (p.slab_floats) *dst = acc[i][cb][r]; else atomicAdd(dst, acc[i][cb][r]);
         }

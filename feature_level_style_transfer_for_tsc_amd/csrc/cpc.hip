@@ -484,9 +484,8 @@ static int cpc_check(const CpcParams& p, size_t lds_bytes, const char* who) {
 
 // the split-bf16 single-panel forward (cpc_enc_gather_kernel + cpc_gram_bf3_kernel) serves these shapes
 static inline bool cpc_gram_bf3_ok(int T, int B, int C, int Bc) {
-  static const bool off = getenv("FST_CPC_GRAM") && atoi(getenv("FST_CPC_GRAM")) == 0;     // diagnostics / FST_MATH=f32: the exact-f32 kernel
-  static const bool f32 = getenv("FST_MATH") && !strcmp(getenv("FST_MATH"), "f32");
-  return !off && !f32 && T > 0 && B > 0 && Bc <= CPC_PANEL && B <= 256 && C > 0 && C <= 64;
+  static const bool f32 = getenv("FST_MATH") && !strcmp(getenv("FST_MATH"), "f32");     // FST_MATH=f32: the exact-f32 kernel
+  return !f32 && T > 0 && B > 0 && Bc <= CPC_PANEL && B <= 256 && C > 0 && C <= 64;
 }
 
 extern "C" int64_t fst_cpc_workspace_floats(int T, int B, int C, int Bc) {

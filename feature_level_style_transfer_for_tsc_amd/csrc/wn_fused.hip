@@ -66,9 +66,7 @@ __device__ __forceinline__ float wn_tanh(float x) {
 // GEMM-1 stage k < 3·CH → (chunk, tap): chunks in groups of WN_GRP, tap-major inside a group — the three windows of a chunk
 // (the same lines but for 2·dil samples) are fetched WN_GRP stages apart: late enough for the first to have landed (adjacent
 // stages pulling the same lines while in flight measured 35 % slower), early enough to still be in L2.
-#ifndef WN_GRP
-#define WN_GRP 2
-#endif
+constexpr int WN_GRP = 2;
 __host__ __device__ __forceinline__ void wn_stage_chunk_tap(int k, int CH, int& c, int& tap) {
   const int g = k / (3 * WN_GRP), rem = k - g * 3 * WN_GRP;
   const int gs = CH - g * WN_GRP < WN_GRP ? CH - g * WN_GRP : WN_GRP;
@@ -176,17 +174,6 @@ extern "C" int fst_wn_pack(const float* in_w, const float* cond_w, const float* 
   FST_LAUNCH_CHECK();
   return 0;
 }
-
-// Diagnostic builds only (tools/build_wn_exp.sh): WN_EXP is a bit mask that removes one cost at a time from the fused
-// forward kernel (wrong results, timing only): 1 no MFMAs, 2 B pieces from the zero block (no activation fetch), 4 A pieces
-// from the zero block (no weight fetch), 8 no t,s / acts stores, 16 no final epilogue, 32 no B fragment reads / split, 64 no skip half
-// (no load / store of the running skip sum, no skip-row MFMAs in GEMM 2: what a deferred skip GEMM would leave in this kernel).
-#ifndef WN_EXP
-#define WN_EXP 0
-#endif
-#ifndef WN_INTERLEAVE
-#define WN_INTERLEAVE 1      // LDS-DMA pieces of stage k+2 issued between the MFMA triples of stage k (0: all up front)
-#endif
 
 #ifdef FST_STAMPS
 // Diagnostic build only (tools/build_stamps.sh): per-phase s_memtime sums of the fused forward kernel, lane 0 of every wave.
@@ -347,7 +334,6 @@ __device__ __forceinline__ int ws_opaque(int x) {
   asm volatile("" : "+s"(x));
   return x;
 }
-template <int AUX = 0>
 __device__ __forceinline__ void ws_acc_load(f32x16& v, __amdgpu_buffer_rsrc_t rs, const WsLane w, int row0, int tcol, int rv, int L) {
   L = ws_opaque(L);
   rv = ws_opaque(rv);
@@ -355,18 +341,18 @@ __device__ __forceinline__ void ws_acc_load(f32x16& v, __amdgpu_buffer_rsrc_t rs
   if (rv >= 32) {
 #pragma unroll
     for (int r = 0; r < 16; ++r)
-      v[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, w.vo, sbase + ((r & 3) + 8 * (r >> 2)) * L * 4, AUX));
+      v[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, w.vo, sbase + ((r & 3) + 8 * (r >> 2)) * L * 4, 0));
   } else {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int row = (r & 3) + 8 * (r >> 2);
       float x = 0.f;
-      if (row < rv) x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, row + 4 < rv ? w.vo : w.vo_lo, sbase + row * L * 4, AUX));
+      if (row < rv) x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, row + 4 < rv ? w.vo : w.vo_lo, sbase + row * L * 4, 0));
       v[r] = x;
     }
   }
 }
-template <int AUX = 0, class V>
+template <class V>
 __device__ __forceinline__ void ws_acc_store(const V& v, __amdgpu_buffer_rsrc_t rs, const WsLane w, int row0, int tcol, int rv, int L) {
   L = ws_opaque(L);
   rv = ws_opaque(rv);
@@ -374,13 +360,13 @@ __device__ __forceinline__ void ws_acc_store(const V& v, __amdgpu_buffer_rsrc_t 
   if (rv >= 32) {
 #pragma unroll
     for (int r = 0; r < 16; ++r)
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (float)v[r]), rs, w.vo, sbase + ((r & 3) + 8 * (r >> 2)) * L * 4, AUX);
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (float)v[r]), rs, w.vo, sbase + ((r & 3) + 8 * (r >> 2)) * L * 4, 0);
   } else {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int row = (r & 3) + 8 * (r >> 2);
       if (row < rv)
-        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (float)v[r]), rs, row + 4 < rv ? w.vo : w.vo_lo, sbase + row * L * 4, AUX);
+        __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (float)v[r]), rs, row + 4 < rv ? w.vo : w.vo_lo, sbase + row * L * 4, 0);
     }
   }
 }
@@ -470,15 +456,13 @@ __device__ __forceinline__ void wn_fwd_tile(WnFwdArgs& p, const int b, const int
     if (ss.gemm2) {
       const int idx = ss.a0 + wave_s + NW * i;
       if (i < 16 / NW && idx < NA)
-        __builtin_amdgcn_global_load_lds(WN_GLOBAL_PTR((WN_EXP & 4) ? zero16 : ss.asrc + idx * 1024 + lane * 16),
-                                         WN_LDS_VOID(ss.sl + idx * 1024), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds(WN_GLOBAL_PTR(ss.asrc + idx * 1024 + lane * 16), WN_LDS_VOID(ss.sl + idx * 1024), 16, 0, 0);
       return;
     }
     const int idx = wave_s + NW * i;
     if (idx >= NI1) return;                            // wave-uniform
     if (idx < NA) {
-      __builtin_amdgcn_global_load_lds(WN_GLOBAL_PTR((WN_EXP & 4) ? zero16 : ss.asrc + idx * 1024 + lane * 16),
-                                       WN_LDS_VOID(ss.sl + idx * 1024), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds(WN_GLOBAL_PTR(ss.asrc + idx * 1024 + lane * 16), WN_LDS_VOID(ss.sl + idx * 1024), 16, 0, 0);
     } else {
       const int bi = idx - NA;
       const int gq = bi >= F_NBLK ? 1 : 0, m = bi - gq * F_NBLK;
@@ -486,7 +470,6 @@ __device__ __forceinline__ void wn_fwd_tile(WnFwdArgs& p, const int b, const int
       const int t = ss.t4 + 32 * m + 4 * (lane & 7);
       bool ok = row < ss.c_count && t >= 0 && t < L;
       if (m == F_NBLK - 1) ok = ok && ss.spill && (lane & 7) == 0;
-      if (WN_EXP & 2) ok = false;
       const char* src = ok ? reinterpret_cast<const char*>(ss.xb + ((long long)row * L + t)) : (row == ss.ones_row ? ones16 : zero16);
       __builtin_amdgcn_global_load_lds(WN_GLOBAL_PTR(src), WN_LDS_VOID(ss.sl + WN_A_BYTES + gq * F_GS + m * 1024), 16, 0, 0);
     }
@@ -534,10 +517,6 @@ __device__ __forceinline__ void wn_fwd_tile(WnFwdArgs& p, const int b, const int
     // 60-180 cycles, an MFMA holds the issue port for 8 of its 32 — interleaved, the address arithmetic and the issue
     // ride in the matrix pipe's shadow instead of in front of it.
     const StageSrc nxt = stage_src(k + 2, slot >= 1 ? slot - 1 : 2);
-#if !WN_INTERLEAVE
-#pragma unroll
-    for (int i = 0; i < NPW1; ++i) issue_piece(nxt, i);
-#endif
     WN_T(td);
     WN_ACC(3, tc, td);                                 // LDS-DMA issue
     int shift = 0;
@@ -560,14 +539,13 @@ __device__ __forceinline__ void wn_fwd_tile(WnFwdArgs& p, const int b, const int
     };
     float v[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (WN_EXP & 32) ? (float)(k + j) : *reinterpret_cast<const float*>(bp + j * 128);
+    for (int j = 0; j < 8; ++j) v[j] = *reinterpret_cast<const float*>(bp + j * 128);
     a_frag(0);                                             // lands under the split of the B fragment below
     wn_u32x4 bh4, bl4;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       unsigned hh, ll;
-      if (WN_EXP & 32) { hh = __float_as_uint(v[2 * j]); ll = __float_as_uint(v[2 * j + 1]); }
-      else wn_split_pair(v[2 * j], v[2 * j + 1], hh, ll);
+      wn_split_pair(v[2 * j], v[2 * j + 1], hh, ll);
       bh4[j] = hh; bl4[j] = ll;
     }
     const wn_bf16x8 bh = __builtin_bit_cast(wn_bf16x8, bh4), bl = __builtin_bit_cast(wn_bf16x8, bl4);
@@ -580,19 +558,14 @@ __device__ __forceinline__ void wn_fwd_tile(WnFwdArgs& p, const int b, const int
     for (int mb = 0; mb < 8; ++mb) {
       if (mb + 1 < 8) a_frag(mb + 1);
       const wn_bf16x8 ah = fah[mb % 2], al = fal[mb % 2];
-      if (WN_EXP & 1) { asm volatile("" ::"v"(al), "v"(ah), "v"(bh), "v"(bl)); }
-      else {
-        acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[mb], 0, 0, 0);
-        acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[mb], 0, 0, 0);
-        acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[mb], 0, 0, 0);
-      }
-#if WN_INTERLEAVE
+      acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[mb], 0, 0, 0);
+      acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[mb], 0, 0, 0);
+      acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[mb], 0, 0, 0);
       if (mb < NPW1) {
         __builtin_amdgcn_sched_barrier(0);
         issue_piece(nxt, mb);
         __builtin_amdgcn_sched_barrier(0);
       }
-#endif
     }
     WN_T(tf);
     WN_ACC(5, te, tf);                                 // A fragments + MFMA issue
@@ -626,7 +599,7 @@ __device__ __forceinline__ void wn_fwd_tile(WnFwdArgs& p, const int b, const int
       const int row = blk * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
       av[r] = row == n ? 1.0f : tv[r] * sv[r];         // acts[n] = 1 carries b_rs through GEMM 2 (rows > n: tanh(0)·σ(0) = 0)
     }
-    const int rows_valid = (WN_EXP & 8) ? 0 : n - blk * 32;               // may be <= 0: nothing stored
+    const int rows_valid = n - blk * 32;               // may be <= 0: nothing stored
     ws_acc_store(tv, ts_rs, wl, blk * 32, tcol, rows_valid, L);
     ws_acc_store(sv, ts_rs, wl, n + blk * 32, tcol, rows_valid, L);
     if (p.acts) {
@@ -639,9 +612,9 @@ __device__ __forceinline__ void wn_fwd_tile(WnFwdArgs& p, const int b, const int
     // running skip sum for the skip rows (out += r) — read here, in accumulator layout, into the two accumulators the
     // gate has just consumed: the round trip hides under the remaining gate blocks and the first k-steps
     {
-      const int rows_e = (WN_EXP & 16) ? 0 : n - blk * 32;
+      const int rows_e = n - blk * 32;
       ws_acc_load(acc[blk], a_rs, wl, blk * 32, tcol, p.last ? 0 : rows_e, L);
-      ws_acc_load(acc[blk + 4], out_rs, wl, blk * 32, tcol, ((p.first != 0) | ((WN_EXP & 64) != 0)) ? 0 : rows_e, L);
+      ws_acc_load(acc[blk + 4], out_rs, wl, blk * 32, tcol, p.first ? 0 : rows_e, L);
     }
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
@@ -668,12 +641,6 @@ __device__ __forceinline__ void wn_fwd_tile(WnFwdArgs& p, const int b, const int
     if (ks >= 1) __builtin_amdgcn_s_barrier();
     const bool more = k + 2 < S;
     const StageSrc nxt = stage_src(more ? k + 2 : k, slot >= 1 ? slot - 1 : 2);
-#if !WN_INTERLEAVE
-    if (more) {
-#pragma unroll
-      for (int i = 0; i < 16 / NW; ++i) issue_piece(nxt, i);
-    }
-#endif
     const char* base = ldsb + slot * F_SLOT;
     // (fragments one row block ahead, as in GEMM 1; on the last layer the residual-row blocks 0-3 are neither read nor multiplied)
     wn_bf16x8 fah[2], fal[2];
@@ -685,22 +652,17 @@ __device__ __forceinline__ void wn_fwd_tile(WnFwdArgs& p, const int b, const int
 #pragma unroll
     for (int mb = 0; mb < 8; ++mb) {
       if (mb + 1 < 8 && !(p.last && mb + 1 < 4)) a_frag(mb + 1);
-      if (!(p.last && mb < 4) && !((WN_EXP & 64) && mb >= 4)) {                       // wave-uniform
+      if (!(p.last && mb < 4)) {                       // wave-uniform
         const wn_bf16x8 ah = fah[mb % 2], al = fal[mb % 2];
-        if (WN_EXP & 1) { asm volatile("" ::"v"(al), "v"(ah), "v"(bh2[ks]), "v"(bl2[ks])); }
-        else {
-          acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh2[ks], acc[mb], 0, 0, 0);
-          acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl2[ks], acc[mb], 0, 0, 0);
-          acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh2[ks], acc[mb], 0, 0, 0);
-        }
+        acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh2[ks], acc[mb], 0, 0, 0);
+        acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl2[ks], acc[mb], 0, 0, 0);
+        acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh2[ks], acc[mb], 0, 0, 0);
       }
-#if WN_INTERLEAVE
       if (more && mb >= 4) {                           // four pieces per wave, behind the skip-row blocks (live on every layer)
         __builtin_amdgcn_sched_barrier(0);
         issue_piece(nxt, mb - 4);
         __builtin_amdgcn_sched_barrier(0);
       }
-#endif
     }
     slot = slot == 2 ? 0 : slot + 1;
   }
@@ -710,10 +672,10 @@ __device__ __forceinline__ void wn_fwd_tile(WnFwdArgs& p, const int b, const int
   // ---------------------------------------------------------------- a_next = a + r[:n];  out (+)= r[n:]
   // straight from the accumulators (the operands were read into them before GEMM 2): stores only, nothing to wait for
 #pragma unroll
-  for (int blk = 0; blk < ((WN_EXP & 16) ? 0 : 4); ++blk) {
+  for (int blk = 0; blk < 4; ++blk) {
     const int rows_e = n - blk * 32;
     if (!p.last) ws_acc_store(acc[blk], an_rs, wl, blk * 32, tcol, rows_e, L);
-    if (!(WN_EXP & 64)) ws_acc_store(acc[blk + 4], out_rs, wl, blk * 32, tcol, rows_e, L);
+    ws_acc_store(acc[blk + 4], out_rs, wl, blk * 32, tcol, rows_e, L);
   }
   WN_T(tg3);
   WN_ACC(8, tg2, tg3);                                 // final epilogue (issue; includes waiting for the operand loads)
@@ -743,12 +705,12 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void wn_layer_fwd_kernel(
 // CU can multiply under; stamps: a third of a wave's life, profiles/r03_wn_fwd_stamps.txt).  Here ONE workgroup walks all tiles
 // of its batch elements through all layers (the same tile body, the layer's arguments from tables in the kernel-argument
 // segment; a_next / out of one layer are read by the next through the SAME CU: s_waitcnt vmcnt(0) + barrier between tiles, as in
-// wn_stack_bwd_kernel), nothing synchronises the workgroups with each other, and `stagger` starts every other workgroup half a
-// tile late: one half of the chip stores while the other multiplies.
+// wn_stack_bwd_kernel), and nothing synchronises the workgroups with each other.  (Starting every other workgroup late, so that one
+// half of the chip stores while the other multiplies, measured no gain at any delay: profiles/r04_wn_fwd_stack_timing.txt.)
 // ------------------------------------------------------------------------------------------------
 struct WnFwdStackParams {
   WnFwdParams layer[WS_MAXL];      // every layer's arguments as the per-layer launch would get them (a = the previous layer's a_next)
-  int nl, stagger;
+  int nl;
 };
 
 __global__ __launch_bounds__(512, 1) void wn_stack_fwd_kernel(WnFwdStackParams ps_by_value) {
@@ -759,8 +721,6 @@ __global__ __launch_bounds__(512, 1) void wn_stack_fwd_kernel(WnFwdStackParams p
   StackArgs& ps = *(StackArgs*)__builtin_amdgcn_kernarg_segment_ptr();
   (void)ps_by_value;
   char* const ldsb = reinterpret_cast<char*>(lds);
-  if ((blockIdx.x >> 3) & 1)                                // workgroup ids 8 apart share an XCD: alternate WITHIN each XCD
-    for (int i = 0; i < ps.stagger; ++i) __builtin_amdgcn_s_sleep(127);
   const int B = ps.layer[0].B, passes = ps.layer[0].tiles_per_seq;
   for (int b = blockIdx.x; b < B; b += gridDim.x) {
     for (int layer = 0; layer < ps.nl; ++layer) {
@@ -800,6 +760,8 @@ extern "C" int fst_wn_stack_fwd(const float* const* a_in, const int64_t* a_bs, c
     FST_REQUIRE(a_bs[i] >= (int64_t)n * L && a_bs[i] % 4 == 0 && al16(a_in[i]) && al16(images[i]) && al16(ts[i]) && al16(a_next[i]),
                 "fst_wn_stack_fwd: layer %d: batch stride %lld smaller than a sample, or an operand that is not 16-byte aligned", i,
                 (long long)a_bs[i]);
+    FST_REQUIRE(i == nl - 1 || a_in[i + 1] == a_next[i], "fst_wn_stack_fwd: the input of layer %d is not the a_next of layer %d",
+                i + 1, i);
     WnFwdParams& q = p.layer[i];
     q.a = a_in[i]; q.a_bs = a_bs[i]; q.u0 = u0; q.u0_bs = u0_bs; q.img = static_cast<const char*>(images[i]);
     q.ts = ts[i]; q.acts = nullptr; q.a_next = i == nl - 1 ? nullptr : a_next[i]; q.out = out;
@@ -807,10 +769,6 @@ extern "C" int fst_wn_stack_fwd(const float* const* a_in, const int64_t* a_bs, c
     q.CH = wn_ch(n); q.CH2 = wn_ch2(h); q.tiles_per_seq = L / 256; q.n_wg = 0;
   }
   p.nl = nl;
-  // diagnostics: every other workgroup of an XCD starts `stagger` x 3.4 us late (measured: no gain at any value — the phases of a tile
-  // are bound inside the CU, not by the memory system the CUs share; profiles/r04_wn_fwd_stack_timing.txt)
-  static const int stagger_env = getenv("FST_WN_FWD_STAGGER") ? atoi(getenv("FST_WN_FWD_STAGGER")) : -1;
-  p.stagger = stagger_env >= 0 ? stagger_env : 0;
   const int cus = fst_cu_count() > 0 ? fst_cu_count() : 256;
   if (int rc = fst_allow_full_lds((const void*)wn_stack_fwd_kernel, "fst_wn_stack_fwd")) return rc;
   hipLaunchKernelGGL(wn_stack_fwd_kernel, dim3((unsigned)(B < cus ? B : cus)), dim3(512), WN_FWD_LDS(8), (hipStream_t)stream, p);
@@ -838,10 +796,8 @@ extern "C" int fst_wn_layer_fwd(const float* a, int64_t a_bs, const float* u0, i
   p.B = B; p.L = L; p.n = n; p.h = h; p.dil = dil; p.first = first ? 1 : 0; p.last = last ? 1 : 0;
   p.CH = wn_ch(n); p.CH2 = wn_ch2(h);
   // 256-sample tiles (8 waves) when they divide the sequence and still fill the chip, else 128-sample tiles (4 waves, two per CU)
-  static const int nw_env = getenv("FST_WN_FWD_NW") ? atoi(getenv("FST_WN_FWD_NW")) : 0;        // diagnostics: force 4 or 8
   const int cus = fst_cu_count() > 0 ? fst_cu_count() : 256;
-  int nw = (L % 256 == 0 && (long long)B * (L / 256) >= cus) ? 8 : 4;
-  if (nw_env == 4 || nw_env == 8) nw = nw_env;
+  const int nw = (L % 256 == 0 && (long long)B * (L / 256) >= cus) ? 8 : 4;
   const int tn = 32 * nw;
   p.tiles_per_seq = (L + tn - 1) / tn;
   p.n_wg = B * p.tiles_per_seq;
@@ -866,10 +822,8 @@ extern "C" int fst_wn_layer_fwd(const float* a, int64_t a_bs, const float* u0, i
 // Image: S3 = 2·CH (CH on the last layer) stages × 4 row blocks × (1 KiB hi + 1 KiB lo), then 16 B of zeros; stage (src, c):
 // lane l holds W_rs[src·n + 16c + 8(l>>5) + j][blk·32 + (l&31)] — W_rs transposed, rows = acts channels.
 // ------------------------------------------------------------------------------------------------
-#ifndef WN_BWD_OCC
-#define WN_BWD_OCC 2                                 // workgroups per CU the register budget is set for: 1024 tiles of the metric shape = two full
+constexpr int WN_BWD_OCC = 2;                        // workgroups per CU the register budget is set for: 1024 tiles of the metric shape = two full
                                                      // rounds of 512 slots (three per CU: 1.33 rounds, 77 -> 70 us; and no scratch)
-#endif
 #define WN_BW_NB 4                                   // column blocks of a B row group (no tap shift: no spill block)
 #define WN_BW_GS (WN_BW_NB * 1024 + 128)
 #define WN_BW_A (4 * 2048)
@@ -1099,9 +1053,6 @@ extern "C" int fst_wn_layer_bwd(const float* d_a, const float* d_out, const floa
 #define DG_TN (8 * 32 * DG_NCB)                       // time samples per workgroup (8 waves)
 #define DG_A_BLOCKS 13
 #define DG_A_BYTES (DG_A_BLOCKS * 2048)
-#ifndef DG_EXP
-#define DG_EXP 0   // diagnostic builds only (timing, wrong results): 1 no MFMA, 2 B pieces from the zero block, 4 A pieces from the
-#endif             // zero block, 8 no epilogue stores, 16 no epilogue tiles at all, 32 no operand loads, 64 no LDS-DMA issued at all
 
 struct WnPackDgradParams {
   const float* in_w;    // [2n][n][3]
@@ -1190,11 +1141,7 @@ __global__ __launch_bounds__(512, 2) void wn_layer_dgrad_kernel(WnDgradParams p)
   const int L = p.L, n = p.n, CHK = p.CHK, dil = p.dil;
   const char* const zero16 = p.img + (long long)CHK * DG_A_BYTES;
   const int NI = DG_A_BLOCKS * 2 + 2 * p.nblkw;        // 1-KiB pieces per stage
-  int my_pieces = (NI - wave_s + 7) >> 3;              // pieces idx = wave + 8 i < NI
-  if (DG_EXP & 128) {                                  // diagnostics: no A pieces at all
-    my_pieces = 0;
-    for (int idx = wave_s; idx < NI; idx += 8) my_pieces += idx >= 2 * DG_A_BLOCKS;
-  }
+  const int my_pieces = (NI - wave_s + 7) >> 3;        // pieces idx = wave + 8 i < NI
   const int depth = p.ns - 1;                          // stages in flight
 
   // Workgroups are persistent: the launch has one per CU (the ring leaves room for one) and workgroup j walks the virtual
@@ -1213,17 +1160,15 @@ __global__ __launch_bounds__(512, 2) void wn_layer_dgrad_kernel(WnDgradParams p)
     const float* xb = p.dg + ((long long)b * (2 * n) + 16 * c) * L;
     const int c_count = min(16, 2 * n - 16 * c);
     const int w4 = (t0 - dil) & ~3;                      // 16-byte aligned start of the window (first column any tap needs)
-    if (DG_EXP & 64) return;
     for (int idx = wave_s; idx < NI; idx += 8) {         // wave-uniform trip count
       if (idx < 2 * DG_A_BLOCKS) {
-        if (DG_EXP & 128) continue;
-        __builtin_amdgcn_global_load_lds(WN_GLOBAL_PTR((DG_EXP & 4) ? zero16 : asrc + idx * 1024 + lane * 16), WN_LDS_VOID(sl + idx * 1024), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds(WN_GLOBAL_PTR(asrc + idx * 1024 + lane * 16), WN_LDS_VOID(sl + idx * 1024), 16, 0, 0);
       } else {
         const int bi = idx - 2 * DG_A_BLOCKS;
         const int gq = bi >= p.nblkw ? 1 : 0, m = bi - gq * p.nblkw;
         const int row = 8 * gq + (lane >> 3);
         const int t = w4 + 32 * m + 4 * (lane & 7);
-        const bool ok = row < c_count && t >= 0 && t < L && !(DG_EXP & 2);
+        const bool ok = row < c_count && t >= 0 && t < L;
         const char* src = ok ? reinterpret_cast<const char*>(xb + ((long long)row * L + t)) : zero16;
         __builtin_amdgcn_global_load_lds(WN_GLOBAL_PTR(src), WN_LDS_VOID(sl + DG_A_BYTES + gq * p.gsw + m * 1024), 16, 0, 0);
       }
@@ -1245,7 +1190,7 @@ __global__ __launch_bounds__(512, 2) void wn_layer_dgrad_kernel(WnDgradParams p)
 #pragma unroll
       for (int cb = 0; cb < DG_NCB; ++cb) {
         const float* src = mb < 4 ? (p.d_a ? p.d_a + ((long long)b * n + mb * 32) * L : nullptr) : p.d_u0 + (long long)b * p.d_u0_bs;
-        const int rows = (DG_EXP & 32) ? 0 : (mb < 4 ? (p.d_a ? n - mb * 32 : 0) : p.h);
+        const int rows = mb < 4 ? (p.d_a ? n - mb * 32 : 0) : p.h;
         wn_acc_load(acc[mb][cb], src, rows, L, t0 + wave_n0 + 32 * cb, lane);
       }
     // first tile: the ring is primed AFTER the operand loads, which are then older than every LDS-DMA piece and covered by
@@ -1293,7 +1238,6 @@ __global__ __launch_bounds__(512, 2) void wn_layer_dgrad_kernel(WnDgradParams p)
           const wn_bf16x8 al = *reinterpret_cast<const wn_bf16x8*>(ab + mb * 2048 + 1024 + lane * 16);
 #pragma unroll
           for (int cb = 0; cb < DG_NCB; ++cb) {
-            if (DG_EXP & 1) { asm volatile("" ::"v"(al), "v"(ah), "v"(bh[cb]), "v"(bl[cb])); continue; }
             acc[mb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[cb], acc[mb][cb], 0, 0, 0);
             acc[mb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[cb], acc[mb][cb], 0, 0, 0);
             acc[mb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[cb], acc[mb][cb], 0, 0, 0);
@@ -1324,8 +1268,7 @@ __global__ __launch_bounds__(512, 2) void wn_layer_dgrad_kernel(WnDgradParams p)
       const int i = k / DG_NCB, cb = k % DG_NCB, tcol = t0 + wave_n0 + 32 * cb;
       float* dst = i < 4 ? p.d_a_new + ((long long)b * n + i * 32) * L : p.d_u0 + (long long)b * p.d_u0_bs;
       const int rows = i < 4 ? n - i * 32 : p.h;
-      if (DG_EXP & 16) { if (acc[i][cb][0] == 12345.678f) dst[0] = 1.f; continue; }
-      wn_acc_store(acc[i][cb], dst, (DG_EXP & 8) ? 0 : rows, L, tcol, lane);
+      wn_acc_store(acc[i][cb], dst, rows, L, tcol, lane);
       if (p.row_sums && i < 4) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) tile[((r & 3) + 8 * (r >> 2) + 4 * half) * 36 + l31] = acc[i][cb][r];
@@ -1455,9 +1398,6 @@ __device__ __forceinline__ void ws_row_sums(const float (&v)[16], float* rows_w,
 // wn_layer_dgrad_kernel.  Global stores of one phase (dg, d_u0) are read by the next through LDS-DMA / loads of the SAME
 // workgroup: s_waitcnt vmcnt(0) by every wave + a workgroup barrier orders them (one CU, one L1).
 // ------------------------------------------------------------------------------------------------
-#ifndef WS_NT
-#define WS_NT 0     // cache policy of the streamed tensors (t,s, dg, d_out): 0 default, 2 non-temporal
-#endif
 #define WS_TN 512
 #define WS_NB 8                                    // 32-sample column blocks of a phase-A window row group: one per wave and column pass
 #define WS_GS (WS_NB * 1024 + 128)
@@ -1576,7 +1516,7 @@ __global__ __launch_bounds__(512, 2) void wn_stack_bwd_kernel(WnStackParams p_by
             for (int j = 0; j < 8; ++j) {
               float x = 0.f;
               if (16 * c + j < nq)
-                x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(dout_r, 16 * c + 8 + j < nq ? vf : vf_lo, sbase + j * Lq * 4, WS_NT));
+                x = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(dout_r, 16 * c + 8 + j < nq ? vf : vf_lo, sbase + j * Lq * 4, 0));
               v[j] = x;
             }
           };
@@ -1624,8 +1564,8 @@ __global__ __launch_bounds__(512, 2) void wn_stack_bwd_kernel(WnStackParams p_by
           for (int blk = 0; blk < 4; ++blk) {
             const int rows_valid = n - blk * 32;
             f32x16 tv, sv;
-            ws_acc_load<WS_NT>(tv, ts_t, wl, blk * 32, tcol, rows_valid, L);
-            ws_acc_load<WS_NT>(sv, ts_s, wl, blk * 32, tcol, rows_valid, L);
+            ws_acc_load(tv, ts_t, wl, blk * 32, tcol, rows_valid, L);
+            ws_acc_load(sv, ts_s, wl, blk * 32, tcol, rows_valid, L);
             float gt[16], gs[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -1633,8 +1573,8 @@ __global__ __launch_bounds__(512, 2) void wn_stack_bwd_kernel(WnStackParams p_by
               gt[r] = d * s2 * (1.f - t * t);
               gs[r] = d * t * s2 * (1.f - s2);
             }
-            ws_acc_store<WS_NT>(gt, dg_t, wl, blk * 32, tcol, rows_valid, L);
-            ws_acc_store<WS_NT>(gs, dg_s, wl, blk * 32, tcol, rows_valid, L);
+            ws_acc_store(gt, dg_t, wl, blk * 32, tcol, rows_valid, L);
+            ws_acc_store(gs, dg_s, wl, blk * 32, tcol, rows_valid, L);
             if (rs_out) {
               ws_row_sums(gt, rsum_w, blk * 32, rows_valid, tcol + l31 < L, lane);
               ws_row_sums(gs, rsum_w, n + blk * 32, rows_valid, tcol + l31 < L, lane);
@@ -1689,7 +1629,7 @@ __global__ __launch_bounds__(512, 2) void wn_stack_bwd_kernel(WnStackParams p_by
               const int t = w4 + 32 * m + 4 * (lane & 7);
               const bool ok = row < c_count && t >= 0 && t < L;
               const char* src = ok ? reinterpret_cast<const char*>(xb + ((long long)row * L + t)) : zero16;
-              __builtin_amdgcn_global_load_lds(WN_GLOBAL_PTR(src), WN_LDS_VOID(sl + DG_A_BYTES + gq * gsw + m * 1024), 16, 0, WS_NT);
+              __builtin_amdgcn_global_load_lds(WN_GLOBAL_PTR(src), WN_LDS_VOID(sl + DG_A_BYTES + gq * gsw + m * 1024), 16, 0, 0);
             }
           }
         };
@@ -1818,7 +1758,7 @@ extern "C" int fst_wn_stack_bwd(const float* const* ts, const void* const* img_b
               "fst_wn_stack_bwd: d_u0 batch stride %lld (needs >= h*L = %lld and a multiple of 4)", (long long)d_u0_bs, (long long)h * L);
   FST_REQUIRE((rs_b == nullptr) == (rs_d == nullptr), "fst_wn_stack_bwd: row sums of both kinds or of neither");
   auto al16 = [](const void* q) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  WnStackParams p;
+  WnStackParams p = {};
   size_t lds_bytes = WS_LDS_A + 8192;                                // phase A: the weight image and the row-sum arrays
   for (int i = 0; i < nl; ++i) {
     FST_REQUIRE(ts[i] && img_b[i] && img_d[i] && dg[i] && (i > 0 || da_out[i]), "fst_wn_stack_bwd: null operand of layer %d", i);

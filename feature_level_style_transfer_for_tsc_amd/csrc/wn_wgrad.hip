@@ -71,8 +71,6 @@ struct WwParams {
                         // one launch, one set of slabs and one reduction for all of them); workgroup x works on set x % n_sets
   int RX;               // staged rows of a k-row slot: xr·(1 + mul) (+ 8 for the leftover rows), a multiple of 8
   int misaligned;       // some tap shift is not a multiple of 4 samples (|shift| < 4): straddling pieces are patched in LDS
-  int exp;              // diagnostics (FST_WW_EXP, timing only, wrong results): 1 every LDS-DMA piece from the zero block, 2 no k-step
-                        // arithmetic (no LDS reads, splits, MFMAs), 4 no LDS-DMA at all
   int Kcols;            // slab row length = n_groups·xr
   float* slab;          // [ksplit][256][Kcols]
   float* slab_extra;    // [ksplit][256][2]
@@ -252,15 +250,14 @@ __global__ __launch_bounds__(512, 2) void wn_wgrad_kernel(WwParams p) {
   };
   // one LDS-DMA piece: k-th dy instruction / k-th k-row instruction of this wave for the stage (b, t0) into the given slot
   auto issue_dy1 = [&](int k, int b, int t0, int slot) {
-    if (p.exp & 4) return;
-    const bool ok = dsrc[k].p != nullptr && t0 + dsrc[k].t < L && !(p.exp & 1);
+    const bool ok = dsrc[k].p != nullptr && t0 + dsrc[k].t < L;
     const char* src = ok ? reinterpret_cast<const char*>(dsrc[k].p + ((long long)b * dsrc[k].bs + t0)) : zero16;
     ww_dma16(src, ww_lds + slot * dslot_bytes + (wave_s + 8 * k) * 1024);
   };
   auto issue_x1 = [&](int k, int b, int t0, int slot) {
-    if (k >= my_nx || (p.exp & 4)) return;                 // wave-uniform
+    if (k >= my_nx) return;                                // wave-uniform
     const int t = t0 + xsrc[k].t;
-    const bool ok = xsrc[k].p != nullptr && t > -4 && t < L && !(p.exp & 1);   // the piece overlaps the sequence (a straddling one is patched)
+    const bool ok = xsrc[k].p != nullptr && t > -4 && t < L;   // the piece overlaps the sequence (a straddling one is patched)
     const char* src = ok ? reinterpret_cast<const char*>(xsrc[k].p + ((long long)b * xsrc[k].bs + t0)) : zero16;
     ww_dma16(src, xring + slot * xslot_bytes + (wave_s + 8 * k) * 1024);
   };
@@ -356,7 +353,7 @@ __global__ __launch_bounds__(512, 2) void wn_wgrad_kernel(WwParams p) {
     // its bf16 hi parts (written over the first piece) and lo parts (over the second) — not once per consuming wave (each dy
     // fragment is consumed by 2 waves, each k-row fragment by 4: 280 VALU instructions per wave and stage against 36 MFMAs).
     // Thread t owns the dy units t and t + 512 (rows t>>2 and 128 + (t>>2), unit t&3) and the k-row units t (and t + 512).
-    if (!(p.exp & 2)) {
+    {
       char* const dw = ww_lds + dslot * dslot_bytes;
       char* const xw = xring + xslot * xslot_bytes;
       const int u = tid & 3, r0 = tid >> 2;
@@ -401,7 +398,6 @@ __global__ __launch_bounds__(512, 2) void wn_wgrad_kernel(WwParams p) {
     }
     __builtin_amdgcn_s_barrier();
     // ---- multiply: fragments are read as they stand (hi = first piece, lo = second piece of the lane's unit)
-    if (!(p.exp & 2))
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       ww_f32x4 araw[MT][2], braw[KT][2];
@@ -584,8 +580,6 @@ extern "C" int64_t fst_wn_wgrad_workspace_floats(int kind, int B, int L, int n, 
 }
 
 static int ww_launch(WwParams& p, int KT, void* stream, bool reduce = true) {
-  static const int exp_env = getenv("FST_WW_EXP") ? atoi(getenv("FST_WW_EXP")) : 0;
-  p.exp = exp_env;
   const size_t lds = (size_t)WW_ND * WW_MROWS * 128 + (size_t)WW_NX * p.RX * 128;
   FST_REQUIRE(lds <= 160 * 1024 && (p.RX >> 3) <= 8 * WW_MAX_NX, "fst_wn_wgrad: %d staged k-rows per stage do not fit (LDS %zu B)", p.RX, lds);
   const bool full = (p.M + 31) / 32 == 8 && ((p.K_main + 31) / 32) % (2 * KT) == 0;
@@ -834,12 +828,8 @@ __device__ __forceinline__ void tz_wait_at_most() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-#ifndef TZ_EXP
-#define TZ_EXP 0   // diagnostic builds (tools/build_tz_exp.sh; timing only, wrong results): 1 no MFMAs, 2 no split pass, 4 no LDS-DMA,
-#endif             // 8 no fragment reads, 16 no slab stores, 32 no stages
-
 #ifdef TZ_STAMPS
-// Diagnostic build only (tools/build_tz_exp.sh stamps): per-phase s_memtime sums of tz_wgrad_kernel, lane 0 of every wave.
+// Diagnostic build only (tools/build_stamps.sh): per-phase s_memtime sums of tz_wgrad_kernel, lane 0 of every wave.
 __device__ unsigned long long tz_stamps[12];
 __device__ __forceinline__ unsigned long long tz_now() {
   unsigned long long t;
@@ -891,8 +881,8 @@ __device__ __forceinline__ void tz_dma16(const char* gsrc, unsigned m0_addr) {
 // INSTRUCTION BUDGET.  With two waves per SIMD a wave issues at most one instruction every four cycles and a taken branch costs
 // tens of cycles: a stage of 36 MFMAs (2 × 1152 cycles of matrix pipe per SIMD) leaves room for ≈300 other instructions per wave.
 // The first form of this loop carried 483 (49 branches, 281 scalar) and ran at 5.9 k cycles per stage — an EMPTY loop with its
-// waits, barrier, index divisions and uniform tests alone took 1.4 k (cost removal: profiles/r04_tz_*).  Hence: diagnostics are
-// compile-time (TZ_EXP), the stage position advances by additions (no divisions), every wave issues the same number of pieces
+// waits, barrier, index divisions and uniform tests alone took 1.4 k (cost removal: profiles/r04_tz_*).  Hence: no run-time
+// diagnostics, the stage position advances by additions (no divisions), every wave issues the same number of pieces
 // per stage (rows beyond the row half re-fetch row 0 — finite values in LDS rows nobody stores — so one counted wait fits all),
 // stages past the end are "virtual" (they re-fetch and re-split the last stage instead of being tested away), FULL drops the
 // block tests around the MFMAs, and LDS addresses are a few per-lane registers plus immediates.
@@ -938,7 +928,6 @@ __global__ __launch_bounds__(512, 2) void tz_wgrad_kernel(TzParams p) {
     if (q.t0 == L) { q.t0 = 0; q.doff += dy_bs - L; q.xoff += x_bs - L; }
   };
   auto issue_stage = [&](const Pos& q, int slot) {         // NDW dy pieces, then (waves < CW) the window piece
-    if (TZ_EXP & 4) return;
 #pragma unroll
     for (int k = 0; k < NDW; ++k)
       tz_dma16(reinterpret_cast<const char*>(dsrc[k] + q.doff), lds0 + slot * DSLOT + (wave_s + 8 * k) * 1024);
@@ -949,7 +938,6 @@ __global__ __launch_bounds__(512, 2) void tz_wgrad_kernel(TzParams p) {
     }
   };
   auto wait_keep_one = [&]() {                             // all but the youngest stage's pieces of this wave have landed
-    if (TZ_EXP & 4) return;
     if (has_x) tz_wait_at_most<NDW + 1>(); else tz_wait_at_most<NDW>();
   };
 
@@ -995,11 +983,10 @@ __global__ __launch_bounds__(512, 2) void tz_wgrad_kernel(TzParams p) {
   // Software pipeline over stages: while stage c multiplies, stage c + 1 — landed in its ring slot during stage c − 1 — goes through
   // the split pass (dy rows in place, the x windows into the OTHER copies buffer) and the pieces of stage c + 3 are issued, in chunks
   // between the MFMA groups.  One barrier per stage.
-  const int n_st = (TZ_EXP & 32) ? 0 : tile_end - tile_begin;
+  const int n_st = tile_end - tile_begin;
   ww_f32x4 sd0, sd1;
   float sxv[XU][8];
   auto split_load = [&](unsigned d_slot, unsigned x_slot) {
-    if (TZ_EXP & 2) return;
     if (dy_thread) { sd0 = tz_read16<0>(d_slot + sd_lane0); sd1 = tz_read16<0>(d_slot + sd_lane1); }
 #pragma unroll
     for (int j = 0; j < XU; ++j) {
@@ -1009,13 +996,12 @@ __global__ __launch_bounds__(512, 2) void tz_wgrad_kernel(TzParams p) {
     }
   };
   auto split_dy_store = [&](unsigned d_slot) {
-    if ((TZ_EXP & 2) || !dy_thread) return;
+    if (!dy_thread) return;
     ww_u32x4 h4, l4;
     ww_split8u(sd0, sd1, h4, l4);
     tz_write16<0>(d_slot + sd_lane0, h4); tz_write16<0>(d_slot + sd_lane1, l4);
   };
   auto split_x_store = [&](unsigned cbuf) {
-    if (TZ_EXP & 2) return;
 #pragma unroll
     for (int j = 0; j < XU; ++j) {
       ww_u32x4 h4, l4;
@@ -1047,7 +1033,6 @@ __global__ __launch_bounds__(512, 2) void tz_wgrad_kernel(TzParams p) {
   ww_f32x4 araw[2][2][2], braw[2][3][2];
   auto frag_reads = [&](auto ks_c, unsigned d_slot, unsigned cbuf) {
     constexpr int ks = decltype(ks_c)::value;
-    if (TZ_EXP & 8) return;
     araw[ks][0][0] = tz_read16<0>(d_slot + a_lane[ks][0]);    araw[ks][0][1] = tz_read16<0>(d_slot + a_lane[ks][1]);
     araw[ks][1][0] = tz_read16<4096>(d_slot + a_lane[ks][0]); araw[ks][1][1] = tz_read16<4096>(d_slot + a_lane[ks][1]);
     const unsigned bb = cbuf + b_lane;
@@ -1056,7 +1041,7 @@ __global__ __launch_bounds__(512, 2) void tz_wgrad_kernel(TzParams p) {
     braw[ks][2][0] = tz_read16<((2 * ks + 8) << 4)>(bb);  braw[ks][2][1] = tz_read16<((2 * ks + 8) << 4) + LO>(bb);
   };
   auto mfma_group = [&](int ks, int sb) {
-    if (!(TZ_EXP & 1) && (FULL || (sb < k_blocks && ch_live))) {       // wave-uniform
+    if (FULL || (sb < k_blocks && ch_live)) {              // wave-uniform
       const ww_bf16x8 bh = __builtin_bit_cast(ww_bf16x8, braw[ks][sb][0]), bl = __builtin_bit_cast(ww_bf16x8, braw[ks][sb][1]);
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
@@ -1143,7 +1128,6 @@ __global__ __launch_bounds__(512, 2) void tz_wgrad_kernel(TzParams p) {
   // (virtual pieces may still be in flight: they target LDS only, and the wave's end waits for them)
 
   float* const slab = p.slab + (long long)blockIdx.x * WW_MROWS * p.Kcols;
-  if (TZ_EXP & 16) return;
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     if (wm * 2 + i >= m_blocks) break;

@@ -20,8 +20,6 @@ from .plan import Plan, Segment, build_plan, pick_mb
 EPI_RELU, EPI_ACC2, EPI_ATOMIC, EPI_ACC1 = 1, 2, 4, 8
 GEMM_BF16X3 = 16
 WGRAD_SLABS = 32
-# weight gradients: one partial-sum slab per K slice, added by the unpack pass (default) instead of fp32 atomics into one buffer
-WGRAD_TWO_STAGE = os.environ.get("FST_WGRAD_ATOMICS", "0") != "1"
 # Arithmetic of the pipelined forward / data-gradient GEMMs: "bf16x3" = split-bf16 operands on the bf16 matrix cores
 # (hi*hi + hi*lo + lo*hi, fp32 accumulate, ~5e-6 of the output scale); "f32" = exact f32 MFMA everywhere.
 MATH = os.environ.get("FST_MATH", "bf16x3")
@@ -252,11 +250,9 @@ def conv_gemm(plan: Plan, a: Tensor, x0: Tensor, x1: Optional[Tensor], bias: Opt
 def conv_wgrad(plan: Plan, x0: Tensor, x1: Optional[Tensor], dy: Tensor, dy2: Optional[Tensor], msplit: int, B: int,
                L: int, M: int, ksplit: int, x0_mul_off: int = 0) -> Tensor:
     lib = _lib.load()
-    if WGRAD_TWO_STAGE:
-        n_slabs = max(1, min(ksplit, B * ((L + 31) // 32)))                    # the library clamps the K split the same way
-        da = torch.empty(n_slabs, plan.packed_floats, device=x0.device, dtype=torch.float32)
-    else:
-        da = torch.zeros(plan.packed_floats, device=x0.device, dtype=torch.float32)
+    # one partial-sum slab per K slice, added by the unpack pass (no fp32 atomics into one buffer)
+    n_slabs = max(1, min(ksplit, B * ((L + 31) // 32)))                        # the library clamps the K split the same way
+    da = torch.empty(n_slabs, plan.packed_floats, device=x0.device, dtype=torch.float32)
     x0_bs, _ = _ncl(x0, "x0")
     x1_bs = _ncl(x1, "x1")[0] if x1 is not None else 0
     dy_bs, _ = _ncl(dy, "dy")
@@ -265,7 +261,7 @@ def conv_wgrad(plan: Plan, x0: Tensor, x1: Optional[Tensor], dy: Tensor, dy2: Op
     bf3 = MATH == "bf16x3"
     check(lib.fst_conv_wgrad(ptr(x0), x0_bs, ptr(x1), x1_bs, ptr(dy), dy_bs, ptr(dy2), dy2_bs, msplit, ptr(da),
                              ptr(plan.dev(x0.device)), plan.host_ptr(), plan.length, B, L, M, ksplit,
-                             (GEMM_BF16X3 if bf3 else 0) | (WGRAD_SLABS if WGRAD_TWO_STAGE else 0), x0_mul_off, stream_ptr()),
+                             (GEMM_BF16X3 if bf3 else 0) | WGRAD_SLABS, x0_mul_off, stream_ptr()),
           "fst_conv_wgrad")
     if t0 is not None:
         wide = bool(((plan.entries()[:, :, 1] - plan.entries()[:, :, 0]) > 1).any())
@@ -340,7 +336,7 @@ class ConvSpec:
         taps at dilation 1, no side input, at most 256 output rows, L % 32 == 0, split-bf16 mode, contiguous 16-byte aligned operands."""
         if self.C1 or MATH != "bf16x3" or not (self.dense_dw or self.row_live is None or self.dense_if_fast) or self.dil != 1:
             return False
-        if os.environ.get("FST_DENSE_TAP_WGRAD", "1") == "0" or not (x0.is_contiguous() and dy.is_contiguous()):
+        if not (x0.is_contiguous() and dy.is_contiguous()):
             return False
         if x0.data_ptr() % 16 or dy.data_ptr() % 16 or dy.size(1) != self.M or x0.size(1) != self.C0:
             return False
@@ -374,9 +370,6 @@ class ConvSpec:
         if win_bf3:
             windowed_c, mb = min(windowed_c, PIPE_C), min(mb, 2)               # bf16 window kernel: 16-channel slots, MB <= 2
         best = 1
-        forced = int(os.environ.get("FST_WIN_NB", "0")) if windowed_c else 0           # diagnostics: force the window kernel's tile width
-        if forced in (1, 2, 4) and mb * forced <= 8 and forced <= max(1, tiles128):
-            return forced
         for nb in ((4, 2, 1) if windowed_c else (2, 1)):
             if mb * nb > (4 if win_bf3 else 8) or nb > max(1, tiles128):       # bf16 window kernel: 8 tiles per wave spill (not built)
                 continue
@@ -1435,65 +1428,62 @@ def wn_stack_bwd(ts_list: Sequence[Tensor], imgs_b: Sequence[Tensor], imgs_d: Se
         KERNEL_TIMER.end("wn_stack_bwd_kernel", t0, flops, 4.0 * B * L * rows)
 
 
+def _wn_layer(S: WNSpecs, ts: Sequence[Tensor], i: int):
+    """Layer i's (in_w, cond_w, in_b, cond_b, rs_w, rs_b) in an unflattened weight or gradient list (``WNSpecs.shapes`` order;
+    cond_w / cond_b are the layer's rows of the stacked cond_layer)."""
+    n, nl = S.n, S.n_layers
+    rows = slice(2 * n * i, 2 * n * (i + 1))
+    return ts[6 + i], ts[2][rows], ts[6 + nl + i], ts[3][rows], ts[6 + 2 * nl + i], ts[6 + 3 * nl + i]
+
+
 def _wn_forward(specs: WNSpecs, u0: Tensor, flat: Tensor):
-    """Forward of the WN stack (WNFn's docstring).  Returns (o, fused, the tensors ``_wn_backward`` needs)."""
-    lib = _lib.load()
-    S, nl = specs, specs.n_layers
+    """Forward of the WN stack (WNFn's docstring).  Returns (o, fused, the tensors ``_wn_backward`` needs).  Fused
+    (``wn_fused_ok``): the gate halves ts = [tanh | sigmoid] of every layer are saved (also in the acts slots: one saved layout);
+    unfused: the gate input g and acts."""
+    S, nl, n, h = specs, specs.n_layers, specs.n, specs.h
     flat = flat.contiguous()
-    weights = S.unflatten(flat)
-    start_w, start_b, cond_w, cond_b, end_w, end_b = weights[:6]
-    in_w, in_b = weights[6: 6 + nl], weights[6 + nl: 6 + 2 * nl]
-    rs_w, rs_b = weights[6 + 2 * nl: 6 + 3 * nl], weights[6 + 3 * nl: 6 + 4 * nl]
+    W = S.unflatten(flat)
     B, _, L = u0.shape
-    h, n = S.h, S.n
+    dev = u0.device
     # the layer inputs are allocated with 16 bytes of slack either side: the time-as-k weight-gradient kernel reads the taps of
     # dilation 1 and 2 through 16-byte pieces that start up to 3 samples outside a row
-    a = S.start.forward(u0, None, start_w, None, start_b, y=empty_with_slack(B, n, L, u0.device))
-    a_list, ts_list, acts_list = [a], [], []
+    a = S.start.forward(u0, None, W[0], None, W[1], y=empty_with_slack(B, n, L, dev))
     fused = wn_fused_ok(n, h, L, a, u0, kernel=S.kernel)
     if fused:
-        # one launch per layer: dilated conv + cond rows → gate in registers → res_skip → residual / skip adds
-        out = torch.empty(B, n, L, device=u0.device, dtype=torch.float32)
-        cb = cond_b.view(nl, 2 * n)
-        stack = wn_stack_fwd_ok(n, h, L, nl, B)
-        if stack:
-            # ONE launch for all layers (persistent workgroups walk their batch elements through the stack)
-            imgs = [wn_pack_layer(in_w[i], cond_w[2 * n * i: 2 * n * (i + 1)], in_b[i], cb[i], rs_w[i], rs_b[i], n, h, i == nl - 1)
-                    for i in range(nl)]
-            a_list += [empty_with_slack(B, n, L, u0.device) for _ in range(nl - 1)]
-            ts_list = [torch.empty(B, 2 * n, L, device=u0.device, dtype=torch.float32) for _ in range(nl)]
-            wn_stack_fwd(a_list, u0, imgs, ts_list, out, n, h)
-            a = a_list[-1]
-        for i in range(0 if stack else nl):
-            last = i == nl - 1
-            img = wn_pack_layer(in_w[i], cond_w[2 * n * i: 2 * n * (i + 1)], in_b[i], cb[i], rs_w[i], rs_b[i], n, h, last)
-            ts = torch.empty(B, 2 * n, L, device=u0.device, dtype=torch.float32)
-            a_next = None if last else empty_with_slack(B, n, L, u0.device)
-            # acts = t·s is not written: the res_skip weight gradient re-forms it from the saved halves while staging
-            wn_layer_fwd(a, u0, img, ts, None, a_next, out, i == 0, last, n, h, 2 ** i)
-            ts_list.append(ts)
-            if not last:
+        # per layer: dilated conv + cond rows → gate in registers → res_skip → residual / skip adds; acts = t·s is not written
+        # (the res_skip weight gradient re-forms it from the saved halves while staging)
+        out = torch.empty(B, n, L, device=dev, dtype=torch.float32)
+        imgs = [wn_pack_layer(*_wn_layer(S, W, i), n, h, i == nl - 1) for i in range(nl)]
+        a_list = [a] + [empty_with_slack(B, n, L, dev) for _ in range(nl - 1)]
+        ts_list = [torch.empty(B, 2 * n, L, device=dev, dtype=torch.float32) for _ in range(nl)]
+        if wn_stack_fwd_ok(n, h, L, nl, B):
+            wn_stack_fwd(a_list, u0, imgs, ts_list, out, n, h)     # ONE launch: persistent workgroups walk their batch elements
+        else:
+            for i in range(nl):
+                last = i == nl - 1
+                wn_layer_fwd(a_list[i], u0, imgs[i], ts_list[i], None, None if last else a_list[i + 1], out, i == 0, last, n,
+                             h, 2 ** i)
+        acts_list = ts_list
+    else:
+        lib = _lib.load()
+        out = torch.zeros(B, n, L, device=dev, dtype=torch.float32)
+        bias_g = torch.stack(W[6 + nl: 6 + 2 * nl]) + W[3].view(nl, 2 * n)
+        a_list, ts_list, acts_list = [a], [], []
+        for i in range(nl):
+            in_w, cond_w, _, _, rs_w, rs_b = _wn_layer(S, W, i)
+            g = S.ins[i].forward(a, u0, in_w, cond_w, bias_g[i])
+            acts = torch.empty(B, n, L, device=dev, dtype=torch.float32)
+            check(lib.fst_gate_fwd(ptr(g), ptr(acts), B, n, L, _gate_numel(acts, g), stream_ptr()), "fst_gate_fwd")
+            ts_list.append(g)
+            acts_list.append(acts)
+            if i < nl - 1:
+                a_next = torch.empty_like(a)
+                S.rs[i].forward(acts, None, rs_w, None, rs_b, y=a_next, res=a, y2=out, msplit=n, flags=EPI_ACC2)
                 a = a_next
                 a_list.append(a)
-    else:
-        out = torch.zeros(B, n, L, device=u0.device, dtype=torch.float32)
-        bias_g = torch.stack(list(in_b)) + cond_b.view(nl, 2 * n)
-    for i in range(0 if fused else nl):
-        g = S.ins[i].forward(a, u0, in_w[i], cond_w[2 * n * i: 2 * n * (i + 1)], bias_g[i])
-        acts = torch.empty(B, n, L, device=u0.device, dtype=torch.float32)
-        check(lib.fst_gate_fwd(ptr(g), ptr(acts), B, n, L, _gate_numel(acts, g), stream_ptr()), "fst_gate_fwd")
-        ts_list.append(g)
-        acts_list.append(acts)
-        if i < nl - 1:
-            a_next = torch.empty_like(a)
-            S.rs[i].forward(acts, None, rs_w[i], None, rs_b[i], y=a_next, res=a, y2=out, msplit=n, flags=EPI_ACC2)
-            a = a_next
-            a_list.append(a)
-        else:
-            S.rs[i].forward(acts, None, rs_w[i], None, rs_b[i], y=None, y2=out, msplit=0, flags=EPI_ACC2)
-    o = S.end.forward(out, None, end_w, None, end_b)
-    if fused:
-        acts_list = ts_list                                           # placeholders (same count) for the saved-tensor layout
+            else:
+                S.rs[i].forward(acts, None, rs_w, None, rs_b, y=None, y2=out, msplit=0, flags=EPI_ACC2)
+    o = S.end.forward(out, None, W[4], None, W[5])
     return o, fused, (u0, out, *a_list, *ts_list, *acts_list, flat)
 
 
@@ -1501,176 +1491,175 @@ def _wn_backward(S: WNSpecs, fused: bool, sv, do: Tensor, d_u0: Tensor, need_w: 
     """Backward of the WN stack: the input gradient is ACCUMULATED into ``d_u0`` ([B, h, L], possibly a channel-slice view of
     a wider tensor with an explicit batch stride); returns the flat weight gradient (None unless ``need_w``).
     ``pool``: the in_layer / cond_layer / res_skip weight gradients served by the time-as-k kernels are not computed here — their
-    operands are left in the pool and their segments of the returned gradient are zero (``WGradJoinFn`` fills them)."""
-    lib = _lib.load()
+    operands are left in the pool and their segments of the returned gradient are zero (``WGradJoinFn`` fills them).
+    Three paths: the whole stack in one launch, fused launches layer by layer, and the conv engine after an unfused forward."""
     nl, h, n = S.n_layers, S.h, S.n
-    u0, out = sv[0], sv[1]
+    u0, out, flat = sv[0], sv[1], sv[2 + 3 * nl]
     a_list, ts_list, acts_list = sv[2: 2 + nl], sv[2 + nl: 2 + 2 * nl], sv[2 + 2 * nl: 2 + 3 * nl]
-    flat = sv[2 + 3 * nl]
-    weights = S.unflatten(flat)
-    start_w, cond_w, end_w = weights[0], weights[2], weights[4]
-    in_w, rs_w = weights[6: 6 + nl], weights[6 + 2 * nl: 6 + 3 * nl]
-    # every gradient is written into its segment of one flat tensor; every segment is written in full (all WN convs have
-    # dense plans, the bias sums are stored, not accumulated), so the tensor needs no zero fill
+    W = S.unflatten(flat)
     B, _, L = u0.shape
-    defer_in = [bool(need_w and pool is not None and fused and wn_wgrad_ok(0, B, L, n, h, 2 ** i, a_list[i])) for i in range(nl)]
-    defer_rs = [bool(need_w and pool is not None and fused and wn_wgrad_ok(1, B, L, n, h, 2 ** i)) for i in range(nl)]
-    deferring = any(defer_in) or any(defer_rs)
+    # every gradient is written into its segment of one flat tensor; every segment is written in full (all WN convs have
+    # dense plans, the bias sums are stored, not accumulated), so the tensor needs no zero fill — unless segments go to the pool
+    deferring = need_w and pool is not None and fused and any(
+        wn_wgrad_ok(0, B, L, n, h, 2 ** i, a_list[i]) or wn_wgrad_ok(1, B, L, n, h, 2 ** i) for i in range(nl))
     d_flat = (torch.zeros_like(flat) if deferring else torch.empty_like(flat)) if need_w else None
-    if need_w and os.environ.get("FST_DEBUG_POISON") == "1":          # tests: an unwritten element shows up as NaN
-        d_flat.fill_(float("nan"))
-        for i in range(nl):
-            if defer_in[i]:
-                S.unflatten(d_flat)[6 + i].zero_()
-                S.unflatten(d_flat)[2][2 * n * i: 2 * n * (i + 1)].zero_()
-            if defer_rs[i]:
-                S.unflatten(d_flat)[6 + 2 * nl + i].zero_()
-    dw = S.unflatten(d_flat) if need_w else [None] * len(S.shapes)
-    g_start_w, g_start_b, g_cond_w, g_cond_b, g_end_w, g_end_b = dw[:6]
-    g_in_w, g_in_b = dw[6: 6 + nl], dw[6 + nl: 6 + 2 * nl]
-    g_rs_w, g_rs_b = dw[6 + 2 * nl: 6 + 3 * nl], dw[6 + 3 * nl: 6 + 4 * nl]
+    G = S.unflatten(d_flat) if need_w else None
     do = do.contiguous()
-    dev = u0.device
 
-    d_out = S.end.grad_x0(do, end_w)
+    d_out = S.end.grad_x0(do, W[4])
+    da_sums = None
     if need_w:
-        S.end.grad_w(out, None, do, out0=g_end_w)
-        row_sum(do, out=g_end_b)
-    # Σ_{b,t} d_out: the res_skip bias gradient of the last layer, and the skip half of every other layer's
-    d_out_sum = row_sum(d_out, out=g_rs_b[nl - 1]) if need_w else None
-    d_a: Optional[Tensor] = None
-    d_a_sum: Optional[Tensor] = None      # Σ_{b,t} of the current d_a rows when the fused dgrad kernel left it behind
-    # res_skip bias gradients of layers 0..nl-2 = [Σ d_a ; Σ d_out] are consecutive segments: one [nl-1, 2n] view whose
-    # second half is the same for every layer (one broadcast) and whose first half is reduced straight into its row by
-    # the data-gradient launch of the layer above
-    d_rs_b_all = None
-    if need_w and nl > 1:
+        S.end.grad_w(out, None, do, out0=G[4])
+        row_sum(do, out=G[5])
+        # Σ_{b,t} d_out: the res_skip bias gradient of the last layer, and the skip half of every other layer's.  The res_skip
+        # biases of layers 0..nl-2 = [Σ d_a ; Σ d_out] are consecutive segments: one [nl-1, 2n] view, second half one broadcast
+        d_out_sum = row_sum(d_out, out=G[6 + 4 * nl - 1])
         o0 = S.offsets[6 + 3 * nl]
-        d_rs_b_all = d_flat[o0: o0 + (nl - 1) * 2 * n].view(nl - 1, 2 * n)
-        d_rs_b_all[:, n:] = d_out_sum
-    fused_bwd = fused and os.environ.get("FST_WN_BWD", "fused") == "fused"          # diagnostics: =unfused
-    fused_dg = [fused and wn_dgrad_ok(n, h, 2 ** i) and os.environ.get("FST_WN_DGRAD", "fused") == "fused" for i in range(nl)]
-    # bias-gradient row sums: every fused launch leaves per-workgroup partials in its slab; ONE reduction per kind adds the
-    # slabs of all layers straight into the flat gradient's segments (instead of one reduction launch per layer and kind)
-    stack = fused_bwd and all(fused_dg) and wn_stack_bwd_ok(n, h, L, nl)
-    if stack:
-        # ---- every layer in ONE persistent launch.  The full pass keeps each layer's dg and d_a (operands of the weight
-        # gradients); a partial pass (GradNorm: no weight gradients) rewrites one dg and two d_a scratch tensors layer after layer
-        imgs_b = [wn_pack_bwd(rs_w[i], n, i == nl - 1, acc_order=True) for i in range(nl)]
-        imgs_d = [wn_pack_dgrad(in_w[i], cond_w[2 * n * i: 2 * n * (i + 1)], n, h) for i in range(nl)]
-        new = lambda c: torch.empty(B, c, L, device=dev, dtype=torch.float32)
-        if need_w:
-            dgs = [new(2 * n) for _ in range(nl)]
-            da_out = [new(n) for _ in range(nl)]
-        else:
-            dgs = [new(2 * n)] * nl
-            da_out = [new(n)] + [None] * (nl - 1)         # d_a stays in the kernel's accumulators; only layer 0's leaves
-        da_in = [da_out[i + 1] if i + 1 < nl else None for i in range(nl)]
-        part_b = torch.empty(nl, 256, B, device=dev, dtype=torch.float32) if need_w else None
-        part_d = torch.empty(nl, 128, B, device=dev, dtype=torch.float32) if need_w else None
-        wn_stack_bwd(ts_list, imgs_b, imgs_d, dgs, da_out, d_out, d_u0, n, h, part_b, part_d)
-        if need_w:
-            for i in range(nl):
-                last = i == nl - 1
-                if defer_rs[i]:
-                    pool.add((1, i), (da_in[i], d_out, ts_list[i]))
-                elif wn_wgrad_ok(1, B, L, n, h, 2 ** i):
-                    wn_wgrad_rs(da_in[i], d_out, ts_list[i], g_rs_w[i], last, n)
-                elif last:
-                    S.rs[i].grad_w(ts_list[i][:, :n], None, d_out, x0_mul_off=n * L, out0=g_rs_w[i])
-                else:
-                    S.rs[i].grad_w(ts_list[i][:, :n], None, da_in[i], d_out, msplit=n, x0_mul_off=n * L, out0=g_rs_w[i])
-                if defer_in[i]:
-                    pool.add((0, i), (dgs[i], a_list[i], u0))
-                elif wn_wgrad_ok(0, B, L, n, h, 2 ** i, a_list[i]):
-                    wn_wgrad_in(dgs[i], a_list[i], u0, g_in_w[i], g_cond_w[2 * n * i: 2 * n * (i + 1)], n, h, 2 ** i)
-                else:
-                    S.ins[i].grad_w(a_list[i], u0, dgs[i], out0=g_in_w[i], out1=g_cond_w[2 * n * i: 2 * n * (i + 1)])
-        d_a, d_a_sum = da_out[0], None
+        d_rs_b = d_flat[o0: o0 + (nl - 1) * 2 * n].view(nl - 1, 2 * n)
+        d_rs_b[:, n:] = d_out_sum
+        # da_sums[i] receives Σ_{b,t} of the cotangent of layer i's input: the residual half of res_skip bias i-1, or for
+        # i = 0 the start conv's bias gradient
+        da_sums = [G[1]] + [d_rs_b[i, :n] for i in range(nl - 1)]
+    part_b = part_d = None         # per-workgroup row sums of dg / of d_a that fused launches leave for ONE reduction per kind
+    if not fused:
+        d_a = _wn_backward_unfused(S, W, G, a_list, ts_list, acts_list, u0, d_out, d_u0, da_sums)
+    elif all(wn_dgrad_ok(n, h, 2 ** i) for i in range(nl)) and wn_stack_bwd_ok(n, h, L, nl):
+        d_a, part_b, part_d = _wn_backward_stack(S, W, G, a_list, ts_list, u0, d_out, d_u0, pool)
     else:
-        part_b = wn_bwd_partials(nl, B, L, dev) if (need_w and fused_bwd) else None
-        part_d = wn_dgrad_partials(nl, B, L, dev) if (need_w and all(fused_dg)) else None
-    for i in (() if stack else reversed(range(nl))):
-        last = i == nl - 1
-        # ---- through res_skip: rs rows [0,n) carried d_a, rows [n,2n) (or all n rows when last) carried d_out
-        dacts = None if fused_bwd else torch.empty(B, n, L, device=dev, dtype=torch.float32)
-        if fused_bwd:
-            pass
-        elif last:
-            bf3 = bf3_ok(S.rs_T_last, L)
-            a_pk = pack_weights(S.rs_T_last, n, rs_w[i], (0, 1, n, 0), bf3=bf3)
-            conv_gemm(S.rs_T_last, a_pk, d_out, None, None, B, L, n, dacts, nb=S.start.nb_for(B, L, pick_mb(n), 0, 0),
-                      bf3=bf3)
-        else:
-            bf3 = bf3_ok(S.rs_T, L)
-            a_pk = pack_weights(S.rs_T, n, rs_w[i], (0, 1, n, 0), rs_w[i], (n * n, 1, n, 0), bf3=bf3)
-            conv_gemm(S.rs_T, a_pk, d_a, d_out, None, B, L, n, dacts, nb=S.start.nb_for(B, L, pick_mb(n), 0, 0),
-                      bf3=bf3)
-        if need_w:
-            # fused forward: acts = t·s is re-formed from the saved halves (rows [0,n) and [n,2n) of ts) while staging
-            x_rs = ts_list[i][:, :n] if fused else acts_list[i]
-            mul = n * L if fused else 0
-            if fused and os.environ.get("FST_WN_PROD", "1") == "0":                   # diagnostics: materialise acts
-                x_rs, mul = (ts_list[i][:, :n] * ts_list[i][:, n:]).contiguous(), 0
-            if defer_rs[i] and mul:
-                pool.add((1, i), (None if last else d_a, d_out, ts_list[i]))
-            elif fused and mul and wn_wgrad_ok(1, B, L, n, h, 2 ** i):
-                wn_wgrad_rs(None if last else d_a, d_out, ts_list[i], g_rs_w[i], last, n)
-            elif last:
-                S.rs[i].grad_w(x_rs, None, d_out, x0_mul_off=mul, out0=g_rs_w[i])      # (its bias gradient is d_out_sum, in place)
-            else:
-                S.rs[i].grad_w(x_rs, None, d_a, d_out, msplit=n, x0_mul_off=mul, out0=g_rs_w[i])
-            if not last and part_d is None and d_a_sum is None:   # Σ d_a not left behind by a fused data-gradient launch
-                row_sum(d_a, out=d_rs_b_all[i, :n])
-        # ---- through the gate
-        dg = torch.empty(B, 2 * n, L, device=dev, dtype=torch.float32)
-        dg_sum = None
-        if fused_bwd:
-            dg_sum = wn_layer_bwd(None if last else d_a, d_out, ts_list[i], wn_pack_bwd(rs_w[i], n, last), dg, last, n,
-                                  want_row_sums=need_w, sums_out=g_in_b[i], part=None if part_b is None else part_b[i])
-        else:
-            check(lib.fst_gate_bwd(ptr(ts_list[i]), ptr(dacts), ptr(dg), B, n, L, _gate_numel(dacts, dg, ts_list[i]),
-                                   stream_ptr()), "fst_gate_bwd")
-        if need_w:
-            # in_layer weights and the layer's rows of the stacked cond_layer weights, unpacked in place
-            if defer_in[i]:
-                pool.add((0, i), (dg, a_list[i], u0))
-            elif fused and wn_wgrad_ok(0, B, L, n, h, 2 ** i, a_list[i]):
-                wn_wgrad_in(dg, a_list[i], u0, g_in_w[i], g_cond_w[2 * n * i: 2 * n * (i + 1)], n, h, 2 ** i)
-            else:
-                S.ins[i].grad_w(a_list[i], u0, dg, out0=g_in_w[i], out1=g_cond_w[2 * n * i: 2 * n * (i + 1)])
-            if dg_sum is None and part_b is None:     # fused: partials left by the backward kernel, reduced below
-                row_sum(dg, out=g_in_b[i])
-        # ---- into the layer input (residual path + dilated conv) and into the conditioning input
-        if fused_dg[i]:
-            img_d = wn_pack_dgrad(in_w[i], cond_w[2 * n * i: 2 * n * (i + 1)], n, h)
-            if need_w:
-                d_a, d_a_sum = wn_layer_dgrad(dg, img_d, d_a, d_u0, n, h, 2 ** i, want_row_sums=True,
-                                              sums_out=d_rs_b_all[i - 1, :n] if i >= 1 else g_start_b,
-                                              part=None if part_d is None else part_d[i])
-            else:
-                d_a, d_a_sum = wn_layer_dgrad(dg, img_d, d_a, d_u0, n, h, 2 ** i), None
-        else:
-            d_a, d_a_sum = S.ins[i].grad_x01(dg, in_w[i], cond_w[2 * n * i: 2 * n * (i + 1)], d_a, d_u0), None
-    S.start.grad_x0(d_a, start_w, out=d_u0, flags=EPI_ACC1)
+        d_a, part_b, part_d = _wn_backward_layers(S, W, G, a_list, ts_list, u0, d_out, d_u0, da_sums, pool)
+    S.start.grad_x0(d_a, W[0], out=d_u0, flags=EPI_ACC1)
     if need_w:
-        S.start.grad_w(u0, None, d_a, out0=g_start_w)
+        S.start.grad_w(u0, None, d_a, out0=G[0])
+        o0 = S.offsets[6 + nl]                          # the in_layer biases of all layers: consecutive [2n] segments
         if part_b is not None:
-            # in_layer biases of all layers = consecutive segments: one [nl, 2n] reduction
-            o0 = S.offsets[6 + nl]
             torch.sum(part_b[:, : 2 * n, :], dim=2, out=d_flat[o0: o0 + nl * 2 * n].view(nl, 2 * n))
         if part_d is not None:
-            # Σ d_a entering layer i (left by the data-gradient launch of layer i) = residual half of res_skip bias i−1, and
-            # the start conv's bias gradient for i = 0
             if nl > 1:
-                torch.sum(part_d[1:, :n, :], dim=2, out=d_rs_b_all[:, :n])
-            torch.sum(part_d[0, :n, :], dim=1, out=g_start_b)
-        elif d_a_sum is None:
-            row_sum(d_a, out=g_start_b)
-        # cond_layer bias = the in_layer biases, stacked (consecutive segments: one copy)
-        o0 = S.offsets[6 + nl]
-        g_cond_b.copy_(d_flat[o0: o0 + nl * 2 * n])
+                torch.sum(part_d[1:, :n, :], dim=2, out=d_rs_b[:, :n])
+            torch.sum(part_d[0, :n, :], dim=1, out=G[1])
+        # cond_layer bias = the in_layer biases, stacked (one copy)
+        G[3].copy_(d_flat[o0: o0 + nl * 2 * n])
     return d_flat
+
+
+def _wn_wgrad_rs(S: WNSpecs, i: int, d_a: Optional[Tensor], d_out: Tensor, ts: Tensor, G, pool) -> None:
+    """res_skip weight gradient of layer i after a fused forward (acts = t·s re-formed from the saved halves while staging):
+    the time-as-k kernel where it serves the layer — its operands left in ``pool`` when there is one — else the conv engine."""
+    n, B, L, last, g_rs_w = S.n, d_out.size(0), d_out.size(2), i == S.n_layers - 1, _wn_layer(S, G, i)[4]
+    if wn_wgrad_ok(1, B, L, n, S.h, 2 ** i):
+        if pool is not None:
+            pool.add((1, i), (d_a, d_out, ts))
+        else:
+            wn_wgrad_rs(d_a, d_out, ts, g_rs_w, last, n)
+    elif last:
+        S.rs[i].grad_w(ts[:, :n], None, d_out, x0_mul_off=n * L, out0=g_rs_w)    # (its bias gradient is Σ d_out, in place)
+    else:
+        S.rs[i].grad_w(ts[:, :n], None, d_a, d_out, msplit=n, x0_mul_off=n * L, out0=g_rs_w)
+
+
+def _wn_wgrad_in(S: WNSpecs, i: int, dg: Tensor, a: Tensor, u0: Tensor, G, pool) -> None:
+    """in_layer weight gradient of layer i and its rows of the stacked cond_layer weight, chosen as in ``_wn_wgrad_rs``."""
+    n, h, B, L = S.n, S.h, dg.size(0), dg.size(2)
+    g_in_w, g_cond_w = _wn_layer(S, G, i)[:2]
+    if wn_wgrad_ok(0, B, L, n, h, 2 ** i, a):
+        if pool is not None:
+            pool.add((0, i), (dg, a, u0))
+        else:
+            wn_wgrad_in(dg, a, u0, g_in_w, g_cond_w, n, h, 2 ** i)
+    else:
+        S.ins[i].grad_w(a, u0, dg, out0=g_in_w, out1=g_cond_w)
+
+
+def _wn_backward_stack(S: WNSpecs, W, G, a_list, ts_list, u0: Tensor, d_out: Tensor, d_u0: Tensor, pool):
+    """Every layer in ONE persistent launch.  With weight gradients (``G``) each layer's dg and d_a are kept (their operands);
+    without (GradNorm's partial passes), one dg and one d_a scratch tensor are rewritten layer after layer.
+    Returns (the cotangent of layer 0's input, part_b, part_d)."""
+    nl, n, h = S.n_layers, S.n, S.h
+    B, _, L = d_out.shape
+    imgs_b = [wn_pack_bwd(_wn_layer(S, W, i)[4], n, i == nl - 1, acc_order=True) for i in range(nl)]
+    imgs_d = [wn_pack_dgrad(*_wn_layer(S, W, i)[:2], n, h) for i in range(nl)]
+    new = lambda *shape: torch.empty(*shape, device=d_out.device, dtype=torch.float32)
+    if G is None:
+        dgs, da_out = [new(B, 2 * n, L)] * nl, [new(B, n, L)] + [None] * (nl - 1)    # only layer 0's d_a leaves the kernel
+        part_b = part_d = None
+    else:
+        dgs, da_out = [new(B, 2 * n, L) for _ in range(nl)], [new(B, n, L) for _ in range(nl)]
+        part_b, part_d = new(nl, 256, B), new(nl, 128, B)
+    wn_stack_bwd(ts_list, imgs_b, imgs_d, dgs, da_out, d_out, d_u0, n, h, part_b, part_d)
+    if G is not None:
+        for i in range(nl):
+            _wn_wgrad_rs(S, i, da_out[i + 1] if i + 1 < nl else None, d_out, ts_list[i], G, pool)
+            _wn_wgrad_in(S, i, dgs[i], a_list[i], u0, G, pool)
+    return da_out[0], part_b, part_d
+
+
+def _wn_backward_layers(S: WNSpecs, W, G, a_list, ts_list, u0: Tensor, d_out: Tensor, d_u0: Tensor, da_sums, pool):
+    """Fused launches layer by layer: through res_skip and the gate (fst_wn_layer_bwd), then into the layer input and the
+    conditioning input (fst_wn_layer_dgrad; the conv engine for a dilation that kernel does not serve).
+    Returns (the cotangent of layer 0's input, part_b, part_d)."""
+    nl, n, h = S.n_layers, S.n, S.h
+    B, _, L = d_out.shape
+    dev = d_out.device
+    fused_dg = [wn_dgrad_ok(n, h, 2 ** i) for i in range(nl)]
+    part_b = wn_bwd_partials(nl, B, L, dev) if G is not None else None
+    part_d = wn_dgrad_partials(nl, B, L, dev) if G is not None and all(fused_dg) else None
+    d_a = None
+    for i in reversed(range(nl)):
+        last = i == nl - 1
+        in_w, cond_w, _, _, rs_w, _ = _wn_layer(S, W, i)
+        if G is not None:
+            _wn_wgrad_rs(S, i, d_a, d_out, ts_list[i], G, pool)
+        dg = torch.empty(B, 2 * n, L, device=dev, dtype=torch.float32)
+        wn_layer_bwd(d_a, d_out, ts_list[i], wn_pack_bwd(rs_w, n, last), dg, last, n, part=None if part_b is None else part_b[i])
+        if G is not None:
+            _wn_wgrad_in(S, i, dg, a_list[i], u0, G, pool)
+        if not fused_dg[i]:
+            d_a = S.ins[i].grad_x01(dg, in_w, cond_w, d_a, d_u0)
+            if G is not None:
+                row_sum(d_a, out=da_sums[i])
+        elif G is None:
+            d_a = wn_layer_dgrad(dg, wn_pack_dgrad(in_w, cond_w, n, h), d_a, d_u0, n, h, 2 ** i)
+        else:
+            d_a = wn_layer_dgrad(dg, wn_pack_dgrad(in_w, cond_w, n, h), d_a, d_u0, n, h, 2 ** i, want_row_sums=True,
+                                 sums_out=da_sums[i], part=None if part_d is None else part_d[i])[0]
+    return d_a, part_b, part_d
+
+
+def _wn_backward_unfused(S: WNSpecs, W, G, a_list, g_list, acts_list, u0: Tensor, d_out: Tensor, d_u0: Tensor, da_sums) -> Tensor:
+    """After an unfused forward (``wn_fused_ok`` false): dacts = W_rsᵀ·[d_a ; d_out], the gate's backward and the data gradient
+    on the conv engine, layer by layer.  Returns the cotangent of layer 0's input."""
+    lib = _lib.load()
+    nl, n = S.n_layers, S.n
+    B, _, L = d_out.shape
+    d_a = None
+    for i in reversed(range(nl)):
+        last = i == nl - 1
+        in_w, cond_w, _, _, rs_w, _ = _wn_layer(S, W, i)
+        # ---- through res_skip: rs rows [0,n) carried d_a, rows [n,2n) (or all n rows when last) carried d_out
+        dacts = torch.empty(B, n, L, device=d_out.device, dtype=torch.float32)
+        plan = S.rs_T_last if last else S.rs_T
+        bf3 = bf3_ok(plan, L)
+        a_pk = pack_weights(plan, n, rs_w, (0, 1, n, 0), *(() if last else (rs_w, (n * n, 1, n, 0))), bf3=bf3)
+        conv_gemm(plan, a_pk, d_out if last else d_a, None if last else d_out, None, B, L, n, dacts,
+                  nb=S.start.nb_for(B, L, pick_mb(n), 0, 0), bf3=bf3)
+        if G is not None:
+            g_in_w, g_cond_w, g_in_b, _, g_rs_w, _ = _wn_layer(S, G, i)
+            if last:
+                S.rs[i].grad_w(acts_list[i], None, d_out, out0=g_rs_w)      # (its bias gradient is Σ d_out, in place)
+            else:
+                S.rs[i].grad_w(acts_list[i], None, d_a, d_out, msplit=n, out0=g_rs_w)
+        # ---- through the gate
+        dg = torch.empty(B, 2 * n, L, device=d_out.device, dtype=torch.float32)
+        check(lib.fst_gate_bwd(ptr(g_list[i]), ptr(dacts), ptr(dg), B, n, L, _gate_numel(dacts, dg, g_list[i]), stream_ptr()),
+              "fst_gate_bwd")
+        if G is not None:
+            S.ins[i].grad_w(a_list[i], u0, dg, out0=g_in_w, out1=g_cond_w)
+            row_sum(dg, out=g_in_b)
+        # ---- into the layer input (residual path + dilated conv) and into the conditioning input
+        d_a = S.ins[i].grad_x01(dg, in_w, cond_w, d_a, d_u0)
+        if G is not None:
+            row_sum(d_a, out=da_sums[i])
+    return d_a
 
 
 class WNFn(torch.autograd.Function):
@@ -2032,7 +2021,7 @@ class GRULastFn(torch.autograd.Function):
                 hp = h_all[:, :-1, :].reshape(-1, H)
                 # a [3H, H] product with a reduction of B·(S−1) ≈ 2·10⁴: the K split of fst_gemm fills the chip (the library
                 # picks 6 workgroups for it: 130 µs)
-                d_w = gemm(g2, True, hp, True) if gemm_ok(g2, hp) and os.environ.get("FST_CPC_GEMM", "1") != "0" else g2.t() @ hp
+                d_w = gemm(g2, True, hp, True) if gemm_ok(g2, hp) else g2.t() @ hp
             else:
                 d_w = torch.zeros_like(w_hh)
             d_b = dgh.sum(dim=(0, 1))

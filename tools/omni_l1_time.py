@@ -39,5 +39,4 @@ with ops.pack_cache():
 us = e0.elapsed_time(e1) * 1e3 / reps
 ref = torch.nn.functional.conv1d(torch.nn.functional.pad(x[:2].double(), (int((kmax - 1) / 2), kmax - 1 - int((kmax - 1) / 2))), w.double())
 err = float((y[:2].double() - ref).abs().max() / ref.abs().max())
-print(f"FST_WIN_NB={os.environ.get('FST_WIN_NB', '-')} FST_WIN_RESIDENT_KB={os.environ.get('FST_WIN_RESIDENT_KB', '-')}: "
-      f"{us:8.1f} us  {2.0 * macs * B * L / us / 1e6:7.1f} useful TFLOP/s  rel err {err:.1e}")
+print(f"{us:8.1f} us  {2.0 * macs * B * L / us / 1e6:7.1f} useful TFLOP/s  rel err {err:.1e}")

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Diagnostics: HIP-event time of the dense many-tap weight gradient (fst_dense_tap_wgrad) at the bench's three shapes.
-Cost removal: build a diagnostic library with tools/build_tz_exp.sh <mask> (1 no MFMAs, 2 no split pass, 4 no LDS-DMA, 8 no fragment
-reads, 16 no slab stores, 32 no stages) and run with FST_HIP_LIB=build/exp/libfst_tzexp<mask>.so (the first column names the library)."""
+FST_HIP_LIB picks the library (the first column names it)."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Diagnostics: where a wave of tz_wgrad_kernel spends a stage (per-phase s_memtime sums of the stamp build).
-   tools/build_tz_exp.sh stamps && FST_HIP_LIB=build/exp/libfst_tzstamps.so python tools/tz_timeline.py"""
+   tools/build_stamps.sh && FST_HIP_LIB=build/exp/libfst_hip_stamps.so python tools/tz_timeline.py"""
 import ctypes, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

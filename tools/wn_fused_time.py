@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Time the fused WN layer kernels at the metric shape (B=256, L=512, n=120, h=25) for a few dilations.
-FST_HIP_LIB picks the library (tools/build_wn_exp.sh variants remove one cost at a time)."""
+FST_HIP_LIB picks the library."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Diagnostics: HIP-event time of the forward of one WN stack (8 layers, n=120, h=25, B=256, L=512) as per-layer launches
-(FST_WN_STACK_FWD=0) and as the one persistent launch, with the start stagger of every other workgroup swept
-(FST_WN_FWD_STAGGER units of 3.4 us; read once per process: run once per value)."""
+(FST_WN_STACK_FWD=0) and as the one persistent launch."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -23,5 +22,5 @@ for mode in ("0", "1"):
         for _ in range(10):
             ops._wn_forward(S, u0, flat)
         e1.record(); torch.cuda.synchronize()
-    print(f"FST_WN_STACK_FWD={mode} stagger={os.environ.get('FST_WN_FWD_STAGGER', 'default')}: {100 * e0.elapsed_time(e1):8.1f} us per stack forward "
+    print(f"FST_WN_STACK_FWD={mode}: {100 * e0.elapsed_time(e1):8.1f} us per stack forward "
           f"(start conv + {nl} layers + end conv) = {100 * e0.elapsed_time(e1) / nl:6.1f} us per layer")

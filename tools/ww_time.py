@@ -1,8 +1,6 @@
 #!/usr/bin/env python3
 """Diagnostics: HIP-event time of the two time-as-k weight-gradient launches (csrc/wn_wgrad.hip) at the bench's shapes, main +
-reduce kernel together.  FST_WW_EXP=<mask> (read by the library at its first launch) removes one cost at a time (timing only):
-1 LDS-DMA pieces from the zero block, 2 no k-step arithmetic, 4 no LDS-DMA at all.
-    for e in 0 1 2 3 4 6; do FST_WW_EXP=$e python tools/ww_time.py; done"""
+reduce kernel together.  SETS=<k>: k operand sets summed by one launch."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -38,7 +36,7 @@ if NS > 1:
         return out
     a, dg, ts, d_a, d_out = more(a), more(dg), more(ts), more(d_a), more(d_out)
     u0 = [u0] + [rnd(B, 2 * h, L)[:, :h] for _ in range(NS - 1)]
-out = [f"FST_WW_EXP={os.environ.get('FST_WW_EXP', '0')} sets={NS}"]
+out = [f"sets={NS}"]
 for dil in (1, 4, 128):
     out.append(f"in dil={dil}: {timed(lambda: ops.wn_wgrad_in(dg, a, u0, dw_in, dw_cond, n, h, dil)):6.1f} us")
 out.append(f"rs: {timed(lambda: ops.wn_wgrad_rs(d_a, d_out, ts, dw_rs, False, n)):6.1f} us")
