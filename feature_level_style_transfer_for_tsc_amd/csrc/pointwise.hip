@@ -463,7 +463,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_vec_kernel(const float* dy, 
   // then (rows wider than a wave) the waves' totals through LDS in wave order.
   if (row_sums) {                                          // uniform
     const int w = rv.shift < 6 ? rv.shift : 6;
-    for (int o = 1 << (w - 1); o > 0; o >>= 1) rs += __shfl_xor(rs, o, 64);
+    for (int o = (1 << w) >> 1; o > 0; o >>= 1) rs += __shfl_xor(rs, o, 64);      // w = 0 (one thread per row): no step
     if (rv.shift <= 6) {
       if (live && t0 == 0) row_sums[bc] = rs;
     } else {

@@ -606,9 +606,16 @@ def conv1d(spec: ConvSpec, x: Tensor, w: Tensor, bias: Optional[Tensor]) -> Tens
     return ConvFn.apply(spec, x, w, bias)
 
 
+def _aligned16(t: Tensor) -> Tensor:
+    """``t`` contiguous at a 16-byte aligned address (the elementwise kernels load float4): a view that starts mid-vector, e.g. an
+    odd-offset row slice handed in as a cotangent, is copied."""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 def relu_bwd(dy: Tensor, y: Tensor) -> Tensor:
     """dy·[y > 0] — the backward of a ReLU that ran in a GEMM / conv epilogue (``y`` = its output)."""
-    dy = dy.contiguous()
+    dy = _aligned16(dy)
     out = torch.empty_like(dy)
     check(_lib.load().fst_relu_bwd(ptr(dy), ptr(y), ptr(out), _same_numel(dy, y), stream_ptr()), "fst_relu_bwd")
     return out
@@ -643,8 +650,10 @@ ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2       # FST_ACT_* of include/fst_hip.h
 
 
 def gemm_ok(*ts: Tensor) -> bool:
-    """Whether ``gemm`` serves these operands: split-bf16 mode, fp32 on the GPU (any shape, any row pitch)."""
-    return MATH == "bf16x3" and all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 for t in ts)
+    """Whether ``gemm`` serves these operands: split-bf16 mode, non-empty fp32 matrices on the GPU with unit column stride and rows
+    that do not overlap (row pitch >= row length; any shape)."""
+    return MATH == "bf16x3" and all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.numel() > 0 and t.stride(1) == 1
+                                    and t.stride(0) >= t.size(1) for t in ts)
 
 
 def gemm(A: Tensor, ta: bool, B: Tensor, tb: bool, bias: Optional[Tensor] = None, act: int = ACT_NONE, slope: float = 0.0) -> Tensor:
@@ -673,7 +682,7 @@ def gemm(A: Tensor, ta: bool, B: Tensor, tb: bool, bias: Optional[Tensor] = None
 
 def act_bwd(dy: Tensor, y: Tensor, slope: float) -> Tensor:
     """dy·act'(y) from the activation's output: dy where y > 0, slope·dy elsewhere (ReLU: slope 0)."""
-    dy = dy.contiguous()
+    dy = _aligned16(dy)
     out = torch.empty_like(dy)
     check(_lib.load().fst_act_bwd(ptr(dy), ptr(y), ptr(out), _same_numel(dy, y), float(slope), stream_ptr()), "fst_act_bwd")
     return out
@@ -687,7 +696,7 @@ class LinearActFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x: Tensor, W: Tensor, b: Optional[Tensor], act: int, slope: float):
         x2 = x.reshape(-1, x.size(-1))
-        if x2.stride(1) != 1:
+        if x2.stride(1) != 1 or x2.stride(0) < x2.size(1):              # e.g. an expanded batch: rows that overlap
             x2 = x2.contiguous()
         y = gemm(x2, False, W, False, b, act, slope)
         ctx.save_for_backward(x2, W, y if act != ACT_NONE else None)
@@ -708,7 +717,7 @@ class LinearActFn(torch.autograd.Function):
 def linear_act(x: Tensor, lin: "torch.nn.Linear", act: int = ACT_NONE, slope: float = 0.0) -> Tensor:
     """``act(lin(x))``: on fst_gemm in split-bf16 mode; with FST_MATH=f32 the library's exact-f32 GEMM and the aten activation, as the
     reference runs them."""
-    if x.is_cuda and x.dtype == torch.float32 and MATH == "bf16x3":
+    if x.is_cuda and x.dtype == torch.float32 and MATH == "bf16x3" and x.numel() > 0 and lin.weight.numel() > 0:
         return LinearActFn.apply(x, lin.weight, lin.bias, act, slope)
     h = torch.nn.functional.linear(x, lin.weight, lin.bias)
     if act == ACT_RELU:

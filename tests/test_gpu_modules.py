@@ -203,6 +203,25 @@ def _joint_trainer(g):
     return tr
 
 
+def check_post_step(module, after, ref_grads, what):
+    """Parameters after one optimiser step vs the reference's, on the elements whose reference gradient is solid: at least 1e-2
+    of the module's gradient scale (the device gradients match to 2e-3 of it, so the sign and |g| >> eps of every checked
+    element agree) and 1e-4 absolute (RMSprop's first step lr·g/(0.1·|g| + eps) is then ±10·lr to within 1e-3).  Omni-scale
+    conv weights are compared on their live taps.  The recipe of the oracle's own post-step check.  Returns the count checked."""
+    scale = max(float(np.abs(v).max()) for v in ref_grads.values())
+    params, masks, checked = dict(module.named_parameters()), live_masks(module), 0
+    for k, ref_g in ref_grads.items():
+        if k not in after:
+            continue
+        solid = np.abs(ref_g) > max(1e-2 * scale, 1e-4)
+        if k in masks:
+            solid &= masks[k].astype(bool)
+        got = params[k].detach().cpu().numpy()
+        np.testing.assert_allclose(got[solid], after[k][solid], rtol=2e-4, atol=2e-5, err_msg=f"{what}post-step {k}")
+        checked += int(solid.sum())
+    return checked
+
+
 def test_joint_step_golden():
     """First joint step from the reference's captured state: all nine losses, GradNorm norms and weights,
     and the accumulated gradients the reference's double backward leaves behind (Q3)."""
@@ -228,6 +247,9 @@ def test_joint_step_golden():
     close(rep["w_t"], g["s0.w_t"], 1e-4, "w_t"); close(rep["w_s"], g["s0.w_s"], 1e-4, "w_s")
     for name in tr.MODULES:
         check_grads(tr.m[name], sub(g, f"s0.grad.{name}."), 2e-3, f"Q3 {name} ", grads=grads[name])
+    # the parameters after the device optimisers (ten RMSprops in shared launches, CPC's Adam) and the clamps of ad_net / fd_s
+    checked = sum(check_post_step(tr.m[name], sub(g, f"sd1.{name}."), sub(g, f"s0.grad.{name}."), f"{name} ") for name in tr.MODULES)
+    assert checked > 10000, checked
 
 
 @pytest.mark.parametrize("phase", ["target_pretrain", "source_pretrain", "ssl_with_ce", "ssl", "nf_with_ce", "nf"])
@@ -247,6 +269,7 @@ def test_pretraining_phase_steps_golden(phase):
             grads[name] = {n: p.grad.detach().clone() for n, p in tr.m[name].named_parameters() if p.grad is not None}
     tr.on_grads_ready = capture
     hidden0 = tr.m["clf_t"].hidden.weight.detach().clone()
+    w0_0 = dict(tr.m["fe_t"].named_parameters())["net_1.net.net.0.conv1d.weight"].detach().clone()
     nf0 = tr.m["nf"].WN[0].end.weight.detach().clone()
     rep = tr.phase_step(phase, *args, t_samples=ts)
     want_total = float(ph[f"{phase}.total"])
@@ -265,6 +288,15 @@ def test_pretraining_phase_steps_golden(phase):
     close(tr.m["clf_t"].state_dict()["net.0.bn.running_mean"], ph[f"{phase}.after.clf_t.bn_mean0"], 1e-4, "clf_t BN running mean")
     assert (not torch.equal(tr.m["clf_t"].hidden.weight.detach(), hidden0)) == ("clf_t" in tr.PHASES[phase])
     assert (not torch.equal(tr.m["nf"].WN[0].end.weight.detach(), nf0)) == ("nf" in tr.PHASES[phase])
+    # the stepped values themselves, where the reference's gradient is solid; an unstepped tensor is bit-for-bit where it was
+    for name, key, start in (("fe_t", "net_1.net.net.0.conv1d.weight", w0_0), ("clf_t", "hidden.weight", hidden0)):
+        after = ph[f"{phase}.after.{name}.{'w0' if name == 'fe_t' else 'hidden'}"]
+        want = sub(ph, f"{phase}.grad.{name}.")
+        if name in tr.PHASES[phase] and key in want:
+            assert check_post_step(tr.m[name], {key: after}, want, f"{phase} {name} ") > 0
+        else:
+            assert np.array_equal(after, start.cpu().numpy())
+            assert torch.equal(dict(tr.m[name].named_parameters())[key].detach(), start)
 
 
 def test_hipgraph_replay_matches_eager_step():
