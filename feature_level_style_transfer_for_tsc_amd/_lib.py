@@ -12,7 +12,7 @@ from typing import Optional
 
 import torch
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 _LIB_NAME = "libfst_hip.so"
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FST_HIP_LIB", os.path.join(_HERE, _LIB_NAME))     # override: diagnostic builds only
@@ -41,6 +41,7 @@ _SIGNATURES = {
                               _P, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "fst_conv_wgrad": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int, _P, _I32P, _I32P, c_int,
                                c_int, c_int, c_int, c_int, c_int, c_int64, c_void_p]),
+    "fst_conv_last_route": (c_int, [POINTER(c_int32)]),
     "fst_row_sum": (c_int, [_P, c_int64, c_int, c_int, c_int, _P, c_void_p]),
     "fst_bn_stats": (c_int, [_P, c_int, c_int, c_int, _P, c_int64, c_void_p]),
     "fst_bn_finalize": (c_int, [_P, c_int, _P, _P, _P, _P, c_int, c_int, c_float, c_float, _P, c_void_p]),

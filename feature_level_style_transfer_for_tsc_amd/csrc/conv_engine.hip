@@ -1115,6 +1115,20 @@ static conv_gemm_fn pick_conv_gemm_bf3(int MB, int NB) {
   return nullptr;
 }
 
+// what the last fst_conv_gemm / fst_conv_wgrad of this host thread launched (fst_conv_last_route)
+static thread_local int32_t g_last_route[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+
+static void set_route(int family, int a1, int a2, int a3, int a4, int a5, int epi, int ksplit) {
+  const int32_t r[8] = {family, a1, a2, a3, a4, a5, epi, ksplit};
+  for (int i = 0; i < 8; ++i) g_last_route[i] = r[i];
+}
+
+extern "C" int fst_conv_last_route(int32_t out[8]) {
+  FST_REQUIRE(out != nullptr, "fst_conv_last_route: null output");
+  for (int i = 0; i < 8; ++i) out[i] = g_last_route[i];
+  return g_last_route[0] != 0 ? 0 : -1;
+}
+
 int fst_check_plan(const int32_t* ph, int plan_len, int M, const char* who) {
   FST_REQUIRE(ph != nullptr && plan_len >= FST_PLAN_HDR, "%s: plan missing or shorter than its header", who);
   FST_REQUIRE(plan_expected_len(ph) == plan_len, "%s: plan length %d != expected %d", who, plan_len,
@@ -1145,6 +1159,7 @@ extern "C" int fst_conv_gemm(const float* x0, int64_t x0_bs, const float* x1, in
                              const int32_t* plan_dev, const int32_t* plan_host, int plan_len, const float* bias,
                              float* y, int64_t y_bs, const float* res, int64_t res_bs, float* y2, int64_t y2_bs,
                              int msplit, int m2_start, int B, int L, int M, int nb_cfg, int ksplit, int flags, void* stream) {
+  set_route(0, 0, 0, 0, 0, 0, 0, 0);
   if (int rc = fst_check_plan(plan_host, plan_len, M, "fst_conv_gemm")) return rc;
   const PlanView pv = plan_view(plan_host);
   FST_REQUIRE(x0 && a_packed && plan_dev, "fst_conv_gemm: null operand");
@@ -1192,6 +1207,7 @@ extern "C" int fst_conv_gemm(const float* x0, int64_t x0_bs, const float* x1, in
   conv_gemm_fn fn = win3 ? pick_conv_win_bf3(pv.MB, nb_cfg)
                          : (bf3 ? pick_conv_gemm_bf3(pv.MB, nb_cfg)
                                 : (pipe ? pick_conv_gemm_pipe(pv.MB, nb_cfg, vec) : pick_conv_gemm(pv.MB, nb_cfg)));
+  int family = win3 ? FST_ROUTE_WIN_BF3 : (bf3 ? FST_ROUTE_BF3 : (pipe ? FST_ROUTE_PIPE : FST_ROUTE_GEMM));
   FST_REQUIRE(fn != nullptr, "fst_conv_gemm: no kernel for MB=%d NB=%d", pv.MB, nb_cfg);
   const int TILE_N = 128 * nb_cfg;
 
@@ -1262,8 +1278,10 @@ extern "C" int fst_conv_gemm(const float* x0, int64_t x0_bs, const float* x1, in
     // 32-row M-groups on 256-sample tiles with resident windows: the waves split over the M-groups instead of over time
     // (conv_win_rows_kernel: a weight fragment is fetched by one wave, not by all four)
     if (resident && pv.MB == 1 && nb_cfg == 2 && pv.n_mgroups >= 4 && res == nullptr &&
-        !(flags & (FST_EPI_ATOMIC | FST_EPI_ACC1 | FST_EPI_ACC2)))
+        !(flags & (FST_EPI_ATOMIC | FST_EPI_ACC1 | FST_EPI_ACC2))) {
       fn = conv_win_rows_kernel;
+      family = FST_ROUTE_WIN_ROWS;
+    }
   } else {
     p.epi_lds_off = (int)((lds_bytes / sizeof(float) + 3) / 4 * 4);   // after the staged window (reused across M-groups)
     if (p.epi_vec) lds_bytes = (size_t)p.epi_lds_off * sizeof(float) + epi_bytes;
@@ -1273,6 +1291,15 @@ extern "C" int fst_conv_gemm(const float* x0, int64_t x0_bs, const float* x1, in
   if (lds_bytes > 48 * 1024)
     if (int rc = fst_allow_full_lds((const void*)fn, "fst_conv_gemm")) return rc;
   dim3 grid((unsigned)(B * p.tiles_per_seq), (unsigned)((pv.n_mgroups + p.mg_per_wg - 1) / p.mg_per_wg), (unsigned)ksplit);
+  {
+    // the branch conv_epilogue takes on these parameters (conv_win_rows_kernel: plain stores only)
+    const bool add = p.res != nullptr || (p.flags & (FST_EPI_ACC1 | FST_EPI_ACC2));
+    const int epi = (p.flags & FST_EPI_ATOMIC) ? FST_ROUTE_EPI_ATOMIC
+                    : p.epi_vec ? (add ? FST_ROUTE_EPI_VEC_ADD : FST_ROUTE_EPI_VEC)
+                                : (add ? FST_ROUTE_EPI_ADD : FST_ROUTE_EPI_PLAIN);
+    if (family == FST_ROUTE_WIN_ROWS) set_route(family, 0, 0, 0, 0, 0, epi, ksplit);
+    else set_route(family, pv.MB, nb_cfg, family == FST_ROUTE_PIPE ? (int)vec : 0, 0, 0, epi, ksplit);
+  }
   hipLaunchKernelGGL(fn, grid, dim3(256), lds_bytes, (hipStream_t)stream, p, plan_dev);
   FST_LAUNCH_CHECK();
   return 0;
@@ -1705,6 +1732,7 @@ extern "C" int fst_conv_wgrad(const float* x0, int64_t x0_bs, const float* x1, i
                               int64_t dy_bs, const float* dy2, int64_t dy2_bs, int msplit, float* da_packed,
                               const int32_t* plan_dev, const int32_t* plan_host, int plan_len, int B, int L, int M,
                               int ksplit, int flags, int64_t x0_mul_off, void* stream) {
+  set_route(0, 0, 0, 0, 0, 0, 0, 0);
   if (int rc = fst_check_plan(plan_host, plan_len, M, "fst_conv_wgrad")) return rc;
   const PlanView pv = plan_view(plan_host);
   FST_REQUIRE(x0 && dy && da_packed && plan_dev, "fst_conv_wgrad: null operand");
@@ -1808,6 +1836,7 @@ extern "C" int fst_conv_wgrad(const float* x0, int64_t x0_bs, const float* x1, i
   if (lds_bytes > 48 * 1024)
     if (int rc = fst_allow_full_lds((const void*)fn, "fst_conv_wgrad")) return rc;
   dim3 grid((unsigned)p.ksplit, (unsigned)(pv.n_items / WG_ITEMS), 1);
+  set_route(FST_ROUTE_WGRAD, pv.MB == 8 ? 2 : 1, TW, (int)wide, vmode, (int)bf3, -1, p.ksplit);
   hipLaunchKernelGGL(fn, grid, dim3(256), lds_bytes, (hipStream_t)stream, p, plan_dev);
   FST_LAUNCH_CHECK();
   return 0;

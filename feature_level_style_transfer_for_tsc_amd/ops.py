@@ -61,14 +61,28 @@ class KernelTimer:
 KERNEL_TIMER: Optional[KernelTimer] = None
 
 
-def _vec16(plan: Plan, L: int, *tensors) -> bool:
-    """Mirror of the host-side test in csrc/conv_engine.hip for the 16-byte-load kernel variants (timer keys only)."""
-    shifts4 = plan.pad_left % 4 == 0 and (plan.ntaps == 1 or plan.dil % 4 == 0)
-    ok = L % 4 == 0 and shifts4
-    for t in tensors:
-        if t is not None:
-            ok = ok and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0
-    return ok
+ROUTE_GEMM, ROUTE_PIPE, ROUTE_BF3, ROUTE_WIN_BF3, ROUTE_WIN_ROWS, ROUTE_WGRAD = 1, 2, 3, 4, 5, 6      # FST_ROUTE_* of fst_hip.h
+ROUTE_EPI_PLAIN, ROUTE_EPI_ADD, ROUTE_EPI_ATOMIC, ROUTE_EPI_VEC, ROUTE_EPI_VEC_ADD = 0, 1, 2, 3, 4
+_ROUTE_NAMES = {ROUTE_GEMM: "conv_gemm_kernel", ROUTE_PIPE: "conv_gemm_pipe_kernel", ROUTE_BF3: "conv_gemm_bf3_kernel",
+                ROUTE_WIN_BF3: "conv_win_bf3_kernel", ROUTE_WIN_ROWS: "conv_win_rows_kernel", ROUTE_WGRAD: "conv_wgrad_kernel"}
+_ROUTE_NARGS = {ROUTE_GEMM: 2, ROUTE_PIPE: 3, ROUTE_BF3: 2, ROUTE_WIN_BF3: 2, ROUTE_WIN_ROWS: 0, ROUTE_WGRAD: 5}
+_ROUTE_BOOLS = {(ROUTE_PIPE, 2), (ROUTE_WGRAD, 2), (ROUTE_WGRAD, 4)}       # (family, argument index) printed as true / false
+
+
+def last_route() -> Tuple[int, ...]:
+    """fst_conv_last_route: (family, 5 template arguments, epilogue mode, ksplit) of the last fst_conv_gemm / fst_conv_wgrad
+    launch of this thread; all zeros if none is recorded."""
+    out = (ctypes.c_int32 * 8)()
+    _lib.load().fst_conv_last_route(out)
+    return tuple(out)
+
+
+def route_kernel_name(route: Sequence[int]) -> str:
+    """The kernel template a route record names, e.g. ``conv_gemm_pipe_kernel<2, 1, true>`` (the KernelTimer key)."""
+    fam = route[0]
+    args = [("true" if route[1 + i] else "false") if (fam, i) in _ROUTE_BOOLS else str(route[1 + i])
+            for i in range(_ROUTE_NARGS[fam])]
+    return _ROUTE_NAMES[fam] + (f"<{', '.join(args)}>" if args else "")
 
 
 def bf3_ok(plan: Plan, L: int) -> bool:
@@ -229,12 +243,7 @@ def conv_gemm(plan: Plan, a: Tensor, x0: Tensor, x1: Optional[Tensor], bias: Opt
                             plan.length, ptr(bias), ptr(y), y_bs, ptr(res), res_bs, ptr(y2), y2_bs, msplit, m2_start, B, L,
                             M, nb, ksplit, flags, stream_ptr()), "fst_conv_gemm")
     if t0 is not None:
-        if bf3:
-            key = f"conv_gemm_bf3_kernel<{plan.MB}, {nb}>" if plan.pipeable else f"conv_win_bf3_kernel<{plan.MB}, {nb}>"
-        elif plan.pipeable and nb <= 2:
-            key = f"conv_gemm_pipe_kernel<{plan.MB}, {nb}, {'true' if _vec16(plan, L, x0, x1) else 'false'}>"
-        else:
-            key = f"conv_gemm_kernel<{plan.MB}, {nb}>"
+        key = route_kernel_name(last_route())
         if KERNEL_TIMER.detail:
             key += f" M={M} rec={plan.total_records} dil={plan.dil}"
         # algorithmic HBM bytes: every operand tensor once (inputs, residual / accumulate operands, outputs)
@@ -264,20 +273,7 @@ def conv_wgrad(plan: Plan, x0: Tensor, x1: Optional[Tensor], dy: Tensor, dy2: Op
                              (GEMM_BF16X3 if bf3 else 0) | WGRAD_SLABS, x0_mul_off, stream_ptr()),
           "fst_conv_wgrad")
     if t0 is not None:
-        wide = bool(((plan.entries()[:, :, 1] - plan.entries()[:, :, 0]) > 1).any())
-        if wide:
-            en = plan.entries()
-            live = en[:, :, 1] > en[:, :, 0]
-            starts4 = bool((((en[:, :, 0] * plan.dil - plan.pad_left) % 4 == 0) | ~live).all()) and \
-                bool(((((en[:, :, 1] - 1 - en[:, :, 0]) * plan.dil) % 4 == 0) | ~live).all())
-            vec = L % 4 == 0 and starts4 and all(t is None or (t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0)
-                                                  for t in (x0, x1, dy, dy2))
-        else:
-            # single-tap windows: 1 = 16-byte staging, 2 = 16-byte staging that starts (shift mod 4) samples early
-            aligned = L % 4 == 0 and all(t is None or (t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0) for t in (x0, x1, dy, dy2))
-            vec = 0 if not aligned else (1 if _vec16(plan, L, x0, x1, dy, dy2) else 2)
-        key = (f"conv_wgrad_kernel<{plan.MB // 4}, 32, {'true' if wide else 'false'}, {int(vec)}, "
-               f"{'true' if bf3 else 'false'}>")
+        key = route_kernel_name(last_route())
         if KERNEL_TIMER.detail:
             key += f" M={M} rec={plan.total_records} ksplit={ksplit}"
         rows_in = x0.size(1) + (x1.size(1) if x1 is not None else 0) + M

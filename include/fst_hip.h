@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FST_ABI_VERSION 12
+#define FST_ABI_VERSION 13
 
 int fst_version(void);
 const char* fst_last_error(void);
@@ -126,6 +126,29 @@ int fst_conv_wgrad(const float* x0, int64_t x0_bs, const float* x1, int64_t x1_b
                    const float* dy, int64_t dy_bs, const float* dy2, int64_t dy2_bs, int msplit,
                    float* da_packed, const int32_t* plan_dev, const int32_t* plan_host, int plan_len,
                    int B, int L, int M, int ksplit, int flags /* 0 or FST_GEMM_BF16X3 */, int64_t x0_mul_off, void* stream);
+
+/* The kernel instance the last fst_conv_gemm / fst_conv_wgrad call of the calling host thread launched, recorded from the
+ * values the launcher dispatched with (host-side, thread-local; a call refused before its launch clears it):
+ *   out[0]     family: FST_ROUTE_GEMM conv_gemm_kernel<MB,NB>, FST_ROUTE_PIPE conv_gemm_pipe_kernel<MB,NB,VEC>,
+ *              FST_ROUTE_BF3 conv_gemm_bf3_kernel<MB,NB>, FST_ROUTE_WIN_BF3 conv_win_bf3_kernel<MB,NB>,
+ *              FST_ROUTE_WIN_ROWS conv_win_rows_kernel (no template arguments),
+ *              FST_ROUTE_WGRAD conv_wgrad_kernel<CB,TW,WIDE,VEC,BF3>
+ *   out[1..5]  the template arguments in declaration order, unused ones 0 (bools as 0 / 1)
+ *   out[6]     forward epilogue: FST_ROUTE_EPI_PLAIN, _ADD, _ATOMIC, _VEC (16-byte plain), _VEC_ADD; -1 for fst_conv_wgrad
+ *   out[7]     ksplit of the launch after the library's clamp
+ * Returns 0, or -1 when no launch is recorded (out zero-filled) or out is null. */
+#define FST_ROUTE_GEMM      1
+#define FST_ROUTE_PIPE      2
+#define FST_ROUTE_BF3       3
+#define FST_ROUTE_WIN_BF3   4
+#define FST_ROUTE_WIN_ROWS  5
+#define FST_ROUTE_WGRAD     6
+#define FST_ROUTE_EPI_PLAIN   0
+#define FST_ROUTE_EPI_ADD     1
+#define FST_ROUTE_EPI_ATOMIC  2
+#define FST_ROUTE_EPI_VEC     3
+#define FST_ROUTE_EPI_VEC_ADD 4
+int fst_conv_last_route(int32_t out[8]);
 
 /* out[m] = Σ_{b,t} x[b,m,t]   (bias gradients): one workgroup per row, written (no zero fill, no atomics, fixed order). */
 int fst_row_sum(const float* x, int64_t x_bs, int B, int C, int L, float* out, void* stream);
