@@ -14,6 +14,9 @@ forward of every module, the GradNorm partial backward passes, one full backward
 Inputs are resident in HBM before the timed region.  One JSON line is printed by rank 0.
 --dump-outputs DIR: rank 0 also writes what the last timed step returned (losses, logits, features, GradNorm weights and
 norms) as DIR/<name>.npy; inputs and weights are seeded, so two builds run with the same arguments can be compared.
+A plain run does only that: set up, warm up, time the steps, dump, print the line.  --full adds everything else the
+benchmark measures after the headline: the roofline leg (one extra eager step with per-kernel HIP-event timing) and, on
+one GPU, the S1 classifier step, the north-star extras, the FST_MATH=f32 rate (a child process) and the CPU baseline.
 """
 from __future__ import annotations
 
@@ -159,12 +162,11 @@ def self_launch(args) -> int:
 
 
 def f32_mode_rate(args):
-    """The same step with every GEMM on the exact-f32 MFMA (FST_MATH=f32), measured by a child process (the arithmetic is
+    """The same step with every GEMM on the exact-f32 MFMA (FST_MATH=f32), measured by a plain child run (the arithmetic is
     fixed at import).  Sits beside the split-bf16 headline so the narrower product arithmetic is visible in the line."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(max(2, min(args.steps, 4))), "--warmup", "1",
-           "--batch", str(args.batch), "--length", str(args.length), "--c-in", str(args.c_in), "--sources", str(args.sources),
-           "--plain"]
+           "--batch", str(args.batch), "--length", str(args.length), "--c-in", str(args.c_in), "--sources", str(args.sources)]
     out = subprocess.run(cmd, env=dict(os.environ, FST_MATH="f32"), cwd=ROOT, capture_output=True, text=True, timeout=900)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     if out.returncode != 0 or not lines:
@@ -301,6 +303,43 @@ def kernel_peak(key: str) -> float:
     return BF16X3_MFMA_PEAK_TFLOPS if bf3 else F32_MFMA_PEAK_TFLOPS
 
 
+def roofline_record(ks: dict, n_timer_steps: int) -> dict:
+    """The roofline leg of --full: the conv-engine kernel with the largest total time in ``ks`` (``KernelTimer.summary()``
+    of ``n_timer_steps`` eager steps), priced against both the MFMA and the HBM ceiling, plus every kernel's own rate."""
+    dom_key = max(ks, key=lambda k: ks[k]["total_ms"])
+    dom = ks[dom_key]
+    achieved = dom["flops"] / (dom["total_ms"] * 1e-3) / 1e12
+    conv_ms = sum(v["total_ms"] for v in ks.values()) / n_timer_steps
+    traffic, traffic_src = None, None
+    # PMC passes cannot run inside bench.py: the newest committed counter summary that covers this kernel
+    for tname in ("traffic_r04.json", "traffic_r03.json", "traffic_r02.json", "traffic_r01.json"):
+        tpath = os.path.join(ROOT, "profiles", tname)
+        if os.path.exists(tpath):
+            tj = json.load(open(tpath))
+            if tj["hbm_bytes_per_launch"].get(dom_key) is not None:
+                traffic, traffic_src = tj["hbm_bytes_per_launch"][dom_key], tj["source"]
+                break
+    peak = kernel_peak(dom_key)
+    mfma = {"achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
+            "peak_basis": ("bf16 dense MFMA peak 2516.6 TFLOP/s / 3 MFMAs per split-bf16 product" if peak != F32_MFMA_PEAK_TFLOPS
+                           else "f32 MFMA peak")}
+    gbs = dom["bytes"] / (dom["total_ms"] * 1e-3) / 1e9
+    hbm = {"achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS,
+           "algorithmic_bytes_per_launch": dom["bytes"] / dom["launches"]}
+    near = hbm if hbm["frac"] >= mfma["frac"] else mfma      # the roofline the dominant kernel is closer to
+    return {"bound": "hbm" if near is hbm else "mfma", "kernel": dom_key, "achieved": near["achieved"],
+            "peak": near["peak"], "unit": near["unit"], "frac": near["frac"], "mfma": mfma, "hbm": hbm,
+            "traffic": traffic,
+            "traffic_unit": "HBM bytes per launch", "traffic_source": traffic_src,
+            "algorithmic_flop_per_launch": dom["flops"] / dom["launches"],
+            "avg_launch_us": dom["avg_us"], "launches_per_step": dom["launches"] / n_timer_steps,
+            "conv_engine_ms_per_step": conv_ms,
+            "kernels": {k: {"avg_us": round(v["avg_us"], 1), "launches_per_step": v["launches"] / n_timer_steps,
+                            "tflops": round(v["flops"] / (v["total_ms"] * 1e-3) / 1e12, 2),
+                            "frac_of_mfma_peak": round(v["flops"] / (v["total_ms"] * 1e-3) / 1e12 / kernel_peak(k), 3)}
+                        for k, v in ks.items()}}
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -308,7 +347,12 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=256, help="pairs per GPU")
     ap.add_argument("--length", type=int, default=512)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the benchmark measures: the roofline leg (one extra eager "
+                         "step with per-kernel timing) and, on one GPU, the S1 classifier step, the north-star extras, the "
+                         "FST_MATH=f32 rate and the CPU baseline. Without it a run only sets up, warms up, times the steps, "
+                         "writes --dump-outputs and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-pairs", type=int, default=0, help="pairs per step of the CPU baseline (default: --batch, the metric's batch)")
     ap.add_argument("--cpu-steps", type=int, default=1)
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU baseline (default: min(affinity, physical cores, cgroup quota))")
@@ -316,7 +360,9 @@ def main() -> None:
     ap.add_argument("--sources", type=int, default=1,
                     help="independent source->target pipelines trained side by side on this GPU (configs[2]: 4); "
                          "value = aggregate pairs/s")
-    ap.add_argument("--plain", action="store_true", help="step rate only: no S1 / north-star extras / CPU / f32 legs")
+    ap.add_argument("--plain", action="store_true",
+                    help="with --full: the roofline leg only, no S1 / north-star extras / CPU / f32 legs (without --full "
+                         "it changes nothing)")
     ap.add_argument("--mode", choices=["graph", "eager", "auto"], default="graph",
                     help="graph: the whole step is one captured hipGraph replayed per step — a failed capture is an error "
                          "(default); eager: launch by launch; auto: graph, falling back to eager with a note on stderr")
@@ -418,55 +464,23 @@ def main() -> None:
         dt = float(t.item())
     rep = {k: v.clone() for k, v in reps[-1].items()}
     dumped = None
-    if args.dump_outputs and rank == 0:                                       # before the extra eager step below moves state
+    if args.dump_outputs and rank == 0:                                       # before --full's extra eager step moves state
         dumped = dump_outputs(args.dump_outputs, reps)
     del reps
-    # per-kernel durations for the roofline leg: HIP events around every conv-engine launch of ONE extra eager step
-    # (same kernels, same shapes as the timed steps; a captured graph cannot carry timing events)
-    timer = ops.KernelTimer()
-    n_timer_steps = 1
-    # every rank runs the step (it contains the gradient all-reduce); only rank 0 records the kernel timings
-    ops.KERNEL_TIMER = timer if rank == 0 else None
-    trainer.step(x_t, y_t, x_s, y_s, epoch=0, t_samples=draw_t())
-    torch.cuda.synchronize()
-    ops.KERNEL_TIMER = None
+    if args.full:
+        # per-kernel durations for the roofline leg: HIP events around every conv-engine launch of ONE extra eager step
+        # (same kernels, same shapes as the timed steps; a captured graph cannot carry timing events)
+        timer = ops.KernelTimer()
+        n_timer_steps = 1
+        # every rank runs the step (it contains the gradient all-reduce); only rank 0 records the kernel timings
+        ops.KERNEL_TIMER = timer if rank == 0 else None
+        trainer.step(x_t, y_t, x_s, y_s, epoch=0, t_samples=draw_t())
+        torch.cuda.synchronize()
+        ops.KERNEL_TIMER = None
     ms_per_step = 1e3 * dt / args.steps
     value = world * args.sources * args.batch * args.steps / dt
 
     if rank == 0:
-        ks = timer.summary()
-        dom_key = max(ks, key=lambda k: ks[k]["total_ms"])
-        dom = ks[dom_key]
-        achieved = dom["flops"] / (dom["total_ms"] * 1e-3) / 1e12
-        conv_ms = sum(v["total_ms"] for v in ks.values()) / n_timer_steps
-        traffic, traffic_src = None, None
-        # PMC passes cannot run inside bench.py: the newest committed counter summary that covers this kernel
-        for tname in ("traffic_r04.json", "traffic_r03.json", "traffic_r02.json", "traffic_r01.json"):
-            tpath = os.path.join(ROOT, "profiles", tname)
-            if os.path.exists(tpath):
-                tj = json.load(open(tpath))
-                if tj["hbm_bytes_per_launch"].get(dom_key) is not None:
-                    traffic, traffic_src = tj["hbm_bytes_per_launch"][dom_key], tj["source"]
-                    break
-        peak = kernel_peak(dom_key)
-        mfma = {"achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
-                "peak_basis": ("bf16 dense MFMA peak 2516.6 TFLOP/s / 3 MFMAs per split-bf16 product" if peak != F32_MFMA_PEAK_TFLOPS
-                               else "f32 MFMA peak")}
-        gbs = dom["bytes"] / (dom["total_ms"] * 1e-3) / 1e9
-        hbm = {"achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS,
-               "algorithmic_bytes_per_launch": dom["bytes"] / dom["launches"]}
-        near = hbm if hbm["frac"] >= mfma["frac"] else mfma      # the roofline the dominant kernel is closer to
-        roofline = {"bound": "hbm" if near is hbm else "mfma", "kernel": dom_key, "achieved": near["achieved"],
-                    "peak": near["peak"], "unit": near["unit"], "frac": near["frac"], "mfma": mfma, "hbm": hbm,
-                    "traffic": traffic,
-                    "traffic_unit": "HBM bytes per launch", "traffic_source": traffic_src,
-                    "algorithmic_flop_per_launch": dom["flops"] / dom["launches"],
-                    "avg_launch_us": dom["avg_us"], "launches_per_step": dom["launches"] / n_timer_steps,
-                    "conv_engine_ms_per_step": conv_ms,
-                    "kernels": {k: {"avg_us": round(v["avg_us"], 1), "launches_per_step": v["launches"] / n_timer_steps,
-                                    "tflops": round(v["flops"] / (v["total_ms"] * 1e-3) / 1e12, 2),
-                                    "frac_of_mfma_peak": round(v["flops"] / (v["total_ms"] * 1e-3) / 1e12 / kernel_peak(k), 3)}
-                                for k, v in ks.items()}}
         metric = "train-step samples/sec (univariate TS, len=512, batch=256) at 1/2/4/8 MI355X"
         try:                                                                   # BASELINE.json's own string when present
             metric = json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"] or metric
@@ -492,17 +506,19 @@ def main() -> None:
                                "cross-Gram; everything pointwise in f32") if ops.MATH == "bf16x3" else
                               "f32 MFMA (v_mfma_f32_32x32x2_f32, exact fp32 FMA chains) for every GEMM-shaped product",
                 "losses": {k: float(rep[k]) for k in ("nf_t", "nf_s", "ce_t", "ce_s", "sl_t", "cdan")},
-                "dumped_outputs": dumped,
-                "roofline": roofline}
+                "dumped_outputs": dumped}
+        if args.full:
+            line["roofline"] = roofline_record(timer.summary(), n_timer_steps)
+        legs = args.full and world == 1 and not args.plain                     # the legs that run programs of their own
         default_shape = args.c_in == 1 and args.sources == 1
-        if world == 1 and not args.plain and default_shape:
+        if legs and default_shape:
             line["s1_classifier_step"] = classifier_step_rate(fst, device, args.batch, args.length)
             line["north_star_extras"] = north_star_extras(fst, ops, trainer, x_t, args.batch, args.length)
-        if world == 1 and not args.plain and ops.MATH == "bf16x3":
+        if legs and ops.MATH == "bf16x3":
             del trainers, trainer                                               # the child needs the HBM
             torch.cuda.empty_cache()
             line["f32_mode"] = f32_mode_rate(args)
-        if world == 1 and not args.plain and not args.no_cpu_baseline:
+        if legs and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.length, args.cpu_pairs or args.batch, args.cpu_steps, args.c_in, args.cpu_threads)
             line["gpu_over_cpu"] = value / args.sources / line["cpu_baseline"]["value"]
         print(json.dumps(line), flush=True)

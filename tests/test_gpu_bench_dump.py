@@ -1,5 +1,6 @@
-"""bench.py on one GPU at a small shape: --steps sets the number of timed steps, ms_per_step is one of them, and
---dump-outputs writes the last timed step's report as float32 / float64 .npy files within 64 MB."""
+"""bench.py on one GPU at a small shape: --steps sets the number of timed steps, ms_per_step is one of them, a run without
+--full carries no extra leg, and --dump-outputs writes the last timed step's report as float32 / float64 .npy files within
+64 MB."""
 import json
 import os
 import subprocess
@@ -23,6 +24,8 @@ def test_bench_steps_and_dump_outputs(tmp_path):
     assert len(lines) == 1, out.stdout[-2000:]
     d = json.loads(lines[0])
     assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    # without --full the run stops at the headline: no roofline step, no S1 / north-star / f32 / CPU legs
+    assert not {"roofline", "s1_classifier_step", "north_star_extras", "f32_mode", "cpu_baseline", "gpu_over_cpu"} & set(d)
     assert abs(d["value"] - 16 * 1e3 / d["ms_per_step"]) <= 1e-6 * d["value"]
     files = sorted(os.listdir(out_dir))
     assert {"ce_t.npy", "nf_t.npy", "cdan.npy", "w_t.npy", "feat_t.npy", "logit_t.npy"} <= set(files)

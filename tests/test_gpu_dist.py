@@ -271,14 +271,14 @@ def test_global_batch_mode_at_config4_per_rank_geometry():
 def test_bench_data_parallel_path_rehearsal():
     """`bench.py --gpus 2` exactly as the driver launches it (torch.distributed.run, one process per rank), rehearsed on
     this one-GPU box: both ranks on cuda:0, gloo instead of RCCL.  Guards the N>1 bench path — two captured graphs with
-    the eager all-reduce between them, barrier + MAX timing, the per-kernel timing step on every rank — and its JSON."""
+    the eager all-reduce between them, barrier + MAX timing, --full's per-kernel timing step on every rank — and its JSON."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, FST_BENCH_ONE_DEVICE="1", FST_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29671", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "16",
-           "--length", "128"]
+           "--length", "128", "--full"]
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -306,6 +306,7 @@ def test_plain_bench_command_starts_its_own_ranks():
     assert len(lines) == 1, out.stdout[-2000:]
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["config"]["global_batch"] == 32 and d["mode"] == "graph" and d["value"] > 0
+    assert "roofline" not in d                                            # without --full: no per-kernel timing step
     # a rank that fails must fail the command: --gpus 2 under a launcher environment that says otherwise
     bad = subprocess.run(cmd, env=dict(env, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0"), cwd=root, capture_output=True, text=True,
                          timeout=300)
