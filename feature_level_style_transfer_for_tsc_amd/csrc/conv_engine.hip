@@ -20,7 +20,7 @@
 // 32-row block only live taps are multiplied; the plan table is a separate __restrict__ kernel argument so it is
 // read with scalar loads; one branch-free epilogue (bias / residual / accumulate / split / atomics) with 16-byte
 // stores through a wave-private LDS transpose.
-#include "fst_common.h"
+#include "fst_device.h"
 #include <type_traits>
 
 // ------------------------------------------------------------------------------------------------
@@ -346,30 +346,9 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemmParams p, const 
 }
 
 #ifdef FST_STAMPS
-// Diagnostic build only (tools/build_stamps.sh): per-phase cycle sums of the pipelined kernel, lane 0 of every wave.
+// per-phase cycle sums of the pipelined kernels, lane 0 of every wave (fst_device.h)
 __device__ unsigned long long fst_stamps[8];
-__device__ __forceinline__ unsigned long long fst_now() {
-  unsigned long long t;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  return t;
-}
-extern "C" int fst_debug_stamps(unsigned long long* out_host, int reset) {
-  if (out_host) hipMemcpyFromSymbol(out_host, HIP_SYMBOL(fst_stamps), sizeof(unsigned long long) * 8);
-  if (reset) { unsigned long long z[8] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(fst_stamps), z, sizeof(z)); }
-  return 0;
-}
-// phase sums live in registers and are flushed ONCE per wave (per-stage atomics would serialise on 8 words and
-// sit in vmcnt, i.e. measure themselves)
-#define FST_T(var) const unsigned long long var = fst_now()
-#define FST_ACC(slot, a, b) fst_sum[slot] += (b) - (a)
-#define FST_SUMS unsigned long long fst_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}
-#define FST_FLUSH \
-  if (lane == 0) for (int i_ = 0; i_ < 8; ++i_) atomicAdd(&fst_stamps[i_], fst_sum[i_])
-#else
-#define FST_T(var)
-#define FST_ACC(slot, a, b)
-#define FST_SUMS
-#define FST_FLUSH
+extern "C" int fst_debug_stamps(unsigned long long* out_host, int reset) { return fst_read_stamps(fst_stamps, out_host, reset); }
 #endif
 
 // ------------------------------------------------------------------------------------------------
@@ -486,7 +465,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_pipe_kernel(ConvGemmParams p
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[mb][nb][r] = 0.f;
 
-  FST_SUMS;
+  FST_SUMS(8);
   FST_T(ts0);
   int q = next_live(q_begin);
   if (q < q_end) {
@@ -540,7 +519,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_pipe_kernel(ConvGemmParams p
   FST_T(th);
   FST_ACC(6, tg, th);                                     // epilogue
   FST_ACC(7, ts0, th);                                    // whole wave
-  FST_FLUSH;
+  FST_FLUSH(fst_stamps);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -561,26 +540,6 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_pipe_kernel(ConvGemmParams p
 //      conflict-free ds_read_b32 at column n + (shift mod 4) — the tap's sub-shift costs nothing — and splits it
 //      into hi / lo in registers.
 // ------------------------------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-#define FST_GLOBAL_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define FST_LDS_VOID(p) ((__attribute__((address_space(3))) void*)(p))
-
-// two floats -> (hi pair, lo pair), each a dword of two round-to-nearest bf16 (first element in the low half)
-__device__ __forceinline__ void split_bf16_pair(float a, float b, unsigned& hi, unsigned& lo) {
-  const f32x2 v = {a, b};
-  hi = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-  const f32x2 r = {a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xffff0000u)};
-  lo = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2));
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 template <int MB, int NB>
 __global__ __launch_bounds__(256, 2) void conv_gemm_bf3_kernel(ConvGemmParams p, const int32_t* __restrict__ plan) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -628,7 +587,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_bf3_kernel(ConvGemmParams p,
       const int idx = wave_s + 4 * i;
       if (idx >= NI) break;                            // wave-uniform
       if (idx < NA) {
-        __builtin_amdgcn_global_load_lds(FST_GLOBAL_PTR(asrc + idx * 1024 + lane * 16), FST_LDS_VOID(sl + idx * 1024), 16, 0, 0);
+        lds_dma16(asrc + idx * 1024 + lane * 16, sl + idx * 1024);
       } else {
         const int bi = idx - NA;
         const int gq = bi >= NBLK ? 1 : 0, m = bi - gq * NBLK;
@@ -637,7 +596,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_bf3_kernel(ConvGemmParams p,
         bool ok = row < c_count && t >= 0 && t < L;
         if (m == NBLK - 1) ok = ok && spill && (lane & 7) == 0;
         const char* src = ok ? reinterpret_cast<const char*>(xb + ((long long)row * L + t)) : zero16;
-        __builtin_amdgcn_global_load_lds(FST_GLOBAL_PTR(src), FST_LDS_VOID(sl + A_BYTES + gq * GS + m * 1024), 16, 0, 0);
+        lds_dma16(src, sl + A_BYTES + gq * GS + m * 1024);
       }
     }
   };
@@ -658,7 +617,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_bf3_kernel(ConvGemmParams p,
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[mb][nb][r] = 0.f;
 
-  FST_SUMS;
+  FST_SUMS(8);
   FST_T(ts0);
   int q0 = next_live(q_begin);
   int q1 = q0 < q_end ? next_live(q0 + 1) : q_end;
@@ -729,7 +688,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_bf3_kernel(ConvGemmParams p,
   FST_T(th);
   FST_ACC(6, tg, th);                                  // epilogue
   FST_ACC(7, ts0, th);                                 // whole wave
-  FST_FLUSH;
+  FST_FLUSH(fst_stamps);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1190,14 +1149,13 @@ extern "C" int fst_conv_gemm(const float* x0, int64_t x0_bs, const float* x1, in
   }
   const bool pipe = plan_is_pipeable(pv) && pick_conv_gemm_pipe(pv.MB, nb_cfg) != nullptr;
   // 16-byte B-tile loads need every address of a stage row to be 16-B aligned
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   const bool shifts4 = pv.pad_left % 4 == 0 && (pv.ntaps == 1 || pv.dil % 4 == 0);   // every tap shift ≡ 0 (mod 4)
-  const bool vec = pipe && L % 4 == 0 && shifts4 && x0_bs % 4 == 0 && al16(x0) &&
-                   (x1 == nullptr || (x1_bs % 4 == 0 && al16(x1)));
+  const bool vec = pipe && L % 4 == 0 && shifts4 && x0_bs % 4 == 0 && fst_aligned16(x0) &&
+                   (x1 == nullptr || (x1_bs % 4 == 0 && fst_aligned16(x1)));
   const bool bf3 = (flags & FST_GEMM_BF16X3) != 0;
   const bool win3 = bf3 && !pipe;                        // windowed plan of <= 16-channel chunks: the bf16 window kernel
   if (bf3 && pipe) {
-    FST_REQUIRE(L % 4 == 0 && x0_bs % 4 == 0 && al16(x0) && (x1 == nullptr || (x1_bs % 4 == 0 && al16(x1))),
+    FST_REQUIRE(L % 4 == 0 && x0_bs % 4 == 0 && fst_aligned16(x0) && (x1 == nullptr || (x1_bs % 4 == 0 && fst_aligned16(x1))),
                 "fst_conv_gemm: FST_GEMM_BF16X3 needs L %% 4 == 0 and 16-byte aligned activations (L=%d)", L);
   }
   if (win3)
@@ -1246,10 +1204,9 @@ extern "C" int fst_conv_gemm(const float* x0, int64_t x0_bs, const float* x1, in
   FST_REQUIRE(max_w > 0, "fst_conv_gemm: plan has no live taps");
   p.ldw = (max_w + 3) & ~3;                               // 16-B aligned LDS rows (float4 staging)
   size_t lds_bytes = (size_t)pv.chunk_cap * p.ldw * sizeof(float);
-  auto al16o = [](const void* q) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  p.stage_vec = L % 4 == 0 && x0_bs % 4 == 0 && al16o(x0) && (x1 == nullptr || (x1_bs % 4 == 0 && al16o(x1)));
+  p.stage_vec = L % 4 == 0 && x0_bs % 4 == 0 && fst_aligned16(x0) && (x1 == nullptr || (x1_bs % 4 == 0 && fst_aligned16(x1)));
   p.epi_vec = !(flags & FST_EPI_ATOMIC) && L % 4 == 0 && y_bs % 4 == 0 && y2_bs % 4 == 0 && res_bs % 4 == 0 &&
-              al16o(y) && al16o(y2) && al16o(res);
+              fst_aligned16(y) && fst_aligned16(y2) && fst_aligned16(res);
   const size_t epi_bytes = 4 * 32 * 36 * sizeof(float);     // one transpose tile per wave
   if (pipe) {
     p.mg_per_wg = 1;
@@ -1810,7 +1767,6 @@ extern "C" int fst_conv_wgrad(const float* x0, int64_t x0_bs, const float* x1, i
   const size_t lds_bytes = ((size_t)p.n_regions * p.region_floats + (TW + 2 + 3) / 4 * 4) * sizeof(float) + dy_bytes;
   FST_REQUIRE(lds_bytes <= 160 * 1024, "fst_conv_wgrad: LDS %zu B exceeds 160 KiB", lds_bytes);
   // 16-byte loads for narrow windows when every tile row address is 16-B aligned
-  auto al16 = [](const void* q) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   const bool shifts4 = pv.pad_left % 4 == 0 && (pv.ntaps == 1 || pv.dil % 4 == 0);
   // windowed plans: the window of every (M-group, chunk) must also START on a multiple of 4 samples and be a
   // multiple of 4 wide
@@ -1822,7 +1778,7 @@ extern "C" int fst_conv_wgrad(const float* x0, int64_t x0_bs, const float* x1, i
     }
   // (single-tap windows take any shift: the kernel starts the row's 16-byte loads `shift mod 4` samples early)
   const bool vec = L % 4 == 0 && (wide ? starts4 : true) && x0_bs % 4 == 0 && x1_bs % 4 == 0 && dy_bs % 4 == 0 &&
-                   dy2_bs % 4 == 0 && al16(x0) && al16(x1) && al16(dy) && al16(dy2);
+                   dy2_bs % 4 == 0 && fst_aligned16(x0) && fst_aligned16(x1) && fst_aligned16(dy) && fst_aligned16(dy2);
   void (*fn)(WgradParams, const int32_t*);
   // VEC: 0 dword staging, 1 16-byte staging, 2 16-byte staging of single-tap windows whose shift is not a multiple of 4
   const int vmode = !vec ? 0 : (wide || shifts4 ? 1 : 2);

@@ -16,7 +16,7 @@
 // a workgroup handles one panel (blockIdx.z / .y), the forward leaves per-(row, panel) partial (max, Σexp, diagonal) in a
 // workspace that cpc_combine_kernel merges (online-softmax combine: lse = M + log Σ_p s_p·e^{m_p − M}), the backward —
 // lse known — is independent per panel: dpred rows of the panel written, denc accumulated over panels with fp32 atomics.
-#include "fst_common.h"
+#include "fst_device.h"
 #include <string.h>
 
 #define CPC_ROWS 16
@@ -177,18 +177,8 @@ __global__ __launch_bounds__(256) void cpc_fwd_kernel(CpcParams p) {
 //                          keeps the B fragments of column tile w in registers for all eight row blocks (4 k-steps x 3 MFMAs
 //                          per tile), the log-softmax runs on the accumulators as in cpc_fwd_kernel.
 // ------------------------------------------------------------------------------------------------
-typedef __bf16 cg_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 cg_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float cg_f32x2 __attribute__((ext_vector_type(2)));
 #define CG_ROWB 144                                  // bytes per image row: 64 bf16 + 16 B so that rows start 36 banks apart
 #define CG_IMG (256 * CG_ROWB)
-
-__device__ __forceinline__ void cg_split_pair(float a, float b, unsigned& hi, unsigned& lo) {
-  const cg_f32x2 v = {a, b};
-  hi = __builtin_bit_cast(unsigned, __builtin_convertvector(v, cg_bf16x2));
-  const cg_f32x2 r = {a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xffff0000u)};
-  lo = __builtin_bit_cast(unsigned, __builtin_convertvector(r, cg_bf16x2));
-}
 
 // enc_t[i][r] = enc[i·s_i + (b, c) strides], r = b·C + c: 64 rows x 32 steps per workgroup through an LDS tile
 __global__ __launch_bounds__(256) void cpc_enc_gather_kernel(CpcParams p, float* __restrict__ enc_t) {
@@ -231,8 +221,8 @@ __global__ __launch_bounds__(512) void cpc_gram_bf3_kernel(CpcParams p, const fl
         v[k] = (row < rows && c < C) ? src[(long long)row * C + c] : 0.f;
       }
       unsigned h0, h1, l0, l1;
-      cg_split_pair(v[0], v[1], h0, l0);
-      cg_split_pair(v[2], v[3], h1, l1);
+      split_bf16_pair(v[0], v[1], h0, l0);
+      split_bf16_pair(v[2], v[3], h1, l1);
       *reinterpret_cast<uint2*>(hi_img + row * CG_ROWB + g4 * 8) = make_uint2(h0, h1);
       *reinterpret_cast<uint2*>(lo_img + row * CG_ROWB + g4 * 8) = make_uint2(l0, l1);
     }
@@ -244,11 +234,11 @@ __global__ __launch_bounds__(512) void cpc_gram_bf3_kernel(CpcParams p, const fl
   // block's 32 encodings b — so the softmax of sample b runs over a lane's own 16 registers, one exchange between the lane
   // halves and a combine over the eight waves through LDS (with samples on the rows a row's maximum is a 5-step butterfly per
   // register: 240 dependent cross-lane exchanges per row block, which is what bounded the f32 kernel).
-  cg_bf16x8 ah[4], al[4];
+  bf16x8 ah[4], al[4];
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks) {
-    ah[ks] = *reinterpret_cast<const cg_bf16x8*>(ph + (wave * 32 + l31) * CG_ROWB + ks * 32 + half * 16);
-    al[ks] = *reinterpret_cast<const cg_bf16x8*>(pl + (wave * 32 + l31) * CG_ROWB + ks * 32 + half * 16);
+    ah[ks] = *reinterpret_cast<const bf16x8*>(ph + (wave * 32 + l31) * CG_ROWB + ks * 32 + half * 16);
+    al[ks] = *reinterpret_cast<const bf16x8*>(pl + (wave * 32 + l31) * CG_ROWB + ks * 32 + half * 16);
   }
   float local = 0.f;
   for (int r0 = 0; r0 < B; r0 += 32) {
@@ -257,8 +247,8 @@ __global__ __launch_bounds__(512) void cpc_gram_bf3_kernel(CpcParams p, const fl
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      const cg_bf16x8 bh = *reinterpret_cast<const cg_bf16x8*>(eh + (r0 + l31) * CG_ROWB + ks * 32 + half * 16);
-      const cg_bf16x8 bl = *reinterpret_cast<const cg_bf16x8*>(el + (r0 + l31) * CG_ROWB + ks * 32 + half * 16);
+      const bf16x8 bh = *reinterpret_cast<const bf16x8*>(eh + (r0 + l31) * CG_ROWB + ks * 32 + half * 16);
+      const bf16x8 bl = *reinterpret_cast<const bf16x8*>(el + (r0 + l31) * CG_ROWB + ks * 32 + half * 16);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[ks], bh, acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[ks], bl, acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[ks], bh, acc, 0, 0, 0);

@@ -48,6 +48,9 @@ static inline __host__ __device__ PlanView plan_view(const int32_t* p) {
   return v;
 }
 
+// 16-byte aligned (a null pointer is: optional tensors pass)
+static inline bool fst_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 static inline int plan_expected_len(const int32_t* p) {
   return FST_PLAN_HDR + 4 * p[0] + 4 * p[0] * p[1] + 4 * p[8];
 }

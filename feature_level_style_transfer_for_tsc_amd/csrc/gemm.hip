@@ -18,12 +18,7 @@
 // order (+ bias, activation) — deterministic, no atomics, no zero fill.
 #include <stdlib.h>
 
-#include "fst_common.h"
-
-typedef __bf16 gm_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 gm_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float gm_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned gm_u32x4 __attribute__((ext_vector_type(4)));
+#include "fst_device.h"
 
 #define GM_BK 32
 #define GM_PITCH 80
@@ -43,13 +38,6 @@ struct GemmParams {
   float* slab;             // [ksplit][M][N] when ksplit > 1
   int tiles_n;
 };
-
-__device__ __forceinline__ void gm_split_pair(float a, float b, unsigned& hi, unsigned& lo) {
-  const gm_f32x2 v = {a, b};
-  hi = __builtin_bit_cast(unsigned, __builtin_convertvector(v, gm_bf16x2));
-  const gm_f32x2 r = {a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xffff0000u)};
-  lo = __builtin_bit_cast(unsigned, __builtin_convertvector(r, gm_bf16x2));
-}
 
 __device__ __forceinline__ float gm_act(float v, int act, float slope) {
   if (act == FST_ACT_RELU) return v > 0.f ? v : 0.f;
@@ -95,8 +83,8 @@ __device__ __forceinline__ void gm_stage(const float (&v)[ROWS / 8], char* hi_im
 #pragma unroll
     for (int j = 0; j < ROWS / 32; ++j) {
       unsigned h0, l0, h1, l1;
-      gm_split_pair(v[4 * j], v[4 * j + 1], h0, l0);
-      gm_split_pair(v[4 * j + 2], v[4 * j + 3], h1, l1);
+      split_bf16_pair(v[4 * j], v[4 * j + 1], h0, l0);
+      split_bf16_pair(v[4 * j + 2], v[4 * j + 3], h1, l1);
       const int off = (r0 + 32 * j) * GM_PITCH + kb;
       *reinterpret_cast<uint2*>(hi_img + off) = make_uint2(h0, h1);
       *reinterpret_cast<uint2*>(lo_img + off) = make_uint2(l0, l1);
@@ -105,15 +93,15 @@ __device__ __forceinline__ void gm_stage(const float (&v)[ROWS / 8], char* hi_im
     const int off = (tid % ROWS) * GM_PITCH + 2 * KR * (tid / ROWS);
 #pragma unroll
     for (int c = 0; c < KR / 8; ++c) {
-      gm_u32x4 h, l;
+      u32x4 h, l;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         unsigned hh, ll;
-        gm_split_pair(v[8 * c + 2 * e], v[8 * c + 2 * e + 1], hh, ll);
+        split_bf16_pair(v[8 * c + 2 * e], v[8 * c + 2 * e + 1], hh, ll);
         h[e] = hh; l[e] = ll;
       }
-      *reinterpret_cast<gm_u32x4*>(hi_img + off + 16 * c) = h;
-      *reinterpret_cast<gm_u32x4*>(lo_img + off + 16 * c) = l;
+      *reinterpret_cast<u32x4*>(hi_img + off + 16 * c) = h;
+      *reinterpret_cast<u32x4*>(lo_img + off + 16 * c) = l;
     }
   }
 }
@@ -159,16 +147,16 @@ __global__ __launch_bounds__(256, TM * TN == 4 ? 2 : 3) void gemm_bf3_kernel(Gem
     }
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      gm_bf16x8 ah[TM], al[TM], bh[TN], bl[TN];
+      bf16x8 ah[TM], al[TM], bh[TN], bl[TN];
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
-        ah[i] = *reinterpret_cast<const gm_bf16x8*>(a_hi + a_off + i * 32 * GM_PITCH + 32 * ks);
-        al[i] = *reinterpret_cast<const gm_bf16x8*>(a_lo + a_off + i * 32 * GM_PITCH + 32 * ks);
+        ah[i] = *reinterpret_cast<const bf16x8*>(a_hi + a_off + i * 32 * GM_PITCH + 32 * ks);
+        al[i] = *reinterpret_cast<const bf16x8*>(a_lo + a_off + i * 32 * GM_PITCH + 32 * ks);
       }
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
-        bh[j] = *reinterpret_cast<const gm_bf16x8*>(b_hi + b_off + j * 32 * GM_PITCH + 32 * ks);
-        bl[j] = *reinterpret_cast<const gm_bf16x8*>(b_lo + b_off + j * 32 * GM_PITCH + 32 * ks);
+        bh[j] = *reinterpret_cast<const bf16x8*>(b_hi + b_off + j * 32 * GM_PITCH + 32 * ks);
+        bl[j] = *reinterpret_cast<const bf16x8*>(b_lo + b_off + j * 32 * GM_PITCH + 32 * ks);
       }
 #pragma unroll
       for (int i = 0; i < TM; ++i)
@@ -256,7 +244,7 @@ extern "C" int fst_gemm(const float* A, int64_t lda, int ta, const float* B, int
   gm_geometry(M, N, K, &big, &p.ksplit, &p.k_per_split);
   FST_REQUIRE(p.ksplit == 1 || (workspace && workspace_floats >= (int64_t)p.ksplit * M * N), "fst_gemm: workspace of %lld floats is too small "
               "(fst_gemm_workspace_floats(%d, %d, %d) = %lld)", (long long)workspace_floats, M, N, K, (long long)p.ksplit * M * N);
-  auto vec = [](const float* q, int64_t ld, int K_) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0 && ld % 4 == 0 && K_ % 4 == 0; };
+  auto vec = [](const float* q, int64_t ld, int K_) { return fst_aligned16(q) && ld % 4 == 0 && K_ % 4 == 0; };
   p.A = A; p.B = B; p.C = C; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.M = M; p.N = N; p.K = K;
   p.ta = ta ? 1 : 0; p.tb = tb ? 1 : 0;
   p.vec_a = !ta && vec(A, lda, K); p.vec_b = !tb && vec(B, ldb, K);
@@ -290,8 +278,7 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const float* dy, const flo
 
 extern "C" int fst_act_bwd(const float* dy, const float* y, float* out, int64_t n, float slope, void* stream) {
   FST_REQUIRE(dy && y && out && n > 0, "fst_act_bwd: bad arguments");
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  FST_REQUIRE(al16(dy) && al16(y) && al16(out), "fst_act_bwd: tensors must be 16-byte aligned");
+  FST_REQUIRE(fst_aligned16(dy) && fst_aligned16(y) && fst_aligned16(out), "fst_act_bwd: tensors must be 16-byte aligned");
   hipLaunchKernelGGL(act_bwd_kernel, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, dy, y, out, (long long)n, slope);
   FST_LAUNCH_CHECK();
   return 0;

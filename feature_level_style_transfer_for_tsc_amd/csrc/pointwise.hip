@@ -79,7 +79,7 @@ struct RowVec {
 static inline bool vec_ok(int L, std::initializer_list<const void*> ptrs) {
   if (L % 4 != 0) return false;
   for (const void* q : ptrs)
-    if (q && (reinterpret_cast<uintptr_t>(q) & 15)) return false;
+    if (!fst_aligned16(q)) return false;
   return true;
 }
 static inline RowVec row_vec(int L) {

@@ -30,8 +30,7 @@ __global__ __launch_bounds__(256) void batch_sum_kernel(const float* x0, const f
 extern "C" int fst_batch_sum(const float* x0, const float* x1, float* part, int B, int64_t N, int S, void* stream) {
   FST_REQUIRE(x0 && part && B > 0 && N > 0 && N % 4 == 0 && S > 0 && S <= B, "fst_batch_sum: bad arguments (B=%d N=%lld S=%d; N %% 4 == 0, "
               "1 <= S <= B)", B, (long long)N, S);
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  FST_REQUIRE(al16(x0) && al16(x1) && al16(part), "fst_batch_sum: tensors must be 16-byte aligned");
+  FST_REQUIRE(fst_aligned16(x0) && fst_aligned16(x1) && fst_aligned16(part), "fst_batch_sum: tensors must be 16-byte aligned");
   hipLaunchKernelGGL(batch_sum_kernel, dim3((unsigned)((N / 4 + 255) / 256), (unsigned)S, x1 ? 2 : 1), dim3(256), 0, (hipStream_t)stream,
                      x0, x1, part, B, (long long)N, S);
   FST_LAUNCH_CHECK();
@@ -112,8 +111,7 @@ __global__ __launch_bounds__(256) void bcast_add_kernel(float* out, const float*
 
 extern "C" int fst_bcast_add(float* out, const float* x, const float* v, int B, int64_t N, void* stream) {
   FST_REQUIRE(out && x && v && B > 0 && N > 0 && N % 4 == 0, "fst_bcast_add: bad arguments (B=%d N=%lld, N %% 4 == 0)", B, (long long)N);
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  FST_REQUIRE(al16(out) && al16(x) && al16(v), "fst_bcast_add: tensors must be 16-byte aligned");
+  FST_REQUIRE(fst_aligned16(out) && fst_aligned16(x) && fst_aligned16(v), "fst_bcast_add: tensors must be 16-byte aligned");
   const long long total4 = (long long)B * N / 4;
   long long blocks = (total4 + 255) / 256;
   if (blocks > 8192) blocks = 8192;
@@ -217,8 +215,7 @@ extern "C" int fst_noise_transfer_bwd_apply(const float* g, const float* dd, con
                                             float r_s, int B, float* dz_t, float* dz_s, int64_t N, void* stream) {
   FST_REQUIRE(g && dd && (dz_t || dz_s) && B > 0 && N > 0 && N % 4 == 0, "fst_noise_transfer_bwd_apply: bad arguments (B=%d N=%lld)", B,
               (long long)N);
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  FST_REQUIRE(al16(g) && al16(dd) && al16(dz_t) && al16(dz_s), "fst_noise_transfer_bwd_apply: tensors must be 16-byte aligned");
+  FST_REQUIRE(fst_aligned16(g) && fst_aligned16(dd) && fst_aligned16(dz_t) && fst_aligned16(dz_s), "fst_noise_transfer_bwd_apply: tensors must be 16-byte aligned");
   const long long total4 = (long long)B * N / 4;
   long long blocks = (total4 + 255) / 256;
   if (blocks > 8192) blocks = 8192;
@@ -242,8 +239,7 @@ __global__ __launch_bounds__(256) void relu_bwd_kernel(const float* dy, const fl
 
 extern "C" int fst_relu_bwd(const float* dy, const float* y, float* out, int64_t n, void* stream) {
   FST_REQUIRE(dy && y && out && n > 0, "fst_relu_bwd: bad arguments");
-  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  FST_REQUIRE(al16(dy) && al16(y) && al16(out), "fst_relu_bwd: tensors must be 16-byte aligned");
+  FST_REQUIRE(fst_aligned16(dy) && fst_aligned16(y) && fst_aligned16(out), "fst_relu_bwd: tensors must be 16-byte aligned");
   long long blocks = (n / 4 + 255) / 256;
   if (blocks > 8192) blocks = 8192;
   if (blocks < 1) blocks = 1;

@@ -25,15 +25,8 @@
 // Biases ride in the GEMMs: GEMM 1 has a constant-one input row (the first padding channel of the conditioning
 // chunk, fed from a 16-byte block of ones), GEMM 2 sees acts[n] = 1 — so n < 128 is required (one spare K row).
 // Two workgroups share a CU (79 KB of LDS, ≤ 256 registers): one's t,s store burst is the other's MFMA time.
-#include "fst_common.h"
+#include "fst_device.h"
 #include <type_traits>
-
-typedef __bf16 wn_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 wn_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float wn_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned wn_u32x4 __attribute__((ext_vector_type(4)));
-#define WN_GLOBAL_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define WN_LDS_VOID(p) ((__attribute__((address_space(3))) void*)(p))
 
 #define WS_MAXL 10                                  // layers of a WN stack the one-launch kernels take (tables in the kernel arguments)
 #define WN_TN 128                                  // time samples per workgroup
@@ -42,18 +35,6 @@ typedef unsigned wn_u32x4 __attribute__((ext_vector_type(4)));
 #define WN_A_BYTES (8 * 2048)                      // 8 row blocks × (1 KiB hi + 1 KiB lo fragments)
 #define WN_TILE_BYTES (32 * 36 * 4)                // one wave's [32][36] fp32 transpose tile
 #define WN_FWD_LDS(NW) (3 * (WN_A_BYTES + 2 * (((NW) + 1) * 1024 + 128)))
-
-__device__ __forceinline__ void wn_split_pair(float a, float b, unsigned& hi, unsigned& lo) {
-  const wn_f32x2 v = {a, b};
-  hi = __builtin_bit_cast(unsigned, __builtin_convertvector(v, wn_bf16x2));
-  const wn_f32x2 r = {a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xffff0000u)};
-  lo = __builtin_bit_cast(unsigned, __builtin_convertvector(r, wn_bf16x2));
-}
-
-template <int N>
-__device__ __forceinline__ void wn_wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // sigmoid and tanh from v_exp_f32 / v_rcp_f32 (≈1 ulp each): absolute error ≈ 2e-7, saturating correctly at ±inf
 __device__ __forceinline__ float wn_sigmoid(float x) {
@@ -141,7 +122,7 @@ __global__ __launch_bounds__(64) void wn_pack_kernel(WnPackParams p) {
   }
   unsigned hi[4], lo[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) wn_split_pair(v[2 * j], v[2 * j + 1], hi[j], lo[j]);
+  for (int j = 0; j < 4; ++j) split_bf16_pair(v[2 * j], v[2 * j + 1], hi[j], lo[j]);
   uint4* dst = p.img + ((long long)st * 8 + blk) * 128 + lane;
   dst[0] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
   dst[64] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
@@ -167,7 +148,7 @@ extern "C" int fst_wn_pack(const float* in_w, const float* cond_w, const float* 
   FST_REQUIRE(n > 0 && n < 128 && h > 0, "fst_wn_pack: needs 0 < n < 128 (one spare K row carries the bias), h > 0; n=%d h=%d", n, h);
   FST_REQUIRE(image_bytes == fst_wn_image_bytes(n, h), "fst_wn_pack: image is %lld bytes, expected %lld",
               (long long)image_bytes, (long long)fst_wn_image_bytes(n, h));
-  FST_REQUIRE((reinterpret_cast<uintptr_t>(image) & 15) == 0, "fst_wn_pack: image must be 16-byte aligned");
+  FST_REQUIRE(fst_aligned16(image), "fst_wn_pack: image must be 16-byte aligned");
   WnPackParams p = {in_w, cond_w, in_b, cond_b, rs_w, rs_b, n, h, last ? 1 : 0, wn_ch(n), wn_ch2(h), static_cast<uint4*>(image)};
   const int stages = 3 * p.CH + p.CH2 + 8;
   hipLaunchKernelGGL(wn_pack_kernel, dim3((unsigned)(stages * 8)), dim3(64), 0, (hipStream_t)stream, p);
@@ -176,28 +157,9 @@ extern "C" int fst_wn_pack(const float* in_w, const float* cond_w, const float* 
 }
 
 #ifdef FST_STAMPS
-// Diagnostic build only (tools/build_stamps.sh): per-phase s_memtime sums of the fused forward kernel, lane 0 of every wave.
+// per-phase cycle sums of the fused forward kernel and the stack backward, lane 0 of every wave (fst_device.h)
 __device__ unsigned long long wn_stamps[12];
-__device__ __forceinline__ unsigned long long wn_now() {
-  unsigned long long t;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  return t;
-}
-extern "C" int fst_debug_wn_stamps(unsigned long long* out_host, int reset) {
-  if (out_host) hipMemcpyFromSymbol(out_host, HIP_SYMBOL(wn_stamps), sizeof(unsigned long long) * 12);
-  if (reset) { unsigned long long z[12] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(wn_stamps), z, sizeof(z)); }
-  return 0;
-}
-#define WN_T(var) const unsigned long long var = wn_now()
-#define WN_ACC(slot, a, b) wn_sum[slot] += (b) - (a)
-#define WN_SUMS unsigned long long wn_sum[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
-#define WN_FLUSH \
-  if (lane == 0) for (int i_ = 0; i_ < 12; ++i_) atomicAdd(&wn_stamps[i_], wn_sum[i_])
-#else
-#define WN_T(var)
-#define WN_ACC(slot, a, b)
-#define WN_SUMS
-#define WN_FLUSH
+extern "C" int fst_debug_wn_stamps(unsigned long long* out_host, int reset) { return fst_read_stamps(wn_stamps, out_host, reset); }
 #endif
 
 // ------------------------------------------------------------------------------------------------
@@ -456,13 +418,13 @@ __device__ __forceinline__ void wn_fwd_tile(WnFwdArgs& p, const int b, const int
     if (ss.gemm2) {
       const int idx = ss.a0 + wave_s + NW * i;
       if (i < 16 / NW && idx < NA)
-        __builtin_amdgcn_global_load_lds(WN_GLOBAL_PTR(ss.asrc + idx * 1024 + lane * 16), WN_LDS_VOID(ss.sl + idx * 1024), 16, 0, 0);
+        lds_dma16(ss.asrc + idx * 1024 + lane * 16, ss.sl + idx * 1024);
       return;
     }
     const int idx = wave_s + NW * i;
     if (idx >= NI1) return;                            // wave-uniform
     if (idx < NA) {
-      __builtin_amdgcn_global_load_lds(WN_GLOBAL_PTR(ss.asrc + idx * 1024 + lane * 16), WN_LDS_VOID(ss.sl + idx * 1024), 16, 0, 0);
+      lds_dma16(ss.asrc + idx * 1024 + lane * 16, ss.sl + idx * 1024);
     } else {
       const int bi = idx - NA;
       const int gq = bi >= F_NBLK ? 1 : 0, m = bi - gq * F_NBLK;
@@ -471,7 +433,7 @@ __device__ __forceinline__ void wn_fwd_tile(WnFwdArgs& p, const int b, const int
       bool ok = row < ss.c_count && t >= 0 && t < L;
       if (m == F_NBLK - 1) ok = ok && ss.spill && (lane & 7) == 0;
       const char* src = ok ? reinterpret_cast<const char*>(ss.xb + ((long long)row * L + t)) : (row == ss.ones_row ? ones16 : zero16);
-      __builtin_amdgcn_global_load_lds(WN_GLOBAL_PTR(src), WN_LDS_VOID(ss.sl + WN_A_BYTES + gq * F_GS + m * 1024), 16, 0, 0);
+      lds_dma16(src, ss.sl + WN_A_BYTES + gq * F_GS + m * 1024);
     }
   };
   constexpr int NPW1 = (NI1 + NW - 1) / NW;            // pieces per wave per GEMM-1 stage (waves >= NI1 % NW issue one fewer)
@@ -483,10 +445,10 @@ __device__ __forceinline__ void wn_fwd_tile(WnFwdArgs& p, const int b, const int
   };
   // wait until this wave's pieces of the stage about to be read have landed; `next` = the one stage issued after it
   auto wait_for = [&](int next, int S) {
-    if (next >= S) wn_wait_vmcnt<0>();
-    else if (next < S1) { if (wave_s < (NI1 % NW)) wn_wait_vmcnt<(NI1 + NW - 1) / NW>(); else wn_wait_vmcnt<NI1 / NW>(); }
-    else if (p.last) wn_wait_vmcnt<8 / NW>();
-    else wn_wait_vmcnt<16 / NW>();
+    if (next >= S) wait_vmcnt<0>();
+    else if (next < S1) { if (wave_s < (NI1 % NW)) wait_vmcnt<(NI1 + NW - 1) / NW>(); else wait_vmcnt<NI1 / NW>(); }
+    else if (p.last) wait_vmcnt<8 / NW>();
+    else wait_vmcnt<16 / NW>();
   };
 
   f32x16 acc[8];
@@ -496,29 +458,29 @@ __device__ __forceinline__ void wn_fwd_tile(WnFwdArgs& p, const int b, const int
     for (int r = 0; r < 16; ++r) acc[mb][r] = 0.f;
 
   const int S = S1 + 8;
-  WN_SUMS;
-  WN_T(ts0);
+  FST_SUMS(12);
+  FST_T(ts0);
   issue(0, 0);
   issue(1, 1);
   int slot = 0;
-  WN_T(ts1);
-  WN_ACC(0, ts0, ts1);                                 // prologue
+  FST_T(ts1);
+  FST_ACC(0, ts0, ts1);                                // prologue
   // ---------------------------------------------------------------- GEMM 1: g = [W_in | W_cond | b] · [a taps ; u0 ; 1]
   for (int k = 0; k < S1; ++k) {
-    WN_T(ta);
+    FST_T(ta);
     wait_for(k + 1, S);
-    WN_T(tb);
-    WN_ACC(1, ta, tb);                                 // vmcnt wait
+    FST_T(tb);
+    FST_ACC(1, ta, tb);                                // vmcnt wait
     __builtin_amdgcn_s_barrier();                      // stage k is in LDS for everyone; the slot refilled next is drained
-    WN_T(tc);
-    WN_ACC(2, tb, tc);                                 // barrier
+    FST_T(tc);
+    FST_ACC(2, tb, tc);                                // barrier
     // stage k+2 goes into the slot every wave has just finished reading (k + 2 < S always holds here: 8 k-steps of
     // GEMM 2 follow).  Its pieces are issued one by one BETWEEN the MFMA triples below: an LDS-DMA issue costs the wave
     // 60-180 cycles, an MFMA holds the issue port for 8 of its 32 — interleaved, the address arithmetic and the issue
     // ride in the matrix pipe's shadow instead of in front of it.
     const StageSrc nxt = stage_src(k + 2, slot >= 1 ? slot - 1 : 2);
-    WN_T(td);
-    WN_ACC(3, tc, td);                                 // LDS-DMA issue
+    FST_T(td);
+    FST_ACC(3, tc, td);                                // LDS-DMA issue
     int shift = 0;
     if (k < 3 * CH) {
       int c_, tap_;
@@ -532,32 +494,32 @@ __device__ __forceinline__ void wn_fwd_tile(WnFwdArgs& p, const int b, const int
     // A fragments run ONE row block ahead of the MFMAs that consume them (two register pairs in rotation): read right in front
     // of their MFMAs — as the first form of this loop did, one `ds_read_b128; s_waitcnt lgkmcnt(0)` per fragment — every one of the
     // 16 reads of a stage exposed the LDS latency to a wave with nothing else to issue (115 such waits in the kernel's code)
-    wn_bf16x8 fah[2], fal[2];
+    bf16x8 fah[2], fal[2];
     auto a_frag = [&](int mb) {
-      fah[mb % 2] = *reinterpret_cast<const wn_bf16x8*>(base + mb * 2048 + lane * 16);
-      fal[mb % 2] = *reinterpret_cast<const wn_bf16x8*>(base + mb * 2048 + 1024 + lane * 16);
+      fah[mb % 2] = *reinterpret_cast<const bf16x8*>(base + mb * 2048 + lane * 16);
+      fal[mb % 2] = *reinterpret_cast<const bf16x8*>(base + mb * 2048 + 1024 + lane * 16);
     };
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = *reinterpret_cast<const float*>(bp + j * 128);
     a_frag(0);                                             // lands under the split of the B fragment below
-    wn_u32x4 bh4, bl4;
+    u32x4 bh4, bl4;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       unsigned hh, ll;
-      wn_split_pair(v[2 * j], v[2 * j + 1], hh, ll);
+      split_bf16_pair(v[2 * j], v[2 * j + 1], hh, ll);
       bh4[j] = hh; bl4[j] = ll;
     }
-    const wn_bf16x8 bh = __builtin_bit_cast(wn_bf16x8, bh4), bl = __builtin_bit_cast(wn_bf16x8, bl4);
+    const bf16x8 bh = __builtin_bit_cast(bf16x8, bh4), bl = __builtin_bit_cast(bf16x8, bl4);
 #ifdef FST_STAMPS
     asm volatile("" ::"v"(bh), "v"(bl));
 #endif
-    WN_T(te);
-    WN_ACC(4, td, te);                                 // B fragment: LDS reads + split
+    FST_T(te);
+    FST_ACC(4, td, te);                                // B fragment: LDS reads + split
 #pragma unroll
     for (int mb = 0; mb < 8; ++mb) {
       if (mb + 1 < 8) a_frag(mb + 1);
-      const wn_bf16x8 ah = fah[mb % 2], al = fal[mb % 2];
+      const bf16x8 ah = fah[mb % 2], al = fal[mb % 2];
       acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[mb], 0, 0, 0);
       acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[mb], 0, 0, 0);
       acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[mb], 0, 0, 0);
@@ -567,18 +529,18 @@ __device__ __forceinline__ void wn_fwd_tile(WnFwdArgs& p, const int b, const int
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-    WN_T(tf);
-    WN_ACC(5, te, tf);                                 // A fragments + MFMA issue
+    FST_T(tf);
+    FST_ACC(5, te, tf);                                // A fragments + MFMA issue
     slot = slot == 2 ? 0 : slot + 1;
   }
-  WN_T(tg0);
+  FST_T(tg0);
 
   // ---------------------------------------------------------------- gate (between stage S1-1 and the first k-step of GEMM 2)
   // Drain: the two k-steps in flight (S1, S1+1: A only, L2 hits issued one and two stages ago) land, so from here on
   // the t,s stores below are OLDER than every LDS-DMA a counted vmcnt will wait for — a counted wait retires
   // everything older than what it waits for, i.e. the stores get two k-steps of MFMA time to complete before the wait
   // in front of k-step S1+2 can see them.
-  wn_wait_vmcnt<0>();
+  wait_vmcnt<0>();
   __builtin_amdgcn_s_barrier();                        // every wave is past its last B read: the B areas are free
   const int tcol = t0 + wave_n0;
   // accumulator-layout global accesses as raw buffer instructions: one descriptor per matrix of this batch element, ONE per-lane
@@ -587,7 +549,7 @@ __device__ __forceinline__ void wn_fwd_tile(WnFwdArgs& p, const int b, const int
   const __amdgpu_buffer_rsrc_t ts_rs = ws_rsrc(p.ts + (long long)b * (2 * n) * L);
   const __amdgpu_buffer_rsrc_t a_rs = ws_rsrc(ab), out_rs = ws_rsrc(p.out + (long long)b * n * L);
   const __amdgpu_buffer_rsrc_t an_rs = ws_rsrc(p.a_next ? p.a_next + (long long)b * n * L : p.out);
-  wn_bf16x8 bh2[8], bl2[8];
+  bf16x8 bh2[8], bl2[8];
 #pragma unroll
   for (int blk = 0; blk < 4; ++blk) {
     float tv[16], sv[16], av[16];
@@ -618,20 +580,20 @@ __device__ __forceinline__ void wn_fwd_tile(WnFwdArgs& p, const int b, const int
     }
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      wn_u32x4 h4, l4;
+      u32x4 h4, l4;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         unsigned hh, ll;
-        wn_split_pair(av[8 * s + 2 * j], av[8 * s + 2 * j + 1], hh, ll);
+        split_bf16_pair(av[8 * s + 2 * j], av[8 * s + 2 * j + 1], hh, ll);
         h4[j] = hh; l4[j] = ll;
       }
-      bh2[2 * blk + s] = __builtin_bit_cast(wn_bf16x8, h4);
-      bl2[2 * blk + s] = __builtin_bit_cast(wn_bf16x8, l4);
+      bh2[2 * blk + s] = __builtin_bit_cast(bf16x8, h4);
+      bl2[2 * blk + s] = __builtin_bit_cast(bf16x8, l4);
     }
   }
   asm volatile("" ::: "memory");                       // the stores stay in front of the LDS-DMA issued below
-  WN_T(tg1);
-  WN_ACC(6, tg0, tg1);                                 // drain + gate + t,s stores (issue)
+  FST_T(tg1);
+  FST_ACC(6, tg0, tg1);                                // drain + gate + t,s stores (issue)
 
   // ---------------------------------------------------------------- GEMM 2: [a ; out] += [W_rs | b] · [acts ; 1]
 #pragma unroll
@@ -643,17 +605,17 @@ __device__ __forceinline__ void wn_fwd_tile(WnFwdArgs& p, const int b, const int
     const StageSrc nxt = stage_src(more ? k + 2 : k, slot >= 1 ? slot - 1 : 2);
     const char* base = ldsb + slot * F_SLOT;
     // (fragments one row block ahead, as in GEMM 1; on the last layer the residual-row blocks 0-3 are neither read nor multiplied)
-    wn_bf16x8 fah[2], fal[2];
+    bf16x8 fah[2], fal[2];
     auto a_frag = [&](int mb) {
-      fah[mb % 2] = *reinterpret_cast<const wn_bf16x8*>(base + mb * 2048 + lane * 16);
-      fal[mb % 2] = *reinterpret_cast<const wn_bf16x8*>(base + mb * 2048 + 1024 + lane * 16);
+      fah[mb % 2] = *reinterpret_cast<const bf16x8*>(base + mb * 2048 + lane * 16);
+      fal[mb % 2] = *reinterpret_cast<const bf16x8*>(base + mb * 2048 + 1024 + lane * 16);
     };
     if (!p.last) a_frag(0);
 #pragma unroll
     for (int mb = 0; mb < 8; ++mb) {
       if (mb + 1 < 8 && !(p.last && mb + 1 < 4)) a_frag(mb + 1);
       if (!(p.last && mb < 4)) {                       // wave-uniform
-        const wn_bf16x8 ah = fah[mb % 2], al = fal[mb % 2];
+        const bf16x8 ah = fah[mb % 2], al = fal[mb % 2];
         acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh2[ks], acc[mb], 0, 0, 0);
         acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl2[ks], acc[mb], 0, 0, 0);
         acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh2[ks], acc[mb], 0, 0, 0);
@@ -667,8 +629,8 @@ __device__ __forceinline__ void wn_fwd_tile(WnFwdArgs& p, const int b, const int
     slot = slot == 2 ? 0 : slot + 1;
   }
 
-  WN_T(tg2);
-  WN_ACC(7, tg1, tg2);                                 // GEMM 2
+  FST_T(tg2);
+  FST_ACC(7, tg1, tg2);                                // GEMM 2
   // ---------------------------------------------------------------- a_next = a + r[:n];  out (+)= r[n:]
   // straight from the accumulators (the operands were read into them before GEMM 2): stores only, nothing to wait for
 #pragma unroll
@@ -677,10 +639,10 @@ __device__ __forceinline__ void wn_fwd_tile(WnFwdArgs& p, const int b, const int
     if (!p.last) ws_acc_store(acc[blk], an_rs, wl, blk * 32, tcol, rows_e, L);
     ws_acc_store(acc[blk + 4], out_rs, wl, blk * 32, tcol, rows_e, L);
   }
-  WN_T(tg3);
-  WN_ACC(8, tg2, tg3);                                 // final epilogue (issue; includes waiting for the operand loads)
-  WN_ACC(9, ts0, tg3);                                 // whole wave
-  WN_FLUSH;
+  FST_T(tg3);
+  FST_ACC(8, tg2, tg3);                                // final epilogue (issue; includes waiting for the operand loads)
+  FST_ACC(9, ts0, tg3);                                // whole wave
+  FST_FLUSH(wn_stamps);
 }
 
 template <int NW>
@@ -730,7 +692,7 @@ __global__ __launch_bounds__(512, 1) void wn_stack_fwd_kernel(WnFwdStackParams p
         wn_fwd_tile<8>(*qp, b, pass * 256, ldsb);
         // this tile's stores (a_next, out, t,s) are complete and every wave is past its LDS reads before the next tile's
         // LDS-DMA refills the ring and reads what was stored
-        wn_wait_vmcnt<0>();
+        wait_vmcnt<0>();
         __syncthreads();
       }
     }
@@ -752,12 +714,11 @@ extern "C" int fst_wn_stack_fwd(const float* const* a_in, const int64_t* a_bs, c
   FST_REQUIRE(image_bytes == fst_wn_image_bytes(n, h), "fst_wn_stack_fwd: images are %lld bytes, expected %lld",
               (long long)image_bytes, (long long)fst_wn_image_bytes(n, h));
   FST_REQUIRE(B == 1 || u0_bs >= (int64_t)h * L, "fst_wn_stack_fwd: batch stride of u0 smaller than a sample");
-  auto al16 = [](const void* q) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  FST_REQUIRE(u0_bs % 4 == 0 && al16(u0) && al16(out), "fst_wn_stack_fwd: needs 16-byte aligned tensors");
+  FST_REQUIRE(u0_bs % 4 == 0 && fst_aligned16(u0) && fst_aligned16(out), "fst_wn_stack_fwd: needs 16-byte aligned tensors");
   WnFwdStackParams p = {};
   for (int i = 0; i < nl; ++i) {
     FST_REQUIRE(a_in[i] && images[i] && ts[i] && (a_next[i] || i == nl - 1), "fst_wn_stack_fwd: null operand of layer %d", i);
-    FST_REQUIRE(a_bs[i] >= (int64_t)n * L && a_bs[i] % 4 == 0 && al16(a_in[i]) && al16(images[i]) && al16(ts[i]) && al16(a_next[i]),
+    FST_REQUIRE(a_bs[i] >= (int64_t)n * L && a_bs[i] % 4 == 0 && fst_aligned16(a_in[i]) && fst_aligned16(images[i]) && fst_aligned16(ts[i]) && fst_aligned16(a_next[i]),
                 "fst_wn_stack_fwd: layer %d: batch stride %lld smaller than a sample, or an operand that is not 16-byte aligned", i,
                 (long long)a_bs[i]);
     FST_REQUIRE(i == nl - 1 || a_in[i + 1] == a_next[i], "fst_wn_stack_fwd: the input of layer %d is not the a_next of layer %d",
@@ -787,9 +748,8 @@ extern "C" int fst_wn_layer_fwd(const float* a, int64_t a_bs, const float* u0, i
   FST_REQUIRE(image_bytes == fst_wn_image_bytes(n, h), "fst_wn_layer_fwd: image is %lld bytes, expected %lld",
               (long long)image_bytes, (long long)fst_wn_image_bytes(n, h));
   FST_REQUIRE(B == 1 || (a_bs >= (int64_t)n * L && u0_bs >= (int64_t)h * L), "fst_wn_layer_fwd: batch stride smaller than a sample");
-  auto al16 = [](const void* q) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  FST_REQUIRE(L % 4 == 0 && a_bs % 4 == 0 && u0_bs % 4 == 0 && al16(a) && al16(u0) && al16(image) && al16(ts) && al16(acts) &&
-              al16(a_next) && al16(out), "fst_wn_layer_fwd: needs L %% 4 == 0 and 16-byte aligned tensors (L=%d)", L);
+  FST_REQUIRE(L % 4 == 0 && a_bs % 4 == 0 && u0_bs % 4 == 0 && fst_aligned16(a) && fst_aligned16(u0) && fst_aligned16(image) && fst_aligned16(ts) && fst_aligned16(acts) &&
+              fst_aligned16(a_next) && fst_aligned16(out), "fst_wn_layer_fwd: needs L %% 4 == 0 and 16-byte aligned tensors (L=%d)", L);
   WnFwdParams p;
   p.a = a; p.a_bs = a_bs; p.u0 = u0; p.u0_bs = u0_bs; p.img = static_cast<const char*>(image);
   p.ts = ts; p.acts = acts; p.a_next = a_next; p.out = out;
@@ -852,7 +812,7 @@ __global__ __launch_bounds__(64) void wn_pack_bwd_kernel(WnPackBwdParams p) {
   }
   unsigned hi[4], lo[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) wn_split_pair(v[2 * j], v[2 * j + 1], hi[j], lo[j]);
+  for (int j = 0; j < 4; ++j) split_bf16_pair(v[2 * j], v[2 * j + 1], hi[j], lo[j]);
   uint4* dst = p.img + ((long long)st * 4 + blk) * 128 + lane;
   dst[0] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
   dst[64] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
@@ -868,7 +828,7 @@ extern "C" int fst_wn_pack_bwd(const float* rs_w, int n, int last, int acc_order
   FST_REQUIRE(rs_w && image && n > 0 && n <= 128, "fst_wn_pack_bwd: bad arguments (n=%d, needs n <= 128)", n);
   FST_REQUIRE(image_bytes == fst_wn_bwd_image_bytes(n, last), "fst_wn_pack_bwd: image is %lld bytes, expected %lld",
               (long long)image_bytes, (long long)fst_wn_bwd_image_bytes(n, last));
-  FST_REQUIRE((reinterpret_cast<uintptr_t>(image) & 15) == 0, "fst_wn_pack_bwd: image must be 16-byte aligned");
+  FST_REQUIRE(fst_aligned16(image), "fst_wn_pack_bwd: image must be 16-byte aligned");
   WnPackBwdParams p = {rs_w, n, last ? 1 : 0, wn_ch(n), static_cast<uint4*>(image), acc_order ? 1 : 0};
   const int stages = (last ? 1 : 2) * p.CH;
   hipLaunchKernelGGL(wn_pack_bwd_kernel, dim3((unsigned)(stages * 4)), dim3(64), 0, (hipStream_t)stream, p);
@@ -915,7 +875,7 @@ __global__ __launch_bounds__(256, WN_BWD_OCC) void wn_layer_bwd_kernel(WnBwdPara
     for (int i = 0; i < 4; ++i) {
       const int idx = wave_s + 4 * i;
       if (idx < 8) {
-        __builtin_amdgcn_global_load_lds(WN_GLOBAL_PTR(asrc + idx * 1024 + lane * 16), WN_LDS_VOID(sl + idx * 1024), 16, 0, 0);
+        lds_dma16(asrc + idx * 1024 + lane * 16, sl + idx * 1024);
       } else {
         const int bi = idx - 8;
         const int gq = bi >> 2, m = bi & 3;
@@ -923,7 +883,7 @@ __global__ __launch_bounds__(256, WN_BWD_OCC) void wn_layer_bwd_kernel(WnBwdPara
         const int t = t0 + 32 * m + 4 * (lane & 7);
         const bool ok = row < c_count && t < L;
         const char* src = ok ? reinterpret_cast<const char*>(xb + ((long long)row * L + t)) : zero16;
-        __builtin_amdgcn_global_load_lds(WN_GLOBAL_PTR(src), WN_LDS_VOID(sl + WN_BW_A + gq * WN_BW_GS + m * 1024), 16, 0, 0);
+        lds_dma16(src, sl + WN_BW_A + gq * WN_BW_GS + m * 1024);
       }
     }
   };
@@ -945,7 +905,7 @@ __global__ __launch_bounds__(256, WN_BWD_OCC) void wn_layer_bwd_kernel(WnBwdPara
   if (S3 > 1) issue(1, 1);
   int slot = 0;
   for (int k = 0; k < S3; ++k) {
-    if (k + 1 < S3) wn_wait_vmcnt<4>(); else wn_wait_vmcnt<0>();     // stage k landed; stage k+1's 4 pieces may fly on
+    if (k + 1 < S3) wait_vmcnt<4>(); else wait_vmcnt<0>();           // stage k landed; stage k+1's 4 pieces may fly on
     __builtin_amdgcn_s_barrier();
     if (k + 2 < S3) issue(k + 2, slot >= 1 ? slot - 1 : 2);
     const char* base = ldsb + slot * WN_BW_SLOT;
@@ -954,18 +914,18 @@ __global__ __launch_bounds__(256, WN_BWD_OCC) void wn_layer_bwd_kernel(WnBwdPara
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = *reinterpret_cast<const float*>(bp + j * 128);
-    wn_u32x4 bh4, bl4;
+    u32x4 bh4, bl4;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       unsigned hh, ll;
-      wn_split_pair(v[2 * j], v[2 * j + 1], hh, ll);
+      split_bf16_pair(v[2 * j], v[2 * j + 1], hh, ll);
       bh4[j] = hh; bl4[j] = ll;
     }
-    const wn_bf16x8 bh = __builtin_bit_cast(wn_bf16x8, bh4), bl = __builtin_bit_cast(wn_bf16x8, bl4);
+    const bf16x8 bh = __builtin_bit_cast(bf16x8, bh4), bl = __builtin_bit_cast(bf16x8, bl4);
 #pragma unroll
     for (int mb = 0; mb < 4; ++mb) {
-      const wn_bf16x8 ah = *reinterpret_cast<const wn_bf16x8*>(base + mb * 2048 + lane * 16);
-      const wn_bf16x8 al = *reinterpret_cast<const wn_bf16x8*>(base + mb * 2048 + 1024 + lane * 16);
+      const bf16x8 ah = *reinterpret_cast<const bf16x8*>(base + mb * 2048 + lane * 16);
+      const bf16x8 al = *reinterpret_cast<const bf16x8*>(base + mb * 2048 + 1024 + lane * 16);
       acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[mb], 0, 0, 0);
       acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[mb], 0, 0, 0);
       acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[mb], 0, 0, 0);
@@ -1019,8 +979,7 @@ extern "C" int fst_wn_layer_bwd(const float* d_a, const float* d_out, const floa
               "of the [B, n, L] tensors", B, n, L, (long long)numel_a);
   FST_REQUIRE(image_bytes == fst_wn_bwd_image_bytes(n, last), "fst_wn_layer_bwd: image is %lld bytes, expected %lld",
               (long long)image_bytes, (long long)fst_wn_bwd_image_bytes(n, last));
-  auto al16 = [](const void* q) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  FST_REQUIRE(L % 4 == 0 && al16(d_a) && al16(d_out) && al16(ts) && al16(image) && al16(dg),
+  FST_REQUIRE(L % 4 == 0 && fst_aligned16(d_a) && fst_aligned16(d_out) && fst_aligned16(ts) && fst_aligned16(image) && fst_aligned16(dg),
               "fst_wn_layer_bwd: needs L %% 4 == 0 and 16-byte aligned tensors (L=%d)", L);
   WnBwdParams p;
   p.d_a = last ? nullptr : d_a; p.d_out = d_out; p.ts = ts; p.img = static_cast<const char*>(image); p.dg = dg;
@@ -1084,7 +1043,7 @@ __global__ __launch_bounds__(64) void wn_pack_dgrad_kernel(WnPackDgradParams p) 
   }
   unsigned hi[4], lo[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) wn_split_pair(v[2 * j], v[2 * j + 1], hi[j], lo[j]);
+  for (int j = 0; j < 4; ++j) split_bf16_pair(v[2 * j], v[2 * j + 1], hi[j], lo[j]);
   uint4* dst = p.img + (long long)blockIdx.x * 128 + lane;
   dst[0] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
   dst[64] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
@@ -1102,7 +1061,7 @@ extern "C" int fst_wn_pack_dgrad(const float* in_w, const float* cond_w, int n, 
   FST_REQUIRE(ntaps == 3, "fst_wn_pack_dgrad: the fused WN kernels are 3-tap (in_w [2n][n][3]); got %d taps", ntaps);
   FST_REQUIRE(image_bytes == fst_wn_dgrad_image_bytes(n), "fst_wn_pack_dgrad: image is %lld bytes, expected %lld",
               (long long)image_bytes, (long long)fst_wn_dgrad_image_bytes(n));
-  FST_REQUIRE((reinterpret_cast<uintptr_t>(image) & 15) == 0, "fst_wn_pack_dgrad: image must be 16-byte aligned");
+  FST_REQUIRE(fst_aligned16(image), "fst_wn_pack_dgrad: image must be 16-byte aligned");
   WnPackDgradParams p = {in_w, cond_w, n, h, (2 * n + 15) / 16, static_cast<uint4*>(image)};
   hipLaunchKernelGGL(wn_pack_dgrad_kernel, dim3((unsigned)(p.CHK * DG_A_BLOCKS)), dim3(64), 0, (hipStream_t)stream, p);
   FST_LAUNCH_CHECK();
@@ -1127,7 +1086,7 @@ struct WnDgradParams {
 template <int N>
 __device__ __forceinline__ void wn_wait_sw(int n) {
   // counted wait for a wave-uniform run-time count (the immediates are instantiated below)
-  if (n == N) { wn_wait_vmcnt<N>(); return; }
+  if (n == N) { wait_vmcnt<N>(); return; }
   if constexpr (N > 0) wn_wait_sw<N - 1>(n);
 }
 
@@ -1162,7 +1121,7 @@ __global__ __launch_bounds__(512, 2) void wn_layer_dgrad_kernel(WnDgradParams p)
     const int w4 = (t0 - dil) & ~3;                      // 16-byte aligned start of the window (first column any tap needs)
     for (int idx = wave_s; idx < NI; idx += 8) {         // wave-uniform trip count
       if (idx < 2 * DG_A_BLOCKS) {
-        __builtin_amdgcn_global_load_lds(WN_GLOBAL_PTR(asrc + idx * 1024 + lane * 16), WN_LDS_VOID(sl + idx * 1024), 16, 0, 0);
+        lds_dma16(asrc + idx * 1024 + lane * 16, sl + idx * 1024);
       } else {
         const int bi = idx - 2 * DG_A_BLOCKS;
         const int gq = bi >= p.nblkw ? 1 : 0, m = bi - gq * p.nblkw;
@@ -1170,7 +1129,7 @@ __global__ __launch_bounds__(512, 2) void wn_layer_dgrad_kernel(WnDgradParams p)
         const int t = w4 + 32 * m + 4 * (lane & 7);
         const bool ok = row < c_count && t >= 0 && t < L;
         const char* src = ok ? reinterpret_cast<const char*>(xb + ((long long)row * L + t)) : zero16;
-        __builtin_amdgcn_global_load_lds(WN_GLOBAL_PTR(src), WN_LDS_VOID(sl + DG_A_BYTES + gq * p.gsw + m * 1024), 16, 0, 0);
+        lds_dma16(src, sl + DG_A_BYTES + gq * p.gsw + m * 1024);
       }
     }
   };
@@ -1213,7 +1172,7 @@ __global__ __launch_bounds__(512, 2) void wn_layer_dgrad_kernel(WnDgradParams p)
       for (int tap = 0; tap < 3; ++tap) {
         // this wave's DG_NCB column blocks of the tap's window: the fragment of a weight block is read from LDS once and
         // multiplied against all of them (LDS reads, 128 B/clk/CU, bound the one-column-block form of this loop)
-        wn_bf16x8 bh[DG_NCB], bl[DG_NCB];
+        bf16x8 bh[DG_NCB], bl[DG_NCB];
 #pragma unroll
         for (int cb = 0; cb < DG_NCB; ++cb) {
           const int colx = wave_n0 + 32 * cb + l31 + (2 - tap) * dil + sub;
@@ -1221,21 +1180,21 @@ __global__ __launch_bounds__(512, 2) void wn_layer_dgrad_kernel(WnDgradParams p)
           float v8[8];
 #pragma unroll
           for (int j = 0; j < 8; ++j) v8[j] = *reinterpret_cast<const float*>(bp + j * 128);
-          wn_u32x4 bh4, bl4;
+          u32x4 bh4, bl4;
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             unsigned hh, ll;
-            wn_split_pair(v8[2 * j], v8[2 * j + 1], hh, ll);
+            split_bf16_pair(v8[2 * j], v8[2 * j + 1], hh, ll);
             bh4[j] = hh; bl4[j] = ll;
           }
-          bh[cb] = __builtin_bit_cast(wn_bf16x8, bh4); bl[cb] = __builtin_bit_cast(wn_bf16x8, bl4);
+          bh[cb] = __builtin_bit_cast(bf16x8, bh4); bl[cb] = __builtin_bit_cast(bf16x8, bl4);
         }
         const char* ab = base + (tap == 0 ? 0 : (tap == 1 ? 4 : 9)) * 2048;
 #pragma unroll
         for (int mb = 0; mb < 5; ++mb) {
           if (mb == 4 && tap != 1) continue;               // the d_u0 block exists on the centre tap only
-          const wn_bf16x8 ah = *reinterpret_cast<const wn_bf16x8*>(ab + mb * 2048 + lane * 16);
-          const wn_bf16x8 al = *reinterpret_cast<const wn_bf16x8*>(ab + mb * 2048 + 1024 + lane * 16);
+          const bf16x8 ah = *reinterpret_cast<const bf16x8*>(ab + mb * 2048 + lane * 16);
+          const bf16x8 al = *reinterpret_cast<const bf16x8*>(ab + mb * 2048 + 1024 + lane * 16);
 #pragma unroll
           for (int cb = 0; cb < DG_NCB; ++cb) {
             acc[mb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[cb], acc[mb][cb], 0, 0, 0);
@@ -1319,8 +1278,7 @@ extern "C" int fst_wn_layer_dgrad(const float* dg, const void* image, int64_t im
               "fst_wn_layer_dgrad: d_u0 batch stride %lld (needs >= h*L = %lld and a multiple of 4)", (long long)d_u0_bs, (long long)h * L);
   FST_REQUIRE(image_bytes == fst_wn_dgrad_image_bytes(n), "fst_wn_layer_dgrad: image is %lld bytes, expected %lld",
               (long long)image_bytes, (long long)fst_wn_dgrad_image_bytes(n));
-  auto al16 = [](const void* q) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  FST_REQUIRE(L % 4 == 0 && al16(dg) && al16(image) && al16(d_a) && al16(d_a_new) && al16(d_u0),
+  FST_REQUIRE(L % 4 == 0 && fst_aligned16(dg) && fst_aligned16(image) && fst_aligned16(d_a) && fst_aligned16(d_a_new) && fst_aligned16(d_u0),
               "fst_wn_layer_dgrad: needs L %% 4 == 0 and 16-byte aligned tensors (L=%d)", L);
   WnDgradParams p;
   p.dg = dg; p.img = static_cast<const char*>(image); p.d_a = d_a; p.d_a_new = d_a_new; p.d_u0 = d_u0; p.d_u0_bs = d_u0_bs;
@@ -1444,15 +1402,14 @@ __global__ __launch_bounds__(512, 2) void wn_stack_bwd_kernel(WnStackParams p_by
     const int S3 = (i == p.nl - 1 ? 1 : 2) * CH;
     const char* const img = p.img_b[i];
     for (int c = 0; c < S3; ++c)
-      __builtin_amdgcn_global_load_lds(WN_GLOBAL_PTR(img + (long long)c * WN_BW_A + wave_s * 1024 + lane * 16),
-                                       WN_LDS_VOID(ldsb + c * WN_BW_A + wave_s * 1024), 16, 0, 0);
+      lds_dma16(img + (long long)c * WN_BW_A + wave_s * 1024 + lane * 16, ldsb + c * WN_BW_A + wave_s * 1024);
   };
   // per-lane byte offset of a B-fragment element of a [channel][time] matrix read straight from memory: lane half hh reads
   // channels 8hh + j of a 16-channel chunk at column l31 of its block
   const unsigned vfrag = (unsigned)(8 * half * L + l31) * 4u;
 
-  WN_SUMS;
-  WN_T(tw0);
+  FST_SUMS(12);
+  FST_T(tw0);
   bool primed = false;                                     // the weight image of the layer at hand is already in flight
   for (int b = blockIdx.x; b < p.B; b += gridDim.x) {
     // acc[0..3] = the cotangent of the residual stream (d_a), carried from layer to layer; acc[4] = the conditioning rows (d_u0)
@@ -1474,17 +1431,17 @@ __global__ __launch_bounds__(512, 2) void wn_stack_bwd_kernel(WnStackParams p_by
         const __amdgpu_buffer_rsrc_t dg_s = ws_rsrc(p.dg[i] + ((long long)b * 2 + 1) * n * L);
         const __amdgpu_buffer_rsrc_t dout_r = ws_rsrc(p.d_out + (long long)b * n * L);
         float* const rs_out = p.rs_b[i];
-        WN_T(ta0);
+        FST_T(ta0);
         if (!primed) issue_res(i);
         primed = false;
         if (rs_out) {
 #pragma unroll
           for (int w = 0; w < 4; ++w) rsum[w * 512 + tid] = 0.f;
         }
-        wn_wait_vmcnt<0>();                                  // this wave's pieces of the image have landed ...
+        wait_vmcnt<0>();                                     // this wave's pieces of the image have landed ...
         __syncthreads();                                     // ... and everyone's; the row-sum arrays are zeroed
-        WN_T(ta1);
-        WN_ACC(0, ta0, ta1);                             // phase A: waiting for the weight image
+        FST_T(ta1);
+        FST_ACC(0, ta0, ta1);                            // phase A: waiting for the weight image
         const char* const w_dout = ldsb + (long long)(last ? 0 : CH) * WN_BW_A;
         auto run_pass = [&](auto pc) {
           constexpr int cb = decltype(pc)::value;
@@ -1495,17 +1452,17 @@ __global__ __launch_bounds__(512, 2) void wn_stack_bwd_kernel(WnStackParams p_by
           for (int mb = 0; mb < 4; ++mb)
 #pragma unroll
             for (int r = 0; r < 16; ++r) da[mb][r] = 0.f;
-          auto multiply = [&](const char* base, const wn_bf16x8 bh, const wn_bf16x8 bl) {
+          auto multiply = [&](const char* base, const bf16x8 bh, const bf16x8 bl) {
 #pragma unroll
             for (int mb = 0; mb < 4; ++mb) {
-              const wn_bf16x8 ah = *reinterpret_cast<const wn_bf16x8*>(base + mb * 2048 + lane * 16);
-              const wn_bf16x8 al = *reinterpret_cast<const wn_bf16x8*>(base + mb * 2048 + 1024 + lane * 16);
+              const bf16x8 ah = *reinterpret_cast<const bf16x8*>(base + mb * 2048 + lane * 16);
+              const bf16x8 al = *reinterpret_cast<const bf16x8*>(base + mb * 2048 + 1024 + lane * 16);
               da[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, da[mb], 0, 0, 0);
               da[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, da[mb], 0, 0, 0);
               da[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, da[mb], 0, 0, 0);
             }
           };
-          WN_T(tp0);
+          FST_T(tp0);
           // ---- the d_out stages: the operand comes straight from memory in fragment layout (eight dword loads per stage: lane
           // half hh reads channels 8hh + j at its column), the next stage's in flight while one is multiplied — no ring, no barrier
           const unsigned vf = tcol + l31 < L ? vfrag : WS_OOB, vf_lo = half == 0 ? vf : WS_OOB;
@@ -1527,28 +1484,28 @@ __global__ __launch_bounds__(512, 2) void wn_stack_bwd_kernel(WnStackParams p_by
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = vn[j];
             if (k + 1 < CH) load_dout(vn, k + 1);
-            wn_u32x4 bh4, bl4;
+            u32x4 bh4, bl4;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
               unsigned hh, ll;
-              wn_split_pair(v[2 * j], v[2 * j + 1], hh, ll);
+              split_bf16_pair(v[2 * j], v[2 * j + 1], hh, ll);
               bh4[j] = hh; bl4[j] = ll;
             }
-            multiply(w_dout + k * WN_BW_A, __builtin_bit_cast(wn_bf16x8, bh4), __builtin_bit_cast(wn_bf16x8, bl4));
+            multiply(w_dout + k * WN_BW_A, __builtin_bit_cast(bf16x8, bh4), __builtin_bit_cast(bf16x8, bl4));
           }
           // ---- the d_a stages: the operand IS the accumulator tile (registers 8s..8s+7 of row block c>>1 are k-step c&1)
           if (!last) {
             auto da_stage = [&](auto cc) {
               constexpr int c = decltype(cc)::value;
               if (c < CH) {                                // wave-uniform
-                wn_u32x4 bh4, bl4;
+                u32x4 bh4, bl4;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                   unsigned hh, ll;
-                  wn_split_pair(acc[c >> 1][cb][8 * (c & 1) + 2 * j], acc[c >> 1][cb][8 * (c & 1) + 2 * j + 1], hh, ll);
+                  split_bf16_pair(acc[c >> 1][cb][8 * (c & 1) + 2 * j], acc[c >> 1][cb][8 * (c & 1) + 2 * j + 1], hh, ll);
                   bh4[j] = hh; bl4[j] = ll;
                 }
-                multiply(ldsb + c * WN_BW_A, __builtin_bit_cast(wn_bf16x8, bh4), __builtin_bit_cast(wn_bf16x8, bl4));
+                multiply(ldsb + c * WN_BW_A, __builtin_bit_cast(bf16x8, bh4), __builtin_bit_cast(bf16x8, bl4));
                 __builtin_amdgcn_sched_barrier(0);        // stage by stage: hoisted fragment reads of later stages cost registers
               }
             };
@@ -1557,8 +1514,8 @@ __global__ __launch_bounds__(512, 2) void wn_stack_bwd_kernel(WnStackParams p_by
             da_stage(std::integral_constant<int, 4>{}); da_stage(std::integral_constant<int, 5>{});
             da_stage(std::integral_constant<int, 6>{}); da_stage(std::integral_constant<int, 7>{});
           }
-          WN_T(tp1);
-          WN_ACC(1, tp0, tp1);                           // phase A: GEMM stages of a pass
+          FST_T(tp1);
+          FST_ACC(1, tp0, tp1);                          // phase A: GEMM stages of a pass
           // ---- gate: four tiles (row blocks) of this column block
 #pragma unroll
           for (int blk = 0; blk < 4; ++blk) {
@@ -1581,8 +1538,8 @@ __global__ __launch_bounds__(512, 2) void wn_stack_bwd_kernel(WnStackParams p_by
             }
             __builtin_amdgcn_sched_barrier(0);            // tile by tile (a scheduler that hoists the loads of later tiles runs out of registers)
           }
-          WN_T(tp2);
-          WN_ACC(2, tp1, tp2);                           // phase A: gate epilogue of a pass
+          FST_T(tp2);
+          FST_ACC(2, tp1, tp2);                          // phase A: gate epilogue of a pass
         };
         run_pass(std::integral_constant<int, 0>{});
         run_pass(std::integral_constant<int, 1>{});
@@ -1595,11 +1552,11 @@ __global__ __launch_bounds__(512, 2) void wn_stack_bwd_kernel(WnStackParams p_by
             rs_out[(long long)tid * p.B + b] = s8;            // [256][B]
           }
         }
-        WN_T(ta3);
-        wn_wait_vmcnt<0>();                                  // this wave's dg stores have reached L2 ...
+        FST_T(ta3);
+        wait_vmcnt<0>();                                     // this wave's dg stores have reached L2 ...
         __syncthreads();                                     // ... and so have everyone's: phase B may fetch them; the ring is free
-        WN_T(ta4);
-        WN_ACC(3, ta3, ta4);                             // phase A -> B: store drain + barrier
+        FST_T(ta4);
+        FST_ACC(3, ta3, ta4);                            // phase A -> B: store drain + barrier
       }
       // ============================================================ phase B: d_a += W_inᵀ (*) dg,  d_u0 += W_condᵀ·dg
       {
@@ -1621,7 +1578,7 @@ __global__ __launch_bounds__(512, 2) void wn_stack_bwd_kernel(WnStackParams p_by
           const int c_count = min(16, 2 * n - 16 * c);
           for (int idx = wave_s; idx < NI; idx += 8) {
             if (idx < 2 * DG_A_BLOCKS) {
-              __builtin_amdgcn_global_load_lds(WN_GLOBAL_PTR(asrc + idx * 1024 + lane * 16), WN_LDS_VOID(sl + idx * 1024), 16, 0, 0);
+              lds_dma16(asrc + idx * 1024 + lane * 16, sl + idx * 1024);
             } else {
               const int bi = idx - 2 * DG_A_BLOCKS;
               const int gq = bi >= nblkw ? 1 : 0, m = bi - gq * nblkw;
@@ -1629,27 +1586,27 @@ __global__ __launch_bounds__(512, 2) void wn_stack_bwd_kernel(WnStackParams p_by
               const int t = w4 + 32 * m + 4 * (lane & 7);
               const bool ok = row < c_count && t >= 0 && t < L;
               const char* src = ok ? reinterpret_cast<const char*>(xb + ((long long)row * L + t)) : zero16;
-              __builtin_amdgcn_global_load_lds(WN_GLOBAL_PTR(src), WN_LDS_VOID(sl + DG_A_BYTES + gq * gsw + m * 1024), 16, 0, 0);
+              lds_dma16(src, sl + DG_A_BYTES + gq * gsw + m * 1024);
             }
           }
         };
-        WN_T(tb0);
+        FST_T(tb0);
         // the d_a tiles are where the previous layer left them; the conditioning rows come from memory
         ws_acc_load(acc[4][0], du_r, wl0, 0, wave_n0, p.h, L);
         ws_acc_load(acc[4][1], du_r, wl1, 0, wave_n0 + 32, p.h, L);
         asm volatile("" ::: "memory");
         issue(0, 0);                                         // two ring slots: one stage in flight while one is multiplied
         int slot = 0;
-        WN_T(tb1);
-        WN_ACC(4, tb0, tb1);                             // phase B: conditioning-row loads + first stage (issue)
+        FST_T(tb1);
+        FST_ACC(4, tb0, tb1);                            // phase B: conditioning-row loads + first stage (issue)
         for (int c = 0; c < CHK; ++c) {
-          wn_wait_vmcnt<0>();
+          wait_vmcnt<0>();
           __builtin_amdgcn_s_barrier();
           if (c + 1 < CHK) issue(c + 1, slot ^ 1);
           const char* base = ldsb + slot * slotb;
 #pragma unroll
           for (int tap = 0; tap < 3; ++tap) {
-            wn_bf16x8 bh[DG_NCB], bl[DG_NCB];
+            bf16x8 bh[DG_NCB], bl[DG_NCB];
 #pragma unroll
             for (int cb = 0; cb < DG_NCB; ++cb) {
               const int colx = wave_n0 + 32 * cb + l31 + (2 - tap) * dil + sub;
@@ -1657,21 +1614,21 @@ __global__ __launch_bounds__(512, 2) void wn_stack_bwd_kernel(WnStackParams p_by
               float v8[8];
 #pragma unroll
               for (int j = 0; j < 8; ++j) v8[j] = *reinterpret_cast<const float*>(bp + j * 128);
-              wn_u32x4 bh4, bl4;
+              u32x4 bh4, bl4;
 #pragma unroll
               for (int j = 0; j < 4; ++j) {
                 unsigned hh, ll;
-                wn_split_pair(v8[2 * j], v8[2 * j + 1], hh, ll);
+                split_bf16_pair(v8[2 * j], v8[2 * j + 1], hh, ll);
                 bh4[j] = hh; bl4[j] = ll;
               }
-              bh[cb] = __builtin_bit_cast(wn_bf16x8, bh4); bl[cb] = __builtin_bit_cast(wn_bf16x8, bl4);
+              bh[cb] = __builtin_bit_cast(bf16x8, bh4); bl[cb] = __builtin_bit_cast(bf16x8, bl4);
             }
             const char* ab = base + (tap == 0 ? 0 : (tap == 1 ? 4 : 9)) * 2048;
 #pragma unroll
             for (int mb = 0; mb < 5; ++mb) {
               if (mb == 4 && tap != 1) continue;
-              const wn_bf16x8 ah = *reinterpret_cast<const wn_bf16x8*>(ab + mb * 2048 + lane * 16);
-              const wn_bf16x8 al = *reinterpret_cast<const wn_bf16x8*>(ab + mb * 2048 + 1024 + lane * 16);
+              const bf16x8 ah = *reinterpret_cast<const bf16x8*>(ab + mb * 2048 + lane * 16);
+              const bf16x8 al = *reinterpret_cast<const bf16x8*>(ab + mb * 2048 + 1024 + lane * 16);
 #pragma unroll
               for (int cb = 0; cb < DG_NCB; ++cb) {
                 acc[mb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[cb], acc[mb][cb], 0, 0, 0);
@@ -1682,8 +1639,8 @@ __global__ __launch_bounds__(512, 2) void wn_stack_bwd_kernel(WnStackParams p_by
           }
           slot ^= 1;
         }
-        WN_T(tb2);
-        WN_ACC(5, tb1, tb2);                             // phase B: GEMM loop
+        FST_T(tb2);
+        FST_ACC(5, tb1, tb2);                            // phase B: GEMM loop
         __syncthreads();                                     // every wave is past its last fragment read: the ring is free
         // the weight image of the next phase A (the layer below, or the top layer of this workgroup's next sequence) depends on
         // nothing this phase stores: it streams into LDS now, under the stores below
@@ -1723,19 +1680,19 @@ __global__ __launch_bounds__(512, 2) void wn_stack_bwd_kernel(WnStackParams p_by
             rs_out[(long long)tid * p.B + b] = s8;            // [128][B]
           }
         }
-        WN_T(tb3);
-        WN_ACC(6, tb2, tb3);                             // phase B: epilogue stores (issue)
+        FST_T(tb3);
+        FST_ACC(6, tb2, tb3);                            // phase B: epilogue stores (issue)
         // d_u0 of this layer must be in L2 before the next layer's phase B reads it back (the wait also retires the primed stages)
-        wn_wait_vmcnt<0>();
+        wait_vmcnt<0>();
         __syncthreads();
-        WN_T(tb4);
-        WN_ACC(7, tb3, tb4);                             // phase B -> A: store drain + barrier
+        FST_T(tb4);
+        FST_ACC(7, tb3, tb4);                            // phase B -> A: store drain + barrier
       }
     }
   }
-  WN_T(tw1);
-  WN_ACC(9, tw0, tw1);
-  WN_FLUSH;
+  FST_T(tw1);
+  FST_ACC(9, tw0, tw1);
+  FST_FLUSH(wn_stamps);
 }
 
 // 1 when fst_wn_stack_bwd serves a WN stack of nl layers on sequences of L samples (dilations 1, 2, 4, ... as the reference's WN)
@@ -1757,12 +1714,11 @@ extern "C" int fst_wn_stack_bwd(const float* const* ts, const void* const* img_b
   FST_REQUIRE(d_u0_bs >= (int64_t)h * L && d_u0_bs % 4 == 0,
               "fst_wn_stack_bwd: d_u0 batch stride %lld (needs >= h*L = %lld and a multiple of 4)", (long long)d_u0_bs, (long long)h * L);
   FST_REQUIRE((rs_b == nullptr) == (rs_d == nullptr), "fst_wn_stack_bwd: row sums of both kinds or of neither");
-  auto al16 = [](const void* q) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   WnStackParams p = {};
   size_t lds_bytes = WS_LDS_A + 8192;                                // phase A: the weight image and the row-sum arrays
   for (int i = 0; i < nl; ++i) {
     FST_REQUIRE(ts[i] && img_b[i] && img_d[i] && dg[i] && (i > 0 || da_out[i]), "fst_wn_stack_bwd: null operand of layer %d", i);
-    FST_REQUIRE(al16(ts[i]) && al16(img_b[i]) && al16(img_d[i]) && al16(dg[i]) && al16(da_out[i]),
+    FST_REQUIRE(fst_aligned16(ts[i]) && fst_aligned16(img_b[i]) && fst_aligned16(img_d[i]) && fst_aligned16(dg[i]) && fst_aligned16(da_out[i]),
                 "fst_wn_stack_bwd: operands of layer %d must be 16-byte aligned", i);
     p.ts[i] = ts[i]; p.img_b[i] = static_cast<const char*>(img_b[i]); p.img_d[i] = static_cast<const char*>(img_d[i]);
     p.dg[i] = dg[i]; p.da_out[i] = da_out[i];
@@ -1771,7 +1727,7 @@ extern "C" int fst_wn_stack_bwd(const float* const* ts, const void* const* img_b
     wn_dgrad_geometry(p.dil[i], &p.nblkw[i], &p.gsw[i], &p.slot_d[i]);
     if ((size_t)2 * p.slot_d[i] > lds_bytes) lds_bytes = (size_t)2 * p.slot_d[i];
   }
-  FST_REQUIRE(al16(d_out) && al16(d_u0), "fst_wn_stack_bwd: d_out / d_u0 must be 16-byte aligned");
+  FST_REQUIRE(fst_aligned16(d_out) && fst_aligned16(d_u0), "fst_wn_stack_bwd: d_out / d_u0 must be 16-byte aligned");
   FST_REQUIRE(lds_bytes <= 160 * 1024, "fst_wn_stack_bwd: %zu bytes of LDS", lds_bytes);
   p.d_out = d_out; p.d_u0 = d_u0; p.d_u0_bs = d_u0_bs;
   p.nl = nl; p.B = B; p.L = L; p.n = n; p.h = h; p.CH = wn_ch(n); p.CHK = (2 * n + 15) / 16;

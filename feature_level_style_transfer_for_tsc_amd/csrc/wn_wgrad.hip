@@ -26,14 +26,7 @@
 #include <stdlib.h>
 #include <type_traits>
 
-#include "fst_common.h"
-
-typedef __bf16 ww_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 ww_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float ww_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned ww_u32x4 __attribute__((ext_vector_type(4)));
-#define WW_GLOBAL_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
-#define WW_LDS_VOID(p) ((__attribute__((address_space(3))) void*)(p))
+#include "fst_device.h"
 
 #define WW_TT 32          // time samples per stage = two MFMA k-steps = one 128-byte LDS row (a full cache line per row)
 #define WW_MROWS 256      // staged dy rows (8 blocks of 32)
@@ -77,55 +70,57 @@ struct WwParams {
   float* w[2];          // reduce outputs
 };
 
-__device__ __forceinline__ void ww_split_pair(float a, float b, unsigned& hi, unsigned& lo) {
-  const ww_f32x2 v = {a, b};
-  hi = __builtin_bit_cast(unsigned, __builtin_convertvector(v, ww_bf16x2));
-  const ww_f32x2 r = {a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xffff0000u)};
-  lo = __builtin_bit_cast(unsigned, __builtin_convertvector(r, ww_bf16x2));
-}
-
 template <class V4>
-__device__ __forceinline__ void ww_split8(const V4& v0, const V4& v1, ww_bf16x8& hi, ww_bf16x8& lo) {
-  ww_u32x4 h, l;
+__device__ __forceinline__ void ww_split8(const V4& v0, const V4& v1, bf16x8& hi, bf16x8& lo) {
+  u32x4 h, l;
   unsigned hh, ll;
-  ww_split_pair(v0.x, v0.y, hh, ll); h[0] = hh; l[0] = ll;
-  ww_split_pair(v0.z, v0.w, hh, ll); h[1] = hh; l[1] = ll;
-  ww_split_pair(v1.x, v1.y, hh, ll); h[2] = hh; l[2] = ll;
-  ww_split_pair(v1.z, v1.w, hh, ll); h[3] = hh; l[3] = ll;
-  hi = __builtin_bit_cast(ww_bf16x8, h);
-  lo = __builtin_bit_cast(ww_bf16x8, l);
+  split_bf16_pair(v0.x, v0.y, hh, ll); h[0] = hh; l[0] = ll;
+  split_bf16_pair(v0.z, v0.w, hh, ll); h[1] = hh; l[1] = ll;
+  split_bf16_pair(v1.x, v1.y, hh, ll); h[2] = hh; l[2] = ll;
+  split_bf16_pair(v1.z, v1.w, hh, ll); h[3] = hh; l[3] = ll;
+  hi = __builtin_bit_cast(bf16x8, h);
+  lo = __builtin_bit_cast(bf16x8, l);
 }
 
-// LDS fragment reads as inline asm.  hipcc's wait-count pass cannot tell ring slots apart: in front of the first compiler-visible
-// LDS read that follows an LDS-DMA issue it places s_waitcnt vmcnt(0) — which drained both rings every stage (the DMA of the
-// next stages, issued a few instructions earlier, had to land before the current stage could be multiplied: 139 µs).  The pass
-// does not look inside asm; ordering is by the counted vmcnt + barrier at the top of the stage, and the reads are retired by
-// the explicit lgkmcnt wait + scheduling barrier below.
-typedef float ww_f32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ ww_f32x4 ww_lds_read16(const char* p) {
-  ww_f32x4 v;
-  const unsigned addr = (unsigned)(uintptr_t)((__attribute__((address_space(3))) const char*)p);
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
+// LDS accesses as inline asm, by byte address (ww_lds_addr) with the constant part of the address as the instruction's immediate
+// offset (0 where there is none): tz_wgrad_kernel's fragment and split-pass reads of a stage then share a handful of per-lane
+// address registers (see its instruction budget).  Why asm: hipcc's wait-count pass cannot tell ring slots apart: in front of the
+// first compiler-visible LDS read that follows an LDS-DMA issue it places s_waitcnt vmcnt(0) — which drained both rings every stage
+// (the DMA of the next stages, issued a few instructions earlier, had to land before the current stage could be multiplied:
+// 139 µs).  The pass does not look inside asm; ordering is by the counted vmcnt + barrier at the top of the stage, and the reads
+// are retired by the explicit lgkmcnt wait + scheduling barrier below.
+__device__ __forceinline__ unsigned ww_lds_addr(const char* p) {
+  return (unsigned)(uintptr_t)((__attribute__((address_space(3))) const char*)p);
+}
+template <int OFF = 0>
+__device__ __forceinline__ f32x4 ww_lds_read16(unsigned addr) {
+  f32x4 v;
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
   return v;
 }
-__device__ __forceinline__ void ww_lds_write16(char* p, const ww_u32x4& v) {
-  const unsigned addr = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)p);
-  asm volatile("ds_write_b128 %0, %1" ::"v"(addr), "v"(v) : "memory");
+template <int OFF = 0>
+__device__ __forceinline__ float ww_lds_read4(unsigned addr) {
+  float v;
+  asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
+  return v;
 }
-__device__ __forceinline__ void ww_lds_zero4(char* p) {
-  const unsigned addr = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)p);
-  asm volatile("ds_write_b32 %0, %1" ::"v"(addr), "v"(0.0f) : "memory");
+template <int OFF = 0>
+__device__ __forceinline__ void ww_lds_write16(unsigned addr, const u32x4& v) {
+  asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(addr), "v"(v), "n"(OFF) : "memory");
 }
-// One LDS-DMA piece as inline asm too: with the builtin the same pass put s_waitcnt vmcnt(0) in front of the address arithmetic of
-// every piece but the first once the issues were spread between the MFMAs (each issue then waited for all earlier pieces to land).
-// M0 carries the wave-uniform LDS byte address; the 64 lanes' 16 bytes land at M0 + 16·lane.  M0 is a register the compiler
-// reserves for itself (it may not appear in a clobber list: "may not be preserved"), so the block saves it and puts it back:
-// the instruction reads M0 when it issues, the restore right behind it is safe.
-__device__ __forceinline__ void ww_dma16(const char* gsrc, char* lds_dst) {
-  const unsigned addr = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)lds_dst);
+template <int OFF = 0>
+__device__ __forceinline__ void ww_lds_zero4(unsigned addr) {
+  asm volatile("ds_write_b32 %0, %1 offset:%2" ::"v"(addr), "v"(0.0f), "n"(OFF) : "memory");
+}
+// One LDS-DMA piece as inline asm too: with the builtin (lds_dma16) the same pass put s_waitcnt vmcnt(0) in front of the address
+// arithmetic of every piece but the first once the issues were spread between the MFMAs (each issue then waited for all earlier
+// pieces to land).  M0 carries the wave-uniform LDS byte address lds_addr; the 64 lanes' 16 bytes land at lds_addr + 16·lane.
+// M0 is a register the compiler reserves for itself (it may not appear in a clobber list: "may not be preserved"), so the block
+// saves it and puts it back: the instruction reads M0 when it issues, the restore right behind it is safe.
+__device__ __forceinline__ void ww_dma16(const char* gsrc, unsigned lds_addr) {
   unsigned saved_m0;
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(saved_m0) : "v"(gsrc), "s"(addr) : "memory");
+               : "=&s"(saved_m0) : "v"(gsrc), "s"(lds_addr) : "memory");
 }
 __device__ __forceinline__ void ww_lds_wait() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -134,17 +129,12 @@ __device__ __forceinline__ void ww_lds_wait() {
 
 // 8 consecutive samples (two raw 16-byte pieces) → their bf16 hi parts and lo parts, 16 bytes each
 template <class V4>
-__device__ __forceinline__ void ww_split8u(const V4& v0, const V4& v1, ww_u32x4& h, ww_u32x4& l) {
+__device__ __forceinline__ void ww_split8u(const V4& v0, const V4& v1, u32x4& h, u32x4& l) {
   unsigned hh, ll;
-  ww_split_pair(v0.x, v0.y, hh, ll); h[0] = hh; l[0] = ll;
-  ww_split_pair(v0.z, v0.w, hh, ll); h[1] = hh; l[1] = ll;
-  ww_split_pair(v1.x, v1.y, hh, ll); h[2] = hh; l[2] = ll;
-  ww_split_pair(v1.z, v1.w, hh, ll); h[3] = hh; l[3] = ll;
-}
-
-template <int N>
-__device__ __forceinline__ void ww_wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+  split_bf16_pair(v0.x, v0.y, hh, ll); h[0] = hh; l[0] = ll;
+  split_bf16_pair(v0.z, v0.w, hh, ll); h[1] = hh; l[1] = ll;
+  split_bf16_pair(v1.x, v1.y, hh, ll); h[2] = hh; l[2] = ll;
+  split_bf16_pair(v1.z, v1.w, hh, ll); h[3] = hh; l[3] = ll;
 }
 
 // A staged row is 32 samples = eight 16-byte pieces (128 B, one cache line of the tensor row).  Logical row r of a region sits at
@@ -252,14 +242,14 @@ __global__ __launch_bounds__(512, 2) void wn_wgrad_kernel(WwParams p) {
   auto issue_dy1 = [&](int k, int b, int t0, int slot) {
     const bool ok = dsrc[k].p != nullptr && t0 + dsrc[k].t < L;
     const char* src = ok ? reinterpret_cast<const char*>(dsrc[k].p + ((long long)b * dsrc[k].bs + t0)) : zero16;
-    ww_dma16(src, ww_lds + slot * dslot_bytes + (wave_s + 8 * k) * 1024);
+    ww_dma16(src, ww_lds_addr(ww_lds + slot * dslot_bytes + (wave_s + 8 * k) * 1024));
   };
   auto issue_x1 = [&](int k, int b, int t0, int slot) {
     if (k >= my_nx) return;                                // wave-uniform
     const int t = t0 + xsrc[k].t;
     const bool ok = xsrc[k].p != nullptr && t > -4 && t < L;   // the piece overlaps the sequence (a straddling one is patched)
     const char* src = ok ? reinterpret_cast<const char*>(xsrc[k].p + ((long long)b * xsrc[k].bs + t0)) : zero16;
-    ww_dma16(src, xring + slot * xslot_bytes + (wave_s + 8 * k) * 1024);
+    ww_dma16(src, ww_lds_addr(xring + slot * xslot_bytes + (wave_s + 8 * k) * 1024));
   };
   auto issue_dy = [&](int tile, int slot) {
     int b, t0;
@@ -312,7 +302,7 @@ __global__ __launch_bounds__(512, 2) void wn_wgrad_kernel(WwParams p) {
   if (n_st > 1) issue_dy(tile_begin + 1, 1);
   int dslot = 0, xslot = 0;
   for (int c = 0; c < n_st; ++c) {
-    if (c + 1 < n_st) ww_wait_vmcnt<4>(); else ww_wait_vmcnt<0>();   // (a wave issues 4 dy pieces per stage)
+    if (c + 1 < n_st) wait_vmcnt<4>(); else wait_vmcnt<0>();         // (a wave issues 4 dy pieces per stage)
     __builtin_amdgcn_s_barrier();                          // everyone's pieces of stage c have landed; stage c - 1 has been read by all
     // The pieces of x(c+1), then of dy(c+2), are issued ONE AT A TIME between the MFMA groups below (issue order unchanged, so
     // the counted wait stands): an LDS-DMA issue blocks its wave for 40-150 cycles while the CU's one address path takes the
@@ -341,9 +331,9 @@ __global__ __launch_bounds__(512, 2) void wn_wgrad_kernel(WwParams p) {
         if (patch_sh != 0) {
           char* rowp = xring + xslot * xslot_bytes + ((tid ^ ((tid >> 3) & 1)) << 7);
           if (at_start && patch_sh < 0)                      // samples t0 + sh + j < 0 of piece 0
-            for (int j = 0; j < -patch_sh; ++j) ww_lds_zero4(rowp + (((0 ^ tid) & 7) << 4) + 4 * j);
+            for (int j = 0; j < -patch_sh; ++j) ww_lds_zero4(ww_lds_addr(rowp + (((0 ^ tid) & 7) << 4) + 4 * j));
           if (at_end && patch_sh > 0)                        // samples t0 + sh + 28 + j >= L of piece 7
-            for (int j = 4 - patch_sh; j < 4; ++j) ww_lds_zero4(rowp + (((7 ^ tid) & 7) << 4) + 4 * j);
+            for (int j = 4 - patch_sh; j < 4; ++j) ww_lds_zero4(ww_lds_addr(rowp + (((7 ^ tid) & 7) << 4) + 4 * j));
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the zeroing stores; NOT __syncthreads(): its fence would drain the ring
         __builtin_amdgcn_s_barrier();
@@ -357,24 +347,24 @@ __global__ __launch_bounds__(512, 2) void wn_wgrad_kernel(WwParams p) {
       char* const dw = ww_lds + dslot * dslot_bytes;
       char* const xw = xring + xslot * xslot_bytes;
       const int u = tid & 3, r0 = tid >> 2;
-      ww_f32x4 e0, e1;
+      f32x4 e0, e1;
       if constexpr (NE > 0) {                              // the leftover k-row's 8 samples of this unit (raw, never split)
-        e0 = ww_lds_read16(xw + e_off + ((2 * u) << 4));
-        e1 = ww_lds_read16(xw + e_off + ((2 * u + 1) << 4));
+        e0 = ww_lds_read16(ww_lds_addr(xw + e_off + ((2 * u) << 4)));
+        e1 = ww_lds_read16(ww_lds_addr(xw + e_off + ((2 * u + 1) << 4)));
       }
-      ww_f32x4 d[2][2], xq[2][2], xm[2][2];
+      f32x4 d[2][2], xq[2][2], xm[2][2];
       char* da[2][2]; char* xa[2][2];
       const int nxu = (p.xr * 4 > 512 + tid) ? 2 : 1;      // k-row units of this thread: rows r0 and (if it exists) 128 + r0
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const int r = r0 + 128 * i;
         da[i][0] = dw + ww_lds_off(r, 2 * u); da[i][1] = dw + ww_lds_off(r, 2 * u + 1);
-        d[i][0] = ww_lds_read16(da[i][0]); d[i][1] = ww_lds_read16(da[i][1]);
+        d[i][0] = ww_lds_read16(ww_lds_addr(da[i][0])); d[i][1] = ww_lds_read16(ww_lds_addr(da[i][1]));
         xa[i][0] = xw + ww_lds_off(r, 2 * u); xa[i][1] = xw + ww_lds_off(r, 2 * u + 1);
         if (i < nxu && r < p.xr) {
-          xq[i][0] = ww_lds_read16(xa[i][0]); xq[i][1] = ww_lds_read16(xa[i][1]);
+          xq[i][0] = ww_lds_read16(ww_lds_addr(xa[i][0])); xq[i][1] = ww_lds_read16(ww_lds_addr(xa[i][1]));
           if constexpr (MUL) {
-            xm[i][0] = ww_lds_read16(xa[i][0] + (p.xr << 7)); xm[i][1] = ww_lds_read16(xa[i][1] + (p.xr << 7));
+            xm[i][0] = ww_lds_read16(ww_lds_addr(xa[i][0] + (p.xr << 7))); xm[i][1] = ww_lds_read16(ww_lds_addr(xa[i][1] + (p.xr << 7)));
           }
         }
       }
@@ -385,13 +375,13 @@ __global__ __launch_bounds__(512, 2) void wn_wgrad_kernel(WwParams p) {
         if constexpr (NE > 0)
           ev[i] += (d[i][0].x * e0.x + d[i][0].y * e0.y) + (d[i][0].z * e0.z + d[i][0].w * e0.w) +
                    (d[i][1].x * e1.x + d[i][1].y * e1.y) + (d[i][1].z * e1.z + d[i][1].w * e1.w);
-        ww_u32x4 h4, l4;
+        u32x4 h4, l4;
         ww_split8u(d[i][0], d[i][1], h4, l4);
-        ww_lds_write16(da[i][0], h4); ww_lds_write16(da[i][1], l4);
+        ww_lds_write16(ww_lds_addr(da[i][0]), h4); ww_lds_write16(ww_lds_addr(da[i][1]), l4);
         if (i < nxu && r < p.xr) {
           if constexpr (MUL) { xq[i][0] *= xm[i][0]; xq[i][1] *= xm[i][1]; }
           ww_split8u(xq[i][0], xq[i][1], h4, l4);
-          ww_lds_write16(xa[i][0], h4); ww_lds_write16(xa[i][1], l4);
+          ww_lds_write16(ww_lds_addr(xa[i][0]), h4); ww_lds_write16(ww_lds_addr(xa[i][1]), l4);
         }
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -400,18 +390,18 @@ __global__ __launch_bounds__(512, 2) void wn_wgrad_kernel(WwParams p) {
     // ---- multiply: fragments are read as they stand (hi = first piece, lo = second piece of the lane's unit)
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      ww_f32x4 araw[MT][2], braw[KT][2];
+      f32x4 araw[MT][2], braw[KT][2];
 #pragma unroll
       for (int i = 0; i < MT; ++i) {
         const char* ap = dsl + a_off + ((i * 32) << 7);
-        araw[i][0] = ww_lds_read16(ap + pc[ks][0]);
-        araw[i][1] = ww_lds_read16(ap + pc[ks][1]);
+        araw[i][0] = ww_lds_read16(ww_lds_addr(ap + pc[ks][0]));
+        araw[i][1] = ww_lds_read16(ww_lds_addr(ap + pc[ks][1]));
       }
 #pragma unroll
       for (int j = 0; j < KT; ++j) {
         const char* bp = xsl + x_off + ((j * 32) << 7);
-        braw[j][0] = ww_lds_read16(bp + pc[ks][0]);
-        braw[j][1] = ww_lds_read16(bp + pc[ks][1]);
+        braw[j][0] = ww_lds_read16(ww_lds_addr(bp + pc[ks][0]));
+        braw[j][1] = ww_lds_read16(ww_lds_addr(bp + pc[ks][1]));
       }
       ww_lds_wait();
       issue_pos(5 * ks);
@@ -422,11 +412,11 @@ __global__ __launch_bounds__(512, 2) void wn_wgrad_kernel(WwParams p) {
         // k-row block, i.e. for every n <= 96 once a workgroup had more than one stage; found by the many-tile small-n cases of
         // test_time_as_k_weight_gradient_kernels)
         if (FULL || wk * KT + j < k_blocks_here) {
-          const ww_bf16x8 bh = __builtin_bit_cast(ww_bf16x8, braw[j][0]), bl = __builtin_bit_cast(ww_bf16x8, braw[j][1]);
+          const bf16x8 bh = __builtin_bit_cast(bf16x8, braw[j][0]), bl = __builtin_bit_cast(bf16x8, braw[j][1]);
 #pragma unroll
           for (int i = 0; i < MT; ++i) {
             if (!FULL && wm * MT + i >= m_blocks) break;   // wave-uniform
-            const ww_bf16x8 ah = __builtin_bit_cast(ww_bf16x8, araw[i][0]), al = __builtin_bit_cast(ww_bf16x8, araw[i][1]);
+            const bf16x8 ah = __builtin_bit_cast(bf16x8, araw[i][0]), al = __builtin_bit_cast(bf16x8, araw[i][1]);
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[i][j], 0, 0, 0);
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[i][j], 0, 0, 0);
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[i][j], 0, 0, 0);
@@ -533,7 +523,6 @@ __global__ __launch_bounds__(256) void wn_wgrad_reduce_kernel(WwParams p) {
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static inline bool ww_al16(const void* q) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 // geometry shared by the size query and the launchers; kind 0 = in_layer + cond_layer, 1 = res_skip
 static int ww_geometry(int kind, int B, int L, int n, int h, int last, int n_sets, WwParams* p) {
@@ -611,7 +600,7 @@ extern "C" int fst_wn_wgrad_in(const float* const* dg, const float* const* a, co
               "n < 128, h <= 32, and dil %% 4 == 0 or — with 16 readable bytes either side of a — dil < 4)", B, L, n, h, dil);
   FST_REQUIRE((long long)B * n * L == (long long)numel_a, "fst_wn_wgrad_in: B*n*L does not match the element count %lld of a", (long long)numel_a);
   FST_REQUIRE(B == 1 || u0_bs >= (int64_t)h * L, "fst_wn_wgrad_in: u0 batch stride %lld < h*L", (long long)u0_bs);
-  FST_REQUIRE(u0_bs % 4 == 0 && ww_al16(workspace), "fst_wn_wgrad_in: operands must be 16-byte aligned");
+  FST_REQUIRE(u0_bs % 4 == 0 && fst_aligned16(workspace), "fst_wn_wgrad_in: operands must be 16-byte aligned");
   WwParams p = {};
   const int KT = ww_geometry(0, B, L, n, h, 0, n_sets, &p);
   FST_REQUIRE(workspace_floats >= (int64_t)p.ksplit * WW_MROWS * (p.Kcols + 2), "fst_wn_wgrad_in: workspace of %lld floats is too small",
@@ -623,7 +612,7 @@ extern "C" int fst_wn_wgrad_in(const float* const* dg, const float* const* a, co
   p.x[3] = {{}, (long long)u0_bs, 0, h, 0, 1, 0, 1, h};
   for (int s = 0; s < n_sets; ++s) {
     FST_REQUIRE(dg[s] && a[s] && u0[s], "fst_wn_wgrad_in: null operand in set %d", s);
-    FST_REQUIRE(ww_al16(dg[s]) && ww_al16(a[s]) && ww_al16(u0[s]), "fst_wn_wgrad_in: operands must be 16-byte aligned");
+    FST_REQUIRE(fst_aligned16(dg[s]) && fst_aligned16(a[s]) && fst_aligned16(u0[s]), "fst_wn_wgrad_in: operands must be 16-byte aligned");
     p.dy[0].ptr[s] = dg[s];
     for (int tap = 0; tap < 3; ++tap) p.x[tap].ptr[s] = a[s];
     p.x[3].ptr[s] = u0[s];
@@ -642,7 +631,7 @@ extern "C" int fst_wn_wgrad_rs(const float* const* d_a, const float* const* d_ou
   FST_REQUIRE(n_sets >= 1 && n_sets <= WW_MAX_SETS, "fst_wn_wgrad_rs: %d operand sets (1..%d)", n_sets, WW_MAX_SETS);
   FST_REQUIRE(fst_wn_wgrad_ok(1, B, L, n, 0, 4), "fst_wn_wgrad_rs: unsupported shape B=%d L=%d n=%d (needs L %% 32 == 0, n < 128)", B, L, n);
   FST_REQUIRE((long long)B * n * L == (long long)numel_a, "fst_wn_wgrad_rs: B*n*L does not match the element count %lld", (long long)numel_a);
-  FST_REQUIRE(ww_al16(workspace), "fst_wn_wgrad_rs: operands must be 16-byte aligned");
+  FST_REQUIRE(fst_aligned16(workspace), "fst_wn_wgrad_rs: operands must be 16-byte aligned");
   WwParams p = {};
   const int KT = ww_geometry(1, B, L, n, 0, last, n_sets, &p);
   FST_REQUIRE(workspace_floats >= (int64_t)p.ksplit * WW_MROWS * (p.Kcols + 2), "fst_wn_wgrad_rs: workspace of %lld floats is too small",
@@ -654,7 +643,7 @@ extern "C" int fst_wn_wgrad_rs(const float* const* d_a, const float* const* d_ou
   p.x[0] = {{}, (long long)2 * n * L, (long long)n * L, n, 0, 0, 0, 1, n};   // t rows; the s rows n·L floats further
   for (int s = 0; s < n_sets; ++s) {
     FST_REQUIRE(d_out[s] && ts[s] && (last || d_a[s]), "fst_wn_wgrad_rs: null operand in set %d", s);
-    FST_REQUIRE(ww_al16(d_out[s]) && ww_al16(ts[s]) && (last || ww_al16(d_a[s])), "fst_wn_wgrad_rs: operands must be 16-byte aligned");
+    FST_REQUIRE(fst_aligned16(d_out[s]) && fst_aligned16(ts[s]) && (last || fst_aligned16(d_a[s])), "fst_wn_wgrad_rs: operands must be 16-byte aligned");
     if (last) p.dy[0].ptr[s] = d_out[s];
     else { p.dy[0].ptr[s] = d_a[s]; p.dy[1].ptr[s] = d_out[s]; }
     p.x[0].ptr[s] = ts[s];
@@ -686,7 +675,7 @@ extern "C" int fst_nt_gemm(const float* A, const float* Bm, float* C, float* wor
   FST_REQUIRE(A && Bm && C && workspace, "fst_nt_gemm: null operand");
   FST_REQUIRE(M > 0 && M <= WW_MROWS && N > 0 && K > 0 && K % WW_TT == 0, "fst_nt_gemm: M=%d N=%d K=%d (needs M <= 256, K %% 32 == 0)", M, N, K);
   FST_REQUIRE((long long)N * K < (1LL << 31) * 4 && (long long)M * N < (1LL << 31), "fst_nt_gemm: operand too large");
-  FST_REQUIRE(ww_al16(A) && ww_al16(Bm) && ww_al16(workspace), "fst_nt_gemm: operands must be 16-byte aligned");
+  FST_REQUIRE(fst_aligned16(A) && fst_aligned16(Bm) && fst_aligned16(workspace), "fst_nt_gemm: operands must be 16-byte aligned");
   FST_REQUIRE((epi_p == nullptr) == (epi_r1 == nullptr) && (epi_p == nullptr || epi_ncls > 0) && (epi_p != nullptr || epi_raw == nullptr),
               "fst_nt_gemm: the epilogue takes p [M][ncls] and r1 [ncls][N] together (and the raw product only with them)");
   WwParams p = {};
@@ -775,7 +764,7 @@ extern "C" int fst_tap_wgrad(const float* dy, const float* x, float* dw, float* 
               "within 3 samples)", B, L, M, C, ntaps, dil, pad_left);
   FST_REQUIRE((long long)B * M * L == (long long)numel_dy && (long long)B * C * L == (long long)numel_x,
               "fst_tap_wgrad: B*M*L / B*C*L do not match the element counts %lld / %lld", (long long)numel_dy, (long long)numel_x);
-  FST_REQUIRE(ww_al16(dy) && ww_al16(x) && ww_al16(workspace), "fst_tap_wgrad: operands must be 16-byte aligned");
+  FST_REQUIRE(fst_aligned16(dy) && fst_aligned16(x) && fst_aligned16(workspace), "fst_tap_wgrad: operands must be 16-byte aligned");
   WwParams p = {};
   tap_geometry(B, L, M, C, ntaps, &p);
   FST_REQUIRE(workspace_floats >= (int64_t)p.ksplit * WW_MROWS * (p.Kcols + 2), "fst_tap_wgrad: workspace of %lld floats is too small",
@@ -823,60 +812,12 @@ struct TzParams {
   int m_halves;                 // 1, or 2: workgroup z takes the rows [128·z, min(M, 128·z + 128))
 };
 
-template <int N>
-__device__ __forceinline__ void tz_wait_at_most() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-#ifdef TZ_STAMPS
-// Diagnostic build only (tools/build_stamps.sh): per-phase s_memtime sums of tz_wgrad_kernel, lane 0 of every wave.
+#ifdef FST_STAMPS
+// per-phase cycle sums of tz_wgrad_kernel, lane 0 of every wave (fst_device.h)
 __device__ unsigned long long tz_stamps[12];
-__device__ __forceinline__ unsigned long long tz_now() {
-  unsigned long long t;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  return t;
-}
-extern "C" int fst_debug_tz_stamps(unsigned long long* out_host, int reset) {
-  if (out_host) hipMemcpyFromSymbol(out_host, HIP_SYMBOL(tz_stamps), sizeof(unsigned long long) * 12);
-  if (reset) { unsigned long long z[12] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(tz_stamps), z, sizeof(z)); }
-  return 0;
-}
-#define TZ_T(var) const unsigned long long var = tz_now()
-#define TZ_ACC(slot, a, b) tz_sum[slot] += (b) - (a)
-#define TZ_SUMS unsigned long long tz_sum[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
-#define TZ_FLUSH \
-  if (lane == 0) for (int i_ = 0; i_ < 12; ++i_) atomicAdd(&tz_stamps[i_], tz_sum[i_])
-#else
-#define TZ_T(var)
-#define TZ_ACC(slot, a, b)
-#define TZ_SUMS
-#define TZ_FLUSH
+extern "C" int fst_debug_tz_stamps(unsigned long long* out_host, int reset) { return fst_read_stamps(tz_stamps, out_host, reset); }
 #endif
 
-// LDS accesses by byte address with the constant part of the address as the instruction's immediate offset: the fragment and
-// split-pass reads of a stage share a handful of per-lane address registers (see the instruction budget below)
-template <int OFF>
-__device__ __forceinline__ ww_f32x4 tz_read16(unsigned addr) {
-  ww_f32x4 v;
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-  return v;
-}
-template <int OFF>
-__device__ __forceinline__ float tz_read4(unsigned addr) {
-  float v;
-  asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-  return v;
-}
-template <int OFF>
-__device__ __forceinline__ void tz_write16(unsigned addr, const ww_u32x4& v) {
-  asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(addr), "v"(v), "n"(OFF) : "memory");
-}
-// one LDS-DMA piece: the 64 lanes' 16 bytes land at LDS byte address m0_addr + 16·lane (M0 saved and restored: see ww_dma16)
-__device__ __forceinline__ void tz_dma16(const char* gsrc, unsigned m0_addr) {
-  unsigned saved_m0;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(saved_m0) : "v"(gsrc), "s"(m0_addr) : "memory");
-}
 
 // INSTRUCTION BUDGET.  With two waves per SIMD a wave issues at most one instruction every four cycles and a taken branch costs
 // tens of cycles: a stage of 36 MFMAs (2 × 1152 cycles of matrix pipe per SIMD) leaves room for ≈300 other instructions per wave.
@@ -896,7 +837,7 @@ __global__ __launch_bounds__(512, 2) void tz_wgrad_kernel(TzParams p) {
   constexpr int X0 = TZ_ND * DSLOT, C0 = X0 + TZ_ND * XSLOT;
   constexpr int XU = (128 * CW) / 512;                     // x copy units per thread (1 or 2): every thread has work
   extern __shared__ __attribute__((aligned(16))) char tz_lds[];
-  const unsigned lds0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)tz_lds);
+  const unsigned lds0 = ww_lds_addr(tz_lds);
   const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
   const int wave_s = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave_s / CW, wk = wave_s % CW;            // row pair, channel of the group
@@ -930,15 +871,15 @@ __global__ __launch_bounds__(512, 2) void tz_wgrad_kernel(TzParams p) {
   auto issue_stage = [&](const Pos& q, int slot) {         // NDW dy pieces, then (waves < CW) the window piece
 #pragma unroll
     for (int k = 0; k < NDW; ++k)
-      tz_dma16(reinterpret_cast<const char*>(dsrc[k] + q.doff), lds0 + slot * DSLOT + (wave_s + 8 * k) * 1024);
+      ww_dma16(reinterpret_cast<const char*>(dsrc[k] + q.doff), lds0 + slot * DSLOT + (wave_s + 8 * k) * 1024);
     if (has_x) {
       const int t = q.t0 + xt;                             // (multiples of 4: a piece is inside the sequence or outside it)
       const char* src = (x_lane && t >= 0 && t < L) ? reinterpret_cast<const char*>(xrow + q.xoff) : zero16;
-      tz_dma16(src, lds0 + X0 + slot * XSLOT + wave_s * TZ_XRAW);
+      ww_dma16(src, lds0 + X0 + slot * XSLOT + wave_s * TZ_XRAW);
     }
   };
   auto wait_keep_one = [&]() {                             // all but the youngest stage's pieces of this wave have landed
-    if (has_x) tz_wait_at_most<NDW + 1>(); else tz_wait_at_most<NDW>();
+    if (has_x) wait_vmcnt<NDW + 1>(); else wait_vmcnt<NDW>();
   };
 
   f32x16 acc[2][3];
@@ -984,32 +925,32 @@ __global__ __launch_bounds__(512, 2) void tz_wgrad_kernel(TzParams p) {
   // the split pass (dy rows in place, the x windows into the OTHER copies buffer) and the pieces of stage c + 3 are issued, in chunks
   // between the MFMA groups.  One barrier per stage.
   const int n_st = tile_end - tile_begin;
-  ww_f32x4 sd0, sd1;
+  f32x4 sd0, sd1;
   float sxv[XU][8];
   auto split_load = [&](unsigned d_slot, unsigned x_slot) {
-    if (dy_thread) { sd0 = tz_read16<0>(d_slot + sd_lane0); sd1 = tz_read16<0>(d_slot + sd_lane1); }
+    if (dy_thread) { sd0 = ww_lds_read16<0>(d_slot + sd_lane0); sd1 = ww_lds_read16<0>(d_slot + sd_lane1); }
 #pragma unroll
     for (int j = 0; j < XU; ++j) {
       const unsigned a = x_slot + sx_src[j];
-      sxv[j][0] = tz_read4<0>(a); sxv[j][1] = tz_read4<4>(a); sxv[j][2] = tz_read4<8>(a); sxv[j][3] = tz_read4<12>(a);
-      sxv[j][4] = tz_read4<16>(a); sxv[j][5] = tz_read4<20>(a); sxv[j][6] = tz_read4<24>(a); sxv[j][7] = tz_read4<28>(a);
+      sxv[j][0] = ww_lds_read4<0>(a); sxv[j][1] = ww_lds_read4<4>(a); sxv[j][2] = ww_lds_read4<8>(a); sxv[j][3] = ww_lds_read4<12>(a);
+      sxv[j][4] = ww_lds_read4<16>(a); sxv[j][5] = ww_lds_read4<20>(a); sxv[j][6] = ww_lds_read4<24>(a); sxv[j][7] = ww_lds_read4<28>(a);
     }
   };
   auto split_dy_store = [&](unsigned d_slot) {
     if (!dy_thread) return;
-    ww_u32x4 h4, l4;
+    u32x4 h4, l4;
     ww_split8u(sd0, sd1, h4, l4);
-    tz_write16<0>(d_slot + sd_lane0, h4); tz_write16<0>(d_slot + sd_lane1, l4);
+    ww_lds_write16<0>(d_slot + sd_lane0, h4); ww_lds_write16<0>(d_slot + sd_lane1, l4);
   };
   auto split_x_store = [&](unsigned cbuf) {
 #pragma unroll
     for (int j = 0; j < XU; ++j) {
-      ww_u32x4 h4, l4;
+      u32x4 h4, l4;
       unsigned hh, ll;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) { ww_split_pair(sxv[j][2 * e], sxv[j][2 * e + 1], hh, ll); h4[e] = hh; l4[e] = ll; }
-      tz_write16<0>(cbuf + sx_dst[j], h4);
-      tz_write16<LO>(cbuf + sx_dst[j], l4);
+      for (int e = 0; e < 4; ++e) { split_bf16_pair(sxv[j][2 * e], sxv[j][2 * e + 1], hh, ll); h4[e] = hh; l4[e] = ll; }
+      ww_lds_write16<0>(cbuf + sx_dst[j], h4);
+      ww_lds_write16<LO>(cbuf + sx_dst[j], l4);
     }
   };
 
@@ -1030,23 +971,23 @@ __global__ __launch_bounds__(512, 2) void tz_wgrad_kernel(TzParams p) {
   // right after that barrier, under the MFMAs of k-step 1 of stage c; those of k-step 1 at the top of the stage, under the MFMAs of
   // k-step 0.  (Stamps of the form with the barrier at the top: the issue of the 20 LDS reads behind it took 20 % of a wave's stage —
   // all eight waves read at once and nobody could multiply yet — the barrier 13 %, profiles/r04_tz_stamps.txt.)
-  ww_f32x4 araw[2][2][2], braw[2][3][2];
+  f32x4 araw[2][2][2], braw[2][3][2];
   auto frag_reads = [&](auto ks_c, unsigned d_slot, unsigned cbuf) {
     constexpr int ks = decltype(ks_c)::value;
-    araw[ks][0][0] = tz_read16<0>(d_slot + a_lane[ks][0]);    araw[ks][0][1] = tz_read16<0>(d_slot + a_lane[ks][1]);
-    araw[ks][1][0] = tz_read16<4096>(d_slot + a_lane[ks][0]); araw[ks][1][1] = tz_read16<4096>(d_slot + a_lane[ks][1]);
+    araw[ks][0][0] = ww_lds_read16<0>(d_slot + a_lane[ks][0]);    araw[ks][0][1] = ww_lds_read16<0>(d_slot + a_lane[ks][1]);
+    araw[ks][1][0] = ww_lds_read16<4096>(d_slot + a_lane[ks][0]); araw[ks][1][1] = ww_lds_read16<4096>(d_slot + a_lane[ks][1]);
     const unsigned bb = cbuf + b_lane;
-    braw[ks][0][0] = tz_read16<((2 * ks) << 4)>(bb);      braw[ks][0][1] = tz_read16<((2 * ks) << 4) + LO>(bb);
-    braw[ks][1][0] = tz_read16<((2 * ks + 4) << 4)>(bb);  braw[ks][1][1] = tz_read16<((2 * ks + 4) << 4) + LO>(bb);
-    braw[ks][2][0] = tz_read16<((2 * ks + 8) << 4)>(bb);  braw[ks][2][1] = tz_read16<((2 * ks + 8) << 4) + LO>(bb);
+    braw[ks][0][0] = ww_lds_read16<((2 * ks) << 4)>(bb);      braw[ks][0][1] = ww_lds_read16<((2 * ks) << 4) + LO>(bb);
+    braw[ks][1][0] = ww_lds_read16<((2 * ks + 4) << 4)>(bb);  braw[ks][1][1] = ww_lds_read16<((2 * ks + 4) << 4) + LO>(bb);
+    braw[ks][2][0] = ww_lds_read16<((2 * ks + 8) << 4)>(bb);  braw[ks][2][1] = ww_lds_read16<((2 * ks + 8) << 4) + LO>(bb);
   };
   auto mfma_group = [&](int ks, int sb) {
     if (FULL || (sb < k_blocks && ch_live)) {              // wave-uniform
-      const ww_bf16x8 bh = __builtin_bit_cast(ww_bf16x8, braw[ks][sb][0]), bl = __builtin_bit_cast(ww_bf16x8, braw[ks][sb][1]);
+      const bf16x8 bh = __builtin_bit_cast(bf16x8, braw[ks][sb][0]), bl = __builtin_bit_cast(bf16x8, braw[ks][sb][1]);
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         if (!FULL && wm * 2 + i >= m_blocks) break;        // wave-uniform
-        const ww_bf16x8 ah = __builtin_bit_cast(ww_bf16x8, araw[ks][i][0]), al = __builtin_bit_cast(ww_bf16x8, araw[ks][i][1]);
+        const bf16x8 ah = __builtin_bit_cast(bf16x8, araw[ks][i][0]), al = __builtin_bit_cast(bf16x8, araw[ks][i][1]);
         acc[i][sb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[i][sb], 0, 0, 0);
         acc[i][sb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[i][sb], 0, 0, 0);
         acc[i][sb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[i][sb], 0, 0, 0);
@@ -1054,8 +995,8 @@ __global__ __launch_bounds__(512, 2) void tz_wgrad_kernel(TzParams p) {
     }
     __builtin_amdgcn_sched_barrier(0);
   };
-  TZ_SUMS;
-  TZ_T(tz_begin);
+  FST_SUMS(12);
+  FST_T(tz_begin);
   if (n_st > 0) {
     issue_next(0);
     issue_next(1);
@@ -1075,56 +1016,56 @@ __global__ __launch_bounds__(512, 2) void tz_wgrad_kernel(TzParams p) {
     const int s_next = (slot + 1) & (TZ_ND - 1), s_dma = (slot + 3) & (TZ_ND - 1);   // c + 3 goes where multiply(c − 1) read
     const unsigned d_cur = lds0 + slot * DSLOT, d_nxt = lds0 + s_next * DSLOT, x_nxt = lds0 + X0 + s_next * XSLOT;
     const unsigned c_cur = lds0 + C0 + cb * COPIES, c_nxt = lds0 + C0 + (cb ^ 1) * COPIES;
-    TZ_T(ta);
+    FST_T(ta);
     ww_lds_wait();                                         // the k-step-0 fragments (read under the previous stage's last MFMAs)
-    TZ_T(tb);
-    TZ_ACC(0, ta, tb);                                     // wait for the k-step-0 fragments
+    FST_T(tb);
+    FST_ACC(0, ta, tb);                                    // wait for the k-step-0 fragments
     frag_reads(std::integral_constant<int, 1>{}, d_cur, c_cur);
     split_load(d_nxt, x_nxt);                              // stage c + 1 landed before the previous barrier (virtual past the end)
-    TZ_T(tc);
-    TZ_ACC(2, tb, tc);                                     // issue of the k-step-1 fragment reads + split reads
+    FST_T(tc);
+    FST_ACC(2, tb, tc);                                    // issue of the k-step-1 fragment reads + split reads
     mfma_group(0, 0);
-    TZ_T(td);
-    TZ_ACC(4, tc, td);                                     // MFMA group (0, 0)
+    FST_T(td);
+    FST_ACC(4, tc, td);                                    // MFMA group (0, 0)
     ww_lds_wait();
-    TZ_T(te);
-    TZ_ACC(3, td, te);                                     // wait for those reads
+    FST_T(te);
+    FST_ACC(3, td, te);                                    // wait for those reads
     split_dy_store(d_nxt);
     __builtin_amdgcn_sched_barrier(0);
-    TZ_T(tf);
-    TZ_ACC(5, te, tf);                                     // dy split
+    FST_T(tf);
+    FST_ACC(5, te, tf);                                    // dy split
     mfma_group(0, 1);
-    TZ_T(tg);
-    TZ_ACC(4, tf, tg);
+    FST_T(tg);
+    FST_ACC(4, tf, tg);
     split_x_store(c_nxt);                                  // (its stores complete under the group below)
     __builtin_amdgcn_sched_barrier(0);
-    TZ_T(th);
-    TZ_ACC(7, tg, th);                                     // x split
+    FST_T(th);
+    FST_ACC(7, tg, th);                                    // x split
     mfma_group(0, 2);
-    TZ_T(ti);
-    TZ_ACC(4, th, ti);
+    FST_T(ti);
+    FST_ACC(4, th, ti);
     issue_next(s_dma);                                     // this wave's pieces of stage c + 3
-    TZ_T(tj);
-    TZ_ACC(6, ti, tj);                                     // LDS-DMA issue
+    FST_T(tj);
+    FST_ACC(6, ti, tj);                                    // LDS-DMA issue
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // this wave's split stores of stage c + 1 are done ...
     wait_keep_one();                                       // ... and its pieces of stage c + 2 have landed (c + 3 may still fly)
-    TZ_T(tk);
-    TZ_ACC(8, tj, tk);                                     // waits in front of the barrier
+    FST_T(tk);
+    FST_ACC(8, tj, tk);                                    // waits in front of the barrier
     __builtin_amdgcn_s_barrier();                          // split(c + 1) is visible; everyone is past its reads of stage c
-    TZ_T(tl);
-    TZ_ACC(1, tk, tl);                                     // barrier
+    FST_T(tl);
+    FST_ACC(1, tk, tl);                                    // barrier
     frag_reads(std::integral_constant<int, 0>{}, d_nxt, c_nxt);     // k-step 0 of stage c + 1, under the MFMAs below
     mfma_group(1, 0);
     mfma_group(1, 1);
     mfma_group(1, 2);
-    TZ_T(tm);
-    TZ_ACC(9, tl, tm);                                     // fragment reads of the next stage + MFMA groups of k-step 1
+    FST_T(tm);
+    FST_ACC(9, tl, tm);                                    // fragment reads of the next stage + MFMA groups of k-step 1
     slot = s_next;
     cb ^= 1;
   }
-  TZ_T(tz_end);
-  TZ_ACC(10, tz_begin, tz_end);                            // whole loop
-  TZ_FLUSH;
+  FST_T(tz_end);
+  FST_ACC(10, tz_begin, tz_end);                           // whole loop
+  FST_FLUSH(tz_stamps);
   // (virtual pieces may still be in flight: they target LDS only, and the wave's end waits for them)
 
   float* const slab = p.slab + (long long)blockIdx.x * WW_MROWS * p.Kcols;
@@ -1193,7 +1134,7 @@ extern "C" int fst_dense_tap_wgrad(const float* dy, const float* x, float* dw, f
               "(needs L %% 32 == 0, M <= 256, 4 < K <= 96, 0 <= pad_left < K)", B, L, M, C, K, pad_left);
   FST_REQUIRE((long long)B * M * L == (long long)numel_dy && (long long)B * C * L == (long long)numel_x,
               "fst_dense_tap_wgrad: B*M*L / B*C*L do not match the element counts %lld / %lld", (long long)numel_dy, (long long)numel_x);
-  FST_REQUIRE(ww_al16(dy) && ww_al16(x) && ww_al16(workspace), "fst_dense_tap_wgrad: operands must be 16-byte aligned");
+  FST_REQUIRE(fst_aligned16(dy) && fst_aligned16(x) && fst_aligned16(workspace), "fst_dense_tap_wgrad: operands must be 16-byte aligned");
   TzParams p = {};
   const int MP = tz_geometry(B, L, M, C, K, pad_left, &p);
   FST_REQUIRE(workspace_floats >= (int64_t)p.ksplit * WW_MROWS * p.Kcols, "fst_dense_tap_wgrad: workspace of %lld floats is too small",

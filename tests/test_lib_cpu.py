@@ -97,3 +97,23 @@ def test_dense_products_refuse_what_the_kernel_does_not_serve():
     assert torch.equal(ops.linear_act(x, lin, ops.ACT_LEAKY, 0.2), want)          # CPU tensors: the framework's composition
     assert torch.equal(ops.linear_act(x, lin, ops.ACT_RELU), torch.relu(lin(x)))
     assert torch.equal(ops.linear_act(x, lin), lin(x))
+
+
+def test_split_and_staging_primitives_are_defined_once():
+    """The split-bf16 product every parity tolerance assumes, and the staging pieces around it, live in csrc/fst_device.h
+    alone: a kernel file that converts to bf16 itself or redefines one of them could drift from the others unnoticed."""
+    import glob
+    csrc = os.path.join(ROOT, "feature_level_style_transfer_for_tsc_amd", "csrc")
+    paths = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
+    assert os.path.join(csrc, "fst_device.h") in paths
+    defined = re.compile(r"(?:\bvoid\s+(\w*split\w*_pair|\w*wait_vmcnt|tz_wait_at_most)\s*\(|"
+                         r"#\s*define\s+(\w*_GLOBAL_PTR|\w*_LDS_VOID)\b)")
+    stray = []
+    for path in paths:
+        name = os.path.basename(path)
+        text = open(path).read()
+        if name != "fst_device.h" and "__builtin_convertvector" in text:
+            stray.append(f"{name}: __builtin_convertvector")
+        if name.endswith(".hip"):
+            stray += [f"{name}: {a or b}" for a, b in defined.findall(text)]
+    assert not stray, stray
