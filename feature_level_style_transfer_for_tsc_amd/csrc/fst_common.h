@@ -60,5 +60,11 @@ static inline int plan_expected_len(const int32_t* p) {
 int fst_allow_full_lds(const void* fn, const char* who);
 int fst_cu_count(void);   // compute units of the current device (0 if the query fails)
 
+// Launch-route record of the time-as-k weight gradients and the fused WN kernels (fst_wn_last_route; storage in wn_wgrad.hip,
+// thread-local, host side only).  A launcher clears it on entry (family 0) and fills it from its own dispatch variables right
+// before its hipLaunchKernelGGL: t1..t4 the template arguments, gx / gy / gz the grid, a8..a10 and lds as fst_hip.h lists them.
+void fst_wn_set_route(int family, int t1, int t2, int t3, int t4, int gx, int gy, int gz, int a8, int a9, int a10, int lds);
+static inline void fst_wn_clear_route(void) { fst_wn_set_route(0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0); }
+
 // Host-side sanity check of a plan against the tensor shapes a launch will touch.
 int fst_check_plan(const int32_t* plan_host, int plan_len, int M, const char* who);

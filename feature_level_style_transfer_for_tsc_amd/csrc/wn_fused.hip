@@ -706,6 +706,7 @@ extern "C" int fst_wn_stack_fwd_ok(int n, int h, int L, int nl) {
 extern "C" int fst_wn_stack_fwd(const float* const* a_in, const int64_t* a_bs, const void* const* images, int64_t image_bytes,
                                 float* const* ts, float* const* a_next, const float* u0, int64_t u0_bs, float* out, int nl, int B,
                                 int L, int n, int h, int64_t numel_a, void* stream) {
+  fst_wn_clear_route();
   FST_REQUIRE(a_in && a_bs && images && ts && a_next && u0 && out, "fst_wn_stack_fwd: null operand");
   FST_REQUIRE(fst_wn_stack_fwd_ok(n, h, L, nl) && B > 0, "fst_wn_stack_fwd: B=%d L=%d n=%d h=%d nl=%d (needs n < 128, L %% 256 == 0, "
               "1 <= nl <= %d)", B, L, n, h, nl, WS_MAXL);
@@ -732,6 +733,7 @@ extern "C" int fst_wn_stack_fwd(const float* const* a_in, const int64_t* a_bs, c
   p.nl = nl;
   const int cus = fst_cu_count() > 0 ? fst_cu_count() : 256;
   if (int rc = fst_allow_full_lds((const void*)wn_stack_fwd_kernel, "fst_wn_stack_fwd")) return rc;
+  fst_wn_set_route(FST_WN_ROUTE_STACK_FWD, 8, 0, 0, 0, B < cus ? B : cus, 1, 1, L / 256, 3, nl, WN_FWD_LDS(8));
   hipLaunchKernelGGL(wn_stack_fwd_kernel, dim3((unsigned)(B < cus ? B : cus)), dim3(512), WN_FWD_LDS(8), (hipStream_t)stream, p);
   FST_LAUNCH_CHECK();
   return 0;
@@ -740,6 +742,7 @@ extern "C" int fst_wn_stack_fwd(const float* const* a_in, const int64_t* a_bs, c
 extern "C" int fst_wn_layer_fwd(const float* a, int64_t a_bs, const float* u0, int64_t u0_bs, const void* image,
                                 int64_t image_bytes, float* ts, float* acts, float* a_next, float* out, int first, int last,
                                 int B, int L, int n, int h, int dil, int64_t numel_a, void* stream) {
+  fst_wn_clear_route();
   FST_REQUIRE(a && u0 && image && ts && out && (last || a_next), "fst_wn_layer_fwd: null operand");
   FST_REQUIRE(B > 0 && L > 0 && n > 0 && n < 128 && h > 0 && dil > 0, "fst_wn_layer_fwd: B=%d L=%d n=%d h=%d dil=%d (needs n < 128)",
               B, L, n, h, dil);
@@ -763,9 +766,11 @@ extern "C" int fst_wn_layer_fwd(const float* a, int64_t a_bs, const float* u0, i
   p.n_wg = B * p.tiles_per_seq;
   if (nw == 8) {
     if (int rc = fst_allow_full_lds((const void*)wn_layer_fwd_kernel<8>, "fst_wn_layer_fwd")) return rc;
+    fst_wn_set_route(FST_WN_ROUTE_LAYER_FWD, 8, 0, 0, 0, p.n_wg, 1, 1, p.tiles_per_seq, 3, 1, WN_FWD_LDS(8));
     hipLaunchKernelGGL(wn_layer_fwd_kernel<8>, dim3((unsigned)p.n_wg), dim3(512), WN_FWD_LDS(8), (hipStream_t)stream, p);
   } else {
     if (int rc = fst_allow_full_lds((const void*)wn_layer_fwd_kernel<4>, "fst_wn_layer_fwd")) return rc;
+    fst_wn_set_route(FST_WN_ROUTE_LAYER_FWD, 4, 0, 0, 0, p.n_wg, 1, 1, p.tiles_per_seq, 3, 1, WN_FWD_LDS(4));
     hipLaunchKernelGGL(wn_layer_fwd_kernel<4>, dim3((unsigned)p.n_wg), dim3(256), WN_FWD_LDS(4), (hipStream_t)stream, p);
   }
   FST_LAUNCH_CHECK();
@@ -973,6 +978,7 @@ __global__ __launch_bounds__(256, WN_BWD_OCC) void wn_layer_bwd_kernel(WnBwdPara
 extern "C" int fst_wn_layer_bwd(const float* d_a, const float* d_out, const float* ts, const void* image, int64_t image_bytes,
                                 float* dg, float* row_sums, int64_t row_sums_rows, int last, int B, int L, int n,
                                 int64_t numel_a, void* stream) {
+  fst_wn_clear_route();
   FST_REQUIRE(d_out && ts && image && dg && (last || d_a), "fst_wn_layer_bwd: null operand");
   FST_REQUIRE(B > 0 && L > 0 && n > 0 && n <= 128, "fst_wn_layer_bwd: B=%d L=%d n=%d (needs n <= 128)", B, L, n);
   FST_REQUIRE((long long)B * n * L == (long long)numel_a, "fst_wn_layer_bwd: B*n*L = %d*%d*%d does not match the element count %lld "
@@ -990,6 +996,7 @@ extern "C" int fst_wn_layer_bwd(const float* d_a, const float* d_out, const floa
   FST_REQUIRE(row_sums == nullptr || row_sums_rows == p.n_wg, "fst_wn_layer_bwd: row_sums has %lld rows, the launch has %d "
               "workgroups (B x ceil(L/128))", (long long)row_sums_rows, p.n_wg);
   if (int rc = fst_allow_full_lds((const void*)wn_layer_bwd_kernel, "fst_wn_layer_bwd")) return rc;
+  fst_wn_set_route(FST_WN_ROUTE_LAYER_BWD, 0, 0, 0, 0, p.n_wg, 1, 1, p.tiles_per_seq, 3, 1, WN_BW_LDS);
   hipLaunchKernelGGL(wn_layer_bwd_kernel, dim3((unsigned)p.n_wg), dim3(256), WN_BW_LDS, (hipStream_t)stream, p);
   FST_LAUNCH_CHECK();
   return 0;
@@ -1006,7 +1013,8 @@ extern "C" int fst_wn_layer_bwd(const float* d_a, const float* d_out, const floa
 //   * a workgroup = 8 waves = one batch element × 256 time samples (each wave 32 samples × 5 row blocks): the weight bytes
 //     per output sample are half those of a 128-sample tile.
 // Image: per 16-channel chunk 13 row blocks × (1 KiB hi + 1 KiB lo): [tap 0: 4 blocks of d_a rows][tap 1: 4 + the d_u0 block]
-// [tap 2: 4]; tap τ multiplies dg at t + (1 − τ)·dil.  Ring of 3 slots (2 when the window of a large dilation needs the room).
+// [tap 2: 4]; tap τ multiplies dg at t + (1 − τ)·dil.  Ring of 2 slots: the launcher takes 3 when they fit 160 KiB, but with
+// 512-sample tiles a slot is 61 696 bytes at dilation 1 and grows with the dilation, so they never do (ns of fst_wn_last_route).
 // ------------------------------------------------------------------------------------------------
 #define DG_NCB 2                                     // 32-sample column blocks per wave
 #define DG_TN (8 * 32 * DG_NCB)                       // time samples per workgroup (8 waves)
@@ -1080,7 +1088,7 @@ struct WnDgradParams {
   int nblkw;            // 32-sample column blocks of the window
   int gsw;              // bytes per 8-channel row group of the window
   int slot;             // bytes per ring slot
-  int ns;               // ring slots (3, or 2 for wide windows)
+  int ns;               // ring slots (3 if they fit the LDS, else 2; with DG_TN = 512 always 2)
 };
 
 template <int N>
@@ -1269,6 +1277,7 @@ extern "C" int fst_wn_dgrad_fits(int n, int h, int dil) {
 extern "C" int fst_wn_layer_dgrad(const float* dg, const void* image, int64_t image_bytes, const float* d_a, float* d_a_new,
                                   float* d_u0, float* row_sums, int64_t row_sums_rows, int B, int L, int n, int h, int dil,
                                   int64_t numel_a, int64_t d_u0_bs, void* stream) {
+  fst_wn_clear_route();
   FST_REQUIRE(dg && image && d_a_new && d_u0, "fst_wn_layer_dgrad: null operand");
   FST_REQUIRE(B > 0 && L > 0 && n > 0 && n <= 128 && h > 0 && h <= 32 && dil > 0, "fst_wn_layer_dgrad: B=%d L=%d n=%d h=%d dil=%d", B, L,
               n, h, dil);
@@ -1300,6 +1309,7 @@ extern "C" int fst_wn_layer_dgrad(const float* dg, const void* image, int64_t im
   int grid = p.n_wg;
   const int cus = fst_cu_count();
   if (cus > 0 && grid > cus && (size_t)2 * lds_bytes > 160 * 1024) grid = cus;
+  fst_wn_set_route(FST_WN_ROUTE_LAYER_DGRAD, 0, 0, 0, 0, grid, 1, 1, p.tiles_per_seq, p.ns, 1, (int)lds_bytes);
   hipLaunchKernelGGL(wn_layer_dgrad_kernel, dim3((unsigned)grid), dim3(512), lds_bytes, (hipStream_t)stream, p);
   FST_LAUNCH_CHECK();
   return 0;
@@ -1706,6 +1716,7 @@ extern "C" int fst_wn_stack_bwd_ok(int n, int h, int L, int nl) {
 extern "C" int fst_wn_stack_bwd(const float* const* ts, const void* const* img_b, const void* const* img_d, float* const* dg,
                                 float* const* da_out, float* const* rs_b, float* const* rs_d, const float* d_out, float* d_u0,
                                 int64_t d_u0_bs, int nl, int B, int L, int n, int h, int64_t numel_a, void* stream) {
+  fst_wn_clear_route();
   FST_REQUIRE(ts && img_b && img_d && dg && da_out && d_out && d_u0, "fst_wn_stack_bwd: null table");
   FST_REQUIRE(fst_wn_stack_bwd_ok(n, h, L, nl), "fst_wn_stack_bwd: not served: n=%d h=%d L=%d nl=%d (needs n <= 128, h <= 32, "
               "L <= 512, L %% 4 == 0, nl <= %d)", n, h, L, nl, WS_MAXL);
@@ -1734,6 +1745,7 @@ extern "C" int fst_wn_stack_bwd(const float* const* ts, const void* const* img_b
   if (int rc = fst_allow_full_lds((const void*)wn_stack_bwd_kernel, "fst_wn_stack_bwd")) return rc;
   const int cus = fst_cu_count() > 0 ? fst_cu_count() : 256;
   const int grid = B < cus ? B : cus;                    // one resident workgroup per CU walks its batch elements
+  fst_wn_set_route(FST_WN_ROUTE_STACK_BWD, 0, 0, 0, 0, grid, 1, 1, 1, 2, nl, (int)lds_bytes);
   hipLaunchKernelGGL(wn_stack_bwd_kernel, dim3((unsigned)grid), dim3(512), lds_bytes, (hipStream_t)stream, p);
   FST_LAUNCH_CHECK();
   return 0;

@@ -524,6 +524,20 @@ __global__ __launch_bounds__(256) void wn_wgrad_reduce_kernel(WwParams p) {
 
 // ------------------------------------------------------------------------------------------------ host side
 
+// what the last launcher of this file or of wn_fused.hip launched on this host thread (fst_wn_last_route)
+static thread_local int32_t g_wn_route[FST_WN_ROUTE_LEN] = {0};
+
+void fst_wn_set_route(int family, int t1, int t2, int t3, int t4, int gx, int gy, int gz, int a8, int a9, int a10, int lds) {
+  const int32_t r[FST_WN_ROUTE_LEN] = {family, t1, t2, t3, t4, gx, gy, gz, a8, a9, a10, lds};
+  for (int i = 0; i < FST_WN_ROUTE_LEN; ++i) g_wn_route[i] = r[i];
+}
+
+extern "C" int fst_wn_last_route(int32_t out[FST_WN_ROUTE_LEN]) {
+  FST_REQUIRE(out != nullptr, "fst_wn_last_route: null output");
+  for (int i = 0; i < FST_WN_ROUTE_LEN; ++i) out[i] = g_wn_route[i];
+  return g_wn_route[0] != 0 ? 0 : -1;
+}
+
 // geometry shared by the size query and the launchers; kind 0 = in_layer + cond_layer, 1 = res_skip
 static int ww_geometry(int kind, int B, int L, int n, int h, int last, int n_sets, WwParams* p) {
   const int KT = kind == 0 ? 3 : 2;
@@ -582,6 +596,7 @@ static int ww_launch(WwParams& p, int KT, void* stream, bool reduce = true) {
     fn = full ? wn_wgrad_kernel<2, 2, true, false, 0> : wn_wgrad_kernel<2, 2, false, false, 0>;
   }
   if (int rc = fst_allow_full_lds((const void*)fn, "fst_wn_wgrad")) return rc;
+  fst_wn_set_route(FST_WN_ROUTE_WGRAD, KT, (int)full, p.mul, p.n_extra, p.ksplit, p.n_groups, 1, p.n_sets, p.misaligned, (int)reduce, (int)lds);
   hipLaunchKernelGGL(fn, dim3((unsigned)p.ksplit, (unsigned)p.n_groups), dim3(512), lds, (hipStream_t)stream, p);
   FST_LAUNCH_CHECK();
   if (!reduce) return 0;
@@ -593,6 +608,7 @@ static int ww_launch(WwParams& p, int KT, void* stream, bool reduce = true) {
 extern "C" int fst_wn_wgrad_in(const float* const* dg, const float* const* a, const float* const* u0, int n_sets, int64_t u0_bs,
                                float* dw_in, float* dw_cond, float* workspace, int64_t workspace_floats, int B, int L, int n, int h,
                                int dil, int a_slack, int64_t numel_a, void* stream) {
+  fst_wn_clear_route();
   FST_REQUIRE(dg && a && u0 && dw_in && dw_cond && workspace, "fst_wn_wgrad_in: null operand");
   FST_REQUIRE(n_sets >= 1 && n_sets <= WW_MAX_SETS, "fst_wn_wgrad_in: %d operand sets (1..%d)", n_sets, WW_MAX_SETS);
   const int served = fst_wn_wgrad_ok(0, B, L, n, h, dil);
@@ -627,6 +643,7 @@ extern "C" int fst_wn_wgrad_in(const float* const* dg, const float* const* a, co
 extern "C" int fst_wn_wgrad_rs(const float* const* d_a, const float* const* d_out, const float* const* ts, int n_sets, float* dw_rs,
                                float* workspace, int64_t workspace_floats, int last, int B, int L, int n, int64_t numel_a,
                                void* stream) {
+  fst_wn_clear_route();
   FST_REQUIRE(d_out && ts && dw_rs && workspace && (last || d_a), "fst_wn_wgrad_rs: null operand");
   FST_REQUIRE(n_sets >= 1 && n_sets <= WW_MAX_SETS, "fst_wn_wgrad_rs: %d operand sets (1..%d)", n_sets, WW_MAX_SETS);
   FST_REQUIRE(fst_wn_wgrad_ok(1, B, L, n, 0, 4), "fst_wn_wgrad_rs: unsupported shape B=%d L=%d n=%d (needs L %% 32 == 0, n < 128)", B, L, n);
@@ -672,6 +689,7 @@ extern "C" int64_t fst_nt_gemm_workspace_floats(int M, int N, int K) {
 
 extern "C" int fst_nt_gemm(const float* A, const float* Bm, float* C, float* workspace, int64_t workspace_floats, int M, int N, int K,
                            const float* epi_p, const float* epi_r1, int epi_ncls, float epi_scale, float* epi_raw, void* stream) {
+  fst_wn_clear_route();
   FST_REQUIRE(A && Bm && C && workspace, "fst_nt_gemm: null operand");
   FST_REQUIRE(M > 0 && M <= WW_MROWS && N > 0 && K > 0 && K % WW_TT == 0, "fst_nt_gemm: M=%d N=%d K=%d (needs M <= 256, K %% 32 == 0)", M, N, K);
   FST_REQUIRE((long long)N * K < (1LL << 31) * 4 && (long long)M * N < (1LL << 31), "fst_nt_gemm: operand too large");
@@ -757,6 +775,7 @@ extern "C" int64_t fst_tap_wgrad_workspace_floats(int B, int L, int M, int C, in
 
 extern "C" int fst_tap_wgrad(const float* dy, const float* x, float* dw, float* workspace, int64_t workspace_floats, int B, int L, int M,
                              int C, int ntaps, int dil, int pad_left, int x_slack, int64_t numel_dy, int64_t numel_x, void* stream) {
+  fst_wn_clear_route();
   FST_REQUIRE(dy && x && dw && workspace, "fst_tap_wgrad: null operand");
   const int served = fst_tap_wgrad_ok(B, L, M, C, ntaps, dil, pad_left);
   FST_REQUIRE(served == 1 || (served == 2 && x_slack), "fst_tap_wgrad: unsupported shape B=%d L=%d M=%d C=%d ntaps=%d dil=%d pad_left=%d "
@@ -1129,6 +1148,7 @@ extern "C" int64_t fst_dense_tap_wgrad_workspace_floats(int B, int L, int M, int
 
 extern "C" int fst_dense_tap_wgrad(const float* dy, const float* x, float* dw, float* workspace, int64_t workspace_floats, int B, int L,
                                    int M, int C, int K, int pad_left, int64_t numel_dy, int64_t numel_x, void* stream) {
+  fst_wn_clear_route();
   FST_REQUIRE(dy && x && dw && workspace, "fst_dense_tap_wgrad: null operand");
   FST_REQUIRE(fst_dense_tap_wgrad_ok(B, L, M, C, K, pad_left), "fst_dense_tap_wgrad: unsupported shape B=%d L=%d M=%d C=%d K=%d pad_left=%d "
               "(needs L %% 32 == 0, M <= 256, 4 < K <= 96, 0 <= pad_left < K)", B, L, M, C, K, pad_left);
@@ -1148,6 +1168,7 @@ extern "C" int fst_dense_tap_wgrad(const float* dy, const float* x, float* dw, f
   void (*fn)(TzParams) = MP == 1 ? (full ? tz_wgrad_kernel<1, true> : tz_wgrad_kernel<1, false>)
                                  : (full ? tz_wgrad_kernel<2, true> : tz_wgrad_kernel<2, false>);
   if (int rc = fst_allow_full_lds((const void*)fn, "fst_dense_tap_wgrad")) return rc;
+  fst_wn_set_route(FST_WN_ROUTE_TZ, MP, (int)full, 0, 0, p.ksplit, p.n_groups, p.m_halves, 1, 0, 1, (int)lds);
   hipLaunchKernelGGL(fn, dim3((unsigned)p.ksplit, (unsigned)p.n_groups, (unsigned)p.m_halves), dim3(512), lds, (hipStream_t)stream, p);
   FST_LAUNCH_CHECK();
   hipLaunchKernelGGL(tz_reduce_kernel, dim3((unsigned)((p.C * 96 + 255) / 256), (unsigned)M), dim3(256), 0, (hipStream_t)stream, p);

@@ -77,6 +77,35 @@ def last_route() -> Tuple[int, ...]:
     return tuple(out)
 
 
+WN_ROUTE_WGRAD, WN_ROUTE_TZ, WN_ROUTE_LAYER_FWD, WN_ROUTE_STACK_FWD, WN_ROUTE_LAYER_BWD, WN_ROUTE_LAYER_DGRAD, WN_ROUTE_STACK_BWD = \
+    1, 2, 3, 4, 5, 6, 7                                                                              # FST_WN_ROUTE_* of fst_hip.h
+WN_ROUTE_LEN = 12
+_WN_ROUTE_NAMES = {WN_ROUTE_WGRAD: "wn_wgrad_kernel", WN_ROUTE_TZ: "tz_wgrad_kernel", WN_ROUTE_LAYER_FWD: "wn_layer_fwd_kernel",
+                   WN_ROUTE_STACK_FWD: "wn_stack_fwd_kernel", WN_ROUTE_LAYER_BWD: "wn_layer_bwd_kernel",
+                   WN_ROUTE_LAYER_DGRAD: "wn_layer_dgrad_kernel", WN_ROUTE_STACK_BWD: "wn_stack_bwd_kernel"}
+
+
+def wn_last_route() -> Tuple[int, ...]:
+    """fst_wn_last_route: (family, 4 template arguments, grid x / y / z, sets | tiles per sequence, misaligned | ring slots,
+    reduce pass | layers, LDS bytes) of the last time-as-k weight-gradient or fused-WN launch of this thread; all zeros if none
+    is recorded."""
+    out = (ctypes.c_int32 * WN_ROUTE_LEN)()
+    _lib.load().fst_wn_last_route(out)
+    return tuple(out)
+
+
+def wn_route_kernel_name(route: Sequence[int]) -> str:
+    """The kernel a fst_wn_last_route record names, e.g. ``wn_wgrad_kernel<2, 3, true, false, 1>``."""
+    fam, tf = route[0], ("false", "true")
+    if fam == WN_ROUTE_WGRAD:
+        return f"wn_wgrad_kernel<2, {route[1]}, {tf[route[2]]}, {tf[route[3]]}, {route[4]}>"
+    if fam == WN_ROUTE_TZ:
+        return f"tz_wgrad_kernel<{route[1]}, {tf[route[2]]}>"
+    if fam == WN_ROUTE_LAYER_FWD:
+        return f"wn_layer_fwd_kernel<{route[1]}>"
+    return _WN_ROUTE_NAMES[fam]
+
+
 def route_kernel_name(route: Sequence[int]) -> str:
     """The kernel template a route record names, e.g. ``conv_gemm_pipe_kernel<2, 1, true>`` (the KernelTimer key)."""
     fam = route[0]

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FST_ABI_VERSION 13
+#define FST_ABI_VERSION 14
 
 int fst_version(void);
 const char* fst_last_error(void);
@@ -369,6 +369,31 @@ int fst_dense_tap_wgrad_ok(int B, int L, int M, int C, int K, int pad_left);
 int64_t fst_dense_tap_wgrad_workspace_floats(int B, int L, int M, int C, int K);
 int fst_dense_tap_wgrad(const float* dy, const float* x, float* dw /* [M][C][K], written */, float* workspace, int64_t workspace_floats,
                         int B, int L, int M, int C, int K, int pad_left, int64_t numel_dy, int64_t numel_x, void* stream);
+
+/* The kernel instance the last call of the calling host thread to one of the launchers above launched — fst_wn_wgrad_in / _rs,
+ * fst_nt_gemm, fst_tap_wgrad, fst_dense_tap_wgrad, fst_wn_layer_fwd / _bwd / _dgrad, fst_wn_stack_fwd / _bwd — recorded from the
+ * values the launcher dispatched with (host side, thread-local; a call refused before its launch clears it):
+ *   out[0]     family: FST_WN_ROUTE_WGRAD wn_wgrad_kernel<2, KT, FULL, MUL, NE>, FST_WN_ROUTE_TZ tz_wgrad_kernel<MP, FULL>,
+ *              FST_WN_ROUTE_LAYER_FWD wn_layer_fwd_kernel<NW>, FST_WN_ROUTE_STACK_FWD wn_stack_fwd_kernel (8-wave tiles),
+ *              FST_WN_ROUTE_LAYER_BWD, FST_WN_ROUTE_LAYER_DGRAD, FST_WN_ROUTE_STACK_BWD (no template arguments)
+ *   out[1..4]  the template arguments: KT, FULL, MUL, NE | MP, FULL | NW; unused ones 0 (bools as 0 / 1)
+ *   out[5..7]  the grid: x = workgroups (weight gradients: the K split after the clamp; fused kernels: tiles, or the persistent
+ *              grid), y = k-row / channel groups, z = row halves (tz); 1 where a dimension is not used
+ *   out[8]     weight gradients: operand sets;  fused kernels: tiles per sequence
+ *   out[9]     weight gradients: 1 when a tap shift is not a multiple of 4 samples;  fused kernels: LDS ring slots
+ *   out[10]    weight gradients: 1 when the reduce pass ran, 0 when the workgroups stored straight into the output (fst_nt_gemm);
+ *              fused kernels: layers of the launch
+ *   out[11]    dynamic LDS bytes of the launch
+ * Returns 0, or -1 when no launch is recorded (out zero-filled) or out is null. */
+#define FST_WN_ROUTE_LEN         12
+#define FST_WN_ROUTE_WGRAD       1
+#define FST_WN_ROUTE_TZ          2
+#define FST_WN_ROUTE_LAYER_FWD   3
+#define FST_WN_ROUTE_STACK_FWD   4
+#define FST_WN_ROUTE_LAYER_BWD   5
+#define FST_WN_ROUTE_LAYER_DGRAD 6
+#define FST_WN_ROUTE_STACK_BWD   7
+int fst_wn_last_route(int32_t out[FST_WN_ROUTE_LEN]);
 
 /* NoiseTransfer (/root/reference/widgets.py:150-167): new_t = avg_t + r_t·mean_b(z_t), new_s likewise, dist = new_t − new_s,
  * learned = selu(W·dist + bias) (unbatched 1x1 conv over the [C, L] map), out[b] = learned + z_s[b].

@@ -128,6 +128,10 @@ for n_sets in (1, 3):
            f"fst_wn_wgrad_rs ({n_sets} sets)")
 expect(lib.fst_wn_wgrad_in(arr(dg), arr(a), arr(u0), 4, h * Lq, P(dwi), P(dwc), P(ws), ws_n, Bq, Lq, n, h, 4, 0, Bq * n * Lq, None), "bad",
        "fst_wn_wgrad_in (4 sets)")
+# the launch-route record: a refused call clears it; the query copies 12 ints into the caller's array and refuses a null one
+route = (ctypes.c_int32 * 12)(*([77] * 12))
+assert lib.fst_wn_last_route(route) == -1 and list(route) == [0] * 12, list(route)
+expect(lib.fst_wn_last_route(None), "bad", "fst_wn_last_route (null output)")
 print("time-as-k weight gradient: operand sets")
 
 # ---- 4. fused WN layer launchers: image sizes and extents

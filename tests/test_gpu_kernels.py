@@ -566,7 +566,7 @@ def test_two_step_lstm_matches_torch_lstm(B, H):
                                              (120, 25, 2, 512, 128, False), (120, 25, 2, 1024, 64, True), (120, 25, 2, 200, 4, True),
                                              (8, 3, 3, 40, 2, True), (128, 32, 1, 256, 32, False), (33, 31, 2, 132, 8, True),
                                              # more tiles than CUs: persistent workgroups, the next tile's first stages
-                                             # streaming in under the epilogue (3-slot ring; 2-slot ring at dilation 128)
+                                             # streaming in under the epilogue (the ring has 2 slots at every dilation)
                                              (8, 3, 131, 1024, 2, True), (16, 5, 67, 2048, 128, True), (8, 3, 300, 500, 16, False)])
 def test_fused_wn_layer_data_gradient(n, h, B, L, dil, res):
     """fst_wn_layer_dgrad (transposed dilated 3-tap conv with one tap-merged window per 16 channels + the transposed
