@@ -55,8 +55,16 @@ class GradBucket:
         copy back run on a SIDE stream ordered after everything already issued on the current stream, so work issued next on
         the current stream that does not touch ``.grad`` (GradNorm's partial backward passes) overlaps the all-reduce;
         ``all_reduce_end`` orders the current stream after it."""
+        self._begin([p.grad for p in params if p.grad is not None])
+
+    def all_reduce_grads(self, grads: List[torch.Tensor]) -> None:
+        """``all_reduce`` on the gradient tensors themselves: a captured pre-training phase keeps the tensors its graph
+        writes (``JointTrainer.replay_phase``), while ``.grad`` belongs to whatever ran or was captured last."""
+        self._begin(list(grads))
+        self.all_reduce_end()
+
+    def _begin(self, grads: List[torch.Tensor]) -> None:
         self._pending = False
-        grads: List[torch.Tensor] = [p.grad for p in params if p.grad is not None]
         if not grads or (self.world == 1 and not self.always_reduce):
             return
         n = sum(g.numel() for g in grads)

@@ -182,6 +182,8 @@ class JointTrainer:
         self.alpha = 3
         self.on_grads_ready = None                                            # test hook: called before the optimisers step
         self._side = torch.cuda.Stream(device=device)                         # launch-bound side chains (CPC)
+        self._phase: Dict[str, dict] = {}                                     # captured pre-training phases (capture_phase)
+        self._phase_pool = None                                               # their shared graph memory pool
         for mod in self.m.values():
             mod.train()
         # GradNorm differentiates the shared OS_blocks only: their convs keep weight gradients in partial passes
@@ -228,11 +230,17 @@ class JointTrainer:
                 "ad": self.m["ad_net"].iter_num, "fd": self.m["fd_s"].iter_num}
         return {"t": {k: v.detach().clone() for k, v in self._state_tensors().items()}, "host": host}
 
-    def restore(self, snap) -> None:
+    def restore(self, snap, new_to_zero: bool = False) -> None:
+        """``new_to_zero``: also return state created since the snapshot (moments an optimiser makes on its first step) to its
+        initial value, zero — the trainer then computes what it would have computed had that state never been created."""
         cur = self._state_tensors()
         with torch.no_grad():
             for k, v in snap["t"].items():
                 cur[k].copy_(v)
+            if new_to_zero:
+                for k, t in cur.items():
+                    if k not in snap["t"]:
+                        t.zero_()
         n = self.m["noise"]
         n.time, n.cal_num_target, n.cal_num_source = snap["host"]["noise"]
         self.m["ad_net"].iter_num, self.m["fd_s"].iter_num = snap["host"]["ad"], snap["host"]["fd"]
@@ -275,7 +283,10 @@ class JointTrainer:
     def load_state_dict(self, sd: dict) -> None:
         """Inverse of ``state_dict``.  A captured graph holds the old buffers' addresses only for parameters and
         optimiser moments that are restored IN PLACE here, but re-capture after loading anyway (GRL coefficients and
-        the epoch's loss coefficients are baked into a capture)."""
+        the epoch's loss coefficients are baked into a capture).  The RMSprop moments are NOT restored in place
+        (``Optimizer.load_state_dict`` replaces the tensors), so a resident phase graph would update dead moments:
+        every phase capture is dropped here and ``replay_phase`` raises until ``capture_phase`` has run again."""
+        self.release_phase()
         dev = self.device
         for k in self.MODULES:
             self.m[k].load_state_dict({n: v.to(dev) for n, v in sd["modules"][k].items()}, strict=True)
@@ -394,7 +405,17 @@ class JointTrainer:
         return L["nf_t"] + L["nf_s"], L
 
     def phase_step(self, phase: str, x_t, y_t, x_s, y_s, t_samples=(None, None)):
-        """One batch of a pre-training phase: forward, backward, the phase's optimisers, zero_grad (eager)."""
+        """One batch of a pre-training phase: forward, backward, the phase's optimisers, zero_grad (eager; ``capture_phase`` /
+        ``replay_phase`` issue the same launches as one hipGraph)."""
+        report = self._phase_fwd_bwd(phase, x_t, y_t, x_s, y_s, t_samples)
+        if self.bucket is not None:
+            self.bucket.all_reduce(self.parameters())
+        self._phase_update(phase)
+        return report
+
+    def _phase_fwd_bwd(self, phase: str, x_t, y_t, x_s, y_s, t_samples):
+        """First half of a phase step, device-side and shape-static when the CPC indices are device scalars: the losses, zero_grad,
+        backward.  Returns the report."""
         with _dist.global_batch(self.bucket if self.sync == "global" else None):
             with ops.pack_cache(), self.m["nf"].shared_fold(), self.m["cpc"].shared_stack():
                 total, L = self.phase_losses(phase, x_t, y_t, x_s, y_s, t_samples)
@@ -402,16 +423,126 @@ class JointTrainer:
                     o.zero_grad(set_to_none=True)
                 self.opt_cpc.zero_grad(set_to_none=True)
                 total.backward()
-        if self.bucket is not None:
-            self.bucket.all_reduce(self.parameters())
+        report = {k: v.detach() for k, v in L.items()}
+        report["total"] = total.detach()
+        return report
+
+    def _phase_update(self, phase: str) -> None:
+        """Second half (after the gradient all-reduce of a data-parallel step): the phase's optimisers."""
         if self.on_grads_ready is not None:
             self.on_grads_ready()
         rmsprop_step_many([self.opts[k] for k in self.PHASES[phase] if k != "cpc"])
         if "cpc" in self.PHASES[phase]:
             self.opt_cpc.step()
-        report = {k: v.detach() for k, v in L.items()}
-        report["total"] = total.detach()
-        return report
+
+    # ------------------------------------------------------------------ hipGraph for the phases: capture once each, replay per batch
+    def capture_phase(self, phase: str, x_t, y_t, x_s, y_s, warmup: int = 2):
+        """Capture one batch of a pre-training phase — exactly what ``phase_step`` issues — into a hipGraph that ``replay_phase``
+        launches.  The batch and the two CPC start indices (int32 device scalars; unused by "source_pretrain" and "nf") live in
+        static device buffers of this phase.  Capturing has no training side effect: the eager warm-up steps (on a side stream;
+        they create the RMSprop moments and load every code object) are undone by ``snapshot`` / ``restore``, moments created
+        by the warm-up go back to zero, and the ``.grad`` attributes are put back as they were.
+        Single GPU: one graph.  With a ``GradBucket`` (mode A): two graphs, forward + backward and update, with the eager
+        gradient all-reduce between them — no collective is ever captured; ``sync="global"`` over more than one rank raises as
+        ``capture`` does.  Any number of phases may be resident at once, next to the joint capture: the reference alternates
+        "ssl" / "ssl_with_ce" and "nf" / "nf_with_ce".  Phase graphs never replay concurrently, so they share one memory pool;
+        the reports are copied out of it, so a phase's report stays valid until that phase's next replay.  Capturing a phase
+        again replaces its graph.  ``on_grads_ready`` is called inside the captured region, as in ``capture``: it fires ONCE, at
+        capture time (on the gradient tensors the graph will write), not per replay and not during the warm-up."""
+        if phase not in self.PHASES:
+            raise ValueError(f"unknown phase {phase!r}; one of {sorted(self.PHASES)}")
+        if self.sync == "global" and self.bucket is not None and self.bucket.world > 1:
+            raise RuntimeError("sync='global' (mode B) puts collectives inside autograd: run it eagerly with phase_step()")
+        if warmup < 1:
+            raise ValueError("capture_phase(): at least one warm-up step (it creates the optimiser moments the graph updates)")
+        self.release_phase(phase)
+        dev = self.device
+        gi = {"x_t": x_t.clone(), "y_t": y_t.clone(), "x_s": x_s.clone(), "y_s": y_s.clone(),
+              "t": torch.zeros(2, dtype=torch.int32, device=dev)}
+        args = (gi["x_t"], gi["y_t"], gi["x_s"], gi["y_s"], (gi["t"][0], gi["t"][1]))
+        params = self.parameters()
+        grads_before = [p.grad for p in params]
+        snap, hook = self.snapshot(), self.on_grads_ready
+        self.on_grads_ready = None
+        main = torch.cuda.current_stream()
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(main)
+        try:
+            with torch.cuda.stream(side):                                     # eager warm-up on a side stream
+                for _ in range(warmup):
+                    keys = sorted(self.phase_step(phase, *args))
+                self.restore(snap, new_to_zero=True)
+        finally:
+            self.on_grads_ready = hook
+        main.wait_stream(side)
+        torch.cuda.synchronize()
+        # static report: the graphs' own outputs live in the shared pool, where a later capture may reuse what this one frees
+        out = torch.zeros(len(keys), device=dev)
+
+        def fwd_bwd():
+            rep = self._phase_fwd_bwd(phase, *args)
+            out.copy_(torch.stack([rep[k] for k in keys]))
+
+        if self._phase_pool is None:
+            self._phase_pool = torch.cuda.graph_pool_handle()
+        try:
+            if self.bucket is None:
+                graphs = [torch.cuda.CUDAGraph()]
+                with torch.cuda.graph(graphs[0], pool=self._phase_pool, capture_error_mode=_CAPTURE_MODE):
+                    fwd_bwd()
+                    self._phase_update(phase)
+            else:
+                graphs = [torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()]
+                with torch.cuda.graph(graphs[0], pool=self._phase_pool, capture_error_mode=_CAPTURE_MODE):
+                    fwd_bwd()
+                self.bucket.all_reduce(params)                                # eager, between the graphs
+                with torch.cuda.graph(graphs[1], pool=self._phase_pool, capture_error_mode=_CAPTURE_MODE):
+                    self._phase_update(phase)
+            # the gradient tensors the graph writes stay allocated as long as the graph does
+            grads = [p.grad for p in params if p.grad is not None]
+        finally:
+            for p, g in zip(params, grads_before):
+                p.grad = g
+        self._phase[phase] = {"graphs": graphs, "in": gi, "grads": grads, "report": {k: out[i] for i, k in enumerate(keys)}}
+        return self
+
+    def replay_phase(self, phase: str, x_t, y_t, x_s, y_s, t_samples=(0, 0)):
+        """One batch of a captured phase on a new batch of the captured shapes; returns the phase's static report (the keys of
+        ``phase_step``: its losses and "total"), valid until this phase's next replay.  Nothing here waits for the device.
+        ``.grad`` is left alone: the gradients are in the tensors the capture kept."""
+        rec = self._phase.get(phase)
+        if rec is None:
+            if phase not in self.PHASES:
+                raise ValueError(f"unknown phase {phase!r}; one of {sorted(self.PHASES)}")
+            raise RuntimeError(f"phase {phase!r} is not captured: call capture_phase({phase!r}, ...) first "
+                               "(load_state_dict drops every phase capture)")
+        gi = rec["in"]
+        batch = (("x_t", x_t), ("y_t", y_t), ("x_s", x_s), ("y_s", y_s))
+        for k, v in batch:
+            if v.shape != gi[k].shape or v.dtype != gi[k].dtype:
+                raise ValueError(f"replay_phase({phase!r}): {k} is {tuple(v.shape)} {v.dtype}, captured "
+                                 f"{tuple(gi[k].shape)} {gi[k].dtype}")
+        for k, v in batch:
+            if v is not gi[k]:
+                gi[k].copy_(v, non_blocking=True)
+        gi["t"].copy_(torch.tensor([int(t_samples[0]), int(t_samples[1])], dtype=torch.int32), non_blocking=True)
+        rec["graphs"][0].replay()
+        if len(rec["graphs"]) == 2:
+            self.bucket.all_reduce_grads(rec["grads"])
+            rec["graphs"][1].replay()
+        return rec["report"]
+
+    def release_phase(self, phase: Optional[str] = None) -> None:
+        """Drop the capture of ``phase`` (of every phase if None); a phase that is not captured is left as it is."""
+        if phase is None:
+            self._phase.clear()
+        else:
+            self._phase.pop(phase, None)
+        if not self._phase:
+            self._phase_pool = None
+
+    def captured_phases(self) -> Tuple[str, ...]:
+        return tuple(sorted(self._phase))
 
     # ------------------------------------------------------------------ one optimisation step (:645-766)
     def step(self, x_t, y_t, x_s, y_s, epoch: int = 0, t_samples=(None, None)):
