@@ -21,6 +21,7 @@
 // read with scalar loads; one branch-free epilogue (bias / residual / accumulate / split / atomics) with 16-byte
 // stores through a wave-private LDS transpose.
 #include "fst_device.h"
+#include <algorithm>
 #include <type_traits>
 
 // ------------------------------------------------------------------------------------------------
@@ -978,15 +979,51 @@ __global__ __launch_bounds__(256, 2) void conv_win_rows_kernel(ConvGemmParams p,
   }
 }
 
-static bool plan_is_pipeable(const PlanView& pv) {
+// Everything the launchers derive from the chunk and (M-group g, chunk q) tables of a checked plan, in one pass.  A span is
+// the distance in taps between the first and the last tap of a live range [e0, e1): the staged window of a time tile of T
+// samples is span * dil + T columns wide.
+struct PlanScan {
+  bool needs_x1; int rows_in[2];       // input rows each sample owns (batch-stride checks)
+  int span_single;                     // widest range of one (g, q)
+  int span_chunk_union;                // widest union over g of a chunk's ranges (one staged chunk feeds every M-group)
+  int span_union;                      // union of all ranges (the resident bf16 window)
+  bool any_live, wide, starts4;        // wgrad: a live range of > 1 tap; every live window starts on / spans a multiple of 4 samples
+  bool pipeable;                       // single-tap ranges of <= PIPE_C channels: the stage kernels serve the plan
+};
+
+static PlanScan plan_scan(const PlanView& pv) {
+  PlanScan s = {false, {0, 0}, 0, 0, 0, false, false, true, true};
+  int lo_all = pv.ntaps, hi_all = 0;
   for (int q = 0; q < pv.n_chunks; ++q) {
-    if (((pv.chunk[4 * q + 2] + 1) & ~1) > PIPE_C) return false;
+    const int32_t* c = pv.chunk + 4 * q;
+    s.needs_x1 |= c[0] == 1;
+    s.rows_in[c[0]] = std::max(s.rows_in[c[0]], c[1] + c[2]);
+    s.pipeable &= ((c[2] + 1) & ~1) <= PIPE_C;
+    int lo_q = pv.ntaps, hi_q = 0;
     for (int g = 0; g < pv.n_mgroups; ++g) {
       const int32_t* e = pv.mg + 4 * (g * pv.n_chunks + q);
-      if (e[1] > e[0] + 1) return false;
+      if (e[1] <= e[0]) continue;
+      const int span = e[1] - 1 - e[0];
+      s.span_single = std::max(s.span_single, span);
+      lo_q = std::min(lo_q, e[0]);
+      hi_q = std::max(hi_q, e[1]);
+      s.wide |= span > 0;
+      s.starts4 &= (e[0] * pv.dil - pv.pad_left) % 4 == 0 && (span * pv.dil) % 4 == 0;
     }
+    if (hi_q == 0) continue;                             // no M-group reads this chunk
+    s.any_live = true;
+    s.span_chunk_union = std::max(s.span_chunk_union, hi_q - 1 - lo_q);
+    lo_all = std::min(lo_all, lo_q);
+    hi_all = std::max(hi_all, hi_q);
   }
-  return true;
+  if (s.any_live) s.span_union = hi_all - 1 - lo_all;
+  s.pipeable &= !s.wide;
+  return s;
+}
+
+// a batch stride shorter than the rows a sample owns would make the B samples of the launch overlap / overrun
+static bool input_strides_hold(const PlanScan& ps, int B, int L, int64_t x0_bs, int64_t x1_bs) {
+  return B == 1 || (x0_bs >= (int64_t)ps.rows_in[0] * L && (!ps.needs_x1 || x1_bs >= (int64_t)ps.rows_in[1] * L));
 }
 
 typedef void (*conv_gemm_fn)(ConvGemmParams, const int32_t*);
@@ -1114,6 +1151,92 @@ int fst_check_plan(const int32_t* ph, int plan_len, int M, const char* who) {
   return 0;
 }
 
+// Every launch decision of fst_conv_gemm: the kernel, what fst_conv_last_route reports of it, the ConvGemmParams fields of
+// the same names and the dynamic LDS.
+struct ConvRoute {
+  conv_gemm_fn fn;
+  int family, vec, epi;                // vec: the f32 pipe's 16-byte B-tile loads; epi: FST_ROUTE_EPI_*, the branch conv_epilogue takes
+  int mg_per_wg, ldw, stage_vec, epi_vec, epi_lds_off;
+  size_t lds_bytes;
+};
+
+// in16 / out16: L, every batch stride and every base address of the inputs / of y, y2 and res are multiples of 16 bytes.
+static int conv_gemm_route(const PlanView& pv, const PlanScan& ps, int nb_cfg, int L, int ksplit, int flags, bool in16,
+                           bool out16, bool has_res, ConvRoute* out) {
+  const int MB = pv.MB, TILE_N = 128 * nb_cfg;
+  const size_t epi_bytes = 4 * 32 * 36 * sizeof(float);     // one transpose tile per wave
+  const bool bf3 = (flags & FST_GEMM_BF16X3) != 0;
+  const bool pipe = ps.pipeable && pick_conv_gemm_pipe(MB, nb_cfg) != nullptr;
+  const bool atomic = (flags & FST_EPI_ATOMIC) != 0;
+  const bool add = has_res || (flags & (FST_EPI_ACC1 | FST_EPI_ACC2));
+  // the f32 window: one staged window feeds every M-group when the whole K range is a single chunk (omni-scale layers);
+  // 16-B aligned LDS rows (float4 staging)
+  const int ldw_f32 =((pv.n_chunks == 1 ? ps.span_chunk_union : ps.span_single) * pv.dil + TILE_N + 3) & ~3;
+  ConvRoute r;
+  r.epi_vec = !atomic && out16;
+  r.epi = atomic ? FST_ROUTE_EPI_ATOMIC
+                 : r.epi_vec ? (add ? FST_ROUTE_EPI_VEC_ADD : FST_ROUTE_EPI_VEC) : (add ? FST_ROUTE_EPI_ADD : FST_ROUTE_EPI_PLAIN);
+  if (!bf3 && !pipe) {                                       // f32 window
+    r.fn = pick_conv_gemm(MB, nb_cfg);
+    r.family = FST_ROUTE_GEMM;
+    r.vec = 0;
+    r.mg_per_wg = pv.n_chunks == 1 ? pv.n_mgroups : 1;
+    r.ldw = ldw_f32;
+    r.stage_vec = in16;
+    r.epi_lds_off = (pv.chunk_cap * r.ldw + 3) / 4 * 4;      // after the staged window (reused across M-groups)
+    r.lds_bytes = r.epi_vec ? (size_t)r.epi_lds_off * sizeof(float) + epi_bytes : (size_t)pv.chunk_cap * r.ldw * sizeof(float);
+  } else if (!bf3) {                                         // f32 pipe (single-tap stages; the kernel reads neither ldw nor stage_vec)
+    // 16-byte B-tile loads need every address of a stage row to be 16-B aligned: every tap shift ≡ 0 (mod 4)
+    const bool shifts4 = pv.pad_left % 4 == 0 && (pv.ntaps == 1 || pv.dil % 4 == 0);
+    r.vec = in16 && shifts4;
+    r.fn = pick_conv_gemm_pipe(MB, nb_cfg, r.vec != 0);
+    r.family = FST_ROUTE_PIPE;
+    r.mg_per_wg = 1;
+    r.ldw = ldw_f32;
+    r.stage_vec = in16;
+    r.epi_lds_off = 0;                                       // the staging buffers are dead after the last barrier
+    r.lds_bytes = std::max(epi_bytes, 2 * ((size_t)(PIPE_C / 2) * MB * 64 + (size_t)PIPE_C * TILE_N) * sizeof(float));
+  } else if (pipe) {                                         // bf16 pipe (as above; a 3-slot ring of 16-channel stages)
+    FST_REQUIRE(in16, "fst_conv_gemm: FST_GEMM_BF16X3 needs L %% 4 == 0 and 16-byte aligned activations (L=%d)", L);
+    r.fn = pick_conv_gemm_bf3(MB, nb_cfg);
+    r.family = FST_ROUTE_BF3;
+    r.vec = 0;
+    r.mg_per_wg = 1;
+    r.ldw = ldw_f32;
+    r.stage_vec = in16;
+    r.epi_lds_off = 0;
+    r.lds_bytes = std::max(epi_bytes, 3 * ((size_t)MB * 2048 + 2 * ((size_t)(TILE_N / 32 + 1) * 1024 + 128)));
+  } else {                                                   // bf16 window
+    FST_REQUIRE(pv.chunk_cap <= 16 && pick_conv_win_bf3(MB, nb_cfg) != nullptr,
+                "fst_conv_gemm: FST_GEMM_BF16X3 on a windowed plan needs chunks of <= 16 channels (got %d) and a supported "
+                "MB x NB (%d x %d)", pv.chunk_cap, MB, nb_cfg);
+    // bf16 window images: per chunk [ldw rows][16 ch] hi + lo = ldw*64 bytes.  All chunks resident (every M-group of
+    // the workgroup reuses them) when they fit next to a second workgroup; otherwise one slot, one M-group per workgroup.
+    const int w_union = ps.span_union * pv.dil + TILE_N;
+    const bool resident = ksplit == 1 && (size_t)pv.n_chunks * w_union * 64 + epi_bytes <= 76 * 1024;
+    // 32-row M-groups on 256-sample tiles with resident windows: the waves split over the M-groups instead of over time
+    // (conv_win_rows_kernel: a weight fragment is fetched by one wave, not by all four; plain stores only)
+    if (resident && MB == 1 && nb_cfg == 2 && pv.n_mgroups >= 4 && !add && !atomic) {
+      r.fn = conv_win_rows_kernel;
+      r.family = FST_ROUTE_WIN_ROWS;
+    } else {
+      r.fn = pick_conv_win_bf3(MB, nb_cfg);
+      r.family = FST_ROUTE_WIN_BF3;
+    }
+    r.vec = 0;
+    r.mg_per_wg = resident ? pv.n_mgroups : 1;
+    r.ldw = resident ? w_union : ps.span_single * pv.dil + TILE_N;
+    r.stage_vec = resident;                                  // (field reused: 1 = all chunks fit)
+    r.epi_lds_off = ((resident ? pv.n_chunks : 1) * r.ldw * 16 + 3) / 4 * 4;
+    r.lds_bytes = (size_t)r.epi_lds_off * sizeof(float) + epi_bytes;   // the epilogue's transpose tiles (vec or not)
+  }
+  FST_REQUIRE(r.fn != nullptr, "fst_conv_gemm: no kernel for MB=%d NB=%d", MB, nb_cfg);
+  FST_REQUIRE(r.lds_bytes <= 160 * 1024, "fst_conv_gemm: LDS window %zu B exceeds 160 KiB (chunk_cap=%d ldw=%d)",
+              r.lds_bytes, pv.chunk_cap, r.ldw);
+  *out = r;
+  return 0;
+}
+
 extern "C" int fst_conv_gemm(const float* x0, int64_t x0_bs, const float* x1, int64_t x1_bs, const float* a_packed,
                              const int32_t* plan_dev, const int32_t* plan_host, int plan_len, const float* bias,
                              float* y, int64_t y_bs, const float* res, int64_t res_bs, float* y2, int64_t y2_bs,
@@ -1121,6 +1244,7 @@ extern "C" int fst_conv_gemm(const float* x0, int64_t x0_bs, const float* x1, in
   set_route(0, 0, 0, 0, 0, 0, 0, 0);
   if (int rc = fst_check_plan(plan_host, plan_len, M, "fst_conv_gemm")) return rc;
   const PlanView pv = plan_view(plan_host);
+  const PlanScan ps = plan_scan(pv);
   FST_REQUIRE(x0 && a_packed && plan_dev, "fst_conv_gemm: null operand");
   FST_REQUIRE(B > 0 && L > 0, "fst_conv_gemm: B=%d L=%d", B, L);
   FST_REQUIRE(msplit >= 0 && msplit <= M, "fst_conv_gemm: msplit=%d outside [0,%d]", msplit, M);
@@ -1129,45 +1253,21 @@ extern "C" int fst_conv_gemm(const float* x0, int64_t x0_bs, const float* x1, in
   FST_REQUIRE(m2_start >= msplit && m2_start <= M, "fst_conv_gemm: m2_start=%d outside [msplit=%d, M=%d]", m2_start, msplit, M);
   FST_REQUIRE(ksplit >= 1 && ksplit <= pv.n_chunks, "fst_conv_gemm: ksplit=%d vs %d chunks", ksplit, pv.n_chunks);
   FST_REQUIRE(ksplit == 1 || (flags & FST_EPI_ATOMIC), "fst_conv_gemm: ksplit>1 needs FST_EPI_ATOMIC");
-  bool needs_x1 = false;
-  for (int q = 0; q < pv.n_chunks; ++q) needs_x1 |= pv.chunk[4 * q] == 1;
-  FST_REQUIRE(!needs_x1 || x1 != nullptr, "fst_conv_gemm: plan reads input 1 but x1 is null");
-  // a batch stride shorter than the rows a sample owns would make the B samples of the launch overlap / overrun
-  {
-    int rows_in[2] = {0, 0};
-    for (int q = 0; q < pv.n_chunks; ++q) {
-      const int32_t* c = pv.chunk + 4 * q;
-      rows_in[c[0]] = rows_in[c[0]] > c[1] + c[2] ? rows_in[c[0]] : c[1] + c[2];
-    }
-    FST_REQUIRE(B == 1 || (x0_bs >= (int64_t)rows_in[0] * L && (!needs_x1 || x1_bs >= (int64_t)rows_in[1] * L)),
-                "fst_conv_gemm: an input batch stride (%lld, %lld) is smaller than its %d / %d channels x L=%d",
-                (long long)x0_bs, (long long)x1_bs, rows_in[0], rows_in[1], L);
-    FST_REQUIRE(B == 1 || ((msplit == 0 || y_bs >= (int64_t)msplit * L) && (res == nullptr || res_bs >= (int64_t)msplit * L) &&
-                           (msplit == M || y2_bs >= (int64_t)(M - m2_start) * L)),
-                "fst_conv_gemm: an output batch stride (y %lld, res %lld, y2 %lld) is smaller than the rows it holds",
-                (long long)y_bs, (long long)res_bs, (long long)y2_bs);
-  }
-  const bool pipe = plan_is_pipeable(pv) && pick_conv_gemm_pipe(pv.MB, nb_cfg) != nullptr;
-  // 16-byte B-tile loads need every address of a stage row to be 16-B aligned
-  const bool shifts4 = pv.pad_left % 4 == 0 && (pv.ntaps == 1 || pv.dil % 4 == 0);   // every tap shift ≡ 0 (mod 4)
-  const bool vec = pipe && L % 4 == 0 && shifts4 && x0_bs % 4 == 0 && fst_aligned16(x0) &&
-                   (x1 == nullptr || (x1_bs % 4 == 0 && fst_aligned16(x1)));
-  const bool bf3 = (flags & FST_GEMM_BF16X3) != 0;
-  const bool win3 = bf3 && !pipe;                        // windowed plan of <= 16-channel chunks: the bf16 window kernel
-  if (bf3 && pipe) {
-    FST_REQUIRE(L % 4 == 0 && x0_bs % 4 == 0 && fst_aligned16(x0) && (x1 == nullptr || (x1_bs % 4 == 0 && fst_aligned16(x1))),
-                "fst_conv_gemm: FST_GEMM_BF16X3 needs L %% 4 == 0 and 16-byte aligned activations (L=%d)", L);
-  }
-  if (win3)
-    FST_REQUIRE(pv.chunk_cap <= 16 && pick_conv_win_bf3(pv.MB, nb_cfg) != nullptr,
-                "fst_conv_gemm: FST_GEMM_BF16X3 on a windowed plan needs chunks of <= 16 channels (got %d) and a supported "
-                "MB x NB (%d x %d)", pv.chunk_cap, pv.MB, nb_cfg);
-  conv_gemm_fn fn = win3 ? pick_conv_win_bf3(pv.MB, nb_cfg)
-                         : (bf3 ? pick_conv_gemm_bf3(pv.MB, nb_cfg)
-                                : (pipe ? pick_conv_gemm_pipe(pv.MB, nb_cfg, vec) : pick_conv_gemm(pv.MB, nb_cfg)));
-  int family = win3 ? FST_ROUTE_WIN_BF3 : (bf3 ? FST_ROUTE_BF3 : (pipe ? FST_ROUTE_PIPE : FST_ROUTE_GEMM));
-  FST_REQUIRE(fn != nullptr, "fst_conv_gemm: no kernel for MB=%d NB=%d", pv.MB, nb_cfg);
-  const int TILE_N = 128 * nb_cfg;
+  FST_REQUIRE(!ps.needs_x1 || x1 != nullptr, "fst_conv_gemm: plan reads input 1 but x1 is null");
+  FST_REQUIRE(input_strides_hold(ps, B, L, x0_bs, x1_bs),
+              "fst_conv_gemm: an input batch stride (%lld, %lld) is smaller than its %d / %d channels x L=%d",
+              (long long)x0_bs, (long long)x1_bs, ps.rows_in[0], ps.rows_in[1], L);
+  FST_REQUIRE(B == 1 || ((msplit == 0 || y_bs >= (int64_t)msplit * L) && (res == nullptr || res_bs >= (int64_t)msplit * L) &&
+                         (msplit == M || y2_bs >= (int64_t)(M - m2_start) * L)),
+              "fst_conv_gemm: an output batch stride (y %lld, res %lld, y2 %lld) is smaller than the rows it holds",
+              (long long)y_bs, (long long)res_bs, (long long)y2_bs);
+  FST_REQUIRE(ps.any_live, "fst_conv_gemm: plan has no live taps");
+
+  const bool in16 = L % 4 == 0 && x0_bs % 4 == 0 && fst_aligned16(x0) && (x1 == nullptr || (x1_bs % 4 == 0 && fst_aligned16(x1)));
+  const bool out16 = L % 4 == 0 && y_bs % 4 == 0 && y2_bs % 4 == 0 && res_bs % 4 == 0 && fst_aligned16(y) && fst_aligned16(y2) &&
+                     fst_aligned16(res);
+  ConvRoute r;
+  if (int rc = conv_gemm_route(pv, ps, nb_cfg, L, ksplit, flags, in16, out16, res != nullptr, &r)) return rc;
 
   ConvGemmParams p;
   p.x[0] = x0; p.x[1] = x1; p.x_bs[0] = x0_bs; p.x_bs[1] = x1_bs;
@@ -1175,89 +1275,15 @@ extern "C" int fst_conv_gemm(const float* x0, int64_t x0_bs, const float* x1, in
   p.y = y; p.y_bs = y_bs; p.res = res; p.res_bs = res_bs; p.y2 = y2; p.y2_bs = y2_bs; p.msplit = msplit;
   p.m2_start = m2_start;
   p.B = B; p.L = L; p.M = M;
-  p.tiles_per_seq = (L + TILE_N - 1) / TILE_N;
+  p.tiles_per_seq = (L + 128 * nb_cfg - 1) / (128 * nb_cfg);
   p.ksplit = ksplit; p.flags = flags;
-  // one staged window feeds every M-group when the whole K range is a single chunk (omni-scale layers)
-  p.mg_per_wg = (pv.n_chunks == 1) ? pv.n_mgroups : 1;
-  int max_w = 0;
-  for (int q = 0; q < pv.n_chunks; ++q) {
-    if (p.mg_per_wg > 1) {
-      int lo = 1 << 30, hi = -1;
-      for (int g = 0; g < pv.n_mgroups; ++g) {
-        const int32_t* e = pv.mg + 4 * (g * pv.n_chunks + q);
-        if (e[1] > e[0]) { lo = lo < e[0] ? lo : e[0]; hi = hi > e[1] ? hi : e[1]; }
-      }
-      if (hi >= 0) { int w = (hi - 1 - lo) * pv.dil + TILE_N; max_w = max_w > w ? max_w : w; }
-    } else {
-      for (int g = 0; g < pv.n_mgroups; ++g) {
-        const int32_t* e = pv.mg + 4 * (g * pv.n_chunks + q);
-        if (e[1] > e[0]) { int w = (e[1] - 1 - e[0]) * pv.dil + TILE_N; max_w = max_w > w ? max_w : w; }
-      }
-    }
-  }
-  int max_w_single = 0;
-  for (int q = 0; q < pv.n_chunks; ++q)
-    for (int g = 0; g < pv.n_mgroups; ++g) {
-      const int32_t* e = pv.mg + 4 * (g * pv.n_chunks + q);
-      if (e[1] > e[0]) { int w = (e[1] - 1 - e[0]) * pv.dil + TILE_N; max_w_single = max_w_single > w ? max_w_single : w; }
-    }
-  FST_REQUIRE(max_w > 0, "fst_conv_gemm: plan has no live taps");
-  p.ldw = (max_w + 3) & ~3;                               // 16-B aligned LDS rows (float4 staging)
-  size_t lds_bytes = (size_t)pv.chunk_cap * p.ldw * sizeof(float);
-  p.stage_vec = L % 4 == 0 && x0_bs % 4 == 0 && fst_aligned16(x0) && (x1 == nullptr || (x1_bs % 4 == 0 && fst_aligned16(x1)));
-  p.epi_vec = !(flags & FST_EPI_ATOMIC) && L % 4 == 0 && y_bs % 4 == 0 && y2_bs % 4 == 0 && res_bs % 4 == 0 &&
-              fst_aligned16(y) && fst_aligned16(y2) && fst_aligned16(res);
-  const size_t epi_bytes = 4 * 32 * 36 * sizeof(float);     // one transpose tile per wave
-  if (pipe) {
-    p.mg_per_wg = 1;
-    lds_bytes = bf3 ? 3 * ((size_t)pv.MB * 2048 + 2 * ((size_t)(TILE_N / 32 + 1) * 1024 + 128))
-                    : 2 * ((size_t)(PIPE_C / 2) * pv.MB * 64 + (size_t)PIPE_C * TILE_N) * sizeof(float);
-    p.epi_lds_off = 0;                                       // the staging buffers are dead after the last barrier
-    if (lds_bytes < epi_bytes) lds_bytes = epi_bytes;
-  } else if (win3) {
-    // bf16 window images: per chunk [ldw rows][16 ch] hi + lo = ldw*64 bytes.  All chunks resident (every M-group of
-    // the workgroup reuses them) when they fit next to a second workgroup; otherwise one slot, one M-group per
-    // workgroup.  max_w above was computed for mg_per_wg == 1 or a single chunk; recompute for the union window.
-    int lo_all = 1 << 30, hi_all = -1;
-    for (int q = 0; q < pv.n_chunks; ++q)
-      for (int g = 0; g < pv.n_mgroups; ++g) {
-        const int32_t* e = pv.mg + 4 * (g * pv.n_chunks + q);
-        if (e[1] > e[0]) { lo_all = lo_all < e[0] ? lo_all : e[0]; hi_all = hi_all > e[1] ? hi_all : e[1]; }
-      }
-    const int w_union = (hi_all - 1 - lo_all) * pv.dil + TILE_N;
-    const bool resident = ksplit == 1 && (size_t)pv.n_chunks * w_union * 64 + epi_bytes <= 76 * 1024;
-    p.stage_vec = resident ? 1 : 0;
-    p.mg_per_wg = resident ? pv.n_mgroups : 1;
-    p.ldw = resident ? w_union : max_w_single;
-    lds_bytes = (size_t)(resident ? pv.n_chunks : 1) * p.ldw * 64;
-    p.epi_lds_off = (int)((lds_bytes / sizeof(float) + 3) / 4 * 4);
-    lds_bytes = (size_t)p.epi_lds_off * sizeof(float) + epi_bytes;       // the epilogue's transpose tiles (vec or not)
-    // 32-row M-groups on 256-sample tiles with resident windows: the waves split over the M-groups instead of over time
-    // (conv_win_rows_kernel: a weight fragment is fetched by one wave, not by all four)
-    if (resident && pv.MB == 1 && nb_cfg == 2 && pv.n_mgroups >= 4 && res == nullptr &&
-        !(flags & (FST_EPI_ATOMIC | FST_EPI_ACC1 | FST_EPI_ACC2))) {
-      fn = conv_win_rows_kernel;
-      family = FST_ROUTE_WIN_ROWS;
-    }
-  } else {
-    p.epi_lds_off = (int)((lds_bytes / sizeof(float) + 3) / 4 * 4);   // after the staged window (reused across M-groups)
-    if (p.epi_vec) lds_bytes = (size_t)p.epi_lds_off * sizeof(float) + epi_bytes;
-  }
-  FST_REQUIRE(lds_bytes <= 160 * 1024, "fst_conv_gemm: LDS window %zu B exceeds 160 KiB (chunk_cap=%d ldw=%d)",
-              lds_bytes, pv.chunk_cap, p.ldw);
-  if (lds_bytes > 48 * 1024)
-    if (int rc = fst_allow_full_lds((const void*)fn, "fst_conv_gemm")) return rc;
-  dim3 grid((unsigned)(B * p.tiles_per_seq), (unsigned)((pv.n_mgroups + p.mg_per_wg - 1) / p.mg_per_wg), (unsigned)ksplit);
-  {
-    // the branch conv_epilogue takes on these parameters (conv_win_rows_kernel: plain stores only)
-    const bool add = p.res != nullptr || (p.flags & (FST_EPI_ACC1 | FST_EPI_ACC2));
-    const int epi = (p.flags & FST_EPI_ATOMIC) ? FST_ROUTE_EPI_ATOMIC
-                    : p.epi_vec ? (add ? FST_ROUTE_EPI_VEC_ADD : FST_ROUTE_EPI_VEC)
-                                : (add ? FST_ROUTE_EPI_ADD : FST_ROUTE_EPI_PLAIN);
-    if (family == FST_ROUTE_WIN_ROWS) set_route(family, 0, 0, 0, 0, 0, epi, ksplit);
-    else set_route(family, pv.MB, nb_cfg, family == FST_ROUTE_PIPE ? (int)vec : 0, 0, 0, epi, ksplit);
-  }
-  hipLaunchKernelGGL(fn, grid, dim3(256), lds_bytes, (hipStream_t)stream, p, plan_dev);
+  p.mg_per_wg = r.mg_per_wg; p.ldw = r.ldw; p.stage_vec = r.stage_vec; p.epi_vec = r.epi_vec; p.epi_lds_off = r.epi_lds_off;
+  if (r.lds_bytes > 48 * 1024)
+    if (int rc = fst_allow_full_lds((const void*)r.fn, "fst_conv_gemm")) return rc;
+  const bool rows = r.family == FST_ROUTE_WIN_ROWS;          // not a template: no MB x NB to report
+  set_route(r.family, rows ? 0 : pv.MB, rows ? 0 : nb_cfg, r.vec, 0, 0, r.epi, ksplit);
+  dim3 grid((unsigned)(B * p.tiles_per_seq), (unsigned)((pv.n_mgroups + r.mg_per_wg - 1) / r.mg_per_wg), (unsigned)ksplit);
+  hipLaunchKernelGGL(r.fn, grid, dim3(256), r.lds_bytes, (hipStream_t)stream, p, plan_dev);
   FST_LAUNCH_CHECK();
   return 0;
 }
@@ -1692,6 +1718,7 @@ extern "C" int fst_conv_wgrad(const float* x0, int64_t x0_bs, const float* x1, i
   set_route(0, 0, 0, 0, 0, 0, 0, 0);
   if (int rc = fst_check_plan(plan_host, plan_len, M, "fst_conv_wgrad")) return rc;
   const PlanView pv = plan_view(plan_host);
+  const PlanScan ps = plan_scan(pv);
   FST_REQUIRE(x0 && dy && da_packed && plan_dev, "fst_conv_wgrad: null operand");
   FST_REQUIRE(pv.MB == 4 || pv.MB == 8, "fst_conv_wgrad: plan MB must be 4 or 8 (got %d)", pv.MB);
   FST_REQUIRE(pv.n_items > 0 && pv.items_per_wg == WG_ITEMS && pv.n_items % WG_ITEMS == 0,
@@ -1699,20 +1726,12 @@ extern "C" int fst_conv_wgrad(const float* x0, int64_t x0_bs, const float* x1, i
   FST_REQUIRE(msplit >= 0 && msplit <= M && (msplit == M || dy2 != nullptr), "fst_conv_wgrad: bad msplit=%d", msplit);
   FST_REQUIRE(msplit == M || msplit % 2 == 0, "fst_conv_wgrad: a split dy needs an even msplit (got %d)", msplit);
   FST_REQUIRE(B > 0 && L > 0 && ksplit >= 1, "fst_conv_wgrad: bad sizes");
-  bool needs_x1 = false;
-  for (int q = 0; q < pv.n_chunks; ++q) needs_x1 |= pv.chunk[4 * q] == 1;
-  FST_REQUIRE(!needs_x1 || x1 != nullptr, "fst_conv_wgrad: plan reads input 1 but x1 is null");
-  {
-    int rows_in[2] = {0, 0};
-    for (int q = 0; q < pv.n_chunks; ++q) {
-      const int32_t* c = pv.chunk + 4 * q;
-      rows_in[c[0]] = rows_in[c[0]] > c[1] + c[2] ? rows_in[c[0]] : c[1] + c[2];
-    }
-    FST_REQUIRE(B == 1 || (x0_bs >= (int64_t)rows_in[0] * L && (!needs_x1 || x1_bs >= (int64_t)rows_in[1] * L) &&
-                           dy_bs >= (int64_t)msplit * L && (msplit == M || dy2_bs >= (int64_t)(M - msplit) * L)),
-                "fst_conv_wgrad: a batch stride (x0 %lld, x1 %lld, dy %lld, dy2 %lld) is smaller than the rows it strides over",
-                (long long)x0_bs, (long long)x1_bs, (long long)dy_bs, (long long)dy2_bs);
-  }
+  FST_REQUIRE(!ps.needs_x1 || x1 != nullptr, "fst_conv_wgrad: plan reads input 1 but x1 is null");
+  FST_REQUIRE(input_strides_hold(ps, B, L, x0_bs, x1_bs) &&
+                  (B == 1 || (dy_bs >= (int64_t)msplit * L && (msplit == M || dy2_bs >= (int64_t)(M - msplit) * L))),
+              "fst_conv_wgrad: a batch stride (x0 %lld, x1 %lld, dy %lld, dy2 %lld) is smaller than the rows it strides over",
+              (long long)x0_bs, (long long)x1_bs, (long long)dy_bs, (long long)dy2_bs);
+  FST_REQUIRE(ps.any_live, "fst_conv_wgrad: plan has no live taps");
   for (int i = 0; i < pv.n_items; ++i) {
     const int32_t* it = pv.item + 4 * i;
     FST_REQUIRE(it[1] < pv.n_chunks && (it[1] < 0 || (it[0] >= 0 && it[0] < pv.n_mgroups && it[2] >= 0)),
@@ -1728,18 +1747,8 @@ extern "C" int fst_conv_wgrad(const float* x0, int64_t x0_bs, const float* x1, i
   p.tiles_per_seq = (L + TW - 1) / TW;
   const int n_tiles = B * p.tiles_per_seq;
   p.ksplit = ksplit < n_tiles ? ksplit : n_tiles;
-  int max_w = 0;
-  bool wide = false;
-  for (int q = 0; q < pv.n_chunks; ++q)
-    for (int g = 0; g < pv.n_mgroups; ++g) {
-      const int32_t* e = pv.mg + 4 * (g * pv.n_chunks + q);
-      if (e[1] > e[0]) {
-        int w = (e[1] - 1 - e[0]) * pv.dil + TW;
-        max_w = max_w > w ? max_w : w;
-        if (e[1] > e[0] + 1) wide = true;
-      }
-    }
-  FST_REQUIRE(max_w > 0, "fst_conv_wgrad: plan has no live taps");
+  const bool wide = ps.wide;
+  const int max_w = ps.span_single * pv.dil + TW;
   p.ldw = max_w | 1;                                     // odd stride: A-operand lanes walk channels
   p.region_floats = (pv.chunk_cap * p.ldw + 3) / 4 * 4;
   p.n_regions = 1;
@@ -1752,7 +1761,7 @@ extern "C" int fst_conv_wgrad(const float* x0, int64_t x0_bs, const float* x1, i
     }
     p.n_regions = p.n_regions > distinct ? p.n_regions : distinct;
   }
-  FST_REQUIRE(x0_mul_off == 0 || (!wide && !needs_x1 && x0_mul_off % 4 == 0),
+  FST_REQUIRE(x0_mul_off == 0 || (!wide && !ps.needs_x1 && x0_mul_off % 4 == 0),
               "fst_conv_wgrad: a product operand (x0_mul_off=%lld) needs a single-input, single-tap plan and a multiple-of-4 offset",
               (long long)x0_mul_off);
   if (wide) {
@@ -1769,15 +1778,9 @@ extern "C" int fst_conv_wgrad(const float* x0, int64_t x0_bs, const float* x1, i
   // 16-byte loads for narrow windows when every tile row address is 16-B aligned
   const bool shifts4 = pv.pad_left % 4 == 0 && (pv.ntaps == 1 || pv.dil % 4 == 0);
   // windowed plans: the window of every (M-group, chunk) must also START on a multiple of 4 samples and be a
-  // multiple of 4 wide
-  bool starts4 = true;
-  for (int q = 0; q < pv.n_chunks; ++q)
-    for (int g = 0; g < pv.n_mgroups; ++g) {
-      const int32_t* e = pv.mg + 4 * (g * pv.n_chunks + q);
-      if (e[1] > e[0] && ((e[0] * pv.dil - pv.pad_left) % 4 != 0 || ((e[1] - 1 - e[0]) * pv.dil) % 4 != 0)) starts4 = false;
-    }
-  // (single-tap windows take any shift: the kernel starts the row's 16-byte loads `shift mod 4` samples early)
-  const bool vec = L % 4 == 0 && (wide ? starts4 : true) && x0_bs % 4 == 0 && x1_bs % 4 == 0 && dy_bs % 4 == 0 &&
+  // multiple of 4 wide (starts4; single-tap windows take any shift: the kernel starts the row's 16-byte loads
+  // `shift mod 4` samples early)
+  const bool vec = L % 4 == 0 && (!wide || ps.starts4) && x0_bs % 4 == 0 && x1_bs % 4 == 0 && dy_bs % 4 == 0 &&
                    dy2_bs % 4 == 0 && fst_aligned16(x0) && fst_aligned16(x1) && fst_aligned16(dy) && fst_aligned16(dy2);
   void (*fn)(WgradParams, const int32_t*);
   // VEC: 0 dword staging, 1 16-byte staging, 2 16-byte staging of single-tap windows whose shift is not a multiple of 4

@@ -59,6 +59,7 @@ static inline int plan_expected_len(const int32_t* p) {
 // so nothing but launches happens while a stream is being captured into a hipGraph).
 int fst_allow_full_lds(const void* fn, const char* who);
 int fst_cu_count(void);   // compute units of the current device (0 if the query fails)
+static inline int fst_cu_count_or(int fallback) { const int cus = fst_cu_count(); return cus > 0 ? cus : fallback; }
 
 // Launch-route record of the time-as-k weight gradients and the fused WN kernels (fst_wn_last_route; storage in wn_wgrad.hip,
 // thread-local, host side only).  A launcher clears it on entry (family 0) and fills it from its own dispatch variables right

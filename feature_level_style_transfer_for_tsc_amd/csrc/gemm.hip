@@ -212,7 +212,7 @@ __global__ __launch_bounds__(256) void gemm_reduce_kernel(GemmParams p) {
 
 // tile size and K split for a shape: the same answer in fst_gemm_workspace_floats and fst_gemm
 static void gm_geometry(int M, int N, int K, int* big, int* ksplit, int* k_per_split) {
-  const int cus = fst_cu_count() > 0 ? fst_cu_count() : 256;
+  const int cus = fst_cu_count_or(256);
   const long long t128 = (long long)((M + 127) / 128) * ((N + 127) / 128);
   const int kmax = K / 128 > 1 ? K / 128 : 1;              // at least four stages per split
   *big = M >= 96 && N >= 96 && t128 * kmax >= cus / 2;

@@ -731,7 +731,7 @@ extern "C" int fst_wn_stack_fwd(const float* const* a_in, const int64_t* a_bs, c
     q.CH = wn_ch(n); q.CH2 = wn_ch2(h); q.tiles_per_seq = L / 256; q.n_wg = 0;
   }
   p.nl = nl;
-  const int cus = fst_cu_count() > 0 ? fst_cu_count() : 256;
+  const int cus = fst_cu_count_or(256);
   if (int rc = fst_allow_full_lds((const void*)wn_stack_fwd_kernel, "fst_wn_stack_fwd")) return rc;
   fst_wn_set_route(FST_WN_ROUTE_STACK_FWD, 8, 0, 0, 0, B < cus ? B : cus, 1, 1, L / 256, 3, nl, WN_FWD_LDS(8));
   hipLaunchKernelGGL(wn_stack_fwd_kernel, dim3((unsigned)(B < cus ? B : cus)), dim3(512), WN_FWD_LDS(8), (hipStream_t)stream, p);
@@ -759,7 +759,7 @@ extern "C" int fst_wn_layer_fwd(const float* a, int64_t a_bs, const float* u0, i
   p.B = B; p.L = L; p.n = n; p.h = h; p.dil = dil; p.first = first ? 1 : 0; p.last = last ? 1 : 0;
   p.CH = wn_ch(n); p.CH2 = wn_ch2(h);
   // 256-sample tiles (8 waves) when they divide the sequence and still fill the chip, else 128-sample tiles (4 waves, two per CU)
-  const int cus = fst_cu_count() > 0 ? fst_cu_count() : 256;
+  const int cus = fst_cu_count_or(256);
   const int nw = (L % 256 == 0 && (long long)B * (L / 256) >= cus) ? 8 : 4;
   const int tn = 32 * nw;
   p.tiles_per_seq = (L + tn - 1) / tn;
@@ -1013,8 +1013,8 @@ extern "C" int fst_wn_layer_bwd(const float* d_a, const float* d_out, const floa
 //   * a workgroup = 8 waves = one batch element × 256 time samples (each wave 32 samples × 5 row blocks): the weight bytes
 //     per output sample are half those of a 128-sample tile.
 // Image: per 16-channel chunk 13 row blocks × (1 KiB hi + 1 KiB lo): [tap 0: 4 blocks of d_a rows][tap 1: 4 + the d_u0 block]
-// [tap 2: 4]; tap τ multiplies dg at t + (1 − τ)·dil.  Ring of 2 slots: the launcher takes 3 when they fit 160 KiB, but with
-// 512-sample tiles a slot is 61 696 bytes at dilation 1 and grows with the dilation, so they never do (ns of fst_wn_last_route).
+// [tap 2: 4]; tap τ multiplies dg at t + (1 − τ)·dil.  Ring of 2 slots (ns of fst_wn_last_route): with 512-sample tiles a slot is
+// 61 696 bytes at dilation 1 and grows with the dilation, so three never fit 160 KiB.
 // ------------------------------------------------------------------------------------------------
 #define DG_NCB 2                                     // 32-sample column blocks per wave
 #define DG_TN (8 * 32 * DG_NCB)                       // time samples per workgroup (8 waves)
@@ -1088,7 +1088,7 @@ struct WnDgradParams {
   int nblkw;            // 32-sample column blocks of the window
   int gsw;              // bytes per 8-channel row group of the window
   int slot;             // bytes per ring slot
-  int ns;               // ring slots (3 if they fit the LDS, else 2; with DG_TN = 512 always 2)
+  int ns;               // ring slots (with DG_TN = 512 always 2: three never fit the LDS)
 };
 
 template <int N>
@@ -1261,17 +1261,13 @@ static inline void wn_dgrad_geometry(int dil, int* nblkw, int* gsw, int* slot) {
   *slot = DG_A_BYTES + 2 * *gsw;
 }
 
-// 1 when fst_wn_layer_dgrad serves (n, h, dil): two ring slots fit the 160 KiB of LDS and the counted-wait table covers a stage
-// (with 512-sample tiles: up to dilation 128, i.e. WN stacks of up to 8 layers); the host side falls back to the generic
-// data-gradient launch otherwise.
+// 1 when fst_wn_layer_dgrad serves (n, h, dil): two ring slots fit the 160 KiB of LDS (with 512-sample tiles: up to dilation
+// 128, i.e. WN stacks of up to 8 layers); the host side falls back to the generic data-gradient launch otherwise.
 extern "C" int fst_wn_dgrad_fits(int n, int h, int dil) {
   if (!(n > 0 && n <= 128 && h > 0 && h <= 32 && dil > 0)) return 0;
   int nblkw, gsw, slot;
   wn_dgrad_geometry(dil, &nblkw, &gsw, &slot);
-  if (2 * slot > 160 * 1024) return 0;
-  const int ns = 3 * slot <= 160 * 1024 ? 3 : 2;
-  const int NI = DG_A_BLOCKS * 2 + 2 * nblkw;
-  return ((NI + 7) / 8) * (ns - 2) <= 16 ? 1 : 0;
+  return 2 * slot <= 160 * 1024 ? 1 : 0;
 }
 
 extern "C" int fst_wn_layer_dgrad(const float* dg, const void* image, int64_t image_bytes, const float* d_a, float* d_a_new,
@@ -1298,14 +1294,12 @@ extern "C" int fst_wn_layer_dgrad(const float* dg, const void* image, int64_t im
   FST_REQUIRE(row_sums == nullptr || row_sums_rows == p.n_wg, "fst_wn_layer_dgrad: row_sums has %lld rows, the launch has %d "
               "workgroups (B x ceil(L/512))", (long long)row_sums_rows, p.n_wg);
   wn_dgrad_geometry(dil, &p.nblkw, &p.gsw, &p.slot);
-  p.ns = 3 * p.slot <= 160 * 1024 ? 3 : 2;
+  p.ns = 2;
   FST_REQUIRE(2 * p.slot <= 160 * 1024, "fst_wn_layer_dgrad: dilation %d needs a %d-byte window slot: too large for LDS", dil, p.slot);
-  const int NI = DG_A_BLOCKS * 2 + 2 * p.nblkw;
-  FST_REQUIRE(((NI + 7) / 8) * (p.ns - 2) <= 16, "fst_wn_layer_dgrad: %d pieces per stage exceed the counted-wait table", NI);
   size_t lds_bytes = (size_t)p.ns * p.slot;
   if (lds_bytes < 8 * WN_TILE_BYTES + 4096) lds_bytes = 8 * WN_TILE_BYTES + 4096;   // tiles + the per-wave row-sum arrays
   if (int rc = fst_allow_full_lds((const void*)wn_layer_dgrad_kernel, "fst_wn_layer_dgrad")) return rc;
-  // one persistent workgroup per CU; with a ring of one slot only (never: ns >= 2) the next tile could not start early
+  // one persistent workgroup per CU (two rings do not fit one)
   int grid = p.n_wg;
   const int cus = fst_cu_count();
   if (cus > 0 && grid > cus && (size_t)2 * lds_bytes > 160 * 1024) grid = cus;
@@ -1743,7 +1737,7 @@ extern "C" int fst_wn_stack_bwd(const float* const* ts, const void* const* img_b
   p.d_out = d_out; p.d_u0 = d_u0; p.d_u0_bs = d_u0_bs;
   p.nl = nl; p.B = B; p.L = L; p.n = n; p.h = h; p.CH = wn_ch(n); p.CHK = (2 * n + 15) / 16;
   if (int rc = fst_allow_full_lds((const void*)wn_stack_bwd_kernel, "fst_wn_stack_bwd")) return rc;
-  const int cus = fst_cu_count() > 0 ? fst_cu_count() : 256;
+  const int cus = fst_cu_count_or(256);
   const int grid = B < cus ? B : cus;                    // one resident workgroup per CU walks its batch elements
   fst_wn_set_route(FST_WN_ROUTE_STACK_BWD, 0, 0, 0, 0, grid, 1, 1, 1, 2, nl, (int)lds_bytes);
   hipLaunchKernelGGL(wn_stack_bwd_kernel, dim3((unsigned)grid), dim3(512), lds_bytes, (hipStream_t)stream, p);

@@ -555,7 +555,7 @@ static int ww_geometry(int kind, int B, int L, int n, int h, int last, int n_set
   p->B = B; p->L = L;
   p->tiles_per_seq = L / WW_TT;
   p->n_tiles = B * p->tiles_per_seq;
-  const int cus = fst_cu_count() > 0 ? fst_cu_count() : 256;
+  const int cus = fst_cu_count_or(256);
   int ks = cus / p->n_groups;
   if (ks > p->n_tiles * n_sets) ks = p->n_tiles * n_sets;
   if (ks < n_sets) ks = n_sets;                                    // every operand set has a workgroup of its own
@@ -680,7 +680,7 @@ extern "C" int fst_wn_wgrad_rs(const float* const* d_a, const float* const* d_ou
 extern "C" int64_t fst_nt_gemm_workspace_floats(int M, int N, int K) {
   if (!(M > 0 && M <= WW_MROWS && N > 0 && K > 0 && K % WW_TT == 0)) return -1;
   const int n_groups = ((N + 31) / 32 + 3) / 4;
-  const int cus = fst_cu_count() > 0 ? fst_cu_count() : 256;
+  const int cus = fst_cu_count_or(256);
   int ks = cus / n_groups;
   if (ks > K / WW_TT) ks = K / WW_TT;
   if (ks < 1) ks = 1;
@@ -706,7 +706,7 @@ extern "C" int fst_nt_gemm(const float* A, const float* Bm, float* C, float* wor
   p.B = 1; p.L = K;
   p.tiles_per_seq = K / WW_TT;
   p.n_tiles = p.tiles_per_seq;
-  const int cus = fst_cu_count() > 0 ? fst_cu_count() : 256;
+  const int cus = fst_cu_count_or(256);
   int ks = cus / p.n_groups;
   if (ks > p.n_tiles) ks = p.n_tiles;
   if (ks < 1) ks = 1;
@@ -758,7 +758,7 @@ static void tap_geometry(int B, int L, int M, int C, int ntaps, WwParams* p) {
   p->B = B; p->L = L;
   p->tiles_per_seq = L / WW_TT;
   p->n_tiles = B * p->tiles_per_seq;
-  const int cus = fst_cu_count() > 0 ? fst_cu_count() : 256;
+  const int cus = fst_cu_count_or(256);
   int ks = cus / p->n_groups;
   if (ks > p->n_tiles) ks = p->n_tiles;
   if (ks < 1) ks = 1;
@@ -1127,7 +1127,7 @@ static int tz_geometry(int B, int L, int M, int C, int K, int pad, TzParams* p) 
   p->Kcols = p->n_groups * TZ_CW * 96;
   p->tiles_per_seq = L / WW_TT;
   p->n_tiles = B * p->tiles_per_seq;
-  const int cus = fst_cu_count() > 0 ? fst_cu_count() : 256;
+  const int cus = fst_cu_count_or(256);
   int ks = cus / (p->n_groups * p->m_halves);
   if (ks > p->n_tiles) ks = p->n_tiles;
   if (ks < 1) ks = 1;

@@ -90,8 +90,8 @@ def test_the_case_lists_span_what_the_issue_asks_for():
 
 
 def test_no_dilation_gets_a_three_slot_dgrad_ring():
-    """fst_wn_layer_dgrad picks 3 ring slots when 3·slot fits 160 KiB; with 512-sample tiles a slot is 61 696 bytes at
-    dilation 1 and grows with the dilation, so the ring always has 2."""
+    """fst_wn_layer_dgrad takes 2 ring slots without asking whether 3 would fit 160 KiB: with 512-sample tiles a slot is
+    61 696 bytes at dilation 1 and grows with the dilation, so they never do."""
     fused = open(os.path.join(CSRC, "wn_fused.hip")).read()
     assert re.search(r"#define DG_TN \(8 \* 32 \* DG_NCB\)", fused) and re.search(r"#define DG_NCB 2\b", fused)
     assert re.search(r"\*nblkw = \(DG_TN \+ 2 \* dil \+ 3 \+ 31\) / 32;", fused) and "*slot = DG_A_BYTES + 2 * *gsw;" in fused
