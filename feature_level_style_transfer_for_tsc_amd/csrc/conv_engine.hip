@@ -12,7 +12,7 @@
 //
 // Two arithmetics.  f32: v_mfma_f32_32x32x2_f32 (exact fp32 chain, 64 FLOP/clk/SIMD).  Split-bf16 ("bf16x3"):
 // every fp32 operand v = hi + lo with hi = bf16(v), lo = bf16(v - hi) (round to nearest), a product formed as
-// hi·hi + hi·lo + lo·hi by three v_mfma_f32_32x32x16_bf16 with fp32 accumulation — relative error of a product
+// hi·hi + hi·lo + lo·hi by three 32x32x16 bf16 MFMAs with fp32 accumulation — relative error of a product
 // <= 3·2^-18 (measured 5e-6 of the output scale) at a third of the 2.5 PFLOP/s bf16 peak instead of 157 TFLOP/s.
 // Weights are split when packed (fst_pack_weights_bf16x3), activations in registers on their way to the MFMA.
 //
@@ -527,7 +527,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_pipe_kernel(ConvGemmParams p
 // forward / data-gradient on the bf16 matrix cores with split operands ("bf16x3").
 //
 // Same plans, stages and epilogue as conv_gemm_pipe_kernel; the product of a stage is formed as
-// hi(A)·hi(B) + hi(A)·lo(B) + lo(A)·hi(B) by three v_mfma_f32_32x32x16_bf16 (fp32 accumulate), where
+// hi(A)·hi(B) + hi(A)·lo(B) + lo(A)·hi(B) by three 32x32x16 bf16 MFMAs (fp32 accumulate), where
 // v = hi + lo + O(2^-18 |v|), hi = bf16_rne(v), lo = bf16_rne(v − hi).  One stage (≤ 16 channels of one tap) is
 // exactly one 16-deep k-step: 3·MB·NB MFMAs of 32 cycles — far shorter than a global round trip, so operands
 // arrive through a 3-slot LDS ring filled by LDS-DMA (global_load_lds_dwordx4: no staging registers, two stages
@@ -649,15 +649,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_bf3_kernel(ConvGemmParams p,
       float v[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = *reinterpret_cast<const float*>(bp + j * 128);
-      u32x4 h, l;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        unsigned hh, ll;
-        split_bf16_pair(v[2 * j], v[2 * j + 1], hh, ll);
-        h[j] = hh; l[j] = ll;
-      }
-      bh[nb] = __builtin_bit_cast(bf16x8, h);
-      bl[nb] = __builtin_bit_cast(bf16x8, l);
+      split_bf16x8(v, bh[nb], bl[nb]);
     }
 #ifdef FST_STAMPS
     asm volatile("" ::"v"(bh[0]), "v"(bl[0]), "v"(bh[NB - 1]), "v"(bl[NB - 1]));
@@ -666,14 +658,10 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_bf3_kernel(ConvGemmParams p,
     FST_ACC(4, td, te);                                // B fragments: LDS reads + split
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) {
-      const bf16x8 ah = *reinterpret_cast<const bf16x8*>(base + mb * 2048 + lane * 16);
-      const bf16x8 al = *reinterpret_cast<const bf16x8*>(base + mb * 2048 + 1024 + lane * 16);
+      bf16x8 ah, al;
+      lds_read_a_frag(base, mb, lane, ah, al);
 #pragma unroll
-      for (int nb = 0; nb < NB; ++nb) {
-        acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[nb], acc[mb][nb], 0, 0, 0);
-        acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[nb], acc[mb][nb], 0, 0, 0);
-        acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[nb], acc[mb][nb], 0, 0, 0);
-      }
+      for (int nb = 0; nb < NB; ++nb) mfma_bf3(acc[mb][nb], ah, al, bh[nb], bl[nb]);
     }
     FST_T(tf);
     FST_ACC(5, te, tf);                                // A fragments + MFMAs (issue)
@@ -825,11 +813,7 @@ __global__ __launch_bounds__(256, 2) void conv_win_bf3_kernel(ConvGemmParams p, 
         for (int mb = 0; mb < MB; ++mb) {
           const bf16x8 a_h = __builtin_bit_cast(bf16x8, ah[mb]), a_l = __builtin_bit_cast(bf16x8, al[mb]);
 #pragma unroll
-          for (int nb = 0; nb < NB; ++nb) {
-            acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_l, bh[nb], acc[mb][nb], 0, 0, 0);
-            acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_h, bl[nb], acc[mb][nb], 0, 0, 0);
-            acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_h, bh[nb], acc[mb][nb], 0, 0, 0);
-          }
+          for (int nb = 0; nb < NB; ++nb) mfma_bf3(acc[mb][nb], a_h, a_l, bh[nb], bl[nb]);
         }
         ++tap;
       };
@@ -950,9 +934,7 @@ __global__ __launch_bounds__(256, 2) void conv_win_rows_kernel(ConvGemmParams p,
         for (int nb = 0; nb < NB; ++nb) {
           const bf16x8 bh = *reinterpret_cast<const bf16x8*>(hi_img + roff + nb * 1024);
           const bf16x8 bl = *reinterpret_cast<const bf16x8*>(lo_img + roff + nb * 1024);
-          acc[0][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_l, bh, acc[0][nb], 0, 0, 0);
-          acc[0][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_h, bl, acc[0][nb], 0, 0, 0);
-          acc[0][nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_h, bh, acc[0][nb], 0, 0, 0);
+          mfma_bf3(acc[0][nb], a_h, a_l, bh, bl);
         }
         ++tap;
       };
@@ -1616,17 +1598,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradParams p, const
 #pragma unroll
       for (int ks = 0; ks < TW / 16; ++ks) {
         const float* ap = lds + roff + ks * 16 + 8 * half;
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = ap[j];
-        u32x4 h, l;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          unsigned hh, ll;
-          split_bf16_pair(v[2 * j], v[2 * j + 1], hh, ll);
-          h[j] = hh; l[j] = ll;
-        }
-        const bf16x8 ah = __builtin_bit_cast(bf16x8, h), al = __builtin_bit_cast(bf16x8, l);
+        bf16x8 ah, al;
+        split_bf16x8(*reinterpret_cast<const float(*)[8]>(ap), ah, al);   // (the 8 floats in place: a local copy changes five instances' schedule)
         const int boff = l31 * DYB + (ks * 16 + 8 * half) * 2;
 #pragma unroll
         for (int i = 0; i < WG_ITEMS; ++i)
@@ -1637,9 +1610,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradParams p, const
               if (blk >= nblk_live) continue;            // output-channel blocks beyond M (M = 25: three of four) hold zeros
             const bf16x8 bh = *reinterpret_cast<const bf16x8*>(dyh + blk * 32 * DYB + boff);
             const bf16x8 bl = *reinterpret_cast<const bf16x8*>(dyl + blk * 32 * DYB + boff);
-            acc[i][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[i][cb], 0, 0, 0);
-            acc[i][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[i][cb], 0, 0, 0);
-            acc[i][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[i][cb], 0, 0, 0);
+            mfma_bf3(acc[i][cb], ah, al, bh, bl);
           }
       }
       continue;

@@ -165,7 +165,7 @@ __global__ __launch_bounds__(256) void cpc_fwd_kernel(CpcParams p) {
 
 // ------------------------------------------------------------------------------------------------
 // Forward, one panel (Bc <= 256), C <= 64: the cross-Gram on the bf16 matrix cores with split operands
-// (hi·hi + hi·lo + lo·hi on v_mfma_f32_32x32x16_bf16, fp32 accumulation: ≈5e-6 of the logit scale), K = C padded to 64.
+// (hi·hi + hi·lo + lo·hi on the 32x32x16 bf16 MFMA, fp32 accumulation: ≈5e-6 of the logit scale), K = C padded to 64.
 //
 // cpc_fwd_kernel reads enc_i[b][c] = feat[b][c][t0 + i] in place: for a fixed step every element sits in a different 128-byte
 // line, so a workgroup pulls 12.8 k lines for 51 KB of operand and the launch moves 130 MB for 39 MB of operands; and its
@@ -249,9 +249,7 @@ __global__ __launch_bounds__(512) void cpc_gram_bf3_kernel(CpcParams p, const fl
     for (int ks = 0; ks < 4; ++ks) {
       const bf16x8 bh = *reinterpret_cast<const bf16x8*>(eh + (r0 + l31) * CG_ROWB + ks * 32 + half * 16);
       const bf16x8 bl = *reinterpret_cast<const bf16x8*>(el + (r0 + l31) * CG_ROWB + ks * 32 + half * 16);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[ks], bh, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[ks], bl, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[ks], bh, acc, 0, 0, 0);
+      mfma_bf3(acc, ah[ks], al[ks], bh, bl);
     }
     // register r of a lane: prediction j = wave·32 + (r&3) + 8(r>>2) + 4·half, encoding b = r0 + l31
     const int jb = wave * 32 + 4 * half;

@@ -9,7 +9,6 @@
 
 #define FST_PLAN_HDR FST_PLAN_HEADER   // 16 ints; see plan.py (fields 0..10 used)
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 void fst_set_error(const char* fmt, ...);

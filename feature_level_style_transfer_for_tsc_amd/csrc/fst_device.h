@@ -7,6 +7,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // The split-bf16 product: v = hi + lo + O(2^-18 |v|) with hi = bf16_rne(v), lo = bf16_rne(v - hi); a product is formed as
 // hi·hi + hi·lo + lo·hi.  Two floats -> (hi pair, lo pair), each a dword of two round-to-nearest bf16 (first element in the low half).
@@ -15,6 +16,35 @@ __device__ __forceinline__ void split_bf16_pair(float a, float b, unsigned& hi, 
   hi = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
   const f32x2 r = {a - __uint_as_float(hi << 16), b - __uint_as_float(hi & 0xffff0000u)};
   lo = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2));
+}
+
+// Eight floats -> one lane's hi and lo fragments of v_mfma_f32_32x32x16_bf16 (element j of the fragment = v[j]).
+__device__ __forceinline__ void split_bf16x8(const float (&v)[8], bf16x8& hi, bf16x8& lo) {
+  u32x4 h, l;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    unsigned hh, ll;
+    split_bf16_pair(v[2 * j], v[2 * j + 1], hh, ll);
+    h[j] = hh; l[j] = ll;
+  }
+  hi = __builtin_bit_cast(bf16x8, h);
+  lo = __builtin_bit_cast(bf16x8, l);
+}
+
+// acc += a·b as lo(a)·hi(b) + hi(a)·lo(b) + hi(a)·hi(b), fp32 accumulation.  The order is part of the arithmetic: the two
+// small terms (2^-9 of the product) are added first and hi·hi last, and every accumulation of the project was validated
+// bit for bit in this order — reordering the three changes the rounding of each fp32 add, i.e. the results every parity
+// tolerance and every recorded output were taken with.  lo·lo (2^-18) is dropped.
+__device__ __forceinline__ void mfma_bf3(f32x16& acc, bf16x8 ah, bf16x8 al, bf16x8 bh, bf16x8 bl) {
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
+}
+
+// The (hi, lo) A fragments of row block mb of a packed weight stage at base: per block 1 KiB hi then 1 KiB lo, 16 bytes per lane.
+__device__ __forceinline__ void lds_read_a_frag(const char* base, int mb, int lane, bf16x8& ah, bf16x8& al) {
+  ah = *reinterpret_cast<const bf16x8*>(base + mb * 2048 + lane * 16);
+  al = *reinterpret_cast<const bf16x8*>(base + mb * 2048 + 1024 + lane * 16);
 }
 
 // wait until at most N of this wave's vector-memory operations (loads, LDS-DMA pieces) are still in flight

@@ -8,7 +8,7 @@
 // products of a Linear layer without a transposed copy:   y = x·Wᵀ (A = x [M][K], B = W [N][K]),   dx = g·W (A = g [M][N], B = W read
 // [K'=N][rows=K]),   dW = gᵀ·x (A = g read [K'=M][rows=N], B = x read [K'=M][rows=K]).
 //
-// Arithmetic: split-bf16 (hi·hi + hi·lo + lo·hi on v_mfma_f32_32x32x16_bf16, fp32 accumulate) like every other product of the
+// Arithmetic: split-bf16 (hi·hi + hi·lo + lo·hi on the 32x32x16 bf16 MFMA, fp32 accumulate) like every other product of the
 // step.  A 256-thread workgroup (2 × 2 waves) owns a 128 × 128 or 64 × 64 tile of C; a stage = 32 k: every thread fetches its
 // share of the two operand tiles into registers one stage ahead (16-byte loads along k where the layout allows, coalesced dword
 // loads across rows for k-major operands), splits fp32 → bf16 hi / lo ONCE per element and writes rows of 32 bf16 (80-byte pitch:
@@ -93,15 +93,10 @@ __device__ __forceinline__ void gm_stage(const float (&v)[ROWS / 8], char* hi_im
     const int off = (tid % ROWS) * GM_PITCH + 2 * KR * (tid / ROWS);
 #pragma unroll
     for (int c = 0; c < KR / 8; ++c) {
-      u32x4 h, l;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        unsigned hh, ll;
-        split_bf16_pair(v[8 * c + 2 * e], v[8 * c + 2 * e + 1], hh, ll);
-        h[e] = hh; l[e] = ll;
-      }
-      *reinterpret_cast<u32x4*>(hi_img + off + 16 * c) = h;
-      *reinterpret_cast<u32x4*>(lo_img + off + 16 * c) = l;
+      bf16x8 h, l;
+      split_bf16x8(*reinterpret_cast<const float(*)[8]>(&v[8 * c]), h, l);   // (elements 8c..8c+7 in place: a local copy changes the schedule)
+      *reinterpret_cast<bf16x8*>(hi_img + off + 16 * c) = h;
+      *reinterpret_cast<bf16x8*>(lo_img + off + 16 * c) = l;
     }
   }
 }
@@ -161,11 +156,7 @@ __global__ __launch_bounds__(256, TM * TN == 4 ? 2 : 3) void gemm_bf3_kernel(Gem
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-        }
+        for (int j = 0; j < TN; ++j) mfma_bf3(acc[i][j], ah[i], al[i], bh[j], bl[j]);
     }
   }
 

@@ -14,7 +14,7 @@
 // three-launch form.
 //
 // Structure (shared with conv_gemm_bf3_kernel): split-bf16 products — hi·hi + hi·lo + lo·hi on
-// v_mfma_f32_32x32x16_bf16, fp32 accumulation — operands through a 3-slot LDS ring filled by LDS-DMA, one raw
+// the 32x32x16 bf16 MFMA, fp32 accumulation — operands through a 3-slot LDS ring filled by LDS-DMA, one raw
 // s_barrier per 16-deep stage behind a counted vmcnt.  A workgroup = 4 waves = one batch element × 128 time samples;
 // every wave owns ALL 256 (padded) output rows of its 32 samples, so that
 //   * row m (tanh half) and row m+128 (sigmoid half) of GEMM 1 sit in the same lane and register index (blocks b and b+4):
@@ -59,7 +59,7 @@ __host__ __device__ __forceinline__ void wn_stage_chunk_tap(int k, int CH, int& 
 // weight image
 //   [S1 stages of GEMM 1][8 k-steps of GEMM 2][16 B of zeros][16 B of ones]
 // one stage / k-step = 8 row blocks × (64 lanes × 8 bf16 hi, 64 lanes × 8 bf16 lo) = 16 KiB, the A fragments of
-// v_mfma_f32_32x32x16_bf16 (lane l: row l&31 of the block, k = 8·(l>>5) + j).
+// the 32x32x16 bf16 MFMA (lane l: row l&31 of the block, k = 8·(l>>5) + j).
 //   GEMM 1  stage k < 3·CH = (chunk c < CH = ⌈n/16⌉, tap) in wn_stage_chunk_tap order: channels 16c.. of `a` at tap `tap`;
 //           then CH2 = ⌈(h+1)/16⌉ stages
 //           of the conditioning input (zero shift) whose channel h is the constant-one row carrying b_in + b_cond.
@@ -495,22 +495,13 @@ __device__ __forceinline__ void wn_fwd_tile(WnFwdArgs& p, const int b, const int
     // of their MFMAs — as the first form of this loop did, one `ds_read_b128; s_waitcnt lgkmcnt(0)` per fragment — every one of the
     // 16 reads of a stage exposed the LDS latency to a wave with nothing else to issue (115 such waits in the kernel's code)
     bf16x8 fah[2], fal[2];
-    auto a_frag = [&](int mb) {
-      fah[mb % 2] = *reinterpret_cast<const bf16x8*>(base + mb * 2048 + lane * 16);
-      fal[mb % 2] = *reinterpret_cast<const bf16x8*>(base + mb * 2048 + 1024 + lane * 16);
-    };
+    auto a_frag = [&](int mb) { lds_read_a_frag(base, mb, lane, fah[mb % 2], fal[mb % 2]); };
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = *reinterpret_cast<const float*>(bp + j * 128);
     a_frag(0);                                             // lands under the split of the B fragment below
-    u32x4 bh4, bl4;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      unsigned hh, ll;
-      split_bf16_pair(v[2 * j], v[2 * j + 1], hh, ll);
-      bh4[j] = hh; bl4[j] = ll;
-    }
-    const bf16x8 bh = __builtin_bit_cast(bf16x8, bh4), bl = __builtin_bit_cast(bf16x8, bl4);
+    bf16x8 bh, bl;
+    split_bf16x8(v, bh, bl);
 #ifdef FST_STAMPS
     asm volatile("" ::"v"(bh), "v"(bl));
 #endif
@@ -519,10 +510,7 @@ __device__ __forceinline__ void wn_fwd_tile(WnFwdArgs& p, const int b, const int
 #pragma unroll
     for (int mb = 0; mb < 8; ++mb) {
       if (mb + 1 < 8) a_frag(mb + 1);
-      const bf16x8 ah = fah[mb % 2], al = fal[mb % 2];
-      acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[mb], 0, 0, 0);
-      acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[mb], 0, 0, 0);
-      acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[mb], 0, 0, 0);
+      mfma_bf3(acc[mb], fah[mb % 2], fal[mb % 2], bh, bl);
       if (mb < NPW1) {
         __builtin_amdgcn_sched_barrier(0);
         issue_piece(nxt, mb);
@@ -580,15 +568,10 @@ __device__ __forceinline__ void wn_fwd_tile(WnFwdArgs& p, const int b, const int
     }
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      u32x4 h4, l4;
+      float v[8];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        unsigned hh, ll;
-        split_bf16_pair(av[8 * s + 2 * j], av[8 * s + 2 * j + 1], hh, ll);
-        h4[j] = hh; l4[j] = ll;
-      }
-      bh2[2 * blk + s] = __builtin_bit_cast(bf16x8, h4);
-      bl2[2 * blk + s] = __builtin_bit_cast(bf16x8, l4);
+      for (int j = 0; j < 8; ++j) v[j] = av[8 * s + j];
+      split_bf16x8(v, bh2[2 * blk + s], bl2[2 * blk + s]);
     }
   }
   asm volatile("" ::: "memory");                       // the stores stay in front of the LDS-DMA issued below
@@ -606,20 +589,12 @@ __device__ __forceinline__ void wn_fwd_tile(WnFwdArgs& p, const int b, const int
     const char* base = ldsb + slot * F_SLOT;
     // (fragments one row block ahead, as in GEMM 1; on the last layer the residual-row blocks 0-3 are neither read nor multiplied)
     bf16x8 fah[2], fal[2];
-    auto a_frag = [&](int mb) {
-      fah[mb % 2] = *reinterpret_cast<const bf16x8*>(base + mb * 2048 + lane * 16);
-      fal[mb % 2] = *reinterpret_cast<const bf16x8*>(base + mb * 2048 + 1024 + lane * 16);
-    };
+    auto a_frag = [&](int mb) { lds_read_a_frag(base, mb, lane, fah[mb % 2], fal[mb % 2]); };
     if (!p.last) a_frag(0);
 #pragma unroll
     for (int mb = 0; mb < 8; ++mb) {
       if (mb + 1 < 8 && !(p.last && mb + 1 < 4)) a_frag(mb + 1);
-      if (!(p.last && mb < 4)) {                       // wave-uniform
-        const bf16x8 ah = fah[mb % 2], al = fal[mb % 2];
-        acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh2[ks], acc[mb], 0, 0, 0);
-        acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl2[ks], acc[mb], 0, 0, 0);
-        acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh2[ks], acc[mb], 0, 0, 0);
-      }
+      if (!(p.last && mb < 4)) mfma_bf3(acc[mb], fah[mb % 2], fal[mb % 2], bh2[ks], bl2[ks]);   // wave-uniform
       if (more && mb >= 4) {                           // four pieces per wave, behind the skip-row blocks (live on every layer)
         __builtin_amdgcn_sched_barrier(0);
         issue_piece(nxt, mb - 4);
@@ -851,6 +826,29 @@ struct WnBwdParams {
   int B, L, n, last, CH, tiles_per_seq, n_wg;
 };
 
+// One stage of GEMM 3 for one 32-sample column block: the stage's four row blocks of W_rsᵀ (A fragments at base) times the
+// B fragment (bh, bl).  The body of wn_layer_bwd_kernel's stage loop and of both operand sources of wn_stack_bwd_kernel's phase A.
+__device__ __forceinline__ void wn_bwd_multiply(f32x16 (&acc)[4], const char* base, int lane, bf16x8 bh, bf16x8 bl) {
+#pragma unroll
+  for (int mb = 0; mb < 4; ++mb) {
+    bf16x8 ah, al;
+    lds_read_a_frag(base, mb, lane, ah, al);
+    mfma_bf3(acc[mb], ah, al, bh, bl);
+  }
+}
+
+// [8 waves][R] per-wave row sums in LDS -> out[R][stride] at column col, the waves added in a fixed order (after a workgroup
+// barrier: every wave has added its last tile).  512 threads.
+__device__ __forceinline__ void wn_reduce_row_sums(const float* rsum, int R, float* out, int stride, int col, int tid) {
+  __syncthreads();
+  if (tid < R) {
+    float s8 = 0.f;
+#pragma unroll
+    for (int w = 0; w < 8; ++w) s8 += rsum[w * R + tid];
+    out[(long long)tid * stride + col] = s8;
+  }
+}
+
 __global__ __launch_bounds__(256, WN_BWD_OCC) void wn_layer_bwd_kernel(WnBwdParams p) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   char* const ldsb = reinterpret_cast<char*>(lds);
@@ -919,22 +917,9 @@ __global__ __launch_bounds__(256, WN_BWD_OCC) void wn_layer_bwd_kernel(WnBwdPara
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = *reinterpret_cast<const float*>(bp + j * 128);
-    u32x4 bh4, bl4;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      unsigned hh, ll;
-      split_bf16_pair(v[2 * j], v[2 * j + 1], hh, ll);
-      bh4[j] = hh; bl4[j] = ll;
-    }
-    const bf16x8 bh = __builtin_bit_cast(bf16x8, bh4), bl = __builtin_bit_cast(bf16x8, bl4);
-#pragma unroll
-    for (int mb = 0; mb < 4; ++mb) {
-      const bf16x8 ah = *reinterpret_cast<const bf16x8*>(base + mb * 2048 + lane * 16);
-      const bf16x8 al = *reinterpret_cast<const bf16x8*>(base + mb * 2048 + 1024 + lane * 16);
-      acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[mb], 0, 0, 0);
-      acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[mb], 0, 0, 0);
-      acc[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[mb], 0, 0, 0);
-    }
+    bf16x8 bh, bl;
+    split_bf16x8(v, bh, bl);
+    wn_bwd_multiply(acc, base, lane, bh, bl);
     slot = slot == 2 ? 0 : slot + 1;
   }
   __syncthreads();                                     // every wave is past its last fragment read: the ring becomes tiles
@@ -1076,6 +1061,63 @@ extern "C" int fst_wn_pack_dgrad(const float* in_w, const float* cond_w, int n, 
   return 0;
 }
 
+// One data-gradient stage into the ring slot at sl, as 1-KiB LDS-DMA pieces dealt round the eight waves: the 13 weight blocks of
+// chunk c of the image, then the two 8-channel row groups of the dg window [16 channels of chunk c][nblkw blocks from column
+// (t0 - dil) & ~3] of one batch element (dg_b: its [2n][L] matrix); rows past 2n and columns outside [0, L) read the image's zeros.
+__device__ __forceinline__ void wn_dgrad_issue(char* sl, const char* img, const float* dg_b, int c, int t0, int n, int L, int dil,
+                                               int nblkw, int gsw, int wave_s, int lane) {
+  const char* asrc = img + (long long)c * DG_A_BYTES;
+  // 16 bytes of zeros behind the last chunk: (2n + 15) / 16 is the CHK of both launchers and of wn_pack_dgrad_kernel's grid
+  const char* const zero16 = img + (long long)((2 * n + 15) / 16) * DG_A_BYTES;
+  const float* xb = dg_b + (long long)(16 * c) * L;
+  const int c_count = min(16, 2 * n - 16 * c);
+  const int w4 = (t0 - dil) & ~3;                        // 16-byte aligned start of the window (first column any tap needs)
+  const int NI = DG_A_BLOCKS * 2 + 2 * nblkw;            // 1-KiB pieces per stage
+  for (int idx = wave_s; idx < NI; idx += 8) {           // wave-uniform trip count
+    if (idx < 2 * DG_A_BLOCKS) {
+      lds_dma16(asrc + idx * 1024 + lane * 16, sl + idx * 1024);
+    } else {
+      const int bi = idx - 2 * DG_A_BLOCKS;
+      const int gq = bi >= nblkw ? 1 : 0, m = bi - gq * nblkw;
+      const int row = 8 * gq + (lane >> 3);
+      const int t = w4 + 32 * m + 4 * (lane & 7);
+      const bool ok = row < c_count && t >= 0 && t < L;
+      const char* src = ok ? reinterpret_cast<const char*>(xb + ((long long)row * L + t)) : zero16;
+      lds_dma16(src, sl + DG_A_BYTES + gq * gsw + m * 1024);
+    }
+  }
+}
+
+// The three taps of one landed stage (ring slot at base) into a wave's accumulators: per tap this wave's DG_NCB column blocks of
+// the tap's window — the fragment of a weight block is read from LDS once and multiplied against all of them (LDS reads,
+// 128 B/clk/CU, bound the one-column-block form of this loop).  sub = (t0 - dil) & 3, the window's sub-piece column offset.
+__device__ __forceinline__ void wn_dgrad_stage(f32x16 (&acc)[5][DG_NCB], const char* base, int gsw, int wave_n0, int dil, int sub,
+                                               int lane) {
+  const int half = lane >> 5, l31 = lane & 31;
+#pragma unroll
+  for (int tap = 0; tap < 3; ++tap) {
+    bf16x8 bh[DG_NCB], bl[DG_NCB];
+#pragma unroll
+    for (int cb = 0; cb < DG_NCB; ++cb) {
+      const int colx = wave_n0 + 32 * cb + l31 + (2 - tap) * dil + sub;
+      const char* bp = base + DG_A_BYTES + half * gsw + (colx >> 5) * 1024 + (colx & 31) * 4;
+      float v8[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v8[j] = *reinterpret_cast<const float*>(bp + j * 128);
+      split_bf16x8(v8, bh[cb], bl[cb]);
+    }
+    const char* ab = base + (tap == 0 ? 0 : (tap == 1 ? 4 : 9)) * 2048;
+#pragma unroll
+    for (int mb = 0; mb < 5; ++mb) {
+      if (mb == 4 && tap != 1) continue;               // the d_u0 block exists on the centre tap only
+      bf16x8 ah, al;
+      lds_read_a_frag(ab, mb, lane, ah, al);
+#pragma unroll
+      for (int cb = 0; cb < DG_NCB; ++cb) mfma_bf3(acc[mb][cb], ah, al, bh[cb], bl[cb]);
+    }
+  }
+}
+
 struct WnDgradParams {
   const float* dg;      // [B][2n][L]
   const char* img;
@@ -1106,7 +1148,6 @@ __global__ __launch_bounds__(512, 2) void wn_layer_dgrad_kernel(WnDgradParams p)
   const int wave_s = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wave_n0 = wave_s * (32 * DG_NCB);
   const int L = p.L, n = p.n, CHK = p.CHK, dil = p.dil;
-  const char* const zero16 = p.img + (long long)CHK * DG_A_BYTES;
   const int NI = DG_A_BLOCKS * 2 + 2 * p.nblkw;        // 1-KiB pieces per stage
   const int my_pieces = (NI - wave_s + 7) >> 3;        // pieces idx = wave + 8 i < NI
   const int depth = p.ns - 1;                          // stages in flight
@@ -1122,24 +1163,7 @@ __global__ __launch_bounds__(512, 2) void wn_layer_dgrad_kernel(WnDgradParams p)
     return wg;
   };
   auto issue = [&](int b, int t0, int c, int slot) {
-    char* const sl = ldsb + slot * p.slot;
-    const char* asrc = p.img + (long long)c * DG_A_BYTES;
-    const float* xb = p.dg + ((long long)b * (2 * n) + 16 * c) * L;
-    const int c_count = min(16, 2 * n - 16 * c);
-    const int w4 = (t0 - dil) & ~3;                      // 16-byte aligned start of the window (first column any tap needs)
-    for (int idx = wave_s; idx < NI; idx += 8) {         // wave-uniform trip count
-      if (idx < 2 * DG_A_BLOCKS) {
-        lds_dma16(asrc + idx * 1024 + lane * 16, sl + idx * 1024);
-      } else {
-        const int bi = idx - 2 * DG_A_BLOCKS;
-        const int gq = bi >= p.nblkw ? 1 : 0, m = bi - gq * p.nblkw;
-        const int row = 8 * gq + (lane >> 3);
-        const int t = w4 + 32 * m + 4 * (lane & 7);
-        const bool ok = row < c_count && t >= 0 && t < L;
-        const char* src = ok ? reinterpret_cast<const char*>(xb + ((long long)row * L + t)) : zero16;
-        lds_dma16(src, sl + DG_A_BYTES + gq * p.gsw + m * 1024);
-      }
-    }
+    wn_dgrad_issue(ldsb + slot * p.slot, p.img, p.dg + (long long)b * (2 * n) * L, c, t0, n, L, dil, p.nblkw, p.gsw, wave_s, lane);
   };
 
   // The epilogue's transpose tiles and row-sum array live in ring slot 0; a tile whose predecessor's epilogue is still
@@ -1175,42 +1199,7 @@ __global__ __launch_bounds__(512, 2) void wn_layer_dgrad_kernel(WnDgradParams p)
       wn_wait_sw<16>(newer * my_pieces);
       __builtin_amdgcn_s_barrier();
       if (c + depth < CHK) issue(b, t0, c + depth, (slot + depth) % p.ns);
-      const char* base = ldsb + slot * p.slot;
-#pragma unroll
-      for (int tap = 0; tap < 3; ++tap) {
-        // this wave's DG_NCB column blocks of the tap's window: the fragment of a weight block is read from LDS once and
-        // multiplied against all of them (LDS reads, 128 B/clk/CU, bound the one-column-block form of this loop)
-        bf16x8 bh[DG_NCB], bl[DG_NCB];
-#pragma unroll
-        for (int cb = 0; cb < DG_NCB; ++cb) {
-          const int colx = wave_n0 + 32 * cb + l31 + (2 - tap) * dil + sub;
-          const char* bp = base + DG_A_BYTES + half * p.gsw + (colx >> 5) * 1024 + (colx & 31) * 4;
-          float v8[8];
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v8[j] = *reinterpret_cast<const float*>(bp + j * 128);
-          u32x4 bh4, bl4;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            unsigned hh, ll;
-            split_bf16_pair(v8[2 * j], v8[2 * j + 1], hh, ll);
-            bh4[j] = hh; bl4[j] = ll;
-          }
-          bh[cb] = __builtin_bit_cast(bf16x8, bh4); bl[cb] = __builtin_bit_cast(bf16x8, bl4);
-        }
-        const char* ab = base + (tap == 0 ? 0 : (tap == 1 ? 4 : 9)) * 2048;
-#pragma unroll
-        for (int mb = 0; mb < 5; ++mb) {
-          if (mb == 4 && tap != 1) continue;               // the d_u0 block exists on the centre tap only
-          const bf16x8 ah = *reinterpret_cast<const bf16x8*>(ab + mb * 2048 + lane * 16);
-          const bf16x8 al = *reinterpret_cast<const bf16x8*>(ab + mb * 2048 + 1024 + lane * 16);
-#pragma unroll
-          for (int cb = 0; cb < DG_NCB; ++cb) {
-            acc[mb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[cb], acc[mb][cb], 0, 0, 0);
-            acc[mb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[cb], acc[mb][cb], 0, 0, 0);
-            acc[mb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[cb], acc[mb][cb], 0, 0, 0);
-          }
-        }
-      }
+      wn_dgrad_stage(acc, ldsb + slot * p.slot, p.gsw, wave_n0, dil, sub, lane);
       slot = slot + 1 == p.ns ? 0 : slot + 1;
     }
     __syncthreads();                                     // every wave is past its last fragment read: the ring is free
@@ -1242,15 +1231,7 @@ __global__ __launch_bounds__(512, 2) void wn_layer_dgrad_kernel(WnDgradParams p)
         wn_tile_row_sums(tile, rsum_w, i * 32, rows, L, tcol, lane);
       }
     }
-    if (p.row_sums) {
-      __syncthreads();
-      if (tid < 128) {                                                        // [128][n_wg]; waves added in a fixed order
-        float s8 = 0.f;
-#pragma unroll
-        for (int w = 0; w < 8; ++w) s8 += rsum[w * 128 + tid];
-        p.row_sums[(long long)tid * p.n_wg + wg] = s8;
-      }
-    }
+    if (p.row_sums) wn_reduce_row_sums(rsum, 128, p.row_sums, p.n_wg, wg, tid);       // [128][n_wg]
   }
 }
 
@@ -1456,16 +1437,6 @@ __global__ __launch_bounds__(512, 2) void wn_stack_bwd_kernel(WnStackParams p_by
           for (int mb = 0; mb < 4; ++mb)
 #pragma unroll
             for (int r = 0; r < 16; ++r) da[mb][r] = 0.f;
-          auto multiply = [&](const char* base, const bf16x8 bh, const bf16x8 bl) {
-#pragma unroll
-            for (int mb = 0; mb < 4; ++mb) {
-              const bf16x8 ah = *reinterpret_cast<const bf16x8*>(base + mb * 2048 + lane * 16);
-              const bf16x8 al = *reinterpret_cast<const bf16x8*>(base + mb * 2048 + 1024 + lane * 16);
-              da[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, da[mb], 0, 0, 0);
-              da[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, da[mb], 0, 0, 0);
-              da[mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, da[mb], 0, 0, 0);
-            }
-          };
           FST_T(tp0);
           // ---- the d_out stages: the operand comes straight from memory in fragment layout (eight dword loads per stage: lane
           // half hh reads channels 8hh + j at its column), the next stage's in flight while one is multiplied — no ring, no barrier
@@ -1488,28 +1459,21 @@ __global__ __launch_bounds__(512, 2) void wn_stack_bwd_kernel(WnStackParams p_by
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = vn[j];
             if (k + 1 < CH) load_dout(vn, k + 1);
-            u32x4 bh4, bl4;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              unsigned hh, ll;
-              split_bf16_pair(v[2 * j], v[2 * j + 1], hh, ll);
-              bh4[j] = hh; bl4[j] = ll;
-            }
-            multiply(w_dout + k * WN_BW_A, __builtin_bit_cast(bf16x8, bh4), __builtin_bit_cast(bf16x8, bl4));
+            bf16x8 bh, bl;
+            split_bf16x8(v, bh, bl);
+            wn_bwd_multiply(da, w_dout + k * WN_BW_A, lane, bh, bl);
           }
           // ---- the d_a stages: the operand IS the accumulator tile (registers 8s..8s+7 of row block c>>1 are k-step c&1)
           if (!last) {
             auto da_stage = [&](auto cc) {
               constexpr int c = decltype(cc)::value;
               if (c < CH) {                                // wave-uniform
-                u32x4 bh4, bl4;
+                float v[8];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                  unsigned hh, ll;
-                  split_bf16_pair(acc[c >> 1][cb][8 * (c & 1) + 2 * j], acc[c >> 1][cb][8 * (c & 1) + 2 * j + 1], hh, ll);
-                  bh4[j] = hh; bl4[j] = ll;
-                }
-                multiply(ldsb + c * WN_BW_A, __builtin_bit_cast(bf16x8, bh4), __builtin_bit_cast(bf16x8, bl4));
+                for (int j = 0; j < 8; ++j) v[j] = acc[c >> 1][cb][8 * (c & 1) + j];
+                bf16x8 bh, bl;
+                split_bf16x8(v, bh, bl);
+                wn_bwd_multiply(da, ldsb + c * WN_BW_A, lane, bh, bl);
                 __builtin_amdgcn_sched_barrier(0);        // stage by stage: hoisted fragment reads of later stages cost registers
               }
             };
@@ -1547,15 +1511,7 @@ __global__ __launch_bounds__(512, 2) void wn_stack_bwd_kernel(WnStackParams p_by
         };
         run_pass(std::integral_constant<int, 0>{});
         run_pass(std::integral_constant<int, 1>{});
-        if (rs_out) {
-          __syncthreads();
-          if (tid < 256) {
-            float s8 = 0.f;
-#pragma unroll
-            for (int w = 0; w < 8; ++w) s8 += rsum[w * 256 + tid];
-            rs_out[(long long)tid * p.B + b] = s8;            // [256][B]
-          }
-        }
+        if (rs_out) wn_reduce_row_sums(rsum, 256, rs_out, p.B, b, tid);       // [256][B]
         FST_T(ta3);
         wait_vmcnt<0>();                                     // this wave's dg stores have reached L2 ...
         __syncthreads();                                     // ... and so have everyone's: phase B may fetch them; the ring is free
@@ -1566,34 +1522,13 @@ __global__ __launch_bounds__(512, 2) void wn_stack_bwd_kernel(WnStackParams p_by
       {
         const int dil = p.dil[i], nblkw = p.nblkw[i], gsw = p.gsw[i], slotb = p.slot_d[i];
         const char* const img = p.img_d[i];
-        const char* const zero16 = img + (long long)CHK * DG_A_BYTES;
         const float* const dgr = p.dg[i] + (long long)b * (2 * n) * L;
         float* const da_store = p.da_out[i];
         const __amdgpu_buffer_rsrc_t dan_r = ws_rsrc(da_store ? da_store + (long long)b * n * L : nullptr);
         const __amdgpu_buffer_rsrc_t du_r = ws_rsrc(p.d_u0 + (long long)b * p.d_u0_bs);
         float* const rs_out = p.rs_d[i];
-        const int NI = DG_A_BLOCKS * 2 + 2 * nblkw;
-        const int sub = (0 - dil) & 3;
-        const int w4 = (0 - dil) & ~3;
-        auto issue = [&](int c, int slot) {
-          char* const sl = ldsb + slot * slotb;
-          const char* asrc = img + (long long)c * DG_A_BYTES;
-          const float* xb = dgr + (long long)(16 * c) * L;
-          const int c_count = min(16, 2 * n - 16 * c);
-          for (int idx = wave_s; idx < NI; idx += 8) {
-            if (idx < 2 * DG_A_BLOCKS) {
-              lds_dma16(asrc + idx * 1024 + lane * 16, sl + idx * 1024);
-            } else {
-              const int bi = idx - 2 * DG_A_BLOCKS;
-              const int gq = bi >= nblkw ? 1 : 0, m = bi - gq * nblkw;
-              const int row = 8 * gq + (lane >> 3);
-              const int t = w4 + 32 * m + 4 * (lane & 7);
-              const bool ok = row < c_count && t >= 0 && t < L;
-              const char* src = ok ? reinterpret_cast<const char*>(xb + ((long long)row * L + t)) : zero16;
-              lds_dma16(src, sl + DG_A_BYTES + gq * gsw + m * 1024);
-            }
-          }
-        };
+        const int sub = (0 - dil) & 3;                       // a 512-sample tile is the whole sequence: t0 = 0
+        auto issue = [&](int c, int slot) { wn_dgrad_issue(ldsb + slot * slotb, img, dgr, c, 0, n, L, dil, nblkw, gsw, wave_s, lane); };
         FST_T(tb0);
         // the d_a tiles are where the previous layer left them; the conditioning rows come from memory
         ws_acc_load(acc[4][0], du_r, wl0, 0, wave_n0, p.h, L);
@@ -1607,40 +1542,7 @@ __global__ __launch_bounds__(512, 2) void wn_stack_bwd_kernel(WnStackParams p_by
           wait_vmcnt<0>();
           __builtin_amdgcn_s_barrier();
           if (c + 1 < CHK) issue(c + 1, slot ^ 1);
-          const char* base = ldsb + slot * slotb;
-#pragma unroll
-          for (int tap = 0; tap < 3; ++tap) {
-            bf16x8 bh[DG_NCB], bl[DG_NCB];
-#pragma unroll
-            for (int cb = 0; cb < DG_NCB; ++cb) {
-              const int colx = wave_n0 + 32 * cb + l31 + (2 - tap) * dil + sub;
-              const char* bp = base + DG_A_BYTES + half * gsw + (colx >> 5) * 1024 + (colx & 31) * 4;
-              float v8[8];
-#pragma unroll
-              for (int j = 0; j < 8; ++j) v8[j] = *reinterpret_cast<const float*>(bp + j * 128);
-              u32x4 bh4, bl4;
-#pragma unroll
-              for (int j = 0; j < 4; ++j) {
-                unsigned hh, ll;
-                split_bf16_pair(v8[2 * j], v8[2 * j + 1], hh, ll);
-                bh4[j] = hh; bl4[j] = ll;
-              }
-              bh[cb] = __builtin_bit_cast(bf16x8, bh4); bl[cb] = __builtin_bit_cast(bf16x8, bl4);
-            }
-            const char* ab = base + (tap == 0 ? 0 : (tap == 1 ? 4 : 9)) * 2048;
-#pragma unroll
-            for (int mb = 0; mb < 5; ++mb) {
-              if (mb == 4 && tap != 1) continue;
-              const bf16x8 ah = *reinterpret_cast<const bf16x8*>(ab + mb * 2048 + lane * 16);
-              const bf16x8 al = *reinterpret_cast<const bf16x8*>(ab + mb * 2048 + 1024 + lane * 16);
-#pragma unroll
-              for (int cb = 0; cb < DG_NCB; ++cb) {
-                acc[mb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[cb], acc[mb][cb], 0, 0, 0);
-                acc[mb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[cb], acc[mb][cb], 0, 0, 0);
-                acc[mb][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[cb], acc[mb][cb], 0, 0, 0);
-              }
-            }
-          }
+          wn_dgrad_stage(acc, ldsb + slot * slotb, gsw, wave_n0, dil, sub, lane);
           slot ^= 1;
         }
         FST_T(tb2);
@@ -1675,15 +1577,7 @@ __global__ __launch_bounds__(512, 2) void wn_stack_bwd_kernel(WnStackParams p_by
             ws_row_sums(av, rsum + wave_s * 128, ib * 32, rows, tcol + l31 < L, lane);
           }
         }
-        if (rs_out) {
-          __syncthreads();
-          if (tid < 128) {
-            float s8 = 0.f;
-#pragma unroll
-            for (int w = 0; w < 8; ++w) s8 += rsum[w * 128 + tid];
-            rs_out[(long long)tid * p.B + b] = s8;            // [128][B]
-          }
-        }
+        if (rs_out) wn_reduce_row_sums(rsum, 128, rs_out, p.B, b, tid);       // [128][B]
         FST_T(tb3);
         FST_ACC(6, tb2, tb3);                            // phase B: epilogue stores (issue)
         // d_u0 of this layer must be in L2 before the next layer's phase B reads it back (the wait also retires the primed stages)

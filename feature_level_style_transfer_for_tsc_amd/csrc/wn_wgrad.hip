@@ -5,7 +5,7 @@
 //   res_skip                dW_rs[m][c]    = Σ_{b,t} [d_a ; d_out][b,m,t]·(t·s)[b,c,t]          (acts = t·s re-formed from the saved halves)
 //
 // A GEMM whose reduction index is TIME: D[m][k] = Σ_t dy[m][t]·x[k][t] with M = 2n output rows, K = 3n + h (or n) "k-rows"
-// and B·L = 131 072 reduction steps.  On v_mfma_f32_32x32x16_bf16 both operands are "row, 8 consecutive time samples" fragments,
+// and B·L = 131 072 reduction steps.  On the 32x32x16 bf16 MFMA both operands are "row, 8 consecutive time samples" fragments,
 // i.e. 32 contiguous bytes of an fp32 activation row — no transposition anywhere.  Design, against the generic
 // conv_wgrad_kernel it replaces for these shapes (99 µs, MFMA-busy 0.24, 706 MB through L2 → LDS for 202 MB of operands):
 //   * one 8-wave workgroup per CU owns ALL 2n output rows × 192 k-rows (6 blocks; in_layer: two such groups, so dy passes the
@@ -70,18 +70,6 @@ struct WwParams {
   float* w[2];          // reduce outputs
 };
 
-template <class V4>
-__device__ __forceinline__ void ww_split8(const V4& v0, const V4& v1, bf16x8& hi, bf16x8& lo) {
-  u32x4 h, l;
-  unsigned hh, ll;
-  split_bf16_pair(v0.x, v0.y, hh, ll); h[0] = hh; l[0] = ll;
-  split_bf16_pair(v0.z, v0.w, hh, ll); h[1] = hh; l[1] = ll;
-  split_bf16_pair(v1.x, v1.y, hh, ll); h[2] = hh; l[2] = ll;
-  split_bf16_pair(v1.z, v1.w, hh, ll); h[3] = hh; l[3] = ll;
-  hi = __builtin_bit_cast(bf16x8, h);
-  lo = __builtin_bit_cast(bf16x8, l);
-}
-
 // LDS accesses as inline asm, by byte address (ww_lds_addr) with the constant part of the address as the instruction's immediate
 // offset (0 where there is none): tz_wgrad_kernel's fragment and split-pass reads of a stage then share a handful of per-lane
 // address registers (see its instruction budget).  Why asm: hipcc's wait-count pass cannot tell ring slots apart: in front of the
@@ -130,11 +118,11 @@ __device__ __forceinline__ void ww_lds_wait() {
 // 8 consecutive samples (two raw 16-byte pieces) → their bf16 hi parts and lo parts, 16 bytes each
 template <class V4>
 __device__ __forceinline__ void ww_split8u(const V4& v0, const V4& v1, u32x4& h, u32x4& l) {
-  unsigned hh, ll;
-  split_bf16_pair(v0.x, v0.y, hh, ll); h[0] = hh; l[0] = ll;
-  split_bf16_pair(v0.z, v0.w, hh, ll); h[1] = hh; l[1] = ll;
-  split_bf16_pair(v1.x, v1.y, hh, ll); h[2] = hh; l[2] = ll;
-  split_bf16_pair(v1.z, v1.w, hh, ll); h[3] = hh; l[3] = ll;
+  const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+  bf16x8 hi, lo;
+  split_bf16x8(v, hi, lo);
+  h = __builtin_bit_cast(u32x4, hi);
+  l = __builtin_bit_cast(u32x4, lo);
 }
 
 // A staged row is 32 samples = eight 16-byte pieces (128 B, one cache line of the tensor row).  Logical row r of a region sits at
@@ -417,9 +405,7 @@ __global__ __launch_bounds__(512, 2) void wn_wgrad_kernel(WwParams p) {
           for (int i = 0; i < MT; ++i) {
             if (!FULL && wm * MT + i >= m_blocks) break;   // wave-uniform
             const bf16x8 ah = __builtin_bit_cast(bf16x8, araw[i][0]), al = __builtin_bit_cast(bf16x8, araw[i][1]);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[i][j], 0, 0, 0);
+            mfma_bf3(acc[i][j], ah, al, bh, bl);
           }
         }
         issue_pos(5 * ks + 1 + j);
@@ -964,12 +950,10 @@ __global__ __launch_bounds__(512, 2) void tz_wgrad_kernel(TzParams p) {
   auto split_x_store = [&](unsigned cbuf) {
 #pragma unroll
     for (int j = 0; j < XU; ++j) {
-      u32x4 h4, l4;
-      unsigned hh, ll;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) { split_bf16_pair(sxv[j][2 * e], sxv[j][2 * e + 1], hh, ll); h4[e] = hh; l4[e] = ll; }
-      ww_lds_write16<0>(cbuf + sx_dst[j], h4);
-      ww_lds_write16<LO>(cbuf + sx_dst[j], l4);
+      bf16x8 hi, lo;
+      split_bf16x8(sxv[j], hi, lo);
+      ww_lds_write16<0>(cbuf + sx_dst[j], __builtin_bit_cast(u32x4, hi));
+      ww_lds_write16<LO>(cbuf + sx_dst[j], __builtin_bit_cast(u32x4, lo));
     }
   };
 
@@ -1007,9 +991,7 @@ __global__ __launch_bounds__(512, 2) void tz_wgrad_kernel(TzParams p) {
       for (int i = 0; i < 2; ++i) {
         if (!FULL && wm * 2 + i >= m_blocks) break;        // wave-uniform
         const bf16x8 ah = __builtin_bit_cast(bf16x8, araw[ks][i][0]), al = __builtin_bit_cast(bf16x8, araw[ks][i][1]);
-        acc[i][sb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[i][sb], 0, 0, 0);
-        acc[i][sb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[i][sb], 0, 0, 0);
-        acc[i][sb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[i][sb], 0, 0, 0);
+        mfma_bf3(acc[i][sb], ah, al, bh, bl);
       }
     }
     __builtin_amdgcn_sched_barrier(0);

@@ -101,7 +101,8 @@ def test_dense_products_refuse_what_the_kernel_does_not_serve():
 
 def test_split_and_staging_primitives_are_defined_once():
     """The split-bf16 product every parity tolerance assumes, and the staging pieces around it, live in csrc/fst_device.h
-    alone: a kernel file that converts to bf16 itself or redefines one of them could drift from the others unnoticed."""
+    alone: a kernel file that converts to bf16 itself, issues the bf16 MFMA itself (the three-term product and its order are
+    mfma_bf3's) or redefines one of them could drift from the others unnoticed."""
     import glob
     csrc = os.path.join(ROOT, "feature_level_style_transfer_for_tsc_amd", "csrc")
     paths = sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")))
@@ -112,8 +113,9 @@ def test_split_and_staging_primitives_are_defined_once():
     for path in paths:
         name = os.path.basename(path)
         text = open(path).read()
-        if name != "fst_device.h" and "__builtin_convertvector" in text:
-            stray.append(f"{name}: __builtin_convertvector")
+        for word in ("__builtin_convertvector", "mfma_f32_32x32x16_bf16"):
+            if name != "fst_device.h" and word in text:
+                stray.append(f"{name}: {word}")
         if name.endswith(".hip"):
             stray += [f"{name}: {a or b}" for a, b in defined.findall(text)]
     assert not stray, stray
