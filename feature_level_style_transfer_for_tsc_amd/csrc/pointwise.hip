@@ -257,6 +257,19 @@ extern "C" int fst_bn_finalize(const float* part, int n_slots, const float* gamm
   return 0;
 }
 
+// The BatchNorm's value of an element in front of the ReLU.  bn_apply* store max(·, 0) of it as the forward output and the
+// backward kernels take the ReLU mask from its sign when the caller kept no `out`, so it is written ONCE, as the explicit
+// fused multiply-add the forward has always been compiled to: forward and mask are the same instruction on the same operands,
+// whatever the compiler's contraction heuristics make of the code around them.
+__device__ __forceinline__ float bn_pre(float y, float sc, float sh) { return __builtin_fmaf(y, sc, sh); }
+// the residual join: branch a's value, then branch b's added to it (res_stats absent: the plain residual, scale 1, shift 0)
+__device__ __forceinline__ float bn_pre_join(float ya, float sca, float sha, float yb, float scb, float shb) {
+#pragma clang fp contract(off)
+  float v = bn_pre(ya, sca, sha);
+  v += bn_pre(yb, scb, shb);
+  return v;
+}
+
 __global__ __launch_bounds__(256) void bn_apply_kernel(const float* y, const float* stats, const float* res,
                                                        const float* res_stats, float* out, int C, int L, int relu) {
   const int bc = blockIdx.x;           // b*C + c
@@ -266,8 +279,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* y, const flo
   if (res && res_stats) { rsc = res_stats[2 * C + c]; rsh = res_stats[3 * C + c]; }
   const long long base = (long long)bc * L;
   for (int t = threadIdx.x; t < L; t += 256) {
-    float v = y[base + t] * sc + sh;
-    if (res) v += res[base + t] * rsc + rsh;
+    float v = res ? bn_pre_join(y[base + t], sc, sh, res[base + t], rsc, rsh) : bn_pre(y[base + t], sc, sh);
     if (relu) v = fmaxf(v, 0.f);
     out[base + t] = v;
   }
@@ -289,10 +301,12 @@ __global__ __launch_bounds__(256) void bn_apply_vec_kernel(const float* y, const
   float4* o4 = reinterpret_cast<float4*>(out) + base;
   for (int t = t0; t < rv.L4; t += 1 << rv.shift) {
     float4 v = y4[t];
-    v.x = v.x * sc + sh; v.y = v.y * sc + sh; v.z = v.z * sc + sh; v.w = v.w * sc + sh;
     if (r4) {
       const float4 q = r4[t];
-      v.x += q.x * rsc + rsh; v.y += q.y * rsc + rsh; v.z += q.z * rsc + rsh; v.w += q.w * rsc + rsh;
+      v.x = bn_pre_join(v.x, sc, sh, q.x, rsc, rsh); v.y = bn_pre_join(v.y, sc, sh, q.y, rsc, rsh);
+      v.z = bn_pre_join(v.z, sc, sh, q.z, rsc, rsh); v.w = bn_pre_join(v.w, sc, sh, q.w, rsc, rsh);
+    } else {
+      v.x = bn_pre(v.x, sc, sh); v.y = bn_pre(v.y, sc, sh); v.z = bn_pre(v.z, sc, sh); v.w = bn_pre(v.w, sc, sh);
     }
     if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
     o4[t] = v;
@@ -315,18 +329,65 @@ extern "C" int fst_bn_apply(const float* y, const float* stats, const float* res
   return 0;
 }
 
+// ---------------------------------------------------------------- BatchNorm backward
+// The element arithmetic of the backward kernels, written once and shared by the single-branch and the join kernels.  The
+// join must leave the very bits two single-branch launches leave (dγ, dβ, dx, row sums), so nothing here is left to the
+// compiler's choice of what to contract: contraction is off, and where the single-branch kernels have always used a fused
+// multiply-add it is spelled out.
+//
+// dy under the ReLU mask: `o` is the forward output, or the pre-activation it was the max(·, 0) of — same sign test
+__device__ __forceinline__ float bn_masked(float g, float o) { return o > 0.f ? g : 0.f; }
+__device__ __forceinline__ float4 bn_masked4(float4 g, float4 o) {
+  g.x = bn_masked(g.x, o.x); g.y = bn_masked(g.y, o.y); g.z = bn_masked(g.z, o.z); g.w = bn_masked(g.w, o.w);
+  return g;
+}
+__device__ __forceinline__ float4 bn_pre4(float4 y, float sc, float sh) {
+  return make_float4(bn_pre(y.x, sc, sh), bn_pre(y.y, sc, sh), bn_pre(y.z, sc, sh), bn_pre(y.w, sc, sh));
+}
+__device__ __forceinline__ float4 bn_pre_join4(float4 ya, float sca, float sha, float4 yb, float scb, float shb) {
+  return make_float4(bn_pre_join(ya.x, sca, sha, yb.x, scb, shb), bn_pre_join(ya.y, sca, sha, yb.y, scb, shb),
+                     bn_pre_join(ya.z, sca, sha, yb.z, scb, shb), bn_pre_join(ya.w, sca, sha, yb.w, scb, shb));
+}
+// terms of Σ dyʹ and Σ dyʹ·x̂
+__device__ __forceinline__ float bn_gx(float g, float y, float mean, float invstd) {
+#pragma clang fp contract(off)
+  return g * (y - mean) * invstd;
+}
+__device__ __forceinline__ float bn_g4(float4 g) {
+#pragma clang fp contract(off)
+  return (g.x + g.y) + (g.z + g.w);
+}
+__device__ __forceinline__ float bn_gx4(float4 g, float4 v, float mean, float invstd) {
+#pragma clang fp contract(off)
+  return (g.x * (v.x - mean) + g.y * (v.y - mean) + g.z * (v.z - mean) + g.w * (v.w - mean)) * invstd;
+}
+// dx / scale = dyʹ − m1 − x̂·m2
+__device__ __forceinline__ float bn_dx_unscaled(float g, float y, float mean, float invstd, float m1, float m2) {
+#pragma clang fp contract(off)
+  const float xh = (y - mean) * invstd;
+  return __builtin_fmaf(-xh, m2, g - m1);
+}
+__device__ __forceinline__ float4 bn_dx4(float4 g, float4 v, float mean, float invstd, float scale, float m1, float m2) {
+#pragma clang fp contract(off)
+  return make_float4(scale * bn_dx_unscaled(g.x, v.x, mean, invstd, m1, m2), scale * bn_dx_unscaled(g.y, v.y, mean, invstd, m1, m2),
+                     scale * bn_dx_unscaled(g.z, v.z, mean, invstd, m1, m2), scale * bn_dx_unscaled(g.w, v.w, mean, invstd, m1, m2));
+}
+
+// relu with out == nullptr: the mask is the sign of bn_pre(y), the value the forward took max(·, 0) of — `out` is not read.
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* dy, const float* y, const float* out,
                                                             const float* stats, int B, int C, int L, int relu, float* red) {
+#pragma clang fp contract(off)
   const int c = blockIdx.x;
-  const float mean = stats[c], invstd = stats[C + c];
+  const float mean = stats[c], invstd = stats[C + c], sc = stats[2 * C + c], sh = stats[3 * C + c];
   float s1 = 0.f, s2 = 0.f;
   for (int b = blockIdx.y; b < B; b += gridDim.y) {
     const long long base = ((long long)b * C + c) * L;
     for (int t = threadIdx.x; t < L; t += 256) {
       float g = dy[base + t];
-      if (relu && !(out[base + t] > 0.f)) g = 0.f;
+      const float v = y[base + t];
+      if (relu) g = bn_masked(g, out ? out[base + t] : bn_pre(v, sc, sh));
       s1 += g;
-      s2 += g * (y[base + t] - mean) * invstd;
+      s2 += bn_gx(g, v, mean, invstd);
     }
   }
   block_sum2(s1, s2);
@@ -339,26 +400,21 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* dy, con
 __global__ __launch_bounds__(256) void bn_bwd_reduce_vec_kernel(const float* dy, const float* y, const float* out,
                                                                 const float* stats, int B, int C, int L, int relu,
                                                                 float* red, RowVec rv) {
+#pragma clang fp contract(off)
   const int c = blockIdx.x, r = threadIdx.x >> rv.shift, t0 = threadIdx.x & ((1 << rv.shift) - 1), rpp = 256 >> rv.shift;
-  const float mean = stats[c], invstd = stats[C + c];
+  const float mean = stats[c], invstd = stats[C + c], sc = stats[2 * C + c], sh = stats[3 * C + c];
   float s1 = 0.f, s2 = 0.f;
   for (int b = blockIdx.y + r * gridDim.y; b < B; b += rpp * gridDim.y) {
     const long long base = ((long long)b * C + c) * rv.L4;
     const float4* dy4 = reinterpret_cast<const float4*>(dy) + base;
     const float4* y4 = reinterpret_cast<const float4*>(y) + base;
-    const float4* o4 = reinterpret_cast<const float4*>(out) + base;
+    const float4* o4 = reinterpret_cast<const float4*>(out) + base;          // not dereferenced when out is null
     for (int t = t0; t < rv.L4; t += 1 << rv.shift) {
       float4 g = dy4[t];
       const float4 v = y4[t];
-      if (relu) {
-        const float4 o = o4[t];
-        if (!(o.x > 0.f)) g.x = 0.f;
-        if (!(o.y > 0.f)) g.y = 0.f;
-        if (!(o.z > 0.f)) g.z = 0.f;
-        if (!(o.w > 0.f)) g.w = 0.f;
-      }
-      s1 += (g.x + g.y) + (g.z + g.w);
-      s2 += (g.x * (v.x - mean) + g.y * (v.y - mean) + g.z * (v.z - mean) + g.w * (v.w - mean)) * invstd;
+      if (relu) g = bn_masked4(g, out ? o4[t] : bn_pre4(v, sc, sh));
+      s1 += bn_g4(g);
+      s2 += bn_gx4(g, v, mean, invstd);
     }
   }
   block_sum2(s1, s2);
@@ -370,14 +426,93 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_vec_kernel(const float* dy,
 
 extern "C" int fst_bn_bwd_reduce(const float* dy, const float* y, const float* out, const float* stats, int B, int C,
                                  int L, int relu, float* red, int64_t numel, void* stream) {
-  FST_REQUIRE(dy && y && stats && red && (!relu || out) && B > 0 && C > 0 && L > 0, "fst_bn_bwd_reduce: bad arguments");
+  FST_REQUIRE(dy && y && stats && red && B > 0 && C > 0 && L > 0, "fst_bn_bwd_reduce: bad arguments");
   FST_REQUIRE_EXTENT("fst_bn_bwd_reduce", B, C, L, numel);
+  if (!relu) out = nullptr;
   if (vec_ok(L, {dy, y, out}))
     hipLaunchKernelGGL(bn_bwd_reduce_vec_kernel, dim3(C, FST_BN_SLOTS), dim3(256), 0, (hipStream_t)stream, dy,
                        y, out, stats, B, C, L, relu, red, row_vec(L));
   else
     hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(C, FST_BN_SLOTS), dim3(256), 0, (hipStream_t)stream, dy, y,
                        out, stats, B, C, L, relu, red);
+  FST_LAUNCH_CHECK();
+  return 0;
+}
+
+// The join relu(BN_a(ya) + BN_b(yb)): both branches' partials from one walk over dy, ya, yb.  The mask is the sign of
+// bn_pre_join, and Σ dyʹ is the same number for both branches (same dy, same mask, same order), so it is summed once and
+// stored twice.  Each Σ dyʹ·x̂ goes through block_sum2 exactly as in the single-branch kernel.
+__global__ __launch_bounds__(256) void bn_bwd_reduce_join_kernel(const float* dy, const float* ya, const float* yb,
+                                                                 const float* sa, const float* sb, int B, int C, int L,
+                                                                 float* reda, float* redb) {
+#pragma clang fp contract(off)
+  const int c = blockIdx.x;
+  const float meana = sa[c], invstda = sa[C + c], sca = sa[2 * C + c], sha = sa[3 * C + c];
+  const float meanb = sb[c], invstdb = sb[C + c], scb = sb[2 * C + c], shb = sb[3 * C + c];
+  float s1 = 0.f, s2a = 0.f, s2b = 0.f, unused = 0.f;
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    const long long base = ((long long)b * C + c) * L;
+    for (int t = threadIdx.x; t < L; t += 256) {
+      const float va = ya[base + t], vb = yb[base + t];
+      const float g = bn_masked(dy[base + t], bn_pre_join(va, sca, sha, vb, scb, shb));
+      s1 += g;
+      s2a += bn_gx(g, va, meana, invstda);
+      s2b += bn_gx(g, vb, meanb, invstdb);
+    }
+  }
+  block_sum2(s1, s2a);
+  block_sum2(s2b, unused);
+  if (threadIdx.x == 0) {
+    reda[(long long)c * FST_BN_SLOTS + blockIdx.y] = s1;
+    reda[((long long)C + c) * FST_BN_SLOTS + blockIdx.y] = s2a;
+    redb[(long long)c * FST_BN_SLOTS + blockIdx.y] = s1;
+    redb[((long long)C + c) * FST_BN_SLOTS + blockIdx.y] = s2b;
+  }
+}
+
+__global__ __launch_bounds__(256) void bn_bwd_reduce_join_vec_kernel(const float* dy, const float* ya, const float* yb,
+                                                                     const float* sa, const float* sb, int B, int C, int L,
+                                                                     float* reda, float* redb, RowVec rv) {
+#pragma clang fp contract(off)
+  const int c = blockIdx.x, r = threadIdx.x >> rv.shift, t0 = threadIdx.x & ((1 << rv.shift) - 1), rpp = 256 >> rv.shift;
+  const float meana = sa[c], invstda = sa[C + c], sca = sa[2 * C + c], sha = sa[3 * C + c];
+  const float meanb = sb[c], invstdb = sb[C + c], scb = sb[2 * C + c], shb = sb[3 * C + c];
+  float s1 = 0.f, s2a = 0.f, s2b = 0.f, unused = 0.f;
+  for (int b = blockIdx.y + r * gridDim.y; b < B; b += rpp * gridDim.y) {
+    const long long base = ((long long)b * C + c) * rv.L4;
+    const float4* dy4 = reinterpret_cast<const float4*>(dy) + base;
+    const float4* ya4 = reinterpret_cast<const float4*>(ya) + base;
+    const float4* yb4 = reinterpret_cast<const float4*>(yb) + base;
+    for (int t = t0; t < rv.L4; t += 1 << rv.shift) {
+      const float4 va = ya4[t], vb = yb4[t];
+      const float4 g = bn_masked4(dy4[t], bn_pre_join4(va, sca, sha, vb, scb, shb));
+      s1 += bn_g4(g);
+      s2a += bn_gx4(g, va, meana, invstda);
+      s2b += bn_gx4(g, vb, meanb, invstdb);
+    }
+  }
+  block_sum2(s1, s2a);
+  block_sum2(s2b, unused);
+  if (threadIdx.x == 0) {
+    reda[(long long)c * FST_BN_SLOTS + blockIdx.y] = s1;
+    reda[((long long)C + c) * FST_BN_SLOTS + blockIdx.y] = s2a;
+    redb[(long long)c * FST_BN_SLOTS + blockIdx.y] = s1;
+    redb[((long long)C + c) * FST_BN_SLOTS + blockIdx.y] = s2b;
+  }
+}
+
+extern "C" int fst_bn_bwd_reduce_join(const float* dy, const float* ya, const float* yb, const float* stats_a,
+                                      const float* stats_b, int B, int C, int L, float* red_a, float* red_b, int64_t numel,
+                                      void* stream) {
+  FST_REQUIRE(dy && ya && yb && stats_a && stats_b && red_a && red_b && red_a != red_b && B > 0 && C > 0 && L > 0,
+              "fst_bn_bwd_reduce_join: bad arguments");
+  FST_REQUIRE_EXTENT("fst_bn_bwd_reduce_join", B, C, L, numel);
+  if (vec_ok(L, {dy, ya, yb}))
+    hipLaunchKernelGGL(bn_bwd_reduce_join_vec_kernel, dim3(C, FST_BN_SLOTS), dim3(256), 0, (hipStream_t)stream, dy, ya, yb,
+                       stats_a, stats_b, B, C, L, red_a, red_b, row_vec(L));
+  else
+    hipLaunchKernelGGL(bn_bwd_reduce_join_kernel, dim3(C, FST_BN_SLOTS), dim3(256), 0, (hipStream_t)stream, dy, ya, yb,
+                       stats_a, stats_b, B, C, L, red_a, red_b);
   FST_LAUNCH_CHECK();
   return 0;
 }
@@ -393,12 +528,34 @@ __device__ __forceinline__ void bn_red_sums(const float* red, int n_slots, int C
   }
 }
 
+// Σ_t dx of this (sample, channel) row of the 16-byte kernels — the bias gradient of the conv in front of the BatchNorm is Σ_b
+// of these: the conv's backward then needs no pass of its own over dx.  A row's 2^shift threads are consecutive: a xor
+// butterfly inside the wave, then (rows wider than a wave) the waves' totals through LDS (wsum, 4 floats) in wave order.
+// Called by every thread of the block (it holds a barrier when rows are wider than a wave).
+__device__ __forceinline__ void bn_row_sum_store(float rs, float* row_sums, int bc, bool live, int t0, RowVec rv, float* wsum) {
+  const int w = rv.shift < 6 ? rv.shift : 6;
+  for (int o = (1 << w) >> 1; o > 0; o >>= 1) rs += __shfl_xor(rs, o, 64);      // w = 0 (one thread per row): no step
+  if (rv.shift <= 6) {
+    if (live && t0 == 0) row_sums[bc] = rs;
+  } else {
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = rs;
+    __syncthreads();
+    if (live && t0 == 0) {
+      const int w0 = threadIdx.x >> 6, nw = 1 << (rv.shift - 6);
+      float tot = 0.f;
+      for (int i = 0; i < nw; ++i) tot += wsum[w0 + i];
+      row_sums[bc] = tot;
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* dy, const float* y, const float* out,
                                                            const float* stats, const float* red, int n_slots, float* red_out,
                                                            float* dx, float* row_sums, int C, int L, int relu, int train, float invN) {
+#pragma clang fp contract(off)
   const int bc = blockIdx.x;
   const int c = bc % C;
-  const float mean = stats[c], invstd = stats[C + c], scale = stats[2 * C + c];
+  const float mean = stats[c], invstd = stats[C + c], scale = stats[2 * C + c], sh = stats[3 * C + c];
   float r1 = 0.f, r2 = 0.f;
   if (red) bn_red_sums(red, n_slots, C, c, r1, r2);
   if (red_out && bc < C && threadIdx.x == 0) { red_out[c] = r1; red_out[C + c] = r2; }
@@ -407,11 +564,11 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* dy, cons
   float rs = 0.f, dummy = 0.f;
   for (int t = threadIdx.x; t < L; t += 256) {
     float g = dy[base + t];
-    if (relu && !(out[base + t] > 0.f)) g = 0.f;
-    const float xh = (y[base + t] - mean) * invstd;
-    const float d = scale * (g - m1 - xh * m2);
-    dx[base + t] = d;
-    rs += d;
+    const float v = y[base + t];
+    if (relu) g = bn_masked(g, out ? out[base + t] : bn_pre(v, scale, sh));
+    const float u = bn_dx_unscaled(g, v, mean, invstd, m1, m2);
+    dx[base + t] = scale * u;
+    rs = __builtin_fmaf(scale, u, rs);                     // (the fused form this sum has always had in the dword kernel)
   }
   if (row_sums) {                                          // uniform
     block_sum2(rs, dummy);
@@ -423,13 +580,14 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_vec_kernel(const float* dy, 
                                                                const float* stats, const float* red, int n_slots,
                                                                float* red_out, float* dx, float* row_sums, int rows, int C,
                                                                int L, int relu, int train, float invN, RowVec rv) {
+#pragma clang fp contract(off)
   __shared__ float wsum[4];
   const int r = threadIdx.x >> rv.shift, t0 = threadIdx.x & ((1 << rv.shift) - 1), rpp = 256 >> rv.shift;
   const int bc_raw = blockIdx.x * rpp + r;
   const bool live = bc_raw < rows;
   const int bc = live ? bc_raw : rows - 1;                 // (idle row groups of the last block walk the last row and store nothing)
   const int c = bc % C;
-  const float mean = stats[c], invstd = stats[C + c], scale = stats[2 * C + c];
+  const float mean = stats[c], invstd = stats[C + c], scale = stats[2 * C + c], sh = stats[3 * C + c];
   float r1 = 0.f, r2 = 0.f;
   if (red) bn_red_sums(red, n_slots, C, c, r1, r2);
   if (red_out && live && bc < C && t0 == 0) { red_out[c] = r1; red_out[C + c] = r2; }
@@ -437,56 +595,29 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_vec_kernel(const float* dy, 
   const long long base = (long long)bc * rv.L4;
   const float4* dy4 = reinterpret_cast<const float4*>(dy) + base;
   const float4* y4 = reinterpret_cast<const float4*>(y) + base;
-  const float4* o4 = reinterpret_cast<const float4*>(out) + base;
+  const float4* o4 = reinterpret_cast<const float4*>(out) + base;            // not dereferenced when out is null
   float4* dx4 = reinterpret_cast<float4*>(dx) + base;
   float rs = 0.f;
   for (int t = t0; t < rv.L4; t += 1 << rv.shift) {
     float4 g = dy4[t];
     const float4 v = y4[t];
-    if (relu) {
-      const float4 o = o4[t];
-      if (!(o.x > 0.f)) g.x = 0.f;
-      if (!(o.y > 0.f)) g.y = 0.f;
-      if (!(o.z > 0.f)) g.z = 0.f;
-      if (!(o.w > 0.f)) g.w = 0.f;
-    }
-    float4 d;
-    d.x = scale * (g.x - m1 - (v.x - mean) * invstd * m2);
-    d.y = scale * (g.y - m1 - (v.y - mean) * invstd * m2);
-    d.z = scale * (g.z - m1 - (v.z - mean) * invstd * m2);
-    d.w = scale * (g.w - m1 - (v.w - mean) * invstd * m2);
+    if (relu) g = bn_masked4(g, out ? o4[t] : bn_pre4(v, scale, sh));
+    const float4 d = bn_dx4(g, v, mean, invstd, scale, m1, m2);
     if (live) dx4[t] = d;
-    rs += (d.x + d.y) + (d.z + d.w);
+    rs += bn_g4(d);
   }
-  // Σ_t dx of this (sample, channel) row — the bias gradient of the conv in front of the BatchNorm is Σ_b of these: the conv's
-  // backward then needs no pass of its own over dx.  A row's 2^shift threads are consecutive: a xor butterfly inside the wave,
-  // then (rows wider than a wave) the waves' totals through LDS in wave order.
-  if (row_sums) {                                          // uniform
-    const int w = rv.shift < 6 ? rv.shift : 6;
-    for (int o = (1 << w) >> 1; o > 0; o >>= 1) rs += __shfl_xor(rs, o, 64);      // w = 0 (one thread per row): no step
-    if (rv.shift <= 6) {
-      if (live && t0 == 0) row_sums[bc] = rs;
-    } else {
-      if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = rs;
-      __syncthreads();
-      if (live && t0 == 0) {
-        const int w0 = threadIdx.x >> 6, nw = 1 << (rv.shift - 6);
-        float tot = 0.f;
-        for (int i = 0; i < nw; ++i) tot += wsum[w0 + i];
-        row_sums[bc] = tot;
-      }
-    }
-  }
+  if (row_sums) bn_row_sum_store(rs, row_sums, bc, live, t0, rv, wsum);      // uniform
 }
 
 extern "C" int fst_bn_bwd_apply(const float* dy, const float* y, const float* out, const float* stats, const float* red,
                                 int n_slots, float* red_out, float* dx, float* row_sums, int B, int C, int L, int relu, int train,
                                 int B_total, int64_t numel, void* stream) {
-  FST_REQUIRE(dy && y && stats && dx && (!relu || out) && (!train || red), "fst_bn_bwd_apply: bad arguments");
+  FST_REQUIRE(dy && y && stats && dx && (!train || red), "fst_bn_bwd_apply: bad arguments");
   FST_REQUIRE(B > 0 && C > 0 && L > 0 && B_total >= B, "fst_bn_bwd_apply: B=%d C=%d L=%d B_total=%d", B, C, L, B_total);
   FST_REQUIRE(!red || n_slots > 0, "fst_bn_bwd_apply: n_slots=%d", n_slots);
   FST_REQUIRE(!red_out || red, "fst_bn_bwd_apply: red_out needs red");
   FST_REQUIRE_EXTENT("fst_bn_bwd_apply", B, C, L, numel);     // the launch walks B (not B_total) samples
+  if (!relu) out = nullptr;
   if (vec_ok(L, {dy, y, out, dx})) {
     const RowVec rv = row_vec(L);
     const int rpp = 256 >> rv.shift;
@@ -495,6 +626,131 @@ extern "C" int fst_bn_bwd_apply(const float* dy, const float* y, const float* ou
   } else {
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(B * C), dim3(256), 0, (hipStream_t)stream, dy, y, out, stats, red, n_slots,
                        red_out, dx, row_sums, C, L, relu, train, 1.0f / ((float)B_total * (float)L));
+  }
+  FST_LAUNCH_CHECK();
+  return 0;
+}
+
+// One branch of the join's apply: what fst_bn_bwd_apply takes per BatchNorm.  dx == nullptr: the branch needs no input
+// gradient — nothing of it is stored but red_out.
+struct BnJoinBranch {
+  const float* y;
+  const float* stats;
+  const float* red;
+  float* red_out;
+  float* dx;
+  float* row_sums;
+};
+
+__global__ __launch_bounds__(256) void bn_bwd_apply_join_kernel(const float* dy, BnJoinBranch a, BnJoinBranch b, int n_slots,
+                                                                int C, int L, int train, float invN) {
+#pragma clang fp contract(off)
+  const int bc = blockIdx.x;
+  const int c = bc % C;
+  const float meana = a.stats[c], invstda = a.stats[C + c], sca = a.stats[2 * C + c], sha = a.stats[3 * C + c];
+  const float meanb = b.stats[c], invstdb = b.stats[C + c], scb = b.stats[2 * C + c], shb = b.stats[3 * C + c];
+  float ra1 = 0.f, ra2 = 0.f, rb1 = 0.f, rb2 = 0.f;
+  if (a.red) bn_red_sums(a.red, n_slots, C, c, ra1, ra2);
+  if (b.red) bn_red_sums(b.red, n_slots, C, c, rb1, rb2);
+  if (bc < C && threadIdx.x == 0) {
+    if (a.red_out) { a.red_out[c] = ra1; a.red_out[C + c] = ra2; }
+    if (b.red_out) { b.red_out[c] = rb1; b.red_out[C + c] = rb2; }
+  }
+  if (!a.dx && !b.dx) return;                              // uniform
+  const float ma1 = train ? ra1 * invN : 0.f, ma2 = train ? ra2 * invN : 0.f;
+  const float mb1 = train ? rb1 * invN : 0.f, mb2 = train ? rb2 * invN : 0.f;
+  const long long base = (long long)bc * L;
+  float rsa = 0.f, rsb = 0.f;
+  for (int t = threadIdx.x; t < L; t += 256) {
+    const float va = a.y[base + t], vb = b.y[base + t];
+    const float g = bn_masked(dy[base + t], bn_pre_join(va, sca, sha, vb, scb, shb));
+    if (a.dx) {
+      const float u = bn_dx_unscaled(g, va, meana, invstda, ma1, ma2);
+      a.dx[base + t] = sca * u;
+      rsa = __builtin_fmaf(sca, u, rsa);
+    }
+    if (b.dx) {
+      const float u = bn_dx_unscaled(g, vb, meanb, invstdb, mb1, mb2);
+      b.dx[base + t] = scb * u;
+      rsb = __builtin_fmaf(scb, u, rsb);
+    }
+  }
+  if (a.row_sums || b.row_sums) {                          // uniform
+    block_sum2(rsa, rsb);
+    if (threadIdx.x == 0) {
+      if (a.row_sums) a.row_sums[bc] = rsa;
+      if (b.row_sums) b.row_sums[bc] = rsb;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void bn_bwd_apply_join_vec_kernel(const float* dy, BnJoinBranch a, BnJoinBranch b, int n_slots,
+                                                                    int rows, int C, int L, int train, float invN, RowVec rv) {
+#pragma clang fp contract(off)
+  __shared__ float wsum[2][4];
+  const int r = threadIdx.x >> rv.shift, t0 = threadIdx.x & ((1 << rv.shift) - 1), rpp = 256 >> rv.shift;
+  const int bc_raw = blockIdx.x * rpp + r;
+  const bool live = bc_raw < rows;
+  const int bc = live ? bc_raw : rows - 1;                 // (idle row groups of the last block walk the last row and store nothing)
+  const int c = bc % C;
+  const float meana = a.stats[c], invstda = a.stats[C + c], sca = a.stats[2 * C + c], sha = a.stats[3 * C + c];
+  const float meanb = b.stats[c], invstdb = b.stats[C + c], scb = b.stats[2 * C + c], shb = b.stats[3 * C + c];
+  float ra1 = 0.f, ra2 = 0.f, rb1 = 0.f, rb2 = 0.f;
+  if (a.red) bn_red_sums(a.red, n_slots, C, c, ra1, ra2);
+  if (b.red) bn_red_sums(b.red, n_slots, C, c, rb1, rb2);
+  if (live && bc < C && t0 == 0) {
+    if (a.red_out) { a.red_out[c] = ra1; a.red_out[C + c] = ra2; }
+    if (b.red_out) { b.red_out[c] = rb1; b.red_out[C + c] = rb2; }
+  }
+  if (!a.dx && !b.dx) return;                              // uniform
+  const float ma1 = train ? ra1 * invN : 0.f, ma2 = train ? ra2 * invN : 0.f;
+  const float mb1 = train ? rb1 * invN : 0.f, mb2 = train ? rb2 * invN : 0.f;
+  const long long base = (long long)bc * rv.L4;
+  const float4* dy4 = reinterpret_cast<const float4*>(dy) + base;
+  const float4* ya4 = reinterpret_cast<const float4*>(a.y) + base;
+  const float4* yb4 = reinterpret_cast<const float4*>(b.y) + base;
+  float4* dxa4 = reinterpret_cast<float4*>(a.dx) + base;                     // not dereferenced when the dx is null
+  float4* dxb4 = reinterpret_cast<float4*>(b.dx) + base;
+  float rsa = 0.f, rsb = 0.f;
+  for (int t = t0; t < rv.L4; t += 1 << rv.shift) {
+    const float4 va = ya4[t], vb = yb4[t];
+    const float4 g = bn_masked4(dy4[t], bn_pre_join4(va, sca, sha, vb, scb, shb));
+    if (a.dx) {
+      const float4 d = bn_dx4(g, va, meana, invstda, sca, ma1, ma2);
+      if (live) dxa4[t] = d;
+      rsa += bn_g4(d);
+    }
+    if (b.dx) {
+      const float4 d = bn_dx4(g, vb, meanb, invstdb, scb, mb1, mb2);
+      if (live) dxb4[t] = d;
+      rsb += bn_g4(d);
+    }
+  }
+  if (a.row_sums) bn_row_sum_store(rsa, a.row_sums, bc, live, t0, rv, wsum[0]);      // uniform
+  if (b.row_sums) bn_row_sum_store(rsb, b.row_sums, bc, live, t0, rv, wsum[1]);      // uniform
+}
+
+extern "C" int fst_bn_bwd_apply_join(const float* dy, const float* ya, const float* yb, const float* stats_a,
+                                     const float* stats_b, const float* red_a, const float* red_b, int n_slots,
+                                     float* red_out_a, float* red_out_b, float* dxa, float* dxb, float* row_sums_a,
+                                     float* row_sums_b, int B, int C, int L, int train, int B_total, int64_t numel, void* stream) {
+  FST_REQUIRE(dy && ya && yb && stats_a && stats_b && (dxa || dxb || red_out_a || red_out_b), "fst_bn_bwd_apply_join: bad arguments");
+  FST_REQUIRE(!train || (red_a && red_b), "fst_bn_bwd_apply_join: train mode needs both branches' partial sums");
+  FST_REQUIRE((dxa || !row_sums_a) && (dxb || !row_sums_b), "fst_bn_bwd_apply_join: row sums of a branch without dx");
+  FST_REQUIRE(!dxa || dxa != dxb, "fst_bn_bwd_apply_join: the two dx are the same buffer");
+  FST_REQUIRE(B > 0 && C > 0 && L > 0 && B_total >= B, "fst_bn_bwd_apply_join: B=%d C=%d L=%d B_total=%d", B, C, L, B_total);
+  FST_REQUIRE((!red_a && !red_b) || n_slots > 0, "fst_bn_bwd_apply_join: n_slots=%d", n_slots);
+  FST_REQUIRE((!red_out_a || red_a) && (!red_out_b || red_b), "fst_bn_bwd_apply_join: red_out needs red");
+  FST_REQUIRE_EXTENT("fst_bn_bwd_apply_join", B, C, L, numel);     // the launch walks B (not B_total) samples
+  const BnJoinBranch a = {ya, stats_a, red_a, red_out_a, dxa, row_sums_a}, b = {yb, stats_b, red_b, red_out_b, dxb, row_sums_b};
+  const float invN = 1.0f / ((float)B_total * (float)L);
+  if (vec_ok(L, {dy, ya, yb, dxa, dxb})) {
+    const RowVec rv = row_vec(L);
+    const int rpp = 256 >> rv.shift;
+    hipLaunchKernelGGL(bn_bwd_apply_join_vec_kernel, dim3((B * C + rpp - 1) / rpp), dim3(256), 0, (hipStream_t)stream, dy, a, b,
+                       n_slots, B * C, C, L, train, invN, rv);
+  } else {
+    hipLaunchKernelGGL(bn_bwd_apply_join_kernel, dim3(B * C), dim3(256), 0, (hipStream_t)stream, dy, a, b, n_slots, C, L, train, invN);
   }
   FST_LAUNCH_CHECK();
   return 0;

@@ -810,6 +810,8 @@ def _bn_stats(y: Tensor, gamma: Tensor, beta: Tensor, rmean: Tensor, rvar: Tenso
 
 def _bn_backward(dy: Tensor, y: Tensor, out: Optional[Tensor], stats: Tensor, relu: bool, training: bool,
                  need_dx: bool = True):
+    """``out`` is needed for nothing but the ReLU mask [out > 0]; with ``relu`` and ``out=None`` the kernels take the same mask
+    from ``y`` and ``stats`` (the forward's own pre-activation function) and read one tensor less per pass."""
     lib = _lib.load()
     B, C, L = y.shape
     # per-slot partial sums [2][C][slots] (Σ dy', Σ dy'·x̂), written by the kernel; fst_bn_bwd_apply adds the slots in order and
@@ -841,6 +843,48 @@ def _bn_backward(dy: Tensor, y: Tensor, out: Optional[Tensor], stats: Tensor, re
     return dx, red[C:], red[:C]                                   # dx, dgamma, dbeta
 
 
+def _bn_backward_join(dy: Tensor, ya: Tensor, yb: Tensor, sa: Tensor, sb: Tensor, training: bool, need_dxa: bool,
+                      need_dxb: bool):
+    """Backward of relu(BN_a(ya) + BN_b(yb)): the branches share ``dy`` and the mask, so ONE reduce and ONE apply walk
+    dy, ya, yb for both (8 tensor passes; a ``_bn_backward`` per branch takes 14).  Per branch the results are the ones
+    ``_bn_backward`` returns, bit for bit."""
+    lib = _lib.load()
+    B, C, L = ya.shape
+    dev = ya.device
+    parts = torch.empty(2, 2, C, BN_SLOTS, device=dev, dtype=torch.float32)          # [branch][Σ dy', Σ dy'·x̂][C][slots]
+    check(lib.fst_bn_bwd_reduce_join(ptr(dy), ptr(ya), ptr(yb), ptr(sa), ptr(sb), B, C, L, ptr(parts[0]), ptr(parts[1]),
+                                     _same_numel(dy, ya, yb), stream_ptr()), "fst_bn_bwd_reduce_join")
+    need = (need_dxa, need_dxb)
+    dx = [torch.empty_like(y) if n else None for y, n in zip((ya, yb), need)]
+    rs = [torch.empty(B, C, device=dev, dtype=torch.float32) if n else None for n in need]
+    red = [None, None]
+    if any(need):
+        if training and _dist.global_batch_active():
+            # as in _bn_backward: the batch means run over every rank's samples, the parameter gradients stay local sums
+            local = parts.sum(dim=3).view(2, 2 * C)
+            red_g = local.clone()
+            B_total = _dist.sum_over_ranks_(red_g) * B
+            check(lib.fst_bn_bwd_apply_join(ptr(dy), ptr(ya), ptr(yb), ptr(sa), ptr(sb), ptr(red_g[0]), ptr(red_g[1]), 1, None, None,
+                                            ptr(dx[0]), ptr(dx[1]), ptr(rs[0]), ptr(rs[1]), B, C, L, int(training), B_total,
+                                            _same_numel(dy, ya, yb, *dx), stream_ptr()), "fst_bn_bwd_apply_join")
+            red = [local[i] if need[i] else None for i in range(2)]
+        else:
+            sums = torch.empty(2, 2 * C, device=dev, dtype=torch.float32)
+            check(lib.fst_bn_bwd_apply_join(ptr(dy), ptr(ya), ptr(yb), ptr(sa), ptr(sb), ptr(parts[0]), ptr(parts[1]), BN_SLOTS,
+                                            ptr(sums[0]) if need[0] else None, ptr(sums[1]) if need[1] else None,
+                                            ptr(dx[0]), ptr(dx[1]), ptr(rs[0]), ptr(rs[1]), B, C, L, int(training), B,
+                                            _same_numel(dy, ya, yb, *dx), stream_ptr()), "fst_bn_bwd_apply_join")
+            red = [sums[i] if need[i] else None for i in range(2)]
+    res = []
+    for i in range(2):
+        if need[i]:
+            _ROW_SUMS.attach(dx[i], rs[i])
+        else:
+            red[i] = parts[i].sum(dim=2).view(2 * C)          # the need_dx = False form of _bn_backward
+        res.append((dx[i], red[i][C:], red[i][:C]))           # dx, dgamma, dbeta
+    return res
+
+
 class BNActFn(torch.autograd.Function):
     """BatchNorm1d (train: batch stats + running update; eval: running stats) → optional ReLU."""
 
@@ -853,15 +897,14 @@ class BNActFn(torch.autograd.Function):
         out = torch.empty_like(y)
         check(lib.fst_bn_apply(ptr(y), ptr(stats), None, None, ptr(out), B, C, L, int(relu), _same_numel(y, out), stream_ptr()),
               "fst_bn_apply")
-        ctx.save_for_backward(y, out, stats)
+        ctx.save_for_backward(y, stats)                        # not out: the backward takes the ReLU mask from y and stats
         ctx.relu, ctx.training = relu, training
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        y, out, stats = ctx.saved_tensors
-        dx, dg, db = _bn_backward(dout.contiguous(), y, out if ctx.relu else None, stats, ctx.relu, ctx.training,
-                                  ctx.needs_input_grad[0])
+        y, stats = ctx.saved_tensors
+        dx, dg, db = _bn_backward(dout.contiguous(), y, None, stats, ctx.relu, ctx.training, ctx.needs_input_grad[0])
         return dx, dg, db, None, None, None, None, None, None
 
 
@@ -878,16 +921,15 @@ class BNAddBNReluFn(torch.autograd.Function):
         out = torch.empty_like(ya)
         check(lib.fst_bn_apply(ptr(ya), ptr(sa), ptr(yb), ptr(sb), ptr(out), B, C, L, 1, _same_numel(ya, yb, out), stream_ptr()),
               "fst_bn_apply")
-        ctx.save_for_backward(ya, yb, out, sa, sb)
+        ctx.save_for_backward(ya, yb, sa, sb)
         ctx.training = training
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        ya, yb, out, sa, sb = ctx.saved_tensors
-        dout = dout.contiguous()
-        dxa, dga, dba = _bn_backward(dout, ya, out, sa, True, ctx.training, ctx.needs_input_grad[0])
-        dxb, dgb, dbb = _bn_backward(dout, yb, out, sb, True, ctx.training, ctx.needs_input_grad[5])
+        ya, yb, sa, sb = ctx.saved_tensors
+        (dxa, dga, dba), (dxb, dgb, dbb) = _bn_backward_join(dout.contiguous(), ya, yb, sa, sb, ctx.training,
+                                                             ctx.needs_input_grad[0], ctx.needs_input_grad[5])
         return dxa, dga, dba, None, None, dxb, dgb, dbb, None, None, None, None, None
 
 

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FST_ABI_VERSION 14
+#define FST_ABI_VERSION 15
 
 int fst_version(void);
 const char* fst_last_error(void);
@@ -179,8 +179,13 @@ int fst_bn_finalize(const float* part, int n_slots, const float* gamma, const fl
 /* out = act(y*scale + shift (+ res*res_scale + res_shift | + res)) */
 int fst_bn_apply(const float* y, const float* stats, const float* res, const float* res_stats,
                  float* out, int B, int C, int L, int relu, int64_t numel, void* stream);
-/* reductions for backward, as FST_BN_SLOTS partial sums per channel (written, no zero fill, no atomics):
- * red[0][c][slot] = Σ dyʹ, red[1][c][slot] = Σ dyʹ·x̂, with dyʹ = dy·[out>0] when relu */
+/* The BatchNorm's value of an element in front of the ReLU is pre(y) = fma(y, scale, shift) — for the join,
+ * pre(ya) + pre(yb) — and fst_bn_apply stores max(pre, 0).  The backward functions need the ReLU only as the mask [out > 0],
+ * and take it either from `out` (when the caller kept it) or, with out = NULL, from the sign of pre recomputed from y and stats
+ * by the very function the forward calls: the same bits, one tensor read less per pass.
+ *
+ * reductions for backward, as FST_BN_SLOTS partial sums per channel (written, no zero fill, no atomics):
+ * red[0][c][slot] = Σ dyʹ, red[1][c][slot] = Σ dyʹ·x̂, with dyʹ = dy·[out>0] when relu (out may be NULL: dy·[pre(y)>0]) */
 int fst_bn_bwd_reduce(const float* dy, const float* y, const float* out, const float* stats,
                       int B, int C, int L, int relu, float* red /* [2][C][FST_BN_SLOTS] */, int64_t numel, void* stream);
 /* dx = scale·(dyʹ − r0/N − x̂·r1/N) in train mode, scale·dyʹ in eval mode; r = the n_slots partials of red added in slot order
@@ -188,10 +193,23 @@ int fst_bn_bwd_reduce(const float* dy, const float* y, const float* out, const f
  * N = B_total·L.  B is the batch of the tensors (launch shape); B_total >= B the batch red was summed over (= B, or all
  * ranks' batches for SyncBN).  red_out (optional, [2C]): receives (r0 | r1) = (dβ | dγ).  row_sums (optional, [B][C]): receives
  * Σ_t dx[b][c][t] — summed over b, the bias gradient of the conv in front of the BatchNorm (OS_CNN.py:67-72: conv1d with bias →
- * BatchNorm1d), which then needs no pass of its own over dx. */
+ * BatchNorm1d), which then needs no pass of its own over dx.  out: as for fst_bn_bwd_reduce (NULL with relu: mask from y). */
 int fst_bn_bwd_apply(const float* dy, const float* y, const float* out, const float* stats, const float* red, int n_slots,
                      float* red_out, float* dx, float* row_sums, int B, int C, int L, int relu, int train, int B_total,
                      int64_t numel, void* stream);
+/* Backward of the residual join out = relu(pre_a(ya) + pre_b(yb)) (fst_bn_apply with res and res_stats): both branches share dy
+ * and the mask [pre_a(ya) + pre_b(yb) > 0], so one reduce walks dy, ya, yb once and one apply walks them once more and writes
+ * both dx — 8 tensor passes where two fst_bn_bwd_reduce / fst_bn_bwd_apply pairs take 14.  Every result (partials, red_out, dx,
+ * row sums) has the bits the two single-branch pairs leave: same element arithmetic, same summation order per branch.
+ * red_a, red_b: distinct [2][C][FST_BN_SLOTS] buffers, laid out as fst_bn_bwd_reduce's. */
+int fst_bn_bwd_reduce_join(const float* dy, const float* ya, const float* yb, const float* stats_a, const float* stats_b,
+                           int B, int C, int L, float* red_a, float* red_b, int64_t numel, void* stream);
+/* n_slots, B_total, train, red_out_*, row_sums_*: as for fst_bn_bwd_apply, shared by the branches.  dxa or dxb may be NULL
+ * (that branch needs no input gradient; its row_sums must be NULL too): its red_out is still written. */
+int fst_bn_bwd_apply_join(const float* dy, const float* ya, const float* yb, const float* stats_a, const float* stats_b,
+                          const float* red_a, const float* red_b, int n_slots, float* red_out_a, float* red_out_b,
+                          float* dxa, float* dxb, float* row_sums_a, float* row_sums_b, int B, int C, int L, int train,
+                          int B_total, int64_t numel, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * WaveGlow pieces — Simplified_NF_WaveGlow.py
