@@ -808,6 +808,16 @@ def _bn_stats(y: Tensor, gamma: Tensor, beta: Tensor, rmean: Tensor, rvar: Tenso
     return stats
 
 
+def _bn_slot_sum(part: Tensor) -> Tensor:
+    """Σ over the last (slot) dimension in slot order — the order fst_bn_bwd_apply adds the slots in, so the parameter gradients of a
+    backward that wants no dx (no apply launch) carry the same bits as those of one that does; torch's own reduction of 16
+    contiguous elements adds them in another order.  (Off the train step's path: a BatchNorm input there always wants its gradient.)"""
+    red = part[..., 0].clone()
+    for s in range(1, part.size(-1)):
+        red += part[..., s]
+    return red
+
+
 def _bn_backward(dy: Tensor, y: Tensor, out: Optional[Tensor], stats: Tensor, relu: bool, training: bool,
                  need_dx: bool = True):
     """``out`` is needed for nothing but the ReLU mask [out > 0]; with ``relu`` and ``out=None`` the kernels take the same mask
@@ -821,7 +831,7 @@ def _bn_backward(dy: Tensor, y: Tensor, out: Optional[Tensor], stats: Tensor, re
                                 stream_ptr()),
           "fst_bn_bwd_reduce")
     if not need_dx:
-        red = part.sum(dim=2).view(2 * C)
+        red = _bn_slot_sum(part).view(2 * C)
         return None, red[C:], red[:C]
     dx = torch.empty_like(y)
     # Σ_t dx per (sample, channel), left by the same launch: the conv in front of this BatchNorm takes its bias gradient from them
@@ -880,7 +890,7 @@ def _bn_backward_join(dy: Tensor, ya: Tensor, yb: Tensor, sa: Tensor, sb: Tensor
         if need[i]:
             _ROW_SUMS.attach(dx[i], rs[i])
         else:
-            red[i] = parts[i].sum(dim=2).view(2 * C)          # the need_dx = False form of _bn_backward
+            red[i] = _bn_slot_sum(parts[i]).view(2 * C)       # the need_dx = False form of _bn_backward
         res.append((dx[i], red[i][C:], red[i][:C]))           # dx, dgamma, dbeta
     return res
 
@@ -1108,13 +1118,25 @@ class WNGradPool:
     """Weight-gradient operands of the applications of ONE WN whose weights go through ``WGradJoinFn``: every application's
     backward leaves (dg, a, u0) / (d_a, d_out, ts) of each layer here instead of launching its own weight-gradient kernels; the
     join node's backward — which autograd runs after ALL applications that take part in the pass — sums them with one launch per
-    layer and kind."""
+    layer and kind.  ``ctx.needs_input_grad`` is fixed at forward time, so an application also defers in a pass that asks for a data
+    gradient only and never reaches the join (``autograd.grad(loss, [x])`` outside ``partial_backward()``): the pool therefore
+    remembers which backward pass (autograd graph task) its operands belong to, and operands of any other pass are dropped — by the
+    next pass's first ``add`` and by the join — never summed into a later pass's gradient."""
 
     def __init__(self):
         self.pending: dict = {}
+        self.task = None               # id of the backward pass that left ``pending``
 
     def add(self, key, operands) -> None:
+        task = torch._C._current_graph_task_id()
+        if task != self.task:
+            self.pending, self.task = {}, task
         self.pending.setdefault(key, []).append(operands)
+
+    def take(self) -> dict:
+        """The operands recorded by the running backward pass (and only those); the pool is left empty."""
+        pending, self.pending = self.pending, {}
+        return pending if self.task == torch._C._current_graph_task_id() else {}
 
 
 class WGradJoinFn(torch.autograd.Function):
@@ -1130,7 +1152,7 @@ class WGradJoinFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         S, pool = ctx.specs, ctx.pool
-        pending, pool.pending = pool.pending, {}
+        pending = pool.take()
         if not pending:
             return None, None, g
         g = g.contiguous()
