@@ -57,7 +57,7 @@ SHAPES = [
 
 @needs_bf3
 @pytest.mark.parametrize("M,N,K", SHAPES)
-@pytest.mark.parametrize("ta,tb", [(False, False), (False, True), (True, True)])
+@pytest.mark.parametrize("ta,tb", [(False, False), (False, True), (True, False), (True, True)])
 def test_gemm_layouts_vs_fp64(M, N, K, ta, tb):
     g = torch.Generator().manual_seed(M * 7 + N * 3 + K + 2 * ta + tb)
     A = torch.randn((K, M) if ta else (M, K), generator=g).to(DEV)
