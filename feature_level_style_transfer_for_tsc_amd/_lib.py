@@ -12,7 +12,7 @@ from typing import Optional
 
 import torch
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 _LIB_NAME = "libfst_hip.so"
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FST_HIP_LIB", os.path.join(_HERE, _LIB_NAME))     # override: diagnostic builds only
@@ -60,6 +60,8 @@ _SIGNATURES = {
     "fst_coupling_inv_bwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int64, c_void_p]),
     "fst_rmsprop_multi": (c_int, [_P, _P, _P, _P, _P, c_int, c_float, c_float, c_void_p]),
     "fst_adam_multi": (c_int, [_P, _P, _P, _P, _P, c_int, _P, c_float, c_float, c_float, c_float, c_void_p]),
+    "fst_rmsprop_multi_dev": (c_int, [_P, _P, _P, _P, _P, c_int, c_float, c_float, c_void_p]),
+    "fst_adam_multi_dev": (c_int, [_P, _P, _P, _P, _P, c_int, _P, _P, c_float, c_float, c_float, c_void_p]),
     "fst_wn_stack_fwd_ok": (c_int, [c_int, c_int, c_int, c_int]),
     "fst_wn_stack_fwd": (c_int, [_P, _P, _P, c_int64, _P, _P, _P, c_int64, _P, c_int, c_int, c_int, c_int, c_int, c_int64, c_void_p]),
     "fst_wn_stack_bwd_ok": (c_int, [c_int, c_int, c_int, c_int]),

@@ -11,9 +11,14 @@ Differences from the reference are mechanical, not numerical:
   - during GradNorm's five partial backward passes only the shared OS_block needs weight gradients, so
     every other conv skips its weight-gradient kernels (``ops.partial_backward``).
 Data parallelism: ``dist.GradBucket`` all-reduces one flat fp32 gradient bucket over RCCL.
+
+Schedules (train_and_test.py:118-134, :665-672): ``make_schedulers`` builds the reference's eleven learning-rate schedulers
+on a trainer's optimisers and ``end_epoch`` steps the ones the reference steps.  A captured step follows them only after
+``enable_device_hparams()``, which moves the learning rates and the four epoch coefficients into device tensors.
 """
 from __future__ import annotations
 
+import warnings
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
@@ -26,7 +31,7 @@ from .cdan import CDAN, RandomLayer
 from .cpc import CPC
 from . import dist as _dist
 from .dist import GradBucket
-from .optim import FusedRMSprop, SharedStepAdam, rmsprop_step_many
+from .optim import FusedRMSprop, SharedStepAdam, push_lr, rmsprop_step_many
 from .os_cnn import OS_CNN, OS_CNN_res, build_layer_with_layer_parameter
 from .structure import generate_layer_parameter_list, layer_parameter_list_input_change, out_channels
 from .waveglow import WaveGlow, WaveGlowLoss
@@ -55,6 +60,66 @@ def loss_coefficients(epoch: int) -> Tuple[float, float, float, float]:
     return 1.5, 1.5, 2.5, 2.5
 
 
+# ---- the reference's learning-rate schedules (train_and_test.py:118-134), on a device-free footing so the table can be tested
+STEP_LR = {"fe_t": (25, 0.8), "clf_t": (25, 0.8), "fe_s": (25, 0.8), "dimunif": (25, 0.8), "clf_s": (25, 0.8),
+           "cpc": (25, 0.7), "noise": (55, 0.6)}                               # name -> (step_size, gamma)
+PLATEAU = ("probtransfer", "nf", "ad_net", "fd_s")                             # ReduceLROnPlateau('min', factor=0.7, min_lr=1e-4)
+EPOCH_SCHEDULERS = {                                                           # kind of epoch -> schedulers stepped after it
+    "target_pretrain": ("fe_t", "clf_t", "cpc"),                               # :172-174
+    "source_pretrain": ("fe_s", "dimunif", "clf_s"),                           # :211-213
+    "ssl_with_ce": ("fe_t", "clf_t", "cpc", "fe_s", "dimunif", "clf_s"),       # :275-280
+    "ssl": ("fe_t", "cpc", "fe_s", "dimunif"),                                 # :343-348
+    "nf_with_ce": ("fe_t", "clf_t", "fe_s", "dimunif", "clf_s", "cpc", "nf"),  # :436-442
+    "nf": ("fe_t", "fe_s", "dimunif", "nf"),                                   # :491-494
+    "joint": ("fe_t", "clf_t", "cpc", "fe_s", "dimunif", "clf_s", "probtransfer", "nf", "noise", "ad_net", "fd_s"),  # :767-777
+}
+# The metric a plateau scheduler is given: a key of the epoch's LAST batch report, or None for the constant 0.0 (quirk Q8: the
+# reference zeroes cdan_loss.data and feature_discriminator_s_loss.data in place at :739-740 before :776-777 read them)
+PLATEAU_METRIC = {
+    "nf_with_ce": {"nf": "total"},                                             # :420, :442
+    "nf": {"nf": "total"},                                                     # :481, :494
+    "joint": {"probtransfer": "ce_s2t2s", "nf": "nf_t", "ad_net": None, "fd_s": None},   # :773-777
+}
+
+
+def make_schedulers(opts: Dict[str, torch.optim.Optimizer]) -> Dict[str, object]:
+    """The reference's scheduler for every optimiser of ``opts`` it schedules ({module name: optimiser}, "cpc" for CPC's Adam):
+    stock ``torch.optim.lr_scheduler`` objects, {name: scheduler}."""
+    sch = torch.optim.lr_scheduler
+    out = {}
+    for k, o in opts.items():
+        if k in STEP_LR:
+            out[k] = sch.StepLR(o, step_size=STEP_LR[k][0], gamma=STEP_LR[k][1])
+        elif k in PLATEAU:
+            out[k] = sch.ReduceLROnPlateau(o, "min", factor=0.7, min_lr=0.0001)
+    return out
+
+
+def step_schedulers(schedulers: Dict[str, object], kind: str, report: Dict[str, torch.Tensor], bucket=None) -> None:
+    """Step the schedulers the reference steps after an epoch of ``kind`` (a phase name or "joint"); ``report`` is the epoch's
+    last batch report.  With a ``GradBucket`` the plateau metrics are averaged over the ranks first, so that every rank's
+    schedulers take the same decisions."""
+    if kind not in EPOCH_SCHEDULERS:
+        raise ValueError(f"unknown kind of epoch {kind!r}; one of {sorted(EPOCH_SCHEDULERS)}")
+    metric_of = PLATEAU_METRIC.get(kind, {})
+    keys = [k for k in EPOCH_SCHEDULERS[kind] if metric_of.get(k) is not None]
+    values = {}
+    if keys:
+        vals = torch.stack([report[metric_of[k]].detach().float().reshape(()) for k in keys])
+        if bucket is not None:
+            vals = bucket.mean_scalars(vals)
+        values = dict(zip(keys, vals.tolist()))
+    with warnings.catch_warnings():
+        # torch warns when a scheduler steps before its optimiser's step() was ever called: the trainers step the optimisers
+        # through rmsprop_step_many and graph replays, never through step()
+        warnings.filterwarnings("ignore", message="Detected call of `lr_scheduler.step\\(\\)` before", category=UserWarning)
+        for k in EPOCH_SCHEDULERS[kind]:
+            if k in PLATEAU:
+                schedulers[k].step(values.get(k, 0.0))
+            else:
+                schedulers[k].step()
+
+
 # hipGraph capture must not be invalidated by other threads' HIP calls: with an RCCL communicator alive, PyTorch's
 # watchdog thread polls events while the step is being captured ("global" mode would then abort the capture).
 _CAPTURE_MODE = "thread_local"
@@ -62,7 +127,7 @@ _CAPTURE_MODE = "thread_local"
 
 class ClassifierTrainer:
     def __init__(self, length: int, in_channel: int, n_class: int, device, bucket: Optional[GradBucket] = None,
-                 sync: str = "ddp"):
+                 sync: str = "ddp", device_hparams: bool = False):
         self.sync = sync
         fe_spec, clf_spec = specs_for(length, in_channel)
         self.fe = OS_CNN_res(fe_spec).to(device)
@@ -73,6 +138,20 @@ class ClassifierTrainer:
         self.bucket = bucket
         self.fe.train(); self.clf.train()
         self._graph = None
+        self.device_hparams = False
+        if device_hparams:
+            self.enable_device_hparams()
+
+    def enable_device_hparams(self) -> None:
+        """Keep both learning rates in device tensors (``optim.push_lr``): ``replay`` then trains at the current ``group["lr"]`` of
+        ``opt_fe`` / ``opt_clf`` — what a ``torch.optim.lr_scheduler`` on them has set — instead of the rates of capture day.
+        Idempotent; before ``capture`` only (a resident graph holds the launches that take the rates by value)."""
+        if self.device_hparams:
+            return
+        if self._graph is not None:
+            raise RuntimeError("enable_device_hparams(): a capture is resident; enable the mode before capture()")
+        self.opt_fe.enable_lr_on_device(); self.opt_clf.enable_lr_on_device()
+        self.device_hparams = True
 
     def parameters(self) -> List[nn.Parameter]:
         return list(self.fe.parameters()) + list(self.clf.parameters())
@@ -91,6 +170,7 @@ class ClassifierTrainer:
 
     # ---- single GPU: the whole step as one hipGraph (the eager step is launch-bound: ~300 launches for ~2 ms of GPU work)
     def capture(self, x: torch.Tensor, y: torch.Tensor, warmup: int = 3):
+        """Capture one step.  The learning rates are baked into the graph unless ``enable_device_hparams()`` ran before."""
         if self.bucket is not None:
             raise RuntimeError("ClassifierTrainer.capture(): single-GPU only (the DP step has an eager all-reduce)")
         self._g_x, self._g_y = x.clone(), y.clone()
@@ -106,10 +186,13 @@ class ClassifierTrainer:
             self._g_out = self.step(self._g_x, self._g_y)
 
     def replay(self, x: torch.Tensor, y: torch.Tensor):
-        """One captured step on a new batch of the captured shape; returns (loss, logits) in static buffers."""
+        """One captured step on a new batch of the captured shape; returns (loss, logits) in static buffers.  With
+        ``device_hparams`` it runs at the optimisers' current ``group["lr"]``, otherwise at the captured rates."""
         if self._graph is None:
             raise RuntimeError("call capture() first")
         self._g_x.copy_(x); self._g_y.copy_(y)
+        if self.device_hparams:
+            push_lr((self.opt_fe, self.opt_clf))
         self._graph.replay()
         return self._g_out
 
@@ -137,10 +220,10 @@ class JointTrainer:
            "nf": 0.001, "noise": 0.005, "ad_net": 0.001, "fd_s": 0.001}       # train_and_test.py:97-106
 
     def __init__(self, cfg: JointConfig, device, bucket: Optional[GradBucket] = None, fe_t_spec=None, clf_spec=None,
-                 fe_s_spec=None, sync: str = "ddp"):
+                 fe_s_spec=None, sync: str = "ddp", device_hparams: bool = False):
         """``sync`` (with a bucket): "ddp" = per-rank batch statistics (SURVEY §8e mode A); "global" = every
         batch-coupled quantity over the samples of all ranks (mode B, eager only) — N ranks reproduce the
-        single-process step on the concatenated batch."""
+        single-process step on the concatenated batch.  ``device_hparams``: ``enable_device_hparams()`` at once."""
         if sync not in ("ddp", "global"):
             raise ValueError(f"sync must be 'ddp' or 'global', got {sync!r}")
         self.cfg, self.device, self.bucket, self.sync = cfg, device, bucket, sync
@@ -184,12 +267,70 @@ class JointTrainer:
         self._side = torch.cuda.Stream(device=device)                         # launch-bound side chains (CPC)
         self._phase: Dict[str, dict] = {}                                     # captured pre-training phases (capture_phase)
         self._phase_pool = None                                               # their shared graph memory pool
+        self._graphs = None                                                   # the captured joint step (capture)
+        self.device_hparams = False
+        self._coef = None                                                     # device_hparams: (cdan, fd_s, sl_t, sl_s) on the device
+        self._coef_host = None                                                # ... and the values it holds
+        self.schedulers = None                                                # make_schedulers()
+        self._sched_epoch = None                                              # epoch of the coefficients last applied
         for mod in self.m.values():
             mod.train()
         # GradNorm differentiates the shared OS_blocks only: their convs keep weight gradients in partial passes
         for key in ("fe_t", "fe_s"):
             for layer in self.m[key].return_last_layer().layer_list:
                 layer.spec.always_weight_grad = True
+        if device_hparams:
+            self.enable_device_hparams()
+
+    # ------------------------------------------------------------------ schedules under graph replay
+    def enable_device_hparams(self) -> None:
+        """Move what the reference schedules into device memory, so that captured steps follow it: the learning rates of the ten
+        RMSprops and CPC's Adam (``optim.push_lr`` carries ``group["lr"]`` over before every replay) and the four epoch
+        coefficients of ``loss_coefficients`` (``replay(..., epoch=)`` refreshes them).  The two GradNorm-weight Adams (never
+        scheduled by the reference) and the GRL coefficients (they saturate: quirk Q7) stay as they are.  Idempotent; raises
+        while a joint or phase capture is resident, whose launches take the values by value."""
+        if self.device_hparams:
+            return
+        if self._graphs is not None or self._phase:
+            raise RuntimeError("enable_device_hparams(): a capture is resident; enable the mode before capture() / capture_phase()")
+        for o in self._scheduled_opts():
+            o.enable_lr_on_device()
+        self._coef_host = tuple(float(v) for v in loss_coefficients(0))
+        self._coef = torch.tensor(self._coef_host, dtype=torch.float32, device=self.device)
+        self.device_hparams = True
+
+    def _scheduled_opts(self):
+        return list(self.opts.values()) + [self.opt_cpc]
+
+    def _set_epoch(self, epoch: int) -> None:
+        """Note the epoch a step runs at (it goes into the checkpoint); with ``device_hparams`` also bring the coefficient
+        tensor to ``loss_coefficients(epoch)`` (a stream-ordered copy, no wait)."""
+        self._sched_epoch = epoch
+        if not self.device_hparams:
+            return
+        want = tuple(float(v) for v in loss_coefficients(epoch))
+        if want != self._coef_host:
+            host = torch.tensor(want, dtype=torch.float32)
+            self._coef.copy_(host.pin_memory() if self._coef.is_cuda else host, non_blocking=True)
+            self._coef_host = want
+
+    def make_schedulers(self) -> Dict[str, object]:
+        """The reference's eleven schedulers (train_and_test.py:118-134) on this trainer's optimisers, {name: scheduler}; kept as
+        ``self.schedulers`` for ``end_epoch`` and the checkpoint."""
+        opts = dict(self.opts)
+        opts["cpc"] = self.opt_cpc
+        self.schedulers = make_schedulers(opts)
+        return self.schedulers
+
+    def end_epoch(self, kind: str, report: Dict[str, torch.Tensor]) -> int:
+        """After an epoch of ``kind`` (one of the six phase names or "joint"): step the schedulers the reference steps there, the
+        plateau ones on the epoch's last batch ``report`` (rank-averaged with a ``GradBucket``), then push the new rates to the
+        device (a no-op without ``device_hparams``, where eager steps read ``group["lr"]`` and captured ones keep their rates).
+        Returns the number of learning rates pushed."""
+        if self.schedulers is None:
+            raise RuntimeError("end_epoch(): call make_schedulers() first")
+        step_schedulers(self.schedulers, kind, report, self.bucket)
+        return push_lr(self._scheduled_opts())
 
     # ------------------------------------------------------------------ helpers
     def parameters(self) -> List[nn.Parameter]:
@@ -251,7 +392,9 @@ class JointTrainer:
         weights and their reference losses, NoiseTransfer's running sums and counters (Q5), the GRL call counters (Q7),
         the fixed CDAN random matrices and WaveGlow's cached — possibly stale — inverses (Q2).  The reference keeps
         none of this across runs (utils.py:9-25 saves the classification modules only); a captured-graph trainer that
-        cannot resume would be a gap of this build, not of the reference."""
+        cannot resume would be a gap of this build, not of the reference.  Once ``make_schedulers()`` has run, also
+        "schedules": the eleven schedulers' state, CPC's learning rate (the RMSprops' are in their ``param_groups``), the epoch of
+        the last step and its loss coefficients."""
         cpu = lambda t: t.detach().cpu().clone()
         cpc = self.opt_cpc
         noise = self.m["noise"]
@@ -278,12 +421,19 @@ class JointTrainer:
             "grl": {"ad_net": self.m["ad_net"].iter_num, "fd_s": self.m["fd_s"].iter_num},
             "random_matrix": [cpu(t) for t in self.random_layer.random_matrix],
             "w_inverse": [cpu(c.W_inverse) if hasattr(c, "W_inverse") else None for c in self.m["nf"].convinv],
+            **({} if self.schedulers is None else
+               {"schedules": {"schedulers": {k: s.state_dict() for k, s in self.schedulers.items()}, "epoch": self._sched_epoch,
+                              "cpc_lr": [g["lr"] for g in cpc.param_groups],       # "opts" carry theirs in param_groups
+                              "coefficients": None if self._sched_epoch is None else loss_coefficients(self._sched_epoch)}}),
         }
 
     def load_state_dict(self, sd: dict) -> None:
         """Inverse of ``state_dict``.  A captured graph holds the old buffers' addresses only for parameters and
-        optimiser moments that are restored IN PLACE here, but re-capture after loading anyway (GRL coefficients and
-        the epoch's loss coefficients are baked into a capture).  The RMSprop moments are NOT restored in place
+        optimiser moments that are restored IN PLACE here, but re-capture after loading anyway (GRL coefficients and,
+        unless ``device_hparams`` is on, the learning rates and the epoch's loss coefficients are baked into a capture; with
+        it on, the loaded ``group["lr"]`` reach the device with the next ``push_lr`` — every replay does one — and the loaded
+        epoch's coefficients are applied here).  A "schedules" entry is loaded into the schedulers of ``make_schedulers()``,
+        which is called here if it has not run; a checkpoint without the entry leaves them alone.  The RMSprop moments are NOT restored in place
         (``Optimizer.load_state_dict`` replaces the tensors), so a resident phase graph would update dead moments:
         every phase capture is dropped here and ``replay_phase`` raises until ``capture_phase`` has run again."""
         self.release_phase()
@@ -314,6 +464,16 @@ class JointTrainer:
                 c.W_inverse = w.to(dev)
             elif hasattr(c, "W_inverse"):
                 del c.W_inverse
+        if "schedules" in sd:
+            if self.schedulers is None:
+                self.make_schedulers()
+            for k, s in self.schedulers.items():
+                s.load_state_dict(sd["schedules"]["schedulers"][k])
+            for g, lr in zip(cpc.param_groups, sd["schedules"]["cpc_lr"]):
+                g["lr"] = lr
+            if sd["schedules"]["epoch"] is not None:
+                self._set_epoch(sd["schedules"]["epoch"])
+        push_lr(self._scheduled_opts())
 
     def save_state(self, path: str) -> None:
         torch.save(self.state_dict(), path)
@@ -447,8 +607,10 @@ class JointTrainer:
         ``capture`` does.  Any number of phases may be resident at once, next to the joint capture: the reference alternates
         "ssl" / "ssl_with_ce" and "nf" / "nf_with_ce".  Phase graphs never replay concurrently, so they share one memory pool;
         the reports are copied out of it, so a phase's report stays valid until that phase's next replay.  Capturing a phase
-        again replaces its graph.  ``on_grads_ready`` is called inside the captured region, as in ``capture``: it fires ONCE, at
-        capture time (on the gradient tensors the graph will write), not per replay and not during the warm-up."""
+        again replaces its graph.  The learning rates of the phase's optimisers are baked into the graph, unless
+        ``enable_device_hparams()`` ran before: then every ``replay_phase`` runs at their current ``group["lr"]``.
+        ``on_grads_ready`` is called inside the captured region, as in ``capture``: it fires ONCE, at capture time (on the gradient
+        tensors the graph will write), not per replay and not during the warm-up."""
         if phase not in self.PHASES:
             raise ValueError(f"unknown phase {phase!r}; one of {sorted(self.PHASES)}")
         if self.sync == "global" and self.bucket is not None and self.bucket.world > 1:
@@ -526,6 +688,8 @@ class JointTrainer:
             if v is not gi[k]:
                 gi[k].copy_(v, non_blocking=True)
         gi["t"].copy_(torch.tensor([int(t_samples[0]), int(t_samples[1])], dtype=torch.int32), non_blocking=True)
+        if self.device_hparams:
+            push_lr(self._scheduled_opts())
         rec["graphs"][0].replay()
         if len(rec["graphs"]) == 2:
             self.bucket.all_reduce_grads(rec["grads"])
@@ -547,6 +711,7 @@ class JointTrainer:
     # ------------------------------------------------------------------ one optimisation step (:645-766)
     def step(self, x_t, y_t, x_s, y_s, epoch: int = 0, t_samples=(None, None)):
         """Eager step.  ``t_samples``: the two CPC start indices (drawn like the reference if None)."""
+        self._set_epoch(epoch)
         ratios = self.m["noise"].advance(x_t.size(0), x_s.size(0))
         return self._step_body(x_t, y_t, x_s, y_s, epoch, t_samples, ratios)
 
@@ -578,7 +743,8 @@ class JointTrainer:
             L, aux = self.forward_losses(x_t, y_t, x_s, y_s, t_samples, noise_ratios)
             lt = torch.stack([L["nf_t"], L["ce_t"]])
             ls = torch.stack([L["nf_s"], L["ce_s"], L["ce_s2t2s"]])
-            a, b, c, d = loss_coefficients(epoch)
+            # device_hparams: 0-dim views of the coefficient tensor (_set_epoch wrote the epoch's values) — same fp32 products
+            a, b, c, d = loss_coefficients(epoch) if self._coef is None else self._coef.unbind(0)
             # Q3: first backward + second backward (weights zeroed) == Σ wᵢ∇Lᵢ + 2·(a∇cdan + b∇fd + c∇sl_t + d∇sl_s)
             total = torch.sum(self.w_t.detach() * lt) + torch.sum(self.w_s.detach() * ls) \
                 + 2.0 * (a * L["cdan"] + b * L["fd_s"] + c * L["sl_t"] + d * L["sl_s"])
@@ -672,7 +838,11 @@ class JointTrainer:
         hipGraphs.  Per-step inputs live in static device buffers that ``replay`` refreshes: the batch, the two CPC
         start indices and NoiseTransfer's two accumulation ratios.  The GRL coefficients are Python floats baked in
         at capture, so the warm-up runs until their call counters saturate (20 calls = 10 steps — quirk Q7); the
-        epoch-dependent loss coefficients are baked too: re-capture when ``loss_coefficients(epoch)`` changes.
+        epoch-dependent loss coefficients and every learning rate are baked too: re-capture when ``loss_coefficients(epoch)``
+        or a ``group["lr"]`` changes — a scheduler attached to ``opts[k]`` does NOT reach a replayed step.  After
+        ``enable_device_hparams()`` both live on the device instead: every ``replay`` runs at the optimisers' current
+        ``group["lr"]`` and ``replay(..., epoch=)`` at that epoch's coefficients, with no re-capture (the GRL coefficients and the
+        GradNorm-weight Adams' rates stay baked).
         Single GPU: one graph.  Data parallel: three graphs (A1 forward + backward, A2 GradNorm's partial passes, B update)
         with the eager RCCL collectives between them, the gradient all-reduce overlapping A2 on a side stream."""
         if self.sync == "global" and self.bucket is not None and self.bucket.world > 1:
@@ -681,6 +851,7 @@ class JointTrainer:
         self._g_in = {"x_t": x_t.clone(), "y_t": y_t.clone(), "x_s": x_s.clone(), "y_s": y_s.clone(),
                       "t": torch.zeros(2, dtype=torch.int32, device=dev), "r": torch.ones(2, device=dev)}
         self._g_epoch = epoch
+        self._set_epoch(epoch)
         T_half = max(1, (self.cfg.L_t // 2) // 2)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -731,8 +902,19 @@ class JointTrainer:
         gi["t"].copy_(dev[:2])
         gi["r"].copy_(dev[2:])
 
-    def replay(self, x_t, y_t, x_s, y_s, t_samples):
-        """One step through the captured graph(s); returns the (static) report tensors."""
+    def replay(self, x_t, y_t, x_s, y_s, t_samples, epoch: Optional[int] = None):
+        """One step through the captured graph(s); returns the (static) report tensors.  With ``device_hparams`` the step runs at
+        the optimisers' current ``group["lr"]`` and, when ``epoch`` is given, at ``loss_coefficients(epoch)``; without it, at the
+        captured values, and an ``epoch`` other than the captured one raises."""
+        if self._graphs is None:
+            raise RuntimeError("call capture() first")
+        if self.device_hparams:
+            if epoch is not None:
+                self._set_epoch(epoch)
+            push_lr(self._scheduled_opts())
+        elif epoch is not None and epoch != self._g_epoch:
+            raise ValueError(f"replay(epoch={epoch}): the graph was captured at epoch {self._g_epoch} and its loss coefficients "
+                             "are baked in; re-capture, or enable_device_hparams() before capturing")
         self._replay_inputs(x_t, y_t, x_s, y_s, t_samples)
         self._graphs[0].replay()
         if len(self._graphs) == 3:

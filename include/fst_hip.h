@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FST_ABI_VERSION 15
+#define FST_ABI_VERSION 16
 
 int fst_version(void);
 const char* fst_last_error(void);
@@ -521,12 +521,21 @@ int fst_lstm2_bwd(const float* w_hh, const float* save, const float* dh2, float*
  * up to 64 tensors ride in one launch's kernel arguments (so a captured hipGraph replays them as they are).  Same update
  * formulas and operation order as torch (RMSprop: centered = False, momentum = 0; Adam: the capturable branch with ONE shared
  * device step counter, already incremented by the caller).
+ * The *_dev entry points compute the same updates (one update body, bit-identical results for equal fp32 rates) with the learning
+ * rates on the DEVICE, read when the kernel runs and not when it is launched: lr_dev_host is a HOST array of n_tensors device
+ * addresses of fp32 scalars (tensors may share one), lr_dev one device scalar beside step_dev.  A captured launch then follows
+ * what is written to those scalars between replays.
  * ------------------------------------------------------------------------------------------- */
 int fst_rmsprop_multi(float* const* p_host, const float* const* g_host, float* const* v_host, const int64_t* numel_host,
                       const float* lr_host, int n_tensors, float alpha, float eps, void* stream);
 int fst_adam_multi(float* const* p_host, const float* const* g_host, float* const* m_host, float* const* v_host,
                    const int64_t* numel_host, int n_tensors, const float* step_dev, float lr, float beta1, float beta2, float eps,
                    void* stream);
+int fst_rmsprop_multi_dev(float* const* p_host, const float* const* g_host, float* const* v_host, const int64_t* numel_host,
+                          const float* const* lr_dev_host, int n_tensors, float alpha, float eps, void* stream);
+int fst_adam_multi_dev(float* const* p_host, const float* const* g_host, float* const* m_host, float* const* v_host,
+                       const int64_t* numel_host, int n_tensors, const float* step_dev, const float* lr_dev, float beta1, float beta2,
+                       float eps, void* stream);
 
 #ifdef __cplusplus
 }
