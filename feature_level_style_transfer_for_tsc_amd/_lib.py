@@ -12,7 +12,7 @@ from typing import Optional
 
 import torch
 
-ABI_VERSION = 16
+ABI_VERSION = 17
 _LIB_NAME = "libfst_hip.so"
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FST_HIP_LIB", os.path.join(_HERE, _LIB_NAME))     # override: diagnostic builds only
@@ -71,6 +71,10 @@ _SIGNATURES = {
     "fst_wn_wgrad_in": (c_int, [_P, _P, _P, c_int, c_int64, _P, _P, _P, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int64,
                                 c_void_p]),
     "fst_wn_wgrad_rs": (c_int, [_P, _P, _P, c_int, _P, _P, c_int64, c_int, c_int, c_int, c_int, c_int64, c_void_p]),
+    "fst_wn_wgrad_in_slabs": (c_int, [_P, _P, _P, c_int, c_int64, _P, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int64,
+                                      c_void_p]),
+    "fst_wn_wgrad_rs_slabs": (c_int, [_P, _P, _P, c_int, _P, c_int64, c_int, c_int, c_int, c_int, c_int64, c_void_p]),
+    "fst_wn_wgrad_reduce_many": (c_int, [_I32P, _I32P, _I32P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "fst_nt_gemm_workspace_floats": (c_int64, [c_int, c_int, c_int]),
     "fst_nt_gemm": (c_int, [_P, _P, _P, _P, c_int64, c_int, c_int, c_int, _P, _P, c_int, c_float, _P, c_void_p]),
     "fst_tap_wgrad_ok": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
@@ -96,13 +100,16 @@ _SIGNATURES = {
     "fst_logdet_inv": (c_int, [_P, c_int, _P, _P, c_void_p]),
     "fst_wn_image_bytes": (c_int64, [c_int, c_int]),
     "fst_wn_pack": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, c_int64, c_void_p]),
+    "fst_wn_pack_stack": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, c_int64, c_void_p]),
     "fst_wn_layer_fwd": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int,
                                  c_int, c_int64, c_void_p]),
     "fst_wn_bwd_image_bytes": (c_int64, [c_int, c_int]),
     "fst_wn_pack_bwd": (c_int, [_P, c_int, c_int, c_int, _P, c_int64, c_void_p]),
+    "fst_wn_pack_bwd_stack": (c_int, [_P, c_int, c_int, c_int, _P, c_int64, c_void_p]),
     "fst_wn_layer_bwd": (c_int, [_P, _P, _P, _P, c_int64, _P, _P, c_int64, c_int, c_int, c_int, c_int, c_int64, c_void_p]),
     "fst_wn_dgrad_image_bytes": (c_int64, [c_int]),
     "fst_wn_pack_dgrad": (c_int, [_P, _P, c_int, c_int, c_int, _P, c_int64, c_void_p]),
+    "fst_wn_pack_dgrad_stack": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P, c_int64, c_void_p]),
     "fst_wn_dgrad_fits": (c_int, [c_int, c_int, c_int]),
     "fst_wn_layer_dgrad": (c_int, [_P, _P, c_int64, _P, _P, _P, _P, c_int64, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64,
                                    c_void_p]),

@@ -79,8 +79,9 @@ struct WnPackParams {
   uint4* img;
 };
 
-__global__ __launch_bounds__(64) void wn_pack_kernel(WnPackParams p) {
-  const int lane = threadIdx.x, blk = blockIdx.x & 7, st = blockIdx.x >> 3;
+// workgroup bx of one layer's pack (64 lanes): row block bx & 7 of stage bx >> 3
+__device__ __forceinline__ void wn_pack_body(const WnPackParams& p, int bx) {
+  const int lane = threadIdx.x, blk = bx & 7, st = bx >> 3;
   const int S1 = 3 * p.CH + p.CH2, n = p.n, h = p.h;
   const int hh = lane >> 5, rowb = (blk & 3) * 32 + (lane & 31);
   const bool row_ok = rowb < n;
@@ -126,10 +127,32 @@ __global__ __launch_bounds__(64) void wn_pack_kernel(WnPackParams p) {
   uint4* dst = p.img + ((long long)st * 8 + blk) * 128 + lane;
   dst[0] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
   dst[64] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
-  if (blockIdx.x == 0 && lane < 2) {
+  if (bx == 0 && lane < 2) {
     const unsigned one = lane ? 0x3f800000u : 0u;
     p.img[(long long)(S1 + 8) * 8 * 128 + lane] = make_uint4(one, one, one, one);
   }
+}
+
+__global__ __launch_bounds__(64) void wn_pack_kernel(WnPackParams p) { wn_pack_body(p, blockIdx.x); }
+
+// Every layer of a WN stack in one launch: layer blockIdx.y of tables in the kernel arguments, the per-layer body unchanged
+// (the images are the per-layer launches' byte for byte).  The top layer (nl - 1) is the `last` one.
+struct WnPackStackParams {
+  const float* in_w[WS_MAXL];
+  const float* cond_w[WS_MAXL];
+  const float* in_b[WS_MAXL];
+  const float* cond_b[WS_MAXL];
+  const float* rs_w[WS_MAXL];
+  const float* rs_b[WS_MAXL];
+  uint4* img[WS_MAXL];
+  int n, h, nl, CH, CH2;
+};
+
+__global__ __launch_bounds__(64) void wn_pack_stack_kernel(WnPackStackParams s) {
+  const int i = blockIdx.y;
+  const WnPackParams p = {s.in_w[i], s.cond_w[i], s.in_b[i], s.cond_b[i], s.rs_w[i], s.rs_b[i], s.n, s.h, i == s.nl - 1 ? 1 : 0,
+                          s.CH, s.CH2, s.img[i]};
+  wn_pack_body(p, blockIdx.x);
 }
 
 static inline int wn_ch(int n) { return (n + 15) / 16; }
@@ -152,6 +175,29 @@ extern "C" int fst_wn_pack(const float* in_w, const float* cond_w, const float* 
   WnPackParams p = {in_w, cond_w, in_b, cond_b, rs_w, rs_b, n, h, last ? 1 : 0, wn_ch(n), wn_ch2(h), static_cast<uint4*>(image)};
   const int stages = 3 * p.CH + p.CH2 + 8;
   hipLaunchKernelGGL(wn_pack_kernel, dim3((unsigned)(stages * 8)), dim3(64), 0, (hipStream_t)stream, p);
+  FST_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fst_wn_pack_stack(const float* const* in_w, const float* const* cond_w, const float* const* in_b,
+                                 const float* const* cond_b, const float* const* rs_w, const float* const* rs_b, int nl, int n, int h,
+                                 int ntaps, void* const* images, int64_t image_bytes, void* stream) {
+  FST_REQUIRE(in_w && cond_w && in_b && cond_b && rs_w && rs_b && images, "fst_wn_pack_stack: null table");
+  FST_REQUIRE(nl >= 1 && nl <= WS_MAXL, "fst_wn_pack_stack: %d layers (1..%d)", nl, WS_MAXL);
+  FST_REQUIRE(ntaps == 3, "fst_wn_pack_stack: the fused WN kernels are 3-tap (in_w [2n][n][3]); got %d taps", ntaps);
+  FST_REQUIRE(n > 0 && n < 128 && h > 0, "fst_wn_pack_stack: needs 0 < n < 128 (one spare K row carries the bias), h > 0; n=%d h=%d", n, h);
+  FST_REQUIRE(image_bytes == fst_wn_image_bytes(n, h), "fst_wn_pack_stack: images are %lld bytes, expected %lld",
+              (long long)image_bytes, (long long)fst_wn_image_bytes(n, h));
+  WnPackStackParams s = {};
+  for (int i = 0; i < nl; ++i) {
+    FST_REQUIRE(in_w[i] && cond_w[i] && in_b[i] && cond_b[i] && rs_w[i] && rs_b[i] && images[i], "fst_wn_pack_stack: null operand in layer %d", i);
+    FST_REQUIRE(fst_aligned16(images[i]), "fst_wn_pack_stack: images must be 16-byte aligned");
+    s.in_w[i] = in_w[i]; s.cond_w[i] = cond_w[i]; s.in_b[i] = in_b[i]; s.cond_b[i] = cond_b[i]; s.rs_w[i] = rs_w[i]; s.rs_b[i] = rs_b[i];
+    s.img[i] = static_cast<uint4*>(images[i]);
+  }
+  s.n = n; s.h = h; s.nl = nl; s.CH = wn_ch(n); s.CH2 = wn_ch2(h);
+  const int stages = 3 * s.CH + s.CH2 + 8;
+  hipLaunchKernelGGL(wn_pack_stack_kernel, dim3((unsigned)(stages * 8), (unsigned)nl), dim3(64), 0, (hipStream_t)stream, s);
   FST_LAUNCH_CHECK();
   return 0;
 }
@@ -777,8 +823,9 @@ struct WnPackBwdParams {
   int acc_order;       // the d_a stages in the k-order in which a 32x32 accumulator tile delivers its rows as a B operand
 };
 
-__global__ __launch_bounds__(64) void wn_pack_bwd_kernel(WnPackBwdParams p) {
-  const int lane = threadIdx.x, blk = blockIdx.x & 3, st = blockIdx.x >> 2;
+// workgroup bx of the n_blocks = 4·S3 of one layer's pack
+__device__ __forceinline__ void wn_pack_bwd_body(const WnPackBwdParams& p, int bx, int n_blocks) {
+  const int lane = threadIdx.x, blk = bx & 3, st = bx >> 2;
   const int n = p.n, hh = lane >> 5, m = blk * 32 + (lane & 31);
   const int src = p.last ? 0 : st / p.CH, c = st - src * p.CH;
   float v[8];
@@ -796,7 +843,23 @@ __global__ __launch_bounds__(64) void wn_pack_bwd_kernel(WnPackBwdParams p) {
   uint4* dst = p.img + ((long long)st * 4 + blk) * 128 + lane;
   dst[0] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
   dst[64] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
-  if (blockIdx.x == 0 && lane == 0) p.img[(long long)gridDim.x * 128] = make_uint4(0u, 0u, 0u, 0u);
+  if (bx == 0 && lane == 0) p.img[(long long)n_blocks * 128] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+__global__ __launch_bounds__(64) void wn_pack_bwd_kernel(WnPackBwdParams p) { wn_pack_bwd_body(p, blockIdx.x, gridDim.x); }
+
+// every layer of a stack, layer blockIdx.y (the top layer is the `last` one: half the stages, its other workgroups leave)
+struct WnPackBwdStackParams {
+  const float* rs_w[WS_MAXL];
+  uint4* img[WS_MAXL];
+  int n, nl, CH, acc_order;
+};
+
+__global__ __launch_bounds__(64) void wn_pack_bwd_stack_kernel(WnPackBwdStackParams s) {
+  const int i = blockIdx.y, last = i == s.nl - 1 ? 1 : 0, n_blocks = (last ? 1 : 2) * s.CH * 4;
+  if ((int)blockIdx.x >= n_blocks) return;
+  const WnPackBwdParams p = {s.rs_w[i], s.n, last, s.CH, s.img[i], s.acc_order};
+  wn_pack_bwd_body(p, blockIdx.x, n_blocks);
 }
 
 extern "C" int64_t fst_wn_bwd_image_bytes(int n, int last) {
@@ -812,6 +875,27 @@ extern "C" int fst_wn_pack_bwd(const float* rs_w, int n, int last, int acc_order
   WnPackBwdParams p = {rs_w, n, last ? 1 : 0, wn_ch(n), static_cast<uint4*>(image), acc_order ? 1 : 0};
   const int stages = (last ? 1 : 2) * p.CH;
   hipLaunchKernelGGL(wn_pack_bwd_kernel, dim3((unsigned)(stages * 4)), dim3(64), 0, (hipStream_t)stream, p);
+  FST_LAUNCH_CHECK();
+  return 0;
+}
+
+// images[i] of fst_wn_bwd_image_bytes(n, i == nl - 1) bytes: image_bytes is that of the layers below the top one
+extern "C" int fst_wn_pack_bwd_stack(const float* const* rs_w, int nl, int n, int acc_order, void* const* images, int64_t image_bytes,
+                                     void* stream) {
+  FST_REQUIRE(rs_w && images && n > 0 && n <= 128, "fst_wn_pack_bwd_stack: bad arguments (n=%d, needs n <= 128)", n);
+  FST_REQUIRE(nl >= 1 && nl <= WS_MAXL, "fst_wn_pack_bwd_stack: %d layers (1..%d)", nl, WS_MAXL);
+  FST_REQUIRE(image_bytes == fst_wn_bwd_image_bytes(n, 0), "fst_wn_pack_bwd_stack: images are %lld bytes, expected %lld",
+              (long long)image_bytes, (long long)fst_wn_bwd_image_bytes(n, 0));
+  WnPackBwdStackParams s = {};
+  for (int i = 0; i < nl; ++i) {
+    FST_REQUIRE(rs_w[i] && images[i], "fst_wn_pack_bwd_stack: null operand in layer %d", i);
+    FST_REQUIRE(fst_aligned16(images[i]), "fst_wn_pack_bwd_stack: images must be 16-byte aligned");
+    s.rs_w[i] = rs_w[i];
+    s.img[i] = static_cast<uint4*>(images[i]);
+  }
+  s.n = n; s.nl = nl; s.CH = wn_ch(n); s.acc_order = acc_order ? 1 : 0;
+  const int stages = (nl > 1 ? 2 : 1) * s.CH;
+  hipLaunchKernelGGL(wn_pack_bwd_stack_kernel, dim3((unsigned)(stages * 4), (unsigned)nl), dim3(64), 0, (hipStream_t)stream, s);
   FST_LAUNCH_CHECK();
   return 0;
 }
@@ -1013,8 +1097,9 @@ struct WnPackDgradParams {
   uint4* img;
 };
 
-__global__ __launch_bounds__(64) void wn_pack_dgrad_kernel(WnPackDgradParams p) {
-  const int lane = threadIdx.x, ab = blockIdx.x % DG_A_BLOCKS, c = blockIdx.x / DG_A_BLOCKS;
+// workgroup bx of the n_blocks = 13·CHK of one layer's pack
+__device__ __forceinline__ void wn_pack_dgrad_body(const WnPackDgradParams& p, int bx, int n_blocks) {
+  const int lane = threadIdx.x, ab = bx % DG_A_BLOCKS, c = bx / DG_A_BLOCKS;
   const int n = p.n, h = p.h, hh = lane >> 5, l31 = lane & 31;
   // block ab of the chunk -> (tap, row block)
   int tap, blk;
@@ -1037,10 +1122,26 @@ __global__ __launch_bounds__(64) void wn_pack_dgrad_kernel(WnPackDgradParams p) 
   unsigned hi[4], lo[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) split_bf16_pair(v[2 * j], v[2 * j + 1], hi[j], lo[j]);
-  uint4* dst = p.img + (long long)blockIdx.x * 128 + lane;
+  uint4* dst = p.img + (long long)bx * 128 + lane;
   dst[0] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
   dst[64] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
-  if (blockIdx.x == 0 && lane == 0) p.img[(long long)gridDim.x * 128] = make_uint4(0u, 0u, 0u, 0u);
+  if (bx == 0 && lane == 0) p.img[(long long)n_blocks * 128] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+__global__ __launch_bounds__(64) void wn_pack_dgrad_kernel(WnPackDgradParams p) { wn_pack_dgrad_body(p, blockIdx.x, gridDim.x); }
+
+// every layer of a stack, layer blockIdx.y
+struct WnPackDgradStackParams {
+  const float* in_w[WS_MAXL];
+  const float* cond_w[WS_MAXL];
+  uint4* img[WS_MAXL];
+  int n, h, CHK;
+};
+
+__global__ __launch_bounds__(64) void wn_pack_dgrad_stack_kernel(WnPackDgradStackParams s) {
+  const int i = blockIdx.y;
+  const WnPackDgradParams p = {s.in_w[i], s.cond_w[i], s.n, s.h, s.CHK, s.img[i]};
+  wn_pack_dgrad_body(p, blockIdx.x, gridDim.x);
 }
 
 extern "C" int64_t fst_wn_dgrad_image_bytes(int n) {
@@ -1057,6 +1158,26 @@ extern "C" int fst_wn_pack_dgrad(const float* in_w, const float* cond_w, int n, 
   FST_REQUIRE(fst_aligned16(image), "fst_wn_pack_dgrad: image must be 16-byte aligned");
   WnPackDgradParams p = {in_w, cond_w, n, h, (2 * n + 15) / 16, static_cast<uint4*>(image)};
   hipLaunchKernelGGL(wn_pack_dgrad_kernel, dim3((unsigned)(p.CHK * DG_A_BLOCKS)), dim3(64), 0, (hipStream_t)stream, p);
+  FST_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fst_wn_pack_dgrad_stack(const float* const* in_w, const float* const* cond_w, int nl, int n, int h, int ntaps,
+                                       void* const* images, int64_t image_bytes, void* stream) {
+  FST_REQUIRE(in_w && cond_w && images && n > 0 && n <= 128 && h > 0 && h <= 32, "fst_wn_pack_dgrad_stack: needs n <= 128, h <= 32 (n=%d h=%d)", n, h);
+  FST_REQUIRE(nl >= 1 && nl <= WS_MAXL, "fst_wn_pack_dgrad_stack: %d layers (1..%d)", nl, WS_MAXL);
+  FST_REQUIRE(ntaps == 3, "fst_wn_pack_dgrad_stack: the fused WN kernels are 3-tap (in_w [2n][n][3]); got %d taps", ntaps);
+  FST_REQUIRE(image_bytes == fst_wn_dgrad_image_bytes(n), "fst_wn_pack_dgrad_stack: images are %lld bytes, expected %lld",
+              (long long)image_bytes, (long long)fst_wn_dgrad_image_bytes(n));
+  WnPackDgradStackParams s = {};
+  for (int i = 0; i < nl; ++i) {
+    FST_REQUIRE(in_w[i] && cond_w[i] && images[i], "fst_wn_pack_dgrad_stack: null operand in layer %d", i);
+    FST_REQUIRE(fst_aligned16(images[i]), "fst_wn_pack_dgrad_stack: images must be 16-byte aligned");
+    s.in_w[i] = in_w[i]; s.cond_w[i] = cond_w[i];
+    s.img[i] = static_cast<uint4*>(images[i]);
+  }
+  s.n = n; s.h = h; s.CHK = (2 * n + 15) / 16;
+  hipLaunchKernelGGL(wn_pack_dgrad_stack_kernel, dim3((unsigned)(s.CHK * DG_A_BLOCKS), (unsigned)nl), dim3(64), 0, (hipStream_t)stream, s);
   FST_LAUNCH_CHECK();
   return 0;
 }

@@ -508,6 +508,96 @@ __global__ __launch_bounds__(256) void wn_wgrad_reduce_kernel(WwParams p) {
   }
 }
 
+// The reductions of up to WW_MAX_RED slab sets (the in_layer and res_skip gradients of every layer of one WN) in ONE launch:
+// entry blockIdx.z of a table passed by value (a captured graph replays it as it is).  An entry holds what the reduction above
+// reads of WwParams.  Every output element is the same sum in the same order as there — per slab group sg the slabs sg, sg+4, ..
+// in turn, then groups 0..3, the leftover k-row slab after slab — so the result has the same bits; what differs is who adds:
+// the 16-byte column quads of ALL rows of an entry are dealt over the workgroups back to back (a slab's [M][Kcols] block is
+// contiguous: a wave reads 1 KiB runs), so no thread of a column block idles behind Kcols = 384 or 128, and the leftover
+// k-row's M sums get workgroups of their own behind the quads'.
+#define WW_MAX_RED 16
+struct WwRedSeg { int rows, out, out_off, out_sc, out_sm; };
+struct WwRedEntry {
+  const float* slab;        // [ksplit][256][Kcols]
+  const float* slab_extra;  // [ksplit][256][2]
+  float* w[2];
+  int ksplit, Kcols, K_main, K, n_extra, M, n_x;
+  int quad_blocks;          // workgroups of 64 column quads: ⌈M·Kcols/4 / 64⌉; the leftover sums follow, 256 per workgroup
+  WwRedSeg x[4];
+};
+struct WwRedParams { WwRedEntry e[WW_MAX_RED]; };
+
+__device__ __forceinline__ void ww_scatter_entry(const WwRedEntry& e, int m, int kk, float v) {
+  int si = 0, c = kk;
+#pragma unroll
+  for (int j = 0; j < 3; ++j)
+    if (si + 1 < e.n_x && c >= e.x[si].rows) { c -= e.x[si].rows; ++si; }
+  int out = e.x[0].out, off = e.x[0].out_off, sc = e.x[0].out_sc, sm = e.x[0].out_sm;
+  if (si == 1) { out = e.x[1].out; off = e.x[1].out_off; sc = e.x[1].out_sc; sm = e.x[1].out_sm; }
+  if (si == 2) { out = e.x[2].out; off = e.x[2].out_off; sc = e.x[2].out_sc; sm = e.x[2].out_sm; }
+  if (si == 3) { out = e.x[3].out; off = e.x[3].out_off; sc = e.x[3].out_sc; sm = e.x[3].out_sm; }
+  float* w = out == 0 ? e.w[0] : e.w[1];
+  w[(long long)m * sm + (long long)c * sc + off] = v;
+}
+
+__global__ __launch_bounds__(256) void wn_wgrad_reduce_many_kernel(WwRedParams p) {
+  __shared__ float4 part[4][64];
+  const WwRedEntry& e = p.e[blockIdx.z];
+  const int bx = blockIdx.x;
+  if (bx >= e.quad_blocks) {                               // (uniform) the leftover k-rows: one thread per (row, leftover row)
+    const int it = (bx - e.quad_blocks) * 256 + threadIdx.x;
+    if (e.K_main < e.K && it < e.M * e.n_extra) {
+      const int m = it / e.n_extra, j = it - m * e.n_extra;
+      const float* q = e.slab_extra + (long long)m * 2 + j;
+      float s = 0.f;
+      int sl = 0;
+      for (; sl + 8 <= e.ksplit; sl += 8) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) v[u] = q[(long long)(sl + u) * WW_MROWS * 2];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) s += v[u];
+      }
+      for (; sl < e.ksplit; ++sl) s += q[(long long)sl * WW_MROWS * 2];
+      ww_scatter_entry(e, m, e.K_main + j, s);
+    }
+    return;
+  }
+  const int cx = threadIdx.x & 63, sg = threadIdx.x >> 6;
+  const int qpr = e.Kcols >> 2;                            // quads per row (Kcols is a multiple of 128)
+  const int quad = bx * 64 + cx;
+  const bool live = quad < e.M * qpr;
+  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (live) {
+    const long long st = (long long)WW_MROWS * e.Kcols;
+    const float* q = e.slab + (long long)quad * 4;         // = row m·Kcols + column kk0 of slab 0
+    int sl = sg;
+    for (; sl + 28 < e.ksplit; sl += 32) {
+      float4 v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const float4*>(q + (sl + 4 * u) * st);
+#pragma unroll
+      for (int u = 0; u < 8; ++u) { s.x += v[u].x; s.y += v[u].y; s.z += v[u].z; s.w += v[u].w; }
+    }
+    for (; sl < e.ksplit; sl += 4) {
+      const float4 v = *reinterpret_cast<const float4*>(q + sl * st);
+      s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+    }
+  }
+  part[sg][cx] = s;
+  __syncthreads();
+  if (sg == 0 && live) {
+    float4 t = part[0][cx];
+#pragma unroll
+    for (int g2 = 1; g2 < 4; ++g2) { const float4 o = part[g2][cx]; t.x += o.x; t.y += o.y; t.z += o.z; t.w += o.w; }
+    const float tv[4] = {t.x, t.y, t.z, t.w};
+    const int m = quad / qpr, kk0 = (quad - m * qpr) * 4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (kk0 + j < e.K_main) ww_scatter_entry(e, m, kk0 + j, tv[j]);
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 
 // what the last launcher of this file or of wn_fused.hip launched on this host thread (fst_wn_last_route)
@@ -591,11 +681,30 @@ static int ww_launch(WwParams& p, int KT, void* stream, bool reduce = true) {
   return 0;
 }
 
-extern "C" int fst_wn_wgrad_in(const float* const* dg, const float* const* a, const float* const* u0, int n_sets, int64_t u0_bs,
-                               float* dw_in, float* dw_cond, float* workspace, int64_t workspace_floats, int B, int L, int n, int h,
-                               int dil, int a_slack, int64_t numel_a, void* stream) {
+// the segments of the two products (operand pointers left empty) — shared by the launchers and fst_wn_wgrad_reduce_many, which
+// reads the k-row segments' output mapping only
+static void ww_in_segments(WwParams& p, int n, int h, int L, int dil, long long u0_bs) {
+  p.n_dy = 1;
+  p.dy[0] = {{}, (long long)2 * n * L, 0, 2 * n, 0, 0, 0, 0, 0};
+  p.n_x = 4;
+  for (int tap = 0; tap < 3; ++tap) p.x[tap] = {{}, (long long)n * L, 0, n, (tap - 1) * dil, 0, tap, 3, 3 * n};
+  p.x[3] = {{}, u0_bs, 0, h, 0, 1, 0, 1, h};
+}
+
+static void ww_rs_segments(WwParams& p, int n, int L, int last) {
+  p.n_dy = last ? 1 : 2;
+  p.dy[0] = {{}, (long long)n * L, 0, n, 0, 0, 0, 0, 0};
+  p.dy[1] = {{}, (long long)n * L, 0, n, 0, 0, 0, 0, 0};
+  p.n_x = 1;
+  p.x[0] = {{}, (long long)2 * n * L, (long long)n * L, n, 0, 0, 0, 1, n};   // t rows; the s rows n·L floats further
+}
+
+// reduce = false (fst_wn_wgrad_in_slabs): the slabs stay in the workspace for fst_wn_wgrad_reduce_many, dw_in / dw_cond are not used
+static int ww_in(const float* const* dg, const float* const* a, const float* const* u0, int n_sets, int64_t u0_bs, float* dw_in,
+                 float* dw_cond, float* workspace, int64_t workspace_floats, int B, int L, int n, int h, int dil, int a_slack,
+                 int64_t numel_a, void* stream, bool reduce) {
   fst_wn_clear_route();
-  FST_REQUIRE(dg && a && u0 && dw_in && dw_cond && workspace, "fst_wn_wgrad_in: null operand");
+  FST_REQUIRE(dg && a && u0 && workspace && (!reduce || (dw_in && dw_cond)), "fst_wn_wgrad_in: null operand");
   FST_REQUIRE(n_sets >= 1 && n_sets <= WW_MAX_SETS, "fst_wn_wgrad_in: %d operand sets (1..%d)", n_sets, WW_MAX_SETS);
   const int served = fst_wn_wgrad_ok(0, B, L, n, h, dil);
   FST_REQUIRE(served == 1 || (served == 2 && a_slack), "fst_wn_wgrad_in: unsupported shape B=%d L=%d n=%d h=%d dil=%d (needs L %% 32 == 0, "
@@ -607,11 +716,7 @@ extern "C" int fst_wn_wgrad_in(const float* const* dg, const float* const* a, co
   const int KT = ww_geometry(0, B, L, n, h, 0, n_sets, &p);
   FST_REQUIRE(workspace_floats >= (int64_t)p.ksplit * WW_MROWS * (p.Kcols + 2), "fst_wn_wgrad_in: workspace of %lld floats is too small",
               (long long)workspace_floats);
-  p.n_dy = 1;
-  p.dy[0] = {{}, (long long)2 * n * L, 0, 2 * n, 0, 0, 0, 0, 0};
-  p.n_x = 4;
-  for (int tap = 0; tap < 3; ++tap) p.x[tap] = {{}, (long long)n * L, 0, n, (tap - 1) * dil, 0, tap, 3, 3 * n};
-  p.x[3] = {{}, (long long)u0_bs, 0, h, 0, 1, 0, 1, h};
+  ww_in_segments(p, n, h, L, dil, (long long)u0_bs);
   for (int s = 0; s < n_sets; ++s) {
     FST_REQUIRE(dg[s] && a[s] && u0[s], "fst_wn_wgrad_in: null operand in set %d", s);
     FST_REQUIRE(fst_aligned16(dg[s]) && fst_aligned16(a[s]) && fst_aligned16(u0[s]), "fst_wn_wgrad_in: operands must be 16-byte aligned");
@@ -623,14 +728,25 @@ extern "C" int fst_wn_wgrad_in(const float* const* dg, const float* const* a, co
   p.slab = workspace;
   p.slab_extra = workspace + (long long)p.ksplit * WW_MROWS * p.Kcols;
   p.w[0] = dw_in; p.w[1] = dw_cond;
-  return ww_launch(p, KT, stream);
+  return ww_launch(p, KT, stream, reduce);
 }
 
-extern "C" int fst_wn_wgrad_rs(const float* const* d_a, const float* const* d_out, const float* const* ts, int n_sets, float* dw_rs,
-                               float* workspace, int64_t workspace_floats, int last, int B, int L, int n, int64_t numel_a,
-                               void* stream) {
+extern "C" int fst_wn_wgrad_in(const float* const* dg, const float* const* a, const float* const* u0, int n_sets, int64_t u0_bs,
+                               float* dw_in, float* dw_cond, float* workspace, int64_t workspace_floats, int B, int L, int n, int h,
+                               int dil, int a_slack, int64_t numel_a, void* stream) {
+  return ww_in(dg, a, u0, n_sets, u0_bs, dw_in, dw_cond, workspace, workspace_floats, B, L, n, h, dil, a_slack, numel_a, stream, true);
+}
+
+extern "C" int fst_wn_wgrad_in_slabs(const float* const* dg, const float* const* a, const float* const* u0, int n_sets, int64_t u0_bs,
+                                     float* workspace, int64_t workspace_floats, int B, int L, int n, int h, int dil, int a_slack,
+                                     int64_t numel_a, void* stream) {
+  return ww_in(dg, a, u0, n_sets, u0_bs, nullptr, nullptr, workspace, workspace_floats, B, L, n, h, dil, a_slack, numel_a, stream, false);
+}
+
+static int ww_rs(const float* const* d_a, const float* const* d_out, const float* const* ts, int n_sets, float* dw_rs, float* workspace,
+                 int64_t workspace_floats, int last, int B, int L, int n, int64_t numel_a, void* stream, bool reduce) {
   fst_wn_clear_route();
-  FST_REQUIRE(d_out && ts && dw_rs && workspace && (last || d_a), "fst_wn_wgrad_rs: null operand");
+  FST_REQUIRE(d_out && ts && (dw_rs || !reduce) && workspace && (last || d_a), "fst_wn_wgrad_rs: null operand");
   FST_REQUIRE(n_sets >= 1 && n_sets <= WW_MAX_SETS, "fst_wn_wgrad_rs: %d operand sets (1..%d)", n_sets, WW_MAX_SETS);
   FST_REQUIRE(fst_wn_wgrad_ok(1, B, L, n, 0, 4), "fst_wn_wgrad_rs: unsupported shape B=%d L=%d n=%d (needs L %% 32 == 0, n < 128)", B, L, n);
   FST_REQUIRE((long long)B * n * L == (long long)numel_a, "fst_wn_wgrad_rs: B*n*L does not match the element count %lld", (long long)numel_a);
@@ -639,11 +755,7 @@ extern "C" int fst_wn_wgrad_rs(const float* const* d_a, const float* const* d_ou
   const int KT = ww_geometry(1, B, L, n, 0, last, n_sets, &p);
   FST_REQUIRE(workspace_floats >= (int64_t)p.ksplit * WW_MROWS * (p.Kcols + 2), "fst_wn_wgrad_rs: workspace of %lld floats is too small",
               (long long)workspace_floats);
-  p.n_dy = last ? 1 : 2;
-  p.dy[0] = {{}, (long long)n * L, 0, n, 0, 0, 0, 0, 0};
-  p.dy[1] = {{}, (long long)n * L, 0, n, 0, 0, 0, 0, 0};
-  p.n_x = 1;
-  p.x[0] = {{}, (long long)2 * n * L, (long long)n * L, n, 0, 0, 0, 1, n};   // t rows; the s rows n·L floats further
+  ww_rs_segments(p, n, L, last);
   for (int s = 0; s < n_sets; ++s) {
     FST_REQUIRE(d_out[s] && ts[s] && (last || d_a[s]), "fst_wn_wgrad_rs: null operand in set %d", s);
     FST_REQUIRE(fst_aligned16(d_out[s]) && fst_aligned16(ts[s]) && (last || fst_aligned16(d_a[s])), "fst_wn_wgrad_rs: operands must be 16-byte aligned");
@@ -654,7 +766,60 @@ extern "C" int fst_wn_wgrad_rs(const float* const* d_a, const float* const* d_ou
   p.slab = workspace;
   p.slab_extra = workspace + (long long)p.ksplit * WW_MROWS * p.Kcols;
   p.w[0] = dw_rs; p.w[1] = nullptr;
-  return ww_launch(p, KT, stream);
+  return ww_launch(p, KT, stream, reduce);
+}
+
+extern "C" int fst_wn_wgrad_rs(const float* const* d_a, const float* const* d_out, const float* const* ts, int n_sets, float* dw_rs,
+                               float* workspace, int64_t workspace_floats, int last, int B, int L, int n, int64_t numel_a,
+                               void* stream) {
+  return ww_rs(d_a, d_out, ts, n_sets, dw_rs, workspace, workspace_floats, last, B, L, n, numel_a, stream, true);
+}
+
+extern "C" int fst_wn_wgrad_rs_slabs(const float* const* d_a, const float* const* d_out, const float* const* ts, int n_sets,
+                                     float* workspace, int64_t workspace_floats, int last, int B, int L, int n, int64_t numel_a,
+                                     void* stream) {
+  return ww_rs(d_a, d_out, ts, n_sets, nullptr, workspace, workspace_floats, last, B, L, n, numel_a, stream, false);
+}
+
+// One launch adds the slab sets that up to 16 fst_wn_wgrad_in_slabs / _rs_slabs calls left in their workspaces (the layers of one
+// WN: they share B, L, n, h) and writes the gradients, bit for bit what fst_wn_wgrad_in / _rs write.  Entry j: kind[j], last[j]
+// (res_skip of the top layer), n_sets[j] as its product was launched with, its workspace, dw0[j] = dw_in | dw_rs, dw1[j] = dw_cond
+// (kind 0 only).  Everything is checked before the launch: a refused call writes nothing.
+extern "C" int fst_wn_wgrad_reduce_many(const int32_t* kind, const int32_t* last, const int32_t* n_sets, float* const* workspace,
+                                        const int64_t* workspace_floats, float* const* dw0, float* const* dw1, int n_entries, int B,
+                                        int L, int n, int h, void* stream) {
+  fst_wn_clear_route();
+  FST_REQUIRE(kind && last && n_sets && workspace && workspace_floats && dw0 && dw1, "fst_wn_wgrad_reduce_many: null table");
+  FST_REQUIRE(n_entries >= 1 && n_entries <= WW_MAX_RED, "fst_wn_wgrad_reduce_many: %d entries (1..%d)", n_entries, WW_MAX_RED);
+  WwRedParams rp = {};
+  unsigned gx = 1;
+  for (int j = 0; j < n_entries; ++j) {
+    FST_REQUIRE(kind[j] == 0 || kind[j] == 1, "fst_wn_wgrad_reduce_many: entry %d has kind %d (0 or 1)", j, (int)kind[j]);
+    FST_REQUIRE(fst_wn_wgrad_ok(kind[j], B, L, n, h, 4), "fst_wn_wgrad_reduce_many: unsupported shape B=%d L=%d n=%d h=%d", B, L, n, h);
+    FST_REQUIRE(n_sets[j] >= 1 && n_sets[j] <= WW_MAX_SETS, "fst_wn_wgrad_reduce_many: entry %d has %d operand sets (1..%d)", j,
+                (int)n_sets[j], WW_MAX_SETS);
+    FST_REQUIRE(workspace[j] && dw0[j] && (kind[j] == 1 || dw1[j]), "fst_wn_wgrad_reduce_many: null operand in entry %d", j);
+    FST_REQUIRE(fst_aligned16(workspace[j]), "fst_wn_wgrad_reduce_many: workspaces must be 16-byte aligned");
+    WwParams p = {};
+    const int lastj = kind[j] == 1 && last[j];
+    ww_geometry(kind[j], B, L, n, h, lastj, n_sets[j], &p);
+    FST_REQUIRE(workspace_floats[j] >= (int64_t)p.ksplit * WW_MROWS * (p.Kcols + 2),
+                "fst_wn_wgrad_reduce_many: workspace %d of %lld floats is too small", j, (long long)workspace_floats[j]);
+    if (kind[j] == 0) ww_in_segments(p, n, h, L, 4, 0);
+    else ww_rs_segments(p, n, L, lastj);
+    WwRedEntry& e = rp.e[j];
+    e.slab = workspace[j];
+    e.slab_extra = workspace[j] + (long long)p.ksplit * WW_MROWS * p.Kcols;
+    e.w[0] = dw0[j]; e.w[1] = kind[j] == 0 ? dw1[j] : nullptr;
+    e.ksplit = p.ksplit; e.Kcols = p.Kcols; e.K_main = p.K_main; e.K = p.K; e.n_extra = p.n_extra; e.M = p.M; e.n_x = p.n_x;
+    for (int i = 0; i < p.n_x; ++i) e.x[i] = {p.x[i].rows, p.x[i].out, p.x[i].out_off, p.x[i].out_sc, p.x[i].out_sm};
+    e.quad_blocks = (p.M * (p.Kcols / 4) + 63) / 64;
+    const unsigned blocks = (unsigned)e.quad_blocks + (unsigned)((p.K_main < p.K ? p.M * p.n_extra : 0) + 255) / 256;
+    if (blocks > gx) gx = blocks;
+  }
+  hipLaunchKernelGGL(wn_wgrad_reduce_many_kernel, dim3(gx, 1, (unsigned)n_entries), dim3(256), 0, (hipStream_t)stream, rp);
+  FST_LAUNCH_CHECK();
+  return 0;
 }
 
 // ------------------------------------------------------------------------------------------------ C = A·Bᵀ on the same kernel

@@ -1009,10 +1009,12 @@ def _sets(x) -> list:
     return list(x) if isinstance(x, (list, tuple)) else [x]
 
 
-def wn_wgrad_in(dg, a, u0, dw_in: Tensor, dw_cond: Tensor, n: int, h: int, dil: int) -> None:
+def wn_wgrad_in(dg, a, u0, dw_in: Tensor, dw_cond: Tensor, n: int, h: int, dil: int, slabs: Optional[list] = None) -> None:
     """dw_in [2n, n, 3] = Σ dg ⊗ a(t + (τ−1)·dil),  dw_cond [2n, h, 1] = Σ dg ⊗ u0 — written in place (fst_wn_wgrad_in).
     ``dg``, ``a``, ``u0``: one tensor each, or equally long lists of up to 3 same-shaped operand sets whose gradients are summed
-    by the one launch (the applications of a WN in a train step)."""
+    by the one launch (the applications of a WN in a train step).
+    ``slabs``: the product only (fst_wn_wgrad_in_slabs) — its slab set is appended to the list, and the targets are written when
+    ``wn_wgrad_reduce_many`` is called on it."""
     lib = _lib.load()
     dgs, as_, u0s = _sets(dg), _sets(a), _sets(u0)
     if not (1 <= len(dgs) <= WN_WGRAD_MAX_SETS and len(as_) == len(dgs) and len(u0s) == len(dgs)):
@@ -1034,15 +1036,20 @@ def wn_wgrad_in(dg, a, u0, dw_in: Tensor, dw_cond: Tensor, n: int, h: int, dil: 
     ws = torch.empty(ws_n, device=dgs[0].device, dtype=torch.float32)
     ns = len(dgs)
     t0 = KERNEL_TIMER.begin() if KERNEL_TIMER is not None else None
-    check(lib.fst_wn_wgrad_in(_ptr_sets(dgs), _ptr_sets(as_), _ptr_sets(u0s), ns, u0_bs, ptr(dw_in), ptr(dw_cond), ptr(ws), ws_n, B, L,
-                              n, h, dil, int(slack), numel, stream_ptr()), "fst_wn_wgrad_in")
+    if slabs is not None:
+        check(lib.fst_wn_wgrad_in_slabs(_ptr_sets(dgs), _ptr_sets(as_), _ptr_sets(u0s), ns, u0_bs, ptr(ws), ws_n, B, L, n, h, dil,
+                                        int(slack), numel, stream_ptr()), "fst_wn_wgrad_in_slabs")
+        slabs.append((0, False, ns, ws, dw_in, dw_cond))
+    else:
+        check(lib.fst_wn_wgrad_in(_ptr_sets(dgs), _ptr_sets(as_), _ptr_sets(u0s), ns, u0_bs, ptr(dw_in), ptr(dw_cond), ptr(ws), ws_n,
+                                  B, L, n, h, dil, int(slack), numel, stream_ptr()), "fst_wn_wgrad_in")
     if t0 is not None:
         KERNEL_TIMER.end("wn_wgrad_kernel<2, 3> bf3", t0, 2.0 * ns * B * L * 2 * n * (3 * n + h), 4.0 * ns * B * L * (2 * n + n + h))
 
 
-def wn_wgrad_rs(d_a, d_out, ts, dw_rs: Tensor, last: bool, n: int) -> None:
+def wn_wgrad_rs(d_a, d_out, ts, dw_rs: Tensor, last: bool, n: int, slabs: Optional[list] = None) -> None:
     """dw_rs [2n | n, n, 1] = Σ [d_a ; d_out] ⊗ (t·s), acts = t·s re-formed from the saved gate halves ts [B, 2n, L] (fst_wn_wgrad_rs).
-    One tensor each or lists of up to 3 operand sets, as ``wn_wgrad_in``; ``d_a`` is None exactly on the last layer."""
+    One tensor each or lists of up to 3 operand sets, and ``slabs``, as ``wn_wgrad_in``; ``d_a`` is None exactly on the last layer."""
     lib = _lib.load()
     d_outs, tss = _sets(d_out), _sets(ts)
     d_as = [None] * len(d_outs) if d_a is None else _sets(d_a)
@@ -1060,10 +1067,33 @@ def wn_wgrad_rs(d_a, d_out, ts, dw_rs: Tensor, last: bool, n: int) -> None:
     ws = torch.empty(ws_n, device=d_outs[0].device, dtype=torch.float32)
     ns = len(d_outs)
     t0 = KERNEL_TIMER.begin() if KERNEL_TIMER is not None else None
-    check(lib.fst_wn_wgrad_rs(None if last else _ptr_sets(d_as), _ptr_sets(d_outs), _ptr_sets(tss), ns, ptr(dw_rs), ptr(ws), ws_n,
-                              int(last), B, L, n, numel, stream_ptr()), "fst_wn_wgrad_rs")
+    if slabs is not None:
+        check(lib.fst_wn_wgrad_rs_slabs(None if last else _ptr_sets(d_as), _ptr_sets(d_outs), _ptr_sets(tss), ns, ptr(ws), ws_n,
+                                        int(last), B, L, n, numel, stream_ptr()), "fst_wn_wgrad_rs_slabs")
+        slabs.append((1, bool(last), ns, ws, dw_rs, None))
+    else:
+        check(lib.fst_wn_wgrad_rs(None if last else _ptr_sets(d_as), _ptr_sets(d_outs), _ptr_sets(tss), ns, ptr(dw_rs), ptr(ws), ws_n,
+                                  int(last), B, L, n, numel, stream_ptr()), "fst_wn_wgrad_rs")
     if t0 is not None:
         KERNEL_TIMER.end("wn_wgrad_kernel<2, 2> bf3", t0, 2.0 * ns * B * L * M * n, 4.0 * ns * B * L * (M + 2 * n))
+
+
+WN_WGRAD_MAX_REDUCE = 16     # (WW_MAX_RED of csrc/wn_wgrad.hip)
+
+
+def wn_wgrad_reduce_many(slabs: list, B: int, L: int, n: int, h: int) -> None:
+    """Adds the slab sets that ``wn_wgrad_in`` / ``wn_wgrad_rs`` calls with ``slabs=`` left behind (the layers of ONE WN) and writes
+    their targets: one launch per 16 sets (fst_wn_wgrad_reduce_many), the bits of the calls without ``slabs``.  Empties the list."""
+    lib = _lib.load()
+    for c0 in range(0, len(slabs), WN_WGRAD_MAX_REDUCE):
+        chunk = slabs[c0: c0 + WN_WGRAD_MAX_REDUCE]
+        ne = len(chunk)
+        ints = lambda vals: (ctypes.c_int32 * ne)(*[int(v) for v in vals])
+        check(lib.fst_wn_wgrad_reduce_many(ints(e[0] for e in chunk), ints(e[1] for e in chunk), ints(e[2] for e in chunk),
+                                           _ptr_table([e[3] for e in chunk]), (ctypes.c_int64 * ne)(*[e[3].numel() for e in chunk]),
+                                           _ptr_table([e[4] for e in chunk]), _ptr_table([e[5] for e in chunk]), ne, B, L, n, h,
+                                           stream_ptr()), "fst_wn_wgrad_reduce_many")
+    del slabs[:]
 
 
 def dense_tap_wgrad(dy: Tensor, x: Tensor, dw: Tensor, M: int, C: int, K: int, pad_left: int) -> None:
@@ -1118,7 +1148,7 @@ class WNGradPool:
     """Weight-gradient operands of the applications of ONE WN whose weights go through ``WGradJoinFn``: every application's
     backward leaves (dg, a, u0) / (d_a, d_out, ts) of each layer here instead of launching its own weight-gradient kernels; the
     join node's backward — which autograd runs after ALL applications that take part in the pass — sums them with one launch per
-    layer and kind.  ``ctx.needs_input_grad`` is fixed at forward time, so an application also defers in a pass that asks for a data
+    layer and kind, and adds the slabs of all of them with one more.  ``ctx.needs_input_grad`` is fixed at forward time, so an application also defers in a pass that asks for a data
     gradient only and never reaches the join (``autograd.grad(loss, [x])`` outside ``partial_backward()``): the pool therefore
     remembers which backward pass (autograd graph task) its operands belong to, and operands of any other pass are dropped — by the
     next pass's first ``add`` and by the join — never summed into a later pass's gradient."""
@@ -1159,6 +1189,9 @@ class WGradJoinFn(torch.autograd.Function):
         nl, n, h = S.n_layers, S.n, S.h
         dw = S.unflatten(g)
         g_cond_w, g_in_w, g_rs_w = dw[2], dw[6: 6 + nl], dw[6 + 2 * nl: 6 + 3 * nl]
+        # the first chunk of every (kind, layer) leaves its slabs (workspaces of all of them live at once) for ONE reduction
+        # launch; chunks beyond WN_WGRAD_MAX_SETS reduce their own, into a temporary that is added to the segment afterwards
+        slabs, later, BL = [], [], None
         for (kind, i), sets in pending.items():
             for c0 in range(0, len(sets), WN_WGRAD_MAX_SETS):
                 chunk = sets[c0: c0 + WN_WGRAD_MAX_SETS]
@@ -1167,16 +1200,21 @@ class WGradJoinFn(torch.autograd.Function):
                     t_in, t_cond = g_in_w[i], g_cond_w[2 * n * i: 2 * n * (i + 1)]
                     if c0:
                         t_in, t_cond = torch.empty_like(t_in), torch.empty_like(t_cond)
-                    wn_wgrad_in(cols[0], cols[1], cols[2], t_in, t_cond, n, h, 2 ** i)
-                    if c0:
-                        g_in_w[i].add_(t_in)
-                        g_cond_w[2 * n * i: 2 * n * (i + 1)].add_(t_cond)
+                        later += [(g_in_w[i], t_in), (g_cond_w[2 * n * i: 2 * n * (i + 1)], t_cond)]
+                    wn_wgrad_in(cols[0], cols[1], cols[2], t_in, t_cond, n, h, 2 ** i, slabs=None if c0 else slabs)
+                    BL = (cols[0][0].size(0), cols[0][0].size(2))
                 else:
                     last = i == nl - 1
-                    t_rs = torch.empty_like(g_rs_w[i]) if c0 else g_rs_w[i]
-                    wn_wgrad_rs(None if last else cols[0], cols[1], cols[2], t_rs, last, n)
+                    t_rs = g_rs_w[i]
                     if c0:
-                        g_rs_w[i].add_(t_rs)
+                        t_rs = torch.empty_like(t_rs)
+                        later.append((g_rs_w[i], t_rs))
+                    wn_wgrad_rs(None if last else cols[0], cols[1], cols[2], t_rs, last, n, slabs=None if c0 else slabs)
+                    BL = (cols[1][0].size(0), cols[1][0].size(2))
+        if slabs:
+            wn_wgrad_reduce_many(slabs, BL[0], BL[1], n, h)
+        for seg, t in later:
+            seg.add_(t)
         return None, None, g
 
 
@@ -1298,6 +1336,78 @@ def wn_pack_layer(in_w: Tensor, cond_w: Tensor, in_b: Tensor, cond_b: Tensor, rs
     if key is not None:
         _PACK_CACHE[key] = (img, in_w, cond_w, in_b, cond_b, rs_w, rs_b, src)
     return img
+
+
+WN_PACK_MAX_LAYERS = 10      # (WS_MAXL of csrc/wn_fused.hip)
+
+
+def _pack_stack(keys, nl: int, launch_one, launch_stack, keep):
+    """Images of the layers of a stack, each cached under its per-layer key: all layers in one launch (``launch_stack``) unless
+    some are cached already or the stack is deeper than the kernels' layer tables; ``keep(i, img)``: the cache entry (the image
+    first, then what must stay alive)."""
+    if _PACK_CACHE is not None:
+        hits = [_PACK_CACHE.get(k) for k in keys]
+        if all(hit is not None for hit in hits):
+            return [hit[0] for hit in hits]
+    if nl > WN_PACK_MAX_LAYERS or (_PACK_CACHE is not None and any(hit is not None for hit in hits)):
+        return [launch_one(i) for i in range(nl)]
+    imgs = launch_stack()
+    if _PACK_CACHE is not None:
+        for i, (k, img) in enumerate(zip(keys, imgs)):
+            _PACK_CACHE[k] = keep(i, img)
+    return imgs
+
+
+def wn_pack_layers(layers: Sequence[Sequence[Tensor]], n: int, h: int) -> List[Tensor]:
+    """``wn_pack_layer`` for every layer of a WN stack (``layers[i]`` = in_w, cond_w, in_b, cond_b, rs_w, rs_b; the top layer is the
+    last one) in one launch (fst_wn_pack_stack), cached per layer as the per-layer calls are."""
+    lib, nl = _lib.load(), len(layers)
+    for in_w in (l[0] for l in layers):
+        if in_w.dim() != 3 or in_w.size(0) != 2 * n or in_w.size(1) != n:
+            raise ValueError(f"wn_pack_layers: in_w must be [2n, n, taps], got {tuple(in_w.shape)} for n={n}")
+    keys = [("wn", n, h, i == nl - 1) + tuple((t.data_ptr(), t._version) for t in layers[i]) for i in range(nl)]
+    src = [[t.contiguous() for t in l] for l in layers]
+
+    def launch_stack():
+        nbytes = lib.fst_wn_image_bytes(n, h)
+        imgs = [torch.empty(nbytes // 4, device=src[0][0].device, dtype=torch.float32) for _ in range(nl)]
+        check(lib.fst_wn_pack_stack(*[_ptr_table([l[j] for l in src]) for j in range(6)], nl, n, h, layers[0][0].size(2),
+                                    _ptr_table(imgs), nbytes, stream_ptr()), "fst_wn_pack_stack")
+        return imgs
+    return _pack_stack(keys, nl, lambda i: wn_pack_layer(*layers[i], n, h, i == nl - 1), launch_stack,
+                       lambda i, img: (img, *layers[i], src[i]))
+
+
+def wn_pack_bwd_layers(rs_ws: Sequence[Tensor], n: int, acc_order: bool = False) -> List[Tensor]:
+    """``wn_pack_bwd`` for every layer of a stack in one launch (fst_wn_pack_bwd_stack)."""
+    lib, nl = _lib.load(), len(rs_ws)
+    keys = [("wn_bwd", n, i == nl - 1, acc_order, w.data_ptr(), w._version) for i, w in enumerate(rs_ws)]
+    src = [w.contiguous() for w in rs_ws]
+
+    def launch_stack():
+        imgs = [torch.empty(lib.fst_wn_bwd_image_bytes(n, int(i == nl - 1)) // 4, device=src[0].device, dtype=torch.float32)
+                for i in range(nl)]
+        check(lib.fst_wn_pack_bwd_stack(_ptr_table(src), nl, n, int(acc_order), _ptr_table(imgs), lib.fst_wn_bwd_image_bytes(n, 0),
+                                        stream_ptr()), "fst_wn_pack_bwd_stack")
+        return imgs
+    return _pack_stack(keys, nl, lambda i: wn_pack_bwd(rs_ws[i], n, i == nl - 1, acc_order), launch_stack,
+                       lambda i, img: (img, rs_ws[i], src[i]))
+
+
+def wn_pack_dgrad_layers(in_ws: Sequence[Tensor], cond_ws: Sequence[Tensor], n: int, h: int) -> List[Tensor]:
+    """``wn_pack_dgrad`` for every layer of a stack in one launch (fst_wn_pack_dgrad_stack)."""
+    lib, nl = _lib.load(), len(in_ws)
+    keys = [("wn_dgrad", n, h, a.data_ptr(), a._version, c.data_ptr(), c._version) for a, c in zip(in_ws, cond_ws)]
+    src = [(a.contiguous(), c.contiguous()) for a, c in zip(in_ws, cond_ws)]
+
+    def launch_stack():
+        nbytes = lib.fst_wn_dgrad_image_bytes(n)
+        imgs = [torch.empty(nbytes // 4, device=src[0][0].device, dtype=torch.float32) for _ in range(nl)]
+        check(lib.fst_wn_pack_dgrad_stack(_ptr_table([s_[0] for s_ in src]), _ptr_table([s_[1] for s_ in src]), nl, n, h,
+                                          in_ws[0].size(2), _ptr_table(imgs), nbytes, stream_ptr()), "fst_wn_pack_dgrad_stack")
+        return imgs
+    return _pack_stack(keys, nl, lambda i: wn_pack_dgrad(in_ws[i], cond_ws[i], n, h), launch_stack,
+                       lambda i, img: (img, in_ws[i], cond_ws[i], src[i]))
 
 
 def wn_layer_fwd(a: Tensor, u0: Tensor, img: Tensor, ts: Tensor, acts: Optional[Tensor], a_next: Optional[Tensor], out: Tensor,
@@ -1551,7 +1661,7 @@ def _wn_forward(specs: WNSpecs, u0: Tensor, flat: Tensor):
         # per layer: dilated conv + cond rows → gate in registers → res_skip → residual / skip adds; acts = t·s is not written
         # (the res_skip weight gradient re-forms it from the saved halves while staging)
         out = torch.empty(B, n, L, device=dev, dtype=torch.float32)
-        imgs = [wn_pack_layer(*_wn_layer(S, W, i), n, h, i == nl - 1) for i in range(nl)]
+        imgs = wn_pack_layers([_wn_layer(S, W, i) for i in range(nl)], n, h)
         a_list = [a] + [empty_with_slack(B, n, L, dev) for _ in range(nl - 1)]
         ts_list = [torch.empty(B, 2 * n, L, device=dev, dtype=torch.float32) for _ in range(nl)]
         if wn_stack_fwd_ok(n, h, L, nl, B):
@@ -1674,8 +1784,8 @@ def _wn_backward_stack(S: WNSpecs, W, G, a_list, ts_list, u0: Tensor, d_out: Ten
     Returns (the cotangent of layer 0's input, part_b, part_d)."""
     nl, n, h = S.n_layers, S.n, S.h
     B, _, L = d_out.shape
-    imgs_b = [wn_pack_bwd(_wn_layer(S, W, i)[4], n, i == nl - 1, acc_order=True) for i in range(nl)]
-    imgs_d = [wn_pack_dgrad(*_wn_layer(S, W, i)[:2], n, h) for i in range(nl)]
+    imgs_b = wn_pack_bwd_layers([_wn_layer(S, W, i)[4] for i in range(nl)], n, acc_order=True)
+    imgs_d = wn_pack_dgrad_layers([_wn_layer(S, W, i)[0] for i in range(nl)], [_wn_layer(S, W, i)[1] for i in range(nl)], n, h)
     new = lambda *shape: torch.empty(*shape, device=d_out.device, dtype=torch.float32)
     if G is None:
         dgs, da_out = [new(B, 2 * n, L)] * nl, [new(B, n, L)] + [None] * (nl - 1)    # only layer 0's d_a leaves the kernel

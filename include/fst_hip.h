@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FST_ABI_VERSION 16
+#define FST_ABI_VERSION 17
 
 int fst_version(void);
 const char* fst_last_error(void);
@@ -269,6 +269,17 @@ int fst_wn_pack(const float* in_w, const float* cond_w, const float* in_b, const
                 const float* rs_w, const float* rs_b, int n, int h, int ntaps /* of in_w; the fused kernels are 3-tap: anything
                 else is refused (Simplified_NF_WaveGlow.py:60 allows any kernel_size; the host side then takes the generic
                 conv-engine path) */, int last, void* image, int64_t image_bytes, void* stream);
+/* Every layer of a WN stack in ONE launch each (ABI v17): HOST tables of nl <= 10 per-layer pointers (copied into the kernel
+ * arguments), layer nl - 1 being the `last` one; images[i] receives byte for byte what the per-layer call writes.
+ * image_bytes: the size of one image (fst_wn_pack_bwd_stack: of a layer below the top one; the top layer's is
+ * fst_wn_bwd_image_bytes(n, 1)). */
+int fst_wn_pack_stack(const float* const* in_w, const float* const* cond_w, const float* const* in_b, const float* const* cond_b,
+                      const float* const* rs_w, const float* const* rs_b, int nl, int n, int h, int ntaps, void* const* images,
+                      int64_t image_bytes, void* stream);
+int fst_wn_pack_bwd_stack(const float* const* rs_w, int nl, int n, int acc_order, void* const* images, int64_t image_bytes,
+                          void* stream);
+int fst_wn_pack_dgrad_stack(const float* const* in_w, const float* const* cond_w, int nl, int n, int h, int ntaps,
+                            void* const* images, int64_t image_bytes, void* stream);
 int fst_wn_layer_fwd(const float* a, int64_t a_bs, const float* u0, int64_t u0_bs, const void* image, int64_t image_bytes,
                      float* ts, float* acts, float* a_next, float* out, int first, int last,
                      int B, int L, int n, int h, int dil, int64_t numel_a, void* stream);
@@ -356,6 +367,20 @@ int fst_wn_wgrad_in(const float* const* dg, const float* const* a, const float* 
 int fst_wn_wgrad_rs(const float* const* d_a /* NULL iff last */, const float* const* d_out, const float* const* ts, int n_sets,
                     float* dw_rs, float* workspace, int64_t workspace_floats, int last, int B, int L, int n, int64_t numel_a,
                     void* stream);
+/* The same products WITHOUT their reduction (ABI v17): the per-workgroup slabs stay in `workspace`, which must then live until
+ * fst_wn_wgrad_reduce_many has added them.  That call reduces the slab sets of 1..16 such calls — the layers of one WN, which
+ * share B, L, n, h — in one launch and writes the gradients with the bits fst_wn_wgrad_in / _rs write (every element adds its
+ * slabs in the same order).  HOST tables of n_entries values: kind[j] (0 | 1), last[j] (kind 1: the top layer), n_sets[j] (as the
+ * product was launched: the slab count depends on it), workspace[j] / workspace_floats[j], dw0[j] = dw_in | dw_rs,
+ * dw1[j] = dw_cond (kind 0; ignored for kind 1).  Every argument is checked before the launch: a refused call writes nothing. */
+int fst_wn_wgrad_in_slabs(const float* const* dg, const float* const* a, const float* const* u0, int n_sets, int64_t u0_bs,
+                          float* workspace, int64_t workspace_floats, int B, int L, int n, int h, int dil, int a_slack,
+                          int64_t numel_a, void* stream);
+int fst_wn_wgrad_rs_slabs(const float* const* d_a /* NULL iff last */, const float* const* d_out, const float* const* ts, int n_sets,
+                          float* workspace, int64_t workspace_floats, int last, int B, int L, int n, int64_t numel_a, void* stream);
+int fst_wn_wgrad_reduce_many(const int32_t* kind, const int32_t* last, const int32_t* n_sets, float* const* workspace,
+                             const int64_t* workspace_floats, float* const* dw0, float* const* dw1, int n_entries, int B, int L,
+                             int n, int h, void* stream);
 
 /* C[m][n] = Σ_k A[m][k]·Bm[n][k]  (A [M][K], Bm [N][K] row-major, the reduction index contiguous in both; M <= 256, K % 32 == 0) on the
  * time-as-k kernel above: RandomLayer's feature-side product x·R₀ (/root/reference/C_DAN.py:21; Bm = R₀ᵀ kept contiguous) and its data
