@@ -62,17 +62,29 @@ __global__ __launch_bounds__(256) void rmsprop_multi_dev_kernel(RmspropDevArgs a
   rmsprop_update(a.p[t], a.g[t], a.v[t], a.numel[t], a.lr[t][0], a.alpha, a.eps);
 }
 
+// Every (parameter, gradient, state...) tuple of a call is checked here BEFORE the first chunk is launched: a refused call has
+// updated nothing, whichever index the bad entry has.  m_host is NULL for RMSprop, lr_dev_host is NULL unless the rates are
+// per-tensor device addresses.
+static int optim_validate(const char* who, float* const* p_host, const float* const* g_host, float* const* m_host, float* const* v_host,
+                          const int64_t* numel_host, const float* const* lr_dev_host, int n_tensors) {
+  for (int i = 0; i < n_tensors; ++i) {
+    FST_REQUIRE(p_host[i] && g_host[i] && (!m_host || m_host[i]) && v_host[i] && numel_host[i] > 0 && numel_host[i] < (1LL << 31),
+                "%s: tensor %d: null pointer or bad element count", who, i);
+    FST_REQUIRE(!lr_dev_host || lr_dev_host[i], "%s: tensor %d: null learning-rate address", who, i);
+  }
+  return 0;
+}
+
 extern "C" int fst_rmsprop_multi(float* const* p_host, const float* const* g_host, float* const* v_host, const int64_t* numel_host,
                                  const float* lr_host, int n_tensors, float alpha, float eps, void* stream) {
   FST_REQUIRE(p_host && g_host && v_host && numel_host && lr_host && n_tensors >= 0, "fst_rmsprop_multi: bad arguments");
+  if (int rc = optim_validate("fst_rmsprop_multi", p_host, g_host, nullptr, v_host, numel_host, nullptr, n_tensors)) return rc;
   for (int base = 0; base < n_tensors; base += OPT_MAX_T) {
     RmspropArgs a;
     a.n = n_tensors - base < OPT_MAX_T ? n_tensors - base : OPT_MAX_T;
     a.alpha = alpha; a.eps = eps;
     long long most = 0;
     for (int i = 0; i < a.n; ++i) {
-      FST_REQUIRE(p_host[base + i] && g_host[base + i] && v_host[base + i] && numel_host[base + i] > 0 && numel_host[base + i] < (1LL << 31),
-                  "fst_rmsprop_multi: tensor %d: null pointer or bad element count", base + i);
       a.p[i] = p_host[base + i]; a.g[i] = g_host[base + i]; a.v[i] = v_host[base + i];
       a.numel[i] = (int)numel_host[base + i]; a.lr[i] = lr_host[base + i];
       most = most > numel_host[base + i] ? most : numel_host[base + i];
@@ -128,14 +140,13 @@ extern "C" int fst_adam_multi(float* const* p_host, const float* const* g_host, 
                               const int64_t* numel_host, int n_tensors, const float* step_dev, float lr, float beta1, float beta2,
                               float eps, void* stream) {
   FST_REQUIRE(p_host && g_host && m_host && v_host && numel_host && step_dev && n_tensors >= 0, "fst_adam_multi: bad arguments");
+  if (int rc = optim_validate("fst_adam_multi", p_host, g_host, m_host, v_host, numel_host, nullptr, n_tensors)) return rc;
   for (int base = 0; base < n_tensors; base += OPT_MAX_T) {
     AdamArgs a;
     a.n = n_tensors - base < OPT_MAX_T ? n_tensors - base : OPT_MAX_T;
     a.step = step_dev; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
     long long most = 0;
     for (int i = 0; i < a.n; ++i) {
-      FST_REQUIRE(p_host[base + i] && g_host[base + i] && m_host[base + i] && v_host[base + i] && numel_host[base + i] > 0 &&
-                  numel_host[base + i] < (1LL << 31), "fst_adam_multi: tensor %d: null pointer or bad element count", base + i);
       a.p[i] = p_host[base + i]; a.g[i] = g_host[base + i]; a.m[i] = m_host[base + i]; a.v[i] = v_host[base + i];
       a.numel[i] = (int)numel_host[base + i];
       most = most > numel_host[base + i] ? most : numel_host[base + i];
@@ -152,15 +163,13 @@ extern "C" int fst_adam_multi(float* const* p_host, const float* const* g_host, 
 extern "C" int fst_rmsprop_multi_dev(float* const* p_host, const float* const* g_host, float* const* v_host, const int64_t* numel_host,
                                      const float* const* lr_dev_host, int n_tensors, float alpha, float eps, void* stream) {
   FST_REQUIRE(p_host && g_host && v_host && numel_host && lr_dev_host && n_tensors >= 0, "fst_rmsprop_multi_dev: bad arguments");
+  if (int rc = optim_validate("fst_rmsprop_multi_dev", p_host, g_host, nullptr, v_host, numel_host, lr_dev_host, n_tensors)) return rc;
   for (int base = 0; base < n_tensors; base += OPT_MAX_T) {
     RmspropDevArgs a;
     a.n = n_tensors - base < OPT_MAX_T ? n_tensors - base : OPT_MAX_T;
     a.alpha = alpha; a.eps = eps;
     long long most = 0;
     for (int i = 0; i < a.n; ++i) {
-      FST_REQUIRE(p_host[base + i] && g_host[base + i] && v_host[base + i] && numel_host[base + i] > 0 && numel_host[base + i] < (1LL << 31),
-                  "fst_rmsprop_multi_dev: tensor %d: null pointer or bad element count", base + i);
-      FST_REQUIRE(lr_dev_host[base + i], "fst_rmsprop_multi_dev: tensor %d: null learning-rate address", base + i);
       a.p[i] = p_host[base + i]; a.g[i] = g_host[base + i]; a.v[i] = v_host[base + i];
       a.numel[i] = (int)numel_host[base + i]; a.lr[i] = lr_dev_host[base + i];
       most = most > numel_host[base + i] ? most : numel_host[base + i];
@@ -178,14 +187,13 @@ extern "C" int fst_adam_multi_dev(float* const* p_host, const float* const* g_ho
                                   float beta2, float eps, void* stream) {
   FST_REQUIRE(p_host && g_host && m_host && v_host && numel_host && step_dev && n_tensors >= 0, "fst_adam_multi_dev: bad arguments");
   FST_REQUIRE(lr_dev, "fst_adam_multi_dev: null learning-rate address");
+  if (int rc = optim_validate("fst_adam_multi_dev", p_host, g_host, m_host, v_host, numel_host, nullptr, n_tensors)) return rc;
   for (int base = 0; base < n_tensors; base += OPT_MAX_T) {
     AdamArgs a;
     a.n = n_tensors - base < OPT_MAX_T ? n_tensors - base : OPT_MAX_T;
     a.step = step_dev; a.lr = 0.0f; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
     long long most = 0;
     for (int i = 0; i < a.n; ++i) {
-      FST_REQUIRE(p_host[base + i] && g_host[base + i] && m_host[base + i] && v_host[base + i] && numel_host[base + i] > 0 &&
-                  numel_host[base + i] < (1LL << 31), "fst_adam_multi_dev: tensor %d: null pointer or bad element count", base + i);
       a.p[i] = p_host[base + i]; a.g[i] = g_host[base + i]; a.m[i] = m_host[base + i]; a.v[i] = v_host[base + i];
       a.numel[i] = (int)numel_host[base + i];
       most = most > numel_host[base + i] ? most : numel_host[base + i];

@@ -1046,7 +1046,9 @@ __global__ __launch_bounds__(256) void logdet_inv_kernel(const float* W, int n, 
   }
   for (int e = tid; e < n * n; e += 256) {
     const int i = e / n, j = e - i * n;
-    inv_t[e] = sign != 0 ? (float)sa[j * n + i] : __builtin_nanf("");
+    // (a zero is stored as +0: the bookkeeping above, -a * (1/pivot) and a * (1/pivot) with a negative pivot, leaves -0 where a = 0)
+    const double v = sa[j * n + i];
+    inv_t[e] = sign != 0 ? (v == 0.0 ? 0.f : (float)v) : __builtin_nanf("");
   }
   if (tid == 0) {
     out[0] = sign > 0 ? (float)s_logabs : (sign < 0 ? __builtin_nanf("") : -__builtin_inff());

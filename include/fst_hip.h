@@ -238,7 +238,11 @@ int fst_coupling_inv_bwd(const float* xn, const float* o, const float* dxn,
  *   { address of the row of v, address of the row's g scalar (0 = plain copy), element offset into flat, row length,
  *     element offset of the row's v gradient in dpar, element offset of its g gradient in dpar }
  * forward: flat[dst + j] = v[j]·g/‖v‖ (norms[r] = ‖v‖ kept for the backward);  backward: dv = (g/‖v‖)(dw − v (dw·v)/‖v‖²),
- * dg = (dw·v)/‖v‖ written into the gradient buffer dpar (the caller hands out its segments as the parameters' gradients). */
+ * dg = (dw·v)/‖v‖ written into the gradient buffer dpar (the caller hands out its segments as the parameters' gradients).
+ * ‖v‖² is summed in fp32.  Where it underflows to 0 or overflows to inf the forward gives what fp32 torch._weight_norm gives on
+ * the CPU (w = ±inf resp. ±0) and so does dg; dv is the formula above evaluated in fp32 as written — all ±inf for ‖v‖ = 0, where
+ * torch's autograd, which groups the same terms differently, gives NaN in some elements, and ±0 for ‖v‖ = inf as torch does.  A row
+ * needs |v| below 1e-19 or above 1e19 throughout to get there, and either result is already unusable: nothing to train on. */
 int fst_wn_fold_fwd(const int64_t* table_dev, int n_rows, float* flat, float* norms /* [n_rows] */, void* stream);
 int fst_wn_fold_bwd(const int64_t* table_dev, int n_rows, const float* d_flat, const float* norms, float* dpar, void* stream);
 
@@ -246,7 +250,8 @@ int fst_wn_fold_bwd(const int64_t* table_dev, int n_rows, const float* d_flat, c
  * d log|det W| / dW its backward needs, in ONE single-workgroup launch (in-place Gauss-Jordan with partial pivoting in double
  * precision in LDS) instead of an LU factorisation, two triangular solves and ~30 tiny launches.  out[0] = log|det W| with
  * torch.logdet's conventions (NaN for a negative determinant, -inf for a singular matrix), out[1] = sign(det);
- * inv_t [n][n] = (W^{-1})^T (NaN-filled when singular).  n <= 96. */
+ * inv_t [n][n] = (W^{-1})^T (NaN-filled when singular; a zero entry is always +0, so W^{-T} of a permutation matrix is that matrix
+ * bit for bit).  n <= 96. */
 int fst_logdet_inv(const float* W, int n, float* out /* [2] */, float* inv_t /* [n][n] */, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
@@ -546,6 +551,8 @@ int fst_lstm2_bwd(const float* w_hh, const float* save, const float* dh2, float*
  * up to 64 tensors ride in one launch's kernel arguments (so a captured hipGraph replays them as they are).  Same update
  * formulas and operation order as torch (RMSprop: centered = False, momentum = 0; Adam: the capturable branch with ONE shared
  * device step counter, already incremented by the caller).
+ * ALL n_tensors entries are validated (non-null pointers, 0 < element count < 2^31, non-null learning-rate address) on the host
+ * BEFORE the first launch: a call that returns < 0 has updated no parameter and no moment, whichever entry was bad.
  * The *_dev entry points compute the same updates (one update body, bit-identical results for equal fp32 rates) with the learning
  * rates on the DEVICE, read when the kernel runs and not when it is launched: lr_dev_host is a HOST array of n_tensors device
  * addresses of fp32 scalars (tensors may share one), lr_dev one device scalar beside step_dev.  A captured launch then follows
