@@ -1,0 +1,175 @@
+// Anomaly guard of the train step: decide ON THE DEVICE whether a step's update would consume a NaN or an inf, and make such a
+// step a no-op on the trainer's state — with no host read, so it works inside a replayed hipGraph (the reference's only
+// protection is torch.autograd.set_detect_anomaly, train_and_test.py:24, which cannot run under capture).
+//
+//   fst_nonfinite_multi    counts the non-finite elements of many fp32 tensors per GROUP (a tensor carries a group id < 32) and
+//                          writes three device words: verdict (1 if a group of the verdict mask counted anything), ok = 1 − verdict
+//                          as fp32, and a cumulative counter of skipped steps.
+//   fst_guard_copy_multi   a multi-tensor copy in 4-byte words that runs unconditionally (verdict == NULL: the SAVE of state that
+//                          cannot be guarded at its writer) or only when (*verdict != 0) == when (the ROLL-BACK).
+//   (the optimiser updates behind the verdict word are in optim.hip, beside the update bodies they share)
+//
+// House style of optim.hip: the pointer tuples ride BY VALUE in the kernel arguments, at most 64 per launch, so a captured launch
+// carries them; no float atomics and no zero fill: every workgroup of the scan writes its own slot with a plain store (and plain
+// zeros into the slots of its tensor that no workgroup of this launch owns), the finalising launch adds the slots.  The counts are
+// integers, so their sum does not depend on the order of the additions: the finaliser's LDS integer adds give the same words on
+// every run.  The scan only reads its inputs.
+#include "fst_common.h"
+
+#define NF_MAX_T 64                 // tensors per launch
+#define NF_SLOTS 64                 // workgroups (and slots) per tensor at most
+#define NF_REC (NF_SLOTS + 1)       // a tensor's record in the slot array: its group id, then its NF_SLOTS counts
+
+struct NonfiniteArgs {
+  const float* x[NF_MAX_T];
+  int numel[NF_MAX_T];
+  int group[NF_MAX_T];
+  int n, base;                      // tensors of this launch; index of its first tensor in the call (its record in the slot array)
+};
+static_assert(sizeof(NonfiniteArgs) + sizeof(int*) <= 4096, "kernel arguments: 4 KB at most");
+
+// NaN and ±inf are the values whose exponent bits are all ones; a test on the bits cannot be folded away by fast-math rules
+__device__ __forceinline__ int nonfinite_bits(uint32_t b) { return (b & 0x7f800000u) == 0x7f800000u; }
+
+// grid (bx, n): up to NF_SLOTS workgroups per tensor, grid-stride beyond.  16-byte loads over the aligned middle of the tensor;
+// the up to three elements in front of the first 16-byte boundary and the up to three after the last full quad go to workgroup 0.
+__global__ __launch_bounds__(256) void nonfinite_multi_kernel(NonfiniteArgs a, int* __restrict__ slots) {
+  const int t = blockIdx.y;
+  if (t >= a.n) return;
+  const uint32_t* __restrict__ x = (const uint32_t*)a.x[t];
+  const int n = a.numel[t];
+  int head = (int)(((16u - (unsigned)((uintptr_t)x & 15u)) & 15u) >> 2);
+  head = head < n ? head : n;
+  const int nv = (n - head) >> 2;
+  const int tail0 = head + 4 * nv;
+  const uint4* __restrict__ xv = (const uint4*)(x + head);
+  int c = 0;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < nv; i += gridDim.x * 256) {
+    const uint4 q = xv[i];
+    c += nonfinite_bits(q.x) + nonfinite_bits(q.y) + nonfinite_bits(q.z) + nonfinite_bits(q.w);
+  }
+  if (blockIdx.x == 0) {
+    if ((int)threadIdx.x < head) c += nonfinite_bits(x[threadIdx.x]);
+    if ((int)threadIdx.x < n - tail0) c += nonfinite_bits(x[tail0 + threadIdx.x]);
+  }
+  __shared__ int total;
+  if (threadIdx.x == 0) total = 0;
+  __syncthreads();
+  if (c) atomicAdd(&total, c);                                      // LDS, integer
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int* rec = slots + (size_t)(a.base + t) * NF_REC;
+    if (blockIdx.x == 0) rec[0] = a.group[t];
+    rec[1 + blockIdx.x] = total;
+    for (int s = blockIdx.x + gridDim.x; s < NF_SLOTS; s += gridDim.x) rec[1 + s] = 0;   // slots no workgroup of this launch owns
+  }
+}
+
+// one workgroup: counts[32] = per-group sums of every slot, then the three words (each may be NULL: not written)
+__global__ __launch_bounds__(256) void nonfinite_finalize_kernel(const int* __restrict__ slots, int n_tensors, unsigned verdict_mask,
+                                                                 int* __restrict__ counts, int* __restrict__ verdict,
+                                                                 float* __restrict__ ok, int* __restrict__ skipped) {
+  __shared__ int cnt[32];
+  if (threadIdx.x < 32) cnt[threadIdx.x] = 0;
+  __syncthreads();
+  for (int i = threadIdx.x; i < n_tensors * NF_SLOTS; i += 256) {
+    const int* rec = slots + (size_t)(i / NF_SLOTS) * NF_REC;
+    const int c = rec[1 + i % NF_SLOTS];
+    if (c) atomicAdd(&cnt[rec[0] & 31], c);                         // LDS, integer: the sum is the same in any order
+  }
+  __syncthreads();
+  if (threadIdx.x < 32) counts[threadIdx.x] = cnt[threadIdx.x];
+  if (threadIdx.x == 0) {
+    int any = 0;
+    for (int g = 0; g < 32; ++g) any |= ((verdict_mask >> g) & 1u) && cnt[g] > 0;
+    if (verdict) verdict[0] = any;
+    if (ok) ok[0] = 1.0f - (float)any;
+    if (skipped) skipped[0] += any;
+  }
+}
+
+extern "C" int64_t fst_nonfinite_slots(int n_tensors) { return n_tensors < 0 ? -1 : (int64_t)n_tensors * NF_REC; }
+
+extern "C" int fst_nonfinite_multi(const float* const* x_host, const int64_t* numel_host, const int32_t* group_host, int n_tensors,
+                                   int32_t verdict_mask, int32_t* slots_dev, int64_t slots_len, int32_t* counts_dev,
+                                   int32_t* verdict_dev, float* ok_dev, int32_t* skipped_dev, void* stream) {
+  FST_REQUIRE(n_tensors >= 0 && n_tensors < (1 << 24) && counts_dev && (n_tensors == 0 || (x_host && numel_host && group_host && slots_dev)),
+              "fst_nonfinite_multi: bad arguments");
+  FST_REQUIRE(slots_len >= fst_nonfinite_slots(n_tensors), "fst_nonfinite_multi: %lld slots, %lld needed", (long long)slots_len,
+              (long long)fst_nonfinite_slots(n_tensors));
+  for (int i = 0; i < n_tensors; ++i) {                              // all of them before the first launch
+    FST_REQUIRE(x_host[i] && ((uintptr_t)x_host[i] & 3) == 0 && numel_host[i] > 0 && numel_host[i] < (1LL << 31),
+                "fst_nonfinite_multi: tensor %d: null or misaligned pointer, or bad element count", i);
+    FST_REQUIRE(group_host[i] >= 0 && group_host[i] < 32, "fst_nonfinite_multi: tensor %d: group %d is not in 0..31", i, group_host[i]);
+  }
+  for (int base = 0; base < n_tensors; base += NF_MAX_T) {
+    NonfiniteArgs a;
+    a.n = n_tensors - base < NF_MAX_T ? n_tensors - base : NF_MAX_T;
+    a.base = base;
+    long long most = 0;
+    for (int i = 0; i < a.n; ++i) {
+      a.x[i] = x_host[base + i]; a.numel[i] = (int)numel_host[base + i]; a.group[i] = group_host[base + i];
+      most = most > numel_host[base + i] ? most : numel_host[base + i];
+    }
+    int bx = (int)((most + 1023) / 1024);                            // one 16-byte load per thread for the largest tensor ...
+    bx = bx < 1 ? 1 : (bx > NF_SLOTS ? NF_SLOTS : bx);               // ... within 64 workgroups per tensor (grid-stride beyond)
+    hipLaunchKernelGGL(nonfinite_multi_kernel, dim3((unsigned)bx, (unsigned)a.n), dim3(256), 0, (hipStream_t)stream, a, (int*)slots_dev);
+    FST_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(nonfinite_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const int*)slots_dev, n_tensors,
+                     (unsigned)verdict_mask, (int*)counts_dev, (int*)verdict_dev, ok_dev, (int*)skipped_dev);
+  FST_LAUNCH_CHECK();
+  return 0;
+}
+
+struct GuardCopyArgs {
+  uint32_t* dst[NF_MAX_T];
+  const uint32_t* src[NF_MAX_T];
+  int words[NF_MAX_T];
+  int n;
+};
+static_assert(sizeof(GuardCopyArgs) + sizeof(const int*) + sizeof(int) <= 4096, "kernel arguments: 4 KB at most");
+
+// verdict is read when the kernel runs, one uniform load per workgroup; a workgroup that is not to copy returns before its first
+// load.  16-byte moves where both pointers allow, 4-byte words otherwise.
+__global__ __launch_bounds__(256) void guard_copy_multi_kernel(GuardCopyArgs a, const int* __restrict__ verdict, int when) {
+  const int t = blockIdx.y;
+  if (t >= a.n) return;
+  if (verdict && (verdict[0] != 0) != (when != 0)) return;
+  uint32_t* __restrict__ d = a.dst[t];
+  const uint32_t* __restrict__ s = a.src[t];
+  const int n = a.words[t];
+  if ((((uintptr_t)d | (uintptr_t)s) & 15u) == 0) {
+    const int nv = n >> 2;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < nv; i += gridDim.x * 256) ((uint4*)d)[i] = ((const uint4*)s)[i];
+    if (blockIdx.x == 0 && (int)threadIdx.x < n - 4 * nv) d[4 * nv + threadIdx.x] = s[4 * nv + threadIdx.x];
+    return;
+  }
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) d[i] = s[i];
+}
+
+extern "C" int fst_guard_copy_multi(void* const* dst_host, const void* const* src_host, const int64_t* words_host, int n_tensors,
+                                    const int32_t* verdict_dev, int when, void* stream) {
+  FST_REQUIRE(n_tensors >= 0 && (n_tensors == 0 || (dst_host && src_host && words_host)) && (when == 0 || when == 1),
+              "fst_guard_copy_multi: bad arguments");
+  for (int i = 0; i < n_tensors; ++i) {                              // all of them before the first launch
+    FST_REQUIRE(dst_host[i] && src_host[i] && dst_host[i] != src_host[i] && (((uintptr_t)dst_host[i] | (uintptr_t)src_host[i]) & 3) == 0 &&
+                words_host[i] > 0 && words_host[i] < (1LL << 31),
+                "fst_guard_copy_multi: tensor %d: null, equal or misaligned pointers, or bad word count", i);
+  }
+  for (int base = 0; base < n_tensors; base += NF_MAX_T) {
+    GuardCopyArgs a;
+    a.n = n_tensors - base < NF_MAX_T ? n_tensors - base : NF_MAX_T;
+    long long most = 0;
+    for (int i = 0; i < a.n; ++i) {
+      a.dst[i] = (uint32_t*)dst_host[base + i]; a.src[i] = (const uint32_t*)src_host[base + i]; a.words[i] = (int)words_host[base + i];
+      most = most > words_host[base + i] ? most : words_host[base + i];
+    }
+    int bx = (int)((most + 1023) / 1024);
+    bx = bx < 1 ? 1 : (bx > NF_SLOTS ? NF_SLOTS : bx);
+    hipLaunchKernelGGL(guard_copy_multi_kernel, dim3((unsigned)bx, (unsigned)a.n), dim3(256), 0, (hipStream_t)stream, a,
+                       (const int*)verdict_dev, when);
+    FST_LAUNCH_CHECK();
+  }
+  return 0;
+}

@@ -205,3 +205,92 @@ extern "C" int fst_adam_multi_dev(float* const* p_host, const float* const* g_ho
   }
   return 0;
 }
+
+// ---- the same updates behind a device VERDICT word (anomaly guard: csrc/guard.hip writes it, fst_nonfinite_multi).  Each
+// workgroup reads verdict[0] once, a uniform 4-byte load when the kernel RUNS, and returns before its first store when the word
+// is non-zero: a step whose gradients hold a NaN or inf leaves parameters and moments as they were, under graph replay too.  The
+// bodies are rmsprop_update / adam_update, so a clean step gives the bits of the unguarded kernels.  One entry point per
+// optimiser serves both learning-rate forms: by value (lr_host / lr) or by device address (lr_dev_host / lr_dev), one of the two.
+static_assert(sizeof(RmspropArgs) + sizeof(const int*) <= 4096 && sizeof(RmspropDevArgs) + sizeof(const int*) <= 4096 &&
+              sizeof(AdamArgs) + 2 * sizeof(const void*) <= 4096, "kernel arguments: 4 KB at most");
+
+__global__ __launch_bounds__(256) void rmsprop_multi_guard_kernel(RmspropArgs a, const int* __restrict__ verdict) {
+  const int t = blockIdx.y;
+  if (t >= a.n || verdict[0] != 0) return;
+  rmsprop_update(a.p[t], a.g[t], a.v[t], a.numel[t], a.lr[t], a.alpha, a.eps);
+}
+
+__global__ __launch_bounds__(256) void rmsprop_multi_dev_guard_kernel(RmspropDevArgs a, const int* __restrict__ verdict) {
+  const int t = blockIdx.y;
+  if (t >= a.n || verdict[0] != 0) return;
+  rmsprop_update(a.p[t], a.g[t], a.v[t], a.numel[t], a.lr[t][0], a.alpha, a.eps);
+}
+
+// lr_dev == NULL: the rate is a.lr
+__global__ __launch_bounds__(256) void adam_multi_guard_kernel(AdamArgs a, const float* __restrict__ lr_dev,
+                                                               const int* __restrict__ verdict) {
+  const int t = blockIdx.y;
+  if (t >= a.n || verdict[0] != 0) return;
+  adam_update(a.p[t], a.g[t], a.m[t], a.v[t], a.numel[t], a.step[0], lr_dev ? lr_dev[0] : a.lr, a.beta1, a.beta2, a.eps);
+}
+
+extern "C" int fst_rmsprop_multi_guard(float* const* p_host, const float* const* g_host, float* const* v_host,
+                                       const int64_t* numel_host, const float* lr_host, const float* const* lr_dev_host, int n_tensors,
+                                       float alpha, float eps, const int32_t* verdict_dev, void* stream) {
+  FST_REQUIRE(p_host && g_host && v_host && numel_host && n_tensors >= 0 && verdict_dev, "fst_rmsprop_multi_guard: bad arguments");
+  FST_REQUIRE((lr_host != nullptr) != (lr_dev_host != nullptr),
+              "fst_rmsprop_multi_guard: the learning rates by value or by device address, one of the two");
+  if (int rc = optim_validate("fst_rmsprop_multi_guard", p_host, g_host, nullptr, v_host, numel_host, lr_dev_host, n_tensors)) return rc;
+  for (int base = 0; base < n_tensors; base += OPT_MAX_T) {
+    const int n = n_tensors - base < OPT_MAX_T ? n_tensors - base : OPT_MAX_T;
+    long long most = 0;
+    for (int i = 0; i < n; ++i) most = most > numel_host[base + i] ? most : numel_host[base + i];
+    int bx = (int)((most + 1023) / 1024);
+    bx = bx < 1 ? 1 : (bx > 64 ? 64 : bx);
+    const dim3 grid((unsigned)bx, (unsigned)n);
+    if (lr_host) {
+      RmspropArgs a;
+      a.n = n; a.alpha = alpha; a.eps = eps;
+      for (int i = 0; i < n; ++i) {
+        a.p[i] = p_host[base + i]; a.g[i] = g_host[base + i]; a.v[i] = v_host[base + i];
+        a.numel[i] = (int)numel_host[base + i]; a.lr[i] = lr_host[base + i];
+      }
+      hipLaunchKernelGGL(rmsprop_multi_guard_kernel, grid, dim3(256), 0, (hipStream_t)stream, a, (const int*)verdict_dev);
+    } else {
+      RmspropDevArgs a;
+      a.n = n; a.alpha = alpha; a.eps = eps;
+      for (int i = 0; i < n; ++i) {
+        a.p[i] = p_host[base + i]; a.g[i] = g_host[base + i]; a.v[i] = v_host[base + i];
+        a.numel[i] = (int)numel_host[base + i]; a.lr[i] = lr_dev_host[base + i];
+      }
+      hipLaunchKernelGGL(rmsprop_multi_dev_guard_kernel, grid, dim3(256), 0, (hipStream_t)stream, a, (const int*)verdict_dev);
+    }
+    FST_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+extern "C" int fst_adam_multi_guard(float* const* p_host, const float* const* g_host, float* const* m_host, float* const* v_host,
+                                    const int64_t* numel_host, int n_tensors, const float* step_dev, float lr, const float* lr_dev,
+                                    float beta1, float beta2, float eps, const int32_t* verdict_dev, void* stream) {
+  FST_REQUIRE(p_host && g_host && m_host && v_host && numel_host && step_dev && n_tensors >= 0 && verdict_dev,
+              "fst_adam_multi_guard: bad arguments");
+  if (int rc = optim_validate("fst_adam_multi_guard", p_host, g_host, m_host, v_host, numel_host, nullptr, n_tensors)) return rc;
+  for (int base = 0; base < n_tensors; base += OPT_MAX_T) {
+    AdamArgs a;
+    a.n = n_tensors - base < OPT_MAX_T ? n_tensors - base : OPT_MAX_T;
+    a.step = step_dev; a.lr = lr_dev ? 0.0f : lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
+    long long most = 0;
+    for (int i = 0; i < a.n; ++i) {
+      a.p[i] = p_host[base + i]; a.g[i] = g_host[base + i]; a.m[i] = m_host[base + i]; a.v[i] = v_host[base + i];
+      a.numel[i] = (int)numel_host[base + i];
+      most = most > numel_host[base + i] ? most : numel_host[base + i];
+    }
+    int bx = (int)((most + 1023) / 1024);
+    bx = bx < 1 ? 1 : (bx > 64 ? 64 : bx);
+    hipLaunchKernelGGL(adam_multi_guard_kernel, dim3((unsigned)bx, (unsigned)a.n), dim3(256), 0, (hipStream_t)stream, a, lr_dev,
+                       (const int*)verdict_dev);
+    FST_LAUNCH_CHECK();
+  }
+  return 0;
+}

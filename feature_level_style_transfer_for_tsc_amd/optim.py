@@ -16,11 +16,16 @@ captured step keeps the rate it was captured with.  ``lr_on_device=True`` (both 
 ``group["lr"]`` a scheduler has changed into it, so a replayed graph follows a stock ``torch.optim.lr_scheduler``.  ``lr_dev``
 lives outside ``param_groups`` and ``state``: ``state_dict()`` does not save it and ``load_state_dict()`` does not replace it (a
 captured graph holds its address); the next ``push_lr`` brings it in line with the loaded ``group["lr"]``.
+
+Anomaly guard.  ``count_nonfinite`` counts NaN / inf elements of many tensors per group on the device and, given an
+``AnomalyGuard``, leaves its verdict there; ``rmsprop_step_many(opts, guard=...)`` and ``SharedStepAdam.step(guard=...)`` then
+launch the same updates behind that verdict word (``fst_*_multi_guard``): a step with a non-finite gradient writes nothing, and
+nothing waits for the host.
 """
 from __future__ import annotations
 
 import ctypes
-from typing import Iterable, List, Sequence
+from typing import Iterable, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -87,7 +92,9 @@ class SharedStepAdam(_DeviceLR, torch.optim.Optimizer):
             self.state[ps[0]]["step"] = group["step"]                             # visible to state snapshots
 
     @torch.no_grad()
-    def step(self, closure=None):
+    def step(self, closure=None, guard: Optional["AnomalyGuard"] = None):
+        """``guard``: the update runs behind ``guard.verdict`` (read on the device when the kernels run) and the shared counter
+        advances by ``guard.ok``: after a non-zero verdict parameters, moments and counter are what they were."""
         assert closure is None
         if self.lr_on_device and not _capturing(self.lr_dev):
             push_lr([self])                                                     # eager: follow group["lr"] as the host-lr step does
@@ -100,11 +107,18 @@ class SharedStepAdam(_DeviceLR, torch.optim.Optimizer):
                 from . import _lib
                 lib = _lib.load()
                 t = group["step"]
-                t += 1
+                t += 1 if guard is None else guard.ok
                 grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in ps]
                 m = [self.state[p]["exp_avg"] for p in ps]
                 v = [self.state[p]["exp_avg_sq"] for p in ps]
                 b1, b2 = group["betas"]
+                if guard is not None:
+                    _lib.check(lib.fst_adam_multi_guard(_ptr_array(ps), _ptr_array(grads), _ptr_array(m), _ptr_array(v),
+                                                        _i64_array([p.numel() for p in ps]), len(ps), t.data_ptr(), group["lr"],
+                                                        self.lr_dev[gi].data_ptr() if self.lr_on_device else None, b1, b2,
+                                                        group["eps"], guard.verdict.data_ptr(), _lib.stream_ptr()),
+                               "fst_adam_multi_guard")
+                    continue
                 if self.lr_on_device:
                     _lib.check(lib.fst_adam_multi_dev(_ptr_array(ps), _ptr_array(grads), _ptr_array(m), _ptr_array(v),
                                                       _i64_array([p.numel() for p in ps]), len(ps), t.data_ptr(),
@@ -120,6 +134,8 @@ class SharedStepAdam(_DeviceLR, torch.optim.Optimizer):
             v = [self.state[p]["exp_avg_sq"] for p in ps]
             b1, b2 = group["betas"]
             t = group["step"]
+            if guard is not None:                                               # CPU: the unguarded arithmetic on copies, kept where ok
+                old = [t.clone()] + [x.detach().clone() for x in list(ps) + m + v]
             t += 1
             b1_t, b2_t = group["betas_dev"]
             bc1 = 1.0 - torch.pow(b1_t, t)
@@ -134,6 +150,10 @@ class SharedStepAdam(_DeviceLR, torch.optim.Optimizer):
             upd = torch._foreach_div(m, denom)
             torch._foreach_mul_(upd, (self.lr_dev[gi] if self.lr_on_device else group["lr"]) / bc1)
             torch._foreach_sub_(ps, upd)
+            if guard is not None:
+                keep = guard.ok > 0
+                for x, o in zip([t] + list(ps) + m + v, old):
+                    x.copy_(torch.where(keep, x, o))
         return None
 
 
@@ -161,27 +181,29 @@ class FusedRMSprop(_DeviceLR, torch.optim.Optimizer):
             self.enable_lr_on_device()
 
     @torch.no_grad()
-    def step(self, closure=None):
+    def step(self, closure=None, guard: Optional["AnomalyGuard"] = None):
         assert closure is None
-        rmsprop_step_many([self])
+        rmsprop_step_many([self], guard)
         return None
 
 
 @torch.no_grad()
-def rmsprop_step_many(opts: Sequence[FusedRMSprop]) -> None:
+def rmsprop_step_many(opts: Sequence[FusedRMSprop], guard: Optional["AnomalyGuard"] = None) -> None:
     """One step of several FusedRMSprops: one series of launches for the optimisers with host learning rates and one for those
-    with ``lr_on_device`` (whose ``lr_dev`` is brought up to date first, except under stream capture)."""
+    with ``lr_on_device`` (whose ``lr_dev`` is brought up to date first, except under stream capture).  ``guard``: the updates run
+    behind ``guard.verdict``, read on the device when the kernels run; with a non-zero verdict no parameter and no moment changes
+    (moments created by this call stay zero)."""
     host = [o for o in opts if not o.lr_on_device]
     dev = [o for o in opts if o.lr_on_device]
     if host:
-        _rmsprop_launch(host, False)
+        _rmsprop_launch(host, False, guard)
     if dev:
         if not _capturing(dev[0].lr_dev):
             push_lr(dev)
-        _rmsprop_launch(dev, True)
+        _rmsprop_launch(dev, True, guard)
 
 
-def _rmsprop_launch(opts: Sequence[FusedRMSprop], on_device: bool) -> None:
+def _rmsprop_launch(opts: Sequence[FusedRMSprop], on_device: bool, guard: Optional["AnomalyGuard"] = None) -> None:
     ps: List[torch.Tensor] = []
     grads: List[torch.Tensor] = []
     vs: List[torch.Tensor] = []
@@ -207,18 +229,129 @@ def _rmsprop_launch(opts: Sequence[FusedRMSprop], on_device: bool) -> None:
         return
     if not ps[0].is_cuda:                                                     # CPU tests of the host logic: torch's own formula
         for p, g, v, lr in zip(ps, grads, vs, lrs):
+            if guard is not None:
+                old_p, old_v = p.detach().clone(), v.clone()
             v.mul_(alpha).addcmul_(g, g, value=1 - alpha)
             if on_device:
                 p.sub_(lr * (g / v.sqrt().add_(eps)))
             else:
                 p.addcdiv_(g, v.sqrt().add_(eps), value=-lr)
+            if guard is not None:
+                keep = guard.ok > 0
+                p.copy_(torch.where(keep, p, old_p)); v.copy_(torch.where(keep, v, old_v))
         return
     from . import _lib
     lib = _lib.load()
     assert all(p.is_contiguous() for p in ps)
+    if guard is not None:
+        _lib.check(lib.fst_rmsprop_multi_guard(_ptr_array(ps), _ptr_array(grads), _ptr_array(vs), _i64_array([p.numel() for p in ps]),
+                                               None if on_device else (ctypes.c_float * len(lrs))(*lrs),
+                                               _ptr_array(lrs) if on_device else None, len(ps), alpha, eps,
+                                               guard.verdict.data_ptr(), _lib.stream_ptr()), "fst_rmsprop_multi_guard")
+        return
     if on_device:
         _lib.check(lib.fst_rmsprop_multi_dev(_ptr_array(ps), _ptr_array(grads), _ptr_array(vs), _i64_array([p.numel() for p in ps]),
                                              _ptr_array(lrs), len(ps), alpha, eps, _lib.stream_ptr()), "fst_rmsprop_multi_dev")
         return
     _lib.check(lib.fst_rmsprop_multi(_ptr_array(ps), _ptr_array(grads), _ptr_array(vs), _i64_array([p.numel() for p in ps]),
                                      (ctypes.c_float * len(lrs))(*lrs), len(ps), alpha, eps, _lib.stream_ptr()), "fst_rmsprop_multi")
+
+
+# ---- anomaly guard: a device-side verdict on the values a step's update consumes
+MAX_GROUPS = 32
+
+
+class AnomalyGuard:
+    """The device words of the anomaly guard: ``counts`` (int32[32], non-finite elements per group of the last
+    ``count_nonfinite``), ``verdict`` (int32, 1 if a group of the verdict mask counted anything), ``ok`` (fp32, 1 − verdict: what a
+    shared step counter advances by) and ``skipped`` (int32, the cumulative number of non-zero verdicts).  The kernels of the
+    guarded optimisers read ``verdict`` when they run; the host reads any of these only when it chooses to."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.counts = torch.zeros(MAX_GROUPS, dtype=torch.int32, device=device)
+        self.verdict = torch.zeros(1, dtype=torch.int32, device=device)
+        self.ok = torch.ones((), dtype=torch.float32, device=device)
+        self.skipped = torch.zeros(1, dtype=torch.int32, device=device)
+        self._slots = None                                                    # scratch of the scan, grown outside captures
+
+    def slots(self, n_words: int) -> torch.Tensor:
+        if self._slots is None or self._slots.numel() < n_words:
+            if _capturing(self.verdict):
+                raise RuntimeError("AnomalyGuard: the scan's slot array would have to grow inside a stream capture; run one eager "
+                                   "step of the same tensors first")
+            self._slots = torch.empty(max(n_words, 1), dtype=torch.int32, device=self.device)
+        return self._slots
+
+
+@torch.no_grad()
+def count_nonfinite(tensors: Sequence[torch.Tensor], groups: Sequence[int], n_groups: int, guard: Optional[AnomalyGuard] = None,
+                    verdict_groups: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """Number of non-finite (NaN, ±inf) elements of the fp32 ``tensors`` per group: ``groups[i]`` in ``range(n_groups)``,
+    ``n_groups`` ≤ 32.  Returns an int32 tensor of ``n_groups`` counts on the tensors' device, without waiting for it: on the GPU
+    one ``fst_nonfinite_multi`` launch per 64 tensors plus a finalising one; the tensors are only read (views that start 4 bytes
+    off a 16-byte boundary included; non-contiguous ones are copied first).  With a ``guard`` the counts go into ``guard.counts``
+    (a view of it is returned) and the call leaves ``guard.verdict`` = 1 if a group of ``verdict_groups`` (default: every group)
+    counted anything, ``guard.ok`` = 1 − verdict, and adds the verdict to ``guard.skipped``."""
+    if not 0 < n_groups <= MAX_GROUPS:
+        raise ValueError(f"count_nonfinite: n_groups must be in 1..{MAX_GROUPS}, got {n_groups}")
+    if len(tensors) != len(groups):
+        raise ValueError(f"count_nonfinite: {len(tensors)} tensors, {len(groups)} group ids")
+    for i, (t, g) in enumerate(zip(tensors, groups)):
+        if not 0 <= int(g) < n_groups:
+            raise ValueError(f"count_nonfinite: tensor {i}: group {g} is not in range({n_groups})")
+        if t.dtype != torch.float32:
+            raise TypeError(f"count_nonfinite: tensor {i} must be float32, got {t.dtype}")
+    mask = (1 << MAX_GROUPS) - 1
+    if verdict_groups is not None:
+        mask = sum(1 << int(g) for g in set(verdict_groups))
+    keep = [(t, int(g)) for t, g in zip(tensors, groups) if t.numel() > 0]
+    dev = guard.device if guard is not None else (tensors[0].device if tensors else torch.device("cpu"))
+    if dev.type != "cuda":                                                    # CPU tests of the host logic
+        counts = torch.zeros(MAX_GROUPS, dtype=torch.int32)
+        for t, g in keep:
+            counts[g] += int((~torch.isfinite(t)).sum())
+        if guard is not None:
+            bad = int(any(int(counts[g]) > 0 for g in range(MAX_GROUPS) if (mask >> g) & 1))
+            guard.counts.copy_(counts)
+            guard.verdict.fill_(bad); guard.ok.fill_(1.0 - bad); guard.skipped.add_(bad)
+            counts = guard.counts
+        return counts[:n_groups]
+    from . import _lib
+    lib = _lib.load()
+    xs = [t if t.is_contiguous() else t.contiguous() for t, _ in keep]
+    n_slots = int(lib.fst_nonfinite_slots(len(xs)))
+    if guard is None:
+        counts, slots = torch.empty(MAX_GROUPS, dtype=torch.int32, device=dev), torch.empty(max(n_slots, 1), dtype=torch.int32, device=dev)
+        words = (None, None, None)
+    else:
+        counts, slots = guard.counts, guard.slots(n_slots)
+        words = (guard.verdict.data_ptr(), guard.ok.data_ptr(), guard.skipped.data_ptr())
+    _lib.check(lib.fst_nonfinite_multi(_ptr_array(xs), _i64_array([x.numel() for x in xs]), (ctypes.c_int32 * len(xs))(*[g for _, g in keep]),
+                                       len(xs), mask - (1 << 32) if mask >> 31 else mask, slots.data_ptr(), slots.numel(), counts.data_ptr(), *words, _lib.stream_ptr()),
+               "fst_nonfinite_multi")
+    return counts[:n_groups]
+
+
+@torch.no_grad()
+def guard_copy(dst: Sequence[torch.Tensor], src: Sequence[torch.Tensor], guard: Optional[AnomalyGuard] = None, when: bool = True) -> None:
+    """Copy every ``src[i]`` into ``dst[i]`` (same shape and dtype, contiguous, elements of 4 or 8 bytes) as one multi-tensor
+    launch per 64 tensors: at once without a ``guard``, otherwise only if ``(guard.verdict != 0) == when`` at the time the kernel
+    runs — the save and the roll-back of state that cannot be guarded where it is written."""
+    for d, s in zip(dst, src):
+        if d.shape != s.shape or d.dtype != s.dtype or not (d.is_contiguous() and s.is_contiguous()) or d.element_size() % 4:
+            raise ValueError(f"guard_copy: {tuple(s.shape)} {s.dtype} -> {tuple(d.shape)} {d.dtype}: contiguous tensors of one shape "
+                             "and dtype with elements of 4 or 8 bytes")
+    pairs = [(d, s) for d, s in zip(dst, src) if d.numel() > 0]
+    if not pairs:
+        return
+    if not pairs[0][0].is_cuda:
+        if guard is None or bool(guard.verdict.item() != 0) == bool(when):
+            for d, s in pairs:
+                d.copy_(s)
+        return
+    from . import _lib
+    _lib.check(_lib.load().fst_guard_copy_multi(_ptr_array([d for d, _ in pairs]), _ptr_array([s for _, s in pairs]),
+                                                _i64_array([d.numel() * d.element_size() // 4 for d, _ in pairs]), len(pairs),
+                                                None if guard is None else guard.verdict.data_ptr(), int(bool(when)),
+                                                _lib.stream_ptr()), "fst_guard_copy_multi")

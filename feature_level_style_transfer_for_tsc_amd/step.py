@@ -15,6 +15,10 @@ Data parallelism: ``dist.GradBucket`` all-reduces one flat fp32 gradient bucket 
 Schedules (train_and_test.py:118-134, :665-672): ``make_schedulers`` builds the reference's eleven learning-rate schedulers
 on a trainer's optimisers and ``end_epoch`` steps the ones the reference steps.  A captured step follows them only after
 ``enable_device_hparams()``, which moves the learning rates and the four epoch coefficients into device tensors.
+
+Anomaly guard (``JointTrainer.enable_anomaly_guard()``): instead of the reference's ``torch.autograd.set_detect_anomaly(True)``
+(train_and_test.py:24), which cannot run under capture, a step whose update would consume a NaN or an inf is made a no-op on the
+trainer's state, decided on the device, in eager and in replayed steps alike.
 """
 from __future__ import annotations
 
@@ -31,7 +35,7 @@ from .cdan import CDAN, RandomLayer
 from .cpc import CPC
 from . import dist as _dist
 from .dist import GradBucket
-from .optim import FusedRMSprop, SharedStepAdam, push_lr, rmsprop_step_many
+from .optim import AnomalyGuard, FusedRMSprop, SharedStepAdam, count_nonfinite, guard_copy, push_lr, rmsprop_step_many
 from .os_cnn import OS_CNN, OS_CNN_res, build_layer_with_layer_parameter
 from .structure import generate_layer_parameter_list, layer_parameter_list_input_change, out_channels
 from .waveglow import WaveGlow, WaveGlowLoss
@@ -126,6 +130,9 @@ _CAPTURE_MODE = "thread_local"
 
 
 class ClassifierTrainer:
+    """S1 of the reference.  The anomaly guard (``JointTrainer.enable_anomaly_guard``) is not offered here: a non-finite batch
+    reaches this trainer's parameters as it does in the reference."""
+
     def __init__(self, length: int, in_channel: int, n_class: int, device, bucket: Optional[GradBucket] = None,
                  sync: str = "ddp", device_hparams: bool = False):
         self.sync = sync
@@ -218,12 +225,17 @@ class JointTrainer:
     MODULES = ("fe_t", "clf_t", "fe_s", "dimunif", "clf_s", "probtransfer", "nf", "noise", "ad_net", "fd_s", "cpc")
     LRS = {"fe_t": 0.001, "clf_t": 0.003, "fe_s": 0.001, "dimunif": 0.001, "clf_s": 0.003, "probtransfer": 0.001,
            "nf": 0.001, "noise": 0.005, "ad_net": 0.001, "fd_s": 0.001}       # train_and_test.py:97-106
+    # groups of the anomaly guard's counts: a module's gradients; "gradnorm" = the ten GradNorm scalars and the two weight
+    # gradients; "losses" = the step's loss scalars (per rank under data parallelism: reported, never part of the verdict);
+    # "buffers" = the BatchNorm running statistics and NoiseTransfer sums the forward pass wrote (decide without a GradBucket only)
+    ANOMALY_GROUPS = MODULES + ("gradnorm", "losses", "buffers")
 
     def __init__(self, cfg: JointConfig, device, bucket: Optional[GradBucket] = None, fe_t_spec=None, clf_spec=None,
-                 fe_s_spec=None, sync: str = "ddp", device_hparams: bool = False):
+                 fe_s_spec=None, sync: str = "ddp", device_hparams: bool = False, anomaly_guard: bool = False):
         """``sync`` (with a bucket): "ddp" = per-rank batch statistics (SURVEY §8e mode A); "global" = every
         batch-coupled quantity over the samples of all ranks (mode B, eager only) — N ranks reproduce the
-        single-process step on the concatenated batch.  ``device_hparams``: ``enable_device_hparams()`` at once."""
+        single-process step on the concatenated batch.  ``device_hparams``: ``enable_device_hparams()`` at once;
+        ``anomaly_guard``: ``enable_anomaly_guard()`` at once."""
         if sync not in ("ddp", "global"):
             raise ValueError(f"sync must be 'ddp' or 'global', got {sync!r}")
         self.cfg, self.device, self.bucket, self.sync = cfg, device, bucket, sync
@@ -273,6 +285,12 @@ class JointTrainer:
         self._coef_host = None                                                # ... and the values it holds
         self.schedulers = None                                                # make_schedulers()
         self._sched_epoch = None                                              # epoch of the coefficients last applied
+        self.anomaly_guard = False
+        self._guard: Optional[AnomalyGuard] = None                            # anomaly_guard: the verdict words on the device
+        self._shadow: Dict[str, torch.Tensor] = {}                            # ... copies of the state rolled back after a bad step
+        self._guard_live = None                                               # ... (live, shadow) lists of the step's save
+        self._guard_fwd = ()                                                  # ... fp32 buffers the forward writes, of that save
+        self._guard_losses = ()                                               # ... loss scalars of a phase step, for the counts
         for mod in self.m.values():
             mod.train()
         # GradNorm differentiates the shared OS_blocks only: their convs keep weight gradients in partial passes
@@ -281,6 +299,117 @@ class JointTrainer:
                 layer.spec.always_weight_grad = True
         if device_hparams:
             self.enable_device_hparams()
+        if anomaly_guard:
+            self.enable_anomaly_guard()
+
+    # ------------------------------------------------------------------ anomaly guard: skip non-finite steps on the device
+    def enable_anomaly_guard(self) -> None:
+        """From now on a step whose update would consume a non-finite value is a NO-OP on the trainer's state: after it every
+        tensor of ``_state_tensors()`` holds the bits it held before.  Decided on the device with no host synchronisation, in
+        ``step``, ``capture`` / ``replay``, ``phase_step`` and ``capture_phase`` / ``replay_phase``; a clean step computes the bits
+        of the unguarded step.
+
+        The verdict covers exactly what the update consumes: every ``.grad`` the step's optimisers read (after the data-parallel
+        all-reduce), and in the joint step the ten GradNorm scalars (after ``mean_scalars``) and the two GradNorm weight
+        gradients — all identical on every rank, so every rank decides alike.  Without a ``GradBucket`` the BatchNorm running
+        statistics and NoiseTransfer's sums as the forward pass left them decide as well, counted as the group "buffers": the
+        ReLU fused into BatchNorm maps NaN to 0, so a bad input can poison the statistics and leave every gradient finite.  With a
+        bucket those per-rank buffers stay out of the verdict (a rank deciding alone would part from the others) and such an
+        input is not caught.  The verdict is taken after ``on_grads_ready`` and before the
+        first optimiser.  Parameters and RMSprop / Adam moments are guarded where they are written (``fst_*_multi_guard``, CPC's
+        shared counter advances by ``ok``); what the forward pass and the tail of the update mutate in place (BatchNorm buffers,
+        NoiseTransfer's sums, the omni-scale conv weights whose masked taps every forward zeroes again (Q1), the GradNorm weights
+        with their Adams, the WGAN-clamped ``ad_net`` / ``fd_s`` parameters) is saved
+        into shadow buffers at the start of the step and rolled back at its end if the verdict says so — both inside the
+        captured region (first and last graph of a data-parallel capture).
+
+        Every report gains ``"skipped"`` (0 or 1) and ``"anomaly"`` (int32 counts of non-finite values per ``ANOMALY_GROUPS``
+        entry; "losses" counts the step's loss scalars for the report only, "buffers" is 0 with a bucket); ``skipped_steps`` is the cumulative device counter.
+        ``init_t`` / ``init_s`` are created by the first COMPLETED step: that one eager step reads the verdict on the host (one
+        synchronisation, once) and leaves them unset if it was skipped; ``capture`` raises if its warm-up ends without them.
+        Host-side call counters — NoiseTransfer's ``time`` / ``cal_num_*`` and the GRL ``iter_num`` — count CALLS, skipped or not.
+        Works with ``device_hparams`` on or off and with or without a ``GradBucket``.  Idempotent; raises while a joint or phase
+        capture is resident, whose launches are the unguarded ones."""
+        if self.anomaly_guard:
+            return
+        if self._graphs is not None or self._phase:
+            raise RuntimeError("enable_anomaly_guard(): a capture is resident; enable the mode before capture() / capture_phase()")
+        self._guard = AnomalyGuard(self.device)
+        # the GradNorm-weight Adams create their state on their first step; a skipped first step must leave none behind, so it
+        # exists from now on, with the values torch would create (capturable: a float32 device step counter)
+        for o, w in ((self.opt_w_t, self.w_t), (self.opt_w_s, self.w_s)):
+            if len(o.state[w]) == 0:
+                o.state[w]["step"] = torch.zeros((), dtype=torch.float32, device=w.device)
+                o.state[w]["exp_avg"] = torch.zeros_like(w, memory_format=torch.preserve_format)
+                o.state[w]["exp_avg_sq"] = torch.zeros_like(w, memory_format=torch.preserve_format)
+        self.anomaly_guard = True
+
+    @property
+    def skipped_steps(self) -> Optional[torch.Tensor]:
+        """The cumulative number of skipped steps as a device tensor (int32, one element; None with the mode off).  Nothing in
+        a step waits for it: read it whenever the host chooses."""
+        return None if self._guard is None else self._guard.skipped
+
+    def _guard_save(self) -> None:
+        """Start of a guarded step: copy the state that is not guarded at its writer into its shadows."""
+        live: List[torch.Tensor] = []
+        names: List[str] = []
+        fwd = []                                                              # fp32 state the forward pass writes
+        for k in self.MODULES:
+            is_param = {n for n, _ in self.m[k].named_parameters()}
+            # Q1: an omni-scale layer re-masks its weight's .data in every forward, after the optimiser has moved the masked taps
+            masked = {f"{n}.conv1d.weight" if n else "conv1d.weight" for n, sub in self.m[k].named_modules()
+                      if isinstance(sub, build_layer_with_layer_parameter)}
+            for n, t in self.m[k].state_dict().items():
+                if n not in is_param or n in masked or k in ("ad_net", "fd_s"):   # buffers; parameters the WGAN clamps rewrite
+                    names.append(f"m.{k}.{n}"); live.append(t)
+                    if n not in is_param and t.dtype == torch.float32:
+                        fwd.append(t)
+        for k, o, w in (("w_t", self.opt_w_t, self.w_t), ("w_s", self.opt_w_s, self.w_s)):
+            names.append(k); live.append(w.data)
+            for n, t in o.state[w].items():
+                if isinstance(t, torch.Tensor):
+                    names.append(f"o.{k}.{n}"); live.append(t)
+        names += ["noise.target_avg", "noise.source_avg"]
+        live += [self.m["noise"].target_avg, self.m["noise"].source_avg]
+        fwd += live[-2:]
+        self._guard_fwd = fwd
+        shadow = []
+        for n, t in zip(names, live):
+            sh = self._shadow.get(n)
+            if sh is None or sh.shape != t.shape or sh.dtype != t.dtype:
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError(f"anomaly guard: no shadow buffer for {n} yet; run one eager step before capturing")
+                sh = self._shadow[n] = torch.empty_like(t, memory_format=torch.contiguous_format)
+            shadow.append(sh)
+        guard_copy(shadow, live)
+        self._guard_live = (live, shadow)
+
+    def _guard_scan(self, modules, gradnorm, losses) -> None:
+        """The verdict of a step: count the non-finite values of the gradients of ``modules`` (one group each), of the
+        ``gradnorm`` tensors and of the ``losses`` scalars; everything but the losses decides."""
+        G = self.ANOMALY_GROUPS
+        xs, gs = [], []
+        for k in modules:
+            for p in self.m[k].parameters():
+                if p.grad is not None:
+                    xs.append(p.grad); gs.append(G.index(k))
+        if self.bucket is None:
+            # One process: what the forward pass has already written into the state (BatchNorm running statistics, NoiseTransfer's
+            # sums) decides too, as the group "buffers" — a NaN input that a fused ReLU turns into 0 (fmaxf) reaches the running
+            # statistics and no gradient.  With a GradBucket these buffers are per-rank values and stay out: ranks must decide alike.
+            xs += list(self._guard_fwd); gs += [G.index("buffers")] * len(self._guard_fwd)
+        xs += list(gradnorm); gs += [G.index("gradnorm")] * len(gradnorm)
+        xs += list(losses); gs += [G.index("losses")] * len(losses)
+        count_nonfinite(xs, gs, len(G), self._guard, verdict_groups=[i for i, k in enumerate(G) if k != "losses"])
+
+    def _guard_rollback(self) -> None:
+        """End of a guarded step: if the verdict is 1, put the shadows of ``_guard_save`` back."""
+        live, shadow = self._guard_live
+        guard_copy(live, shadow, self._guard, when=True)
+
+    def _guard_report(self) -> Dict[str, torch.Tensor]:
+        return {"skipped": self._guard.verdict[0].clone(), "anomaly": self._guard.counts[: len(self.ANOMALY_GROUPS)].clone()}
 
     # ------------------------------------------------------------------ schedules under graph replay
     def enable_device_hparams(self) -> None:
@@ -571,11 +700,15 @@ class JointTrainer:
         if self.bucket is not None:
             self.bucket.all_reduce(self.parameters())
         self._phase_update(phase)
+        if self._guard is not None:
+            report.update(self._guard_report())
         return report
 
     def _phase_fwd_bwd(self, phase: str, x_t, y_t, x_s, y_s, t_samples):
         """First half of a phase step, device-side and shape-static when the CPC indices are device scalars: the losses, zero_grad,
         backward.  Returns the report."""
+        if self._guard is not None:
+            self._guard_save()
         with _dist.global_batch(self.bucket if self.sync == "global" else None):
             with ops.pack_cache(), self.m["nf"].shared_fold(), self.m["cpc"].shared_stack():
                 total, L = self.phase_losses(phase, x_t, y_t, x_s, y_s, t_samples)
@@ -585,12 +718,22 @@ class JointTrainer:
                 total.backward()
         report = {k: v.detach() for k, v in L.items()}
         report["total"] = total.detach()
+        if self._guard is not None:
+            self._guard_losses = tuple(report.values())
         return report
 
     def _phase_update(self, phase: str) -> None:
         """Second half (after the gradient all-reduce of a data-parallel step): the phase's optimisers."""
         if self.on_grads_ready is not None:
             self.on_grads_ready()
+        if self._guard is not None:
+            self._guard_scan(self.PHASES[phase], (), self._guard_losses)
+            self._guard_losses = ()
+            rmsprop_step_many([self.opts[k] for k in self.PHASES[phase] if k != "cpc"], self._guard)
+            if "cpc" in self.PHASES[phase]:
+                self.opt_cpc.step(guard=self._guard)
+            self._guard_rollback()
+            return
         rmsprop_step_many([self.opts[k] for k in self.PHASES[phase] if k != "cpc"])
         if "cpc" in self.PHASES[phase]:
             self.opt_cpc.step()
@@ -639,7 +782,16 @@ class JointTrainer:
         main.wait_stream(side)
         torch.cuda.synchronize()
         # static report: the graphs' own outputs live in the shared pool, where a later capture may reuse what this one frees
+        keys = [k for k in keys if k not in ("skipped", "anomaly")]            # anomaly guard: static tensors of their own
         out = torch.zeros(len(keys), device=dev)
+        g_rep = {} if self._guard is None else {"skipped": torch.zeros((), dtype=torch.int32, device=dev),
+                                                "anomaly": torch.zeros(len(self.ANOMALY_GROUPS), dtype=torch.int32, device=dev)}
+
+        def update():
+            self._phase_update(phase)
+            if self._guard is not None:
+                g_rep["skipped"].copy_(self._guard.verdict[0])
+                g_rep["anomaly"].copy_(self._guard.counts[: len(self.ANOMALY_GROUPS)])
 
         def fwd_bwd():
             rep = self._phase_fwd_bwd(phase, *args)
@@ -652,20 +804,20 @@ class JointTrainer:
                 graphs = [torch.cuda.CUDAGraph()]
                 with torch.cuda.graph(graphs[0], pool=self._phase_pool, capture_error_mode=_CAPTURE_MODE):
                     fwd_bwd()
-                    self._phase_update(phase)
+                    update()
             else:
                 graphs = [torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()]
                 with torch.cuda.graph(graphs[0], pool=self._phase_pool, capture_error_mode=_CAPTURE_MODE):
                     fwd_bwd()
                 self.bucket.all_reduce(params)                                # eager, between the graphs
                 with torch.cuda.graph(graphs[1], pool=self._phase_pool, capture_error_mode=_CAPTURE_MODE):
-                    self._phase_update(phase)
+                    update()
             # the gradient tensors the graph writes stay allocated as long as the graph does
             grads = [p.grad for p in params if p.grad is not None]
         finally:
             for p, g in zip(params, grads_before):
                 p.grad = g
-        self._phase[phase] = {"graphs": graphs, "in": gi, "grads": grads, "report": {k: out[i] for i, k in enumerate(keys)}}
+        self._phase[phase] = {"graphs": graphs, "in": gi, "grads": grads, "report": {**{k: out[i] for i, k in enumerate(keys)}, **g_rep}}
         return self
 
     def replay_phase(self, phase: str, x_t, y_t, x_s, y_s, t_samples=(0, 0)):
@@ -739,6 +891,8 @@ class JointTrainer:
         return st
 
     def _step_part_a1(self, x_t, y_t, x_s, y_s, epoch, t_samples, noise_ratios):
+        if self._guard is not None:
+            self._guard_save()
         if True:
             L, aux = self.forward_losses(x_t, y_t, x_s, y_s, t_samples, noise_ratios)
             lt = torch.stack([L["nf_t"], L["ce_t"]])
@@ -780,7 +934,7 @@ class JointTrainer:
         report.update({k: v.detach() for k, v in aux.items()})
         # scalars that must be identical on every rank: loss values and gradient-norm bases (10 floats)
         scal = torch.cat([lt.detach(), ls.detach(), base_t, base_s]).contiguous()
-        return {"report": report, "scal": scal}
+        return {"report": report, "scal": scal, "loss_keys": tuple(L)}
 
     def _step_part_a(self, x_t, y_t, x_s, y_s, epoch, t_samples, noise_ratios):
         with self._step_scope():
@@ -799,6 +953,7 @@ class JointTrainer:
     def _step_part_b(self, mid):
         scal = mid["scal"]
         lt_v, ls_v, base_t, base_s = scal[0:2], scal[2:5], scal[5:7], scal[7:10]
+        guard, first = self._guard, self.init_t is None
         if self.init_t is None:                                               # :658-664
             self.init_t, self.init_s = torch.sigmoid(lt_v).clone(), torch.sigmoid(ls_v).clone()
         # ‖wᵢ·g‖ = |wᵢ|·‖g‖, so the norms are differentiable functions of w alone (:685-715)
@@ -815,9 +970,17 @@ class JointTrainer:
             w.grad.copy_(g)
         if self.on_grads_ready is not None:
             self.on_grads_ready()
+        if guard is not None:
+            self._guard_scan(self.MODULES, (scal, self.w_t.grad, self.w_s.grad), [mid["report"][k] for k in mid["loss_keys"]])
+            if first and int(guard.verdict) != 0:                             # the one host read: only a COMPLETED step sets them
+                self.init_t = self.init_s = None
         self.opt_w_t.step(); self.opt_w_s.step()
-        rmsprop_step_many(list(self.opts.values()))
-        self.opt_cpc.step()
+        if guard is not None:
+            rmsprop_step_many(list(self.opts.values()), guard)
+            self.opt_cpc.step(guard=guard)
+        else:
+            rmsprop_step_many(list(self.opts.values()))
+            self.opt_cpc.step()
         with torch.no_grad():                                                 # :756-766
             self.w_t.clamp_(min=0.0)
             self.w_t.mul_(7 / torch.sum(self.w_t))
@@ -827,9 +990,13 @@ class JointTrainer:
                 p.clamp_(-0.0005, 0.0005)
             for p in self.m["fd_s"].parameters():
                 p.clamp_(-0.01, 0.01)
+        if guard is not None:
+            self._guard_rollback()
         report = dict(mid["report"])
         report.update({"w_t": self.w_t.detach().clone(), "w_s": self.w_s.detach().clone(),
                        "norms_t": nt.detach(), "norms_s": ns.detach()})
+        if guard is not None:
+            report.update(self._guard_report())
         return report
 
     # ------------------------------------------------------------------ hipGraph: capture once, replay per step
@@ -863,6 +1030,9 @@ class JointTrainer:
         torch.cuda.synchronize()
         if self.m["ad_net"].iter_num < self.m["ad_net"].max_iter or self.m["fd_s"].iter_num < self.m["fd_s"].max_iter:
             raise RuntimeError("capture(): GRL call counters not saturated yet; increase warmup")
+        if self._guard is not None and self.init_t is None:
+            raise RuntimeError("capture(): the anomaly guard skipped every warm-up step (non-finite gradients), so the GradNorm "
+                               "reference losses init_t / init_s do not exist yet; capture on a batch the step completes on")
         self._replay_inputs(x_t, y_t, x_s, y_s, (0, 0))
         if self.bucket is None:
             self._graphs = [torch.cuda.CUDAGraph()]

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FST_ABI_VERSION 17
+#define FST_ABI_VERSION 18
 
 int fst_version(void);
 const char* fst_last_error(void);
@@ -568,6 +568,35 @@ int fst_rmsprop_multi_dev(float* const* p_host, const float* const* g_host, floa
 int fst_adam_multi_dev(float* const* p_host, const float* const* g_host, float* const* m_host, float* const* v_host,
                        const int64_t* numel_host, int n_tensors, const float* step_dev, const float* lr_dev, float beta1, float beta2,
                        float eps, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Anomaly guard (ABI v18): skip a train step whose update would consume a NaN or an inf, decided on the device, so that it works
+ * inside a replayed hipGraph (the reference's protection is torch.autograd.set_detect_anomaly, train_and_test.py:24).
+ * nonfinite_multi counts the elements of n_tensors fp32 tensors whose exponent bits are all ones, per group (group_host[i] in
+ * 0..31; pointers 4-byte aligned, 0 < element count < 2^31), and only reads them.  slots_dev is int32 scratch of at least
+ * nonfinite_slots(n_tensors) words that every call rewrites (nothing has to be zeroed): per tensor a record of 65 words, its
+ * group id and the counts of its up to 64 workgroups.  A finalising launch writes counts_dev[32]
+ * (int32, all 32 words) and, where the pointer is not NULL: verdict_dev[0] = 1 if a group whose bit is set in verdict_mask counted
+ * anything (bit g: group g), else 0; ok_dev[0] = 1.0f - verdict; skipped_dev[0] += verdict.  n_tensors == 0 is a clean verdict.
+ * The *_multi_guard entry points are the updates of rmsprop_multi[_dev] / adam_multi[_dev] (same update bodies: same bits on a
+ * clean step) behind verdict_dev, read when the kernel RUNS: with a non-zero word nothing is written.  Learning rates: by value
+ * (lr_host / lr) or by device address (lr_dev_host / lr_dev); for RMSprop exactly one of the two arrays, for Adam lr_dev or NULL.
+ * guard_copy_multi copies words_host[i] 4-byte words from src_host[i] to dst_host[i] (4-byte aligned device pointers, no overlap)
+ * when verdict_dev is NULL or (verdict_dev[0] != 0) == when (0 or 1), read when the kernel runs; otherwise it writes nothing.
+ * Every entry is validated on the host BEFORE the first launch, as for the optimisers: a refused call has written nothing.
+ * ------------------------------------------------------------------------------------------- */
+int64_t fst_nonfinite_slots(int n_tensors);
+int fst_nonfinite_multi(const float* const* x_host, const int64_t* numel_host, const int32_t* group_host, int n_tensors,
+                        int32_t verdict_mask, int32_t* slots_dev, int64_t slots_len, int32_t* counts_dev, int32_t* verdict_dev,
+                        float* ok_dev, int32_t* skipped_dev, void* stream);
+int fst_rmsprop_multi_guard(float* const* p_host, const float* const* g_host, float* const* v_host, const int64_t* numel_host,
+                            const float* lr_host, const float* const* lr_dev_host, int n_tensors, float alpha, float eps,
+                            const int32_t* verdict_dev, void* stream);
+int fst_adam_multi_guard(float* const* p_host, const float* const* g_host, float* const* m_host, float* const* v_host,
+                         const int64_t* numel_host, int n_tensors, const float* step_dev, float lr, const float* lr_dev, float beta1,
+                         float beta2, float eps, const int32_t* verdict_dev, void* stream);
+int fst_guard_copy_multi(void* const* dst_host, const void* const* src_host, const int64_t* words_host, int n_tensors,
+                         const int32_t* verdict_dev, int when, void* stream);
 
 #ifdef __cplusplus
 }
