@@ -12,7 +12,7 @@ from typing import Optional
 
 import torch
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 _LIB_NAME = "libfst_hip.so"
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FST_HIP_LIB", os.path.join(_HERE, _LIB_NAME))     # override: diagnostic builds only
@@ -71,6 +71,8 @@ _SIGNATURES = {
     "fst_wn_stack_fwd": (c_int, [_P, _P, _P, c_int64, _P, _P, _P, c_int64, _P, c_int, c_int, c_int, c_int, c_int, c_int64, c_void_p]),
     "fst_wn_stack_bwd_ok": (c_int, [c_int, c_int, c_int, c_int]),
     "fst_wn_stack_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int, c_int, c_int, c_int, c_int, c_int64, c_void_p]),
+    "fst_wn_stack_bwd_proj": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int64, _P, c_int64, c_int, c_int, c_int, c_int, c_int,
+                                      c_int64, c_void_p]),
     "fst_wn_wgrad_ok": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "fst_wn_wgrad_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "fst_wn_wgrad_in": (c_int, [_P, _P, _P, c_int, c_int64, _P, _P, _P, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int64,
@@ -111,6 +113,8 @@ _SIGNATURES = {
     "fst_wn_bwd_image_bytes": (c_int64, [c_int, c_int]),
     "fst_wn_pack_bwd": (c_int, [_P, c_int, c_int, c_int, _P, c_int64, c_void_p]),
     "fst_wn_pack_bwd_stack": (c_int, [_P, c_int, c_int, c_int, _P, c_int64, c_void_p]),
+    "fst_wn_bwd_proj_image_bytes": (c_int64, [c_int, c_int, c_int]),
+    "fst_wn_pack_bwd_proj_stack": (c_int, [_P, _P, c_int, c_int, c_int, _P, c_int64, c_void_p]),
     "fst_wn_layer_bwd": (c_int, [_P, _P, _P, _P, c_int64, _P, _P, c_int64, c_int, c_int, c_int, c_int, c_int64, c_void_p]),
     "fst_wn_dgrad_image_bytes": (c_int64, [c_int]),
     "fst_wn_pack_dgrad": (c_int, [_P, _P, c_int, c_int, c_int, _P, c_int64, c_void_p]),

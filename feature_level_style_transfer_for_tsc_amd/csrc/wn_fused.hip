@@ -900,6 +900,89 @@ extern "C" int fst_wn_pack_bwd_stack(const float* const* rs_w, int nl, int n, in
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The projected image of fst_wn_stack_bwd_proj: d_out = W_endᵀ·do is a rank-2h image of the end conv's cotangent do [B][2h][L],
+// so the skip half of GEMM 3 is  W_skip,iᵀ·d_out = (W_end·W_skip,i)ᵀ·do  and the kernel multiplies do itself: 2h operand rows
+// instead of n, CHO = ceil(2h/16) stages instead of CH.  Per layer [d_a stages: CH, acc_order][skip stages: CHO] (the top layer:
+// skip stages only), then 16 B of zeros.  Skip stage c: lane l holds F_i[16c + 8(l>>5) + j][blk·32 + (l&31)], F_i = W_end·W_skip,i
+// ([2h][n]; rows >= 2h and columns >= n are zero) — every element one fp32 fmaf chain over k = 0..n-1, then the hi/lo split.
+// ------------------------------------------------------------------------------------------------
+struct WnPackBwdProjParams {
+  const float* rs_w[WS_MAXL];
+  uint4* img[WS_MAXL];
+  const float* end_w;  // [2h][n]
+  int n, h2, nl, CH, CHO;
+};
+
+__global__ __launch_bounds__(64) void wn_pack_bwd_proj_stack_kernel(WnPackBwdProjParams s) {
+  const int i = blockIdx.y, last = i == s.nl - 1 ? 1 : 0, n_da = last ? 0 : s.CH, n_blocks = (n_da + s.CHO) * 4;
+  const int bx = blockIdx.x;
+  if (bx >= n_blocks) return;
+  if ((bx >> 2) < n_da) {                              // a d_a stage: what fst_wn_pack_bwd (acc_order = 1) writes there
+    const WnPackBwdParams p = {s.rs_w[i], s.n, 0, s.CH, s.img[i], 1};
+    wn_pack_bwd_body(p, bx, n_blocks);
+    return;
+  }
+  const int lane = threadIdx.x, blk = bx & 3, c = (bx >> 2) - n_da;
+  const int n = s.n, m = blk * 32 + (lane & 31), hh = lane >> 5;
+  const float* const w_skip = s.rs_w[i] + (long long)(last ? 0 : n) * n;       // [n][n]: skip channel k, acts channel m
+  // the stage's 16 rows of W_end, rows >= h2 as zeros: every lane then runs the same chain of independent loads
+  __shared__ float e_rows[16 * 128];
+  for (int x = lane; x < 16 * n; x += 64) {
+    const int r = x / n, k = x - r * n;
+    e_rows[r * 128 + k] = 16 * c + r < s.h2 ? s.end_w[(long long)(16 * c + r) * n + k] : 0.f;
+  }
+  __syncthreads();
+  float v[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = 0.f;
+  if (m < n) {
+#pragma unroll 8
+    for (int k = 0; k < n; ++k) {                        // one fmaf chain per element, k ascending
+      const float w = w_skip[(long long)k * n + m];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = fmaf(e_rows[(8 * hh + j) * 128 + k], w, v[j]);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j)
+    if (16 * c + 8 * hh + j >= s.h2) v[j] = 0.f;         // dead rows are zeros whatever the weights hold
+  unsigned hi[4], lo[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) split_bf16_pair(v[2 * j], v[2 * j + 1], hi[j], lo[j]);
+  uint4* dst = s.img[i] + ((long long)(bx >> 2) * 4 + blk) * 128 + lane;
+  dst[0] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
+  dst[64] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+  if (bx == 0 && lane == 0) s.img[i][(long long)n_blocks * 128] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+extern "C" int64_t fst_wn_bwd_proj_image_bytes(int n, int h2, int last) {
+  if (n <= 0 || h2 <= 0) return -1;
+  return (int64_t)((last ? 0 : wn_ch(n)) + wn_ch(h2)) * WN_BW_A + 16;
+}
+
+// images[i] of fst_wn_bwd_proj_image_bytes(n, h2, i == nl - 1) bytes: image_bytes is that of the layers below the top one
+extern "C" int fst_wn_pack_bwd_proj_stack(const float* const* rs_w, const float* end_w, int nl, int n, int h2, void* const* images,
+                                          int64_t image_bytes, void* stream) {
+  FST_REQUIRE(rs_w && end_w && images && n > 0 && n <= 128 && h2 > 0 && h2 <= 64,
+              "fst_wn_pack_bwd_proj_stack: bad arguments (n=%d, h2=%d; needs n <= 128, h2 <= 64)", n, h2);
+  FST_REQUIRE(nl >= 1 && nl <= WS_MAXL, "fst_wn_pack_bwd_proj_stack: %d layers (1..%d)", nl, WS_MAXL);
+  FST_REQUIRE(image_bytes == fst_wn_bwd_proj_image_bytes(n, h2, 0), "fst_wn_pack_bwd_proj_stack: images are %lld bytes, expected %lld",
+              (long long)image_bytes, (long long)fst_wn_bwd_proj_image_bytes(n, h2, 0));
+  WnPackBwdProjParams s = {};
+  for (int i = 0; i < nl; ++i) {
+    FST_REQUIRE(rs_w[i] && images[i], "fst_wn_pack_bwd_proj_stack: null operand in layer %d", i);
+    FST_REQUIRE(fst_aligned16(images[i]), "fst_wn_pack_bwd_proj_stack: images must be 16-byte aligned");
+    s.rs_w[i] = rs_w[i];
+    s.img[i] = static_cast<uint4*>(images[i]);
+  }
+  s.end_w = end_w; s.n = n; s.h2 = h2; s.nl = nl; s.CH = wn_ch(n); s.CHO = wn_ch(h2);
+  const int stages = (nl > 1 ? s.CH : 0) + s.CHO;
+  hipLaunchKernelGGL(wn_pack_bwd_proj_stack_kernel, dim3((unsigned)(stages * 4), (unsigned)nl), dim3(64), 0, (hipStream_t)stream, s);
+  FST_LAUNCH_CHECK();
+  return 0;
+}
+
 struct WnBwdParams {
   const float* d_a;    // [B][n][L], null on the last layer
   const float* d_out;  // [B][n][L]
@@ -1456,9 +1539,15 @@ __device__ __forceinline__ void ws_row_sums(const float (&v)[16], float* rows_w,
 // scratch tensor that is rewritten layer after layer.
 //
 // Phase A runs as TWO column passes (the wave's two 32-sample column blocks one after the other): d_a occupies 128 registers,
-// so the dacts accumulators get 64 (4 row blocks × 1 column block).  Per pass: the d_out stages (operand through the LDS-DMA
-// ring; they depend on nothing the previous phase stored, so the first two are issued under its last stores), then the d_a
-// stages (weights through the ring, the operand from the accumulators), then the gate on four tiles.  Phase B = the body of
+// so the dacts accumulators get 64 (4 row blocks × 1 column block).  Per pass: the skip stages (the operand straight from
+// memory in fragment layout, the weights from the layer's resident image), then the d_a stages (the operand from the
+// accumulators), then the gate on four tiles.
+//
+// The skip operand is d_out [B][n][L] against W_skip,iᵀ (fst_wn_stack_bwd: SR = n rows, SCH = CH stages) or — the form
+// GradNorm's partial passes run — the end conv's cotangent do [B][2h][L] against (W_end·W_skip,i)ᵀ (fst_wn_stack_bwd_proj, images of
+// fst_wn_pack_bwd_proj_stack: SR = 2h, SCH = ceil(2h/16)): d_out = W_endᵀ·do has rank 2h, so every wave re-reading its n-channel
+// slice of it in every layer moved n/2h times the bytes the result needs (62.9 vs 26.2 MB per layer at n = 120, h = 25, B = 256,
+// L = 512), and the pass took CH MFMA stages where ceil(2h/16) do.  One kernel, two row / stage counts in its arguments.  Phase B = the body of
 // wn_layer_dgrad_kernel.  Global stores of one phase (dg, d_u0) are read by the next through LDS-DMA / loads of the SAME
 // workgroup: s_waitcnt vmcnt(0) by every wave + a workgroup barrier orders them (one CU, one L1).
 // ------------------------------------------------------------------------------------------------
@@ -1476,11 +1565,12 @@ struct WnStackParams {
   float* da_out[WS_MAXL];        // cotangent of the layer's input [B][n][L]: written when not null (layer 0: always)
   float* rs_b[WS_MAXL];          // optional [256][B]: per-sequence Σ_t dg[row]
   float* rs_d[WS_MAXL];          // optional [128][B]: per-sequence Σ_t da_out[row]
-  const float* d_out;            // [B][n][L]
+  const float* d_out;            // the skip operand [B][SR][L]: d_out (SR = n), or the end conv's cotangent do (SR = 2h: the projected form)
   float* d_u0;                   // [B][h][L] with batch stride d_u0_bs, accumulated in place
   long long d_u0_bs;
   int dil[WS_MAXL], nblkw[WS_MAXL], gsw[WS_MAXL], slot_d[WS_MAXL];
   int nl, B, L, n, h, CH, CHK;
+  int SR, SCH;                   // rows of the skip operand and its stages in the image: n, CH — or 2h, ceil(2h/16) (fst_wn_pack_bwd_proj_stack)
 };
 
 __global__ __launch_bounds__(512, 2) void wn_stack_bwd_kernel(WnStackParams p_by_value) {
@@ -1503,9 +1593,9 @@ __global__ __launch_bounds__(512, 2) void wn_stack_bwd_kernel(WnStackParams p_by
   const unsigned vlane = (unsigned)(4 * half * L + l31) * 4u;
   const WsLane wl0 = ws_lane(vlane, wave_n0, L, lane), wl1 = ws_lane(vlane, wave_n0 + 32, L, lane);
 
-  // layer i's W_rsᵀ image ([d_a stages][d_out stages]; the top layer: d_out stages only): one 1-KiB piece per wave and stage
+  // layer i's W_rsᵀ image ([d_a stages][skip stages]; the top layer: skip stages only): one 1-KiB piece per wave and stage
   auto issue_res = [&](int i) {
-    const int S3 = (i == p.nl - 1 ? 1 : 2) * CH;
+    const int S3 = (i == p.nl - 1 ? 0 : CH) + p.SCH;
     const char* const img = p.img_b[i];
     for (int c = 0; c < S3; ++c)
       lds_dma16(img + (long long)c * WN_BW_A + wave_s * 1024 + lane * 16, ldsb + c * WN_BW_A + wave_s * 1024);
@@ -1535,7 +1625,7 @@ __global__ __launch_bounds__(512, 2) void wn_stack_bwd_kernel(WnStackParams p_by
         const __amdgpu_buffer_rsrc_t ts_s = ws_rsrc(p.ts[i] + ((long long)b * 2 + 1) * n * L);
         const __amdgpu_buffer_rsrc_t dg_t = ws_rsrc(p.dg[i] + (long long)b * (2 * n) * L);
         const __amdgpu_buffer_rsrc_t dg_s = ws_rsrc(p.dg[i] + ((long long)b * 2 + 1) * n * L);
-        const __amdgpu_buffer_rsrc_t dout_r = ws_rsrc(p.d_out + (long long)b * n * L);
+        const __amdgpu_buffer_rsrc_t dout_r = ws_rsrc(p.d_out + (long long)b * p.SR * L);
         float* const rs_out = p.rs_b[i];
         FST_T(ta0);
         if (!primed) issue_res(i);
@@ -1559,11 +1649,11 @@ __global__ __launch_bounds__(512, 2) void wn_stack_bwd_kernel(WnStackParams p_by
 #pragma unroll
             for (int r = 0; r < 16; ++r) da[mb][r] = 0.f;
           FST_T(tp0);
-          // ---- the d_out stages: the operand comes straight from memory in fragment layout (eight dword loads per stage: lane
-          // half hh reads channels 8hh + j at its column), the next stage's in flight while one is multiplied — no ring, no barrier
+          // ---- the skip stages (d_out, or do against the projected image): the operand comes straight from memory in fragment
+          // layout (eight dword loads per stage: lane half hh reads channels 8hh + j at its column), the next stage's in flight while one is multiplied — no ring, no barrier
           const unsigned vf = tcol + l31 < L ? vfrag : WS_OOB, vf_lo = half == 0 ? vf : WS_OOB;
           auto load_dout = [&](float (&v)[8], int c) {
-            const int Lq = ws_opaque(L), nq = ws_opaque(n);
+            const int Lq = ws_opaque(L), nq = ws_opaque(p.SR);
             const int sbase = (16 * c * Lq + tcol) * 4;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
@@ -1575,11 +1665,12 @@ __global__ __launch_bounds__(512, 2) void wn_stack_bwd_kernel(WnStackParams p_by
           };
           float vn[8];
           load_dout(vn, 0);
-          for (int k = 0; k < CH; ++k) {
+          const int SCH = p.SCH;
+          for (int k = 0; k < SCH; ++k) {
             float v[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = vn[j];
-            if (k + 1 < CH) load_dout(vn, k + 1);
+            if (k + 1 < SCH) load_dout(vn, k + 1);
             bf16x8 bh, bl;
             split_bf16x8(v, bh, bl);
             wn_bwd_multiply(da, w_dout + k * WN_BW_A, lane, bh, bl);
@@ -1722,24 +1813,25 @@ extern "C" int fst_wn_stack_bwd_ok(int n, int h, int L, int nl) {
   return 1;
 }
 
-extern "C" int fst_wn_stack_bwd(const float* const* ts, const void* const* img_b, const void* const* img_d, float* const* dg,
-                                float* const* da_out, float* const* rs_b, float* const* rs_d, const float* d_out, float* d_u0,
-                                int64_t d_u0_bs, int nl, int B, int L, int n, int h, int64_t numel_a, void* stream) {
-  fst_wn_clear_route();
-  FST_REQUIRE(ts && img_b && img_d && dg && da_out && d_out && d_u0, "fst_wn_stack_bwd: null table");
-  FST_REQUIRE(fst_wn_stack_bwd_ok(n, h, L, nl), "fst_wn_stack_bwd: not served: n=%d h=%d L=%d nl=%d (needs n <= 128, h <= 32, "
-              "L <= 512, L %% 4 == 0, nl <= %d)", n, h, L, nl, WS_MAXL);
+// the launch behind fst_wn_stack_bwd (skip = d_out: rows = n) and fst_wn_stack_bwd_proj (skip = do: rows = 2h)
+static int wn_stack_bwd_launch(const char* who, const float* const* ts, const void* const* img_b, const void* const* img_d,
+                               float* const* dg, float* const* da_out, float* const* rs_b, float* const* rs_d, const float* skip,
+                               int skip_rows, float* d_u0, int64_t d_u0_bs, int nl, int B, int L, int n, int h, int64_t numel_a,
+                               void* stream) {
+  FST_REQUIRE(ts && img_b && img_d && dg && da_out && skip && d_u0, "%s: null table", who);
+  FST_REQUIRE(fst_wn_stack_bwd_ok(n, h, L, nl), "%s: not served: n=%d h=%d L=%d nl=%d (needs n <= 128, h <= 32, "
+              "L <= 512, L %% 4 == 0, nl <= %d)", who, n, h, L, nl, WS_MAXL);
   FST_REQUIRE(B > 0 && (long long)B * n * L == (long long)numel_a,
-              "fst_wn_stack_bwd: B*n*L does not match the element count %lld of the [B][n][L] tensors", (long long)numel_a);
+              "%s: B*n*L does not match the element count %lld of the [B][n][L] tensors", who, (long long)numel_a);
   FST_REQUIRE(d_u0_bs >= (int64_t)h * L && d_u0_bs % 4 == 0,
-              "fst_wn_stack_bwd: d_u0 batch stride %lld (needs >= h*L = %lld and a multiple of 4)", (long long)d_u0_bs, (long long)h * L);
-  FST_REQUIRE((rs_b == nullptr) == (rs_d == nullptr), "fst_wn_stack_bwd: row sums of both kinds or of neither");
+              "%s: d_u0 batch stride %lld (needs >= h*L = %lld and a multiple of 4)", who, (long long)d_u0_bs, (long long)h * L);
+  FST_REQUIRE((rs_b == nullptr) == (rs_d == nullptr), "%s: row sums of both kinds or of neither", who);
   WnStackParams p = {};
   size_t lds_bytes = WS_LDS_A + 8192;                                // phase A: the weight image and the row-sum arrays
   for (int i = 0; i < nl; ++i) {
-    FST_REQUIRE(ts[i] && img_b[i] && img_d[i] && dg[i] && (i > 0 || da_out[i]), "fst_wn_stack_bwd: null operand of layer %d", i);
+    FST_REQUIRE(ts[i] && img_b[i] && img_d[i] && dg[i] && (i > 0 || da_out[i]), "%s: null operand of layer %d", who, i);
     FST_REQUIRE(fst_aligned16(ts[i]) && fst_aligned16(img_b[i]) && fst_aligned16(img_d[i]) && fst_aligned16(dg[i]) && fst_aligned16(da_out[i]),
-                "fst_wn_stack_bwd: operands of layer %d must be 16-byte aligned", i);
+                "%s: operands of layer %d must be 16-byte aligned", who, i);
     p.ts[i] = ts[i]; p.img_b[i] = static_cast<const char*>(img_b[i]); p.img_d[i] = static_cast<const char*>(img_d[i]);
     p.dg[i] = dg[i]; p.da_out[i] = da_out[i];
     p.rs_b[i] = rs_b ? rs_b[i] : nullptr; p.rs_d[i] = rs_d ? rs_d[i] : nullptr;
@@ -1747,15 +1839,39 @@ extern "C" int fst_wn_stack_bwd(const float* const* ts, const void* const* img_b
     wn_dgrad_geometry(p.dil[i], &p.nblkw[i], &p.gsw[i], &p.slot_d[i]);
     if ((size_t)2 * p.slot_d[i] > lds_bytes) lds_bytes = (size_t)2 * p.slot_d[i];
   }
-  FST_REQUIRE(fst_aligned16(d_out) && fst_aligned16(d_u0), "fst_wn_stack_bwd: d_out / d_u0 must be 16-byte aligned");
-  FST_REQUIRE(lds_bytes <= 160 * 1024, "fst_wn_stack_bwd: %zu bytes of LDS", lds_bytes);
-  p.d_out = d_out; p.d_u0 = d_u0; p.d_u0_bs = d_u0_bs;
+  FST_REQUIRE(fst_aligned16(skip) && fst_aligned16(d_u0), "%s: %s / d_u0 must be 16-byte aligned", who, skip_rows == n ? "d_out" : "d_o");
+  FST_REQUIRE(lds_bytes <= 160 * 1024, "%s: %zu bytes of LDS", who, lds_bytes);
+  p.d_out = skip; p.d_u0 = d_u0; p.d_u0_bs = d_u0_bs;
   p.nl = nl; p.B = B; p.L = L; p.n = n; p.h = h; p.CH = wn_ch(n); p.CHK = (2 * n + 15) / 16;
-  if (int rc = fst_allow_full_lds((const void*)wn_stack_bwd_kernel, "fst_wn_stack_bwd")) return rc;
+  p.SR = skip_rows; p.SCH = wn_ch(skip_rows);
+  FST_REQUIRE((size_t)(p.CH + p.SCH) * WN_BW_A <= WS_LDS_A, "%s: a weight image of %d stages does not fit its LDS", who, p.CH + p.SCH);
+  if (int rc = fst_allow_full_lds((const void*)wn_stack_bwd_kernel, who)) return rc;
   const int cus = fst_cu_count_or(256);
   const int grid = B < cus ? B : cus;                    // one resident workgroup per CU walks its batch elements
   fst_wn_set_route(FST_WN_ROUTE_STACK_BWD, 0, 0, 0, 0, grid, 1, 1, 1, 2, nl, (int)lds_bytes);
   hipLaunchKernelGGL(wn_stack_bwd_kernel, dim3((unsigned)grid), dim3(512), lds_bytes, (hipStream_t)stream, p);
   FST_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int fst_wn_stack_bwd(const float* const* ts, const void* const* img_b, const void* const* img_d, float* const* dg,
+                                float* const* da_out, float* const* rs_b, float* const* rs_d, const float* d_out, float* d_u0,
+                                int64_t d_u0_bs, int nl, int B, int L, int n, int h, int64_t numel_a, void* stream) {
+  fst_wn_clear_route();
+  return wn_stack_bwd_launch("fst_wn_stack_bwd", ts, img_b, img_d, dg, da_out, rs_b, rs_d, d_out, n, d_u0, d_u0_bs, nl, B, L, n, h,
+                             numel_a, stream);
+}
+
+// The same launch on the end conv's cotangent: d_o [B][h2][L] in place of d_out = W_endᵀ·d_o, img_b the images of
+// fst_wn_pack_bwd_proj_stack (skip stages = (W_end·W_skip,i)ᵀ).  numel_o = element count of d_o as the caller holds it.
+extern "C" int fst_wn_stack_bwd_proj(const float* const* ts, const void* const* img_b, const void* const* img_d, float* const* dg,
+                                     float* const* da_out, float* const* rs_b, float* const* rs_d, const float* d_o, int h2,
+                                     int64_t numel_o, float* d_u0, int64_t d_u0_bs, int nl, int B, int L, int n, int h,
+                                     int64_t numel_a, void* stream) {
+  fst_wn_clear_route();
+  FST_REQUIRE(h2 > 0 && h2 <= 64, "fst_wn_stack_bwd_proj: h2=%d (needs 0 < h2 <= 64)", h2);
+  FST_REQUIRE(B > 0 && L > 0 && (long long)B * h2 * L == (long long)numel_o,
+              "fst_wn_stack_bwd_proj: B*h2*L does not match the element count %lld of d_o [B][h2][L]", (long long)numel_o);
+  return wn_stack_bwd_launch("fst_wn_stack_bwd_proj", ts, img_b, img_d, dg, da_out, rs_b, rs_d, d_o, h2, d_u0, d_u0_bs, nl, B, L, n, h,
+                             numel_a, stream);
 }

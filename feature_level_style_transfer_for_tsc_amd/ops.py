@@ -1394,6 +1394,31 @@ def wn_pack_bwd_layers(rs_ws: Sequence[Tensor], n: int, acc_order: bool = False)
                        lambda i, img: (img, rs_ws[i], src[i]))
 
 
+def wn_pack_bwd_proj_layers(rs_ws: Sequence[Tensor], end_w: Tensor, n: int) -> List[Tensor]:
+    """The images of ``wn_stack_bwd`` on the end conv's cotangent (fst_wn_pack_bwd_proj_stack, one launch per stack): layer i's
+    d_a stages in accumulator order, then (W_end·W_skip,i)ᵀ as its skip stages.  Cached per layer under the versions of both
+    weights (they are fixed for a step: the same images serve every backward pass of it)."""
+    lib, nl, h2 = _lib.load(), len(rs_ws), end_w.size(0)
+    if nl > WN_PACK_MAX_LAYERS or tuple(end_w.shape) != (h2, n, 1) or h2 > 64:
+        raise ValueError(f"wn_pack_bwd_proj_layers: {nl} layers, end_w {tuple(end_w.shape)} (at most {WN_PACK_MAX_LAYERS} layers, "
+                         f"end_w [2h <= 64, n = {n}, 1])")
+    keys = [("wn_bwd_proj", n, h2, i == nl - 1, w.data_ptr(), w._version, end_w.data_ptr(), end_w._version)
+            for i, w in enumerate(rs_ws)]
+    if _PACK_CACHE is not None:
+        hits = [_PACK_CACHE.get(k) for k in keys]
+        if all(hit is not None for hit in hits):
+            return [hit[0] for hit in hits]
+    src, end_c = [w.contiguous() for w in rs_ws], end_w.contiguous()
+    imgs = [torch.empty(lib.fst_wn_bwd_proj_image_bytes(n, h2, int(i == nl - 1)) // 4, device=end_w.device, dtype=torch.float32)
+            for i in range(nl)]
+    check(lib.fst_wn_pack_bwd_proj_stack(_ptr_table(src), ptr(end_c), nl, n, h2, _ptr_table(imgs),
+                                         lib.fst_wn_bwd_proj_image_bytes(n, h2, 0), stream_ptr()), "fst_wn_pack_bwd_proj_stack")
+    if _PACK_CACHE is not None:
+        for i, (k, img) in enumerate(zip(keys, imgs)):
+            _PACK_CACHE[k] = (img, rs_ws[i], src[i], end_w, end_c)
+    return imgs
+
+
 def wn_pack_dgrad_layers(in_ws: Sequence[Tensor], cond_ws: Sequence[Tensor], n: int, h: int) -> List[Tensor]:
     """``wn_pack_dgrad`` for every layer of a stack in one launch (fst_wn_pack_dgrad_stack)."""
     lib, nl = _lib.load(), len(in_ws)
@@ -1549,6 +1574,18 @@ def wn_layer_dgrad(dg: Tensor, img: Tensor, d_a: Optional[Tensor], d_u0: Tensor,
     return d_a_new, part.sum(dim=1)[:n]
 
 
+def wn_skip_proj_ok(h: int, need_w: bool) -> bool:
+    """Whether the one-launch stack backward takes its skip cotangent from BEFORE the end conv (``wn_stack_bwd(..., do=...)``): the
+    end conv's cotangent do [B, 2h, L] against (W_end·W_skip,i)ᵀ instead of d_out = W_endᵀ·do [B, n, L] against W_skip,iᵀ.
+    By default inside ``partial_backward()`` (GradNorm's partial passes: gradient norms are all they produce), which then never
+    form d_out.  Every other pass keeps the d_out form, whether or not it wants weight gradients (``needs_input_grad`` removes
+    outputs, it never changes the ones that remain): a pass with weight gradients forms d_out anyway, and its gradients feed the
+    optimisers, whose normalised updates turn a rounding-level change of a near-zero gradient into a full-size change of the
+    weight — so the weights stay bit for bit what the d_out form gives.  FST_WN_SKIP_PROJ (diagnostics): "0" = never, "2" = always."""
+    mode = os.environ.get("FST_WN_SKIP_PROJ", "1")
+    return 2 * h <= 64 and (mode == "2" or (mode != "0" and _PARTIAL_BACKWARD and not need_w))
+
+
 def wn_stack_bwd_ok(n: int, h: int, L: int, nl: int) -> bool:
     """Whether the whole backward of a WN stack runs as ONE persistent launch (fst_wn_stack_bwd: sequences of up to 512 samples —
     a 512-sample tile is then the whole sequence and one workgroup walks every layer of its batch element)."""
@@ -1599,18 +1636,30 @@ def _ptr_table(ts: Sequence[Optional[Tensor]]):
 
 
 def wn_stack_bwd(ts_list: Sequence[Tensor], imgs_b: Sequence[Tensor], imgs_d: Sequence[Tensor], dgs: Sequence[Tensor],
-                 da_out: Sequence[Optional[Tensor]], d_out: Tensor, d_u0: Tensor, n: int, h: int,
-                 part_b: Optional[Tensor] = None, part_d: Optional[Tensor] = None) -> None:
+                 da_out: Sequence[Optional[Tensor]], d_out: Optional[Tensor], d_u0: Tensor, n: int, h: int,
+                 part_b: Optional[Tensor] = None, part_d: Optional[Tensor] = None, do: Optional[Tensor] = None) -> None:
     """Layers nl-1 .. 0 of a WN stack's backward in one launch (csrc/wn_fused.hip, fst_wn_stack_bwd): per layer
     dg = gate'(t, s)·W_rsᵀ·[d_a ; d_out],  d_a += W_inᵀ (*) dg,  d_u0 += W_condᵀ·dg, the residual cotangent d_a staying in the
     accumulators from layer to layer.  ``imgs_b``: ``wn_pack_bwd(..., acc_order=True)``.  ``da_out[i]`` (the cotangent of layer i's
     input) is written where a tensor is given — ``da_out[0]`` always; the rest are the res_skip weight gradients' operands.
     ``dgs`` entries may alias one scratch tensor when nothing reads dg afterwards (GradNorm's partial passes).  ``part_b``
-    [nl, 256, B] / ``part_d`` [nl, 128, B]: per-sequence row sums of dg / da_out (the bias gradients), both or neither."""
+    [nl, 256, B] / ``part_d`` [nl, 128, B]: per-sequence row sums of dg / da_out (the bias gradients), both or neither.
+    ``do`` (then ``d_out`` is None): the projected form, fst_wn_stack_bwd_proj — the end conv's cotangent [B, 2h, L] takes the
+    place of d_out = W_endᵀ·do and ``imgs_b`` is ``wn_pack_bwd_proj_layers``' (skip stages (W_end·W_skip,i)ᵀ)."""
     lib = _lib.load()
     nl = len(ts_list)
-    B, _, L = d_out.shape
-    numel = _same_numel(d_out, *[t for t in da_out if t is not None])
+    if (do is None) == (d_out is None):
+        raise ValueError("wn_stack_bwd: d_out or do, one of them")
+    if do is not None:
+        if do.dim() != 3 or not do.is_contiguous() or do.dtype != torch.float32:
+            raise ValueError("wn_stack_bwd: do must be a contiguous fp32 [B, 2h, L]")
+        B, h2, L = do.shape
+        numel = _same_numel(*[t for t in da_out if t is not None])
+        if numel != B * n * L:
+            raise ValueError(f"wn_stack_bwd: da_out must be [B, n, L] = {(B, n, L)}")
+    else:
+        B, _, L = d_out.shape
+        numel = _same_numel(d_out, *[t for t in da_out if t is not None])
     for t in list(ts_list) + list(dgs):
         if t.numel() != 2 * numel or not t.is_contiguous():
             raise ValueError("wn_stack_bwd: ts / dg must be contiguous [B, 2n, L]")
@@ -1625,14 +1674,21 @@ def wn_stack_bwd(ts_list: Sequence[Tensor], imgs_b: Sequence[Tensor], imgs_d: Se
     t0 = KERNEL_TIMER.begin() if KERNEL_TIMER is not None else None
     rs_b = None if part_b is None else _ptr_table([part_b[i] for i in range(nl)])
     rs_d = None if part_d is None else _ptr_table([part_d[i] for i in range(nl)])
-    check(lib.fst_wn_stack_bwd(_ptr_table(ts_list), _ptr_table(imgs_b), _ptr_table(imgs_d), _ptr_table(dgs), _ptr_table(da_out),
-                               rs_b, rs_d, ptr(d_out), ptr(d_u0), d_u0_bs, nl, B, L, n, h, numel, stream_ptr()),
-          "fst_wn_stack_bwd")
+    if do is not None:
+        check(lib.fst_wn_stack_bwd_proj(_ptr_table(ts_list), _ptr_table(imgs_b), _ptr_table(imgs_d), _ptr_table(dgs),
+                                        _ptr_table(da_out), rs_b, rs_d, ptr(do), h2, do.numel(), ptr(d_u0), d_u0_bs, nl, B, L, n, h,
+                                        numel, stream_ptr()), "fst_wn_stack_bwd_proj")
+    else:
+        check(lib.fst_wn_stack_bwd(_ptr_table(ts_list), _ptr_table(imgs_b), _ptr_table(imgs_d), _ptr_table(dgs), _ptr_table(da_out),
+                                   rs_b, rs_d, ptr(d_out), ptr(d_u0), d_u0_bs, nl, B, L, n, h, numel, stream_ptr()),
+              "fst_wn_stack_bwd")
     if t0 is not None:
-        # per layer: GEMM 3 (K = 2n, n on the top layer) + the data gradient.  Algorithmic bytes (every operand once): t,s and
-        # d_out read, dg written and read back, d_u0 in/out, plus every d_a tensor that is written
-        flops = 2.0 * B * L * (n * (2 * n * nl - n) + nl * 2 * n * (3 * n + h))
-        rows = nl * (2 * n + n + 2 * 2 * n + 2 * h) + n * sum(t is not None for t in da_out)
+        # per layer: GEMM 3 (K = n + the skip operand's rows; those alone on the top layer) + the data gradient.  Algorithmic bytes
+        # (every operand once): t,s and the skip operand (d_out: n rows, do: 2h) read, dg written and read back, d_u0 in/out, plus
+        # every d_a tensor that is written
+        sr = n if do is None else h2
+        flops = 2.0 * B * L * (n * ((n + sr) * nl - n) + nl * 2 * n * (3 * n + h))
+        rows = nl * (2 * n + sr + 2 * 2 * n + 2 * h) + n * sum(t is not None for t in da_out)
         KERNEL_TIMER.end("wn_stack_bwd_kernel", t0, flops, 4.0 * B * L * rows)
 
 
@@ -1714,7 +1770,10 @@ def _wn_backward(S: WNSpecs, fused: bool, sv, do: Tensor, d_u0: Tensor, need_w: 
     G = S.unflatten(d_flat) if need_w else None
     do = do.contiguous()
 
-    d_out = S.end.grad_x0(do, W[4])
+    stack = fused and all(wn_dgrad_ok(n, h, 2 ** i) for i in range(nl)) and wn_stack_bwd_ok(n, h, L, nl)
+    proj = stack and wn_skip_proj_ok(h, need_w)         # the stack backward multiplies do itself: (W_end·W_skip,i)ᵀ·do
+    # d_out = W_endᵀ·do: the skip cotangent of every layer; in the projected form only the weight gradients read it
+    d_out = None if proj and not need_w else S.end.grad_x0(do, W[4])
     da_sums = None
     if need_w:
         S.end.grad_w(out, None, do, out0=G[4])
@@ -1731,8 +1790,8 @@ def _wn_backward(S: WNSpecs, fused: bool, sv, do: Tensor, d_u0: Tensor, need_w: 
     part_b = part_d = None         # per-workgroup row sums of dg / of d_a that fused launches leave for ONE reduction per kind
     if not fused:
         d_a = _wn_backward_unfused(S, W, G, a_list, ts_list, acts_list, u0, d_out, d_u0, da_sums)
-    elif all(wn_dgrad_ok(n, h, 2 ** i) for i in range(nl)) and wn_stack_bwd_ok(n, h, L, nl):
-        d_a, part_b, part_d = _wn_backward_stack(S, W, G, a_list, ts_list, u0, d_out, d_u0, pool)
+    elif stack:
+        d_a, part_b, part_d = _wn_backward_stack(S, W, G, a_list, ts_list, u0, d_out, d_u0, pool, do if proj else None)
     else:
         d_a, part_b, part_d = _wn_backward_layers(S, W, G, a_list, ts_list, u0, d_out, d_u0, da_sums, pool)
     S.start.grad_x0(d_a, W[0], out=d_u0, flags=EPI_ACC1)
@@ -1778,22 +1837,26 @@ def _wn_wgrad_in(S: WNSpecs, i: int, dg: Tensor, a: Tensor, u0: Tensor, G, pool)
         S.ins[i].grad_w(a, u0, dg, out0=g_in_w, out1=g_cond_w)
 
 
-def _wn_backward_stack(S: WNSpecs, W, G, a_list, ts_list, u0: Tensor, d_out: Tensor, d_u0: Tensor, pool):
+def _wn_backward_stack(S: WNSpecs, W, G, a_list, ts_list, u0: Tensor, d_out: Optional[Tensor], d_u0: Tensor, pool,
+                       do: Optional[Tensor] = None):
     """Every layer in ONE persistent launch.  With weight gradients (``G``) each layer's dg and d_a are kept (their operands);
     without (GradNorm's partial passes), one dg and one d_a scratch tensor are rewritten layer after layer.
+    ``do``: the projected form — the launch reads the end conv's cotangent in place of ``d_out``, which then only the res_skip
+    weight gradients need (``G``; None in a partial pass).
     Returns (the cotangent of layer 0's input, part_b, part_d)."""
     nl, n, h = S.n_layers, S.n, S.h
-    B, _, L = d_out.shape
-    imgs_b = wn_pack_bwd_layers([_wn_layer(S, W, i)[4] for i in range(nl)], n, acc_order=True)
+    B, _, L = u0.shape
+    rs_ws = [_wn_layer(S, W, i)[4] for i in range(nl)]
+    imgs_b = wn_pack_bwd_layers(rs_ws, n, acc_order=True) if do is None else wn_pack_bwd_proj_layers(rs_ws, W[4], n)
     imgs_d = wn_pack_dgrad_layers([_wn_layer(S, W, i)[0] for i in range(nl)], [_wn_layer(S, W, i)[1] for i in range(nl)], n, h)
-    new = lambda *shape: torch.empty(*shape, device=d_out.device, dtype=torch.float32)
+    new = lambda *shape: torch.empty(*shape, device=u0.device, dtype=torch.float32)
     if G is None:
         dgs, da_out = [new(B, 2 * n, L)] * nl, [new(B, n, L)] + [None] * (nl - 1)    # only layer 0's d_a leaves the kernel
         part_b = part_d = None
     else:
         dgs, da_out = [new(B, 2 * n, L) for _ in range(nl)], [new(B, n, L) for _ in range(nl)]
         part_b, part_d = new(nl, 256, B), new(nl, 128, B)
-    wn_stack_bwd(ts_list, imgs_b, imgs_d, dgs, da_out, d_out, d_u0, n, h, part_b, part_d)
+    wn_stack_bwd(ts_list, imgs_b, imgs_d, dgs, da_out, d_out if do is None else None, d_u0, n, h, part_b, part_d, do)
     if G is not None:
         for i in range(nl):
             _wn_wgrad_rs(S, i, da_out[i + 1] if i + 1 < nl else None, d_out, ts_list[i], G, pool)

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FST_ABI_VERSION 18
+#define FST_ABI_VERSION 19
 
 int fst_version(void);
 const char* fst_last_error(void);
@@ -285,6 +285,13 @@ int fst_wn_pack_bwd_stack(const float* const* rs_w, int nl, int n, int acc_order
                           void* stream);
 int fst_wn_pack_dgrad_stack(const float* const* in_w, const float* const* cond_w, int nl, int n, int h, int ntaps,
                             void* const* images, int64_t image_bytes, void* stream);
+/* The images of fst_wn_stack_bwd_proj (ABI v19), one launch per stack: per layer [d_a stages as fst_wn_pack_bwd with acc_order = 1]
+ * [skip stages: F_iᵀ, F_i = W_end·W_skip,i ([h2][n]), ceil(h2/16) of them] (the top layer: skip stages only), then 16 B of zeros.
+ * end_w [h2][n] is the end conv's weight, h2 <= 64.  Every F_i element is one fp32 fmaf chain over the n products in index order,
+ * then the hi/lo split: no atomics, two runs give the same bytes.  image_bytes: that of a layer below the top one. */
+int64_t fst_wn_bwd_proj_image_bytes(int n, int h2, int last);
+int fst_wn_pack_bwd_proj_stack(const float* const* rs_w, const float* end_w, int nl, int n, int h2, void* const* images,
+                               int64_t image_bytes, void* stream);
 int fst_wn_layer_fwd(const float* a, int64_t a_bs, const float* u0, int64_t u0_bs, const void* image, int64_t image_bytes,
                      float* ts, float* acts, float* a_next, float* out, int first, int last,
                      int B, int L, int n, int h, int dil, int64_t numel_a, void* stream);
@@ -350,6 +357,13 @@ int fst_wn_stack_bwd(const float* const* ts, const void* const* img_b, const voi
                      float* const* da_out, float* const* rs_b /* optional */, float* const* rs_d /* optional */,
                      const float* d_out, float* d_u0, int64_t d_u0_bs, int nl, int B, int L, int n, int h, int64_t numel_a,
                      void* stream);
+/* The same launch fed with the end conv's cotangent d_o [B][h2][L] (h2 = 2h <= 64; numel_o its element count) in place of
+ * d_out = W_endᵀ·d_o: by associativity W_skip,iᵀ·d_out = (W_end·W_skip,i)ᵀ·d_o, and img_b[i] (fst_wn_pack_bwd_proj_stack) holds that
+ * product, so the skip operand has h2 rows and ceil(h2/16) stages instead of n and ceil(n/16).  Everything else as above. */
+int fst_wn_stack_bwd_proj(const float* const* ts, const void* const* img_b, const void* const* img_d, float* const* dg,
+                          float* const* da_out, float* const* rs_b /* optional */, float* const* rs_d /* optional */,
+                          const float* d_o, int h2, int64_t numel_o, float* d_u0, int64_t d_u0_bs, int nl, int B, int L, int n,
+                          int h, int64_t numel_a, void* stream);
 
 /* Weight gradients of the same layer (the gradients autograd derives for Simplified_NF_WaveGlow.py:107-116), time as the MFMA
  * reduction index, split-bf16 products, per-workgroup partial slabs added in a fixed order (deterministic, no atomics):

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Diagnostics: the backward of one WN stack (n=120, h=25, 8 layers) at the bench shape, as one persistent launch
-(fst_wn_stack_bwd) against one launch pair per layer; without weight gradients (GradNorm's partial passes) and with the
+(fst_wn_stack_bwd; its skip operand d_out, FST_WN_SKIP_PROJ=0, or the end conv's cotangent in every pass, =2: fst_wn_stack_bwd_proj;
+the default, =1, takes the latter in the partial passes only) against one
+launch pair per layer; without weight gradients (GradNorm's partial passes) and with the
 operands of the weight gradients kept (the full pass; the weight-gradient kernels themselves are not timed here)."""
 import os
 import sys
@@ -22,8 +24,8 @@ flat = S.flatten(ws).requires_grad_(True)
 x = torch.randn(B, 2 * h, L, device=dev)
 do = torch.randn(B, 2 * h, L, device=dev)
 reps = int(os.environ.get("WS_REPS", 10))
-for mode in ("0", "1"):
-    os.environ["FST_WN_STACK"] = mode
+for mode, proj in (("0", "0"), ("1", "0"), ("1", "2")):
+    os.environ["FST_WN_STACK"], os.environ["FST_WN_SKIP_PROJ"] = mode, proj
     with ops.pack_cache():
         u0 = x[:, :h].detach().requires_grad_(True)
         o = ops.WNFn.apply(S, u0, flat)
@@ -46,5 +48,5 @@ for mode in ("0", "1"):
                 run()
             e1.record()
             torch.cuda.synchronize()
-            print(f"FST_WN_STACK={mode} {'partial (no weight gradients)' if partial else 'full data path (operands kept)  '}: "
+            print(f"FST_WN_STACK={mode} FST_WN_SKIP_PROJ={proj} {'partial (no weight gradients)' if partial else 'full data path (operands kept)  '}: "
                   f"{e0.elapsed_time(e1) * 1e3 / reps:9.1f} us per stack backward = {e0.elapsed_time(e1) * 1e3 / reps / nl:7.1f} us per layer", flush=True)
