@@ -12,7 +12,7 @@ from typing import Optional
 
 import torch
 
-ABI_VERSION = 19
+ABI_VERSION = 20
 _LIB_NAME = "libfst_hip.so"
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FST_HIP_LIB", os.path.join(_HERE, _LIB_NAME))     # override: diagnostic builds only
@@ -69,6 +69,7 @@ _SIGNATURES = {
     "fst_guard_copy_multi": (c_int, [_P, _P, _P, c_int, _I32P, c_int, c_void_p]),
     "fst_wn_stack_fwd_ok": (c_int, [c_int, c_int, c_int, c_int]),
     "fst_wn_stack_fwd": (c_int, [_P, _P, _P, c_int64, _P, _P, _P, c_int64, _P, c_int, c_int, c_int, c_int, c_int, c_int64, c_void_p]),
+    "fst_wn_stack_infer": (c_int, [_P, _P, _P, c_int64, _P, _P, c_int64, _P, c_int, c_int, c_int, c_int, c_int, c_int64, c_void_p]),
     "fst_wn_stack_bwd_ok": (c_int, [c_int, c_int, c_int, c_int]),
     "fst_wn_stack_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int, c_int, c_int, c_int, c_int, c_int64, c_void_p]),
     "fst_wn_stack_bwd_proj": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int64, _P, c_int64, c_int, c_int, c_int, c_int, c_int,
@@ -110,6 +111,8 @@ _SIGNATURES = {
     "fst_wn_pack_stack": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, c_int64, c_void_p]),
     "fst_wn_layer_fwd": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int,
                                  c_int, c_int64, c_void_p]),
+    "fst_wn_layer_infer": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                   c_int64, c_void_p]),
     "fst_wn_bwd_image_bytes": (c_int64, [c_int, c_int]),
     "fst_wn_pack_bwd": (c_int, [_P, c_int, c_int, c_int, _P, c_int64, c_void_p]),
     "fst_wn_pack_bwd_stack": (c_int, [_P, c_int, c_int, c_int, _P, c_int64, c_void_p]),

@@ -405,7 +405,9 @@ __device__ __forceinline__ void wn_tile_row_sums(const float* tile, float* rows,
 // (the arguments stay in the kernel-argument segment — constant address space: scalar loads at the point of use, rematerialised
 // rather than kept in registers — for the per-layer kernel and for the persistent one alike)
 typedef const __attribute__((address_space(4))) WnFwdParams WnFwdArgs;
-template <int NW>
+// SAVE = false: the tile of a pass that no backward follows (wn_layer_infer_kernel / wn_stack_infer_kernel) — the gate block stores
+// neither t,s nor acts (p.ts / p.acts are null and never touched); every other instruction is the saving tile's, in the same order
+template <int NW, bool SAVE = true>
 __device__ __forceinline__ void wn_fwd_tile(WnFwdArgs& p, const int b, const int t0, char* const ldsb) {
   constexpr int F_TN = 32 * NW, F_NBLK = F_TN / 32 + 1, F_GS = F_NBLK * 1024 + 128, F_SLOT = WN_A_BYTES + 2 * F_GS;
   constexpr int NA = WN_A_BYTES / 1024;              // 16 one-KiB pieces of A per stage
@@ -574,13 +576,16 @@ __device__ __forceinline__ void wn_fwd_tile(WnFwdArgs& p, const int b, const int
   // the t,s stores below are OLDER than every LDS-DMA a counted vmcnt will wait for — a counted wait retires
   // everything older than what it waits for, i.e. the stores get two k-steps of MFMA time to complete before the wait
   // in front of k-step S1+2 can see them.
+  // (SAVE = false: there are no such stores.  The counts of wait_for stand — a counted wait names how many of the NEWEST operations,
+  // the LDS-DMA pieces of the k-step issued last, may still fly; the t,s stores were older than every piece a counted wait is placed
+  // behind, as the a / out operand loads of the gate still are, so they never entered a count.)
   wait_vmcnt<0>();
   __builtin_amdgcn_s_barrier();                        // every wave is past its last B read: the B areas are free
   const int tcol = t0 + wave_n0;
   // accumulator-layout global accesses as raw buffer instructions: one descriptor per matrix of this batch element, ONE per-lane
   // offset, row / column terms in the scalar offset (no 64-bit per-lane addresses, no exec masks: see ws_acc_load)
   const WsLane wl = ws_lane((unsigned)(4 * half * L + l31) * 4u, tcol, L, lane);
-  const __amdgpu_buffer_rsrc_t ts_rs = ws_rsrc(p.ts + (long long)b * (2 * n) * L);
+  const __amdgpu_buffer_rsrc_t ts_rs = ws_rsrc(SAVE ? p.ts + (long long)b * (2 * n) * L : nullptr);
   const __amdgpu_buffer_rsrc_t a_rs = ws_rsrc(ab), out_rs = ws_rsrc(p.out + (long long)b * n * L);
   const __amdgpu_buffer_rsrc_t an_rs = ws_rsrc(p.a_next ? p.a_next + (long long)b * n * L : p.out);
   bf16x8 bh2[8], bl2[8];
@@ -596,13 +601,23 @@ __device__ __forceinline__ void wn_fwd_tile(WnFwdArgs& p, const int b, const int
       av[r] = row == n ? 1.0f : tv[r] * sv[r];         // acts[n] = 1 carries b_rs through GEMM 2 (rows > n: tanh(0)·σ(0) = 0)
     }
     const int rows_valid = n - blk * 32;               // may be <= 0: nothing stored
-    ws_acc_store(tv, ts_rs, wl, blk * 32, tcol, rows_valid, L);
-    ws_acc_store(sv, ts_rs, wl, n + blk * 32, tcol, rows_valid, L);
-    if (p.acts) {
-      float aw[16];
+    if constexpr (SAVE) {
+      ws_acc_store(tv, ts_rs, wl, blk * 32, tcol, rows_valid, L);
+      ws_acc_store(sv, ts_rs, wl, n + blk * 32, tcol, rows_valid, L);
+      if (p.acts) {
+        float aw[16];
 #pragma unroll
-      for (int r = 0; r < 16; ++r) aw[r] = tv[r] * sv[r];
-      wn_acc_store(aw, p.acts + ((long long)b * n + blk * 32) * L, rows_valid, L, tcol, lane);
+        for (int r = 0; r < 16; ++r) aw[r] = tv[r] * sv[r];
+        wn_acc_store(aw, p.acts + ((long long)b * n + blk * 32) * L, rows_valid, L, tcol, lane);
+      }
+    } else {
+      // The stores also pinned this block's gate in front of the operand loads below: they consume tv / sv here.  Without them
+      // nothing uses the gate's result before GEMM 2, the compiler sinks the tanh / sigmoid chains of all four blocks behind the
+      // loads, and the loads land in fresh registers beside accumulators that still hold the gate's input: 300-430 spilled
+      // VGPRs and 204 bytes of scratch in the first build.  An empty volatile statement per value keeps the order (volatile
+      // statements are not reordered among themselves, and ws_acc_load starts with one); it emits no instruction.
+#pragma unroll
+      for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(av[r]));
     }
     // GEMM 2 accumulates onto what its rows are added to — the layer input for the residual rows (a_next = a + r), the
     // running skip sum for the skip rows (out += r) — read here, in accumulator layout, into the two accumulators the
@@ -720,6 +735,42 @@ __global__ __launch_bounds__(512, 1) void wn_stack_fwd_kernel(WnFwdStackParams p
   }
 }
 
+// The same two kernels for a pass that no backward follows: wn_fwd_tile<NW, false> — no t,s / acts stores, a_next and out bit for bit
+// the saving kernels'.  Same workgroup → tile map, same persistent loop (a_next of layer i may be the buffer layer i − 1 read: every
+// tile of a layer is stored and waited for — vmcnt(0) + barrier — before this workgroup starts the next layer, and no other
+// workgroup touches this batch element).
+template <int NW>
+__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void wn_layer_infer_kernel(WnFwdParams p) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  int wg = blockIdx.x;
+  if ((p.n_wg & 7) == 0) wg = (wg & 7) * (p.n_wg >> 3) + (wg >> 3);
+  const int b = wg / p.tiles_per_seq;
+  const int t0 = (wg - b * p.tiles_per_seq) * (32 * NW);
+  wn_fwd_tile<NW, false>(*(WnFwdArgs*)__builtin_amdgcn_kernarg_segment_ptr(), b, t0, reinterpret_cast<char*>(lds));
+}
+
+__global__ __launch_bounds__(512, 1) void wn_stack_infer_kernel(WnFwdStackParams ps_by_value) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  typedef const __attribute__((address_space(4))) WnFwdStackParams StackArgs;
+  StackArgs& ps = *(StackArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+  (void)ps_by_value;
+  char* const ldsb = reinterpret_cast<char*>(lds);
+  const int B = ps.layer[0].B, passes = ps.layer[0].tiles_per_seq;
+  for (int b = blockIdx.x; b < B; b += gridDim.x) {
+    for (int layer = 0; layer < ps.nl; ++layer) {
+      for (int pass = 0; pass < passes; ++pass) {
+        WnFwdArgs* qp = &ps.layer[layer];
+        asm volatile("" : "+s"(qp));                       // (opaque, as in wn_stack_fwd_kernel)
+        wn_fwd_tile<8, false>(*qp, b, pass * 256, ldsb);
+        // this tile's stores (a_next, out) are complete and every wave is past its LDS reads before the next tile's LDS-DMA
+        // refills the ring and reads what was stored
+        wait_vmcnt<0>();
+        __syncthreads();
+      }
+    }
+  }
+}
+
 extern "C" int fst_wn_stack_fwd_ok(int n, int h, int L, int nl) {
   return n > 0 && n < 128 && h > 0 && L > 0 && L % 256 == 0 && nl >= 1 && nl <= WS_MAXL;
 }
@@ -793,6 +844,84 @@ extern "C" int fst_wn_layer_fwd(const float* a, int64_t a_bs, const float* u0, i
     if (int rc = fst_allow_full_lds((const void*)wn_layer_fwd_kernel<4>, "fst_wn_layer_fwd")) return rc;
     fst_wn_set_route(FST_WN_ROUTE_LAYER_FWD, 4, 0, 0, 0, p.n_wg, 1, 1, p.tiles_per_seq, 3, 1, WN_FWD_LDS(4));
     hipLaunchKernelGGL(wn_layer_fwd_kernel<4>, dim3((unsigned)p.n_wg), dim3(256), WN_FWD_LDS(4), (hipStream_t)stream, p);
+  }
+  FST_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fst_wn_stack_infer(const float* const* a_in, const int64_t* a_bs, const void* const* images, int64_t image_bytes,
+                                  float* const* a_next, const float* u0, int64_t u0_bs, float* out, int nl, int B, int L, int n, int h,
+                                  int64_t numel_a, void* stream) {
+  fst_wn_clear_route();
+  FST_REQUIRE(a_in && a_bs && images && a_next && u0 && out, "fst_wn_stack_infer: null operand");
+  FST_REQUIRE(fst_wn_stack_fwd_ok(n, h, L, nl) && B > 0, "fst_wn_stack_infer: B=%d L=%d n=%d h=%d nl=%d (needs n < 128, L %% 256 == 0, "
+              "1 <= nl <= %d)", B, L, n, h, nl, WS_MAXL);
+  FST_REQUIRE((long long)B * n * L == (long long)numel_a, "fst_wn_stack_infer: B*n*L = %d*%d*%d does not match the element count %lld "
+              "of the [B, n, L] tensors", B, n, L, (long long)numel_a);
+  FST_REQUIRE(image_bytes == fst_wn_image_bytes(n, h), "fst_wn_stack_infer: images are %lld bytes, expected %lld",
+              (long long)image_bytes, (long long)fst_wn_image_bytes(n, h));
+  FST_REQUIRE(B == 1 || u0_bs >= (int64_t)h * L, "fst_wn_stack_infer: batch stride of u0 smaller than a sample");
+  FST_REQUIRE(u0_bs % 4 == 0 && fst_aligned16(u0) && fst_aligned16(out), "fst_wn_stack_infer: needs 16-byte aligned tensors");
+  WnFwdStackParams p = {};
+  for (int i = 0; i < nl; ++i) {
+    FST_REQUIRE(a_in[i] && images[i] && (a_next[i] || i == nl - 1), "fst_wn_stack_infer: null operand of layer %d", i);
+    FST_REQUIRE(a_bs[i] >= (int64_t)n * L && a_bs[i] % 4 == 0 && fst_aligned16(a_in[i]) && fst_aligned16(images[i]) && fst_aligned16(a_next[i]),
+                "fst_wn_stack_infer: layer %d: batch stride %lld smaller than a sample, or an operand that is not 16-byte aligned", i,
+                (long long)a_bs[i]);
+    FST_REQUIRE(i == nl - 1 || a_in[i + 1] == a_next[i], "fst_wn_stack_infer: the input of layer %d is not the a_next of layer %d",
+                i + 1, i);
+    // (a_next[i] == a_in[i - 1] is fine: the two-buffer alternation — see wn_stack_infer_kernel)
+    FST_REQUIRE(i == nl - 1 || a_next[i] != a_in[i], "fst_wn_stack_infer: layer %d would store a_next over the input its neighbouring "
+                "tiles still read", i);
+    WnFwdParams& q = p.layer[i];
+    q.a = a_in[i]; q.a_bs = a_bs[i]; q.u0 = u0; q.u0_bs = u0_bs; q.img = static_cast<const char*>(images[i]);
+    q.ts = nullptr; q.acts = nullptr; q.a_next = i == nl - 1 ? nullptr : a_next[i]; q.out = out;
+    q.B = B; q.L = L; q.n = n; q.h = h; q.dil = 1 << i; q.first = i == 0; q.last = i == nl - 1;
+    q.CH = wn_ch(n); q.CH2 = wn_ch2(h); q.tiles_per_seq = L / 256; q.n_wg = 0;
+  }
+  p.nl = nl;
+  const int cus = fst_cu_count_or(256);
+  if (int rc = fst_allow_full_lds((const void*)wn_stack_infer_kernel, "fst_wn_stack_infer")) return rc;
+  fst_wn_set_route(FST_WN_ROUTE_STACK_INFER, 8, 0, 0, 0, B < cus ? B : cus, 1, 1, L / 256, 3, nl, WN_FWD_LDS(8));
+  hipLaunchKernelGGL(wn_stack_infer_kernel, dim3((unsigned)(B < cus ? B : cus)), dim3(512), WN_FWD_LDS(8), (hipStream_t)stream, p);
+  FST_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fst_wn_layer_infer(const float* a, int64_t a_bs, const float* u0, int64_t u0_bs, const void* image,
+                                  int64_t image_bytes, float* a_next, float* out, int first, int last, int B, int L, int n, int h,
+                                  int dil, int64_t numel_a, void* stream) {
+  fst_wn_clear_route();
+  FST_REQUIRE(a && u0 && image && out && (last || a_next), "fst_wn_layer_infer: null operand");
+  FST_REQUIRE(B > 0 && L > 0 && n > 0 && n < 128 && h > 0 && dil > 0, "fst_wn_layer_infer: B=%d L=%d n=%d h=%d dil=%d (needs n < 128)",
+              B, L, n, h, dil);
+  FST_REQUIRE((long long)B * n * L == (long long)numel_a, "fst_wn_layer_infer: B*n*L = %d*%d*%d does not match the element count %lld "
+              "of the [B, n, L] tensors", B, n, L, (long long)numel_a);
+  FST_REQUIRE(image_bytes == fst_wn_image_bytes(n, h), "fst_wn_layer_infer: image is %lld bytes, expected %lld",
+              (long long)image_bytes, (long long)fst_wn_image_bytes(n, h));
+  FST_REQUIRE(B == 1 || (a_bs >= (int64_t)n * L && u0_bs >= (int64_t)h * L), "fst_wn_layer_infer: batch stride smaller than a sample");
+  FST_REQUIRE(L % 4 == 0 && a_bs % 4 == 0 && u0_bs % 4 == 0 && fst_aligned16(a) && fst_aligned16(u0) && fst_aligned16(image) &&
+              fst_aligned16(a_next) && fst_aligned16(out), "fst_wn_layer_infer: needs L %% 4 == 0 and 16-byte aligned tensors (L=%d)", L);
+  FST_REQUIRE(last || a_next != a, "fst_wn_layer_infer: a_next is a — a tile's neighbours read a's halo while the tile stores a_next");
+  WnFwdParams p;
+  p.a = a; p.a_bs = a_bs; p.u0 = u0; p.u0_bs = u0_bs; p.img = static_cast<const char*>(image);
+  p.ts = nullptr; p.acts = nullptr; p.a_next = last ? nullptr : a_next; p.out = out;
+  p.B = B; p.L = L; p.n = n; p.h = h; p.dil = dil; p.first = first ? 1 : 0; p.last = last ? 1 : 0;
+  p.CH = wn_ch(n); p.CH2 = wn_ch2(h);
+  // the tile-size choice of fst_wn_layer_fwd
+  const int cus = fst_cu_count_or(256);
+  const int nw = (L % 256 == 0 && (long long)B * (L / 256) >= cus) ? 8 : 4;
+  const int tn = 32 * nw;
+  p.tiles_per_seq = (L + tn - 1) / tn;
+  p.n_wg = B * p.tiles_per_seq;
+  if (nw == 8) {
+    if (int rc = fst_allow_full_lds((const void*)wn_layer_infer_kernel<8>, "fst_wn_layer_infer")) return rc;
+    fst_wn_set_route(FST_WN_ROUTE_LAYER_INFER, 8, 0, 0, 0, p.n_wg, 1, 1, p.tiles_per_seq, 3, 1, WN_FWD_LDS(8));
+    hipLaunchKernelGGL(wn_layer_infer_kernel<8>, dim3((unsigned)p.n_wg), dim3(512), WN_FWD_LDS(8), (hipStream_t)stream, p);
+  } else {
+    if (int rc = fst_allow_full_lds((const void*)wn_layer_infer_kernel<4>, "fst_wn_layer_infer")) return rc;
+    fst_wn_set_route(FST_WN_ROUTE_LAYER_INFER, 4, 0, 0, 0, p.n_wg, 1, 1, p.tiles_per_seq, 3, 1, WN_FWD_LDS(4));
+    hipLaunchKernelGGL(wn_layer_infer_kernel<4>, dim3((unsigned)p.n_wg), dim3(256), WN_FWD_LDS(4), (hipStream_t)stream, p);
   }
   FST_LAUNCH_CHECK();
   return 0;

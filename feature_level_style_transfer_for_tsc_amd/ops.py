@@ -79,10 +79,12 @@ def last_route() -> Tuple[int, ...]:
 
 WN_ROUTE_WGRAD, WN_ROUTE_TZ, WN_ROUTE_LAYER_FWD, WN_ROUTE_STACK_FWD, WN_ROUTE_LAYER_BWD, WN_ROUTE_LAYER_DGRAD, WN_ROUTE_STACK_BWD = \
     1, 2, 3, 4, 5, 6, 7                                                                              # FST_WN_ROUTE_* of fst_hip.h
+WN_ROUTE_LAYER_INFER, WN_ROUTE_STACK_INFER = 8, 9
 WN_ROUTE_LEN = 12
 _WN_ROUTE_NAMES = {WN_ROUTE_WGRAD: "wn_wgrad_kernel", WN_ROUTE_TZ: "tz_wgrad_kernel", WN_ROUTE_LAYER_FWD: "wn_layer_fwd_kernel",
                    WN_ROUTE_STACK_FWD: "wn_stack_fwd_kernel", WN_ROUTE_LAYER_BWD: "wn_layer_bwd_kernel",
-                   WN_ROUTE_LAYER_DGRAD: "wn_layer_dgrad_kernel", WN_ROUTE_STACK_BWD: "wn_stack_bwd_kernel"}
+                   WN_ROUTE_LAYER_DGRAD: "wn_layer_dgrad_kernel", WN_ROUTE_STACK_BWD: "wn_stack_bwd_kernel",
+                   WN_ROUTE_LAYER_INFER: "wn_layer_infer_kernel", WN_ROUTE_STACK_INFER: "wn_stack_infer_kernel"}
 
 
 def wn_last_route() -> Tuple[int, ...]:
@@ -103,6 +105,8 @@ def wn_route_kernel_name(route: Sequence[int]) -> str:
         return f"tz_wgrad_kernel<{route[1]}, {tf[route[2]]}>"
     if fam == WN_ROUTE_LAYER_FWD:
         return f"wn_layer_fwd_kernel<{route[1]}>"
+    if fam == WN_ROUTE_LAYER_INFER:
+        return f"wn_layer_infer_kernel<{route[1]}>"
     return _WN_ROUTE_NAMES[fam]
 
 
@@ -1454,6 +1458,25 @@ def wn_layer_fwd(a: Tensor, u0: Tensor, img: Tensor, ts: Tensor, acts: Optional[
         KERNEL_TIMER.end("wn_layer_fwd_kernel", t0, flops, 4.0 * B * L * rows)
 
 
+def wn_layer_infer(a: Tensor, u0: Tensor, img: Tensor, a_next: Optional[Tensor], out: Tensor, first: bool, last: bool, n: int, h: int,
+                   dil: int) -> None:
+    """``wn_layer_fwd`` for a pass that no backward follows (fst_wn_layer_infer): neither the gate halves nor acts are stored;
+    ``a_next`` and ``out`` receive the same bits.  ``a_next`` must not be ``a``."""
+    lib = _lib.load()
+    a_bs, L = _ncl(a, "a")
+    u0_bs, _ = _ncl(u0, "u0")
+    B = a.size(0)
+    numel = _same_numel(a, out, a_next)
+    t0 = KERNEL_TIMER.begin() if KERNEL_TIMER is not None else None
+    check(lib.fst_wn_layer_infer(ptr(a), a_bs, ptr(u0), u0_bs, ptr(img), img.numel() * 4, ptr(a_next), ptr(out), int(first), int(last),
+                                 B, L, n, h, dil, numel, stream_ptr()), "fst_wn_layer_infer")
+    if t0 is not None:
+        rs_rows = n if last else 2 * n
+        flops = 2.0 * B * L * (2 * n * (3 * n + h) + rs_rows * n)
+        rows = n + h + (0 if first else n) + (0 if last else n) + n                   # a, u0, out in; a_next, out out — no t,s rows
+        KERNEL_TIMER.end("wn_layer_infer_kernel", t0, flops, 4.0 * B * L * rows)
+
+
 def wn_pack_bwd(rs_w: Tensor, n: int, last: bool, acc_order: bool = False) -> Tensor:
     """``acc_order``: the image of fst_wn_stack_bwd (the d_a stages in the k-order of an accumulator tile's rows)."""
     lib = _lib.load()
@@ -1628,6 +1651,25 @@ def wn_stack_fwd(a_list: Sequence[Tensor], u0: Tensor, imgs: Sequence[Tensor], t
         KERNEL_TIMER.end("wn_stack_fwd_kernel", t0, flops, 4.0 * B * L * rows)
 
 
+def wn_stack_infer(a_list: Sequence[Tensor], u0: Tensor, imgs: Sequence[Tensor], out: Tensor, n: int, h: int) -> None:
+    """``wn_stack_fwd`` for a pass that no backward follows (fst_wn_stack_infer): no gate halves are stored.  ``a_list[i]`` = input
+    of layer i, ``a_list[i + 1]`` written as its a_next — entries two apart may be the same tensor (two buffers in alternation),
+    neighbours may not."""
+    lib = _lib.load()
+    nl = len(imgs)
+    B, L = u0.size(0), u0.size(2)
+    u0_bs, _ = _ncl(u0, "u0")
+    numel = _same_numel(out, *a_list)
+    bs = (ctypes.c_int64 * nl)(*[_ncl(a, "a")[0] for a in a_list])
+    t0 = KERNEL_TIMER.begin() if KERNEL_TIMER is not None else None
+    check(lib.fst_wn_stack_infer(_ptr_table(a_list), bs, _ptr_table(imgs), imgs[0].numel() * 4, _ptr_table(list(a_list[1:]) + [None]),
+                                 ptr(u0), u0_bs, ptr(out), nl, B, L, n, h, numel, stream_ptr()), "fst_wn_stack_infer")
+    if t0 is not None:
+        flops = 2.0 * B * L * (nl * 2 * n * (3 * n + h) + (2 * nl - 1) * n * n)
+        rows = nl * (n + h) + (nl - 1) * (n + 2 * n) + n             # a, u0 in; a_next out, out in/out (first layer: out only) — no t,s rows
+        KERNEL_TIMER.end("wn_stack_infer_kernel", t0, flops, 4.0 * B * L * rows)
+
+
 def _ptr_table(ts: Sequence[Optional[Tensor]]):
     arr = (ctypes.c_void_p * len(ts))()
     for i, t in enumerate(ts):
@@ -1700,19 +1742,42 @@ def _wn_layer(S: WNSpecs, ts: Sequence[Tensor], i: int):
     return ts[6 + i], ts[2][rows], ts[6 + nl + i], ts[3][rows], ts[6 + 2 * nl + i], ts[6 + 3 * nl + i]
 
 
-def _wn_forward(specs: WNSpecs, u0: Tensor, flat: Tensor):
+def wn_infer_enabled() -> bool:
+    """FST_WN_INFER=0 (diagnostics, like FST_WN_STACK_FWD): a forward that no backward follows keeps the saving launches."""
+    return os.environ.get("FST_WN_INFER", "1") != "0"
+
+
+def _wn_forward(specs: WNSpecs, u0: Tensor, flat: Tensor, save: bool = True):
     """Forward of the WN stack (WNFn's docstring).  Returns (o, fused, the tensors ``_wn_backward`` needs).  Fused
     (``wn_fused_ok``): the gate halves ts = [tanh | sigmoid] of every layer are saved (also in the acts slots: one saved layout);
-    unfused: the gate input g and acts."""
+    unfused: the gate input g and acts.
+    ``save=False`` (no backward follows), fused path: the layers run on the kernels that store no gate halves, through two
+    [B, n, L] tensors in alternation — the same ``o``, and nothing to save: returns (o, True, ())."""
     S, nl, n, h = specs, specs.n_layers, specs.n, specs.h
     flat = flat.contiguous()
     W = S.unflatten(flat)
     B, _, L = u0.shape
     dev = u0.device
+    infer = not save and wn_infer_enabled()
     # the layer inputs are allocated with 16 bytes of slack either side: the time-as-k weight-gradient kernel reads the taps of
-    # dilation 1 and 2 through 16-byte pieces that start up to 3 samples outside a row
-    a = S.start.forward(u0, None, W[0], None, W[1], y=empty_with_slack(B, n, L, dev))
+    # dilation 1 and 2 through 16-byte pieces that start up to 3 samples outside a row.  (The forward's own staging stays inside a
+    # row — wn_fwd_tile's stage_src reads 16-byte aligned pieces of columns [0, L) only — so a forward that feeds no weight
+    # gradient allocates none.)
+    y0 = torch.empty(B, n, L, device=dev, dtype=torch.float32) if infer else empty_with_slack(B, n, L, dev)
+    a = S.start.forward(u0, None, W[0], None, W[1], y=y0)
     fused = wn_fused_ok(n, h, L, a, u0, kernel=S.kernel)
+    if fused and infer:
+        out = torch.empty(B, n, L, device=dev, dtype=torch.float32)
+        imgs = wn_pack_layers([_wn_layer(S, W, i) for i in range(nl)], n, h)
+        other = torch.empty_like(a) if nl > 1 else None
+        a_list = [a if i % 2 == 0 else other for i in range(nl)]
+        if wn_stack_fwd_ok(n, h, L, nl, B):
+            wn_stack_infer(a_list, u0, imgs, out, n, h)
+        else:
+            for i in range(nl):
+                last = i == nl - 1
+                wn_layer_infer(a_list[i], u0, imgs[i], None if last else a_list[i + 1], out, i == 0, last, n, h, 2 ** i)
+        return S.end.forward(out, None, W[4], None, W[5]), True, ()
     if fused:
         # per layer: dilated conv + cond rows → gate in registers → res_skip → residual / skip adds; acts = t·s is not written
         # (the res_skip weight gradient re-forms it from the saved halves while staging)
@@ -1942,13 +2007,17 @@ class WNFn(torch.autograd.Function):
     ``u0`` may be a channel-slice view of a wider tensor (explicit batch stride).
     ``flat``: the effective (weight-norm-folded) weights as one tensor in ``WNSpecs.shapes`` order — start_w, start_b,
     cond_w, cond_b, end_w, end_b, in_w[0..], in_b[0..], rs_w[0..], rs_b[0..] (``WNSpecs.flatten``).
+    When neither ``u0`` nor ``flat`` requires a gradient (``torch.no_grad()``, or frozen weights on a detached input) no backward
+    can follow: the layers run on the kernels that store no gate halves and nothing is kept (``_wn_forward(save=False)``).
     """
 
     @staticmethod
     def forward(ctx, specs: WNSpecs, u0: Tensor, flat: Tensor):
-        o, fused, saved = _wn_forward(specs, u0, flat)
+        # (grad mode is off inside a Function's forward: whether a backward can follow is what needs_input_grad says)
+        o, fused, saved = _wn_forward(specs, u0, flat, save=any(ctx.needs_input_grad))
         ctx.specs, ctx.fused = specs, fused
-        ctx.save_for_backward(*saved)
+        if saved:
+            ctx.save_for_backward(*saved)
         return o
 
     @staticmethod
@@ -2023,7 +2092,7 @@ class FlowFn(torch.autograd.Function):
         x = x.contiguous()
         h = specs.h
         assert x.size(1) == 2 * h
-        o, fused, saved = _wn_forward(specs, x[:, :h], flat)
+        o, fused, saved = _wn_forward(specs, x[:, :h], flat, save=any(ctx.needs_input_grad))
         B, C, L = x.shape
         if inverse:
             xn = torch.empty_like(x)
@@ -2034,7 +2103,8 @@ class FlowFn(torch.autograd.Function):
             xn, s_ls, s_sq = _coupling_forward(x, o)
             keep = x
         ctx.specs, ctx.fused, ctx.inverse = specs, fused, inverse
-        ctx.save_for_backward(keep, o, *saved)
+        if saved:
+            ctx.save_for_backward(keep, o, *saved)
         ctx.set_materialize_grads(False)
         return xn, o, s_ls, s_sq
 

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FST_ABI_VERSION 19
+#define FST_ABI_VERSION 20
 
 int fst_version(void);
 const char* fst_last_error(void);
@@ -340,6 +340,24 @@ int fst_wn_stack_fwd(const float* const* a_in, const int64_t* a_bs, const void* 
                      float* const* a_next, const float* u0, int64_t u0_bs, float* out, int nl, int B, int L, int n, int h,
                      int64_t numel_a, void* stream);
 
+/* The same two forwards for a pass that no backward follows (ABI v20) — the sampling / transfer direction WaveGlow.infer
+ * (Simplified_NF_WaveGlow.py:181-203), the feature dump of train_and_test.py:792-797, any forward under no_grad: the gate halves
+ * (t | s) and acts are not stored — half of a layer's store bytes, and the only tensors a pass keeps per layer.  Everything else of
+ * the tile body is the saving kernels', in the same order: a_next and out are bit for bit what fst_wn_layer_fwd / fst_wn_stack_fwd
+ * write (wn_layer_infer_kernel<NW>, wn_stack_infer_kernel: the same tile body with the stores compiled out).
+ *   fst_wn_layer_infer   the arguments, checks and tile-size choice of fst_wn_layer_fwd without ts and acts; a_next == a is
+ *                        refused (a tile's neighbours read a's halo while the tile stores a_next).
+ *   fst_wn_stack_infer   the tables of fst_wn_stack_fwd without ts, same shape rule (fst_wn_stack_fwd_ok).  a_in[i+1] == a_next[i]
+ *                        as there; a_next[i] == a_in[i] is refused; a_next[i] == a_in[i-1] is allowed — two buffers in
+ *                        alternation serve a stack of any depth (one workgroup walks every tile of a layer of its batch element
+ *                        before the next layer starts, and launches are stream-ordered). */
+int fst_wn_layer_infer(const float* a, int64_t a_bs, const float* u0, int64_t u0_bs, const void* image, int64_t image_bytes,
+                       float* a_next, float* out, int first, int last, int B, int L, int n, int h, int dil, int64_t numel_a,
+                       void* stream);
+int fst_wn_stack_infer(const float* const* a_in, const int64_t* a_bs, const void* const* images, int64_t image_bytes,
+                       float* const* a_next, const float* u0, int64_t u0_bs, float* out, int nl, int B, int L, int n, int h,
+                       int64_t numel_a, void* stream);
+
 /* The whole backward of a WN stack — fst_wn_layer_bwd and fst_wn_layer_dgrad of every layer, top layer first — as ONE persistent
  * launch (the backward autograd derives for the loop of Simplified_NF_WaveGlow.py:104-121), for sequences of up to 512 samples:
  * a 512-sample tile is then a whole sequence, the dilated taps never leave it, and one workgroup walks all layers of its batch
@@ -433,11 +451,13 @@ int fst_dense_tap_wgrad(const float* dy, const float* x, float* dw /* [M][C][K],
                         int B, int L, int M, int C, int K, int pad_left, int64_t numel_dy, int64_t numel_x, void* stream);
 
 /* The kernel instance the last call of the calling host thread to one of the launchers above launched — fst_wn_wgrad_in / _rs,
- * fst_nt_gemm, fst_tap_wgrad, fst_dense_tap_wgrad, fst_wn_layer_fwd / _bwd / _dgrad, fst_wn_stack_fwd / _bwd — recorded from the
+ * fst_nt_gemm, fst_tap_wgrad, fst_dense_tap_wgrad, fst_wn_layer_fwd / _infer / _bwd / _dgrad, fst_wn_stack_fwd / _infer / _bwd — recorded from the
  * values the launcher dispatched with (host side, thread-local; a call refused before its launch clears it):
  *   out[0]     family: FST_WN_ROUTE_WGRAD wn_wgrad_kernel<2, KT, FULL, MUL, NE>, FST_WN_ROUTE_TZ tz_wgrad_kernel<MP, FULL>,
  *              FST_WN_ROUTE_LAYER_FWD wn_layer_fwd_kernel<NW>, FST_WN_ROUTE_STACK_FWD wn_stack_fwd_kernel (8-wave tiles),
- *              FST_WN_ROUTE_LAYER_BWD, FST_WN_ROUTE_LAYER_DGRAD, FST_WN_ROUTE_STACK_BWD (no template arguments)
+ *              FST_WN_ROUTE_LAYER_BWD, FST_WN_ROUTE_LAYER_DGRAD, FST_WN_ROUTE_STACK_BWD (no template arguments),
+ *              FST_WN_ROUTE_LAYER_INFER wn_layer_infer_kernel<NW>, FST_WN_ROUTE_STACK_INFER wn_stack_infer_kernel (8-wave tiles):
+ *              the rest of their records is what the saving launch of the same shape records
  *   out[1..4]  the template arguments: KT, FULL, MUL, NE | MP, FULL | NW; unused ones 0 (bools as 0 / 1)
  *   out[5..7]  the grid: x = workgroups (weight gradients: the K split after the clamp; fused kernels: tiles, or the persistent
  *              grid), y = k-row / channel groups, z = row halves (tz); 1 where a dimension is not used
@@ -455,6 +475,8 @@ int fst_dense_tap_wgrad(const float* dy, const float* x, float* dw /* [M][C][K],
 #define FST_WN_ROUTE_LAYER_BWD   5
 #define FST_WN_ROUTE_LAYER_DGRAD 6
 #define FST_WN_ROUTE_STACK_BWD   7
+#define FST_WN_ROUTE_LAYER_INFER 8
+#define FST_WN_ROUTE_STACK_INFER 9
 int fst_wn_last_route(int32_t out[FST_WN_ROUTE_LEN]);
 
 /* NoiseTransfer (/root/reference/widgets.py:150-167): new_t = avg_t + r_t·mean_b(z_t), new_s likewise, dist = new_t − new_s,
