@@ -108,7 +108,7 @@ __device__ __forceinline__ void conv_epilogue_block(const ConvGemmParams& p, f32
             if (MODE == 2) {
               atomicAdd(dst + vo + nb * 32, v);
             } else {
-              if (p.flags & FST_EPI_RELU) v = fmaxf(v, 0.f);
+              if (p.flags & FST_EPI_RELU) v = v < 0.f ? 0.f : v;
               dst[vo + nb * 32] = v;
             }
           }
@@ -162,7 +162,7 @@ __device__ __forceinline__ void conv_epilogue_block_vec(const ConvGemmParams& p,
       if (MODE == 1) {
         o.x += ea[j].x + eb[j].x; o.y += ea[j].y + eb[j].y; o.z += ea[j].z + eb[j].z; o.w += ea[j].w + eb[j].w;
       }
-      if (p.flags & FST_EPI_RELU) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
+      if (p.flags & FST_EPI_RELU) { o.x = o.x < 0.f ? 0.f : o.x; o.y = o.y < 0.f ? 0.f : o.y; o.z = o.z < 0.f ? 0.f : o.z; o.w = o.w < 0.f ? 0.f : o.w; }
       *reinterpret_cast<float4*>(dst[j]) = o;
     }
   }
@@ -1400,9 +1400,11 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradParams p, const
   // VEC (narrow windows, every address 16-B aligned — checked on the host): 16-byte loads, 8 lanes per 32-sample
   // row.  dy: row = (tid>>3) + 32*i; windows: row = tid>>3.  12 load instructions per thread per tile instead of 48.
   const int vrow = tid >> 3, vcol = (tid & 7) * 4;
+  int fetched_tt0 = 0;                                   // first sample of the tile held in dy_st / x_st
   auto fetch = [&](int tile) {
     const int b = tile / p.tiles_per_seq;
     const int tt0 = (tile - b * p.tiles_per_seq) * TW;
+    fetched_tt0 = tt0;
     if (VEC) {
       const bool tv_ok = tt0 + vcol < L;
 #pragma unroll
@@ -1587,6 +1589,10 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradParams p, const
     __syncthreads();   // previous tile's readers are done
     commit();
     __syncthreads();
+    // The last tile of a sequence whose length is no multiple of TW: its dy columns tau >= nvalid are staged as zeros, but the x
+    // sample a tap with a negative shift pairs with them lies inside the sequence — a NaN or inf there would give 0·NaN in a tap
+    // that never reads it.  Such a tile (uniform; none when L % TW == 0) takes the x operand through a mask on tau.
+    const int nvalid = L - fetched_tt0;
     if (tile + 1 < tile_end) fetch(tile + 1);
 
     if (BF3) {
@@ -1600,6 +1606,14 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradParams p, const
         const float* ap = lds + roff + ks * 16 + 8 * half;
         bf16x8 ah, al;
         split_bf16x8(*reinterpret_cast<const float(*)[8]>(ap), ah, al);   // (the 8 floats in place: a local copy changes five instances' schedule)
+        if (nvalid < TW) {                                 // uniform: keep the first n of this lane's 8 samples, clear the bits of the rest
+          const int n = min(max(nvalid - (ks * 16 + 8 * half), 0), 8);
+          u32x4 m;
+#pragma unroll
+          for (int q = 0; q < 4; ++q) m[q] = n >= 2 * q + 2 ? 0xFFFFFFFFu : (n == 2 * q + 1 ? 0x0000FFFFu : 0u);
+          ah = __builtin_bit_cast(bf16x8, __builtin_bit_cast(u32x4, ah) & m);
+          al = __builtin_bit_cast(bf16x8, __builtin_bit_cast(u32x4, al) & m);
+        }
         const int boff = l31 * DYB + (ks * 16 + 8 * half) * 2;
 #pragma unroll
         for (int i = 0; i < WG_ITEMS; ++i)
@@ -1618,11 +1632,15 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradParams p, const
     const float* bbase = dyt + (wave * CB * 32 + l31) * DYS + half;
     // straight-line k-steps: padding items multiply the zero row instead of branching around their MFMAs (all
     // workgroups of a launch are co-resident, so the launch lasts as long as a full workgroup either way)
+    const bool ragged = nvalid < TW;
 #pragma unroll 2
     for (int tau = 0; tau < TW; tau += 2) {
       float av[WG_ITEMS], bv[CB];
 #pragma unroll
-      for (int i = 0; i < WG_ITEMS; ++i) av[i] = lds[rowoff[i] + tau + half];
+      for (int i = 0; i < WG_ITEMS; ++i) {
+        av[i] = lds[rowoff[i] + tau + half];
+        if (ragged && tau + half >= nvalid) av[i] = 0.f;
+      }
 #pragma unroll
       for (int cb = 0; cb < CB; ++cb) bv[cb] = bbase[cb * 32 * DYS + tau];
 #pragma unroll

@@ -40,7 +40,7 @@ struct GemmParams {
 };
 
 __device__ __forceinline__ float gm_act(float v, int act, float slope) {
-  if (act == FST_ACT_RELU) return v > 0.f ? v : 0.f;
+  if (act == FST_ACT_RELU) return v < 0.f ? 0.f : v;
   if (act == FST_ACT_LEAKY) return v > 0.f ? v : slope * v;
   return v;
 }

@@ -280,7 +280,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* y, const flo
   const long long base = (long long)bc * L;
   for (int t = threadIdx.x; t < L; t += 256) {
     float v = res ? bn_pre_join(y[base + t], sc, sh, res[base + t], rsc, rsh) : bn_pre(y[base + t], sc, sh);
-    if (relu) v = fmaxf(v, 0.f);
+    if (relu) v = v < 0.f ? 0.f : v;
     out[base + t] = v;
   }
 }
@@ -308,7 +308,7 @@ __global__ __launch_bounds__(256) void bn_apply_vec_kernel(const float* y, const
     } else {
       v.x = bn_pre(v.x, sc, sh); v.y = bn_pre(v.y, sc, sh); v.z = bn_pre(v.z, sc, sh); v.w = bn_pre(v.w, sc, sh);
     }
-    if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+    if (relu) { v.x = v.x < 0.f ? 0.f : v.x; v.y = v.y < 0.f ? 0.f : v.y; v.z = v.z < 0.f ? 0.f : v.z; v.w = v.w < 0.f ? 0.f : v.w; }
     o4[t] = v;
   }
 }

@@ -312,10 +312,10 @@ class JointTrainer:
         The verdict covers exactly what the update consumes: every ``.grad`` the step's optimisers read (after the data-parallel
         all-reduce), and in the joint step the ten GradNorm scalars (after ``mean_scalars``) and the two GradNorm weight
         gradients — all identical on every rank, so every rank decides alike.  Without a ``GradBucket`` the BatchNorm running
-        statistics and NoiseTransfer's sums as the forward pass left them decide as well, counted as the group "buffers": the
-        ReLU fused into BatchNorm maps NaN to 0, so a bad input can poison the statistics and leave every gradient finite.  With a
-        bucket those per-rank buffers stay out of the verdict (a rank deciding alone would part from the others) and such an
-        input is not caught.  The verdict is taken after ``on_grads_ready`` and before the
+        statistics and NoiseTransfer's sums as the forward pass left them decide as well, counted as the group "buffers" — a
+        second line: the fused ReLUs propagate NaN as torch's do, so a bad input reaches the gradients of whatever consumes the
+        features (in the "nf" phase, whose features are detached, the flow's).  With a bucket those per-rank buffers stay out of
+        the verdict (a rank deciding alone would part from the others).  The verdict is taken after ``on_grads_ready`` and before the
         first optimiser.  Parameters and RMSprop / Adam moments are guarded where they are written (``fst_*_multi_guard``, CPC's
         shared counter advances by ``ok``); what the forward pass and the tail of the update mutate in place (BatchNorm buffers,
         NoiseTransfer's sums, the omni-scale conv weights whose masked taps every forward zeroes again (Q1), the GradNorm weights
@@ -396,8 +396,8 @@ class JointTrainer:
                     xs.append(p.grad); gs.append(G.index(k))
         if self.bucket is None:
             # One process: what the forward pass has already written into the state (BatchNorm running statistics, NoiseTransfer's
-            # sums) decides too, as the group "buffers" — a NaN input that a fused ReLU turns into 0 (fmaxf) reaches the running
-            # statistics and no gradient.  With a GradBucket these buffers are per-rank values and stay out: ranks must decide alike.
+            # sums) decides too, as the group "buffers" — a second line behind the gradients, which a NaN input reaches now that the
+            # fused ReLUs propagate it.  With a GradBucket these buffers are per-rank values and stay out: ranks must decide alike.
             xs += list(self._guard_fwd); gs += [G.index("buffers")] * len(self._guard_fwd)
         xs += list(gradnorm); gs += [G.index("gradnorm")] * len(gradnorm)
         xs += list(losses); gs += [G.index("losses")] * len(losses)

@@ -443,9 +443,10 @@ def test_phase_capture_and_replay_with_the_guard(phase):
     # the eager phase step takes the same decision
     before = on.snapshot()
     rep = on.phase_step(phase, *poisoned(args, 0, NAN), t_samples=ts)
-    # "nf" detaches the features and the ReLU fused into BatchNorm maps NaN to 0: no gradient sees it, fe_t's running statistics do
-    hit = "buffers" if phase == "nf" else "fe_t"
-    assert int(rep["skipped"]) == 1 and counts_of(rep)[hit] > 0 and counts_of(rep)["gradnorm"] == 0
+    # "nf" detaches the features, so fe_t has no gradient — but its fused ReLUs hand the NaN on as torch's do: the flow's own
+    # gradients see it, and so do fe_t's running statistics (the second line, without a GradBucket)
+    hit = ("buffers", "nf") if phase == "nf" else ("fe_t",)
+    assert int(rep["skipped"]) == 1 and all(counts_of(rep)[k] > 0 for k in hit) and counts_of(rep)["gradnorm"] == 0
     unchanged(before["t"], on.snapshot()["t"], f"eager {phase}")
 
 
@@ -475,6 +476,17 @@ def _worker_guard_rccl(rank, world, port, q):
     except AssertionError as e:
         out["checks"] = str(e)
     out["skipped"] = int(on.skipped_steps)
+    # With a bucket the forward-written buffers stay out of the verdict ("buffers" == 0): a NaN sample is caught through the
+    # gradients alone, also in the "nf" phase, whose features are detached — the fused ReLUs do not turn it into 0.
+    try:
+        for what, run in (("nf", lambda b: on.phase_step("nf", *b, t_samples=ts)), ("joint", lambda b: on.step(*b, epoch=0, t_samples=ts))):
+            before = on.snapshot()
+            rep = run(poisoned(args, 0, NAN))
+            assert int(rep["skipped"]) == 1 and counts_of(rep)["buffers"] == 0, f"eager {what} step on a NaN sample: {counts_of(rep)}"
+            unchanged(before["t"], on.snapshot()["t"], f"eager {what} step, one RCCL rank")
+        out["eager"] = None
+    except AssertionError as e:
+        out["eager"] = str(e)
     q.put((0, out))
     dist.destroy_process_group()
 
@@ -493,6 +505,7 @@ def test_data_parallel_capture_keeps_the_guard_on_one_rccl_rank():
     assert out["graphs"] == (3, 3), out
     assert out["checks"] is None, out["checks"]
     assert out["skipped"] == 1
+    assert out["eager"] is None, out["eager"]
 
 
 # ---------------------------------------------------------------------------------------------- 6. the real tensor count

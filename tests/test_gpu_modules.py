@@ -485,10 +485,9 @@ def test_device_loader_pinned_async_copies():
     assert n == 32 and len(sh) == 4
 
 
-def test_inference_mode_folds_batchnorm_into_the_convs():
-    """Eval mode with autograd off (the eval pass and the K-way voting forward): every conv → BatchNorm (→ residual add
-    → ReLU) runs as ONE launch with the normalisation folded into weights and bias.  Same logits as the unfolded eval
-    path (autograd on) and as the oracle; a third of the conv-engine + BatchNorm launches."""
+def _eval_mode_pair():
+    """(fe, clf, their state dicts, meta, tup, gen): the small target feature extractor and classifier in eval mode, with
+    non-trivial running statistics."""
     g = load("joint_small")
     meta = json.loads(str(g["meta"]))
     tup = lambda lp: [[tuple(t) for t in l] for l in lp]
@@ -503,6 +502,14 @@ def test_inference_mode_folds_batchnorm_into_the_convs():
                 P[k] = torch.rand(P[k].shape, generator=gen) + 0.5
     fe.load_state_dict(Pf); clf.load_state_dict(Pc)
     fe.eval(); clf.eval()
+    return fe, clf, Pf, Pc, meta, tup, gen
+
+
+def test_inference_mode_folds_batchnorm_into_the_convs():
+    """Eval mode with autograd off (the eval pass and the K-way voting forward): every conv → BatchNorm (→ residual add
+    → ReLU) runs as ONE launch with the normalisation folded into weights and bias.  Same logits as the unfolded eval
+    path (autograd on) and as the oracle; a third of the conv-engine + BatchNorm launches."""
+    fe, clf, Pf, Pc, meta, tup, gen = _eval_mode_pair()
     x = torch.randn(6, meta["C_in_t"], meta["L_t"], generator=gen)
     logits_unfolded, pooled_unfolded = clf(fe(x.to(DEV)))                  # autograd on: BatchNorm kernels in eval mode
     with torch.no_grad():
@@ -529,6 +536,24 @@ def test_inference_mode_folds_batchnorm_into_the_convs():
     counts = {k: v["launches"] for k, v in timer.summary().items()}
     assert sum(n for k, n in counts.items() if not k.startswith("gemm_bf3")) == 7, counts
     assert sum(n for k, n in counts.items() if k.startswith("gemm_bf3")) == (1 if ops.MATH == "bf16x3" else 0), counts
+
+
+def test_folded_inference_keeps_a_nan_series_non_finite():
+    """A batch in which one series holds a NaN.  The ReLU in the folded conv's epilogue hands it on as torch.relu does: the
+    series gets non-finite logits instead of a confident class — for exactly the rows where the unfolded eval pass (autograd on:
+    the BatchNorm kernels) on the same weights does — and every clean row carries the bits it has in the clean batch."""
+    fe, clf, _, _, meta, _, gen = _eval_mode_pair()
+    x = torch.randn(6, meta["C_in_t"], meta["L_t"], generator=gen)
+    bad = x.clone()
+    bad[2, 0, meta["L_t"] // 2] = float("nan")
+    unfolded, _ = clf(fe(bad.to(DEV)))
+    with torch.no_grad():
+        clean, _ = clf(fe(x.to(DEV)))
+        folded, _ = clf(fe(bad.to(DEV)))
+    rows_unfolded, rows = ~torch.isfinite(unfolded).all(dim=1), ~torch.isfinite(folded).all(dim=1)
+    assert rows_unfolded.tolist() == [False, False, True, False, False, False], f"unfolded eval pass: {unfolded}"
+    assert rows.tolist() == rows_unfolded.tolist(), f"folded eval pass: {folded}"
+    assert torch.equal(folded[~rows].view(torch.int32), clean[~rows].view(torch.int32)), "a NaN series moved the logits of another row"
 
 
 def test_trainer_state_checkpoint_resume_equals_uninterrupted(tmp_path):
