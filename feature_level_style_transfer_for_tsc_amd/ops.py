@@ -709,6 +709,15 @@ def gemm(A: Tensor, ta: bool, B: Tensor, tb: bool, bias: Optional[Tensor] = None
     return C
 
 
+def _gemm_rows(t: Tensor) -> Tensor:
+    """The matrix ``t`` as ``gemm`` takes it — unit column stride, rows that do not overlap — copied only if it is not.
+    ``contiguous()`` does not do: it passes a dimension of size 1 through whatever its stride, and the [1, 1] cotangent that
+    ``mean`` hands the last layer of a head at a batch of one is an expanded scalar with strides (0, 0)."""
+    if t.stride(1) == 1 and t.stride(0) >= t.size(1):
+        return t
+    return torch.empty(t.shape, device=t.device, dtype=t.dtype).copy_(t)
+
+
 def act_bwd(dy: Tensor, y: Tensor, slope: float) -> Tensor:
     """dy·act'(y) from the activation's output: dy where y > 0, slope·dy elsewhere (ReLU: slope 0)."""
     dy = _aligned16(dy)
@@ -726,7 +735,7 @@ class LinearActFn(torch.autograd.Function):
     def forward(ctx, x: Tensor, W: Tensor, b: Optional[Tensor], act: int, slope: float):
         x2 = x.reshape(-1, x.size(-1))
         if x2.stride(1) != 1 or x2.stride(0) < x2.size(1):              # e.g. an expanded batch: rows that overlap
-            x2 = x2.contiguous()
+            x2 = _gemm_rows(x2.contiguous())
         y = gemm(x2, False, W, False, b, act, slope)
         ctx.save_for_backward(x2, W, y if act != ACT_NONE else None)
         ctx.lead, ctx.act, ctx.slope, ctx.has_bias = x.shape[:-1], act, slope, b is not None
@@ -737,6 +746,7 @@ class LinearActFn(torch.autograd.Function):
         x2, W, y = ctx.saved_tensors
         g = dy.reshape(-1, W.size(0))
         g = act_bwd(g, y, ctx.slope if ctx.act == ACT_LEAKY else 0.0) if ctx.act != ACT_NONE else g.contiguous()
+        g = _gemm_rows(g)
         dx = gemm(g, False, W, True).view(*ctx.lead, W.size(1)) if ctx.needs_input_grad[0] else None
         dW = gemm(g, True, x2, True) if ctx.needs_input_grad[1] and _want_weight_grad() else None
         db = g.sum(dim=0) if ctx.has_bias and ctx.needs_input_grad[2] and _want_weight_grad() else None
@@ -1193,30 +1203,41 @@ class WGradJoinFn(torch.autograd.Function):
         nl, n, h = S.n_layers, S.n, S.h
         dw = S.unflatten(g)
         g_cond_w, g_in_w, g_rs_w = dw[2], dw[6: 6 + nl], dw[6 + 2 * nl: 6 + 3 * nl]
-        # the first chunk of every (kind, layer) leaves its slabs (workspaces of all of them live at once) for ONE reduction
-        # launch; chunks beyond WN_WGRAD_MAX_SETS reduce their own, into a temporary that is added to the segment afterwards
-        slabs, later, BL = [], [], None
+        # One launch sums only operand sets of one shape, and the applications of a step differ in batch size whenever the target
+        # and the source batch do (the last batch pair of an epoch): the sets of a (kind, layer) are grouped by (B, L) — and, for
+        # u0, its batch stride — first.  Equal batches make one group, i.e. the launches below as they always were.
+        # The first chunk of every group leaves its slabs (workspaces of all of them live at once) for ONE reduction launch per
+        # (B, L); chunks beyond WN_WGRAD_MAX_SETS reduce their own.  The first launch of a (kind, layer) writes the segment, every
+        # other one a temporary that is added to the segment afterwards.
+        slabs, later = {}, []
         for (kind, i), sets in pending.items():
-            for c0 in range(0, len(sets), WN_WGRAD_MAX_SETS):
-                chunk = sets[c0: c0 + WN_WGRAD_MAX_SETS]
-                cols = [list(col) for col in zip(*chunk)]
-                if kind == 0:
-                    t_in, t_cond = g_in_w[i], g_cond_w[2 * n * i: 2 * n * (i + 1)]
-                    if c0:
-                        t_in, t_cond = torch.empty_like(t_in), torch.empty_like(t_cond)
-                        later += [(g_in_w[i], t_in), (g_cond_w[2 * n * i: 2 * n * (i + 1)], t_cond)]
-                    wn_wgrad_in(cols[0], cols[1], cols[2], t_in, t_cond, n, h, 2 ** i, slabs=None if c0 else slabs)
-                    BL = (cols[0][0].size(0), cols[0][0].size(2))
-                else:
-                    last = i == nl - 1
-                    t_rs = g_rs_w[i]
-                    if c0:
-                        t_rs = torch.empty_like(t_rs)
-                        later.append((g_rs_w[i], t_rs))
-                    wn_wgrad_rs(None if last else cols[0], cols[1], cols[2], t_rs, last, n, slabs=None if c0 else slabs)
-                    BL = (cols[1][0].size(0), cols[1][0].size(2))
-        if slabs:
-            wn_wgrad_reduce_many(slabs, BL[0], BL[1], n, h)
+            groups = {}
+            for s in sets:
+                lead = s[0] if kind == 0 else s[1]                                   # dg | d_out: [B, ., L]
+                shape = (lead.size(0), lead.size(2)) + ((s[2].stride(0),) if kind == 0 else ())
+                groups.setdefault(shape, []).append(s)
+            own = True                                                               # this launch writes the segment itself
+            for shape, members in groups.items():
+                for c0 in range(0, len(members), WN_WGRAD_MAX_SETS):
+                    chunk = members[c0: c0 + WN_WGRAD_MAX_SETS]
+                    cols = [list(col) for col in zip(*chunk)]
+                    to = None if c0 else slabs.setdefault(shape[:2], [])
+                    if kind == 0:
+                        t_in, t_cond = g_in_w[i], g_cond_w[2 * n * i: 2 * n * (i + 1)]
+                        if not own:
+                            t_in, t_cond = torch.empty_like(t_in), torch.empty_like(t_cond)
+                            later += [(g_in_w[i], t_in), (g_cond_w[2 * n * i: 2 * n * (i + 1)], t_cond)]
+                        wn_wgrad_in(cols[0], cols[1], cols[2], t_in, t_cond, n, h, 2 ** i, slabs=to)
+                    else:
+                        last = i == nl - 1
+                        t_rs = g_rs_w[i]
+                        if not own:
+                            t_rs = torch.empty_like(t_rs)
+                            later.append((g_rs_w[i], t_rs))
+                        wn_wgrad_rs(None if last else cols[0], cols[1], cols[2], t_rs, last, n, slabs=to)
+                    own = False
+        for (B, L), entries in slabs.items():
+            wn_wgrad_reduce_many(entries, B, L, n, h)
         for seg, t in later:
             seg.add_(t)
         return None, None, g
@@ -2293,14 +2314,23 @@ class CPCNceFn(torch.autograd.Function):
         ws = torch.empty(n_ws, device=feat.device, dtype=torch.float32) if n_ws else None
         check(lib.fst_cpc_nce_fwd(feat.data_ptr() + 4 * t0_host, 1, C * L, L, ptr(t0_dev), ptr(pred), T, B, C, Bc, col_off,
                                   ptr(lse), ptr(acc), ptr(ws), stream_ptr()), "fst_cpc_nce_fwd")
-        ctx.save_for_backward(feat, pred, lse)
+        nce = acc.sum() * (-1.0 / (B * T))
+        # A batch of one (the last batch of an epoch) has no negatives: log_softmax over a single logit is 0 whatever the logit,
+        # and so is every gradient.  The backward launch would return exp(total − lse) − 1 with ``total`` from its fp32 Gram
+        # product and ``lse`` from the forward's split-bf16 one — their rounding difference — as a cotangent of ``pred``, which
+        # the GRU carries on into the features: the backward of this case launches nothing (``nce`` is kept for its NaN).
+        ctx.no_negatives = Bc == 1
+        ctx.save_for_backward(feat, pred, nce if ctx.no_negatives else lse)
         ctx.t0_host, ctx.t0_dev, ctx.T, ctx.col_off = t0_host, t0_dev, T, col_off
-        return acc.sum() * (-1.0 / (B * T))
+        return nce
 
     @staticmethod
     def backward(ctx, g):
         lib = _lib.load()
         feat, pred, lse = ctx.saved_tensors
+        if ctx.no_negatives:
+            zero = (g.float() * lse) * 0.0                   # 0, or NaN where the reference's gradient is NaN (a non-finite logit)
+            return zero.expand_as(feat).contiguous(), zero.expand_as(pred).contiguous(), None, None, None
         B, C, L = feat.shape
         T, t0 = ctx.T, ctx.t0_host
         dfeat = torch.zeros_like(feat)

@@ -618,6 +618,75 @@ def test_waveglow_pool_over_step_shaped_passes(monkeypatch):
                 assert_close(again[k], v, tol_p, f"{label}: {k}")
 
 
+@bf3_only
+@pytest.mark.parametrize("apps", [(("fwd", 3), ("fwd", 5), ("inv", 5)),                  # the joint step's three, target batch 3, source 5
+                                  (("fwd", 3), ("fwd", 5), ("inv", 5), ("fwd", 2)),     # more sets per key than WN_WGRAD_MAX_SETS, three shapes
+                                  (("fwd", 5), ("fwd", 5), ("inv", 5), ("fwd", 5), ("fwd", 3))],   # one shape alone fills more than a launch
+                         ids=["3-5-5", "3-5-5-2", "5-5-5-5-3"])
+def test_waveglow_pool_over_uneven_batches(apps, monkeypatch):
+    """The applications of one small WaveGlow inside one ``pack_cache`` + ``shared_fold`` scope differ in BATCH SIZE, as the flow
+    passes of a train step do whenever the target and the source batch differ: every (kind, layer) key of a pool then holds
+    operand sets of several shapes, which no single weight-gradient launch can sum.  Every parameter gradient and every input
+    gradient against oracle.restatement in fp64, and against the same losses taken outside ``shared_fold`` (no pool: every
+    application launches its own weight gradients).  Tolerances: those of test_waveglow_pool_over_step_shaped_passes."""
+    n_flows, n_group, n, L = 3, 6, 8, 64
+    h = n_group // 2
+    assert len(apps) > ops.WN_WGRAD_MAX_SETS or len({B for _, B in apps}) > 1
+    torch.manual_seed(5)
+    wg = fst.WaveGlow(n_flows, n_group, n).to(DEV)
+    with torch.no_grad():
+        for wn in wg.WN:
+            wn.end.weight.normal_(0.0, 0.05)
+            wn.end.bias.normal_(0.0, 0.05)
+    assert all(any(ops.wn_wgrad_ok(kind, B, L, n, h, 2 ** i) for kind in (0, 1) for i in range(8)) for _, B in apps)
+    adds, add0 = [], ops.WNGradPool.add
+    monkeypatch.setattr(ops.WNGradPool, "add", lambda self, key, operands: (adds.append(key), add0(self, key, operands))[1])
+    g = _gen(43)
+    xs_host = [_rnd(g, B, n_group, L) for _, B in apps]
+    rs_host = [_rnd(g, B, n_group, L) for _, B in apps]
+    wts = (1.0, 0.5, 2.0, 1.5, 0.75)[: len(apps)]
+    tol_p, tol_x = n_flows * 1e-4, n_flows * 5e-5
+
+    def losses(xs, rs, forward, infer):
+        return [forward(x) if way == "fwd" else (infer(x) * r).sum() / r.numel() for (way, _), x, r in zip(apps, xs, rs)]
+
+    params = dict(wg.named_parameters())
+
+    def device_pass(scope):
+        xs = [x.to(DEV).requires_grad_(True) for x in xs_host]
+        wg.zero_grad()
+        with ops.pack_cache(), scope():
+            ls = losses(xs, [r.to(DEV) for r in rs_host], lambda u: fst.WaveGlowLoss()(wg(u)), wg.infer)
+            pools = [wn._fold_cache[0][1] for wn in wg.WN] if wg.WN[0]._fold_cache is not None else []
+            sum(w * l for w, l in zip(wts, ls)).backward()
+            assert all(p.pending == {} for p in pools), "operands left in a pool after the pass"
+        return ls, {k: p.grad.clone() for k, p in params.items() if p.grad is not None}, [x.grad.clone() for x in xs], pools
+
+    ls, got, dxs, pools = device_pass(wg.shared_fold)
+    assert len(pools) == n_flows and all(p is not None for p in pools)
+    assert adds, "no application deferred a weight gradient: the pool path did not run"
+    n_adds = len(adds)
+    _, alone, dxs_alone, _ = device_pass(contextlib.nullcontext)
+    assert len(adds) == n_adds, "an application outside shared_fold left operands in a pool"
+    inv = {k: wg.convinv[k].W_inverse.double().cpu() for k in range(n_flows)}
+
+    P = R.to_params({k: v.detach().double().cpu().numpy() for k, v in wg.state_dict().items()})
+    xs64 = [x.double().requires_grad_(True) for x in xs_host]
+    ls64 = losses(xs64, [r.double() for r in rs_host], lambda u: R.waveglow_loss(R.waveglow_forward(u, P, n_flows)),
+                  lambda z: R.waveglow_infer(z, P, n_flows, inv))
+    total64 = sum(w * l for w, l in zip(wts, ls64))
+    for l, l64 in zip(ls, ls64):
+        assert_close(l, l64, 1e-4, "loss")
+    want = dict(zip(params, torch.autograd.grad(total64, [P[k] for k in params], retain_graph=True, allow_unused=True)))
+    assert set(got) == set(alone) == {k for k, v in want.items() if v is not None}
+    for k, v in got.items():
+        assert_close(v, want[k], tol_p, f"pooled {k} vs fp64")
+        assert_close(v, alone[k], tol_p, f"pooled {k} vs every application on its own")
+    for i, (dx, dx_alone, dx64) in enumerate(zip(dxs, dxs_alone, torch.autograd.grad(total64, xs64))):
+        assert_close(dx, dx64, tol_x, f"input {i} {apps[i]} vs fp64")
+        assert_close(dx, dx_alone, tol_x, f"input {i} {apps[i]} vs every application on its own")
+
+
 # ------------------------------------------------------------------------------------------------ _RowSums across passes
 def _conv_bn(two_consumers):
     """conv -> BNActFn at OS-CNN size; with ``two_consumers`` the conv output also feeds a plain scaling, so autograd SUMS two

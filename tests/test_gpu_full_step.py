@@ -165,6 +165,32 @@ def _step_both(js, tr, batch, ts):
     return rep_o, want, rep, grads
 
 
+def _phase_both(js, tr, phase, batch, ts):
+    """``_step_both`` for one batch of a pre-training phase: ``tr.phase_step`` and ``js.phase_step`` from identical state, the
+    oracle on the device run's ReLU branches; same return value.  ``js`` must be fresh: the oracle's ``phase_step`` never zeroes
+    its gradients, so a leaf's ``.grad`` is what this one pass left there (None where the phase does not reach it)."""
+    (x_t, y_t), (x_s, y_s) = batch
+    grads, branches = {}, []
+
+    def grab():
+        for name in tr.MODULES:
+            grads[name] = {n: p.grad.detach().clone() for n, p in tr.m[name].named_parameters() if p.grad is not None}
+    tr.on_grads_ready = grab
+    with _head_unit_branches(record=branches):
+        rep = tr.phase_step(phase, x_t.to(DEV), y_t.to(DEV), x_s.to(DEV), y_s.to(DEV), t_samples=ts)
+    tr.on_grads_ready = None
+    assert branches, "no ReLU layer of the phase was recorded"
+    assert all(p.grad is None for P in js.m.values() for p in P.values()), "the oracle carries gradients of an earlier pass"
+    flips = []
+    with _head_unit_branches(impose=branches, flips=flips):
+        rep_o = js.phase_step(phase, x_t, y_t, x_s, y_s, t_samples=ts)
+    if os.environ.get("FST_GRAD_REPORT"):
+        print(f"[branch report] {phase}: {sum(int(b.numel()) for b in branches)} synchronised units, flipped (layer, units, |x|/max): {flips}")
+    want = {name: {n: p.grad.detach().numpy().copy() for n, p in P.items() if p.requires_grad and p.grad is not None}
+            for name, P in js.m.items()}
+    return rep_o, want, rep, grads
+
+
 # Gradient tolerances (of each module's largest gradient), with the oracle on the device run's piece of EVERY ReLU / LeakyReLU
 # layer — the MLP heads and the dimension unification (torch ops) and the omni-scale layers (fused into the BatchNorm launches,
 # recorded from their outputs) — each imposed branch bounded to a rounding-level pre-activation (FLIP_BOUND).  Measured on the

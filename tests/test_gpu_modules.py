@@ -192,13 +192,18 @@ def test_small_heads_golden():
     close(du(d("xs")), g["du_out"], 1e-4, "dimunif")
 
 
-def _joint_trainer(g):
+def _joint_trainer_untrained(g):
+    """A trainer of the joint fixture's geometry with its own (torch-seeded) initial weights: the fixture's state not loaded."""
     meta = json.loads(str(g["meta"]))
     tup = lambda lp: [[tuple(t) for t in l] for l in lp]
     cfg = fst.JointConfig(L_t=meta["L_t"], C_in_t=meta["C_in_t"], L_s=meta["L_s"], C_in_s=meta["C_in_s"],
                           n_class_t=meta["ncls_t"], n_class_s=meta["ncls_s"], nf_channels=meta["nf"][2],
                           cpc_hidden=meta["cpc"][1], cdan_dim=64, ad_hidden=32, dropout_p=0.0)
-    tr = fst.JointTrainer(cfg, DEV, fe_t_spec=tup(meta["lp_t"]), clf_spec=tup(meta["lp_clf"]), fe_s_spec=tup(meta["lp_s"]))
+    return fst.JointTrainer(cfg, DEV, fe_t_spec=tup(meta["lp_t"]), clf_spec=tup(meta["lp_clf"]), fe_s_spec=tup(meta["lp_s"]))
+
+
+def _joint_trainer(g):
+    tr = _joint_trainer_untrained(g)
     tr.load_params({name: tsd(sub(g, f"sd0.{name}.")) for name in tr.MODULES}, [torch.tensor(g["m0"]), torch.tensor(g["m1"])])
     return tr
 
