@@ -775,59 +775,86 @@ extern "C" int fst_wn_stack_fwd_ok(int n, int h, int L, int nl) {
   return n > 0 && n < 128 && h > 0 && L > 0 && L % 256 == 0 && nl >= 1 && nl <= WS_MAXL;
 }
 
-extern "C" int fst_wn_stack_fwd(const float* const* a_in, const int64_t* a_bs, const void* const* images, int64_t image_bytes,
-                                float* const* ts, float* const* a_next, const float* u0, int64_t u0_bs, float* out, int nl, int B,
-                                int L, int n, int h, int64_t numel_a, void* stream) {
-  fst_wn_clear_route();
-  FST_REQUIRE(a_in && a_bs && images && ts && a_next && u0 && out, "fst_wn_stack_fwd: null operand");
-  FST_REQUIRE(fst_wn_stack_fwd_ok(n, h, L, nl) && B > 0, "fst_wn_stack_fwd: B=%d L=%d n=%d h=%d nl=%d (needs n < 128, L %% 256 == 0, "
-              "1 <= nl <= %d)", B, L, n, h, nl, WS_MAXL);
-  FST_REQUIRE((long long)B * n * L == (long long)numel_a, "fst_wn_stack_fwd: B*n*L = %d*%d*%d does not match the element count %lld "
-              "of the [B, n, L] tensors", B, n, L, (long long)numel_a);
-  FST_REQUIRE(image_bytes == fst_wn_image_bytes(n, h), "fst_wn_stack_fwd: images are %lld bytes, expected %lld",
+// The launch behind fst_wn_stack_fwd (save: ts[i] receives layer i's gate halves) and fst_wn_stack_infer (no ts table: nothing but
+// a_next and out is stored, so a_next[i] may be the buffer layer i − 1 read, but not layer i's own input).
+static int wn_stack_fwd_launch(const char* who, bool save, const float* const* a_in, const int64_t* a_bs, const void* const* images,
+                               int64_t image_bytes, float* const* ts, float* const* a_next, const float* u0, int64_t u0_bs,
+                               float* out, int nl, int B, int L, int n, int h, int64_t numel_a, void* stream) {
+  FST_REQUIRE(a_in && a_bs && images && (ts || !save) && a_next && u0 && out, "%s: null operand", who);
+  FST_REQUIRE(fst_wn_stack_fwd_ok(n, h, L, nl) && B > 0, "%s: B=%d L=%d n=%d h=%d nl=%d (needs n < 128, L %% 256 == 0, "
+              "1 <= nl <= %d)", who, B, L, n, h, nl, WS_MAXL);
+  FST_REQUIRE((long long)B * n * L == (long long)numel_a, "%s: B*n*L = %d*%d*%d does not match the element count %lld "
+              "of the [B, n, L] tensors", who, B, n, L, (long long)numel_a);
+  FST_REQUIRE(image_bytes == fst_wn_image_bytes(n, h), "%s: images are %lld bytes, expected %lld", who,
               (long long)image_bytes, (long long)fst_wn_image_bytes(n, h));
-  FST_REQUIRE(B == 1 || u0_bs >= (int64_t)h * L, "fst_wn_stack_fwd: batch stride of u0 smaller than a sample");
-  FST_REQUIRE(u0_bs % 4 == 0 && fst_aligned16(u0) && fst_aligned16(out), "fst_wn_stack_fwd: needs 16-byte aligned tensors");
+  FST_REQUIRE(B == 1 || u0_bs >= (int64_t)h * L, "%s: batch stride of u0 smaller than a sample", who);
+  FST_REQUIRE(u0_bs % 4 == 0 && fst_aligned16(u0) && fst_aligned16(out), "%s: needs 16-byte aligned tensors", who);
   WnFwdStackParams p = {};
   for (int i = 0; i < nl; ++i) {
-    FST_REQUIRE(a_in[i] && images[i] && ts[i] && (a_next[i] || i == nl - 1), "fst_wn_stack_fwd: null operand of layer %d", i);
-    FST_REQUIRE(a_bs[i] >= (int64_t)n * L && a_bs[i] % 4 == 0 && fst_aligned16(a_in[i]) && fst_aligned16(images[i]) && fst_aligned16(ts[i]) && fst_aligned16(a_next[i]),
-                "fst_wn_stack_fwd: layer %d: batch stride %lld smaller than a sample, or an operand that is not 16-byte aligned", i,
+    const bool last = i == nl - 1;
+    float* const ts_i = save ? ts[i] : nullptr;
+    FST_REQUIRE(a_in[i] && images[i] && (ts_i || !save) && (a_next[i] || last), "%s: null operand of layer %d", who, i);
+    FST_REQUIRE(a_bs[i] >= (int64_t)n * L && a_bs[i] % 4 == 0 && fst_aligned16(a_in[i]) && fst_aligned16(images[i]) && fst_aligned16(ts_i) && fst_aligned16(a_next[i]),
+                "%s: layer %d: batch stride %lld smaller than a sample, or an operand that is not 16-byte aligned", who, i,
                 (long long)a_bs[i]);
-    FST_REQUIRE(i == nl - 1 || a_in[i + 1] == a_next[i], "fst_wn_stack_fwd: the input of layer %d is not the a_next of layer %d",
-                i + 1, i);
+    FST_REQUIRE(last || a_in[i + 1] == a_next[i], "%s: the input of layer %d is not the a_next of layer %d", who, i + 1, i);
+    FST_REQUIRE(save || last || a_next[i] != a_in[i], "%s: layer %d would store a_next over the input its neighbouring "
+                "tiles still read", who, i);
     WnFwdParams& q = p.layer[i];
     q.a = a_in[i]; q.a_bs = a_bs[i]; q.u0 = u0; q.u0_bs = u0_bs; q.img = static_cast<const char*>(images[i]);
-    q.ts = ts[i]; q.acts = nullptr; q.a_next = i == nl - 1 ? nullptr : a_next[i]; q.out = out;
-    q.B = B; q.L = L; q.n = n; q.h = h; q.dil = 1 << i; q.first = i == 0; q.last = i == nl - 1;
+    q.ts = ts_i; q.acts = nullptr; q.a_next = last ? nullptr : a_next[i]; q.out = out;
+    q.B = B; q.L = L; q.n = n; q.h = h; q.dil = 1 << i; q.first = i == 0; q.last = last;
     q.CH = wn_ch(n); q.CH2 = wn_ch2(h); q.tiles_per_seq = L / 256; q.n_wg = 0;
   }
   p.nl = nl;
   const int cus = fst_cu_count_or(256);
-  if (int rc = fst_allow_full_lds((const void*)wn_stack_fwd_kernel, "fst_wn_stack_fwd")) return rc;
-  fst_wn_set_route(FST_WN_ROUTE_STACK_FWD, 8, 0, 0, 0, B < cus ? B : cus, 1, 1, L / 256, 3, nl, WN_FWD_LDS(8));
-  hipLaunchKernelGGL(wn_stack_fwd_kernel, dim3((unsigned)(B < cus ? B : cus)), dim3(512), WN_FWD_LDS(8), (hipStream_t)stream, p);
+  const dim3 grid((unsigned)(B < cus ? B : cus));        // one resident workgroup per CU walks its batch elements
+  if (int rc = fst_allow_full_lds(save ? (const void*)wn_stack_fwd_kernel : (const void*)wn_stack_infer_kernel, who)) return rc;
+  fst_wn_set_route(save ? FST_WN_ROUTE_STACK_FWD : FST_WN_ROUTE_STACK_INFER, 8, 0, 0, 0, (int)grid.x, 1, 1, L / 256, 3, nl, WN_FWD_LDS(8));
+  if (save) {
+    hipLaunchKernelGGL(wn_stack_fwd_kernel, grid, dim3(512), WN_FWD_LDS(8), (hipStream_t)stream, p);
+  } else {
+    hipLaunchKernelGGL(wn_stack_infer_kernel, grid, dim3(512), WN_FWD_LDS(8), (hipStream_t)stream, p);
+  }
   FST_LAUNCH_CHECK();
   return 0;
 }
 
-extern "C" int fst_wn_layer_fwd(const float* a, int64_t a_bs, const float* u0, int64_t u0_bs, const void* image,
-                                int64_t image_bytes, float* ts, float* acts, float* a_next, float* out, int first, int last,
-                                int B, int L, int n, int h, int dil, int64_t numel_a, void* stream) {
+extern "C" int fst_wn_stack_fwd(const float* const* a_in, const int64_t* a_bs, const void* const* images, int64_t image_bytes,
+                                float* const* ts, float* const* a_next, const float* u0, int64_t u0_bs, float* out, int nl, int B,
+                                int L, int n, int h, int64_t numel_a, void* stream) {
   fst_wn_clear_route();
-  FST_REQUIRE(a && u0 && image && ts && out && (last || a_next), "fst_wn_layer_fwd: null operand");
-  FST_REQUIRE(B > 0 && L > 0 && n > 0 && n < 128 && h > 0 && dil > 0, "fst_wn_layer_fwd: B=%d L=%d n=%d h=%d dil=%d (needs n < 128)",
+  return wn_stack_fwd_launch("fst_wn_stack_fwd", true, a_in, a_bs, images, image_bytes, ts, a_next, u0, u0_bs, out, nl, B, L, n, h,
+                             numel_a, stream);
+}
+
+extern "C" int fst_wn_stack_infer(const float* const* a_in, const int64_t* a_bs, const void* const* images, int64_t image_bytes,
+                                  float* const* a_next, const float* u0, int64_t u0_bs, float* out, int nl, int B, int L, int n, int h,
+                                  int64_t numel_a, void* stream) {
+  fst_wn_clear_route();
+  return wn_stack_fwd_launch("fst_wn_stack_infer", false, a_in, a_bs, images, image_bytes, nullptr, a_next, u0, u0_bs, out, nl, B, L,
+                             n, h, numel_a, stream);
+}
+
+// The launch behind fst_wn_layer_fwd (save: ts, and acts where given, are written) and fst_wn_layer_infer (neither exists; a_next
+// must then not be a: a tile's neighbours read a's halo while the tile stores a_next).
+static int wn_layer_fwd_launch(const char* who, bool save, const float* a, int64_t a_bs, const float* u0, int64_t u0_bs,
+                               const void* image, int64_t image_bytes, float* ts, float* acts, float* a_next, float* out, int first,
+                               int last, int B, int L, int n, int h, int dil, int64_t numel_a, void* stream) {
+  FST_REQUIRE(a && u0 && image && (ts || !save) && out && (last || a_next), "%s: null operand", who);
+  FST_REQUIRE(B > 0 && L > 0 && n > 0 && n < 128 && h > 0 && dil > 0, "%s: B=%d L=%d n=%d h=%d dil=%d (needs n < 128)", who,
               B, L, n, h, dil);
-  FST_REQUIRE((long long)B * n * L == (long long)numel_a, "fst_wn_layer_fwd: B*n*L = %d*%d*%d does not match the element count %lld "
-              "of the [B, n, L] tensors", B, n, L, (long long)numel_a);
-  FST_REQUIRE(image_bytes == fst_wn_image_bytes(n, h), "fst_wn_layer_fwd: image is %lld bytes, expected %lld",
+  FST_REQUIRE((long long)B * n * L == (long long)numel_a, "%s: B*n*L = %d*%d*%d does not match the element count %lld "
+              "of the [B, n, L] tensors", who, B, n, L, (long long)numel_a);
+  FST_REQUIRE(image_bytes == fst_wn_image_bytes(n, h), "%s: image is %lld bytes, expected %lld", who,
               (long long)image_bytes, (long long)fst_wn_image_bytes(n, h));
-  FST_REQUIRE(B == 1 || (a_bs >= (int64_t)n * L && u0_bs >= (int64_t)h * L), "fst_wn_layer_fwd: batch stride smaller than a sample");
+  FST_REQUIRE(B == 1 || (a_bs >= (int64_t)n * L && u0_bs >= (int64_t)h * L), "%s: batch stride smaller than a sample", who);
   FST_REQUIRE(L % 4 == 0 && a_bs % 4 == 0 && u0_bs % 4 == 0 && fst_aligned16(a) && fst_aligned16(u0) && fst_aligned16(image) && fst_aligned16(ts) && fst_aligned16(acts) &&
-              fst_aligned16(a_next) && fst_aligned16(out), "fst_wn_layer_fwd: needs L %% 4 == 0 and 16-byte aligned tensors (L=%d)", L);
+              fst_aligned16(a_next) && fst_aligned16(out), "%s: needs L %% 4 == 0 and 16-byte aligned tensors (L=%d)", who, L);
+  FST_REQUIRE(save || last || a_next != a, "%s: a_next is a — a tile's neighbours read a's halo while the tile stores a_next", who);
   WnFwdParams p;
   p.a = a; p.a_bs = a_bs; p.u0 = u0; p.u0_bs = u0_bs; p.img = static_cast<const char*>(image);
-  p.ts = ts; p.acts = acts; p.a_next = a_next; p.out = out;
+  p.ts = ts; p.acts = acts; p.a_next = last ? nullptr : a_next; p.out = out;
   p.B = B; p.L = L; p.n = n; p.h = h; p.dil = dil; p.first = first ? 1 : 0; p.last = last ? 1 : 0;
   p.CH = wn_ch(n); p.CH2 = wn_ch2(h);
   // 256-sample tiles (8 waves) when they divide the sequence and still fill the chip, else 128-sample tiles (4 waves, two per CU)
@@ -836,95 +863,37 @@ extern "C" int fst_wn_layer_fwd(const float* a, int64_t a_bs, const float* u0, i
   const int tn = 32 * nw;
   p.tiles_per_seq = (L + tn - 1) / tn;
   p.n_wg = B * p.tiles_per_seq;
-  if (nw == 8) {
-    if (int rc = fst_allow_full_lds((const void*)wn_layer_fwd_kernel<8>, "fst_wn_layer_fwd")) return rc;
-    fst_wn_set_route(FST_WN_ROUTE_LAYER_FWD, 8, 0, 0, 0, p.n_wg, 1, 1, p.tiles_per_seq, 3, 1, WN_FWD_LDS(8));
-    hipLaunchKernelGGL(wn_layer_fwd_kernel<8>, dim3((unsigned)p.n_wg), dim3(512), WN_FWD_LDS(8), (hipStream_t)stream, p);
+  const dim3 grid((unsigned)p.n_wg), block(64 * nw);
+  const int lds = nw == 8 ? WN_FWD_LDS(8) : WN_FWD_LDS(4);
+  const void* const kernel = save ? (nw == 8 ? (const void*)wn_layer_fwd_kernel<8> : (const void*)wn_layer_fwd_kernel<4>)
+                                  : (nw == 8 ? (const void*)wn_layer_infer_kernel<8> : (const void*)wn_layer_infer_kernel<4>);
+  if (int rc = fst_allow_full_lds(kernel, who)) return rc;
+  fst_wn_set_route(save ? FST_WN_ROUTE_LAYER_FWD : FST_WN_ROUTE_LAYER_INFER, nw, 0, 0, 0, p.n_wg, 1, 1, p.tiles_per_seq, 3, 1, lds);
+  if (save) {
+    if (nw == 8) hipLaunchKernelGGL(wn_layer_fwd_kernel<8>, grid, block, lds, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(wn_layer_fwd_kernel<4>, grid, block, lds, (hipStream_t)stream, p);
   } else {
-    if (int rc = fst_allow_full_lds((const void*)wn_layer_fwd_kernel<4>, "fst_wn_layer_fwd")) return rc;
-    fst_wn_set_route(FST_WN_ROUTE_LAYER_FWD, 4, 0, 0, 0, p.n_wg, 1, 1, p.tiles_per_seq, 3, 1, WN_FWD_LDS(4));
-    hipLaunchKernelGGL(wn_layer_fwd_kernel<4>, dim3((unsigned)p.n_wg), dim3(256), WN_FWD_LDS(4), (hipStream_t)stream, p);
+    if (nw == 8) hipLaunchKernelGGL(wn_layer_infer_kernel<8>, grid, block, lds, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(wn_layer_infer_kernel<4>, grid, block, lds, (hipStream_t)stream, p);
   }
   FST_LAUNCH_CHECK();
   return 0;
 }
 
-extern "C" int fst_wn_stack_infer(const float* const* a_in, const int64_t* a_bs, const void* const* images, int64_t image_bytes,
-                                  float* const* a_next, const float* u0, int64_t u0_bs, float* out, int nl, int B, int L, int n, int h,
-                                  int64_t numel_a, void* stream) {
+extern "C" int fst_wn_layer_fwd(const float* a, int64_t a_bs, const float* u0, int64_t u0_bs, const void* image,
+                                int64_t image_bytes, float* ts, float* acts, float* a_next, float* out, int first, int last,
+                                int B, int L, int n, int h, int dil, int64_t numel_a, void* stream) {
   fst_wn_clear_route();
-  FST_REQUIRE(a_in && a_bs && images && a_next && u0 && out, "fst_wn_stack_infer: null operand");
-  FST_REQUIRE(fst_wn_stack_fwd_ok(n, h, L, nl) && B > 0, "fst_wn_stack_infer: B=%d L=%d n=%d h=%d nl=%d (needs n < 128, L %% 256 == 0, "
-              "1 <= nl <= %d)", B, L, n, h, nl, WS_MAXL);
-  FST_REQUIRE((long long)B * n * L == (long long)numel_a, "fst_wn_stack_infer: B*n*L = %d*%d*%d does not match the element count %lld "
-              "of the [B, n, L] tensors", B, n, L, (long long)numel_a);
-  FST_REQUIRE(image_bytes == fst_wn_image_bytes(n, h), "fst_wn_stack_infer: images are %lld bytes, expected %lld",
-              (long long)image_bytes, (long long)fst_wn_image_bytes(n, h));
-  FST_REQUIRE(B == 1 || u0_bs >= (int64_t)h * L, "fst_wn_stack_infer: batch stride of u0 smaller than a sample");
-  FST_REQUIRE(u0_bs % 4 == 0 && fst_aligned16(u0) && fst_aligned16(out), "fst_wn_stack_infer: needs 16-byte aligned tensors");
-  WnFwdStackParams p = {};
-  for (int i = 0; i < nl; ++i) {
-    FST_REQUIRE(a_in[i] && images[i] && (a_next[i] || i == nl - 1), "fst_wn_stack_infer: null operand of layer %d", i);
-    FST_REQUIRE(a_bs[i] >= (int64_t)n * L && a_bs[i] % 4 == 0 && fst_aligned16(a_in[i]) && fst_aligned16(images[i]) && fst_aligned16(a_next[i]),
-                "fst_wn_stack_infer: layer %d: batch stride %lld smaller than a sample, or an operand that is not 16-byte aligned", i,
-                (long long)a_bs[i]);
-    FST_REQUIRE(i == nl - 1 || a_in[i + 1] == a_next[i], "fst_wn_stack_infer: the input of layer %d is not the a_next of layer %d",
-                i + 1, i);
-    // (a_next[i] == a_in[i - 1] is fine: the two-buffer alternation — see wn_stack_infer_kernel)
-    FST_REQUIRE(i == nl - 1 || a_next[i] != a_in[i], "fst_wn_stack_infer: layer %d would store a_next over the input its neighbouring "
-                "tiles still read", i);
-    WnFwdParams& q = p.layer[i];
-    q.a = a_in[i]; q.a_bs = a_bs[i]; q.u0 = u0; q.u0_bs = u0_bs; q.img = static_cast<const char*>(images[i]);
-    q.ts = nullptr; q.acts = nullptr; q.a_next = i == nl - 1 ? nullptr : a_next[i]; q.out = out;
-    q.B = B; q.L = L; q.n = n; q.h = h; q.dil = 1 << i; q.first = i == 0; q.last = i == nl - 1;
-    q.CH = wn_ch(n); q.CH2 = wn_ch2(h); q.tiles_per_seq = L / 256; q.n_wg = 0;
-  }
-  p.nl = nl;
-  const int cus = fst_cu_count_or(256);
-  if (int rc = fst_allow_full_lds((const void*)wn_stack_infer_kernel, "fst_wn_stack_infer")) return rc;
-  fst_wn_set_route(FST_WN_ROUTE_STACK_INFER, 8, 0, 0, 0, B < cus ? B : cus, 1, 1, L / 256, 3, nl, WN_FWD_LDS(8));
-  hipLaunchKernelGGL(wn_stack_infer_kernel, dim3((unsigned)(B < cus ? B : cus)), dim3(512), WN_FWD_LDS(8), (hipStream_t)stream, p);
-  FST_LAUNCH_CHECK();
-  return 0;
+  return wn_layer_fwd_launch("fst_wn_layer_fwd", true, a, a_bs, u0, u0_bs, image, image_bytes, ts, acts, a_next, out, first, last, B, L,
+                             n, h, dil, numel_a, stream);
 }
 
 extern "C" int fst_wn_layer_infer(const float* a, int64_t a_bs, const float* u0, int64_t u0_bs, const void* image,
                                   int64_t image_bytes, float* a_next, float* out, int first, int last, int B, int L, int n, int h,
                                   int dil, int64_t numel_a, void* stream) {
   fst_wn_clear_route();
-  FST_REQUIRE(a && u0 && image && out && (last || a_next), "fst_wn_layer_infer: null operand");
-  FST_REQUIRE(B > 0 && L > 0 && n > 0 && n < 128 && h > 0 && dil > 0, "fst_wn_layer_infer: B=%d L=%d n=%d h=%d dil=%d (needs n < 128)",
-              B, L, n, h, dil);
-  FST_REQUIRE((long long)B * n * L == (long long)numel_a, "fst_wn_layer_infer: B*n*L = %d*%d*%d does not match the element count %lld "
-              "of the [B, n, L] tensors", B, n, L, (long long)numel_a);
-  FST_REQUIRE(image_bytes == fst_wn_image_bytes(n, h), "fst_wn_layer_infer: image is %lld bytes, expected %lld",
-              (long long)image_bytes, (long long)fst_wn_image_bytes(n, h));
-  FST_REQUIRE(B == 1 || (a_bs >= (int64_t)n * L && u0_bs >= (int64_t)h * L), "fst_wn_layer_infer: batch stride smaller than a sample");
-  FST_REQUIRE(L % 4 == 0 && a_bs % 4 == 0 && u0_bs % 4 == 0 && fst_aligned16(a) && fst_aligned16(u0) && fst_aligned16(image) &&
-              fst_aligned16(a_next) && fst_aligned16(out), "fst_wn_layer_infer: needs L %% 4 == 0 and 16-byte aligned tensors (L=%d)", L);
-  FST_REQUIRE(last || a_next != a, "fst_wn_layer_infer: a_next is a — a tile's neighbours read a's halo while the tile stores a_next");
-  WnFwdParams p;
-  p.a = a; p.a_bs = a_bs; p.u0 = u0; p.u0_bs = u0_bs; p.img = static_cast<const char*>(image);
-  p.ts = nullptr; p.acts = nullptr; p.a_next = last ? nullptr : a_next; p.out = out;
-  p.B = B; p.L = L; p.n = n; p.h = h; p.dil = dil; p.first = first ? 1 : 0; p.last = last ? 1 : 0;
-  p.CH = wn_ch(n); p.CH2 = wn_ch2(h);
-  // the tile-size choice of fst_wn_layer_fwd
-  const int cus = fst_cu_count_or(256);
-  const int nw = (L % 256 == 0 && (long long)B * (L / 256) >= cus) ? 8 : 4;
-  const int tn = 32 * nw;
-  p.tiles_per_seq = (L + tn - 1) / tn;
-  p.n_wg = B * p.tiles_per_seq;
-  if (nw == 8) {
-    if (int rc = fst_allow_full_lds((const void*)wn_layer_infer_kernel<8>, "fst_wn_layer_infer")) return rc;
-    fst_wn_set_route(FST_WN_ROUTE_LAYER_INFER, 8, 0, 0, 0, p.n_wg, 1, 1, p.tiles_per_seq, 3, 1, WN_FWD_LDS(8));
-    hipLaunchKernelGGL(wn_layer_infer_kernel<8>, dim3((unsigned)p.n_wg), dim3(512), WN_FWD_LDS(8), (hipStream_t)stream, p);
-  } else {
-    if (int rc = fst_allow_full_lds((const void*)wn_layer_infer_kernel<4>, "fst_wn_layer_infer")) return rc;
-    fst_wn_set_route(FST_WN_ROUTE_LAYER_INFER, 4, 0, 0, 0, p.n_wg, 1, 1, p.tiles_per_seq, 3, 1, WN_FWD_LDS(4));
-    hipLaunchKernelGGL(wn_layer_infer_kernel<4>, dim3((unsigned)p.n_wg), dim3(256), WN_FWD_LDS(4), (hipStream_t)stream, p);
-  }
-  FST_LAUNCH_CHECK();
-  return 0;
+  return wn_layer_fwd_launch("fst_wn_layer_infer", false, a, a_bs, u0, u0_bs, image, image_bytes, nullptr, nullptr, a_next, out, first,
+                             last, B, L, n, h, dil, numel_a, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes
 import math
 import os
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -1342,178 +1342,181 @@ def wn_fused_ok(n: int, h: int, L: int, *tensors: Tensor, kernel: int = 3) -> bo
     return all(t.data_ptr() % 16 == 0 and t.stride(0) % 4 == 0 for t in tensors)
 
 
-def wn_pack_layer(in_w: Tensor, cond_w: Tensor, in_b: Tensor, cond_b: Tensor, rs_w: Tensor, rs_b: Tensor, n: int, h: int,
-                  last: bool) -> Tensor:
-    """One layer's weight image for the fused kernels (cached for the step like every packed weight)."""
-    lib = _lib.load()
-    if in_w.dim() != 3 or in_w.size(0) != 2 * n or in_w.size(1) != n:
-        raise ValueError(f"wn_pack_layer: in_w must be [2n, n, taps], got {tuple(in_w.shape)} for n={n}")
-    key = None
-    if _PACK_CACHE is not None:
-        key = ("wn", n, h, last) + tuple((t.data_ptr(), t._version) for t in (in_w, cond_w, in_b, cond_b, rs_w, rs_b))
-        hit = _PACK_CACHE.get(key)
-        if hit is not None:
-            return hit[0]
-    nbytes = lib.fst_wn_image_bytes(n, h)
-    img = torch.empty(nbytes // 4, device=in_w.device, dtype=torch.float32)
-    src = [t.contiguous() for t in (in_w, cond_w, in_b, cond_b, rs_w, rs_b)]
-    check(lib.fst_wn_pack(*[ptr(t) for t in src], n, h, in_w.size(2), int(last), ptr(img), nbytes, stream_ptr()), "fst_wn_pack")
-    if key is not None:
-        _PACK_CACHE[key] = (img, in_w, cond_w, in_b, cond_b, rs_w, rs_b, src)
-    return img
-
-
 WN_PACK_MAX_LAYERS = 10      # (WS_MAXL of csrc/wn_fused.hip)
 
 
-def _pack_stack(keys, nl: int, launch_one, launch_stack, keep):
-    """Images of the layers of a stack, each cached under its per-layer key: all layers in one launch (``launch_stack``) unless
-    some are cached already or the stack is deeper than the kernels' layer tables; ``keep(i, img)``: the cache entry (the image
-    first, then what must stay alive)."""
+class _WnImages(NamedTuple):
+    """One of the WN weight-image formats (forward, backward, projected backward, data gradient) for the ``nl`` layers at hand, as
+    the cache protocol below needs it.  Of layer i: ``key(i)`` the cache key, ``nbytes(i)`` the image size, ``sources(i)`` the
+    weights it is made of.  ``one(i, src, img)`` launches the per-layer pack (None: the format has none), ``stack(srcs, imgs)`` the
+    pack of all layers — ``src`` / ``srcs[i]`` being contiguous ``sources(i)``.  A cache entry is the image, then what must stay
+    alive: the weights (a data pointer in a key cannot be recycled) and the contiguous copies handed to the kernel."""
+    nl: int
+    key: Callable
+    nbytes: Callable
+    sources: Callable
+    one: Optional[Callable]
+    stack: Callable
+
+
+def _pack_one(f: _WnImages, i: int) -> Tensor:
+    """Layer i's image: the cached one inside a ``pack_cache`` scope that holds it, else a new one (cached for the step like
+    every packed weight)."""
     if _PACK_CACHE is not None:
-        hits = [_PACK_CACHE.get(k) for k in keys]
-        if all(hit is not None for hit in hits):
-            return [hit[0] for hit in hits]
-    if nl > WN_PACK_MAX_LAYERS or (_PACK_CACHE is not None and any(hit is not None for hit in hits)):
-        return [launch_one(i) for i in range(nl)]
-    imgs = launch_stack()
+        hit = _PACK_CACHE.get(f.key(i))
+        if hit is not None:
+            return hit[0]
+    src = [t.contiguous() for t in f.sources(i)]
+    img = torch.empty(f.nbytes(i) // 4, device=src[0].device, dtype=torch.float32)
+    f.one(i, src, img)
     if _PACK_CACHE is not None:
-        for i, (k, img) in enumerate(zip(keys, imgs)):
-            _PACK_CACHE[k] = keep(i, img)
+        _PACK_CACHE[f.key(i)] = (img, *f.sources(i), src)
+    return img
+
+
+def _pack_stack(f: _WnImages) -> List[Tensor]:
+    """Images of the layers of a stack, each cached under its per-layer key: all layers in one launch unless all are cached
+    already — or, where the format has a per-layer pack, some are, or the stack is deeper than the kernels' layer tables."""
+    hits = [None if _PACK_CACHE is None else _PACK_CACHE.get(f.key(i)) for i in range(f.nl)]
+    if _PACK_CACHE is not None and all(hit is not None for hit in hits):
+        return [hit[0] for hit in hits]
+    if f.one is not None and (f.nl > WN_PACK_MAX_LAYERS or any(hit is not None for hit in hits)):
+        return [_pack_one(f, i) for i in range(f.nl)]
+    srcs = [[t.contiguous() for t in f.sources(i)] for i in range(f.nl)]
+    imgs = [torch.empty(f.nbytes(i) // 4, device=srcs[i][0].device, dtype=torch.float32) for i in range(f.nl)]
+    f.stack(srcs, imgs)
+    if _PACK_CACHE is not None:
+        for i, img in enumerate(imgs):
+            _PACK_CACHE[f.key(i)] = (img, *f.sources(i), srcs[i])
     return imgs
+
+
+def _wn_fwd_images(who: str, layers: Sequence[Sequence[Tensor]], lasts: Sequence[bool], n: int, h: int) -> _WnImages:
+    lib, nl = _lib.load(), len(layers)
+    for in_w in (l[0] for l in layers):
+        if in_w.dim() != 3 or in_w.size(0) != 2 * n or in_w.size(1) != n:
+            raise ValueError(f"{who}: in_w must be [2n, n, taps], got {tuple(in_w.shape)} for n={n}")
+    nbytes = lib.fst_wn_image_bytes(n, h)
+    return _WnImages(
+        nl, lambda i: ("wn", n, h, lasts[i]) + tuple((t.data_ptr(), t._version) for t in layers[i]), lambda i: nbytes,
+        lambda i: layers[i],
+        lambda i, src, img: check(lib.fst_wn_pack(*[ptr(t) for t in src], n, h, layers[i][0].size(2), int(lasts[i]), ptr(img), nbytes,
+                                                  stream_ptr()), "fst_wn_pack"),
+        lambda srcs, imgs: check(lib.fst_wn_pack_stack(*[_ptr_table([l[j] for l in srcs]) for j in range(6)], nl, n, h,
+                                                       layers[0][0].size(2), _ptr_table(imgs), nbytes, stream_ptr()),
+                                 "fst_wn_pack_stack"))
+
+
+def wn_pack_layer(in_w: Tensor, cond_w: Tensor, in_b: Tensor, cond_b: Tensor, rs_w: Tensor, rs_b: Tensor, n: int, h: int,
+                  last: bool) -> Tensor:
+    """One layer's weight image for the fused kernels (cached for the step like every packed weight)."""
+    return _pack_one(_wn_fwd_images("wn_pack_layer", [(in_w, cond_w, in_b, cond_b, rs_w, rs_b)], [last], n, h), 0)
 
 
 def wn_pack_layers(layers: Sequence[Sequence[Tensor]], n: int, h: int) -> List[Tensor]:
     """``wn_pack_layer`` for every layer of a WN stack (``layers[i]`` = in_w, cond_w, in_b, cond_b, rs_w, rs_b; the top layer is the
     last one) in one launch (fst_wn_pack_stack), cached per layer as the per-layer calls are."""
-    lib, nl = _lib.load(), len(layers)
-    for in_w in (l[0] for l in layers):
-        if in_w.dim() != 3 or in_w.size(0) != 2 * n or in_w.size(1) != n:
-            raise ValueError(f"wn_pack_layers: in_w must be [2n, n, taps], got {tuple(in_w.shape)} for n={n}")
-    keys = [("wn", n, h, i == nl - 1) + tuple((t.data_ptr(), t._version) for t in layers[i]) for i in range(nl)]
-    src = [[t.contiguous() for t in l] for l in layers]
+    nl = len(layers)
+    return _pack_stack(_wn_fwd_images("wn_pack_layers", layers, [i == nl - 1 for i in range(nl)], n, h))
 
-    def launch_stack():
-        nbytes = lib.fst_wn_image_bytes(n, h)
-        imgs = [torch.empty(nbytes // 4, device=src[0][0].device, dtype=torch.float32) for _ in range(nl)]
-        check(lib.fst_wn_pack_stack(*[_ptr_table([l[j] for l in src]) for j in range(6)], nl, n, h, layers[0][0].size(2),
-                                    _ptr_table(imgs), nbytes, stream_ptr()), "fst_wn_pack_stack")
-        return imgs
-    return _pack_stack(keys, nl, lambda i: wn_pack_layer(*layers[i], n, h, i == nl - 1), launch_stack,
-                       lambda i, img: (img, *layers[i], src[i]))
+
+def _wn_bwd_images(rs_ws: Sequence[Tensor], lasts: Sequence[bool], n: int, acc_order: bool) -> _WnImages:
+    lib, nl = _lib.load(), len(rs_ws)
+    nbytes = lambda i: lib.fst_wn_bwd_image_bytes(n, int(lasts[i]))
+    return _WnImages(
+        nl, lambda i: ("wn_bwd", n, lasts[i], acc_order, rs_ws[i].data_ptr(), rs_ws[i]._version), nbytes, lambda i: (rs_ws[i],),
+        lambda i, src, img: check(lib.fst_wn_pack_bwd(ptr(src[0]), n, int(lasts[i]), int(acc_order), ptr(img), nbytes(i), stream_ptr()),
+                                  "fst_wn_pack_bwd"),
+        lambda srcs, imgs: check(lib.fst_wn_pack_bwd_stack(_ptr_table([s_[0] for s_ in srcs]), nl, n, int(acc_order), _ptr_table(imgs),
+                                                           lib.fst_wn_bwd_image_bytes(n, 0), stream_ptr()), "fst_wn_pack_bwd_stack"))
+
+
+def wn_pack_bwd(rs_w: Tensor, n: int, last: bool, acc_order: bool = False) -> Tensor:
+    """``acc_order``: the image of fst_wn_stack_bwd (the d_a stages in the k-order of an accumulator tile's rows)."""
+    return _pack_one(_wn_bwd_images([rs_w], [last], n, acc_order), 0)
 
 
 def wn_pack_bwd_layers(rs_ws: Sequence[Tensor], n: int, acc_order: bool = False) -> List[Tensor]:
     """``wn_pack_bwd`` for every layer of a stack in one launch (fst_wn_pack_bwd_stack)."""
-    lib, nl = _lib.load(), len(rs_ws)
-    keys = [("wn_bwd", n, i == nl - 1, acc_order, w.data_ptr(), w._version) for i, w in enumerate(rs_ws)]
-    src = [w.contiguous() for w in rs_ws]
-
-    def launch_stack():
-        imgs = [torch.empty(lib.fst_wn_bwd_image_bytes(n, int(i == nl - 1)) // 4, device=src[0].device, dtype=torch.float32)
-                for i in range(nl)]
-        check(lib.fst_wn_pack_bwd_stack(_ptr_table(src), nl, n, int(acc_order), _ptr_table(imgs), lib.fst_wn_bwd_image_bytes(n, 0),
-                                        stream_ptr()), "fst_wn_pack_bwd_stack")
-        return imgs
-    return _pack_stack(keys, nl, lambda i: wn_pack_bwd(rs_ws[i], n, i == nl - 1, acc_order), launch_stack,
-                       lambda i, img: (img, rs_ws[i], src[i]))
+    nl = len(rs_ws)
+    return _pack_stack(_wn_bwd_images(rs_ws, [i == nl - 1 for i in range(nl)], n, acc_order))
 
 
 def wn_pack_bwd_proj_layers(rs_ws: Sequence[Tensor], end_w: Tensor, n: int) -> List[Tensor]:
     """The images of ``wn_stack_bwd`` on the end conv's cotangent (fst_wn_pack_bwd_proj_stack, one launch per stack): layer i's
     d_a stages in accumulator order, then (W_end·W_skip,i)ᵀ as its skip stages.  Cached per layer under the versions of both
-    weights (they are fixed for a step: the same images serve every backward pass of it)."""
+    weights (they are fixed for a step: the same images serve every backward pass of it).  There is no per-layer pack: unless
+    every layer is cached, the whole stack is packed again."""
     lib, nl, h2 = _lib.load(), len(rs_ws), end_w.size(0)
     if nl > WN_PACK_MAX_LAYERS or tuple(end_w.shape) != (h2, n, 1) or h2 > 64:
         raise ValueError(f"wn_pack_bwd_proj_layers: {nl} layers, end_w {tuple(end_w.shape)} (at most {WN_PACK_MAX_LAYERS} layers, "
                          f"end_w [2h <= 64, n = {n}, 1])")
-    keys = [("wn_bwd_proj", n, h2, i == nl - 1, w.data_ptr(), w._version, end_w.data_ptr(), end_w._version)
-            for i, w in enumerate(rs_ws)]
-    if _PACK_CACHE is not None:
-        hits = [_PACK_CACHE.get(k) for k in keys]
-        if all(hit is not None for hit in hits):
-            return [hit[0] for hit in hits]
-    src, end_c = [w.contiguous() for w in rs_ws], end_w.contiguous()
-    imgs = [torch.empty(lib.fst_wn_bwd_proj_image_bytes(n, h2, int(i == nl - 1)) // 4, device=end_w.device, dtype=torch.float32)
-            for i in range(nl)]
-    check(lib.fst_wn_pack_bwd_proj_stack(_ptr_table(src), ptr(end_c), nl, n, h2, _ptr_table(imgs),
-                                         lib.fst_wn_bwd_proj_image_bytes(n, h2, 0), stream_ptr()), "fst_wn_pack_bwd_proj_stack")
-    if _PACK_CACHE is not None:
-        for i, (k, img) in enumerate(zip(keys, imgs)):
-            _PACK_CACHE[k] = (img, rs_ws[i], src[i], end_w, end_c)
-    return imgs
+    return _pack_stack(_WnImages(
+        nl, lambda i: ("wn_bwd_proj", n, h2, i == nl - 1, rs_ws[i].data_ptr(), rs_ws[i]._version, end_w.data_ptr(), end_w._version),
+        lambda i: lib.fst_wn_bwd_proj_image_bytes(n, h2, int(i == nl - 1)), lambda i: (rs_ws[i], end_w), None,
+        lambda srcs, imgs: check(lib.fst_wn_pack_bwd_proj_stack(_ptr_table([s_[0] for s_ in srcs]), ptr(srcs[0][1]), nl, n, h2,
+                                                                _ptr_table(imgs), lib.fst_wn_bwd_proj_image_bytes(n, h2, 0),
+                                                                stream_ptr()), "fst_wn_pack_bwd_proj_stack")))
+
+
+def _wn_dgrad_images(in_ws: Sequence[Tensor], cond_ws: Sequence[Tensor], n: int, h: int) -> _WnImages:
+    lib, nl = _lib.load(), len(in_ws)
+    nbytes = lib.fst_wn_dgrad_image_bytes(n)
+    return _WnImages(
+        nl, lambda i: ("wn_dgrad", n, h, in_ws[i].data_ptr(), in_ws[i]._version, cond_ws[i].data_ptr(), cond_ws[i]._version),
+        lambda i: nbytes, lambda i: (in_ws[i], cond_ws[i]),
+        lambda i, src, img: check(lib.fst_wn_pack_dgrad(ptr(src[0]), ptr(src[1]), n, h, in_ws[i].size(2), ptr(img), nbytes, stream_ptr()),
+                                  "fst_wn_pack_dgrad"),
+        lambda srcs, imgs: check(lib.fst_wn_pack_dgrad_stack(_ptr_table([s_[0] for s_ in srcs]), _ptr_table([s_[1] for s_ in srcs]), nl, n,
+                                                             h, in_ws[0].size(2), _ptr_table(imgs), nbytes, stream_ptr()),
+                                 "fst_wn_pack_dgrad_stack"))
+
+
+def wn_pack_dgrad(in_w: Tensor, cond_w: Tensor, n: int, h: int) -> Tensor:
+    return _pack_one(_wn_dgrad_images([in_w], [cond_w], n, h), 0)
 
 
 def wn_pack_dgrad_layers(in_ws: Sequence[Tensor], cond_ws: Sequence[Tensor], n: int, h: int) -> List[Tensor]:
     """``wn_pack_dgrad`` for every layer of a stack in one launch (fst_wn_pack_dgrad_stack)."""
-    lib, nl = _lib.load(), len(in_ws)
-    keys = [("wn_dgrad", n, h, a.data_ptr(), a._version, c.data_ptr(), c._version) for a, c in zip(in_ws, cond_ws)]
-    src = [(a.contiguous(), c.contiguous()) for a, c in zip(in_ws, cond_ws)]
-
-    def launch_stack():
-        nbytes = lib.fst_wn_dgrad_image_bytes(n)
-        imgs = [torch.empty(nbytes // 4, device=src[0][0].device, dtype=torch.float32) for _ in range(nl)]
-        check(lib.fst_wn_pack_dgrad_stack(_ptr_table([s_[0] for s_ in src]), _ptr_table([s_[1] for s_ in src]), nl, n, h,
-                                          in_ws[0].size(2), _ptr_table(imgs), nbytes, stream_ptr()), "fst_wn_pack_dgrad_stack")
-        return imgs
-    return _pack_stack(keys, nl, lambda i: wn_pack_dgrad(in_ws[i], cond_ws[i], n, h), launch_stack,
-                       lambda i, img: (img, in_ws[i], cond_ws[i], src[i]))
+    return _pack_stack(_wn_dgrad_images(in_ws, cond_ws, n, h))
 
 
-def wn_layer_fwd(a: Tensor, u0: Tensor, img: Tensor, ts: Tensor, acts: Optional[Tensor], a_next: Optional[Tensor], out: Tensor,
-                 first: bool, last: bool, n: int, h: int, dil: int) -> None:
+def _wn_layer_forward(save: bool, a: Tensor, u0: Tensor, img: Tensor, ts: Optional[Tensor], acts: Optional[Tensor],
+                      a_next: Optional[Tensor], out: Tensor, first: bool, last: bool, n: int, h: int, dil: int) -> None:
+    """One WN layer's forward launch: fst_wn_layer_fwd (``save``: ``ts``, and ``acts`` where given, are written) or
+    fst_wn_layer_infer (neither exists)."""
     lib = _lib.load()
     a_bs, L = _ncl(a, "a")
     u0_bs, _ = _ncl(u0, "u0")
     B = a.size(0)
     numel = _same_numel(a, out, acts, a_next)
-    if ts.numel() != 2 * numel or not ts.is_contiguous():
+    if save and (ts.numel() != 2 * numel or not ts.is_contiguous()):
         raise ValueError("wn_layer_fwd: ts must be the contiguous [B, 2n, L] partner of a")
+    if save:
+        fn, who, key, saved = lib.fst_wn_layer_fwd, "fst_wn_layer_fwd", "wn_layer_fwd_kernel", (ptr(ts), ptr(acts))
+    else:
+        fn, who, key, saved = lib.fst_wn_layer_infer, "fst_wn_layer_infer", "wn_layer_infer_kernel", ()
     t0 = KERNEL_TIMER.begin() if KERNEL_TIMER is not None else None
-    check(lib.fst_wn_layer_fwd(ptr(a), a_bs, ptr(u0), u0_bs, ptr(img), img.numel() * 4, ptr(ts), ptr(acts), ptr(a_next), ptr(out),
-                               int(first), int(last), B, L, n, h, dil, numel, stream_ptr()), "fst_wn_layer_fwd")
+    check(fn(ptr(a), a_bs, ptr(u0), u0_bs, ptr(img), img.numel() * 4, *saved, ptr(a_next), ptr(out), int(first), int(last), B, L, n, h,
+             dil, numel, stream_ptr()), who)
     if t0 is not None:
         rs_rows = n if last else 2 * n
         flops = 2.0 * B * L * (2 * n * (3 * n + h) + rs_rows * n)
-        rows = n + h + (0 if first else n) + (0 if last else n) + n + 2 * n + (n if acts is not None else 0)
-        KERNEL_TIMER.end("wn_layer_fwd_kernel", t0, flops, 4.0 * B * L * rows)
+        rows = n + h + (0 if first else n) + (0 if last else n) + n                   # a, u0, out in; a_next, out out
+        rows += (2 * n if save else 0) + (n if acts is not None else 0)               # t,s / acts out
+        KERNEL_TIMER.end(key, t0, flops, 4.0 * B * L * rows)
+
+
+def wn_layer_fwd(a: Tensor, u0: Tensor, img: Tensor, ts: Tensor, acts: Optional[Tensor], a_next: Optional[Tensor], out: Tensor,
+                 first: bool, last: bool, n: int, h: int, dil: int) -> None:
+    _wn_layer_forward(True, a, u0, img, ts, acts, a_next, out, first, last, n, h, dil)
 
 
 def wn_layer_infer(a: Tensor, u0: Tensor, img: Tensor, a_next: Optional[Tensor], out: Tensor, first: bool, last: bool, n: int, h: int,
                    dil: int) -> None:
     """``wn_layer_fwd`` for a pass that no backward follows (fst_wn_layer_infer): neither the gate halves nor acts are stored;
     ``a_next`` and ``out`` receive the same bits.  ``a_next`` must not be ``a``."""
-    lib = _lib.load()
-    a_bs, L = _ncl(a, "a")
-    u0_bs, _ = _ncl(u0, "u0")
-    B = a.size(0)
-    numel = _same_numel(a, out, a_next)
-    t0 = KERNEL_TIMER.begin() if KERNEL_TIMER is not None else None
-    check(lib.fst_wn_layer_infer(ptr(a), a_bs, ptr(u0), u0_bs, ptr(img), img.numel() * 4, ptr(a_next), ptr(out), int(first), int(last),
-                                 B, L, n, h, dil, numel, stream_ptr()), "fst_wn_layer_infer")
-    if t0 is not None:
-        rs_rows = n if last else 2 * n
-        flops = 2.0 * B * L * (2 * n * (3 * n + h) + rs_rows * n)
-        rows = n + h + (0 if first else n) + (0 if last else n) + n                   # a, u0, out in; a_next, out out — no t,s rows
-        KERNEL_TIMER.end("wn_layer_infer_kernel", t0, flops, 4.0 * B * L * rows)
-
-
-def wn_pack_bwd(rs_w: Tensor, n: int, last: bool, acc_order: bool = False) -> Tensor:
-    """``acc_order``: the image of fst_wn_stack_bwd (the d_a stages in the k-order of an accumulator tile's rows)."""
-    lib = _lib.load()
-    key = None
-    if _PACK_CACHE is not None:
-        key = ("wn_bwd", n, last, acc_order, rs_w.data_ptr(), rs_w._version)
-        hit = _PACK_CACHE.get(key)
-        if hit is not None:
-            return hit[0]
-    nbytes = lib.fst_wn_bwd_image_bytes(n, int(last))
-    img = torch.empty(nbytes // 4, device=rs_w.device, dtype=torch.float32)
-    src = rs_w.contiguous()
-    check(lib.fst_wn_pack_bwd(ptr(src), n, int(last), int(acc_order), ptr(img), nbytes, stream_ptr()), "fst_wn_pack_bwd")
-    if key is not None:
-        _PACK_CACHE[key] = (img, rs_w, src)
-    return img
+    _wn_layer_forward(False, a, u0, img, None, None, a_next, out, first, last, n, h, dil)
 
 
 def wn_bwd_partials(n_layers: int, B: int, L: int, device) -> Tensor:
@@ -1548,23 +1551,6 @@ def wn_layer_bwd(d_a: Optional[Tensor], d_out: Tensor, ts: Tensor, img: Tensor, 
     if sums_out is not None:
         return torch.sum(part[: 2 * n], dim=1, out=sums_out)
     return part.sum(dim=1)[: 2 * n]
-
-
-def wn_pack_dgrad(in_w: Tensor, cond_w: Tensor, n: int, h: int) -> Tensor:
-    lib = _lib.load()
-    key = None
-    if _PACK_CACHE is not None:
-        key = ("wn_dgrad", n, h, in_w.data_ptr(), in_w._version, cond_w.data_ptr(), cond_w._version)
-        hit = _PACK_CACHE.get(key)
-        if hit is not None:
-            return hit[0]
-    nbytes = lib.fst_wn_dgrad_image_bytes(n)
-    img = torch.empty(nbytes // 4, device=in_w.device, dtype=torch.float32)
-    src = (in_w.contiguous(), cond_w.contiguous())
-    check(lib.fst_wn_pack_dgrad(ptr(src[0]), ptr(src[1]), n, h, in_w.size(2), ptr(img), nbytes, stream_ptr()), "fst_wn_pack_dgrad")
-    if key is not None:
-        _PACK_CACHE[key] = (img, in_w, cond_w, src)
-    return img
 
 
 WN_DGRAD_TILE = 512       # time samples per workgroup of fst_wn_layer_dgrad (the library checks the row-sum extent against it)
@@ -1648,11 +1634,10 @@ def wn_stack_fwd_ok(n: int, h: int, L: int, nl: int, B: int) -> bool:
     return bool(lib.fst_wn_stack_fwd_ok(n, h, L, nl)) and B * (L // 256) >= 2 * 256 and B >= 256
 
 
-def wn_stack_fwd(a_list: Sequence[Tensor], u0: Tensor, imgs: Sequence[Tensor], ts_list: Sequence[Tensor], out: Tensor, n: int,
-                 h: int) -> None:
-    """All layers of a WN stack's forward in one launch (csrc/wn_fused.hip, fst_wn_stack_fwd): ``a_list[i]`` = input of layer i
-    (``a_list[0]`` = the start conv's output; ``a_list[i + 1]`` is written as layer i's a_next), ``imgs[i]`` = ``wn_pack_layer`` image,
-    ``ts_list[i]`` [B, 2n, L] written, ``out`` [B, n, L] the skip sum."""
+def _wn_stack_forward(save: bool, a_list: Sequence[Tensor], u0: Tensor, imgs: Sequence[Tensor], ts_list: Sequence[Tensor], out: Tensor,
+                      n: int, h: int) -> None:
+    """The forward of a whole WN stack in one launch: fst_wn_stack_fwd (``save``: every ``ts_list[i]`` is written) or
+    fst_wn_stack_infer (``ts_list`` is empty)."""
     lib = _lib.load()
     nl = len(imgs)
     B, L = u0.size(0), u0.size(2)
@@ -1662,33 +1647,33 @@ def wn_stack_fwd(a_list: Sequence[Tensor], u0: Tensor, imgs: Sequence[Tensor], t
     for ts in ts_list:
         if ts.numel() != 2 * numel or not ts.is_contiguous():
             raise ValueError("wn_stack_fwd: every ts must be the contiguous [B, 2n, L] partner of a")
+    if save:
+        fn, who, key, saved = lib.fst_wn_stack_fwd, "fst_wn_stack_fwd", "wn_stack_fwd_kernel", (_ptr_table(ts_list),)
+    else:
+        fn, who, key, saved = lib.fst_wn_stack_infer, "fst_wn_stack_infer", "wn_stack_infer_kernel", ()
     t0 = KERNEL_TIMER.begin() if KERNEL_TIMER is not None else None
-    check(lib.fst_wn_stack_fwd(_ptr_table(a_list), bs, _ptr_table(imgs), imgs[0].numel() * 4, _ptr_table(ts_list),
-                               _ptr_table(list(a_list[1:]) + [None]), ptr(u0), u0_bs, ptr(out), nl, B, L, n, h, numel, stream_ptr()),
-          "fst_wn_stack_fwd")
+    check(fn(_ptr_table(a_list), bs, _ptr_table(imgs), imgs[0].numel() * 4, *saved, _ptr_table(list(a_list[1:]) + [None]), ptr(u0), u0_bs,
+             ptr(out), nl, B, L, n, h, numel, stream_ptr()), who)
     if t0 is not None:
         flops = 2.0 * B * L * (nl * 2 * n * (3 * n + h) + (2 * nl - 1) * n * n)
-        rows = nl * (n + h + 2 * n) + (nl - 1) * (n + 2 * n) + n      # a, u0 in, t,s out; a_next out, out in/out (first layer: out only)
-        KERNEL_TIMER.end("wn_stack_fwd_kernel", t0, flops, 4.0 * B * L * rows)
+        rows = nl * (n + h) + (nl - 1) * (n + 2 * n) + n             # a, u0 in; a_next out, out in/out (first layer: out only)
+        rows += nl * 2 * n if save else 0                            # t,s out
+        KERNEL_TIMER.end(key, t0, flops, 4.0 * B * L * rows)
+
+
+def wn_stack_fwd(a_list: Sequence[Tensor], u0: Tensor, imgs: Sequence[Tensor], ts_list: Sequence[Tensor], out: Tensor, n: int,
+                 h: int) -> None:
+    """All layers of a WN stack's forward in one launch (csrc/wn_fused.hip, fst_wn_stack_fwd): ``a_list[i]`` = input of layer i
+    (``a_list[0]`` = the start conv's output; ``a_list[i + 1]`` is written as layer i's a_next), ``imgs[i]`` = ``wn_pack_layer`` image,
+    ``ts_list[i]`` [B, 2n, L] written, ``out`` [B, n, L] the skip sum."""
+    _wn_stack_forward(True, a_list, u0, imgs, ts_list, out, n, h)
 
 
 def wn_stack_infer(a_list: Sequence[Tensor], u0: Tensor, imgs: Sequence[Tensor], out: Tensor, n: int, h: int) -> None:
     """``wn_stack_fwd`` for a pass that no backward follows (fst_wn_stack_infer): no gate halves are stored.  ``a_list[i]`` = input
     of layer i, ``a_list[i + 1]`` written as its a_next — entries two apart may be the same tensor (two buffers in alternation),
     neighbours may not."""
-    lib = _lib.load()
-    nl = len(imgs)
-    B, L = u0.size(0), u0.size(2)
-    u0_bs, _ = _ncl(u0, "u0")
-    numel = _same_numel(out, *a_list)
-    bs = (ctypes.c_int64 * nl)(*[_ncl(a, "a")[0] for a in a_list])
-    t0 = KERNEL_TIMER.begin() if KERNEL_TIMER is not None else None
-    check(lib.fst_wn_stack_infer(_ptr_table(a_list), bs, _ptr_table(imgs), imgs[0].numel() * 4, _ptr_table(list(a_list[1:]) + [None]),
-                                 ptr(u0), u0_bs, ptr(out), nl, B, L, n, h, numel, stream_ptr()), "fst_wn_stack_infer")
-    if t0 is not None:
-        flops = 2.0 * B * L * (nl * 2 * n * (3 * n + h) + (2 * nl - 1) * n * n)
-        rows = nl * (n + h) + (nl - 1) * (n + 2 * n) + n             # a, u0 in; a_next out, out in/out (first layer: out only) — no t,s rows
-        KERNEL_TIMER.end("wn_stack_infer_kernel", t0, flops, 4.0 * B * L * rows)
+    _wn_stack_forward(False, a_list, u0, imgs, (), out, n, h)
 
 
 def _ptr_table(ts: Sequence[Optional[Tensor]]):
@@ -1787,32 +1772,26 @@ def _wn_forward(specs: WNSpecs, u0: Tensor, flat: Tensor, save: bool = True):
     y0 = torch.empty(B, n, L, device=dev, dtype=torch.float32) if infer else empty_with_slack(B, n, L, dev)
     a = S.start.forward(u0, None, W[0], None, W[1], y=y0)
     fused = wn_fused_ok(n, h, L, a, u0, kernel=S.kernel)
-    if fused and infer:
-        out = torch.empty(B, n, L, device=dev, dtype=torch.float32)
-        imgs = wn_pack_layers([_wn_layer(S, W, i) for i in range(nl)], n, h)
-        other = torch.empty_like(a) if nl > 1 else None
-        a_list = [a if i % 2 == 0 else other for i in range(nl)]
-        if wn_stack_fwd_ok(n, h, L, nl, B):
-            wn_stack_infer(a_list, u0, imgs, out, n, h)
-        else:
-            for i in range(nl):
-                last = i == nl - 1
-                wn_layer_infer(a_list[i], u0, imgs[i], None if last else a_list[i + 1], out, i == 0, last, n, h, 2 ** i)
-        return S.end.forward(out, None, W[4], None, W[5]), True, ()
     if fused:
         # per layer: dilated conv + cond rows → gate in registers → res_skip → residual / skip adds; acts = t·s is not written
         # (the res_skip weight gradient re-forms it from the saved halves while staging)
         out = torch.empty(B, n, L, device=dev, dtype=torch.float32)
         imgs = wn_pack_layers([_wn_layer(S, W, i) for i in range(nl)], n, h)
-        a_list = [a] + [empty_with_slack(B, n, L, dev) for _ in range(nl - 1)]
-        ts_list = [torch.empty(B, 2 * n, L, device=dev, dtype=torch.float32) for _ in range(nl)]
+        if infer:                                                  # nothing is kept: two buffers in alternation, no gate halves
+            other = torch.empty_like(a) if nl > 1 else None
+            a_list, ts_list = [a if i % 2 == 0 else other for i in range(nl)], None
+        else:
+            a_list = [a] + [empty_with_slack(B, n, L, dev) for _ in range(nl - 1)]
+            ts_list = [torch.empty(B, 2 * n, L, device=dev, dtype=torch.float32) for _ in range(nl)]
         if wn_stack_fwd_ok(n, h, L, nl, B):
-            wn_stack_fwd(a_list, u0, imgs, ts_list, out, n, h)     # ONE launch: persistent workgroups walk their batch elements
+            _wn_stack_forward(not infer, a_list, u0, imgs, ts_list or (), out, n, h)     # ONE launch: persistent workgroups walk their batch elements
         else:
             for i in range(nl):
                 last = i == nl - 1
-                wn_layer_fwd(a_list[i], u0, imgs[i], ts_list[i], None, None if last else a_list[i + 1], out, i == 0, last, n,
-                             h, 2 ** i)
+                _wn_layer_forward(not infer, a_list[i], u0, imgs[i], ts_list[i] if ts_list else None, None,
+                                  None if last else a_list[i + 1], out, i == 0, last, n, h, 2 ** i)
+        if infer:
+            return S.end.forward(out, None, W[4], None, W[5]), True, ()
         acts_list = ts_list
     else:
         lib = _lib.load()

@@ -1,5 +1,5 @@
-"""The forward-only WN kernels (fst_wn_layer_infer / fst_wn_stack_infer), checked without a GPU: the two launchers name exactly the
-instances we think, tests/test_gpu_wn_infer.py declares a case for each of them, and the header, the ctypes binding and the route
+"""The forward-only WN kernels (fst_wn_layer_infer / fst_wn_stack_infer), checked without a GPU: the launchers they share with the saving
+entry points name exactly the instances we think, each on its side of ``save``, tests/test_gpu_wn_infer.py declares a case for each of them, and the header, the ctypes binding and the route
 names agree on the new symbols."""
 import os
 import re
@@ -8,7 +8,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import test_gpu_wn_infer as I  # noqa: E402
-from test_wn_routes_cpu import CSRC, _body, _instances  # noqa: E402
+from test_wn_routes_cpu import CSRC, _body, _instances, fwd_launcher  # noqa: E402
 
 from feature_level_style_transfer_for_tsc_amd import _lib, ops  # noqa: E402
 
@@ -22,14 +22,24 @@ def _launched(body: str) -> set:
 
 
 def test_the_launchers_name_exactly_the_infer_kernels():
-    layer, stack = _body(FUSED, 'extern "C" int fst_wn_layer_infer('), _body(FUSED, 'extern "C" int fst_wn_stack_infer(')
+    # each pair of entry points shares one launcher (fwd_launcher: the infer entry points pass save = false and do nothing else,
+    # the saving ones save = true), and inside it the kernels are named on their own side of that selection only
+    (layer_save, layer, layer_rest), (stack_save, stack, stack_rest) = fwd_launcher("layer"), fwd_launcher("stack")
     assert _launched(layer) == {"wn_layer_infer_kernel<4>", "wn_layer_infer_kernel<8>"} == _instances(layer, "wn_layer_infer_kernel")
     assert _launched(stack) == {"wn_stack_infer_kernel"}
-    for body in (layer, stack):                                # neither can reach a saving kernel
-        assert "wn_layer_fwd_kernel" not in body and "wn_stack_fwd_kernel" not in body
-    # and the saving launchers are as they were: none of them launches an infer kernel
-    for head in ('extern "C" int fst_wn_layer_fwd(', 'extern "C" int fst_wn_stack_fwd('):
-        assert "infer" not in _body(FUSED, head)
+    for side in (layer, stack):                                # neither can reach a saving kernel
+        assert "wn_layer_fwd_kernel" not in side and "wn_stack_fwd_kernel" not in side
+    # and the saving sides are as the saving launchers were: none of them launches an infer kernel
+    assert _launched(layer_save) == {"wn_layer_fwd_kernel<4>", "wn_layer_fwd_kernel<8>"} == _instances(layer_save, "wn_layer_fwd_kernel")
+    assert _launched(stack_save) == {"wn_stack_fwd_kernel"}
+    for side in (layer_save, stack_save):
+        assert "infer" not in side.lower()
+    for rest in (layer_rest, stack_rest):                      # no kernel, no launch and no route family outside the selection
+        assert "_kernel" not in rest and "hipLaunchKernelGGL" not in rest and "FST_WN_ROUTE" not in rest
+    assert "FST_WN_ROUTE_LAYER_INFER" in layer and "FST_WN_ROUTE_LAYER_FWD" in layer_save
+    assert "FST_WN_ROUTE_STACK_INFER" in stack and "FST_WN_ROUTE_STACK_FWD" in stack_save
+    whole = _body(FUSED, "static int wn_layer_fwd_launch(") + _body(FUSED, "static int wn_stack_fwd_launch(")
+    assert _launched(whole) == _launched(layer) | _launched(layer_save) | _launched(stack) | _launched(stack_save)
     # the infer kernels are the saving tile body with the stores compiled out, nothing else
     assert re.search(r"wn_fwd_tile<NW, false>\(", FUSED) and re.search(r"wn_fwd_tile<8, false>\(", FUSED)
     assert re.search(r"template <int NW, bool SAVE = true>\s*\n__device__ __forceinline__ void wn_fwd_tile\(", FUSED)

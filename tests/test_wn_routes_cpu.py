@@ -22,12 +22,53 @@ def _instances(body: str, kernel: str) -> set:
     return {f"{kernel}<{', '.join(a.strip() for a in args.split(','))}>" for args in re.findall(kernel + r"<([^<>()]*)>", body)}
 
 
+def _until(text: str, i: int, stops: str, pair: str) -> int:
+    """From ``i`` on, the index of the first character of ``stops`` outside any ``pair`` of brackets — or of the bracket that
+    closes the pair ``i`` is in."""
+    depth = 0
+    while depth > 0 or (text[i] not in stops and text[i] != pair[1]):
+        depth += (text[i] == pair[0]) - (text[i] == pair[1])
+        i += 1
+    return i
+
+
+def _save_sides(body: str):
+    """A launcher that takes ``bool save``, split by that selection: (the text reachable only when saving, only when not, the
+    rest).  The selections are the arms of every ``save ? x : y`` (a nested ?: stands in parentheses) and the blocks of every
+    ``if (save) { } else { }``."""
+    yes, no, rest, pos = "", "", "", 0
+    for m in re.finditer(r"\bsave \?|\bif \(save\) \{", body):
+        assert m.start() >= pos, "a save selection inside a save selection"
+        if m.group().endswith("?"):
+            mid = _until(body, m.end(), ":", "()")
+            assert body[mid] == ":"
+            end = _until(body, mid + 1, ",;", "()")
+            arms, after = (body[m.end(): mid], body[mid + 1: end]), end
+        else:
+            mid = _until(body, m.end(), "", "{}")
+            assert body[mid:].startswith("} else {")
+            end = _until(body, mid + len("} else {"), "", "{}")
+            arms, after = (body[m.end(): mid], body[mid + len("} else {"): end]), end + 1
+        rest, yes, no, pos = rest + body[pos: m.start()], yes + arms[0], no + arms[1], after
+    return yes, no, rest + body[pos:]
+
+
+def fwd_launcher(form: str):
+    """(saving side, no-save side, rest) of the launcher behind fst_wn_<form>_fwd and fst_wn_<form>_infer (form: layer / stack),
+    after checking that these two pass save = true and save = false and do nothing else."""
+    fused = open(os.path.join(CSRC, "wn_fused.hip")).read()
+    for name, save in ((f"fst_wn_{form}_fwd", "true"), (f"fst_wn_{form}_infer", "false")):
+        stmts = [s.strip() for s in _body(fused, f'extern "C" int {name}(').split("{", 1)[1].split(";") if s.strip()]
+        assert len(stmts) == 2 and stmts[0] == "fst_wn_clear_route()", (name, stmts)
+        assert re.match(r"return wn_" + form + r"_fwd_launch\(\"" + name + r"\", " + save + r",[^()]*\)$", stmts[1]), (name, stmts[1])
+    return _save_sides(_body(fused, f"static int wn_{form}_fwd_launch("))
+
+
 def source_instances():
     wgrad = open(os.path.join(CSRC, "wn_wgrad.hip")).read()
-    fused = open(os.path.join(CSRC, "wn_fused.hip")).read()
     ww = _instances(_body(wgrad, "static int ww_launch("), "wn_wgrad_kernel")
     tz = _instances(_body(wgrad, 'extern "C" int fst_dense_tap_wgrad('), "tz_wgrad_kernel")
-    fw = _instances(_body(fused, 'extern "C" int fst_wn_layer_fwd('), "wn_layer_fwd_kernel")
+    fw = _instances(fwd_launcher("layer")[0], "wn_layer_fwd_kernel")      # what fst_wn_layer_fwd can reach: the saving side
     return ww, tz, fw
 
 
