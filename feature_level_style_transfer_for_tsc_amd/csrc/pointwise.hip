@@ -69,12 +69,16 @@ __device__ __forceinline__ void block_sum2(float& a, float& b) {
               (long long)(numel))
 
 
-// 16-byte path of the per-row kernels (L a multiple of 4, 16-byte aligned bases): a row of L/4 float4 is covered by
-// tpr = min(256, pow2ceil(L/4)) threads and a 256-thread block walks 256/tpr rows at a time, so every lane carries a
-// 16-byte load whatever L is (the dword path keeps half the block idle at L = 512 and issues 4x the loads).
+// The per-row kernels are templates over the element V a thread loads and stores: float4 on the 16-byte path, float on the
+// dword path.  A row of nv elements V is covered by 2^shift consecutive threads and a block of T threads walks T >> shift rows
+// at a time.
+// 16-byte path (L a multiple of 4, 16-byte aligned bases): 2^shift = min(256, pow2ceil(L/4)), so every lane carries a 16-byte
+// load whatever L is (the dword path keeps half the block idle at L = 512 and issues 4x the loads).
+// Dword path (everything else): a fixed shift — the whole 256-thread block of a BatchNorm kernel on one row, a wave of
+// row_sum's 1024 threads per batch row.
 struct RowVec {
   int shift;   // log2(threads per row)
-  int L4;      // float4 per row
+  int nv;      // elements V per row
 };
 static inline bool vec_ok(int L, std::initializer_list<const void*> ptrs) {
   if (L % 4 != 0) return false;
@@ -84,10 +88,34 @@ static inline bool vec_ok(int L, std::initializer_list<const void*> ptrs) {
 }
 static inline RowVec row_vec(int L) {
   RowVec v;
-  v.L4 = L / 4;
+  v.nv = L / 4;
   v.shift = 0;
-  while ((1 << v.shift) < v.L4 && v.shift < 8) ++v.shift;
+  while ((1 << v.shift) < v.nv && v.shift < 8) ++v.shift;
   return v;
+}
+static inline RowVec row_dword(int L, int shift) { return RowVec{shift, L}; }
+constexpr int BN_DWORD_SHIFT = 8, ROW_SUM_DWORD_SHIFT = 6;
+
+// In a kernel.  The dword path's shift is fixed, so its instances take it as a constant and not from the argument, and mask the
+// row group r with the count of row groups (which changes nothing, threadIdx.x < T — but the optimiser is not told): the
+// BatchNorm instances then fold r to 0 and get a block-uniform row index, scalar loads of the per-channel values, unrolled
+// shuffle trees and unswitched loops.
+template <class V>
+__device__ __forceinline__ RowVec row_geometry(RowVec rv, int dword_shift) {
+  if (std::is_same_v<V, float>) rv.shift = dword_shift;
+  return rv;
+}
+template <class V>
+__device__ __forceinline__ int row_group(RowVec rv, int T) {
+  const int r = threadIdx.x >> rv.shift;
+  return std::is_same_v<V, float> ? r & ((T >> rv.shift) - 1) : r;
+}
+
+// The one choice a per-row launcher makes: launch(V{}, geometry) with V = float4 when `vec`, V = float otherwise.
+template <class Launch>
+static inline void launch_rows(bool vec, int L, int dword_shift, Launch launch) {
+  if (vec) launch(float4{}, row_vec(L));
+  else launch(float{}, row_dword(L, dword_shift));
 }
 
 // ---------------------------------------------------------------- row sums (bias gradients)
@@ -107,40 +135,35 @@ __device__ __forceinline__ float block_sum1024(float s) {
   return r;
 }
 
-__global__ __launch_bounds__(1024) void row_sum_kernel(const float* x, long long x_bs, int B, int C, int L, float* out) {
-  const int c = blockIdx.x;
-  float s = 0.f;
-  for (int b = threadIdx.x >> 6; b < B; b += 16) {           // a wave per batch row
-    const float* row = x + (long long)b * x_bs + (long long)c * L;
-    for (int t = threadIdx.x & 63; t < L; t += 64) s += row[t];
-  }
-  s = block_sum1024(s);
-  if (threadIdx.x == 0) out[c] = s;
+// a thread's running sum: two halves (s0, s1) of a float4, added at the end; one (s0) of a float
+__device__ __forceinline__ void row_sum_add(float& s0, float& s1, const float4& v) {
+  s0 += v.x + v.y;
+  s1 += v.z + v.w;
 }
+__device__ __forceinline__ void row_sum_add(float& s0, float&, float v) { s0 += v; }
 
-__global__ __launch_bounds__(1024) void row_sum_vec_kernel(const float* x, long long x_bs, int B, int C, int L, float* out, RowVec rv) {
-  // threads-per-row = min(256, pow2ceil(L/4)); 1024/tpr batch rows in flight per pass
-  const int c = blockIdx.x, r = threadIdx.x >> rv.shift, t0 = threadIdx.x & ((1 << rv.shift) - 1), rpp = 1024 >> rv.shift;
+template <class V>
+__global__ __launch_bounds__(1024) void row_sum_kernel(const float* x, long long x_bs, int B, int C, int L, float* out, RowVec rv) {
+  rv = row_geometry<V>(rv, ROW_SUM_DWORD_SHIFT);
+  const int c = blockIdx.x, r = row_group<V>(rv, 1024), t0 = threadIdx.x & ((1 << rv.shift) - 1), rpp = 1024 >> rv.shift;
   float s0 = 0.f, s1 = 0.f;
   for (int b = r; b < B; b += rpp) {
-    const float4* row = reinterpret_cast<const float4*>(x + (long long)b * x_bs + (long long)c * L);
-    for (int t = t0; t < rv.L4; t += 1 << rv.shift) {
-      const float4 v = row[t];
-      s0 += v.x + v.y;
-      s1 += v.z + v.w;
+    const V* row = reinterpret_cast<const V*>(x + (long long)b * x_bs + (long long)c * L);
+    for (int t = t0; t < rv.nv; t += 1 << rv.shift) {
+      const V v = row[t];
+      row_sum_add(s0, s1, v);
     }
   }
-  const float s = block_sum1024(s0 + s1);
+  const float s = block_sum1024(std::is_same_v<V, float> ? s0 : s0 + s1);
   if (threadIdx.x == 0) out[c] = s;
 }
 
 extern "C" int fst_row_sum(const float* x, int64_t x_bs, int B, int C, int L, float* out, void* stream) {
   FST_REQUIRE(x && out && B > 0 && C > 0 && L > 0, "fst_row_sum: bad arguments");
   FST_REQUIRE(B == 1 || x_bs >= (int64_t)C * L, "fst_row_sum: batch stride %lld < C*L = %lld", (long long)x_bs, (long long)C * L);
-  if (vec_ok(L, {x}) && x_bs % 4 == 0)
-    hipLaunchKernelGGL(row_sum_vec_kernel, dim3(C), dim3(1024), 0, (hipStream_t)stream, x, (long long)x_bs, B, C, L, out, row_vec(L));
-  else
-    hipLaunchKernelGGL(row_sum_kernel, dim3(C), dim3(1024), 0, (hipStream_t)stream, x, (long long)x_bs, B, C, L, out);
+  launch_rows(vec_ok(L, {x}) && x_bs % 4 == 0, L, ROW_SUM_DWORD_SHIFT, [&](auto v, RowVec rv) {
+    hipLaunchKernelGGL(row_sum_kernel<decltype(v)>, dim3(C), dim3(1024), 0, (hipStream_t)stream, x, (long long)x_bs, B, C, L, out, rv);
+  });
   FST_LAUNCH_CHECK();
   return 0;
 }
@@ -154,38 +177,27 @@ extern "C" int fst_row_sum(const float* x, int64_t x_bs, int B, int C, int L, fl
 // (x − k)² carry ~1e-6; the slot stores (count, k, Σ(x−k), Σ(x−k)²) and fst_bn_finalize turns the slots into (count, mean, M2)
 // and merges them with Chan's formula IN DOUBLE, in slot order: no atomics, no zero fill, the same bits on every run, and
 // slots of other ranks (their own shifts) merge the same way.
-__global__ __launch_bounds__(256) void bn_stats_kernel(const float* y, int B, int C, int L, float* part) {
-  const int c = blockIdx.x;
-  const float k = y[(long long)c * L];
-  float s1 = 0.f, s2 = 0.f;
-  int n = 0;
-  for (int b = blockIdx.y; b < B; b += gridDim.y) {
-    const float* row = y + ((long long)b * C + c) * L;
-    for (int t = threadIdx.x; t < L; t += 256) {
-      const float d = row[t] - k;
-      s1 += d; s2 += d * d;
-    }
-    n += L;
-  }
-  block_sum2(s1, s2);
-  if (threadIdx.x == 0) {
-    float* o = part + ((long long)c * FST_BN_SLOTS + blockIdx.y) * 4;
-    o[0] = (float)n; o[1] = k; o[2] = s1; o[3] = s2;
-  }
+//
+// Σ(x−k) and Σ(x−k)² take one element more
+__device__ __forceinline__ void bn_moments_add(float& s1, float& s2, float v, float k) {
+  const float d = v - k;
+  s1 += d; s2 += d * d;
+}
+__device__ __forceinline__ void bn_moments_add(float& s1, float& s2, float4 v, float k) {
+  const float dx = v.x - k, dy = v.y - k, dz = v.z - k, dw = v.w - k;
+  s1 += (dx + dy) + (dz + dw);
+  s2 += (dx * dx + dy * dy) + (dz * dz + dw * dw);
 }
 
-__global__ __launch_bounds__(256) void bn_stats_vec_kernel(const float* y, int B, int C, int L, float* part, RowVec rv) {
-  const int c = blockIdx.x, r = threadIdx.x >> rv.shift, t0 = threadIdx.x & ((1 << rv.shift) - 1), rpp = 256 >> rv.shift;
+template <class V>
+__global__ __launch_bounds__(256) void bn_stats_kernel(const float* y, int B, int C, int L, float* part, RowVec rv) {
+  rv = row_geometry<V>(rv, BN_DWORD_SHIFT);
+  const int c = blockIdx.x, r = row_group<V>(rv, 256), t0 = threadIdx.x & ((1 << rv.shift) - 1), rpp = 256 >> rv.shift;
   const float k = y[(long long)c * L];
   float s1 = 0.f, s2 = 0.f;
   for (int b = blockIdx.y + r * gridDim.y; b < B; b += rpp * gridDim.y) {
-    const float4* row = reinterpret_cast<const float4*>(y + ((long long)b * C + c) * L);
-    for (int t = t0; t < rv.L4; t += 1 << rv.shift) {
-      const float4 v = row[t];
-      const float dx = v.x - k, dy = v.y - k, dz = v.z - k, dw = v.w - k;
-      s1 += (dx + dy) + (dz + dw);
-      s2 += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-    }
+    const V* row = reinterpret_cast<const V*>(y + ((long long)b * C + c) * L);
+    for (int t = t0; t < rv.nv; t += 1 << rv.shift) bn_moments_add(s1, s2, row[t], k);
   }
   block_sum2(s1, s2);
   if (threadIdx.x == 0) {
@@ -200,10 +212,9 @@ extern "C" int fst_bn_stats(const float* y, int B, int C, int L, float* part, in
   FST_REQUIRE(y && part && B > 0 && C > 0 && L > 0, "fst_bn_stats: bad arguments");
   FST_REQUIRE_EXTENT("fst_bn_stats", B, C, L, numel);
   // always FST_BN_SLOTS workgroups per channel: a slot without samples stores a zero count, so no slot is left unwritten
-  if (vec_ok(L, {y}))
-    hipLaunchKernelGGL(bn_stats_vec_kernel, dim3(C, FST_BN_SLOTS), dim3(256), 0, (hipStream_t)stream, y, B, C, L, part, row_vec(L));
-  else
-    hipLaunchKernelGGL(bn_stats_kernel, dim3(C, FST_BN_SLOTS), dim3(256), 0, (hipStream_t)stream, y, B, C, L, part);
+  launch_rows(vec_ok(L, {y}), L, BN_DWORD_SHIFT, [&](auto v, RowVec rv) {
+    hipLaunchKernelGGL(bn_stats_kernel<decltype(v)>, dim3(C, FST_BN_SLOTS), dim3(256), 0, (hipStream_t)stream, y, B, C, L, part, rv);
+  });
   FST_LAUNCH_CHECK();
   return 0;
 }
@@ -269,47 +280,38 @@ __device__ __forceinline__ float bn_pre_join(float ya, float sca, float sha, flo
   v += bn_pre(yb, scb, shb);
   return v;
 }
-
-__global__ __launch_bounds__(256) void bn_apply_kernel(const float* y, const float* stats, const float* res,
-                                                       const float* res_stats, float* out, int C, int L, int relu) {
-  const int bc = blockIdx.x;           // b*C + c
-  const int c = bc % C;
-  const float sc = stats[2 * C + c], sh = stats[3 * C + c];
-  float rsc = 1.f, rsh = 0.f;
-  if (res && res_stats) { rsc = res_stats[2 * C + c]; rsh = res_stats[3 * C + c]; }
-  const long long base = (long long)bc * L;
-  for (int t = threadIdx.x; t < L; t += 256) {
-    float v = res ? bn_pre_join(y[base + t], sc, sh, res[base + t], rsc, rsh) : bn_pre(y[base + t], sc, sh);
-    if (relu) v = v < 0.f ? 0.f : v;
-    out[base + t] = v;
-  }
+__device__ __forceinline__ float4 bn_pre(float4 y, float sc, float sh) {
+  return make_float4(bn_pre(y.x, sc, sh), bn_pre(y.y, sc, sh), bn_pre(y.z, sc, sh), bn_pre(y.w, sc, sh));
 }
+__device__ __forceinline__ float4 bn_pre_join(float4 ya, float sca, float sha, float4 yb, float scb, float shb) {
+  return make_float4(bn_pre_join(ya.x, sca, sha, yb.x, scb, shb), bn_pre_join(ya.y, sca, sha, yb.y, scb, shb),
+                     bn_pre_join(ya.z, sca, sha, yb.z, scb, shb), bn_pre_join(ya.w, sca, sha, yb.w, scb, shb));
+}
+// the forward's ReLU: NaN stays NaN
+__device__ __forceinline__ float bn_relu(float v) { return v < 0.f ? 0.f : v; }
+__device__ __forceinline__ float4 bn_relu(float4 v) { return make_float4(bn_relu(v.x), bn_relu(v.y), bn_relu(v.z), bn_relu(v.w)); }
 
-__global__ __launch_bounds__(256) void bn_apply_vec_kernel(const float* y, const float* stats, const float* res,
-                                                           const float* res_stats, float* out, int rows, int C, int L,
-                                                           int relu, RowVec rv) {
-  const int r = threadIdx.x >> rv.shift, t0 = threadIdx.x & ((1 << rv.shift) - 1), rpp = 256 >> rv.shift;
+template <class V>
+__global__ __launch_bounds__(256) void bn_apply_kernel(const float* y, const float* stats, const float* res,
+                                                       const float* res_stats, float* out, int rows, int C, int L,
+                                                       int relu, RowVec rv) {
+  rv = row_geometry<V>(rv, BN_DWORD_SHIFT);
+  const int r = row_group<V>(rv, 256), t0 = threadIdx.x & ((1 << rv.shift) - 1), rpp = 256 >> rv.shift;
   const int bc = blockIdx.x * rpp + r;           // b*C + c
   if (bc >= rows) return;
   const int c = bc % C;
   const float sc = stats[2 * C + c], sh = stats[3 * C + c];
   float rsc = 1.f, rsh = 0.f;
   if (res && res_stats) { rsc = res_stats[2 * C + c]; rsh = res_stats[3 * C + c]; }
-  const long long base = (long long)bc * rv.L4;
-  const float4* y4 = reinterpret_cast<const float4*>(y) + base;
-  const float4* r4 = res ? reinterpret_cast<const float4*>(res) + base : nullptr;
-  float4* o4 = reinterpret_cast<float4*>(out) + base;
-  for (int t = t0; t < rv.L4; t += 1 << rv.shift) {
-    float4 v = y4[t];
-    if (r4) {
-      const float4 q = r4[t];
-      v.x = bn_pre_join(v.x, sc, sh, q.x, rsc, rsh); v.y = bn_pre_join(v.y, sc, sh, q.y, rsc, rsh);
-      v.z = bn_pre_join(v.z, sc, sh, q.z, rsc, rsh); v.w = bn_pre_join(v.w, sc, sh, q.w, rsc, rsh);
-    } else {
-      v.x = bn_pre(v.x, sc, sh); v.y = bn_pre(v.y, sc, sh); v.z = bn_pre(v.z, sc, sh); v.w = bn_pre(v.w, sc, sh);
-    }
-    if (relu) { v.x = v.x < 0.f ? 0.f : v.x; v.y = v.y < 0.f ? 0.f : v.y; v.z = v.z < 0.f ? 0.f : v.z; v.w = v.w < 0.f ? 0.f : v.w; }
-    o4[t] = v;
+  const long long base = (long long)bc * rv.nv;
+  const V* yv = reinterpret_cast<const V*>(y) + base;
+  const V* qv = res ? reinterpret_cast<const V*>(res) + base : nullptr;
+  V* ov = reinterpret_cast<V*>(out) + base;
+  for (int t = t0; t < rv.nv; t += 1 << rv.shift) {
+    V v = yv[t];
+    v = qv ? bn_pre_join(v, sc, sh, qv[t], rsc, rsh) : bn_pre(v, sc, sh);
+    if (relu) v = bn_relu(v);
+    ov[t] = v;
   }
 }
 
@@ -317,14 +319,11 @@ extern "C" int fst_bn_apply(const float* y, const float* stats, const float* res
                             int B, int C, int L, int relu, int64_t numel, void* stream) {
   FST_REQUIRE(y && stats && out && B > 0 && C > 0 && L > 0, "fst_bn_apply: bad arguments");
   FST_REQUIRE_EXTENT("fst_bn_apply", B, C, L, numel);
-  if (vec_ok(L, {y, res, out})) {
-    const RowVec rv = row_vec(L);
+  launch_rows(vec_ok(L, {y, res, out}), L, BN_DWORD_SHIFT, [&](auto v, RowVec rv) {
     const int rpp = 256 >> rv.shift;
-    hipLaunchKernelGGL(bn_apply_vec_kernel, dim3((B * C + rpp - 1) / rpp), dim3(256), 0, (hipStream_t)stream, y, stats, res,
-                       res_stats, out, B * C, C, L, relu, rv);
-  } else {
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(B * C), dim3(256), 0, (hipStream_t)stream, y, stats, res, res_stats, out, C, L, relu);
-  }
+    hipLaunchKernelGGL(bn_apply_kernel<decltype(v)>, dim3((B * C + rpp - 1) / rpp), dim3(256), 0, (hipStream_t)stream, y, stats,
+                       res, res_stats, out, B * C, C, L, relu, rv);
+  });
   FST_LAUNCH_CHECK();
   return 0;
 }
@@ -337,27 +336,21 @@ extern "C" int fst_bn_apply(const float* y, const float* stats, const float* res
 //
 // dy under the ReLU mask: `o` is the forward output, or the pre-activation it was the max(·, 0) of — same sign test
 __device__ __forceinline__ float bn_masked(float g, float o) { return o > 0.f ? g : 0.f; }
-__device__ __forceinline__ float4 bn_masked4(float4 g, float4 o) {
+__device__ __forceinline__ float4 bn_masked(float4 g, float4 o) {
   g.x = bn_masked(g.x, o.x); g.y = bn_masked(g.y, o.y); g.z = bn_masked(g.z, o.z); g.w = bn_masked(g.w, o.w);
   return g;
 }
-__device__ __forceinline__ float4 bn_pre4(float4 y, float sc, float sh) {
-  return make_float4(bn_pre(y.x, sc, sh), bn_pre(y.y, sc, sh), bn_pre(y.z, sc, sh), bn_pre(y.w, sc, sh));
-}
-__device__ __forceinline__ float4 bn_pre_join4(float4 ya, float sca, float sha, float4 yb, float scb, float shb) {
-  return make_float4(bn_pre_join(ya.x, sca, sha, yb.x, scb, shb), bn_pre_join(ya.y, sca, sha, yb.y, scb, shb),
-                     bn_pre_join(ya.z, sca, sha, yb.z, scb, shb), bn_pre_join(ya.w, sca, sha, yb.w, scb, shb));
-}
 // terms of Σ dyʹ and Σ dyʹ·x̂
+__device__ __forceinline__ float bn_g(float g) { return g; }
+__device__ __forceinline__ float bn_g(float4 g) {
+#pragma clang fp contract(off)
+  return (g.x + g.y) + (g.z + g.w);
+}
 __device__ __forceinline__ float bn_gx(float g, float y, float mean, float invstd) {
 #pragma clang fp contract(off)
   return g * (y - mean) * invstd;
 }
-__device__ __forceinline__ float bn_g4(float4 g) {
-#pragma clang fp contract(off)
-  return (g.x + g.y) + (g.z + g.w);
-}
-__device__ __forceinline__ float bn_gx4(float4 g, float4 v, float mean, float invstd) {
+__device__ __forceinline__ float bn_gx(float4 g, float4 v, float mean, float invstd) {
 #pragma clang fp contract(off)
   return (g.x * (v.x - mean) + g.y * (v.y - mean) + g.z * (v.z - mean) + g.w * (v.w - mean)) * invstd;
 }
@@ -367,54 +360,47 @@ __device__ __forceinline__ float bn_dx_unscaled(float g, float y, float mean, fl
   const float xh = (y - mean) * invstd;
   return __builtin_fmaf(-xh, m2, g - m1);
 }
-__device__ __forceinline__ float4 bn_dx4(float4 g, float4 v, float mean, float invstd, float scale, float m1, float m2) {
+__device__ __forceinline__ float4 bn_dx_unscaled(float4 g, float4 v, float mean, float invstd, float m1, float m2) {
+  return make_float4(bn_dx_unscaled(g.x, v.x, mean, invstd, m1, m2), bn_dx_unscaled(g.y, v.y, mean, invstd, m1, m2),
+                     bn_dx_unscaled(g.z, v.z, mean, invstd, m1, m2), bn_dx_unscaled(g.w, v.w, mean, invstd, m1, m2));
+}
+__device__ __forceinline__ float bn_dx(float scale, float u) {
 #pragma clang fp contract(off)
-  return make_float4(scale * bn_dx_unscaled(g.x, v.x, mean, invstd, m1, m2), scale * bn_dx_unscaled(g.y, v.y, mean, invstd, m1, m2),
-                     scale * bn_dx_unscaled(g.z, v.z, mean, invstd, m1, m2), scale * bn_dx_unscaled(g.w, v.w, mean, invstd, m1, m2));
+  return scale * u;
+}
+__device__ __forceinline__ float4 bn_dx(float scale, float4 u) {
+#pragma clang fp contract(off)
+  return make_float4(scale * u.x, scale * u.y, scale * u.z, scale * u.w);
+}
+// the row's Σ_t dx takes d = scale·u: the dword path has always fused that product into the sum, the 16-byte path adds the
+// rounded products
+__device__ __forceinline__ float bn_row_sum_add(float rs, float scale, float u, float) { return __builtin_fmaf(scale, u, rs); }
+__device__ __forceinline__ float bn_row_sum_add(float rs, float, float4, float4 d) {
+#pragma clang fp contract(off)
+  return rs + bn_g(d);
 }
 
 // relu with out == nullptr: the mask is the sign of bn_pre(y), the value the forward took max(·, 0) of — `out` is not read.
+template <class V>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* dy, const float* y, const float* out,
-                                                            const float* stats, int B, int C, int L, int relu, float* red) {
+                                                            const float* stats, int B, int C, int L, int relu,
+                                                            float* red, RowVec rv) {
 #pragma clang fp contract(off)
-  const int c = blockIdx.x;
-  const float mean = stats[c], invstd = stats[C + c], sc = stats[2 * C + c], sh = stats[3 * C + c];
-  float s1 = 0.f, s2 = 0.f;
-  for (int b = blockIdx.y; b < B; b += gridDim.y) {
-    const long long base = ((long long)b * C + c) * L;
-    for (int t = threadIdx.x; t < L; t += 256) {
-      float g = dy[base + t];
-      const float v = y[base + t];
-      if (relu) g = bn_masked(g, out ? out[base + t] : bn_pre(v, sc, sh));
-      s1 += g;
-      s2 += bn_gx(g, v, mean, invstd);
-    }
-  }
-  block_sum2(s1, s2);
-  if (threadIdx.x == 0) {
-    red[(long long)c * FST_BN_SLOTS + blockIdx.y] = s1;
-    red[((long long)C + c) * FST_BN_SLOTS + blockIdx.y] = s2;
-  }
-}
-
-__global__ __launch_bounds__(256) void bn_bwd_reduce_vec_kernel(const float* dy, const float* y, const float* out,
-                                                                const float* stats, int B, int C, int L, int relu,
-                                                                float* red, RowVec rv) {
-#pragma clang fp contract(off)
-  const int c = blockIdx.x, r = threadIdx.x >> rv.shift, t0 = threadIdx.x & ((1 << rv.shift) - 1), rpp = 256 >> rv.shift;
+  rv = row_geometry<V>(rv, BN_DWORD_SHIFT);
+  const int c = blockIdx.x, r = row_group<V>(rv, 256), t0 = threadIdx.x & ((1 << rv.shift) - 1), rpp = 256 >> rv.shift;
   const float mean = stats[c], invstd = stats[C + c], sc = stats[2 * C + c], sh = stats[3 * C + c];
   float s1 = 0.f, s2 = 0.f;
   for (int b = blockIdx.y + r * gridDim.y; b < B; b += rpp * gridDim.y) {
-    const long long base = ((long long)b * C + c) * rv.L4;
-    const float4* dy4 = reinterpret_cast<const float4*>(dy) + base;
-    const float4* y4 = reinterpret_cast<const float4*>(y) + base;
-    const float4* o4 = reinterpret_cast<const float4*>(out) + base;          // not dereferenced when out is null
-    for (int t = t0; t < rv.L4; t += 1 << rv.shift) {
-      float4 g = dy4[t];
-      const float4 v = y4[t];
-      if (relu) g = bn_masked4(g, out ? o4[t] : bn_pre4(v, sc, sh));
-      s1 += bn_g4(g);
-      s2 += bn_gx4(g, v, mean, invstd);
+    const long long base = ((long long)b * C + c) * rv.nv;
+    const V* dyv = reinterpret_cast<const V*>(dy) + base;
+    const V* yv = reinterpret_cast<const V*>(y) + base;
+    const V* ov = reinterpret_cast<const V*>(out) + base;                    // not dereferenced when out is null
+    for (int t = t0; t < rv.nv; t += 1 << rv.shift) {
+      V g = dyv[t];
+      const V v = yv[t];
+      if (relu) g = bn_masked(g, out ? ov[t] : bn_pre(v, sc, sh));
+      s1 += bn_g(g);
+      s2 += bn_gx(g, v, mean, invstd);
     }
   }
   block_sum2(s1, s2);
@@ -429,12 +415,10 @@ extern "C" int fst_bn_bwd_reduce(const float* dy, const float* y, const float* o
   FST_REQUIRE(dy && y && stats && red && B > 0 && C > 0 && L > 0, "fst_bn_bwd_reduce: bad arguments");
   FST_REQUIRE_EXTENT("fst_bn_bwd_reduce", B, C, L, numel);
   if (!relu) out = nullptr;
-  if (vec_ok(L, {dy, y, out}))
-    hipLaunchKernelGGL(bn_bwd_reduce_vec_kernel, dim3(C, FST_BN_SLOTS), dim3(256), 0, (hipStream_t)stream, dy,
-                       y, out, stats, B, C, L, relu, red, row_vec(L));
-  else
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(C, FST_BN_SLOTS), dim3(256), 0, (hipStream_t)stream, dy, y,
-                       out, stats, B, C, L, relu, red);
+  launch_rows(vec_ok(L, {dy, y, out}), L, BN_DWORD_SHIFT, [&](auto v, RowVec rv) {
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel<decltype(v)>, dim3(C, FST_BN_SLOTS), dim3(256), 0, (hipStream_t)stream, dy, y, out,
+                       stats, B, C, L, relu, red, rv);
+  });
   FST_LAUNCH_CHECK();
   return 0;
 }
@@ -442,53 +426,27 @@ extern "C" int fst_bn_bwd_reduce(const float* dy, const float* y, const float* o
 // The join relu(BN_a(ya) + BN_b(yb)): both branches' partials from one walk over dy, ya, yb.  The mask is the sign of
 // bn_pre_join, and Σ dyʹ is the same number for both branches (same dy, same mask, same order), so it is summed once and
 // stored twice.  Each Σ dyʹ·x̂ goes through block_sum2 exactly as in the single-branch kernel.
+template <class V>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_join_kernel(const float* dy, const float* ya, const float* yb,
                                                                  const float* sa, const float* sb, int B, int C, int L,
-                                                                 float* reda, float* redb) {
+                                                                 float* reda, float* redb, RowVec rv) {
 #pragma clang fp contract(off)
-  const int c = blockIdx.x;
-  const float meana = sa[c], invstda = sa[C + c], sca = sa[2 * C + c], sha = sa[3 * C + c];
-  const float meanb = sb[c], invstdb = sb[C + c], scb = sb[2 * C + c], shb = sb[3 * C + c];
-  float s1 = 0.f, s2a = 0.f, s2b = 0.f, unused = 0.f;
-  for (int b = blockIdx.y; b < B; b += gridDim.y) {
-    const long long base = ((long long)b * C + c) * L;
-    for (int t = threadIdx.x; t < L; t += 256) {
-      const float va = ya[base + t], vb = yb[base + t];
-      const float g = bn_masked(dy[base + t], bn_pre_join(va, sca, sha, vb, scb, shb));
-      s1 += g;
-      s2a += bn_gx(g, va, meana, invstda);
-      s2b += bn_gx(g, vb, meanb, invstdb);
-    }
-  }
-  block_sum2(s1, s2a);
-  block_sum2(s2b, unused);
-  if (threadIdx.x == 0) {
-    reda[(long long)c * FST_BN_SLOTS + blockIdx.y] = s1;
-    reda[((long long)C + c) * FST_BN_SLOTS + blockIdx.y] = s2a;
-    redb[(long long)c * FST_BN_SLOTS + blockIdx.y] = s1;
-    redb[((long long)C + c) * FST_BN_SLOTS + blockIdx.y] = s2b;
-  }
-}
-
-__global__ __launch_bounds__(256) void bn_bwd_reduce_join_vec_kernel(const float* dy, const float* ya, const float* yb,
-                                                                     const float* sa, const float* sb, int B, int C, int L,
-                                                                     float* reda, float* redb, RowVec rv) {
-#pragma clang fp contract(off)
-  const int c = blockIdx.x, r = threadIdx.x >> rv.shift, t0 = threadIdx.x & ((1 << rv.shift) - 1), rpp = 256 >> rv.shift;
+  rv = row_geometry<V>(rv, BN_DWORD_SHIFT);
+  const int c = blockIdx.x, r = row_group<V>(rv, 256), t0 = threadIdx.x & ((1 << rv.shift) - 1), rpp = 256 >> rv.shift;
   const float meana = sa[c], invstda = sa[C + c], sca = sa[2 * C + c], sha = sa[3 * C + c];
   const float meanb = sb[c], invstdb = sb[C + c], scb = sb[2 * C + c], shb = sb[3 * C + c];
   float s1 = 0.f, s2a = 0.f, s2b = 0.f, unused = 0.f;
   for (int b = blockIdx.y + r * gridDim.y; b < B; b += rpp * gridDim.y) {
-    const long long base = ((long long)b * C + c) * rv.L4;
-    const float4* dy4 = reinterpret_cast<const float4*>(dy) + base;
-    const float4* ya4 = reinterpret_cast<const float4*>(ya) + base;
-    const float4* yb4 = reinterpret_cast<const float4*>(yb) + base;
-    for (int t = t0; t < rv.L4; t += 1 << rv.shift) {
-      const float4 va = ya4[t], vb = yb4[t];
-      const float4 g = bn_masked4(dy4[t], bn_pre_join4(va, sca, sha, vb, scb, shb));
-      s1 += bn_g4(g);
-      s2a += bn_gx4(g, va, meana, invstda);
-      s2b += bn_gx4(g, vb, meanb, invstdb);
+    const long long base = ((long long)b * C + c) * rv.nv;
+    const V* dyv = reinterpret_cast<const V*>(dy) + base;
+    const V* yav = reinterpret_cast<const V*>(ya) + base;
+    const V* ybv = reinterpret_cast<const V*>(yb) + base;
+    for (int t = t0; t < rv.nv; t += 1 << rv.shift) {
+      const V va = yav[t], vb = ybv[t];
+      const V g = bn_masked(dyv[t], bn_pre_join(va, sca, sha, vb, scb, shb));
+      s1 += bn_g(g);
+      s2a += bn_gx(g, va, meana, invstda);
+      s2b += bn_gx(g, vb, meanb, invstdb);
     }
   }
   block_sum2(s1, s2a);
@@ -507,12 +465,10 @@ extern "C" int fst_bn_bwd_reduce_join(const float* dy, const float* ya, const fl
   FST_REQUIRE(dy && ya && yb && stats_a && stats_b && red_a && red_b && red_a != red_b && B > 0 && C > 0 && L > 0,
               "fst_bn_bwd_reduce_join: bad arguments");
   FST_REQUIRE_EXTENT("fst_bn_bwd_reduce_join", B, C, L, numel);
-  if (vec_ok(L, {dy, ya, yb}))
-    hipLaunchKernelGGL(bn_bwd_reduce_join_vec_kernel, dim3(C, FST_BN_SLOTS), dim3(256), 0, (hipStream_t)stream, dy, ya, yb,
-                       stats_a, stats_b, B, C, L, red_a, red_b, row_vec(L));
-  else
-    hipLaunchKernelGGL(bn_bwd_reduce_join_kernel, dim3(C, FST_BN_SLOTS), dim3(256), 0, (hipStream_t)stream, dy, ya, yb,
-                       stats_a, stats_b, B, C, L, red_a, red_b);
+  launch_rows(vec_ok(L, {dy, ya, yb}), L, BN_DWORD_SHIFT, [&](auto v, RowVec rv) {
+    hipLaunchKernelGGL(bn_bwd_reduce_join_kernel<decltype(v)>, dim3(C, FST_BN_SLOTS), dim3(256), 0, (hipStream_t)stream, dy, ya, yb,
+                       stats_a, stats_b, B, C, L, red_a, red_b, rv);
+  });
   FST_LAUNCH_CHECK();
   return 0;
 }
@@ -542,49 +498,24 @@ __device__ __forceinline__ void bn_row_sum_store(float rs, float* row_sums, int 
     __syncthreads();
     if (live && t0 == 0) {
       const int w0 = threadIdx.x >> 6, nw = 1 << (rv.shift - 6);
-      float tot = 0.f;
+      float tot = -0.f;                                      // (the identity of +: a row that sums to -0.f keeps its sign)
       for (int i = 0; i < nw; ++i) tot += wsum[w0 + i];
       row_sums[bc] = tot;
     }
   }
 }
 
+template <class V>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* dy, const float* y, const float* out,
-                                                           const float* stats, const float* red, int n_slots, float* red_out,
-                                                           float* dx, float* row_sums, int C, int L, int relu, int train, float invN) {
-#pragma clang fp contract(off)
-  const int bc = blockIdx.x;
-  const int c = bc % C;
-  const float mean = stats[c], invstd = stats[C + c], scale = stats[2 * C + c], sh = stats[3 * C + c];
-  float r1 = 0.f, r2 = 0.f;
-  if (red) bn_red_sums(red, n_slots, C, c, r1, r2);
-  if (red_out && bc < C && threadIdx.x == 0) { red_out[c] = r1; red_out[C + c] = r2; }
-  const float m1 = train ? r1 * invN : 0.f, m2 = train ? r2 * invN : 0.f;
-  const long long base = (long long)bc * L;
-  float rs = 0.f, dummy = 0.f;
-  for (int t = threadIdx.x; t < L; t += 256) {
-    float g = dy[base + t];
-    const float v = y[base + t];
-    if (relu) g = bn_masked(g, out ? out[base + t] : bn_pre(v, scale, sh));
-    const float u = bn_dx_unscaled(g, v, mean, invstd, m1, m2);
-    dx[base + t] = scale * u;
-    rs = __builtin_fmaf(scale, u, rs);                     // (the fused form this sum has always had in the dword kernel)
-  }
-  if (row_sums) {                                          // uniform
-    block_sum2(rs, dummy);
-    if (threadIdx.x == 0) row_sums[bc] = rs;
-  }
-}
-
-__global__ __launch_bounds__(256) void bn_bwd_apply_vec_kernel(const float* dy, const float* y, const float* out,
-                                                               const float* stats, const float* red, int n_slots,
-                                                               float* red_out, float* dx, float* row_sums, int rows, int C,
-                                                               int L, int relu, int train, float invN, RowVec rv) {
+                                                           const float* stats, const float* red, int n_slots,
+                                                           float* red_out, float* dx, float* row_sums, int rows, int C,
+                                                           int L, int relu, int train, float invN, RowVec rv) {
 #pragma clang fp contract(off)
   __shared__ float wsum[4];
-  const int r = threadIdx.x >> rv.shift, t0 = threadIdx.x & ((1 << rv.shift) - 1), rpp = 256 >> rv.shift;
+  rv = row_geometry<V>(rv, BN_DWORD_SHIFT);
+  const int r = row_group<V>(rv, 256), t0 = threadIdx.x & ((1 << rv.shift) - 1), rpp = 256 >> rv.shift;
   const int bc_raw = blockIdx.x * rpp + r;
-  const bool live = bc_raw < rows;
+  const bool live = std::is_same_v<V, float> || bc_raw < rows;          // (the dword grid holds no idle row group)
   const int bc = live ? bc_raw : rows - 1;                 // (idle row groups of the last block walk the last row and store nothing)
   const int c = bc % C;
   const float mean = stats[c], invstd = stats[C + c], scale = stats[2 * C + c], sh = stats[3 * C + c];
@@ -592,19 +523,19 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_vec_kernel(const float* dy, 
   if (red) bn_red_sums(red, n_slots, C, c, r1, r2);
   if (red_out && live && bc < C && t0 == 0) { red_out[c] = r1; red_out[C + c] = r2; }
   const float m1 = train ? r1 * invN : 0.f, m2 = train ? r2 * invN : 0.f;
-  const long long base = (long long)bc * rv.L4;
-  const float4* dy4 = reinterpret_cast<const float4*>(dy) + base;
-  const float4* y4 = reinterpret_cast<const float4*>(y) + base;
-  const float4* o4 = reinterpret_cast<const float4*>(out) + base;            // not dereferenced when out is null
-  float4* dx4 = reinterpret_cast<float4*>(dx) + base;
+  const long long base = (long long)bc * rv.nv;
+  const V* dyv = reinterpret_cast<const V*>(dy) + base;
+  const V* yv = reinterpret_cast<const V*>(y) + base;
+  const V* ov = reinterpret_cast<const V*>(out) + base;                      // not dereferenced when out is null
+  V* dxv = reinterpret_cast<V*>(dx) + base;
   float rs = 0.f;
-  for (int t = t0; t < rv.L4; t += 1 << rv.shift) {
-    float4 g = dy4[t];
-    const float4 v = y4[t];
-    if (relu) g = bn_masked4(g, out ? o4[t] : bn_pre4(v, scale, sh));
-    const float4 d = bn_dx4(g, v, mean, invstd, scale, m1, m2);
-    if (live) dx4[t] = d;
-    rs += bn_g4(d);
+  for (int t = t0; t < rv.nv; t += 1 << rv.shift) {
+    V g = dyv[t];
+    const V v = yv[t];
+    if (relu) g = bn_masked(g, out ? ov[t] : bn_pre(v, scale, sh));
+    const V u = bn_dx_unscaled(g, v, mean, invstd, m1, m2), d = bn_dx(scale, u);
+    if (live) dxv[t] = d;
+    rs = bn_row_sum_add(rs, scale, u, d);
   }
   if (row_sums) bn_row_sum_store(rs, row_sums, bc, live, t0, rv, wsum);      // uniform
 }
@@ -618,15 +549,12 @@ extern "C" int fst_bn_bwd_apply(const float* dy, const float* y, const float* ou
   FST_REQUIRE(!red_out || red, "fst_bn_bwd_apply: red_out needs red");
   FST_REQUIRE_EXTENT("fst_bn_bwd_apply", B, C, L, numel);     // the launch walks B (not B_total) samples
   if (!relu) out = nullptr;
-  if (vec_ok(L, {dy, y, out, dx})) {
-    const RowVec rv = row_vec(L);
+  launch_rows(vec_ok(L, {dy, y, out, dx}), L, BN_DWORD_SHIFT, [&](auto v, RowVec rv) {
     const int rpp = 256 >> rv.shift;
-    hipLaunchKernelGGL(bn_bwd_apply_vec_kernel, dim3((B * C + rpp - 1) / rpp), dim3(256), 0, (hipStream_t)stream, dy, y, out,
-                       stats, red, n_slots, red_out, dx, row_sums, B * C, C, L, relu, train, 1.0f / ((float)B_total * (float)L), rv);
-  } else {
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(B * C), dim3(256), 0, (hipStream_t)stream, dy, y, out, stats, red, n_slots,
-                       red_out, dx, row_sums, C, L, relu, train, 1.0f / ((float)B_total * (float)L));
-  }
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<decltype(v)>, dim3((B * C + rpp - 1) / rpp), dim3(256), 0, (hipStream_t)stream, dy, y,
+                       out, stats, red, n_slots, red_out, dx, row_sums, B * C, C, L, relu, train,
+                       1.0f / ((float)B_total * (float)L), rv);
+  });
   FST_LAUNCH_CHECK();
   return 0;
 }
@@ -642,55 +570,15 @@ struct BnJoinBranch {
   float* row_sums;
 };
 
+template <class V>
 __global__ __launch_bounds__(256) void bn_bwd_apply_join_kernel(const float* dy, BnJoinBranch a, BnJoinBranch b, int n_slots,
-                                                                int C, int L, int train, float invN) {
-#pragma clang fp contract(off)
-  const int bc = blockIdx.x;
-  const int c = bc % C;
-  const float meana = a.stats[c], invstda = a.stats[C + c], sca = a.stats[2 * C + c], sha = a.stats[3 * C + c];
-  const float meanb = b.stats[c], invstdb = b.stats[C + c], scb = b.stats[2 * C + c], shb = b.stats[3 * C + c];
-  float ra1 = 0.f, ra2 = 0.f, rb1 = 0.f, rb2 = 0.f;
-  if (a.red) bn_red_sums(a.red, n_slots, C, c, ra1, ra2);
-  if (b.red) bn_red_sums(b.red, n_slots, C, c, rb1, rb2);
-  if (bc < C && threadIdx.x == 0) {
-    if (a.red_out) { a.red_out[c] = ra1; a.red_out[C + c] = ra2; }
-    if (b.red_out) { b.red_out[c] = rb1; b.red_out[C + c] = rb2; }
-  }
-  if (!a.dx && !b.dx) return;                              // uniform
-  const float ma1 = train ? ra1 * invN : 0.f, ma2 = train ? ra2 * invN : 0.f;
-  const float mb1 = train ? rb1 * invN : 0.f, mb2 = train ? rb2 * invN : 0.f;
-  const long long base = (long long)bc * L;
-  float rsa = 0.f, rsb = 0.f;
-  for (int t = threadIdx.x; t < L; t += 256) {
-    const float va = a.y[base + t], vb = b.y[base + t];
-    const float g = bn_masked(dy[base + t], bn_pre_join(va, sca, sha, vb, scb, shb));
-    if (a.dx) {
-      const float u = bn_dx_unscaled(g, va, meana, invstda, ma1, ma2);
-      a.dx[base + t] = sca * u;
-      rsa = __builtin_fmaf(sca, u, rsa);
-    }
-    if (b.dx) {
-      const float u = bn_dx_unscaled(g, vb, meanb, invstdb, mb1, mb2);
-      b.dx[base + t] = scb * u;
-      rsb = __builtin_fmaf(scb, u, rsb);
-    }
-  }
-  if (a.row_sums || b.row_sums) {                          // uniform
-    block_sum2(rsa, rsb);
-    if (threadIdx.x == 0) {
-      if (a.row_sums) a.row_sums[bc] = rsa;
-      if (b.row_sums) b.row_sums[bc] = rsb;
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void bn_bwd_apply_join_vec_kernel(const float* dy, BnJoinBranch a, BnJoinBranch b, int n_slots,
-                                                                    int rows, int C, int L, int train, float invN, RowVec rv) {
+                                                                int rows, int C, int L, int train, float invN, RowVec rv) {
 #pragma clang fp contract(off)
   __shared__ float wsum[2][4];
-  const int r = threadIdx.x >> rv.shift, t0 = threadIdx.x & ((1 << rv.shift) - 1), rpp = 256 >> rv.shift;
+  rv = row_geometry<V>(rv, BN_DWORD_SHIFT);
+  const int r = row_group<V>(rv, 256), t0 = threadIdx.x & ((1 << rv.shift) - 1), rpp = 256 >> rv.shift;
   const int bc_raw = blockIdx.x * rpp + r;
-  const bool live = bc_raw < rows;
+  const bool live = std::is_same_v<V, float> || bc_raw < rows;          // (the dword grid holds no idle row group)
   const int bc = live ? bc_raw : rows - 1;                 // (idle row groups of the last block walk the last row and store nothing)
   const int c = bc % C;
   const float meana = a.stats[c], invstda = a.stats[C + c], sca = a.stats[2 * C + c], sha = a.stats[3 * C + c];
@@ -705,25 +593,25 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_join_vec_kernel(const float*
   if (!a.dx && !b.dx) return;                              // uniform
   const float ma1 = train ? ra1 * invN : 0.f, ma2 = train ? ra2 * invN : 0.f;
   const float mb1 = train ? rb1 * invN : 0.f, mb2 = train ? rb2 * invN : 0.f;
-  const long long base = (long long)bc * rv.L4;
-  const float4* dy4 = reinterpret_cast<const float4*>(dy) + base;
-  const float4* ya4 = reinterpret_cast<const float4*>(a.y) + base;
-  const float4* yb4 = reinterpret_cast<const float4*>(b.y) + base;
-  float4* dxa4 = reinterpret_cast<float4*>(a.dx) + base;                     // not dereferenced when the dx is null
-  float4* dxb4 = reinterpret_cast<float4*>(b.dx) + base;
+  const long long base = (long long)bc * rv.nv;
+  const V* dyv = reinterpret_cast<const V*>(dy) + base;
+  const V* yav = reinterpret_cast<const V*>(a.y) + base;
+  const V* ybv = reinterpret_cast<const V*>(b.y) + base;
+  V* dxav = reinterpret_cast<V*>(a.dx) + base;                               // not dereferenced when the dx is null
+  V* dxbv = reinterpret_cast<V*>(b.dx) + base;
   float rsa = 0.f, rsb = 0.f;
-  for (int t = t0; t < rv.L4; t += 1 << rv.shift) {
-    const float4 va = ya4[t], vb = yb4[t];
-    const float4 g = bn_masked4(dy4[t], bn_pre_join4(va, sca, sha, vb, scb, shb));
+  for (int t = t0; t < rv.nv; t += 1 << rv.shift) {
+    const V va = yav[t], vb = ybv[t];
+    const V g = bn_masked(dyv[t], bn_pre_join(va, sca, sha, vb, scb, shb));
     if (a.dx) {
-      const float4 d = bn_dx4(g, va, meana, invstda, sca, ma1, ma2);
-      if (live) dxa4[t] = d;
-      rsa += bn_g4(d);
+      const V u = bn_dx_unscaled(g, va, meana, invstda, ma1, ma2), d = bn_dx(sca, u);
+      if (live) dxav[t] = d;
+      rsa = bn_row_sum_add(rsa, sca, u, d);
     }
     if (b.dx) {
-      const float4 d = bn_dx4(g, vb, meanb, invstdb, scb, mb1, mb2);
-      if (live) dxb4[t] = d;
-      rsb += bn_g4(d);
+      const V u = bn_dx_unscaled(g, vb, meanb, invstdb, mb1, mb2), d = bn_dx(scb, u);
+      if (live) dxbv[t] = d;
+      rsb = bn_row_sum_add(rsb, scb, u, d);
     }
   }
   if (a.row_sums) bn_row_sum_store(rsa, a.row_sums, bc, live, t0, rv, wsum[0]);      // uniform
@@ -744,14 +632,11 @@ extern "C" int fst_bn_bwd_apply_join(const float* dy, const float* ya, const flo
   FST_REQUIRE_EXTENT("fst_bn_bwd_apply_join", B, C, L, numel);     // the launch walks B (not B_total) samples
   const BnJoinBranch a = {ya, stats_a, red_a, red_out_a, dxa, row_sums_a}, b = {yb, stats_b, red_b, red_out_b, dxb, row_sums_b};
   const float invN = 1.0f / ((float)B_total * (float)L);
-  if (vec_ok(L, {dy, ya, yb, dxa, dxb})) {
-    const RowVec rv = row_vec(L);
+  launch_rows(vec_ok(L, {dy, ya, yb, dxa, dxb}), L, BN_DWORD_SHIFT, [&](auto v, RowVec rv) {
     const int rpp = 256 >> rv.shift;
-    hipLaunchKernelGGL(bn_bwd_apply_join_vec_kernel, dim3((B * C + rpp - 1) / rpp), dim3(256), 0, (hipStream_t)stream, dy, a, b,
-                       n_slots, B * C, C, L, train, invN, rv);
-  } else {
-    hipLaunchKernelGGL(bn_bwd_apply_join_kernel, dim3(B * C), dim3(256), 0, (hipStream_t)stream, dy, a, b, n_slots, C, L, train, invN);
-  }
+    hipLaunchKernelGGL(bn_bwd_apply_join_kernel<decltype(v)>, dim3((B * C + rpp - 1) / rpp), dim3(256), 0, (hipStream_t)stream, dy,
+                       a, b, n_slots, B * C, C, L, train, invN, rv);
+  });
   FST_LAUNCH_CHECK();
   return 0;
 }

@@ -141,8 +141,8 @@ def bn_input(B: int, C: int, L: int):
 
 
 def check_slots(part: torch.Tensor, y: torch.Tensor, what: str):
-    """Row b of a channel belongs to slot b mod 16 in both kernels: bn_stats_kernel walks b = blockIdx.y, blockIdx.y + 16, ...;
-    bn_stats_vec_kernel's row group r walks b = blockIdx.y + 16·(r + j·rows_per_pass) — the same residue class, regrouped.
+    """Row b of a channel belongs to slot b mod 16 on both paths of bn_stats_kernel: the dword one walks b = blockIdx.y,
+    blockIdx.y + 16, ...; the 16-byte one's row group r walks b = blockIdx.y + 16·(r + j·rows_per_pass) — the same residue class, regrouped.
     Bounds, from the inherited 1e-5·Σ|terms| for sums: with d = x − k, |Σd − s1| <= 1e-5·Σ|d| and |Σd² − s2| <= 1e-5·Σd²; then
     mean = k + s1/n is off by <= 1e-5·Σ|d|/n and M2 = s2 − s1²/n by <= 1e-5·(Σd² + 2·|Σd|·Σ|d|/n) (first order in the two errors)."""
     B, C, L = y.shape

@@ -154,6 +154,114 @@ def test_row_sum_of_views(L):
     assert float((ops.row_sum(odd_view[:, c0:c0 + C]).double().cpu() - want).abs().max()) <= 1e-5 * bound, f"misaligned slice L={L}"
 
 
+# ------------------------------------------------------------------ BatchNorm entry points off 16-byte alignment
+PAD, CANARY, BN_EPS = 64, 1234.5, 1e-5          # PAD floats = 256 bytes: a body at PAD is 16-byte aligned, at PAD + 1 one float past
+
+
+class _Canaried:
+    """Device tensors inside canary-filled buffers, each a chosen number of floats past a 16-byte boundary."""
+
+    def __init__(self):
+        self.bufs = {}
+
+    def put(self, name, t, off):
+        n = t.numel()
+        buf = torch.full((PAD + off + n + PAD,), CANARY, device=DEV)
+        body = buf[PAD + off: PAD + off + n].view(t.shape)
+        body.copy_(t)
+        assert body.data_ptr() % 16 == 4 * off
+        self.bufs[name] = (buf, body)
+        return body
+
+    def new(self, name, shape, off):
+        return self.put(name, torch.full(shape, CANARY), off)
+
+    def assert_only_bodies_written(self, outputs):
+        for name, (buf, body) in self.bufs.items():
+            lo, n = body.storage_offset(), body.numel()
+            assert bool((buf[:lo] == CANARY).all()) and bool((buf[lo + n:] == CANARY).all()), f"{name}: written outside the tensor"
+        for name in outputs:
+            assert not bool((self.bufs[name][1] == CANARY).any()), f"{name}: not every element was written"
+
+
+@pytest.mark.parametrize("case", ["every tensor", "written tensor only"])
+@pytest.mark.parametrize("L", [8, 256])
+def test_bn_entry_points_off_16_byte_alignment(L, case):
+    """L % 4 == 0 with a base one float past a 16-byte boundary must take the scalar path: every BatchNorm entry point through
+    its raw symbol, against fp64, on operands that are all misaligned or of which only the written tensor is (`out` of the
+    forward, `dx` of the backward, `dxa` alone of the join).  L = 256 is L/4 = 64, where the 16-byte kernels' row sums go from
+    the in-wave butterfly to the LDS step.  Canary words on both sides of every tensor: nothing outside the outputs is written."""
+    lib = _lib.load()
+    B, C = 3, 5
+    rd = 1 if case == "every tensor" else 0                                   # offset of everything but the written tensor
+    g = torch.Generator().manual_seed(11 * L + rd)
+    mk = lambda *s: torch.randn(*s, generator=g)
+    n, sp, S = B * C * L, _lib.stream_ptr, ops.BN_SLOTS
+    host = dict(ya=mk(B, C, L) * 2 + 0.7, yb=mk(B, C, L) * 3 - 1, dy=mk(B, C, L), ga=torch.rand(C, generator=g) + 0.5,
+                gb=torch.rand(C, generator=g) + 0.5, ba=mk(C), bb=mk(C), rm=mk(C), rv=torch.rand(C, generator=g) + 0.5)
+    m = _Canaried()
+    d = {k: m.put(k, v, rd) for k, v in host.items()}
+    p = lambda t: t.data_ptr()
+
+    stats = {}
+    for k in "ab":
+        part, stats[k] = m.new("part_" + k, (C, S, 4), rd), m.new("stats_" + k, (4 * C,), rd)
+        rm, rv = m.put("rm_" + k, host["rm"], rd), m.put("rv_" + k, host["rv"], rd)
+        _lib.check(lib.fst_bn_stats(p(d["y" + k]), B, C, L, p(part), n, sp()), "bn_stats")
+        _lib.check(lib.fst_bn_finalize(p(part), S, p(d["g" + k]), p(d["b" + k]), p(rm), p(rv), 1, C, BN_EPS, 0.1, p(stats[k]), sp()),
+                   "bn_finalize")
+    out, out_j = m.new("out", (B, C, L), 1), m.new("out_join", (B, C, L), 1)
+    _lib.check(lib.fst_bn_apply(p(d["ya"]), p(stats["a"]), None, None, p(out), B, C, L, 1, n, sp()), "bn_apply")
+    _lib.check(lib.fst_bn_apply(p(d["ya"]), p(stats["a"]), p(d["yb"]), p(stats["b"]), p(out_j), B, C, L, 1, n, sp()), "bn_apply join")
+
+    h64 = {k: v.double().requires_grad_(k != "dy") for k, v in host.items() if k not in ("rm", "rv")}
+    rm64 = {k: host["rm"].double() for k in "ab"}
+    rv64 = {k: host["rv"].double() for k in "ab"}
+    pre = {k: F.batch_norm(h64["y" + k], rm64[k], rv64[k], h64["g" + k], h64["b" + k], True, 0.1, BN_EPS) for k in "ab"}
+    what = f"L={L} {case}: "
+    assert_close(out, _relu64(pre["a"], out), 1e-5, what + "out")
+    assert_close(out_j, _relu64(pre["a"] + pre["b"], out_j), 1e-5, what + "out of the join")
+    for k in "ab":
+        assert_close(m.bufs["rm_" + k][1], rm64[k], 1e-5, what + f"running mean {k}")
+        assert_close(m.bufs["rv_" + k][1], rv64[k], 1e-5, what + f"running var {k}")
+
+    def assert_branch(tag, dx, red, rs, want_dx, want_dgamma, want_dbeta):
+        assert_close(dx, want_dx, 5e-5, what + tag + " dx")
+        assert_close(red[:C], want_dbeta, 5e-5, what + tag + " dbeta")
+        assert_close(red[C:], want_dgamma, 5e-5, what + tag + " dgamma")
+        bound = float(want_dx.abs().sum(dim=2).max())                          # the measure of test_bn_backward_row_sums
+        err = float((rs.double().cpu() - want_dx.sum(dim=2)).abs().max())
+        assert err <= 2e-5 * bound, f"{what}{tag} row sums vs fp64: {err:.3e} (Σ|dx| up to {bound:.3e})"
+
+    # single branch; the backward reads the forward's output from a buffer placed like the other operands it reads
+    out_in = m.put("out_in", out, rd)
+    part, red = m.new("bwd_part", (2, C, S), rd), m.new("red", (2 * C,), rd)
+    dx, rs = m.new("dx", (B, C, L), 1), m.new("rs", (B, C), rd)
+    _lib.check(lib.fst_bn_bwd_reduce(p(d["dy"]), p(d["ya"]), p(out_in), p(stats["a"]), B, C, L, 1, p(part), n, sp()), "bn_bwd_reduce")
+    _lib.check(lib.fst_bn_bwd_apply(p(d["dy"]), p(d["ya"]), p(out_in), p(stats["a"]), p(part), S, p(red), p(dx), p(rs), B, C, L, 1,
+                                    1, B, n, sp()), "bn_bwd_apply")
+    want = torch.autograd.grad((_relu64(pre["a"], out) * h64["dy"]).sum(), [h64["ya"], h64["ga"], h64["ba"]], retain_graph=True)
+    assert_branch("single", dx, red, rs, *want)
+
+    # the join: dxa alone is the misaligned one of "written tensor only"
+    jp = {k: m.new("join_part_" + k, (2, C, S), rd) for k in "ab"}
+    jr = {k: m.new("join_red_" + k, (2 * C,), rd) for k in "ab"}
+    jdx = dict(a=m.new("dxa", (B, C, L), 1), b=m.new("dxb", (B, C, L), rd))
+    jrs = {k: m.new("join_rs_" + k, (B, C), rd) for k in "ab"}
+    _lib.check(lib.fst_bn_bwd_reduce_join(p(d["dy"]), p(d["ya"]), p(d["yb"]), p(stats["a"]), p(stats["b"]), B, C, L, p(jp["a"]),
+                                          p(jp["b"]), n, sp()), "bn_bwd_reduce_join")
+    _lib.check(lib.fst_bn_bwd_apply_join(p(d["dy"]), p(d["ya"]), p(d["yb"]), p(stats["a"]), p(stats["b"]), p(jp["a"]), p(jp["b"]), S,
+                                         p(jr["a"]), p(jr["b"]), p(jdx["a"]), p(jdx["b"]), p(jrs["a"]), p(jrs["b"]), B, C, L, 1, B, n,
+                                         sp()), "bn_bwd_apply_join")
+    want = torch.autograd.grad((_relu64(pre["a"] + pre["b"], out_j) * h64["dy"]).sum(),
+                               [h64[k + b] for b in "ab" for k in ("y", "g", "b")])
+    for i, k in enumerate("ab"):
+        assert_branch("join " + k, jdx[k], jr[k], jrs[k], *want[3 * i: 3 * i + 3])
+
+    m.assert_only_bodies_written(["part_a", "part_b", "stats_a", "stats_b", "out", "out_join", "bwd_part", "red", "dx", "rs",
+                                  "join_part_a", "join_part_b", "join_red_a", "join_red_b", "dxa", "dxb", "join_rs_a", "join_rs_b"])
+
+
 # ------------------------------------------------------------------ affine coupling
 COUPLING_SHAPES = [(1, 1, 3), (256, 25, 512), (2, 40, 5000)]       # the last: h·L > 64 workgroups x 1024 -> grid-stride
 
