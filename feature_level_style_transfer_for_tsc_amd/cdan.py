@@ -46,15 +46,27 @@ class RandomLayer(nn.Module):
             self._transposed[i] = self.random_matrix[i].t().contiguous()
         return self._transposed[i]
 
+    def _rt_k32(self, i: int) -> torch.Tensor:
+        """``_rt(i)`` with its rows zero-padded to a multiple of 32 columns (``nt_gemm`` reduces in 32-sample stages): ``_rt(i)``
+        itself where the input width already is one."""
+        pad = -self.random_matrix[i].shape[0] % 32
+        if pad == 0:
+            return self._rt(i)
+        if ("k32", i) not in self._transposed:
+            self._transposed[("k32", i)] = nn.functional.pad(self._rt(i), (0, pad)).contiguous()
+        return self._transposed[("k32", i)]
+
     def forward(self, input_list):
         if self.input_num == 2:
             x, pr = input_list
             R0, R1 = self.random_matrix
             if (x.dim() == 2 and R0.shape[0] >= 256 and not R1.requires_grad
-                    and ops.nt_gemm_ok(x.shape[0], R0.shape[1], R0.shape[0], x.contiguous(), R0, self._rt(0))
+                    and ops.nt_gemm_ok(x.shape[0], R0.shape[1], self._rt_k32(0).shape[1], x.contiguous(), R0, self._rt_k32(0))
                     and ops.nt_gemm_ok(x.shape[0], R0.shape[0], R0.shape[1], R0)):
-                # one GEMM with the class-side product, the 1/√O scale and the Hadamard product in its epilogue
-                return ops.RandomLayerFn.apply(x, pr, R0, self._rt(0), R1.contiguous(), 1.0 / math.pow(float(self.output_dim), 0.5))
+                # one GEMM with the class-side product, the 1/√O scale and the Hadamard product in its epilogue.  A feature width
+                # C·L that is no multiple of 32 runs on zero-padded operands (exact): the fall-back below adds its K slices with
+                # float atomics, and the step would no longer reproduce its own bits
+                return ops.RandomLayerFn.apply(x, pr, R0, self._rt_k32(0), R1.contiguous(), 1.0 / math.pow(float(self.output_dim), 0.5))
         outs = []
         for i in range(self.input_num):
             R = self.random_matrix[i]

@@ -2446,11 +2446,14 @@ def nt_gemm(A: Tensor, Bm: Tensor, epi: Optional[Tuple[Tensor, Tensor, float]] =
 class RandomLayerFn(torch.autograd.Function):
     """RandomLayer.forward for two inputs (C_DAN.py:18-25):  (x·R₀ / √O) ⊙ (p·R₁)  with fixed Gaussian R₀ [D, O], R₁ [ncls, O] — the
     feature-side product on the matrix cores with the class-side product, the scale and the Hadamard product in its epilogue
-    (one pass over the [B, O] result).  ``R0t`` = R₀ᵀ kept contiguous (the forward's operand); the backward's is R₀ itself."""
+    (one pass over the [B, O] result).  ``R0t`` = R₀ᵀ kept contiguous (the forward's operand); the backward's is R₀ itself.
+    ``R0t`` may carry zero columns behind its D (D rounded up to the kernel's 32-sample stages): x is zero-padded to match."""
 
     @staticmethod
     def forward(ctx, x: Tensor, p: Tensor, R0: Tensor, R0t: Tensor, R1: Tensor, scale: float):
         x, p = x.contiguous(), p.contiguous()
+        if R0t.shape[1] != x.shape[1]:
+            x = torch.nn.functional.pad(x, (0, R0t.shape[1] - x.shape[1]))
         out, y0 = nt_gemm(x, R0t, (p, R1, scale), want_raw=True)
         ctx.save_for_backward(p, R0, R1, y0)
         ctx.scale = scale

@@ -1,6 +1,6 @@
 """CPU ORACLE — TEST INFRASTRUCTURE ONLY.
 
-A from-the-spec CPU restatement (PyTorch CPU ops, fp32) of the train-step hot path of
+A from-the-spec CPU restatement (PyTorch CPU ops, fp32; fp64 on request, see ``joint_step_as``) of the train-step hot path of
 BaeHann/feature_level_style_transfer_for_TSC.  It exists to CHECK the HIP path; nothing
 in ``feature_level_style_transfer_for_tsc_amd/`` may import it.  Allowed importers:
 ``tests/``, ``__graft_entry__.smoke()`` and ``bench.py``'s ``cpu_baseline`` leg.
@@ -221,7 +221,9 @@ def waveglow_infer(z: Tensor, P: Params, n_flows: int, inv_cache: Dict[int, Tens
         x1 = (x1 - b) / torch.exp(s)
         x = torch.cat([x0, x1], 1)
         if k not in inv_cache:
-            inv_cache[k] = P[f"convinv.{k}.conv.weight"].detach().squeeze().float().inverse()[..., None]
+            W = P[f"convinv.{k}.conv.weight"].detach().squeeze()
+            # the reference's literal ``.float().inverse()``; an operand that is already double (the fp64 mode) stays double
+            inv_cache[k] = (W if W.dtype == torch.float64 else W.float()).inverse()[..., None]
         x = F.conv1d(x, inv_cache[k])
     return x
 
@@ -246,7 +248,7 @@ def cpc_nce(feat: Tensor, P: Params, timestep: int, t_samples: Optional[int] = N
     t = t_samples
     enc = z[:, t + 1: t + 1 + timestep, :].transpose(0, 1)        # [T, B, C]
     hid = P["gru.weight_hh_l0"].shape[1]
-    h0 = torch.zeros(1, B, hid)
+    h0 = torch.zeros(1, B, hid, dtype=feat.dtype)
     out, _ = torch._VF.gru(z[:, : t + 1, :], h0,
                            [P["gru.weight_ih_l0"], P["gru.weight_hh_l0"], P["gru.bias_ih_l0"], P["gru.bias_hh_l0"]],
                            True, 1, 0.0, False, False, True)
@@ -331,8 +333,8 @@ def cdan_loss(feat_t: Tensor, feat_g: Tensor, logit_t: Tensor, logit_g: Tensor, 
 # --------------------------------------------------------------------------------------
 # a16-a18 — small heads                                              widgets.py:15-167
 # --------------------------------------------------------------------------------------
-def new_noise_state(channels: int, length: int) -> Dict[str, object]:
-    return {"target_avg": torch.zeros(channels, length), "source_avg": torch.zeros(channels, length),
+def new_noise_state(channels: int, length: int, dtype: torch.dtype = torch.float32) -> Dict[str, object]:
+    return {"target_avg": torch.zeros(channels, length, dtype=dtype), "source_avg": torch.zeros(channels, length, dtype=dtype),
             "time": 0, "n_t": 0, "n_s": 0}
 
 
@@ -364,7 +366,7 @@ def prob_transfer(pooled: Tensor, P: Params) -> Tensor:
     """LSTM over the input repeated twice, returns h_n (:51-55)."""
     x = torch.stack([pooled, pooled], dim=1)
     B, H = pooled.shape
-    zeros = torch.zeros(1, B, H)
+    zeros = torch.zeros(1, B, H, dtype=pooled.dtype)
     _, h_n, _ = torch._VF.lstm(x, (zeros, zeros),
                                [P["model.weight_ih_l0"], P["model.weight_hh_l0"], P["model.bias_ih_l0"], P["model.bias_hh_l0"]],
                                True, 1, 0.0, False, False, True)
@@ -436,20 +438,24 @@ class JointStep:
         self.n_flows, self.T, self.dropout_p = n_flows, cpc_timestep, dropout_p
         self.opts = {k: torch.optim.RMSprop(_leaves(mods[k]), lr=lr) for k, lr in self.LRS.items()}
         self.opt_cpc = torch.optim.Adam(_leaves(mods["cpc"]), lr=0.002)
-        self.w_t = torch.tensor([2.0, 5.0], requires_grad=True)                    # :501-505
-        self.w_s = torch.tensor([2.0, 2.0, 4.0], requires_grad=True)
+        # fp32 as the reference, or fp64 throughout when the parameters are double (``joint_step_as``): activations, ``mats``,
+        # the GRU / LSTM initial states, the GradNorm weights and NoiseTransfer's sums all follow the parameters' dtype
+        self.dtype = next(iter(mods["fe_t"].values())).dtype
+        self.w_t = torch.tensor([2.0, 5.0], dtype=self.dtype, requires_grad=True)   # :501-505
+        self.w_s = torch.tensor([2.0, 2.0, 4.0], dtype=self.dtype, requires_grad=True)
         self.opt_w_t = torch.optim.Adam([self.w_t], lr=0.0002)
         self.opt_w_s = torch.optim.Adam([self.w_s], lr=0.001)
         self.init_t = self.init_s = None
         self.alpha = 3
         C = feature_width(fe_t_spec)
         L = mods["dimunif"]["length_unification.weight"].shape[0]
-        self.noise_state = new_noise_state(C, L)
+        self.noise_state = new_noise_state(C, L, self.dtype)
         self.inv_cache: Dict[int, Tensor] = {}
         self.ad_counter, self.fd_counter = new_grl_counter(), new_grl_counter()
 
     def forward_losses(self, x_t, y_t, x_s, y_s, t_samples: Tuple[Optional[int], Optional[int]] = (None, None)):
         m = self.m
+        x_t, x_s = x_t.to(self.dtype), x_s.to(self.dtype)                          # (fp64 mode: the fp32 series the device receives, widened)
         feat_t = feature_extractor(x_t, m["fe_t"], self.fe_t_spec, True)
         sl_t = cpc_nce(feat_t, m["cpc"], self.T, t_samples[0])
         feat_s = dimension_unification(feature_extractor(x_s, m["fe_s"], self.fe_s_spec, True), m["dimunif"])
@@ -492,6 +498,7 @@ class JointStep:
         (their BatchNorm running statistics move) although their losses are not in the total and they are not
         stepped (:308-324); "nf": the features are detached, so only the flow receives gradients (:467-471)."""
         m, L = self.m, {}
+        x_t, x_s = x_t.to(self.dtype), x_s.to(self.dtype)
         if phase == "target_pretrain":
             feat_t = feature_extractor(x_t, m["fe_t"], self.fe_t_spec, True)
             L["sl_t"] = cpc_nce(feat_t, m["cpc"], self.T, t_samples[0])
@@ -746,6 +753,25 @@ def build_joint_step(L_t: int, C_in_t: int, L_s: int, C_in_s: int, n_class_t: in
     mods.update(init_small_heads(C, C_s, L_t, L_s, gen))
     mats = [torch.randn(C * L_t, 1024, generator=gen), torch.randn(n_class_t, 1024, generator=gen)]
     return JointStep(mods, mats, fe_t_spec, clf_spec, fe_s_spec, 3, L_t // 2, dropout_p)
+
+
+def joint_step_as(js: JointStep, dtype: torch.dtype = torch.float64) -> JointStep:
+    """A fresh ``JointStep`` in ``dtype`` holding copies of ``js``'s parameters, BatchNorm buffers and ``mats`` — the fp64 mode:
+    every tensor of the step is then double (parameters, ``mats``, the recurrent initial states, ``w_t`` / ``w_s``, the noise
+    sums, the cached ``W_inverse``), so the step's own rounding is 2^-29 of fp32's.  ``js`` must not have stepped yet: optimiser
+    moments, GradNorm's ``init_t`` / ``init_s``, the GRL counters and the noise state start fresh.  Inputs are cast by the
+    step (the fp32 series the device receives, widened); integer tensors (``num_batches_tracked``) keep their type."""
+    assert js.init_t is None and js.noise_state["time"] == 0, "joint_step_as: the step has already run"
+    mods: Dict[str, Params] = {}
+    for name, P in js.m.items():
+        mods[name] = {}
+        for k, v in P.items():
+            t = v.detach().clone()
+            if t.is_floating_point():
+                t = t.to(dtype).requires_grad_(v.requires_grad)
+            mods[name][k] = t
+    return JointStep(mods, [m.detach().to(dtype) for m in js.mats], js.fe_t_spec, js.clf_spec, js.fe_s_spec, js.n_flows, js.T,
+                     js.dropout_p)
 
 
 # --------------------------------------------------------------------------------------
