@@ -1,8 +1,9 @@
 """Drop-in conditional-adversarial pieces (surface of the reference's C_DAN.py).
 
 ``RandomLayer``'s [B, C·L] × [C·L, 1024] product — the one large GEMM of the head, HBM-bound on the
-fixed 105 MB matrix — runs on the MFMA conv engine with a K split; the class-probability product and
-the Hadamard stay tiny torch ops.
+fixed 105 MB matrix — runs on the matrix cores with a K split: one split-bf16 GEMM with the rest of the
+layer in its epilogue, or, under FST_MATH=f32, the exact-fp32 dense GEMM with the class-probability
+product and the Hadamard as tiny torch ops.
 """
 from __future__ import annotations
 
@@ -70,7 +71,10 @@ class RandomLayer(nn.Module):
         outs = []
         for i in range(self.input_num):
             R = self.random_matrix[i]
-            if R.shape[0] >= 256:                                           # the feature-side GEMM
+            if R.shape[0] >= 256 and ops.MATH != "bf16x3" and ops.gemm_f32_ok(input_list[i].contiguous(), self._rt(i)):
+                # the feature-side GEMM in exact fp32: K slices added in a fixed order, the step reproduces its own bits
+                outs.append(ops.FixedGemmF32Fn.apply(input_list[i], self._rt(i)))
+            elif R.shape[0] >= 256:                                         # (K slices added with float atomics)
                 outs.append(ops.FixedMatmulFn.apply(input_list[i], R, self._rt(i)))
             else:                                                           # [B, n_class] × [n_class, O]
                 outs.append(torch.mm(input_list[i], R))

@@ -16,6 +16,18 @@
 // 16 ds_read_b128 per 24 MFMAs and no conversion.  40 KiB of LDS per workgroup: three workgroups per CU hide each other's barriers.
 // K is split over gridDim.z when the tiles alone do not fill the chip: partial tiles go to slabs that a second kernel adds in slab
 // order (+ bias, activation) — deterministic, no atomics, no zero fill.
+//
+// The same contract in EXACT fp32 (fst_gemm_f32, gemm_f32_kernel): RandomLayer's feature-side product and its data gradient under
+// FST_MATH=f32 (C_DAN.py:20-25 of the reference), the arithmetic the reference itself runs.  Same tiles, same fetch, same geometry,
+// same K split and slab reduction; the operands go into LDS unsplit (rows of 32 floats at a 144-byte pitch: the 16-byte staging
+// writes and the ds_read_b128 fragment reads are bank-conflict-free, 9 sixteen-byte slots per row being odd) and the product runs
+// on v_mfma_f32_32x32x2_f32, whose result is bit for bit a k-ordered fmaf chain per accumulator.  The chain order of one C element:
+//   * inside a 32-k stage starting at k0, lane half h holds k0 + 16h .. k0 + 16h + 15 (four ds_read_b128), and MFMA q = 0..15 of
+//     the stage multiplies k0 + q (half 0) then k0 + 16 + q (half 1):   k0, k0+16, k0+1, k0+17, …, k0+15, k0+31;
+//   * the stages of a split run in ascending k0, starting from 0.f; k past the end of the split enters as 0·0;
+//   * the splits (slab z covers k in [z·k_per_split, (z+1)·k_per_split)) are added by gemm_reduce_kernel: slab z joins chain
+//     z mod 4 in ascending z (a tail of fewer than four slabs joins chain 0), then ((s0 + s1) + (s2 + s3)) + bias, activation.
+// No atomics, no zero fill: two launches on the same operands give the same bits.
 #include <stdlib.h>
 
 #include "fst_device.h"
@@ -184,6 +196,102 @@ __global__ __launch_bounds__(256, TM * TN == 4 ? 2 : 3) void gemm_bf3_kernel(Gem
   }
 }
 
+#define GF_PITCH 144
+
+// One fetched operand tile (gm_fetch's thread map) into its LDS image: rows of 32 floats, k in storage order.  Either layout hands a
+// thread ROWS/32 pieces of four consecutive k: of rows (t>>3) + 32j at k = 4(t&7), or of row t % ROWS at k = KR·(t / ROWS) + 4j.
+template <int ROWS>
+__device__ __forceinline__ void gf_stage(const float (&v)[ROWS / 8], char* img, int trans, int tid) {
+  constexpr int KR = ROWS / 8;
+  const int off = trans ? (tid % ROWS) * GF_PITCH + 4 * KR * (tid / ROWS) : (tid >> 3) * GF_PITCH + 16 * (tid & 7);
+  const int step = trans ? 16 : 32 * GF_PITCH;
+#pragma unroll
+  for (int j = 0; j < ROWS / 32; ++j)
+    *reinterpret_cast<float4*>(img + off + j * step) = make_float4(v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]);
+}
+
+// The exact-fp32 twin of gemm_bf3_kernel (chain order: file header).  16 ds_read_b128 per 64 (TM = TN = 2) MFMAs of 64 cycles each.
+template <int TM, int TN>
+__global__ __launch_bounds__(256, TM * TN == 4 ? 2 : 3) void gemm_f32_kernel(GemmParams p) {
+  constexpr int BM = 64 * TM, BN = 64 * TN;
+  __shared__ __attribute__((aligned(16))) char lds[(BM + BN) * GF_PITCH];
+  char* const a_img = lds;
+  char* const b_img = lds + BM * GF_PITCH;
+  const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), wm = wave >> 1, wn = wave & 1;
+  const int tile_m = blockIdx.x / p.tiles_n, tile_n = blockIdx.x - tile_m * p.tiles_n;
+  const int m0 = tile_m * BM, n0 = tile_n * BN;
+  const int k_begin = blockIdx.z * p.k_per_split;
+  const int k_end = min(p.K, k_begin + p.k_per_split);
+  const int n_st = (k_end - k_begin + GM_BK - 1) / GM_BK;
+
+  f32x16 acc[TM][TN];
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+  float va[BM / 8], vb[BN / 8];
+  gm_fetch<BM>(va, p.A, p.lda, p.ta, p.vec_a, m0, p.M, k_begin, k_end, tid);
+  gm_fetch<BN>(vb, p.B, p.ldb, p.tb, p.vec_b, n0, p.N, k_begin, k_end, tid);
+  const int a_off = (wm * 32 * TM + l31) * GF_PITCH + 64 * half;
+  const int b_off = (wn * 32 * TN + l31) * GF_PITCH + 64 * half;
+  for (int s = 0; s < n_st; ++s) {
+    __syncthreads();                                       // every wave is past its fragment reads of the previous stage
+    gf_stage<BM>(va, a_img, p.ta, tid);
+    gf_stage<BN>(vb, b_img, p.tb, tid);
+    __syncthreads();
+    if (s + 1 < n_st) {                                    // the next stage's operands travel under this stage's MFMAs
+      const int k0 = k_begin + (s + 1) * GM_BK;
+      gm_fetch<BM>(va, p.A, p.lda, p.ta, p.vec_a, m0, p.M, k0, k_end, tid);
+      gm_fetch<BN>(vb, p.B, p.ldb, p.tb, p.vec_b, n0, p.N, k0, k_end, tid);
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      float4 a[TM], b[TN];
+#pragma unroll
+      for (int i = 0; i < TM; ++i) a[i] = *reinterpret_cast<const float4*>(a_img + a_off + i * 32 * GF_PITCH + 16 * c);
+#pragma unroll
+      for (int j = 0; j < TN; ++j) b[j] = *reinterpret_cast<const float4*>(b_img + b_off + j * 32 * GF_PITCH + 16 * c);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int j = 0; j < TN; ++j) {
+            const float av = e == 0 ? a[i].x : e == 1 ? a[i].y : e == 2 ? a[i].z : a[i].w;
+            const float bv = e == 0 ? b[j].x : e == 1 ? b[j].y : e == 2 ? b[j].z : b[j].w;
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[i][j], 0, 0, 0);
+          }
+    }
+  }
+
+  // the accumulator layout and the stores of gemm_bf3_kernel
+  const bool direct = p.ksplit == 1;
+  float* const out = direct ? p.C : p.slab + (long long)blockIdx.z * p.M * p.N;
+  const long long ldo = direct ? p.ldc : p.N;
+#pragma unroll
+  for (int j = 0; j < TN; ++j) {
+    const int n = n0 + wn * 32 * TN + 32 * j + l31;
+    if (n >= p.N) continue;
+    const float bv = (direct && p.bias) ? p.bias[n] : 0.f;
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+      const int mr = m0 + wm * 32 * TM + 32 * i + 4 * half;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int m = mr + (r & 3) + 8 * (r >> 2);
+        if (m < p.M) {
+          const float v = acc[i][j][r] + bv;
+          out[(long long)m * ldo + n] = direct ? gm_act(v, p.act, p.slope) : v;
+        }
+      }
+    }
+  }
+}
+
 // C[m][n] = act(Σ_z slab[z][m][n] + bias[n]), slabs added in z order (four independent chains, combined in a fixed tree)
 __global__ __launch_bounds__(256) void gemm_reduce_kernel(GemmParams p) {
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -201,7 +309,7 @@ __global__ __launch_bounds__(256) void gemm_reduce_kernel(GemmParams p) {
   p.C[(long long)m * p.ldc + n] = gm_act(v, p.act, p.slope);
 }
 
-// tile size and K split for a shape: the same answer in fst_gemm_workspace_floats and fst_gemm
+// tile size and K split for a shape: the same answer in the workspace queries and in both launchers
 static void gm_geometry(int M, int N, int K, int* big, int* ksplit, int* k_per_split) {
   const int cus = fst_cu_count_or(256);
   const long long t128 = (long long)((M + 127) / 128) * ((N + 127) / 128);
@@ -217,24 +325,25 @@ static void gm_geometry(int M, int N, int K, int* big, int* ksplit, int* k_per_s
   *ksplit = (K + kps - 1) / kps;
 }
 
-extern "C" int64_t fst_gemm_workspace_floats(int M, int N, int K) {
+static int64_t gm_workspace_floats(int M, int N, int K) {
   if (M <= 0 || N <= 0 || K <= 0) return -1;
   int big, ks, kps;
   gm_geometry(M, N, K, &big, &ks, &kps);
   return ks > 1 ? (int64_t)ks * M * N : 0;
 }
 
-extern "C" int fst_gemm(const float* A, int64_t lda, int ta, const float* B, int64_t ldb, int tb, float* C, int64_t ldc, int M, int N,
-                        int K, const float* bias, int act, float slope, float* workspace, int64_t workspace_floats, void* stream) {
-  FST_REQUIRE(A && B && C && M > 0 && N > 0 && K > 0, "fst_gemm: bad arguments (M=%d N=%d K=%d)", M, N, K);
-  FST_REQUIRE(lda >= (ta ? M : K) && ldb >= (tb ? N : K) && ldc >= N, "fst_gemm: leading dimensions lda=%lld ldb=%lld ldc=%lld are smaller "
-              "than a row (M=%d N=%d K=%d ta=%d tb=%d)", (long long)lda, (long long)ldb, (long long)ldc, M, N, K, ta, tb);
-  FST_REQUIRE(act == FST_ACT_NONE || act == FST_ACT_RELU || act == FST_ACT_LEAKY, "fst_gemm: unknown activation %d", act);
+// fst_gemm (f32 = false) and fst_gemm_f32 (f32 = true): one set of checks, one geometry, one reduction
+static int gm_run(const char* who, bool f32, const float* A, int64_t lda, int ta, const float* B, int64_t ldb, int tb, float* C, int64_t ldc,
+                  int M, int N, int K, const float* bias, int act, float slope, float* workspace, int64_t workspace_floats, void* stream) {
+  FST_REQUIRE(A && B && C && M > 0 && N > 0 && K > 0, "%s: bad arguments (M=%d N=%d K=%d)", who, M, N, K);
+  FST_REQUIRE(lda >= (ta ? M : K) && ldb >= (tb ? N : K) && ldc >= N, "%s: leading dimensions lda=%lld ldb=%lld ldc=%lld are smaller "
+              "than a row (M=%d N=%d K=%d ta=%d tb=%d)", who, (long long)lda, (long long)ldb, (long long)ldc, M, N, K, ta, tb);
+  FST_REQUIRE(act == FST_ACT_NONE || act == FST_ACT_RELU || act == FST_ACT_LEAKY, "%s: unknown activation %d", who, act);
   GemmParams p = {};
   int big;
   gm_geometry(M, N, K, &big, &p.ksplit, &p.k_per_split);
-  FST_REQUIRE(p.ksplit == 1 || (workspace && workspace_floats >= (int64_t)p.ksplit * M * N), "fst_gemm: workspace of %lld floats is too small "
-              "(fst_gemm_workspace_floats(%d, %d, %d) = %lld)", (long long)workspace_floats, M, N, K, (long long)p.ksplit * M * N);
+  FST_REQUIRE(p.ksplit == 1 || (workspace && workspace_floats >= (int64_t)p.ksplit * M * N), "%s: workspace of %lld floats is too small "
+              "(%s_workspace_floats(%d, %d, %d) = %lld)", who, (long long)workspace_floats, who, M, N, K, (long long)p.ksplit * M * N);
   auto vec = [](const float* q, int64_t ld, int K_) { return fst_aligned16(q) && ld % 4 == 0 && K_ % 4 == 0; };
   p.A = A; p.B = B; p.C = C; p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.M = M; p.N = N; p.K = K;
   p.ta = ta ? 1 : 0; p.tb = tb ? 1 : 0;
@@ -242,15 +351,35 @@ extern "C" int fst_gemm(const float* A, int64_t lda, int ta, const float* B, int
   p.bias = bias; p.act = act; p.slope = slope; p.slab = workspace;
   const int bt = big ? 128 : 64;
   p.tiles_n = (N + bt - 1) / bt;
-  const unsigned tiles = (unsigned)(((M + bt - 1) / bt) * p.tiles_n);
-  if (big) hipLaunchKernelGGL((gemm_bf3_kernel<2, 2>), dim3(tiles, 1, (unsigned)p.ksplit), dim3(256), 0, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL((gemm_bf3_kernel<1, 1>), dim3(tiles, 1, (unsigned)p.ksplit), dim3(256), 0, (hipStream_t)stream, p);
+  const dim3 grid((unsigned)(((M + bt - 1) / bt) * p.tiles_n), 1, (unsigned)p.ksplit);
+  if (f32) {
+    if (big) hipLaunchKernelGGL((gemm_f32_kernel<2, 2>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((gemm_f32_kernel<1, 1>), grid, dim3(256), 0, (hipStream_t)stream, p);
+  } else {
+    if (big) hipLaunchKernelGGL((gemm_bf3_kernel<2, 2>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((gemm_bf3_kernel<1, 1>), grid, dim3(256), 0, (hipStream_t)stream, p);
+  }
   FST_LAUNCH_CHECK();
   if (p.ksplit > 1) {
     hipLaunchKernelGGL(gemm_reduce_kernel, dim3((unsigned)(((long long)M * N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
     FST_LAUNCH_CHECK();
   }
   return 0;
+}
+
+extern "C" int64_t fst_gemm_workspace_floats(int M, int N, int K) { return gm_workspace_floats(M, N, K); }
+
+extern "C" int fst_gemm(const float* A, int64_t lda, int ta, const float* B, int64_t ldb, int tb, float* C, int64_t ldc, int M, int N,
+                        int K, const float* bias, int act, float slope, float* workspace, int64_t workspace_floats, void* stream) {
+  return gm_run("fst_gemm", false, A, lda, ta, B, ldb, tb, C, ldc, M, N, K, bias, act, slope, workspace, workspace_floats, stream);
+}
+
+// the exact-fp32 product: the geometry, and so the workspace, of fst_gemm
+extern "C" int64_t fst_gemm_f32_workspace_floats(int M, int N, int K) { return gm_workspace_floats(M, N, K); }
+
+extern "C" int fst_gemm_f32(const float* A, int64_t lda, int ta, const float* B, int64_t ldb, int tb, float* C, int64_t ldc, int M, int N,
+                            int K, const float* bias, int act, float slope, float* workspace, int64_t workspace_floats, void* stream) {
+  return gm_run("fst_gemm_f32", true, A, lda, ta, B, ldb, tb, C, ldc, M, N, K, bias, act, slope, workspace, workspace_floats, stream);
 }
 
 // out = dy·act'(y) from the activation's OUTPUT (y > 0 ⇔ pre-activation > 0 for ReLU and for LeakyReLU with a positive slope)

@@ -685,6 +685,24 @@ def gemm_ok(*ts: Tensor) -> bool:
                                     and t.stride(0) >= t.size(1) for t in ts)
 
 
+def _gemm_launch(who: str, timer_key: str, A: Tensor, ta: bool, B: Tensor, tb: bool, bias: Optional[Tensor], act: int, slope: float) -> Tensor:
+    """The launch ``gemm`` and ``gemm_f32`` share: entry points ``fst_<who>`` / ``fst_<who>_workspace_floats`` take the same arguments."""
+    lib = _lib.load()
+    K, M = (A.shape if ta else A.shape[::-1])
+    Kb, N = (B.shape if tb else B.shape[::-1])
+    if K != Kb or (bias is not None and (bias.numel() != N or not bias.is_contiguous())):
+        raise ValueError(f"{who}: A {tuple(A.shape)} (ta={ta}) and B {tuple(B.shape)} (tb={tb}) do not share a reduction length, or bias is not [N]")
+    C = torch.empty(M, N, device=A.device, dtype=torch.float32)
+    ws_n = getattr(lib, f"fst_{who}_workspace_floats")(M, N, K)
+    ws = torch.empty(ws_n, device=A.device, dtype=torch.float32) if ws_n > 0 else None
+    t0 = KERNEL_TIMER.begin() if KERNEL_TIMER is not None else None
+    check(getattr(lib, f"fst_{who}")(ptr(A), A.stride(0), int(ta), ptr(B), B.stride(0), int(tb), ptr(C), N, M, N, K, ptr(bias), act,
+                                     float(slope), ptr(ws), ws_n, stream_ptr()), f"fst_{who}")
+    if t0 is not None:
+        KERNEL_TIMER.end(timer_key, t0, 2.0 * M * N * K, 4.0 * (M * K + N * K + M * N))
+    return C
+
+
 def gemm(A: Tensor, ta: bool, B: Tensor, tb: bool, bias: Optional[Tensor] = None, act: int = ACT_NONE, slope: float = 0.0) -> Tensor:
     """C[m, n] = act(Σ_k A(m,k)·B(n,k) + bias[n]) on the matrix cores in split-bf16 (fst_gemm).  ``A`` is a row-major matrix holding
     A(m,k) at [m, k] (``ta`` False) or at [k, m] (``ta`` True: the reduction index runs down the rows); ``B`` likewise with B(n,k) —
@@ -693,20 +711,21 @@ def gemm(A: Tensor, ta: bool, B: Tensor, tb: bool, bias: Optional[Tensor] = None
     if not gemm_ok(A, B):
         raise ValueError(f"gemm: operands {tuple(A.shape)} / {tuple(B.shape)} must be fp32 matrices with unit column stride on the GPU "
                          f"(split-bf16 mode; FST_MATH={MATH})")
-    lib = _lib.load()
-    K, M = (A.shape if ta else A.shape[::-1])
-    Kb, N = (B.shape if tb else B.shape[::-1])
-    if K != Kb or (bias is not None and (bias.numel() != N or not bias.is_contiguous())):
-        raise ValueError(f"gemm: A {tuple(A.shape)} (ta={ta}) and B {tuple(B.shape)} (tb={tb}) do not share a reduction length, or bias is not [N]")
-    C = torch.empty(M, N, device=A.device, dtype=torch.float32)
-    ws_n = lib.fst_gemm_workspace_floats(M, N, K)
-    ws = torch.empty(ws_n, device=A.device, dtype=torch.float32) if ws_n > 0 else None
-    t0 = KERNEL_TIMER.begin() if KERNEL_TIMER is not None else None
-    check(lib.fst_gemm(ptr(A), A.stride(0), int(ta), ptr(B), B.stride(0), int(tb), ptr(C), N, M, N, K, ptr(bias), act, float(slope),
-                       ptr(ws), ws_n, stream_ptr()), "fst_gemm")
-    if t0 is not None:
-        KERNEL_TIMER.end("gemm_bf3_kernel bf3", t0, 2.0 * M * N * K, 4.0 * (M * K + N * K + M * N))
-    return C
+    return _gemm_launch("gemm", "gemm_bf3_kernel bf3", A, ta, B, tb, bias, act, slope)
+
+
+def gemm_f32_ok(*ts: Tensor) -> bool:
+    """Whether ``gemm_f32`` serves these operands: ``gemm_ok`` in either arithmetic (the kernel is exact fp32 whatever ``MATH`` says)."""
+    return all(t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.numel() > 0 and t.stride(1) == 1
+               and t.stride(0) >= t.size(1) for t in ts)
+
+
+def gemm_f32(A: Tensor, ta: bool, B: Tensor, tb: bool, bias: Optional[Tensor] = None, act: int = ACT_NONE, slope: float = 0.0) -> Tensor:
+    """``gemm``'s contract in exact fp32 (fst_gemm_f32: unsplit operands on the fp32 matrix-core instruction, one fixed fmaf chain
+    per element, K splits added in slab order) — the same bits on every call, and the exact product wherever fp32 can hold it."""
+    if not gemm_f32_ok(A, B):
+        raise ValueError(f"gemm_f32: operands {tuple(A.shape)} / {tuple(B.shape)} must be fp32 matrices with unit column stride on the GPU")
+    return _gemm_launch("gemm_f32", "gemm_f32_kernel f32", A, ta, B, tb, bias, act, slope)
 
 
 def _gemm_rows(t: Tensor) -> Tensor:
@@ -2489,6 +2508,22 @@ class FixedMatmulFn(torch.autograd.Function):
         (Rt,) = ctx.saved_tensors
         Bx, D, O = ctx.shape
         return _fixed_matmul(dy.contiguous(), Rt, Bx, O, D), None, None
+
+
+class FixedGemmF32Fn(torch.autograd.Function):
+    """y = x @ R for a fixed R given only as its contiguous transpose ``Rt`` [O, D], in exact fp32 on ``gemm_f32`` — RandomLayer's
+    big GEMM (C_DAN.py:21) under FST_MATH=f32.  Forward and data gradient read the same copy of the matrix, reduction index
+    contiguous in one and major in the other; both add their K slices in a fixed order, so a step reproduces its own bits."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, Rt: Tensor):
+        ctx.save_for_backward(Rt)
+        return gemm_f32(_gemm_rows(x), False, Rt, False)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (Rt,) = ctx.saved_tensors
+        return gemm_f32(_gemm_rows(dy), False, Rt, True), None
 
 
 _matmul_plans: Dict[Tuple[int, int], Plan] = {}

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FST_ABI_VERSION 20
+#define FST_ABI_VERSION 21
 
 int fst_version(void);
 const char* fst_last_error(void);
@@ -519,8 +519,18 @@ int fst_relu_bwd(const float* dy, const float* y, float* out, int64_t n, void* s
 int64_t fst_gemm_workspace_floats(int M, int N, int K);
 int fst_gemm(const float* A, int64_t lda, int ta, const float* B, int64_t ldb, int tb, float* C, int64_t ldc, int M, int N, int K,
              const float* bias, int act, float slope, float* workspace, int64_t workspace_floats, void* stream);
+/* fst_gemm's contract in EXACT fp32 (ABI v21): the same arguments, layouts, refusals, K split and workspace rule, the operands unsplit
+ * on v_mfma_f32_32x32x2_f32 — RandomLayer's feature-side product torch.mm(feature, R₀) under FST_MATH=f32 (C_DAN.py:20-25 of the
+ * reference: (x, 0, R₀ᵀ, 0) with R₀ᵀ kept contiguous) and its data gradient (dy, 0, R₀ᵀ, 1), which read the same copy of the matrix.
+ * Every C element is one fmaf chain, bit for bit: inside a 32-k stage starting at k0 the order is k0, k0+16, k0+1, k0+17, …, k0+15,
+ * k0+31; the stages of a split in ascending k0 from 0.f; then the splits, slab z joining chain z mod 4 in ascending z (a tail of
+ * fewer than four slabs joins chain 0), ((s0 + s1) + (s2 + s3)) + bias, activation.  No atomics, no zero fill: the same bits on every
+ * run, and an exact result wherever every partial sum is representable.  A refusal returns -1 and launches nothing. */
+int64_t fst_gemm_f32_workspace_floats(int M, int N, int K);
+int fst_gemm_f32(const float* A, int64_t lda, int ta, const float* B, int64_t ldb, int tb, float* C, int64_t ldc, int M, int N, int K,
+                 const float* bias, int act, float slope, float* workspace, int64_t workspace_floats, void* stream);
 /* out = dy·act'(y) from the activation's output y: dy where y > 0, slope·dy elsewhere (slope = 0: ReLU) — nn.ReLU / nn.LeakyReLU backward
- * behind an activation that ran in fst_gemm's epilogue. */
+ * behind an activation that ran in fst_gemm's / fst_gemm_f32's epilogue. */
 int fst_act_bwd(const float* dy, const float* y, float* out, int64_t n, float slope, void* stream);
 int fst_axpy(float* y, const float* x, float alpha, int64_t n, void* stream);          /* y += alpha*x */
 int fst_add_slices(float* dst, int64_t dst_bs, const float* a, int64_t a_bs, const float* b, int64_t b_bs,
