@@ -202,48 +202,131 @@ __device__ __forceinline__ void conv_epilogue(const ConvGemmParams& p, f32x16 (&
     conv_epilogue_mode<MB, NB, 0, false>(p, acc, g, b, t0, wave_n0, half, l31, add_bias, tile);
 }
 
+// ------------------------------------------------------------------------------------------------
+// pieces the forward kernels share
+// ------------------------------------------------------------------------------------------------
+// Where a thread of a forward workgroup works: its lane coordinates, the sample b and first time sample t0 of the workgroup's
+// tile (blockIdx.x), the chunk range [q_begin, q_end) of its K slice (blockIdx.z) and the first tile column of its wave when
+// the four waves share the tile's 128·NB samples (wave_n0 = 0 with NB = 0: the waves split over rows).
+struct ConvTile {
+  int tid, lane, wave, half, l31, b, t0, q_begin, q_end, wave_n0;
+};
+
+template <int TILE_N, int NB>
+__device__ __forceinline__ ConvTile conv_tile(const ConvGemmParams& p, const PlanView& pv) {
+  ConvTile c;
+  c.tid = threadIdx.x; c.lane = c.tid & 63; c.wave = c.tid >> 6;
+  c.half = c.lane >> 5; c.l31 = c.lane & 31;
+  c.b = blockIdx.x / p.tiles_per_seq;
+  c.t0 = (blockIdx.x - c.b * p.tiles_per_seq) * TILE_N;
+  c.q_begin = (int)(((long long)blockIdx.z * pv.n_chunks) / p.ksplit);
+  c.q_end = (int)(((long long)(blockIdx.z + 1) * pv.n_chunks) / p.ksplit);
+  c.wave_n0 = c.wave * NB * 32;
+  return c;
+}
+
+// The staged window, in LDS columns relative to (t0 - pad_left): [jlo, jlo + width) covers the live tap ranges of the chunks
+// [q0, q1) in the M-groups [g0, g1) for a tile of tile_n samples (width 0: nothing live) ...
+__device__ __forceinline__ void conv_window_union(const PlanView& pv, int q0, int q1, int g0, int g1, int tile_n, int& jlo, int& width) {
+  int lo = 1 << 30, hi = -1;
+  for (int q = q0; q < q1; ++q)
+    for (int g = g0; g < g1; ++g) {
+      const int32_t* e = pv.mg + 4 * (g * pv.n_chunks + q);
+      if (e[1] > e[0]) { lo = min(lo, e[0]); hi = max(hi, e[1]); }
+    }
+  if (hi < 0) { jlo = 0; width = 0; return; }
+  jlo = lo * pv.dil;
+  width = (hi - 1 - lo) * pv.dil + tile_n;
+}
+// ... and of one chunk
+__device__ __forceinline__ void conv_window(const PlanView& pv, int q, int g0, int g1, int tile_n, int& jlo, int& width) {
+  conv_window_union(pv, q, q + 1, g0, g1, tile_n, jlo, width);
+}
+
+// Stage the window [jlo, jlo + width) of chunk q (≤ 16 channels), already split, as two bf16 images [time][16 channels] (32-byte
+// rows, ldw rows each, lo behind hi) at hi_img.  Thread = (time j, channel quad cq): 4 channels of one sample -> 8 bytes of each
+// image row.
+__device__ __forceinline__ void stage_window_bf16(const ConvGemmParams& p, const PlanView& pv, const ConvTile& ct, int q, int jlo,
+                                                  int width, char* hi_img) {
+  const int32_t* c = pv.chunk + 4 * q;
+  const int src = c[0], c_begin = c[1], c_count = c[2], L = p.L;
+  const float* xb = p.x[src] + (long long)ct.b * p.x_bs[src] + (long long)c_begin * L;
+  const int tbase = ct.t0 - pv.pad_left + jlo;
+  char* const lo_img = hi_img + p.ldw * 32;
+  const int cq = ct.tid & 3;
+  for (int j = ct.tid >> 2; j < width; j += 64) {
+    const int t = tbase + j;
+    const bool t_ok = t >= 0 && t < L;
+    float v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int cc = 4 * cq + k;
+      v[k] = (t_ok && cc < c_count) ? xb[(long long)cc * L + t] : 0.f;
+    }
+    unsigned h0, h1, l0, l1;
+    split_bf16_pair(v[0], v[1], h0, l0);
+    split_bf16_pair(v[2], v[3], h1, l1);
+    *reinterpret_cast<uint2*>(hi_img + j * 32 + cq * 8) = make_uint2(h0, h1);
+    *reinterpret_cast<uint2*>(lo_img + j * 32 + cq * 8) = make_uint2(l0, l1);
+  }
+}
+
+// The tap walk of the window kernels: the A fragments of the nk k-steps of one (M-group, chunk) stream from L2 (≈500+ cycles)
+// while a k-step is a few hundred cycles of MFMA, so RING k-steps of them are kept in flight in a register ring.  load(k)
+// returns the fragments of k-step k, step(frag) multiplies one k-step; the ring is indexed statically through the unrolled
+// loops: prime, full blocks (no branches around the refills, which are clamped to nk - 1 at the tail), then the tail.
+template <int RING, class Load, class Step>
+__device__ __forceinline__ void ring_walk(int nk, Load&& load, Step&& step) {
+  decltype(load(0)) ring[RING];
+#pragma unroll
+  for (int j = 0; j < RING; ++j) ring[j] = load(j < nk ? j : nk - 1);
+  int kb = 0;
+  for (; kb + RING <= nk; kb += RING) {
+#pragma unroll
+    for (int j = 0; j < RING; ++j) {
+      const auto frag = ring[j];
+      ring[j] = load(kb + j + RING < nk ? kb + j + RING : nk - 1);
+      step(frag);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < RING; ++j)
+    if (kb + j < nk) step(ring[j]);
+}
+template <int MB> struct FragF32 { float v[MB]; };            // one k-step of packed f32 A records
+template <int MB> struct FragBf3 { uint4 h[MB], l[MB]; };     // one 16-deep k-step of the hi / lo weight image
+
+// the first chunk at or after q, before q_end, in which the M-group of the entries ent has a live tap
+__device__ __forceinline__ int next_live(const int32_t* ent, int q, int q_end) {
+  while (q < q_end && ent[4 * q + 1] <= ent[4 * q]) ++q;
+  return q;
+}
+
 template <int MB, int NB>
 __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemmParams p, const int32_t* __restrict__ plan) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int TILE_N = 128 * NB;
   const PlanView pv = plan_view(plan);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int half = lane >> 5, l31 = lane & 31;
-  const int b = blockIdx.x / p.tiles_per_seq;
-  const int t0 = (blockIdx.x - b * p.tiles_per_seq) * TILE_N;
+  const ConvTile ct = conv_tile<TILE_N, NB>(p, pv);
   const int g_begin = blockIdx.y * p.mg_per_wg;
   const int g_end = min(pv.n_mgroups, g_begin + p.mg_per_wg);
-  const int q_begin = (int)(((long long)blockIdx.z * pv.n_chunks) / p.ksplit);
-  const int q_end = (int)(((long long)(blockIdx.z + 1) * pv.n_chunks) / p.ksplit);
-  const int wave_n0 = wave * NB * 32;
   const int ldw = p.ldw, L = p.L, dil = pv.dil;
 
-  // staged window of chunk q, in units of LDS columns relative to (t0 - pad_left): [jlo, jlo+width)
-  auto window = [&](int q, int g0, int g1, int& jlo, int& width) {
-    int lo = 1 << 30, hi = -1;
-    for (int g = g0; g < g1; ++g) {
-      const int32_t* e = pv.mg + 4 * (g * pv.n_chunks + q);
-      if (e[1] > e[0]) { lo = min(lo, e[0]); hi = max(hi, e[1]); }
-    }
-    if (hi < 0) { jlo = 0; width = 0; return; }
-    jlo = lo * dil;
-    width = (hi - 1 - lo) * dil + TILE_N;
-  };
   auto stage = [&](int q, int jlo, int width) {
     const int32_t* c = pv.chunk + 4 * q;
     const int src = c[0], c_begin = c[1], c_count = c[2];
     const int c_pad = (c_count + 1) & ~1;
-    const float* xb = p.x[src] + (long long)b * p.x_bs[src] + (long long)c_begin * L;
-    const int tbase = t0 - pv.pad_left + jlo;
+    const float* xb = p.x[src] + (long long)ct.b * p.x_bs[src] + (long long)c_begin * L;
+    const int tbase = ct.t0 - pv.pad_left + jlo;
     if (p.stage_vec && (tbase & 3) == 0 && (width & 3) == 0 && (ldw & 3) == 0) {
       // 16-byte staging: L, strides and bases are multiples of 4 floats (host-checked), so a float4 is entirely
       // inside or outside [0, L)
       const int w4 = width >> 2;
-      for (int cc = wave; cc < c_pad; cc += 4) {
+      for (int cc = ct.wave; cc < c_pad; cc += 4) {
         const float* row = xb + (long long)cc * L;
         float4* dst = reinterpret_cast<float4*>(lds + cc * ldw);
         const bool live = cc < c_count;
-        for (int j4 = lane; j4 < w4; j4 += 64) {
+        for (int j4 = ct.lane; j4 < w4; j4 += 64) {
           const int t = tbase + 4 * j4;
           float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
           if (live && t >= 0 && t < L) v = *reinterpret_cast<const float4*>(row + t);
@@ -252,39 +335,34 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemmParams p, const 
       }
       return;
     }
-    for (int cc = wave; cc < c_pad; cc += 4) {
+    for (int cc = ct.wave; cc < c_pad; cc += 4) {
       const float* row = xb + (long long)cc * L;
       float* dst = lds + cc * ldw;
       const bool live = cc < c_count;
-      for (int j = lane; j < width; j += 64) {
+      for (int j = ct.lane; j < width; j += 64) {
         const int t = tbase + j;
         dst[j] = (live && t >= 0 && t < L) ? row[t] : 0.f;
       }
     }
   };
 
-  const bool stage_once = (q_end - q_begin == 1);
+  const bool stage_once = (ct.q_end - ct.q_begin == 1);
   int jlo = 0, width = 0;
   if (stage_once) {
-    window(q_begin, g_begin, g_end, jlo, width);
-    stage(q_begin, jlo, width);
+    conv_window(pv, ct.q_begin, g_begin, g_end, TILE_N, jlo, width);
+    stage(ct.q_begin, jlo, width);
     __syncthreads();
   }
 
   for (int g = g_begin; g < g_end; ++g) {
     f32x16 acc[MB][NB];
-#pragma unroll
-    for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-      for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[mb][nb][r] = 0.f;
+    zero_acc(acc);
 
-    for (int q = q_begin; q < q_end; ++q) {
+    for (int q = ct.q_begin; q < ct.q_end; ++q) {
       const int32_t* e = pv.mg + 4 * (g * pv.n_chunks + q);
       const int lo = e[0], hi = e[1];
       if (!stage_once) {
-        window(q, g, g + 1, jlo, width);
+        conv_window(pv, q, g, g + 1, TILE_N, jlo, width);
         __syncthreads();   // previous chunk's readers are done
         stage(q, jlo, width);
         __syncthreads();
@@ -293,56 +371,33 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvGemmParams p, const 
       const int c_pad = (pv.chunk[4 * q + 2] + 1) & ~1;
       const int half_c = c_pad >> 1;
       const int nk = (hi - lo) * half_c;                     // k-steps of this (M-group, chunk): tap-major
-      const float* ap = p.a + (long long)e[2] * (MB * 64) + lane;
-      // The A records stream from L2 (≈500+ cycles) while a k-step is only MB*NB*64 cycles of MFMA: keep RING
-      // k-steps of A in flight in a register ring (statically indexed through the unrolled inner loop).
-      constexpr int RING = (MB * NB >= 8) ? 2 : (MB * NB >= 4 ? 4 : 8);
-      float ring[RING][MB];
-#pragma unroll
-      for (int j = 0; j < RING; ++j) {
-        const int kk = j < nk ? j : nk - 1;
-#pragma unroll
-        for (int mb = 0; mb < MB; ++mb) ring[j][mb] = ap[((long long)kk * MB + mb) * 64];
-      }
+      const float* ap = p.a + (long long)e[2] * (MB * 64) + ct.lane;
+      constexpr int RING = (MB * NB >= 8) ? 2 : (MB * NB >= 4 ? 4 : 8);   // a k-step is only MB*NB*64 cycles of MFMA
       int tap = lo, cp = 0;
-      const float* bbase = lds + half * ldw - jlo + wave_n0 + l31;
-      auto kstep = [&](const float (&av)[MB]) {
-        float bv[NB];
-        const float* bp = bbase + tap * dil + 2 * cp * ldw;
+      const float* bbase = lds + ct.half * ldw - jlo + ct.wave_n0 + ct.l31;
+      ring_walk<RING>(
+          nk,
+          [&](int k) {
+            FragF32<MB> a;
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) bv[nb] = bp[nb * 32];
+            for (int mb = 0; mb < MB; ++mb) a.v[mb] = ap[((long long)k * MB + mb) * 64];
+            return a;
+          },
+          [&](const FragF32<MB>& a) {
+            float bv[NB];
+            const float* bp = bbase + tap * dil + 2 * cp * ldw;
 #pragma unroll
-        for (int mb = 0; mb < MB; ++mb)
+            for (int nb = 0; nb < NB; ++nb) bv[nb] = bp[nb * 32];
 #pragma unroll
-          for (int nb = 0; nb < NB; ++nb)
-            acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[mb], bv[nb], acc[mb][nb], 0, 0, 0);
-        if (++cp == half_c) { cp = 0; ++tap; }
-      };
-      int kb = 0;
-      for (; kb + RING <= nk; kb += RING) {                   // full blocks: no branches around the ring loads
+            for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
-        for (int j = 0; j < RING; ++j) {
-          float av[MB];
-#pragma unroll
-          for (int mb = 0; mb < MB; ++mb) av[mb] = ring[j][mb];
-          const int kn = kb + j + RING < nk ? kb + j + RING : nk - 1;   // refill this slot (clamped at the tail)
-#pragma unroll
-          for (int mb = 0; mb < MB; ++mb) ring[j][mb] = ap[((long long)kn * MB + mb) * 64];
-          kstep(av);
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < RING; ++j) {                        // tail: operands are already in the ring
-        if (kb + j < nk) {
-          float av[MB];
-#pragma unroll
-          for (int mb = 0; mb < MB; ++mb) av[mb] = ring[j][mb];
-          kstep(av);
-        }
-      }
+              for (int nb = 0; nb < NB; ++nb)
+                acc[mb][nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.v[mb], bv[nb], acc[mb][nb], 0, 0, 0);
+            if (++cp == half_c) { cp = 0; ++tap; }
+          });
     }
 
-    conv_epilogue<MB, NB>(p, acc, g, b, t0, wave_n0, half, l31, p.bias != nullptr && blockIdx.z == 0, lds);
+    conv_epilogue<MB, NB>(p, acc, g, ct.b, ct.t0, ct.wave_n0, ct.half, ct.l31, p.bias != nullptr && blockIdx.z == 0, lds);
   }
 }
 
@@ -376,27 +431,17 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_pipe_kernel(ConvGemmParams p
   constexpr int BV = B_FLOATS / 256;                 // floats per thread per stage
   constexpr int LOG_N = NB == 1 ? 7 : (NB == 2 ? 8 : 9);
   const PlanView pv = plan_view(plan);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int half = lane >> 5, l31 = lane & 31;
-  const int b = blockIdx.x / p.tiles_per_seq;
-  const int t0 = (blockIdx.x - b * p.tiles_per_seq) * TILE_N;
+  const ConvTile ct = conv_tile<TILE_N, NB>(p, pv);
+  const int lane = ct.lane;
   const int g = blockIdx.y;
-  const int q_begin = (int)(((long long)blockIdx.z * pv.n_chunks) / p.ksplit);
-  const int q_end = (int)(((long long)(blockIdx.z + 1) * pv.n_chunks) / p.ksplit);
-  const int wave_n0 = wave * NB * 32;
   const int L = p.L;
   constexpr int STAGE_FLOATS = A_FLOATS + B_FLOATS;      // buffer b: A at lds + b*STAGE_FLOATS, B right after it
   const int32_t* ent = pv.mg + 4 * (g * pv.n_chunks);
 
-  auto next_live = [&](int q) {
-    while (q < q_end && ent[4 * q + 1] <= ent[4 * q]) ++q;
-    return q;
-  };
-
   float4 a_st[AV];
   float b_st[BV];
-  const int wave_s = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int jcol = tid & (TILE_N - 1);
+  const int wave_s = __builtin_amdgcn_readfirstlane(ct.tid >> 6);
+  const int jcol = ct.tid & (TILE_N - 1);
   auto fetch = [&](int q) {
     const int32_t* c = pv.chunk + 4 * q;
     const int32_t* e = ent + 4 * q;
@@ -405,18 +450,18 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_pipe_kernel(ConvGemmParams p
     const float4* asrc = reinterpret_cast<const float4*>(p.a + (long long)e[2] * (MB * 64));
 #pragma unroll
     for (int i = 0; i < AV; ++i) {
-      const int idx = tid + 256 * i;
+      const int idx = ct.tid + 256 * i;
       a_st[i] = idx < nvec ? asrc[idx] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    const float* xb = p.x[c[0]] + (long long)b * p.x_bs[c[0]] + (long long)c[1] * L;
-    const int tbase = t0 - pv.pad_left + e[0] * pv.dil;
+    const float* xb = p.x[c[0]] + (long long)ct.b * p.x_bs[c[0]] + (long long)c[1] * L;
+    const int tbase = ct.t0 - pv.pad_left + e[0] * pv.dil;
     if (VEC) {
       // 16-byte loads: the host guarantees every tap shift, L, the strides and the base pointers are multiples
       // of 4 floats, so a float4 is entirely inside or entirely outside [0, L).  Element ev = tid + 256*i of the
       // [PIPE_C][TILE_N/4] float4 tile: row = (tid >> (LOG_N-2)) + (1024 >> LOG_N)*i (wave-uniform), column 4*(tid & (TILE_N/4-1)).
       const int row0 = wave_s >> (LOG_N - 8 >= 0 ? LOG_N - 8 : 0);
-      const int row_lane = LOG_N - 8 >= 0 ? 0 : ((tid & 63) >> (LOG_N - 2));      // TILE_N=128: a wave spans 2 rows
-      const int col = (tid & (TILE_N / 4 - 1)) * 4;
+      const int row_lane = LOG_N - 8 >= 0 ? 0 : ((ct.tid & 63) >> (LOG_N - 2));      // TILE_N=128: a wave spans 2 rows
+      const int col = (ct.tid & (TILE_N / 4 - 1)) * 4;
       const int t = tbase + col;
       const bool t_ok = t >= 0 && t < L;
 #pragma unroll
@@ -444,32 +489,27 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_pipe_kernel(ConvGemmParams p
   auto commit = [&](int buf) {
 #pragma unroll
     for (int i = 0; i < AV; ++i) {
-      const int idx = tid + 256 * i;
+      const int idx = ct.tid + 256 * i;
       if (idx < A_FLOATS / 4) reinterpret_cast<float4*>(lds + buf * STAGE_FLOATS)[idx] = a_st[i];
     }
     if (VEC) {
 #pragma unroll
       for (int i = 0; i < BV / 4; ++i)
-        reinterpret_cast<float4*>(lds + buf * STAGE_FLOATS + A_FLOATS)[tid + 256 * i] =
+        reinterpret_cast<float4*>(lds + buf * STAGE_FLOATS + A_FLOATS)[ct.tid + 256 * i] =
             make_float4(b_st[4 * i], b_st[4 * i + 1], b_st[4 * i + 2], b_st[4 * i + 3]);
     } else {
 #pragma unroll
-      for (int i = 0; i < BV; ++i) lds[buf * STAGE_FLOATS + A_FLOATS + tid + 256 * i] = b_st[i];
+      for (int i = 0; i < BV; ++i) lds[buf * STAGE_FLOATS + A_FLOATS + ct.tid + 256 * i] = b_st[i];
     }
   };
 
   f32x16 acc[MB][NB];
-#pragma unroll
-  for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mb][nb][r] = 0.f;
+  zero_acc(acc);
 
   FST_SUMS(8);
   FST_T(ts0);
-  int q = next_live(q_begin);
-  if (q < q_end) {
+  int q = next_live(ent, ct.q_begin, ct.q_end);
+  if (q < ct.q_end) {
     fetch(q);
     commit(0);
   }
@@ -477,15 +517,15 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_pipe_kernel(ConvGemmParams p
   FST_T(ts1);
   FST_ACC(0, ts0, ts1);                                   // prologue
   int buf = 0;
-  while (q < q_end) {
+  while (q < ct.q_end) {
     FST_T(ta);
     const int nrec = ((pv.chunk[4 * q + 2] + 1) & ~1) / 2;   // read before the prefetch is in flight
-    const int qn = next_live(q + 1);
-    if (qn < q_end) fetch(qn);
+    const int qn = next_live(ent, q + 1, ct.q_end);
+    if (qn < ct.q_end) fetch(qn);
     FST_T(tb);
     FST_ACC(1, ta, tb);                                   // fetch issue
     const float* ap = lds + buf * STAGE_FLOATS + lane;
-    const float* bp = lds + buf * STAGE_FLOATS + A_FLOATS + half * TILE_N + wave_n0 + l31;
+    const float* bp = lds + buf * STAGE_FLOATS + A_FLOATS + ct.half * TILE_N + ct.wave_n0 + ct.l31;
     for (int r = 0; r < nrec; ++r) {
       float av[MB], bv[NB];
 #pragma unroll
@@ -505,7 +545,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_pipe_kernel(ConvGemmParams p
 #endif
     FST_T(td);
     FST_ACC(3, tc, td);                                   // waiting for the prefetched stage
-    if (qn < q_end) commit(buf ^ 1);
+    if (qn < ct.q_end) commit(buf ^ 1);
     FST_T(te);
     FST_ACC(4, td, te);                                   // LDS commit
     __syncthreads();
@@ -516,7 +556,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_pipe_kernel(ConvGemmParams p
   }
   FST_T(tg);
 
-  conv_epilogue<MB, NB>(p, acc, g, b, t0, wave_n0, half, l31, p.bias != nullptr && blockIdx.z == 0, lds);
+  conv_epilogue<MB, NB>(p, acc, g, ct.b, ct.t0, ct.wave_n0, ct.half, ct.l31, p.bias != nullptr && blockIdx.z == 0, lds);
   FST_T(th);
   FST_ACC(6, tg, th);                                     // epilogue
   FST_ACC(7, ts0, th);                                    // whole wave
@@ -554,23 +594,16 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_bf3_kernel(ConvGemmParams p,
   constexpr int NPW = (NI + 3) / 4;                   // per wave (waves >= NI % 4 issue one fewer when NI % 4 != 0)
   char* const ldsb = reinterpret_cast<char*>(lds);
   const PlanView pv = plan_view(plan);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int half = lane >> 5, l31 = lane & 31;
-  const int b = blockIdx.x / p.tiles_per_seq;
-  const int t0 = (blockIdx.x - b * p.tiles_per_seq) * TILE_N;
+  const ConvTile ct = conv_tile<TILE_N, NB>(p, pv);
+  // (as plain ints: with the struct captured by the lambdas below the NB = 2 instances compile to 3 % more instructions and
+  // measured 3-10 % slower: profiles/conv_engine_refactor.txt)
+  const int tid = ct.tid, lane = ct.lane, half = ct.half, l31 = ct.l31, b = ct.b, t0 = ct.t0, q_begin = ct.q_begin, q_end = ct.q_end,
+            wave_n0 = ct.wave_n0;
   const int g = blockIdx.y;
-  const int q_begin = (int)(((long long)blockIdx.z * pv.n_chunks) / p.ksplit);
-  const int q_end = (int)(((long long)(blockIdx.z + 1) * pv.n_chunks) / p.ksplit);
-  const int wave_n0 = wave * NB * 32;
   const int L = p.L;
   const int32_t* ent = pv.mg + 4 * (g * pv.n_chunks);
   const int wave_s = __builtin_amdgcn_readfirstlane(tid >> 6);
   const char* const zero16 = reinterpret_cast<const char*>(p.a) + (long long)pv.n_stages * A_BYTES;
-
-  auto next_live = [&](int q) {
-    while (q < q_end && ent[4 * q + 1] <= ent[4 * q]) ++q;
-    return q;
-  };
 
   // LDS-DMA of stage q into ring slot `slot`: piece idx = wave + 4*i; pieces [0, NA) are A, the rest B sub-tiles
   auto issue = [&](int q, int slot) {
@@ -611,17 +644,12 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_bf3_kernel(ConvGemmParams p,
   };
 
   f32x16 acc[MB][NB];
-#pragma unroll
-  for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mb][nb][r] = 0.f;
+  zero_acc(acc);
 
   FST_SUMS(8);
   FST_T(ts0);
-  int q0 = next_live(q_begin);
-  int q1 = q0 < q_end ? next_live(q0 + 1) : q_end;
+  int q0 = next_live(ent, q_begin, q_end);
+  int q1 = q0 < q_end ? next_live(ent, q0 + 1, q_end) : q_end;
   if (q0 < q_end) issue(q0, 0);
   if (q1 < q_end) issue(q1, 1);
   int slot = 0;
@@ -629,7 +657,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_bf3_kernel(ConvGemmParams p,
   FST_ACC(0, ts0, ts1);                                // prologue
   while (q0 < q_end) {
     FST_T(ta);
-    const int q2 = q1 < q_end ? next_live(q1 + 1) : q_end;
+    const int q2 = q1 < q_end ? next_live(ent, q1 + 1, q_end) : q_end;
     wait_stage(q1 < q_end ? 1 : 0);                    // stage q0 has landed (this wave's pieces) ...
     FST_T(tb);
     FST_ACC(1, ta, tb);                                // next_live + vmcnt wait
@@ -697,154 +725,73 @@ __global__ __launch_bounds__(256, 2) void conv_win_bf3_kernel(ConvGemmParams p, 
   constexpr int TILE_N = 128 * NB;
   char* const ldsb = reinterpret_cast<char*>(lds);
   const PlanView pv = plan_view(plan);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int half = lane >> 5, l31 = lane & 31;
-  const int b = blockIdx.x / p.tiles_per_seq;
-  const int t0 = (blockIdx.x - b * p.tiles_per_seq) * TILE_N;
+  const ConvTile ct = conv_tile<TILE_N, NB>(p, pv);
   const int g_begin = blockIdx.y * p.mg_per_wg;
   const int g_end = min(pv.n_mgroups, g_begin + p.mg_per_wg);
-  const int q_begin = (int)(((long long)blockIdx.z * pv.n_chunks) / p.ksplit);
-  const int q_end = (int)(((long long)(blockIdx.z + 1) * pv.n_chunks) / p.ksplit);
-  const int wave_n0 = wave * NB * 32;
-  const int L = p.L, dil = pv.dil;
   const int slot_bytes = p.ldw * 64;                    // one chunk: hi image [ldw rows][32 B], then lo image
 
-  auto window = [&](int q, int g0, int g1, int& jlo, int& width) {
-    int lo = 1 << 30, hi = -1;
-    for (int g = g0; g < g1; ++g) {
-      const int32_t* e = pv.mg + 4 * (g * pv.n_chunks + q);
-      if (e[1] > e[0]) { lo = min(lo, e[0]); hi = max(hi, e[1]); }
-    }
-    if (hi < 0) { jlo = 0; width = 0; return; }
-    jlo = lo * dil;
-    width = (hi - 1 - lo) * dil + TILE_N;
-  };
-  // stage chunk q: thread = (time j, channel quad cq): 4 channels of one sample -> 8 bytes of each image row
-  auto stage = [&](int q, int slot, int jlo, int width) {
-    const int32_t* c = pv.chunk + 4 * q;
-    const int src = c[0], c_begin = c[1], c_count = c[2];
-    const float* xb = p.x[src] + (long long)b * p.x_bs[src] + (long long)c_begin * L;
-    const int tbase = t0 - pv.pad_left + jlo;
-    char* const hi_img = ldsb + slot * slot_bytes;
-    char* const lo_img = hi_img + p.ldw * 32;
-    const int cq = tid & 3;
-    for (int j = tid >> 2; j < width; j += 64) {
-      const int t = tbase + j;
-      const bool t_ok = t >= 0 && t < L;
-      float v[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int cc = 4 * cq + k;
-        v[k] = (t_ok && cc < c_count) ? xb[(long long)cc * L + t] : 0.f;
-      }
-      unsigned h0, h1, l0, l1;
-      split_bf16_pair(v[0], v[1], h0, l0);
-      split_bf16_pair(v[2], v[3], h1, l1);
-      *reinterpret_cast<uint2*>(hi_img + j * 32 + cq * 8) = make_uint2(h0, h1);
-      *reinterpret_cast<uint2*>(lo_img + j * 32 + cq * 8) = make_uint2(l0, l1);
-    }
-  };
-
-  // every chunk of this K range resident at once (host-decided): stage them all, then every M-group reuses them
+  // every chunk of this K range resident at once (host-decided): stage them all on one common origin, the union window, then
+  // every M-group reuses them
   const bool resident = p.stage_vec != 0;               // (field reused: 1 = all chunks fit)
   int jlo_all = 0, width_all = 0;
   if (resident) {
-    for (int q = q_begin; q < q_end; ++q) {
-      int jl, w;
-      window(q, g_begin, g_end, jl, w);
-      // one common origin for all chunks: the union window
-      if (q == q_begin) { jlo_all = jl; width_all = w; }
-      else if (w > 0) {
-        const int lo2 = min(jlo_all, jl), hi2 = max(jlo_all + width_all, jl + w);
-        if (width_all == 0) { jlo_all = jl; width_all = w; } else { jlo_all = lo2; width_all = hi2 - lo2; }
-      }
-    }
-    for (int q = q_begin; q < q_end; ++q) stage(q, q - q_begin, jlo_all, width_all);
+    conv_window_union(pv, ct.q_begin, ct.q_end, g_begin, g_end, TILE_N, jlo_all, width_all);
+    for (int q = ct.q_begin; q < ct.q_end; ++q)
+      stage_window_bf16(p, pv, ct, q, jlo_all, width_all, ldsb + (q - ct.q_begin) * slot_bytes);
     __syncthreads();
   }
 
   for (int g = g_begin; g < g_end; ++g) {
     f32x16 acc[MB][NB];
-#pragma unroll
-    for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-      for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[mb][nb][r] = 0.f;
+    zero_acc(acc);
 
-    for (int q = q_begin; q < q_end; ++q) {
+    for (int q = ct.q_begin; q < ct.q_end; ++q) {
       const int32_t* e = pv.mg + 4 * (g * pv.n_chunks + q);
       const int lo = e[0], hi = e[1];
-      int jlo = jlo_all, slot = q - q_begin;
+      int jlo = jlo_all, slot = q - ct.q_begin;
       if (!resident) {
         int width;
-        window(q, g, g + 1, jlo, width);
+        conv_window(pv, q, g, g + 1, TILE_N, jlo, width);
         slot = 0;
         __syncthreads();   // previous chunk's readers are done
-        stage(q, 0, jlo, width);
+        stage_window_bf16(p, pv, ct, q, jlo, width, ldsb);
         __syncthreads();
       }
       if (hi <= lo) continue;
-      const int nk = hi - lo;                                // one 16-deep k-step per live tap
-      const uint4* ap = reinterpret_cast<const uint4*>(p.a) + (long long)e[3] * (MB * 128) + lane;
-      constexpr int RING = MB == 1 ? 4 : 2;
-      uint4 rh[RING][MB], rl[RING][MB];
-#pragma unroll
-      for (int j = 0; j < RING; ++j) {
-        const int kk = j < nk ? j : nk - 1;
-#pragma unroll
-        for (int mb = 0; mb < MB; ++mb) {
-          rh[j][mb] = ap[(kk * MB + mb) * 128];
-          rl[j][mb] = ap[(kk * MB + mb) * 128 + 64];
-        }
-      }
-      const char* hi_img = ldsb + slot * slot_bytes + (wave_n0 + l31 - jlo) * 32 + half * 16;
+      const uint4* ap = reinterpret_cast<const uint4*>(p.a) + (long long)e[3] * (MB * 128) + ct.lane;
+      const char* hi_img = ldsb + slot * slot_bytes + (ct.wave_n0 + ct.l31 - jlo) * 32 + ct.half * 16;
       const char* lo_img = hi_img + p.ldw * 32;
       int tap = lo;
-      auto kstep = [&](const uint4 (&ah)[MB], const uint4 (&al)[MB]) {
-        const int roff = tap * dil * 32;
-        bf16x8 bh[NB], bl[NB];
+      ring_walk<(MB == 1 ? 4 : 2)>(
+          hi - lo,                                           // one 16-deep k-step per live tap
+          [&](int k) {
+            FragBf3<MB> a;
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-          bh[nb] = *reinterpret_cast<const bf16x8*>(hi_img + roff + nb * 1024);
-          bl[nb] = *reinterpret_cast<const bf16x8*>(lo_img + roff + nb * 1024);
-        }
+            for (int mb = 0; mb < MB; ++mb) {
+              a.h[mb] = ap[(k * MB + mb) * 128];
+              a.l[mb] = ap[(k * MB + mb) * 128 + 64];
+            }
+            return a;
+          },
+          [&](const FragBf3<MB>& a) {
+            const int roff = tap * pv.dil * 32;
+            bf16x8 bh[NB], bl[NB];
 #pragma unroll
-        for (int mb = 0; mb < MB; ++mb) {
-          const bf16x8 a_h = __builtin_bit_cast(bf16x8, ah[mb]), a_l = __builtin_bit_cast(bf16x8, al[mb]);
+            for (int nb = 0; nb < NB; ++nb) {
+              bh[nb] = *reinterpret_cast<const bf16x8*>(hi_img + roff + nb * 1024);
+              bl[nb] = *reinterpret_cast<const bf16x8*>(lo_img + roff + nb * 1024);
+            }
 #pragma unroll
-          for (int nb = 0; nb < NB; ++nb) mfma_bf3(acc[mb][nb], a_h, a_l, bh[nb], bl[nb]);
-        }
-        ++tap;
-      };
-      int kb = 0;
-      for (; kb + RING <= nk; kb += RING) {
+            for (int mb = 0; mb < MB; ++mb) {
+              const bf16x8 a_h = __builtin_bit_cast(bf16x8, a.h[mb]), a_l = __builtin_bit_cast(bf16x8, a.l[mb]);
 #pragma unroll
-        for (int j = 0; j < RING; ++j) {
-          uint4 ah[MB], al[MB];
-#pragma unroll
-          for (int mb = 0; mb < MB; ++mb) { ah[mb] = rh[j][mb]; al[mb] = rl[j][mb]; }
-          const int kn = kb + j + RING < nk ? kb + j + RING : nk - 1;
-#pragma unroll
-          for (int mb = 0; mb < MB; ++mb) {
-            rh[j][mb] = ap[(kn * MB + mb) * 128];
-            rl[j][mb] = ap[(kn * MB + mb) * 128 + 64];
-          }
-          kstep(ah, al);
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < RING; ++j) {
-        if (kb + j < nk) {
-          uint4 ah[MB], al[MB];
-#pragma unroll
-          for (int mb = 0; mb < MB; ++mb) { ah[mb] = rh[j][mb]; al[mb] = rl[j][mb]; }
-          kstep(ah, al);
-        }
-      }
+              for (int nb = 0; nb < NB; ++nb) mfma_bf3(acc[mb][nb], a_h, a_l, bh[nb], bl[nb]);
+            }
+            ++tap;
+          });
     }
 
-    conv_epilogue<MB, NB>(p, acc, g, b, t0, wave_n0, half, l31, p.bias != nullptr && blockIdx.z == 0, lds);
+    conv_epilogue<MB, NB>(p, acc, g, ct.b, ct.t0, ct.wave_n0, ct.half, ct.l31, p.bias != nullptr && blockIdx.z == 0, lds);
   }
 }
 
@@ -862,102 +809,54 @@ __global__ __launch_bounds__(256, 2) void conv_win_rows_kernel(ConvGemmParams p,
   constexpr int NB = 8, TILE_N = 256;
   char* const ldsb = reinterpret_cast<char*>(lds);
   const PlanView pv = plan_view(plan);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int half = lane >> 5, l31 = lane & 31;
-  const int b = blockIdx.x / p.tiles_per_seq;
-  const int t0 = (blockIdx.x - b * p.tiles_per_seq) * TILE_N;
-  const int L = p.L, dil = pv.dil, G = pv.n_mgroups, Q = pv.n_chunks;
+  const ConvTile ct = conv_tile<TILE_N, 0>(p, pv);       // (its K range is every chunk: resident windows have no K split)
+  const int G = pv.n_mgroups, Q = pv.n_chunks;
   const int slot_bytes = p.ldw * 64;
   // the union window of every (M-group, chunk): one common origin
-  int lo_all = 1 << 30, hi_all = -1;
-  for (int g = 0; g < G; ++g)
-    for (int q = 0; q < Q; ++q) {
-      const int32_t* e = pv.mg + 4 * (g * Q + q);
-      if (e[1] > e[0]) { lo_all = min(lo_all, e[0]); hi_all = max(hi_all, e[1]); }
-    }
-  const int jlo = lo_all * dil, width = (hi_all - 1 - lo_all) * dil + TILE_N;
-  for (int q = 0; q < Q; ++q) {                          // stage chunk q: thread = (time j, channel quad cq)
-    const int32_t* c = pv.chunk + 4 * q;
-    const int src = c[0], c_begin = c[1], c_count = c[2];
-    const float* xb = p.x[src] + (long long)b * p.x_bs[src] + (long long)c_begin * L;
-    const int tbase = t0 - pv.pad_left + jlo;
-    char* const hi_img = ldsb + q * slot_bytes;
-    char* const lo_img = hi_img + p.ldw * 32;
-    const int cq = tid & 3;
-    for (int j = tid >> 2; j < width; j += 64) {
-      const int t = tbase + j;
-      const bool t_ok = t >= 0 && t < L;
-      float v[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int cc = 4 * cq + k;
-        v[k] = (t_ok && cc < c_count) ? xb[(long long)cc * L + t] : 0.f;
-      }
-      unsigned h0, h1, l0, l1;
-      split_bf16_pair(v[0], v[1], h0, l0);
-      split_bf16_pair(v[2], v[3], h1, l1);
-      *reinterpret_cast<uint2*>(hi_img + j * 32 + cq * 8) = make_uint2(h0, h1);
-      *reinterpret_cast<uint2*>(lo_img + j * 32 + cq * 8) = make_uint2(l0, l1);
-    }
-  }
+  int jlo, width;
+  conv_window_union(pv, 0, Q, 0, G, TILE_N, jlo, width);
+  for (int q = 0; q < Q; ++q) stage_window_bf16(p, pv, ct, q, jlo, width, ldsb + q * slot_bytes);
   __syncthreads();
   // M-groups of this wave: position i of its list is group 4i + w on even i, 4i + 3 - w on odd i (the tap count grows with
   // the group index: alternating the direction pairs a wave's small groups with large ones)
   for (int i = 0; 4 * i < G; ++i) {
-    const int g = 4 * i + ((i & 1) ? 3 - wave : wave);
+    const int g = 4 * i + ((i & 1) ? 3 - ct.wave : ct.wave);
     if (g >= G) continue;
     f32x16 acc[1][NB];
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[0][nb][r] = 0.f;
+    zero_acc(acc);
     for (int q = 0; q < Q; ++q) {
       const int32_t* e = pv.mg + 4 * (g * Q + q);
       const int lo = e[0], nk = e[1] - e[0];
       if (nk <= 0) continue;
-      const uint4* ap = reinterpret_cast<const uint4*>(p.a) + (long long)e[3] * 128 + lane;
-      constexpr int RING = 4;
-      uint4 rh[RING], rl[RING];
-#pragma unroll
-      for (int j = 0; j < RING; ++j) {
-        const int kk = j < nk ? j : nk - 1;
-        rh[j] = ap[kk * 128];
-        rl[j] = ap[kk * 128 + 64];
-      }
-      const char* hi_img = ldsb + q * slot_bytes + (l31 - jlo) * 32 + half * 16;
+      const uint4* ap = reinterpret_cast<const uint4*>(p.a) + (long long)e[3] * 128 + ct.lane;
+      const char* hi_img = ldsb + q * slot_bytes + (ct.l31 - jlo) * 32 + ct.half * 16;
       const char* lo_img = hi_img + p.ldw * 32;
       int tap = lo;
-      auto kstep = [&](const uint4 ah, const uint4 al) {
-        const int roff = tap * dil * 32;
-        const bf16x8 a_h = __builtin_bit_cast(bf16x8, ah), a_l = __builtin_bit_cast(bf16x8, al);
+      ring_walk<4>(
+          nk,
+          [&](int k) {
+            FragBf3<1> a;
+            a.h[0] = ap[k * 128];
+            a.l[0] = ap[k * 128 + 64];
+            return a;
+          },
+          [&](const FragBf3<1>& a) {
+            const int roff = tap * pv.dil * 32;
+            const bf16x8 a_h = __builtin_bit_cast(bf16x8, a.h[0]), a_l = __builtin_bit_cast(bf16x8, a.l[0]);
 #pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-          const bf16x8 bh = *reinterpret_cast<const bf16x8*>(hi_img + roff + nb * 1024);
-          const bf16x8 bl = *reinterpret_cast<const bf16x8*>(lo_img + roff + nb * 1024);
-          mfma_bf3(acc[0][nb], a_h, a_l, bh, bl);
-        }
-        ++tap;
-      };
-      int kb = 0;
-      for (; kb + RING <= nk; kb += RING) {
-#pragma unroll
-        for (int j = 0; j < RING; ++j) {
-          const uint4 ah = rh[j], al = rl[j];
-          const int kn = kb + j + RING < nk ? kb + j + RING : nk - 1;
-          rh[j] = ap[kn * 128];
-          rl[j] = ap[kn * 128 + 64];
-          kstep(ah, al);
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < RING; ++j)
-        if (kb + j < nk) kstep(rh[j], rl[j]);
+            for (int nb = 0; nb < NB; ++nb) {
+              const bf16x8 bh = *reinterpret_cast<const bf16x8*>(hi_img + roff + nb * 1024);
+              const bf16x8 bl = *reinterpret_cast<const bf16x8*>(lo_img + roff + nb * 1024);
+              mfma_bf3(acc[0][nb], a_h, a_l, bh, bl);
+            }
+            ++tap;
+          });
     }
     // plain stores only (the launcher sends residual / accumulate / atomic epilogues to conv_win_bf3_kernel): the other modes'
     // operand arrays for eight column blocks would cost this kernel its registers
-    float* tile = lds + p.epi_lds_off + wave * (32 * 36);
-    if (p.epi_vec) conv_epilogue_mode<1, NB, 0, true>(p, acc, g, b, t0, 0, half, l31, p.bias != nullptr, tile);
-    else conv_epilogue_mode<1, NB, 0, false>(p, acc, g, b, t0, 0, half, l31, p.bias != nullptr, tile);
+    float* tile = lds + p.epi_lds_off + ct.wave * (32 * 36);
+    if (p.epi_vec) conv_epilogue_mode<1, NB, 0, true>(p, acc, g, ct.b, ct.t0, 0, ct.half, ct.l31, p.bias != nullptr, tile);
+    else conv_epilogue_mode<1, NB, 0, false>(p, acc, g, ct.b, ct.t0, 0, ct.half, ct.l31, p.bias != nullptr, tile);
   }
 }
 
@@ -1290,6 +1189,303 @@ struct WgradParams {
 
 #define WG_ITEMS 4   // row-blocks (32 packed K-rows each) per workgroup
 
+// Both operands of conv_wgrad_kernel travel global → registers (fetch, one (b,t) tile ahead of the multiply) → LDS (commit).  In the
+// dword thread maps below a row is row_u + (0 or half) with row_u wave-uniform; the fetches address with it: the row part of every
+// global address is SGPR arithmetic and one per-lane offset (half·L + column) the only address VGPR, so nothing large is hoisted
+// out of the tile loop.
+__device__ __forceinline__ int wg_wave_u(int tid) { return __builtin_amdgcn_readfirstlane(tid >> 6); }
+
+// The dy tile: MBW·32 output channels × TW samples starting at channel m0, sample tt0 of batch element b.  In LDS at dyt: rows of
+// DYS floats (f32), or split when staged into a hi and a lo bf16 image of DYB-byte rows (BF3: an 80-byte row makes a 16-lane group's
+// ds_read_b128 cover all 64 banks), shared by the four waves.
+// Thread map.  VEC (every address 16-B aligned — checked on the host): 8 lanes per row; piece i = samples col .. col + 3 of row
+// (tid>>3) + 32i: DYV/4 16-byte loads per thread instead of DYV dword ones.  Dword: a half-wave per row; piece i = sample col of
+// row (tid>>5) + 8i = 2·wave + half + 8i (msplit is even: a wave's two rows share a side).
+template <int MBW, int TW, bool VEC, bool BF3>
+struct WgDyStage {
+  static constexpr int DYS = TW + 1;                     // odd row stride: lanes ↔ rows never share a bank
+  static constexpr int DYB = 2 * TW + 16;
+  static constexpr int DYV = MBW * 32 / 8;               // floats per thread per tile
+  float st[DYV];
+
+  static __device__ __forceinline__ int col(int tid) { return VEC ? (tid & 7) * 4 : tid & 31; }
+  static __device__ __forceinline__ int row(int tid, int i) { return VEC ? (tid >> 3) + 32 * i : (tid >> 5) + 8 * i; }
+  static __device__ __forceinline__ int row_u(int tid, int i) { return 2 * wg_wave_u(tid) + 8 * i; }                  // dword
+
+  __device__ __forceinline__ void fetch(const WgradParams& p, int m0, int b, int tt0, int tid) {
+    const int L = p.L;
+    const bool t_ok = tt0 + col(tid) < L;
+    if constexpr (VEC) {
+#pragma unroll
+      for (int i = 0; i < DYV / 4; ++i) {
+        const int m = m0 + row(tid, i);
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (t_ok && m < p.M) {
+          const float* rp = (m < p.msplit) ? p.dy + ((long long)b * p.dy_bs + (long long)m * L)
+                                           : p.dy2 + ((long long)b * p.dy2_bs + (long long)(m - p.msplit) * L);
+          v = *reinterpret_cast<const float4*>(rp + tt0 + col(tid));
+        }
+        st[4 * i] = v.x; st[4 * i + 1] = v.y; st[4 * i + 2] = v.z; st[4 * i + 3] = v.w;
+      }
+    } else {
+      const int half = (tid >> 5) & 1, vlane = half * L + col(tid);
+#pragma unroll
+      for (int i = 0; i < DYV; ++i) {
+        const int m_even = m0 + row_u(tid, i);
+        const float* rp = (m_even < p.msplit)
+                              ? p.dy + ((long long)b * p.dy_bs + (long long)m_even * L + tt0)
+                              : p.dy2 + ((long long)b * p.dy2_bs + (long long)(m_even - p.msplit) * L + tt0);
+        st[i] = (t_ok && m_even + half < p.M) ? rp[vlane] : 0.f;
+      }
+    }
+  }
+
+  __device__ __forceinline__ void commit(float* dyt, int tid) const {
+    char* const dyh = reinterpret_cast<char*>(dyt);
+    char* const dyl = dyh + MBW * 32 * DYB;
+    if constexpr (VEC && BF3) {
+#pragma unroll
+      for (int i = 0; i < DYV / 4; ++i) {
+        unsigned h0, h1, l0, l1;
+        split_bf16_pair(st[4 * i], st[4 * i + 1], h0, l0);
+        split_bf16_pair(st[4 * i + 2], st[4 * i + 3], h1, l1);
+        const int off = row(tid, i) * DYB + col(tid) * 2;
+        *reinterpret_cast<uint2*>(dyh + off) = make_uint2(h0, h1);
+        *reinterpret_cast<uint2*>(dyl + off) = make_uint2(l0, l1);
+      }
+    } else if constexpr (VEC) {
+#pragma unroll
+      for (int i = 0; i < DYV / 4; ++i)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) dyt[row(tid, i) * DYS + col(tid) + k] = st[4 * i + k];
+    } else if constexpr (BF3) {
+#pragma unroll
+      for (int i = 0; i < DYV; ++i) {
+        unsigned hh, ll;
+        split_bf16_pair(st[i], 0.f, hh, ll);
+        const int off = row(tid, i) * DYB + col(tid) * 2;
+        *reinterpret_cast<unsigned short*>(dyh + off) = (unsigned short)hh;
+        *reinterpret_cast<unsigned short*>(dyl + off) = (unsigned short)ll;
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < DYV; ++i) dyt[row(tid, i) * DYS + col(tid)] = st[i];
+    }
+  }
+};
+
+// One staged x window: source rows (channel 0 of batch element 0) and batch stride, channel count, first time sample relative to
+// the tile, columns, and (VEC 2) the samples by which it starts past a 16-byte boundary.
+struct WgWindow {
+  const float* src;
+  long long bs;
+  int cnt, shift, width, sub;
+};
+
+// The x window of one chunk, raw fp32 rows of ldw floats at reg.  Thread map: piece i of thread tid starts at (row, col):
+//   WIDE, 16-byte:   [≤ 64 rows][≤ 128 columns] = 32 float4 per row: 8 pieces, row (tid>>5) + 8i, columns 4(tid&31) .. +3
+//   WIDE, dword:     32 pieces, row (tid>>6) + 4(i>>1) = wave + …, column lane + 64(i&1)
+//   narrow, 16-byte: one piece, row tid>>3, columns 4(tid&7) − sub .. +3: a tap shift that is not a multiple of 4 samples (VEC 2)
+//                    starts the row's eight float4 `sub` samples early, and lanes 0 .. sub−1 of the row fetch the tail columns
+//                    TW−sub .. TW−1 one by one
+//   narrow, dword:   4 pieces, row (tid>>5) + 8i = 2·wave + half + …, column l31
+// Narrow windows may be the product x0[i]·x0[i + x0_mul_off].
+template <int TW, bool WIDE, int VEC>
+struct WgXStage {
+  static constexpr int PIECES = WIDE ? (VEC ? 8 : 32) : (VEC ? 1 : 4);
+  static constexpr int XV = WIDE ? 32 : (VEC == 2 ? 5 : 4);   // floats per thread per window
+  float st[XV];
+
+  static __device__ __forceinline__ int row(int tid, int i) {
+    if constexpr (VEC != 0) return WIDE ? (tid >> 5) + 8 * i : tid >> 3;
+    else return WIDE ? (tid >> 6) + 4 * (i >> 1) : (tid >> 5) + 8 * i;
+  }
+  // dword: row = row_u (wave-uniform) + row_l
+  static __device__ __forceinline__ int row_u(int tid, int i) { return WIDE ? wg_wave_u(tid) + 4 * (i >> 1) : 2 * wg_wave_u(tid) + 8 * i; }
+  static __device__ __forceinline__ int row_l(int tid) { return WIDE ? 0 : (tid >> 5) & 1; }
+  static __device__ __forceinline__ int col(int tid, int i) {
+    if constexpr (VEC != 0) return WIDE ? (tid & 31) * 4 : (tid & 7) * 4;
+    else return WIDE ? (tid & 63) + 64 * (i & 1) : tid & 31;
+  }
+
+  __device__ __forceinline__ void fetch(const WgradParams& p, const WgWindow& w, int b, int tt0, int tid) {
+    const int L = p.L;
+    if constexpr (WIDE && VEC != 0) {
+      const int wc = col(tid, 0);
+      const int t = tt0 + w.shift + wc;
+      const bool ok = wc < w.width && t >= 0 && t < L;
+#pragma unroll
+      for (int i = 0; i < PIECES; ++i) {
+        const int cc = row(tid, i);
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (ok && cc < w.cnt) v = *reinterpret_cast<const float4*>(w.src + ((long long)b * w.bs + (long long)cc * L + t));
+        st[4 * i] = v.x; st[4 * i + 1] = v.y; st[4 * i + 2] = v.z; st[4 * i + 3] = v.w;
+      }
+    } else if constexpr (VEC != 0) {
+      const int vrow = row(tid, 0), vcol = col(tid, 0);
+      const int t = tt0 + w.shift - w.sub + vcol;
+      const float* rowp = w.src + ((long long)b * w.bs + (long long)vrow * L);
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (t >= 0 && t < L && vrow < w.cnt) {
+        v = *reinterpret_cast<const float4*>(rowp + t);
+        if (p.x0_mul_off) {
+          const float4 m = *reinterpret_cast<const float4*>(rowp + t + p.x0_mul_off);
+          // (the pairs spelt out: left to itself the compiler pairs (y, z) and (x, w) and waits for the load to move registers)
+          const f32x2 lo = f32x2{v.x, v.y} * f32x2{m.x, m.y}, hi = f32x2{v.z, v.w} * f32x2{m.z, m.w};
+          v = make_float4(lo[0], lo[1], hi[0], hi[1]);
+        }
+      }
+      st[0] = v.x; st[1] = v.y; st[2] = v.z; st[3] = v.w;
+      if constexpr (VEC == 2) {
+        float xe = 0.f;
+        const int te = tt0 + w.shift + TW - w.sub + (tid & 7);
+        if ((tid & 7) < w.sub && te >= 0 && te < L && vrow < w.cnt) {
+          xe = rowp[te];
+          if (p.x0_mul_off) xe *= rowp[te + p.x0_mul_off];
+        }
+        st[4] = xe;
+      }
+    } else if constexpr (WIDE) {
+      const int tbase = tt0 + w.shift;
+#pragma unroll
+      for (int i = 0; i < PIECES; i += 2) {
+        const int cc = row_u(tid, i);
+        const float* rp = w.src + ((long long)b * w.bs + (long long)cc * L + tbase);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          const int j = col(tid, i + k), t = tbase + j;
+          st[i + k] = (cc < w.cnt && j < w.width && t >= 0 && t < L) ? rp[j] : 0.f;
+        }
+      }
+    } else {
+      const int tbase = tt0 + w.shift, t = tbase + col(tid, 0);
+      const bool ok = t >= 0 && t < L;
+      const int vlane = row_l(tid) * L + col(tid, 0);
+#pragma unroll
+      for (int i = 0; i < PIECES; ++i) {
+        const int cc_even = row_u(tid, i);
+        const float* rp = w.src + ((long long)b * w.bs + (long long)cc_even * L + tbase);
+        float xv = 0.f;
+        if (ok && cc_even + row_l(tid) < w.cnt) {
+          xv = rp[vlane];
+          if (p.x0_mul_off) xv *= rp[vlane + p.x0_mul_off];
+        }
+        st[i] = xv;
+      }
+    }
+  }
+
+  __device__ __forceinline__ void commit(float* reg, const WgWindow& w, int chunk_cap, int ldw, int tid) const {
+    if constexpr (WIDE && VEC != 0) {
+#pragma unroll
+      for (int i = 0; i < PIECES; ++i) {
+        const int cc = row(tid, i), wc = col(tid, i);
+        if (cc < chunk_cap && wc < w.width) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) reg[cc * ldw + wc + k] = st[4 * i + k];
+        }
+      }
+    } else if constexpr (VEC != 0) {
+      const int vrow = row(tid, 0), c0 = col(tid, 0) - w.sub;
+      if (vrow < chunk_cap) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (c0 + k >= 0) reg[vrow * ldw + c0 + k] = st[k];
+        if constexpr (VEC == 2)
+          if ((tid & 7) < w.sub) reg[vrow * ldw + TW - w.sub + (tid & 7)] = st[4];
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < PIECES; ++i) {
+        const int cc = row(tid, i), j = col(tid, i);
+        if (cc < chunk_cap && (!WIDE || j < w.width)) reg[cc * ldw + j] = st[i];
+      }
+    }
+  }
+};
+
+// One staged (b,t) tile in split-bf16.  Wave w multiplies item w: rows = its 32 packed K-rows (the lane's row of the x windows
+// starts at lds + roff), columns = every LIVE output block of the dy images.  The A fragment — 8 consecutive raw fp32 samples at
+// any tap offset, eight ds_read_b32 — is split into hi / lo once, by the only wave that uses it.  nvalid < TW (uniform): the x
+// operand goes through a mask on tau, see the tile loop.
+template <int CB, int TW, int DYB>
+__device__ __forceinline__ void wg_multiply_bf3(f32x16 (&acc)[WG_ITEMS][CB], const float* lds, int roff, const char* dyh, const char* dyl,
+                                                int nblk_live, int nvalid, int half, int l31) {
+#pragma unroll
+  for (int ks = 0; ks < TW / 16; ++ks) {
+    const float* ap = lds + roff + ks * 16 + 8 * half;
+    bf16x8 ah, al;
+    split_bf16x8(*reinterpret_cast<const float(*)[8]>(ap), ah, al);   // (the 8 floats in place: a local copy changes five instances' schedule)
+    if (nvalid < TW) {                                 // uniform: keep the first n of this lane's 8 samples, clear the bits of the rest
+      const int n = min(max(nvalid - (ks * 16 + 8 * half), 0), 8);
+      u32x4 m;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) m[q] = n >= 2 * q + 2 ? 0xFFFFFFFFu : (n == 2 * q + 1 ? 0x0000FFFFu : 0u);
+      ah = __builtin_bit_cast(bf16x8, __builtin_bit_cast(u32x4, ah) & m);
+      al = __builtin_bit_cast(bf16x8, __builtin_bit_cast(u32x4, al) & m);
+    }
+    const int boff = l31 * DYB + (ks * 16 + 8 * half) * 2;
+#pragma unroll
+    for (int i = 0; i < WG_ITEMS; ++i)
+#pragma unroll
+      for (int cb = 0; cb < CB; ++cb) {
+        const int blk = i * CB + cb;
+        if constexpr (CB == 1)                        // (the 8-block form measured 10-50 % slower with this test in its loop)
+          if (blk >= nblk_live) continue;            // output-channel blocks beyond M (M = 25: three of four) hold zeros
+        const bf16x8 bh = *reinterpret_cast<const bf16x8*>(dyh + blk * 32 * DYB + boff);
+        const bf16x8 bl = *reinterpret_cast<const bf16x8*>(dyl + blk * 32 * DYB + boff);
+        mfma_bf3(acc[i][cb], ah, al, bh, bl);
+      }
+  }
+}
+
+// One staged tile in f32: every wave multiplies the rows of all items (lds + rowoff[i]) against its own CB output blocks (bbase).
+// Straight-line k-steps: padding items multiply the zero row instead of branching around their MFMAs (all workgroups of a launch
+// are co-resident, so the launch lasts as long as a full workgroup either way).
+template <int CB, int TW, int DYS>
+__device__ __forceinline__ void wg_multiply_f32(f32x16 (&acc)[WG_ITEMS][CB], const float* lds, const int (&rowoff)[WG_ITEMS],
+                                                const float* bbase, int nvalid, int half) {
+  const bool ragged = nvalid < TW;
+#pragma unroll 2
+  for (int tau = 0; tau < TW; tau += 2) {
+    float av[WG_ITEMS], bv[CB];
+#pragma unroll
+    for (int i = 0; i < WG_ITEMS; ++i) {
+      av[i] = lds[rowoff[i] + tau + half];
+      if (ragged && tau + half >= nvalid) av[i] = 0.f;
+    }
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb) bv[cb] = bbase[cb * 32 * DYS + tau];
+#pragma unroll
+    for (int i = 0; i < WG_ITEMS; ++i)
+#pragma unroll
+      for (int cb = 0; cb < CB; ++cb)
+        acc[i][cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[cb], acc[i][cb], 0, 0, 0);
+  }
+}
+
+// The record rows of one accumulator tile: register r of a lane holds packed K-row rb·32 + (r&3) + 8(r>>2) + 4·half of chunk q in
+// M-group g = (tap, channel) → put(r, dst), dst the lane's float of output-channel block 0 in that row's record (block k: + 64k),
+// in this K slice's slab when there are slabs.
+template <int MBW, class Put>
+__device__ __forceinline__ void wg_record_rows(const WgradParams& p, const PlanView& pv, int g, int q, int rb, int half, int l31, Put&& put) {
+  const int32_t* e = pv.mg + 4 * (g * pv.n_chunks + q);
+  const int c_pad = (pv.chunk[4 * q + 2] + 1) & ~1;
+  const int nrows = (e[1] - e[0]) * c_pad;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int row = rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+    if (row >= nrows) continue;
+    const int tapi = row / c_pad, c = row - tapi * c_pad;
+    const long long rec = (long long)e[2] + tapi * (c_pad / 2) + (c >> 1);
+    put(r, p.da + (long long)blockIdx.x * p.slab_floats + rec * MBW * 64 + (c & 1) * 32 + l31);
+  }
+}
+// a plain store into the slab, or an fp32 atomic into the one gradient
+__device__ __forceinline__ void wg_put(const WgradParams& p, float* dst, float v) {
+  if (p.slab_floats) *dst = v; else atomicAdd(dst, v);
+}
+
 // CB: output-channel blocks per wave (M tile = 4*CB*32).  WIDE=false: every chunk is a single tap of ≤ 32
 // channels (window = TW columns, up to WG_ITEMS windows per workgroup); WIDE=true: one windowed chunk of
 // ≤ 64 channels and ≤ 128 columns (omni-scale layers, all items of a workgroup share it).
@@ -1297,20 +1493,15 @@ struct WgradParams {
 //
 // BF3: the products run on the bf16 matrix cores with split operands (see conv_gemm_bf3_kernel): time is cut into
 // 16-deep k-steps; wave w owns item w (its 32 packed K-rows are the MFMA rows) against ALL 4·CB output-channel
-// blocks, so the A fragment — 8 consecutive raw fp32 samples of the staged x window at any tap offset, eight
-// ds_read_b32 — is split into hi / lo once, by the only wave that uses it; dy is split when it is staged, into two
-// bf16 images [M rows][32 samples] (80-byte rows: a 16-lane group's ds_read_b128 covers all 64 banks) shared by the
-// four waves.
+// blocks (wg_multiply_bf3); dy is split when it is staged (WgDyStage).
 template <int CB, int TW, bool WIDE, int VEC, bool BF3>
 __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradParams p, const int32_t* __restrict__ plan) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   static_assert(TW == 32, "staging maps one half-wave to one 32-sample row");
   constexpr int MBW = 4 * CB;
-  constexpr int DYS = TW + 1;   // odd row stride: lanes ↔ rows never share a bank
-  constexpr int DYB = 2 * TW + 16;                       // BF3: bytes per row of a dy image
-  constexpr int DYV = MBW * 32 / 8;                      // dy floats per thread per tile
   constexpr int NREG = WIDE ? 1 : WG_ITEMS;              // staged windows per workgroup
-  constexpr int XV = WIDE ? 32 : (VEC == 2 ? 5 : 4);     // x floats per thread per window (VEC 2: one float4 + the sub-shift tail)
+  using DyStage = WgDyStage<MBW, TW, VEC != 0, BF3>;
+  using XStage = WgXStage<TW, WIDE, VEC>;
   const PlanView pv = plan_view(plan);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int half = lane >> 5, l31 = lane & 31;
@@ -1318,9 +1509,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradParams p, const
 
   float* xreg = lds;                                     // n_regions windows of region_floats
   float* zrow = lds + p.n_regions * p.region_floats;     // TW+2 zeros
-  float* dyt = zrow + (TW + 2 + 3) / 4 * 4;              // [MBW*32][DYS]   (BF3: hi image, then lo image, [MBW*32][DYB bytes])
-  char* const dyh = reinterpret_cast<char*>(dyt);
-  char* const dyl = dyh + MBW * 32 * DYB;
+  float* dyt = zrow + (TW + 2 + 3) / 4 * 4;              // the dy tile (WgDyStage)
 
   // decode this workgroup's items (all share one M-group)
   int it_q[WG_ITEMS], it_rb[WG_ITEMS], it_region[WG_ITEMS];
@@ -1336,12 +1525,9 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradParams p, const
   if (g < 0) return;
   const int m0 = g * MBW * 32;
 
-  // per staged window: source rows, channel count, first time sample relative to the tile
-  const float* reg_src[NREG];
-  int reg_cnt[NREG], reg_shift[NREG], reg_width[NREG], reg_sub[NREG];
-  long long reg_bs[NREG];
+  WgWindow win[NREG];
 #pragma unroll
-  for (int r = 0; r < NREG; ++r) { reg_src[r] = nullptr; reg_cnt[r] = 0; reg_shift[r] = 0; reg_width[r] = 0; reg_bs[r] = 0; reg_sub[r] = 0; }
+  for (int r = 0; r < NREG; ++r) win[r] = WgWindow{nullptr, 0, 0, 0, 0, 0};
 #pragma unroll
   for (int i = 0; i < WG_ITEMS; ++i) {
     if (i >= nit || (i > 0 && it_region[i] == it_region[i - 1])) continue;
@@ -1350,12 +1536,12 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradParams p, const
 #pragma unroll
     for (int r = 0; r < NREG; ++r) {
       if (r == it_region[i]) {
-        reg_src[r] = p.x[c[0]] + (long long)c[1] * L;
-        reg_bs[r] = p.x_bs[c[0]];
-        reg_cnt[r] = c[2];
-        reg_shift[r] = e[0] * dil - pv.pad_left;
-        reg_sub[r] = VEC == 2 ? (reg_shift[r] & 3) : 0;  // samples by which the window starts past a 16-byte boundary
-        reg_width[r] = (e[1] - 1 - e[0]) * dil + TW;
+        win[r].src = p.x[c[0]] + (long long)c[1] * L;
+        win[r].bs = p.x_bs[c[0]];
+        win[r].cnt = c[2];
+        win[r].shift = e[0] * dil - pv.pad_left;
+        win[r].sub = VEC == 2 ? (win[r].shift & 3) : 0;
+        win[r].width = (e[1] - 1 - e[0]) * dil + TW;
       }
     }
   }
@@ -1378,210 +1564,34 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradParams p, const
     }
   }
   for (int j = tid; j < TW + 2; j += 256) zrow[j] = 0.f;
+  int my_rowoff = rowoff[0];                             // BF3: of this wave's item
+#pragma unroll
+  for (int i = 1; i < WG_ITEMS; ++i) my_rowoff = wave == i ? rowoff[i] : my_rowoff;
 
   f32x16 acc[WG_ITEMS][CB];
-#pragma unroll
-  for (int i = 0; i < WG_ITEMS; ++i)
-#pragma unroll
-    for (int cb = 0; cb < CB; ++cb)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][cb][r] = 0.f;
+  zero_acc(acc);
 
   const int n_tiles = p.B * p.tiles_per_seq;
   const int tile_begin = (int)(((long long)blockIdx.x * n_tiles) / p.ksplit);
   const int tile_end = (int)(((long long)(blockIdx.x + 1) * n_tiles) / p.ksplit);
 
-  float dy_st[DYV];
-  float x_st[NREG][XV];
-  // Addressing: the row part of every address is wave-uniform (SGPR arithmetic); one per-lane offset
-  // (half·L + l31, or lane) is the only address VGPR, so nothing large is hoisted out of the tile loop.
-  const int wave_s = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int vlane = half * L + l31;
-  // VEC (narrow windows, every address 16-B aligned — checked on the host): 16-byte loads, 8 lanes per 32-sample
-  // row.  dy: row = (tid>>3) + 32*i; windows: row = tid>>3.  12 load instructions per thread per tile instead of 48.
-  const int vrow = tid >> 3, vcol = (tid & 7) * 4;
-  int fetched_tt0 = 0;                                   // first sample of the tile held in dy_st / x_st
+  DyStage dys;
+  XStage xs[NREG];
+  int fetched_tt0 = 0;                                   // first sample of the tile held in dys / xs
   auto fetch = [&](int tile) {
     const int b = tile / p.tiles_per_seq;
     const int tt0 = (tile - b * p.tiles_per_seq) * TW;
     fetched_tt0 = tt0;
-    if (VEC) {
-      const bool tv_ok = tt0 + vcol < L;
+    dys.fetch(p, m0, b, tt0, tid);
 #pragma unroll
-      for (int i = 0; i < DYV / 4; ++i) {
-        const int m = m0 + vrow + 32 * i;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (tv_ok && m < p.M) {
-          const float* rp = (m < p.msplit) ? p.dy + ((long long)b * p.dy_bs + (long long)m * L)
-                                           : p.dy2 + ((long long)b * p.dy2_bs + (long long)(m - p.msplit) * L);
-          v = *reinterpret_cast<const float4*>(rp + tt0 + vcol);
-        }
-        dy_st[4 * i] = v.x; dy_st[4 * i + 1] = v.y; dy_st[4 * i + 2] = v.z; dy_st[4 * i + 3] = v.w;
-      }
-#pragma unroll
-      for (int r = 0; r < NREG; ++r) {
-        if (reg_src[r] == nullptr) continue;
-        if (WIDE) {
-          // window [<=64 rows][<=128 columns] = 32 float4 per row: row = (tid>>5) + 8*i, column 4*(tid&31)
-          const int wc = (tid & 31) * 4;
-          const int t = tt0 + reg_shift[r] + wc;
-          const bool ok = wc < reg_width[r] && t >= 0 && t < L;
-#pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            const int cc = (tid >> 5) + 8 * i;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (ok && cc < reg_cnt[r])
-              v = *reinterpret_cast<const float4*>(reg_src[r] + ((long long)b * reg_bs[r] + (long long)cc * L + t));
-            x_st[r][4 * i] = v.x; x_st[r][4 * i + 1] = v.y; x_st[r][4 * i + 2] = v.z; x_st[r][4 * i + 3] = v.w;
-          }
-        } else {
-          // a tap shift that is not a multiple of 4 samples: the row's eight float4 start `sub` samples early (window
-          // columns vcol-sub .. vcol-sub+3) and lanes 0..sub-1 of the row fetch the tail columns 32-sub .. 31 one by one
-          const int sub = reg_sub[r];
-          const int t = tt0 + reg_shift[r] - sub + vcol;
-          const float* rowp = reg_src[r] + ((long long)b * reg_bs[r] + (long long)vrow * L);
-          float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (t >= 0 && t < L && vrow < reg_cnt[r]) {
-            v = *reinterpret_cast<const float4*>(rowp + t);
-            if (p.x0_mul_off) {
-              const float4 w = *reinterpret_cast<const float4*>(rowp + t + p.x0_mul_off);
-              v.x *= w.x; v.y *= w.y; v.z *= w.z; v.w *= w.w;
-            }
-          }
-          x_st[r][0] = v.x; x_st[r][1] = v.y; x_st[r][2] = v.z; x_st[r][3] = v.w;
-          if constexpr (VEC == 2) {
-            float xe = 0.f;
-            const int te = tt0 + reg_shift[r] + TW - sub + (tid & 7);
-            if ((tid & 7) < sub && te >= 0 && te < L && vrow < reg_cnt[r]) {
-              xe = rowp[te];
-              if (p.x0_mul_off) xe *= rowp[te + p.x0_mul_off];
-            }
-            x_st[r][4] = xe;
-          }
-        }
-      }
-      return;
-    }
-    const bool t_ok = tt0 + l31 < L;
-    // dy tile: one half-wave per 32-sample row; rows m_even + half (msplit is even: a wave's two rows share a side)
-#pragma unroll
-    for (int i = 0; i < DYV; ++i) {
-      const int m_even = m0 + wave_s * 2 + 8 * i;
-      const float* rp = (m_even < p.msplit)
-                            ? p.dy + ((long long)b * p.dy_bs + (long long)m_even * L + tt0)
-                            : p.dy2 + ((long long)b * p.dy2_bs + (long long)(m_even - p.msplit) * L + tt0);
-      dy_st[i] = (t_ok && m_even + half < p.M) ? rp[vlane] : 0.f;
-    }
-#pragma unroll
-    for (int r = 0; r < NREG; ++r) {
-      if (reg_src[r] == nullptr) continue;
-      const int tbase = tt0 + reg_shift[r];
-      if (WIDE) {
-        // rows cc = wave + 4*i (i < 16), columns lane and lane+64
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int cc = wave_s + 4 * i;
-          const float* rp = reg_src[r] + ((long long)b * reg_bs[r] + (long long)cc * L + tbase);
-#pragma unroll
-          for (int k = 0; k < 2; ++k) {
-            const int j = lane + 64 * k, t = tbase + j;
-            x_st[r][2 * i + k] = (cc < reg_cnt[r] && j < reg_width[r] && t >= 0 && t < L) ? rp[j] : 0.f;
-          }
-        }
-      } else {
-        // rows cc = wave*2 + half + 8*i (i < 4), column l31
-        const int t = tbase + l31;
-        const bool ok = t >= 0 && t < L;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int cc_even = wave_s * 2 + 8 * i;
-          const float* rp = reg_src[r] + ((long long)b * reg_bs[r] + (long long)cc_even * L + tbase);
-          float xv = 0.f;
-          if (ok && cc_even + half < reg_cnt[r]) {
-            xv = rp[vlane];
-            if (p.x0_mul_off) xv *= rp[vlane + p.x0_mul_off];
-          }
-          x_st[r][i] = xv;
-        }
-      }
-    }
+    for (int r = 0; r < NREG; ++r)
+      if (win[r].src != nullptr) xs[r].fetch(p, win[r], b, tt0, tid);
   };
   auto commit = [&]() {
-    if (VEC) {
-      if (BF3) {
+    dys.commit(dyt, tid);
 #pragma unroll
-        for (int i = 0; i < DYV / 4; ++i) {
-          unsigned h0, h1, l0, l1;
-          split_bf16_pair(dy_st[4 * i], dy_st[4 * i + 1], h0, l0);
-          split_bf16_pair(dy_st[4 * i + 2], dy_st[4 * i + 3], h1, l1);
-          const int off = (vrow + 32 * i) * DYB + vcol * 2;
-          *reinterpret_cast<uint2*>(dyh + off) = make_uint2(h0, h1);
-          *reinterpret_cast<uint2*>(dyl + off) = make_uint2(l0, l1);
-        }
-      } else {
-#pragma unroll
-      for (int i = 0; i < DYV / 4; ++i)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) dyt[(vrow + 32 * i) * DYS + vcol + k] = dy_st[4 * i + k];
-      }
-#pragma unroll
-      for (int r = 0; r < NREG; ++r) {
-        if (reg_src[r] == nullptr) continue;
-        float* reg = xreg + r * p.region_floats;
-        if (WIDE) {
-          const int wc = (tid & 31) * 4;
-#pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            const int cc = (tid >> 5) + 8 * i;
-            if (cc < pv.chunk_cap && wc < reg_width[r]) {
-#pragma unroll
-              for (int k = 0; k < 4; ++k) reg[cc * ldw + wc + k] = x_st[r][4 * i + k];
-            }
-          }
-        } else if (vrow < pv.chunk_cap) {
-          const int sub = reg_sub[r], c0 = vcol - sub;
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-            if (c0 + k >= 0) reg[vrow * ldw + c0 + k] = x_st[r][k];
-          if constexpr (VEC == 2)
-            if ((tid & 7) < sub) reg[vrow * ldw + TW - sub + (tid & 7)] = x_st[r][4];
-        }
-      }
-      return;
-    }
-    if (BF3) {
-#pragma unroll
-      for (int i = 0; i < DYV; ++i) {
-        unsigned hh, ll;
-        split_bf16_pair(dy_st[i], 0.f, hh, ll);
-        const int off = (wave * 2 + half + 8 * i) * DYB + l31 * 2;
-        *reinterpret_cast<unsigned short*>(dyh + off) = (unsigned short)hh;
-        *reinterpret_cast<unsigned short*>(dyl + off) = (unsigned short)ll;
-      }
-    } else {
-#pragma unroll
-    for (int i = 0; i < DYV; ++i) dyt[(wave * 2 + half + 8 * i) * DYS + l31] = dy_st[i];
-    }
-#pragma unroll
-    for (int r = 0; r < NREG; ++r) {
-      if (reg_src[r] == nullptr) continue;
-      float* reg = xreg + r * p.region_floats;
-      if (WIDE) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-#pragma unroll
-          for (int k = 0; k < 2; ++k) {
-            const int cc = wave + 4 * i, j = lane + 64 * k;
-            if (cc < pv.chunk_cap && j < reg_width[r]) reg[cc * ldw + j] = x_st[r][2 * i + k];
-          }
-      } else {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int cc = wave * 2 + half + 8 * i;
-          if (cc < pv.chunk_cap) reg[cc * ldw + l31] = x_st[r][i];
-        }
-      }
-    }
+    for (int r = 0; r < NREG; ++r)
+      if (win[r].src != nullptr) xs[r].commit(xreg + r * p.region_floats, win[r], pv.chunk_cap, ldw, tid);
   };
 
   if (tile_begin < tile_end) fetch(tile_begin);
@@ -1595,107 +1605,37 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_kernel(WgradParams p, const
     const int nvalid = L - fetched_tt0;
     if (tile + 1 < tile_end) fetch(tile + 1);
 
-    if (BF3) {
-      // wave w multiplies item w: rows = its 32 packed K-rows (lane's row: rowoff_w), columns = every LIVE output block
-      const int nblk_live = min(MBW, (p.M - m0 + 31) / 32);
-      int roff = rowoff[0];
-#pragma unroll
-      for (int i = 1; i < WG_ITEMS; ++i) roff = wave == i ? rowoff[i] : roff;
-#pragma unroll
-      for (int ks = 0; ks < TW / 16; ++ks) {
-        const float* ap = lds + roff + ks * 16 + 8 * half;
-        bf16x8 ah, al;
-        split_bf16x8(*reinterpret_cast<const float(*)[8]>(ap), ah, al);   // (the 8 floats in place: a local copy changes five instances' schedule)
-        if (nvalid < TW) {                                 // uniform: keep the first n of this lane's 8 samples, clear the bits of the rest
-          const int n = min(max(nvalid - (ks * 16 + 8 * half), 0), 8);
-          u32x4 m;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) m[q] = n >= 2 * q + 2 ? 0xFFFFFFFFu : (n == 2 * q + 1 ? 0x0000FFFFu : 0u);
-          ah = __builtin_bit_cast(bf16x8, __builtin_bit_cast(u32x4, ah) & m);
-          al = __builtin_bit_cast(bf16x8, __builtin_bit_cast(u32x4, al) & m);
-        }
-        const int boff = l31 * DYB + (ks * 16 + 8 * half) * 2;
-#pragma unroll
-        for (int i = 0; i < WG_ITEMS; ++i)
-#pragma unroll
-          for (int cb = 0; cb < CB; ++cb) {
-            const int blk = i * CB + cb;
-            if constexpr (CB == 1)                        // (the 8-block form measured 10-50 % slower with this test in its loop)
-              if (blk >= nblk_live) continue;            // output-channel blocks beyond M (M = 25: three of four) hold zeros
-            const bf16x8 bh = *reinterpret_cast<const bf16x8*>(dyh + blk * 32 * DYB + boff);
-            const bf16x8 bl = *reinterpret_cast<const bf16x8*>(dyl + blk * 32 * DYB + boff);
-            mfma_bf3(acc[i][cb], ah, al, bh, bl);
-          }
-      }
-      continue;
-    }
-    const float* bbase = dyt + (wave * CB * 32 + l31) * DYS + half;
-    // straight-line k-steps: padding items multiply the zero row instead of branching around their MFMAs (all
-    // workgroups of a launch are co-resident, so the launch lasts as long as a full workgroup either way)
-    const bool ragged = nvalid < TW;
-#pragma unroll 2
-    for (int tau = 0; tau < TW; tau += 2) {
-      float av[WG_ITEMS], bv[CB];
-#pragma unroll
-      for (int i = 0; i < WG_ITEMS; ++i) {
-        av[i] = lds[rowoff[i] + tau + half];
-        if (ragged && tau + half >= nvalid) av[i] = 0.f;
-      }
-#pragma unroll
-      for (int cb = 0; cb < CB; ++cb) bv[cb] = bbase[cb * 32 * DYS + tau];
-#pragma unroll
-      for (int i = 0; i < WG_ITEMS; ++i)
-#pragma unroll
-        for (int cb = 0; cb < CB; ++cb)
-          acc[i][cb] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[cb], acc[i][cb], 0, 0, 0);
+    if constexpr (BF3) {
+      const char* const dyh = reinterpret_cast<const char*>(dyt);
+      wg_multiply_bf3<CB, TW, DyStage::DYB>(acc, lds, my_rowoff, dyh, dyh + MBW * 32 * DyStage::DYB, min(MBW, (p.M - m0 + 31) / 32), nvalid,
+                                            half, l31);
+    } else {
+      wg_multiply_f32<CB, TW, DyStage::DYS>(acc, lds, rowoff, dyt + (wave * CB * 32 + l31) * DyStage::DYS + half, nvalid, half);
     }
   }
 
-  if (BF3) {
-    // this wave's item: acc[i][cb] is output-channel block i*CB+cb of item `wave`
+  // acc rows = packed K-rows (tap, channel), columns = output channel (lane) → record layout
+  if constexpr (BF3) {
+    // acc[i][cb] is output-channel block i*CB+cb of this wave's item
     int my_q = it_q[0], my_rb = it_rb[0];
 #pragma unroll
     for (int i = 1; i < WG_ITEMS; ++i) { my_q = wave == i ? it_q[i] : my_q; my_rb = wave == i ? it_rb[i] : my_rb; }
     if (wave >= nit || my_q < 0) return;
-    const int32_t* e = pv.mg + 4 * (g * pv.n_chunks + my_q);
-    const int c_pad = (pv.chunk[4 * my_q + 2] + 1) & ~1;
-    const int nrows = (e[1] - e[0]) * c_pad;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = my_rb * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-      if (row >= nrows) continue;
-      const int tapi = row / c_pad, c = row - tapi * c_pad;
-      const long long rec = (long long)e[2] + tapi * (c_pad / 2) + (c >> 1);
+    wg_record_rows<MBW>(p, pv, g, my_q, my_rb, half, l31, [&](int r, float* dst) {
 #pragma unroll
       for (int i = 0; i < WG_ITEMS; ++i)
 #pragma unroll
-        for (int cb = 0; cb < CB; ++cb) {
-          float* dst = p.da + (long long)blockIdx.x * p.slab_floats + (rec * MBW + i * CB + cb) * 64 + (c & 1) * 32 + l31;
-          if (p.slab_floats) *dst = acc[i][cb][r]; else atomicAdd(dst, acc[i][cb][r]);
-        }
-    }
-    return;
-  }
-  // epilogue: acc rows = packed K-rows (tap, channel), cols = output channel m (lane) → record layout
+        for (int cb = 0; cb < CB; ++cb) wg_put(p, dst + (i * CB + cb) * 64, acc[i][cb][r]);
+    });
+  } else {
+    // acc[i][cb] is output-channel block wave*CB+cb of item i
 #pragma unroll
-  for (int i = 0; i < WG_ITEMS; ++i) {
-    if (i >= nit) continue;
-    const int q = it_q[i];
-    const int32_t* e = pv.mg + 4 * (g * pv.n_chunks + q);
-    const int c_pad = (pv.chunk[4 * q + 2] + 1) & ~1;
-    const int nrows = (e[1] - e[0]) * c_pad;
+    for (int i = 0; i < WG_ITEMS; ++i) {
+      if (i >= nit) continue;
+      wg_record_rows<MBW>(p, pv, g, it_q[i], it_rb[i], half, l31, [&](int r, float* dst) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = it_rb[i] * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-      if (row >= nrows) continue;
-      const int tapi = row / c_pad, c = row - tapi * c_pad;
-      const long long rec = (long long)e[2] + tapi * (c_pad / 2) + (c >> 1);
-#pragma unroll
-      for (int cb = 0; cb < CB; ++cb) {
-        const int mbw = wave * CB + cb;
-        float* dst = p.da + (long long)blockIdx.x * p.slab_floats + (rec * MBW + mbw) * 64 + (c & 1) * 32 + l31;
-        if (p.slab_floats) *dst = acc[i][cb][r]; else atomicAdd(dst, acc[i][cb][r]);
-      }
+        for (int cb = 0; cb < CB; ++cb) wg_put(p, dst + (wave * CB + cb) * 64, acc[i][cb][r]);
+      });
     }
   }
 }

@@ -1,5 +1,5 @@
-// Device primitives shared by the split-bf16 kernels of libfst_hip.so (gfx950 only): the operand split every parity
-// tolerance of the project rests on, the operand-staging pieces around it, and the diagnostic cycle stamps.
+// Device primitives shared by the matrix-core kernels of libfst_hip.so (gfx950 only): the operand split every parity
+// tolerance of the project rests on, the operand-staging pieces around it, accumulator zeroing, and the diagnostic cycle stamps.
 #pragma once
 #include "fst_common.h"
 
@@ -39,6 +39,22 @@ __device__ __forceinline__ void mfma_bf3(f32x16& acc, bf16x8 ah, bf16x8 al, bf16
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
+}
+
+// Clear the accumulators of one 32x32 MFMA tile, of a row of tiles, of a grid of tiles.
+__device__ __forceinline__ void zero_acc(f32x16& acc) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+}
+template <int N>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[N]) {
+#pragma unroll
+  for (int j = 0; j < N; ++j) zero_acc(acc[j]);
+}
+template <int M, int N>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[M][N]) {
+#pragma unroll
+  for (int i = 0; i < M; ++i) zero_acc(acc[i]);
 }
 
 // The (hi, lo) A fragments of row block mb of a packed weight stage at base: per block 1 KiB hi then 1 KiB lo, 16 bytes per lane.

@@ -18,8 +18,9 @@
 // order (+ bias, activation) — deterministic, no atomics, no zero fill.
 //
 // The same contract in EXACT fp32 (fst_gemm_f32, gemm_f32_kernel): RandomLayer's feature-side product and its data gradient under
-// FST_MATH=f32 (C_DAN.py:20-25 of the reference), the arithmetic the reference itself runs.  Same tiles, same fetch, same geometry,
-// same K split and slab reduction; the operands go into LDS unsplit (rows of 32 floats at a 144-byte pitch: the 16-byte staging
+// FST_MATH=f32 (C_DAN.py:20-25 of the reference), the arithmetic the reference itself runs.  Both kernels are gemm_tile, the one
+// tile frame (geometry, fetch, barriers, K split, store), over an arithmetic description (GemmBf3, GemmF32: LDS image, stage,
+// multiply); in fp32 the operands go into LDS unsplit (rows of 32 floats at a 144-byte pitch: the 16-byte staging
 // writes and the ds_read_b128 fragment reads are bank-conflict-free, 9 sixteen-byte slots per row being odd) and the product runs
 // on v_mfma_f32_32x32x2_f32, whose result is bit for bit a k-ordered fmaf chain per accumulator.  The chain order of one C element:
 //   * inside a 32-k stage starting at k0, lane half h holds k0 + 16h .. k0 + 16h + 15 (four ds_read_b128), and MFMA q = 0..15 of
@@ -33,7 +34,6 @@
 #include "fst_device.h"
 
 #define GM_BK 32
-#define GM_PITCH 80
 
 struct GemmParams {
   const float* A;
@@ -87,40 +87,117 @@ __device__ __forceinline__ void gm_fetch(float (&v)[ROWS / 8], const float* X, l
   }
 }
 
-template <int ROWS>
-__device__ __forceinline__ void gm_stage(const float (&v)[ROWS / 8], char* hi_img, char* lo_img, int trans, int tid) {
-  constexpr int KR = ROWS / 8;
-  if (!trans) {
-    const int kb = 8 * (tid & 7), r0 = tid >> 3;           // byte offset of k = 4(t&7) in a row of bf16
+// The two arithmetics of gemm_tile.  Each describes the LDS form of a fetched operand tile — IMAGES images of ROWS rows of 32 k at
+// PITCH bytes, one behind the other; HALF bytes from lane half 0's fragment to lane half 1's — with `stage` writing a tile
+// (gm_fetch's thread map) into it and `multiply` taking one 32-k stage out of it: a / b point at this lane's row of the first
+// image of the A / B tile.
+
+// split-bf16: a hi and a lo image, rows of 32 bf16; 16 ds_read_b128 per 24 MFMAs and no conversion in the multiply
+struct GemmBf3 {
+  static constexpr int PITCH = 80, IMAGES = 2, HALF = 16;
+
+  template <int ROWS>
+  static __device__ __forceinline__ void stage(const float (&v)[ROWS / 8], char* hi_img, int trans, int tid) {
+    constexpr int KR = ROWS / 8;
+    char* const lo_img = hi_img + ROWS * PITCH;
+    if (!trans) {
+      const int kb = 8 * (tid & 7), r0 = tid >> 3;           // byte offset of k = 4(t&7) in a row of bf16
 #pragma unroll
-    for (int j = 0; j < ROWS / 32; ++j) {
-      unsigned h0, l0, h1, l1;
-      split_bf16_pair(v[4 * j], v[4 * j + 1], h0, l0);
-      split_bf16_pair(v[4 * j + 2], v[4 * j + 3], h1, l1);
-      const int off = (r0 + 32 * j) * GM_PITCH + kb;
-      *reinterpret_cast<uint2*>(hi_img + off) = make_uint2(h0, h1);
-      *reinterpret_cast<uint2*>(lo_img + off) = make_uint2(l0, l1);
-    }
-  } else {
-    const int off = (tid % ROWS) * GM_PITCH + 2 * KR * (tid / ROWS);
+      for (int j = 0; j < ROWS / 32; ++j) {
+        unsigned h0, l0, h1, l1;
+        split_bf16_pair(v[4 * j], v[4 * j + 1], h0, l0);
+        split_bf16_pair(v[4 * j + 2], v[4 * j + 3], h1, l1);
+        const int off = (r0 + 32 * j) * PITCH + kb;
+        *reinterpret_cast<uint2*>(hi_img + off) = make_uint2(h0, h1);
+        *reinterpret_cast<uint2*>(lo_img + off) = make_uint2(l0, l1);
+      }
+    } else {
+      const int off = (tid % ROWS) * PITCH + 2 * KR * (tid / ROWS);
 #pragma unroll
-    for (int c = 0; c < KR / 8; ++c) {
-      bf16x8 h, l;
-      split_bf16x8(*reinterpret_cast<const float(*)[8]>(&v[8 * c]), h, l);   // (elements 8c..8c+7 in place: a local copy changes the schedule)
-      *reinterpret_cast<bf16x8*>(hi_img + off + 16 * c) = h;
-      *reinterpret_cast<bf16x8*>(lo_img + off + 16 * c) = l;
+      for (int c = 0; c < KR / 8; ++c) {
+        bf16x8 h, l;
+        split_bf16x8(*reinterpret_cast<const float(*)[8]>(&v[8 * c]), h, l);   // (elements 8c..8c+7 in place: a local copy changes the schedule)
+        *reinterpret_cast<bf16x8*>(hi_img + off + 16 * c) = h;
+        *reinterpret_cast<bf16x8*>(lo_img + off + 16 * c) = l;
+      }
     }
   }
-}
 
-template <int TM, int TN>
-__global__ __launch_bounds__(256, TM * TN == 4 ? 2 : 3) void gemm_bf3_kernel(GemmParams p) {
-  constexpr int BM = 64 * TM, BN = 64 * TN;
-  __shared__ __attribute__((aligned(16))) char lds[2 * (BM + BN) * GM_PITCH];
-  char* const a_hi = lds;
-  char* const a_lo = a_hi + BM * GM_PITCH;
-  char* const b_hi = a_lo + BM * GM_PITCH;
-  char* const b_lo = b_hi + BN * GM_PITCH;
+  template <int TM, int TN>
+  static __device__ __forceinline__ void multiply(f32x16 (&acc)[TM][TN], const char* a_hi, const char* b_hi) {
+    const char* const a_lo = a_hi + 64 * TM * PITCH;
+    const char* const b_lo = b_hi + 64 * TN * PITCH;
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      bf16x8 ah[TM], al[TM], bh[TN], bl[TN];
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {
+        ah[i] = *reinterpret_cast<const bf16x8*>(a_hi + i * 32 * PITCH + 32 * ks);
+        al[i] = *reinterpret_cast<const bf16x8*>(a_lo + i * 32 * PITCH + 32 * ks);
+      }
+#pragma unroll
+      for (int j = 0; j < TN; ++j) {
+        bh[j] = *reinterpret_cast<const bf16x8*>(b_hi + j * 32 * PITCH + 32 * ks);
+        bl[j] = *reinterpret_cast<const bf16x8*>(b_lo + j * 32 * PITCH + 32 * ks);
+      }
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) mfma_bf3(acc[i][j], ah[i], al[i], bh[j], bl[j]);
+    }
+  }
+};
+
+// exact fp32 (chain order: file header): one image, rows of 32 floats, k in storage order.  16 ds_read_b128 per 64 (TM = TN = 2)
+// MFMAs of 64 cycles each.
+struct GemmF32 {
+  static constexpr int PITCH = 144, IMAGES = 1, HALF = 64;
+
+  // Either layout hands a thread ROWS/32 pieces of four consecutive k: of rows (t>>3) + 32j at k = 4(t&7), or of row t % ROWS at
+  // k = KR·(t / ROWS) + 4j.
+  template <int ROWS>
+  static __device__ __forceinline__ void stage(const float (&v)[ROWS / 8], char* img, int trans, int tid) {
+    constexpr int KR = ROWS / 8;
+    const int off = trans ? (tid % ROWS) * PITCH + 4 * KR * (tid / ROWS) : (tid >> 3) * PITCH + 16 * (tid & 7);
+    const int step = trans ? 16 : 32 * PITCH;
+#pragma unroll
+    for (int j = 0; j < ROWS / 32; ++j)
+      *reinterpret_cast<float4*>(img + off + j * step) = make_float4(v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]);
+  }
+
+  template <int TM, int TN>
+  static __device__ __forceinline__ void multiply(f32x16 (&acc)[TM][TN], const char* a_img, const char* b_img) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      float4 a[TM], b[TN];
+#pragma unroll
+      for (int i = 0; i < TM; ++i) a[i] = *reinterpret_cast<const float4*>(a_img + i * 32 * PITCH + 16 * c);
+#pragma unroll
+      for (int j = 0; j < TN; ++j) b[j] = *reinterpret_cast<const float4*>(b_img + j * 32 * PITCH + 16 * c);
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int j = 0; j < TN; ++j) {
+            const float av = e == 0 ? a[i].x : e == 1 ? a[i].y : e == 2 ? a[i].z : a[i].w;
+            const float bv = e == 0 ? b[j].x : e == 1 ? b[j].y : e == 2 ? b[j].z : b[j].w;
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[i][j], 0, 0, 0);
+          }
+    }
+  }
+};
+
+// bytes of LDS of a 64·TM × 64·TN tile in arithmetic Arith
+template <class Arith, int TM, int TN>
+constexpr int gemm_lds_bytes() { return Arith::IMAGES * 64 * (TM + TN) * Arith::PITCH; }
+
+// The tile frame of both kernels: geometry, the fetch one stage ahead, the two barriers of a stage, the store.
+template <class Arith, int TM, int TN>
+__device__ __forceinline__ void gemm_tile(const GemmParams& p, char* lds) {
+  constexpr int BM = 64 * TM, BN = 64 * TN, PITCH = Arith::PITCH;
+  char* const a_img = lds;
+  char* const b_img = lds + Arith::IMAGES * BM * PITCH;
   const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), wm = wave >> 1, wn = wave & 1;
   const int tile_m = blockIdx.x / p.tiles_n, tile_n = blockIdx.x - tile_m * p.tiles_n;
@@ -130,46 +207,24 @@ __global__ __launch_bounds__(256, TM * TN == 4 ? 2 : 3) void gemm_bf3_kernel(Gem
   const int n_st = (k_end - k_begin + GM_BK - 1) / GM_BK;
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
   float va[BM / 8], vb[BN / 8];
   gm_fetch<BM>(va, p.A, p.lda, p.ta, p.vec_a, m0, p.M, k_begin, k_end, tid);
   gm_fetch<BN>(vb, p.B, p.ldb, p.tb, p.vec_b, n0, p.N, k_begin, k_end, tid);
-  const int a_off = (wm * 32 * TM + l31) * GM_PITCH + 16 * half;
-  const int b_off = (wn * 32 * TN + l31) * GM_PITCH + 16 * half;
+  const int a_off = (wm * 32 * TM + l31) * PITCH + Arith::HALF * half;
+  const int b_off = (wn * 32 * TN + l31) * PITCH + Arith::HALF * half;
   for (int s = 0; s < n_st; ++s) {
     __syncthreads();                                       // every wave is past its fragment reads of the previous stage
-    gm_stage<BM>(va, a_hi, a_lo, p.ta, tid);
-    gm_stage<BN>(vb, b_hi, b_lo, p.tb, tid);
+    Arith::template stage<BM>(va, a_img, p.ta, tid);
+    Arith::template stage<BN>(vb, b_img, p.tb, tid);
     __syncthreads();
     if (s + 1 < n_st) {                                    // the next stage's operands travel under this stage's MFMAs
       const int k0 = k_begin + (s + 1) * GM_BK;
       gm_fetch<BM>(va, p.A, p.lda, p.ta, p.vec_a, m0, p.M, k0, k_end, tid);
       gm_fetch<BN>(vb, p.B, p.ldb, p.tb, p.vec_b, n0, p.N, k0, k_end, tid);
     }
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 ah[TM], al[TM], bh[TN], bl[TN];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        ah[i] = *reinterpret_cast<const bf16x8*>(a_hi + a_off + i * 32 * GM_PITCH + 32 * ks);
-        al[i] = *reinterpret_cast<const bf16x8*>(a_lo + a_off + i * 32 * GM_PITCH + 32 * ks);
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        bh[j] = *reinterpret_cast<const bf16x8*>(b_hi + b_off + j * 32 * GM_PITCH + 32 * ks);
-        bl[j] = *reinterpret_cast<const bf16x8*>(b_lo + b_off + j * 32 * GM_PITCH + 32 * ks);
-      }
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) mfma_bf3(acc[i][j], ah[i], al[i], bh[j], bl[j]);
-    }
+    Arith::template multiply<TM, TN>(acc, a_img + a_off, b_img + b_off);
   }
 
   // accumulator layout: lane = column n, register r = row (r&3) + 8(r>>2) + 4·half — one store instruction = 2 rows × 128 bytes
@@ -196,100 +251,17 @@ __global__ __launch_bounds__(256, TM * TN == 4 ? 2 : 3) void gemm_bf3_kernel(Gem
   }
 }
 
-#define GF_PITCH 144
-
-// One fetched operand tile (gm_fetch's thread map) into its LDS image: rows of 32 floats, k in storage order.  Either layout hands a
-// thread ROWS/32 pieces of four consecutive k: of rows (t>>3) + 32j at k = 4(t&7), or of row t % ROWS at k = KR·(t / ROWS) + 4j.
-template <int ROWS>
-__device__ __forceinline__ void gf_stage(const float (&v)[ROWS / 8], char* img, int trans, int tid) {
-  constexpr int KR = ROWS / 8;
-  const int off = trans ? (tid % ROWS) * GF_PITCH + 4 * KR * (tid / ROWS) : (tid >> 3) * GF_PITCH + 16 * (tid & 7);
-  const int step = trans ? 16 : 32 * GF_PITCH;
-#pragma unroll
-  for (int j = 0; j < ROWS / 32; ++j)
-    *reinterpret_cast<float4*>(img + off + j * step) = make_float4(v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]);
+// The kernels own their LDS: 40 KiB (split-bf16) and 36 KiB (fp32) at 128 × 128.
+template <int TM, int TN>
+__global__ __launch_bounds__(256, TM * TN == 4 ? 2 : 3) void gemm_bf3_kernel(GemmParams p) {
+  __shared__ __attribute__((aligned(16))) char lds[gemm_lds_bytes<GemmBf3, TM, TN>()];
+  gemm_tile<GemmBf3, TM, TN>(p, lds);
 }
 
-// The exact-fp32 twin of gemm_bf3_kernel (chain order: file header).  16 ds_read_b128 per 64 (TM = TN = 2) MFMAs of 64 cycles each.
 template <int TM, int TN>
 __global__ __launch_bounds__(256, TM * TN == 4 ? 2 : 3) void gemm_f32_kernel(GemmParams p) {
-  constexpr int BM = 64 * TM, BN = 64 * TN;
-  __shared__ __attribute__((aligned(16))) char lds[(BM + BN) * GF_PITCH];
-  char* const a_img = lds;
-  char* const b_img = lds + BM * GF_PITCH;
-  const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), wm = wave >> 1, wn = wave & 1;
-  const int tile_m = blockIdx.x / p.tiles_n, tile_n = blockIdx.x - tile_m * p.tiles_n;
-  const int m0 = tile_m * BM, n0 = tile_n * BN;
-  const int k_begin = blockIdx.z * p.k_per_split;
-  const int k_end = min(p.K, k_begin + p.k_per_split);
-  const int n_st = (k_end - k_begin + GM_BK - 1) / GM_BK;
-
-  f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  float va[BM / 8], vb[BN / 8];
-  gm_fetch<BM>(va, p.A, p.lda, p.ta, p.vec_a, m0, p.M, k_begin, k_end, tid);
-  gm_fetch<BN>(vb, p.B, p.ldb, p.tb, p.vec_b, n0, p.N, k_begin, k_end, tid);
-  const int a_off = (wm * 32 * TM + l31) * GF_PITCH + 64 * half;
-  const int b_off = (wn * 32 * TN + l31) * GF_PITCH + 64 * half;
-  for (int s = 0; s < n_st; ++s) {
-    __syncthreads();                                       // every wave is past its fragment reads of the previous stage
-    gf_stage<BM>(va, a_img, p.ta, tid);
-    gf_stage<BN>(vb, b_img, p.tb, tid);
-    __syncthreads();
-    if (s + 1 < n_st) {                                    // the next stage's operands travel under this stage's MFMAs
-      const int k0 = k_begin + (s + 1) * GM_BK;
-      gm_fetch<BM>(va, p.A, p.lda, p.ta, p.vec_a, m0, p.M, k0, k_end, tid);
-      gm_fetch<BN>(vb, p.B, p.ldb, p.tb, p.vec_b, n0, p.N, k0, k_end, tid);
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      float4 a[TM], b[TN];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) a[i] = *reinterpret_cast<const float4*>(a_img + a_off + i * 32 * GF_PITCH + 16 * c);
-#pragma unroll
-      for (int j = 0; j < TN; ++j) b[j] = *reinterpret_cast<const float4*>(b_img + b_off + j * 32 * GF_PITCH + 16 * c);
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) {
-            const float av = e == 0 ? a[i].x : e == 1 ? a[i].y : e == 2 ? a[i].z : a[i].w;
-            const float bv = e == 0 ? b[j].x : e == 1 ? b[j].y : e == 2 ? b[j].z : b[j].w;
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc[i][j], 0, 0, 0);
-          }
-    }
-  }
-
-  // the accumulator layout and the stores of gemm_bf3_kernel
-  const bool direct = p.ksplit == 1;
-  float* const out = direct ? p.C : p.slab + (long long)blockIdx.z * p.M * p.N;
-  const long long ldo = direct ? p.ldc : p.N;
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int n = n0 + wn * 32 * TN + 32 * j + l31;
-    if (n >= p.N) continue;
-    const float bv = (direct && p.bias) ? p.bias[n] : 0.f;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const int mr = m0 + wm * 32 * TM + 32 * i + 4 * half;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = mr + (r & 3) + 8 * (r >> 2);
-        if (m < p.M) {
-          const float v = acc[i][j][r] + bv;
-          out[(long long)m * ldo + n] = direct ? gm_act(v, p.act, p.slope) : v;
-        }
-      }
-    }
-  }
+  __shared__ __attribute__((aligned(16))) char lds[gemm_lds_bytes<GemmF32, TM, TN>()];
+  gemm_tile<GemmF32, TM, TN>(p, lds);
 }
 
 // C[m][n] = act(Σ_z slab[z][m][n] + bias[n]), slabs added in z order (four independent chains, combined in a fixed tree)
