@@ -37,13 +37,15 @@
 __device__ __attribute__((aligned(16))) float ww_zero16[4] = {0.f, 0.f, 0.f, 0.f};
 
 #define WW_MAX_SETS 3
+// where the reduction writes a k-row segment: k-row c of the segment's `rows`, output row m → w[out][m·out_sm + c·out_sc + out_off]
+struct WwOut { int rows, out, out_off, out_sc, out_sm; };
 struct WwSeg {
   const float* ptr[WW_MAX_SETS];   // one tensor per operand set (application of the WN); rows of a [B][.][L] tensor: row c of sample
                                    // b of set s at ptr[s] + b·bs + c·L
   long long bs;         // batch stride (floats)
   long long mul_off;    // product operand: the partner row lives mul_off floats further (t·s halves); 0 = none
-  int rows, shift;      // rows of this segment; time shift of the row's samples (x[k][t] = row[t + shift])
-  int out, out_off, out_sc, out_sm;   // reduce: k-row c of this segment, output row m → w[out][m·out_sm + c·out_sc + out_off]
+  int shift;            // time shift of the row's samples (x[k][t] = row[t + shift])
+  WwOut o;              // o.rows: rows of this segment (the other fields: k-row segments only)
 };
 
 struct WwParams {
@@ -134,14 +136,275 @@ __device__ __forceinline__ int ww_dma_row(int i, int lane) { return 8 * i + ((la
 // byte offset of piece q of logical row r inside a slot
 __device__ __forceinline__ int ww_lds_off(int r, int q) { return ((r ^ ((r >> 3) & 1)) << 7) + (((q ^ r) & 7) << 4); }
 
-// which tensor row / piece a lane of a k-row DMA instruction fetches → (address for batch 0, t0 = 0; batch stride; first sample)
+// ---- pieces shared by wn_wgrad_kernel and tz_wgrad_kernel
+
+// Thread map of an LDS-DMA instruction: lane → (logical row r of the slot, piece q of that row) of instruction i.  A wave issues
+// the instructions i = wave + 8k of a slot.
+struct WwDmaLane { int r, q; };
+__device__ __forceinline__ WwDmaLane ww_dma_lane(int i, int lane) {
+  const int r = ww_dma_row(i, lane);
+  return {r, (lane ^ r) & 7};
+}
+
+// Fragment lane addressing: an MFMA operand fragment of k-step ks is row block·32 + l31 (LDS row l31 ^ ((l31 >> 3) & 1) of the
+// block: byte offset `row`), 8 samples = the pieces 4·ks + 2·half (after the split pass: the hi parts) and the next one (the lo
+// parts), at the byte offsets piece[ks][0 | 1] inside the row.
+struct WwFragLane { int row, piece[2][2]; };
+__device__ __forceinline__ WwFragLane ww_frag_lane(int l31, int half) {
+  WwFragLane f;
+  f.row = (l31 ^ ((l31 >> 3) & 1)) << 7;
+  const int sw = l31 & 7;
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) f.piece[ks][j] = (((4 * ks + 2 * half + j) ^ sw) & 7) << 4;
+  return f;
+}
+
+// the tiles [begin, end) of workgroup wg among the n_wgs that share n_tiles (the K split)
+__device__ __forceinline__ void ww_tile_range(int wg, int n_wgs, int n_tiles, int& begin, int& end) {
+  begin = (int)(((long long)wg * n_tiles) / n_wgs);
+  end = (int)(((long long)(wg + 1) * n_tiles) / n_wgs);
+}
+
+// One 32×32 accumulator tile → a slab of row length ld: register r = output row (r&3) + 8(r>>2) + 4·half, lane & 31 = k-row; dst =
+// the slab element (row 4·half, k-row l31) of the tile: one wave-instruction stores two rows × 32 consecutive floats
+__device__ __forceinline__ void ww_store_tile(float* dst, int ld, const f32x16& acc) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) dst[(long long)((r & 3) + 8 * (r >> 2)) * ld] = acc[r];
+}
+
+// ---- k-row decode
+
+// k-row kk → (segment si, channel c of it): the segments follow each other, at most four.  S: WwSeg or WwOut (ww_out)
+__device__ __forceinline__ const WwOut& ww_out(const WwSeg& s) { return s.o; }
+__device__ __forceinline__ const WwOut& ww_out(const WwOut& o) { return o; }
+struct WwRow { int si, c; };
+template <class S>
+__device__ __forceinline__ WwRow ww_k_row(const S (&x)[4], int n_x, int kk) {
+  WwRow r = {0, kk};
+#pragma unroll
+  for (int j = 0; j < 3; ++j)                              // (a k-row that stopped at a segment before j stays there)
+    if (r.si == j && j + 1 < n_x && r.c >= ww_out(x[j]).rows) { r.c -= ww_out(x[j]).rows; ++r.si; }
+  return r;
+}
+// f(segment si), f = one scalar field: a segment's fields by a chain of compares (kernel arguments are read with scalar loads; no
+// pointer into the argument block — and no struct-valued f: the compiler then builds the chain as a table in scratch)
+template <class S, class F>
+__device__ __forceinline__ auto ww_pick(const S (&x)[4], int si, F f) {
+  auto v = f(x[0]);
+  if (si == 1) v = f(x[1]);
+  if (si == 2) v = f(x[2]);
+  if (si == 3) v = f(x[3]);
+  return v;
+}
+
+// which tensor row / piece a lane of an LDS-DMA instruction fetches → (address for batch 0, t0 = 0; batch stride; first sample)
 struct WwSrc { const float* p; int bs, t; };
+
+// The dy rows of a stage: 32 LDS-DMA instructions per slot, 4 per wave; lane → (row, piece) by ww_dma_lane(wave + 8k).
+struct WwDyStage {
+  WwSrc src[4];
+
+  __device__ __forceinline__ void build(const WwParams& p, int set, int wave_s, int lane) {
+    // (both segments' pointers are read up front, wave-uniform: read inside the per-lane branches below they became one vector
+    // load and one vmcnt(0) wait per instruction k, four in a row in front of the first stage — 3 µs of a 60 µs res_skip launch)
+    const float* const d0 = p.dy[0].ptr[set];
+    const float* const d1 = p.dy[1].ptr[set];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const WwDmaLane m = ww_dma_lane(wave_s + 8 * k, lane);
+      const int r = m.r, q = m.q;
+      src[k].p = nullptr; src[k].bs = 0; src[k].t = 4 * q;
+      if (r < p.M) {
+        if (p.n_dy > 1 && r >= p.dy[0].o.rows) {
+          src[k].p = d1 + ((long long)(r - p.dy[0].o.rows) * p.L + 4 * q); src[k].bs = (int)p.dy[1].bs;
+        } else {
+          src[k].p = d0 + ((long long)r * p.L + 4 * q); src[k].bs = (int)p.dy[0].bs;
+        }
+      }
+    }
+  }
+  // the k-th piece of this wave for the stage (b, t0) into the slot at `slot`
+  __device__ __forceinline__ void issue1(int k, int b, int t0, int L, char* slot, int wave_s, const char* zero16) const {
+    const bool ok = src[k].p != nullptr && t0 + src[k].t < L;
+    const char* s = ok ? reinterpret_cast<const char*>(src[k].p + ((long long)b * src[k].bs + t0)) : zero16;
+    ww_dma16(s, ww_lds_addr(slot + (wave_s + 8 * k) * 1024));
+  }
+};
+
+// The k-rows of a stage and group g: slot rows [0, xr) the rows, [xr, 2·xr) their partners (product operand), then 8 rows for the
+// leftover k-rows (group 0 only): RX/8 LDS-DMA instructions per slot, up to WW_MAX_NX per wave; lane → (row, piece) by
+// ww_dma_lane(wave + 8k).
+struct WwXStage {
+  WwSrc src[WW_MAX_NX];
+  int my_nx;                                               // instructions of this wave (wave-uniform)
+
+  __device__ __forceinline__ void build(const WwParams& p, int set, int g, int wave_s, int lane) {
+    const int NXI = p.RX >> 3;
+    my_nx = (NXI - wave_s + 7) >> 3;
+    // (the set's four pointers are read up front, wave-uniform, as in WwDyStage::build: picked from the argument block under the
+    // per-lane compares they were a vector load and a vmcnt(0) wait per instruction k)
+    const float* const xp[4] = {p.x[0].ptr[set], p.x[1].ptr[set], p.x[2].ptr[set], p.x[3].ptr[set]};
+#pragma unroll
+    for (int k = 0; k < WW_MAX_NX; ++k) {
+      src[k].p = nullptr; src[k].bs = 0; src[k].t = 0;
+      if (k >= my_nx) continue;
+      const WwDmaLane m = ww_dma_lane(wave_s + 8 * k, lane);
+      const int rr = m.r, q = m.q;
+      int kk = -1;
+      bool partner = false;
+      if (rr < p.xr) kk = g * p.xr + rr;
+      else if (p.mul && rr < 2 * p.xr) { kk = g * p.xr + rr - p.xr; partner = true; }
+      else {
+        const int e = rr - p.xr * (1 + p.mul);              // leftover rows: the k-rows K_main .. K-1, staged by group 0
+        if (g == 0 && e < p.n_extra) kk = p.K_main + e;
+      }
+      if (kk >= 0 && kk < p.K && (kk < p.K_main || rr >= p.xr * (1 + p.mul))) {
+        const WwRow row = ww_k_row(p.x, p.n_x, kk);
+        const float* sp = ww_pick(xp, row.si, [](const float* x) { return x; });
+        const long long sbs = ww_pick(p.x, row.si, [](const WwSeg& x) { return x.bs; });
+        const long long smo = ww_pick(p.x, row.si, [](const WwSeg& x) { return x.mul_off; });
+        const int ssh = ww_pick(p.x, row.si, [](const WwSeg& x) { return x.shift; });
+        src[k].p = sp + ((long long)row.c * p.L + ssh + 4 * q) + (partner ? smo : 0);
+        src[k].bs = (int)sbs;
+        src[k].t = ssh + 4 * q;
+      }
+    }
+  }
+  __device__ __forceinline__ void issue1(int k, int b, int t0, int L, char* slot, int wave_s, const char* zero16) const {
+    if (k >= my_nx) return;                                // wave-uniform
+    const int t = t0 + src[k].t;
+    const bool ok = src[k].p != nullptr && t > -4 && t < L;   // the piece overlaps the sequence (a straddling one is patched)
+    const char* s = ok ? reinterpret_cast<const char*>(src[k].p + ((long long)b * src[k].bs + t0)) : zero16;
+    ww_dma16(s, ww_lds_addr(slot + (wave_s + 8 * k) * 1024));
+  }
+};
+
+// (misaligned taps) the tap shift of the staged k-row `tid` of group g, for ww_patch_edges; 0 = nothing to patch
+__device__ __forceinline__ int ww_patch_shift(const WwParams& p, int g, int tid) {
+  if (!(p.misaligned && tid < p.xr)) return 0;
+  const int kk = g * p.xr + tid;
+  const int sh = ww_pick(p.x, ww_k_row(p.x, p.n_x, kk).si, [](const WwSeg& x) { return x.shift; });
+  return (kk < p.K_main && (sh & 3) != 0 && sh > -4 && sh < 4) ? sh : 0;
+}
+
+// Boundary patch of the k-row slot at xslot for the stage at t0.  Tap shifts that are not multiples of 4 samples (dilation 1-3):
+// the LDS-DMA source is only 4-byte aligned (the hardware takes it), and in the first / last stage of a sequence one piece per
+// shifted row straddles the sequence's end: its out-of-range samples are a neighbouring row's data — zero them here, behind one
+// more barrier (2 stages in L/32).  Thread tid patches slot row tid.
+__device__ __forceinline__ void ww_patch_edges(char* xslot, int tid, int patch_sh, int t0, int L) {
+  const bool at_start = t0 == 0, at_end = t0 + WW_TT >= L;
+  if (at_start || at_end) {
+    if (patch_sh != 0) {
+      char* rowp = xslot + ((tid ^ ((tid >> 3) & 1)) << 7);
+      if (at_start && patch_sh < 0)                      // samples t0 + sh + j < 0 of piece 0
+        for (int j = 0; j < -patch_sh; ++j) ww_lds_zero4(ww_lds_addr(rowp + (((0 ^ tid) & 7) << 4) + 4 * j));
+      if (at_end && patch_sh > 0)                        // samples t0 + sh + 28 + j >= L of piece 7
+        for (int j = 4 - patch_sh; j < 4; ++j) ww_lds_zero4(ww_lds_addr(rowp + (((7 ^ tid) & 7) << 4) + 4 * j));
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the zeroing stores; NOT __syncthreads(): its fence would drain the ring
+    __builtin_amdgcn_s_barrier();
+  }
+}
+
+// Split pass: every staged 8-sample unit (two raw 16-byte pieces of a row) is split ONCE per workgroup, in place, into its bf16 hi
+// parts (written over the first piece) and lo parts (over the second) — not once per consuming wave (each dy fragment is consumed
+// by 2 waves, each k-row fragment by 4: 280 VALU instructions per wave and stage against 36 MFMAs).
+// Thread map: thread t owns the dy units t and t + 512 (rows t>>2 and 128 + (t>>2), unit t&3 = pieces 2u, 2u + 1) of the slot at
+// dw and the k-row units t (and t + 512, if the row exists) of the slot at xw; a product operand's partner row sits xr rows further.
+// NE: ev[i] += the dot product of dy unit i with the same 8 samples of the leftover k-row (raw, never split; slot byte e_off).
+// (Not __forceinline__: inlined ahead of the optimiser, the k-row registers that a thread without a second unit never loads were
+// given values — 32 v_mov per stage, 2 µs of a 60 µs res_skip launch; the inliner proper takes its one call site as it is.)
+template <bool MUL, int NE>
+static __device__ void ww_split_pass(char* dw, char* xw, int tid, int xr, int e_off, float (&ev)[2]) {
+  const int u = tid & 3, r0 = tid >> 2;
+  f32x4 e0, e1;
+  if constexpr (NE > 0) {
+    e0 = ww_lds_read16(ww_lds_addr(xw + e_off + ((2 * u) << 4)));
+    e1 = ww_lds_read16(ww_lds_addr(xw + e_off + ((2 * u + 1) << 4)));
+  }
+  f32x4 d[2][2], xq[2][2], xm[2][2];
+  char* da[2][2]; char* xa[2][2];
+  const int nxu = (xr * 4 > 512 + tid) ? 2 : 1;          // k-row units of this thread: rows r0 and (if it exists) 128 + r0
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int r = r0 + 128 * i;
+    da[i][0] = dw + ww_lds_off(r, 2 * u); da[i][1] = dw + ww_lds_off(r, 2 * u + 1);
+    d[i][0] = ww_lds_read16(ww_lds_addr(da[i][0])); d[i][1] = ww_lds_read16(ww_lds_addr(da[i][1]));
+    xa[i][0] = xw + ww_lds_off(r, 2 * u); xa[i][1] = xw + ww_lds_off(r, 2 * u + 1);
+    if (i < nxu && r < xr) {
+      xq[i][0] = ww_lds_read16(ww_lds_addr(xa[i][0])); xq[i][1] = ww_lds_read16(ww_lds_addr(xa[i][1]));
+      if constexpr (MUL) {
+        xm[i][0] = ww_lds_read16(ww_lds_addr(xa[i][0] + (xr << 7))); xm[i][1] = ww_lds_read16(ww_lds_addr(xa[i][1] + (xr << 7)));
+      }
+    }
+  }
+  ww_lds_wait();
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int r = r0 + 128 * i;
+    if constexpr (NE > 0)
+      ev[i] += (d[i][0].x * e0.x + d[i][0].y * e0.y) + (d[i][0].z * e0.z + d[i][0].w * e0.w) +
+               (d[i][1].x * e1.x + d[i][1].y * e1.y) + (d[i][1].z * e1.z + d[i][1].w * e1.w);
+    u32x4 h4, l4;
+    ww_split8u(d[i][0], d[i][1], h4, l4);
+    ww_lds_write16(ww_lds_addr(da[i][0]), h4); ww_lds_write16(ww_lds_addr(da[i][1]), l4);
+    if (i < nxu && r < xr) {
+      if constexpr (MUL) { xq[i][0] *= xm[i][0]; xq[i][1] *= xm[i][1]; }
+      ww_split8u(xq[i][0], xq[i][1], h4, l4);
+      ww_lds_write16(ww_lds_addr(xa[i][0]), h4); ww_lds_write16(ww_lds_addr(xa[i][1]), l4);
+    }
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+
+// One k-step (16 samples) of a wave's MT × KT tiles: fragments are read as they stand after the split pass (hi = first piece, lo =
+// second piece of the lane's unit) from ap (the wave's first dy row block, this lane's row) and bp (its first k-row block), then
+// MT·KT triple-MFMAs.  m_live / k_live: the wave's live row / k-row blocks (FULL: all of them, no tests).  issue(pos), pos = 0..4,
+// is called at five fixed places between the MFMA groups (the LDS-DMA pieces of later stages: see the stage loop).
+// The body is straight-line code (no run-time branches: the compiler then issues all of a k-step's fragment reads up front and
+// waits for them one by one as the splits consume them; with uniform branches around the optional parts it read, waited, split
+// and multiplied fragment by fragment — 139 µs instead of the ring's rate).
+template <int MT, int KT, bool FULL, class Issue>
+__device__ __forceinline__ void ww_k_step(f32x16 (&acc)[MT][KT], const char* ap, const char* bp, const int (&piece)[2], int m_live,
+                                          int k_live, Issue issue) {
+  f32x4 araw[MT][2], braw[KT][2];
+#pragma unroll
+  for (int i = 0; i < MT; ++i) {
+    araw[i][0] = ww_lds_read16(ww_lds_addr(ap + ((i * 32) << 7) + piece[0]));
+    araw[i][1] = ww_lds_read16(ww_lds_addr(ap + ((i * 32) << 7) + piece[1]));
+  }
+#pragma unroll
+  for (int j = 0; j < KT; ++j) {
+    braw[j][0] = ww_lds_read16(ww_lds_addr(bp + ((j * 32) << 7) + piece[0]));
+    braw[j][1] = ww_lds_read16(ww_lds_addr(bp + ((j * 32) << 7) + piece[1]));
+  }
+  ww_lds_wait();
+  issue(0);
+#pragma unroll
+  for (int j = 0; j < KT; ++j) {
+    // (blocks beyond K hold zeros: their products are skipped — wave-uniform — but NOT the LDS-DMA piece issued behind them:
+    // a `break` here once left the later stages of a workgroup without part of their operands whenever a wave had a dead
+    // k-row block, i.e. for every n <= 96 once a workgroup had more than one stage; found by the many-tile small-n cases of
+    // test_time_as_k_weight_gradient_kernels)
+    if (FULL || j < k_live) {
+      const bf16x8 bh = __builtin_bit_cast(bf16x8, braw[j][0]), bl = __builtin_bit_cast(bf16x8, braw[j][1]);
+#pragma unroll
+      for (int i = 0; i < MT; ++i) {
+        if (!FULL && i >= m_live) break;                   // wave-uniform
+        const bf16x8 ah = __builtin_bit_cast(bf16x8, araw[i][0]), al = __builtin_bit_cast(bf16x8, araw[i][1]);
+        mfma_bf3(acc[i][j], ah, al, bh, bl);
+      }
+    }
+    issue(1 + j);
+  }
+  if constexpr (KT < 3) issue(3);
+  issue(4);
+}
 
 // FULL: every output-row block and every k-row block of every group is live: no block tests in the inner loop.  MUL: product
 // operand (every k-row fragment is the product of two staged rows).  NE: leftover k-rows accumulated on the VALU (0 or 1).
-// The k-step body is straight-line code (no run-time branches: the compiler then issues all of a k-step's fragment reads up
-// front and waits for them one by one as the splits consume them; with uniform branches around the optional parts it read,
-// waited, split and multiplied fragment by fragment — 139 µs instead of the ring's rate).
 template <int MT, int KT, bool FULL, bool MUL, int NE>
 __global__ __launch_bounds__(512, 2) void wn_wgrad_kernel(WwParams p) {
   extern __shared__ __attribute__((aligned(16))) char ww_lds[];
@@ -154,69 +417,11 @@ __global__ __launch_bounds__(512, 2) void wn_wgrad_kernel(WwParams p) {
   char* const xring = ww_lds + WW_ND * dslot_bytes;
   const char* const zero16 = reinterpret_cast<const char*>(ww_zero16);
 
-  // ---- dy rows: 32 LDS-DMA instructions per stage, 4 per wave (i = wave + 8k)
-  WwSrc dsrc[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int i = wave_s + 8 * k;
-    const int r = ww_dma_row(i, lane), q = (lane ^ r) & 7;
-    dsrc[k].p = nullptr; dsrc[k].bs = 0; dsrc[k].t = 4 * q;
-    if (r < p.M) {
-      if (p.n_dy > 1 && r >= p.dy[0].rows) {
-        dsrc[k].p = p.dy[1].ptr[set] + ((long long)(r - p.dy[0].rows) * L + 4 * q); dsrc[k].bs = (int)p.dy[1].bs;
-      } else {
-        dsrc[k].p = p.dy[0].ptr[set] + ((long long)r * L + 4 * q); dsrc[k].bs = (int)p.dy[0].bs;
-      }
-    }
-  }
-  // ---- k-rows of this group: [0, xr) the rows, [xr, 2·xr) their partners (product operand), then 8 rows for the leftover
-  // k-rows (group 0 only); RX/8 instructions per stage
-  const int NXI = p.RX >> 3;
-  const int my_nx = (NXI - wave_s + 7) >> 3;
-  WwSrc xsrc[WW_MAX_NX];
-#pragma unroll
-  for (int k = 0; k < WW_MAX_NX; ++k) {
-    xsrc[k].p = nullptr; xsrc[k].bs = 0; xsrc[k].t = 0;
-    const int i = wave_s + 8 * k;
-    if (k >= my_nx) continue;
-    const int rr = ww_dma_row(i, lane), q = (lane ^ rr) & 7;
-    int kk = -1;
-    bool partner = false;
-    if (rr < p.xr) kk = g * p.xr + rr;
-    else if (p.mul && rr < 2 * p.xr) { kk = g * p.xr + rr - p.xr; partner = true; }
-    else {
-      const int e = rr - p.xr * (1 + p.mul);              // leftover rows: the k-rows K_main .. K-1, staged by group 0
-      if (g == 0 && e < p.n_extra) kk = p.K_main + e;
-    }
-    if (kk >= 0 && kk < p.K && (kk < p.K_main || rr >= p.xr * (1 + p.mul))) {
-      int si = 0, c0 = kk;
-#pragma unroll
-      for (int j = 0; j < 3; ++j)
-        if (si + 1 < p.n_x && c0 >= p.x[si].rows) { c0 -= p.x[si].rows; ++si; }
-      // the segment's fields by a chain of compares (kernel arguments are read with scalar loads; no pointer into the argument block)
-      const float* sp = p.x[0].ptr[set];
-      long long sbs = p.x[0].bs, smo = p.x[0].mul_off;
-      int ssh = p.x[0].shift;
-      if (si == 1) { sp = p.x[1].ptr[set]; sbs = p.x[1].bs; smo = p.x[1].mul_off; ssh = p.x[1].shift; }
-      if (si == 2) { sp = p.x[2].ptr[set]; sbs = p.x[2].bs; smo = p.x[2].mul_off; ssh = p.x[2].shift; }
-      if (si == 3) { sp = p.x[3].ptr[set]; sbs = p.x[3].bs; smo = p.x[3].mul_off; ssh = p.x[3].shift; }
-      xsrc[k].p = sp + ((long long)c0 * L + ssh + 4 * q) + (partner ? smo : 0);
-      xsrc[k].bs = (int)sbs;
-      xsrc[k].t = ssh + 4 * q;
-    }
-  }
-
-  // (misaligned taps) the tap shift of the staged k-row `tid` of this group, for the boundary patch below; 0 = nothing to patch
-  int patch_sh = 0;
-  if (p.misaligned && tid < p.xr) {
-    const int kk = g * p.xr + tid;
-    int c0 = kk, si = 0;
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-      if (si + 1 < p.n_x && c0 >= p.x[si].rows) { c0 -= p.x[si].rows; ++si; }
-    const int sh = si == 0 ? p.x[0].shift : (si == 1 ? p.x[1].shift : (si == 2 ? p.x[2].shift : p.x[3].shift));
-    if (kk < p.K_main && (sh & 3) != 0 && sh > -4 && sh < 4) patch_sh = sh;
-  }
+  WwDyStage dys;
+  dys.build(p, set, wave_s, lane);
+  WwXStage xs;
+  xs.build(p, set, g, wave_s, lane);
+  const int patch_sh = ww_patch_shift(p, g, tid);
   // The tables above are per-lane selections of kernel arguments: the compiler reads some of them with vector loads, and — not
   // seeing the inline-asm waits below — would make every first use inside the stage loop wait for vmcnt(0), i.e. for the whole
   // LDS-DMA ring.  A wait it does see, here, retires them once.
@@ -226,60 +431,36 @@ __global__ __launch_bounds__(512, 2) void wn_wgrad_kernel(WwParams p) {
     b = tile / p.tiles_per_seq;
     t0 = (tile - b * p.tiles_per_seq) * WW_TT;
   };
-  // one LDS-DMA piece: k-th dy instruction / k-th k-row instruction of this wave for the stage (b, t0) into the given slot
-  auto issue_dy1 = [&](int k, int b, int t0, int slot) {
-    const bool ok = dsrc[k].p != nullptr && t0 + dsrc[k].t < L;
-    const char* src = ok ? reinterpret_cast<const char*>(dsrc[k].p + ((long long)b * dsrc[k].bs + t0)) : zero16;
-    ww_dma16(src, ww_lds_addr(ww_lds + slot * dslot_bytes + (wave_s + 8 * k) * 1024));
-  };
-  auto issue_x1 = [&](int k, int b, int t0, int slot) {
-    if (k >= my_nx) return;                                // wave-uniform
-    const int t = t0 + xsrc[k].t;
-    const bool ok = xsrc[k].p != nullptr && t > -4 && t < L;   // the piece overlaps the sequence (a straddling one is patched)
-    const char* src = ok ? reinterpret_cast<const char*>(xsrc[k].p + ((long long)b * xsrc[k].bs + t0)) : zero16;
-    ww_dma16(src, ww_lds_addr(xring + slot * xslot_bytes + (wave_s + 8 * k) * 1024));
-  };
+  // all pieces of this wave for a tile at once (the first stages; later ones are spread over the k-steps)
   auto issue_dy = [&](int tile, int slot) {
     int b, t0;
     tile_bt(tile, b, t0);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) issue_dy1(k, b, t0, slot);
+    for (int k = 0; k < 4; ++k) dys.issue1(k, b, t0, L, ww_lds + slot * dslot_bytes, wave_s, zero16);
   };
   auto issue_x = [&](int tile, int slot) {
     int b, t0;
     tile_bt(tile, b, t0);
 #pragma unroll
-    for (int k = 0; k < WW_MAX_NX; ++k) issue_x1(k, b, t0, slot);
+    for (int k = 0; k < WW_MAX_NX; ++k) xs.issue1(k, b, t0, L, xring + slot * xslot_bytes, wave_s, zero16);
   };
 
   f32x16 acc[MT][KT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < KT; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
   float ev[2] = {0.f, 0.f};                                // leftover k-row: partial dot products of this thread's two dy units
 
   // the workgroups x ≡ set (mod n_sets) share the set's tiles
   const int wg_in_set = blockIdx.x / p.n_sets, wgs_of_set = (p.ksplit - set + p.n_sets - 1) / p.n_sets;
-  const int tile_begin = (int)(((long long)wg_in_set * p.n_tiles) / wgs_of_set);
-  const int tile_end = (int)(((long long)(wg_in_set + 1) * p.n_tiles) / wgs_of_set);
+  int tile_begin, tile_end;
+  ww_tile_range(wg_in_set, wgs_of_set, p.n_tiles, tile_begin, tile_end);
   const int m_blocks = (p.M + 31) >> 5;
   const int k_blocks_here = min(2 * KT, ((p.K_main + 31) >> 5) - g * 2 * KT);   // live k-row blocks of this group
+  const int m_live = m_blocks - wm * MT, k_live = k_blocks_here - wk * KT;       // ... of this wave's MT × KT tiles
   const bool do_extra = NE > 0 && g == 0;
 
-  // fragment addressing: row block·32 + l31 (LDS row l31 ^ ((l31 >> 3) & 1) of the block), pieces 4·ks + 2·half and the next
-  const int row_l = (l31 ^ ((l31 >> 3) & 1)) << 7;
-  const int sw = l31 & 7;
-  int pc[2][2];
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) {
-    pc[ks][0] = (((4 * ks + 2 * half) ^ sw) & 7) << 4;
-    pc[ks][1] = (((4 * ks + 2 * half + 1) ^ sw) & 7) << 4;
-  }
-  const int a_off = ((wm * MT * 32) << 7) + row_l;
-  const int x_off = ((wk * KT * 32) << 7) + row_l, xp_off = x_off + (p.xr << 7);
+  const WwFragLane fl = ww_frag_lane(l31, half);
+  const int a_off = ((wm * MT * 32) << 7) + fl.row;
+  const int x_off = ((wk * KT * 32) << 7) + fl.row;
   const int e_off = (p.xr * (1 + p.mul)) << 7;           // the leftover rows' octet: LDS row = e, piece slot = (q ^ e) & 7
 
   // Two rings, one barrier per stage: the dy rows run two stages ahead (three slots), the k-rows one (two slots — all that fits
@@ -303,132 +484,34 @@ __global__ __launch_bounds__(512, 2) void wn_wgrad_kernel(WwParams p) {
     if (have_dy) tile_bt(tile_begin + c + 2, db, dt0);
     const int x_next = xslot ^ 1, d_next = dslot >= 1 ? dslot - 1 : 2;
     auto issue_pos = [&](int pos) {                        // pos 0..4: k-row pieces, 5..8: dy pieces
-      if (pos < WW_MAX_NX) { if (have_x) issue_x1(pos, nb, nt0, x_next); }
-      else if (pos < WW_MAX_NX + 4) { if (have_dy) issue_dy1(pos - WW_MAX_NX, db, dt0, d_next); }
+      if (pos < WW_MAX_NX) { if (have_x) xs.issue1(pos, nb, nt0, L, xring + x_next * xslot_bytes, wave_s, zero16); }
+      else if (pos < WW_MAX_NX + 4) { if (have_dy) dys.issue1(pos - WW_MAX_NX, db, dt0, L, ww_lds + d_next * dslot_bytes, wave_s, zero16); }
     };
-    const char* const dsl = ww_lds + dslot * dslot_bytes;
-    const char* const xsl = xring + xslot * xslot_bytes;
+    char* const dsl = ww_lds + dslot * dslot_bytes;
+    char* const xsl = xring + xslot * xslot_bytes;
     if (p.misaligned) {                                    // kernel argument: uniform
-      // tap shifts that are not multiples of 4 samples (dilation 1-3): the LDS-DMA source is only 4-byte aligned (the hardware
-      // takes it), and in the first / last stage of a sequence one piece per shifted row straddles the sequence's end: its
-      // out-of-range samples are a neighbouring row's data — zero them here, behind one more barrier (2 stages in L/32)
       int bq, t0;
       tile_bt(tile_begin + c, bq, t0);
-      const bool at_start = t0 == 0, at_end = t0 + WW_TT >= L;
-      if (at_start || at_end) {
-        if (patch_sh != 0) {
-          char* rowp = xring + xslot * xslot_bytes + ((tid ^ ((tid >> 3) & 1)) << 7);
-          if (at_start && patch_sh < 0)                      // samples t0 + sh + j < 0 of piece 0
-            for (int j = 0; j < -patch_sh; ++j) ww_lds_zero4(ww_lds_addr(rowp + (((0 ^ tid) & 7) << 4) + 4 * j));
-          if (at_end && patch_sh > 0)                        // samples t0 + sh + 28 + j >= L of piece 7
-            for (int j = 4 - patch_sh; j < 4; ++j) ww_lds_zero4(ww_lds_addr(rowp + (((7 ^ tid) & 7) << 4) + 4 * j));
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the zeroing stores; NOT __syncthreads(): its fence would drain the ring
-        __builtin_amdgcn_s_barrier();
-      }
+      ww_patch_edges(xsl, tid, patch_sh, t0, L);
     }
-    // ---- split pass: every staged 8-sample unit (two raw 16-byte pieces of a row) is split ONCE per workgroup, in place, into
-    // its bf16 hi parts (written over the first piece) and lo parts (over the second) — not once per consuming wave (each dy
-    // fragment is consumed by 2 waves, each k-row fragment by 4: 280 VALU instructions per wave and stage against 36 MFMAs).
-    // Thread t owns the dy units t and t + 512 (rows t>>2 and 128 + (t>>2), unit t&3) and the k-row units t (and t + 512).
-    {
-      char* const dw = ww_lds + dslot * dslot_bytes;
-      char* const xw = xring + xslot * xslot_bytes;
-      const int u = tid & 3, r0 = tid >> 2;
-      f32x4 e0, e1;
-      if constexpr (NE > 0) {                              // the leftover k-row's 8 samples of this unit (raw, never split)
-        e0 = ww_lds_read16(ww_lds_addr(xw + e_off + ((2 * u) << 4)));
-        e1 = ww_lds_read16(ww_lds_addr(xw + e_off + ((2 * u + 1) << 4)));
-      }
-      f32x4 d[2][2], xq[2][2], xm[2][2];
-      char* da[2][2]; char* xa[2][2];
-      const int nxu = (p.xr * 4 > 512 + tid) ? 2 : 1;      // k-row units of this thread: rows r0 and (if it exists) 128 + r0
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int r = r0 + 128 * i;
-        da[i][0] = dw + ww_lds_off(r, 2 * u); da[i][1] = dw + ww_lds_off(r, 2 * u + 1);
-        d[i][0] = ww_lds_read16(ww_lds_addr(da[i][0])); d[i][1] = ww_lds_read16(ww_lds_addr(da[i][1]));
-        xa[i][0] = xw + ww_lds_off(r, 2 * u); xa[i][1] = xw + ww_lds_off(r, 2 * u + 1);
-        if (i < nxu && r < p.xr) {
-          xq[i][0] = ww_lds_read16(ww_lds_addr(xa[i][0])); xq[i][1] = ww_lds_read16(ww_lds_addr(xa[i][1]));
-          if constexpr (MUL) {
-            xm[i][0] = ww_lds_read16(ww_lds_addr(xa[i][0] + (p.xr << 7))); xm[i][1] = ww_lds_read16(ww_lds_addr(xa[i][1] + (p.xr << 7)));
-          }
-        }
-      }
-      ww_lds_wait();
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int r = r0 + 128 * i;
-        if constexpr (NE > 0)
-          ev[i] += (d[i][0].x * e0.x + d[i][0].y * e0.y) + (d[i][0].z * e0.z + d[i][0].w * e0.w) +
-                   (d[i][1].x * e1.x + d[i][1].y * e1.y) + (d[i][1].z * e1.z + d[i][1].w * e1.w);
-        u32x4 h4, l4;
-        ww_split8u(d[i][0], d[i][1], h4, l4);
-        ww_lds_write16(ww_lds_addr(da[i][0]), h4); ww_lds_write16(ww_lds_addr(da[i][1]), l4);
-        if (i < nxu && r < p.xr) {
-          if constexpr (MUL) { xq[i][0] *= xm[i][0]; xq[i][1] *= xm[i][1]; }
-          ww_split8u(xq[i][0], xq[i][1], h4, l4);
-          ww_lds_write16(ww_lds_addr(xa[i][0]), h4); ww_lds_write16(ww_lds_addr(xa[i][1]), l4);
-        }
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    }
+    ww_split_pass<MUL, NE>(dsl, xsl, tid, p.xr, e_off, ev);
     __builtin_amdgcn_s_barrier();
-    // ---- multiply: fragments are read as they stand (hi = first piece, lo = second piece of the lane's unit)
 #pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      f32x4 araw[MT][2], braw[KT][2];
-#pragma unroll
-      for (int i = 0; i < MT; ++i) {
-        const char* ap = dsl + a_off + ((i * 32) << 7);
-        araw[i][0] = ww_lds_read16(ww_lds_addr(ap + pc[ks][0]));
-        araw[i][1] = ww_lds_read16(ww_lds_addr(ap + pc[ks][1]));
-      }
-#pragma unroll
-      for (int j = 0; j < KT; ++j) {
-        const char* bp = xsl + x_off + ((j * 32) << 7);
-        braw[j][0] = ww_lds_read16(ww_lds_addr(bp + pc[ks][0]));
-        braw[j][1] = ww_lds_read16(ww_lds_addr(bp + pc[ks][1]));
-      }
-      ww_lds_wait();
-      issue_pos(5 * ks);
-#pragma unroll
-      for (int j = 0; j < KT; ++j) {
-        // (blocks beyond K hold zeros: their products are skipped — wave-uniform — but NOT the LDS-DMA piece issued behind them:
-        // a `break` here once left the later stages of a workgroup without part of their operands whenever a wave had a dead
-        // k-row block, i.e. for every n <= 96 once a workgroup had more than one stage; found by the many-tile small-n cases of
-        // test_time_as_k_weight_gradient_kernels)
-        if (FULL || wk * KT + j < k_blocks_here) {
-          const bf16x8 bh = __builtin_bit_cast(bf16x8, braw[j][0]), bl = __builtin_bit_cast(bf16x8, braw[j][1]);
-#pragma unroll
-          for (int i = 0; i < MT; ++i) {
-            if (!FULL && wm * MT + i >= m_blocks) break;   // wave-uniform
-            const bf16x8 ah = __builtin_bit_cast(bf16x8, araw[i][0]), al = __builtin_bit_cast(bf16x8, araw[i][1]);
-            mfma_bf3(acc[i][j], ah, al, bh, bl);
-          }
-        }
-        issue_pos(5 * ks + 1 + j);
-      }
-      if constexpr (KT < 3) issue_pos(5 * ks + 3);
-      issue_pos(5 * ks + 4);
-    }
+    for (int ks = 0; ks < 2; ++ks)
+      ww_k_step<MT, KT, FULL>(acc, dsl + a_off, xsl + x_off, fl.piece[ks], m_live, k_live, [&](int pos) { issue_pos(5 * ks + pos); });
     dslot = dslot == WW_ND - 1 ? 0 : dslot + 1;
     xslot ^= 1;
   }
 
-  // ---- partial D tile → this workgroup's slab: register r of a tile = output row (r&3) + 8(r>>2) + 4·half, lane & 31 = k-row:
-  // one wave-instruction stores two rows × 32 consecutive floats
+  // ---- partial D tile → this workgroup's slab
   float* const slab = p.slab + (long long)blockIdx.x * WW_MROWS * p.Kcols;
 #pragma unroll
   for (int i = 0; i < MT; ++i) {
-    if (wm * MT + i >= m_blocks) break;
+    if (i >= m_live) break;
 #pragma unroll
     for (int j = 0; j < KT; ++j) {
-      if (wk * KT + j >= k_blocks_here) break;
-      float* dst = slab + (long long)((wm * MT + i) * 32 + 4 * half) * p.Kcols + g * p.xr + (wk * KT + j) * 32 + l31;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) dst[(long long)((r & 3) + 8 * (r >> 2)) * p.Kcols] = acc[i][j][r];
+      if (j >= k_live) break;
+      ww_store_tile(slab + (long long)((wm * MT + i) * 32 + 4 * half) * p.Kcols + g * p.xr + (wk * KT + j) * 32 + l31, p.Kcols, acc[i][j]);
     }
   }
   if (do_extra) {
@@ -443,143 +526,49 @@ __global__ __launch_bounds__(512, 2) void wn_wgrad_kernel(WwParams p) {
   }
 }
 
-// out[m][k-row] = Σ_slabs, written in PyTorch layout: k-row kk of x segment s, channel c → w[seg.out][m·out_sm + c·out_sc + out_off].
-// One workgroup per (output row, 256 k-rows): thread (column quad cx, slab group sg) adds every fourth slab of its 16 bytes with
-// eight loads in flight, the four groups meet in LDS — fixed order, so the result is the same bits on every run.  (One thread
-// per element walking all slabs on its own had ~6 KB in flight per CU: 60 µs for 50 MB.)
-__device__ __forceinline__ void ww_scatter(const WwParams& p, int m, int kk, float v) {
-  int si = 0, c = kk;
-#pragma unroll
-  for (int j = 0; j < 3; ++j)
-    if (si + 1 < p.n_x && c >= p.x[si].rows) { c -= p.x[si].rows; ++si; }
-  int out = p.x[0].out, off = p.x[0].out_off, sc = p.x[0].out_sc, sm = p.x[0].out_sm;
-  if (si == 1) { out = p.x[1].out; off = p.x[1].out_off; sc = p.x[1].out_sc; sm = p.x[1].out_sm; }
-  if (si == 2) { out = p.x[2].out; off = p.x[2].out_off; sc = p.x[2].out_sc; sm = p.x[2].out_sm; }
-  if (si == 3) { out = p.x[3].out; off = p.x[3].out_off; sc = p.x[3].out_sc; sm = p.x[3].out_sm; }
-  float* w = out == 0 ? p.w[0] : p.w[1];
-  const long long at = (long long)m * sm + (long long)c * sc + off;
-  if (p.epi_p) {                                          // (uniform) RandomLayer: Hadamard product with the class-side map, scaled
-    float sd = 0.f;
-    for (int j = 0; j < p.epi_ncls; ++j) sd += p.epi_p[m * p.epi_ncls + j] * p.epi_r1[(long long)j * sm + c];
-    if (p.epi_raw) p.epi_raw[at] = v;
-    v = v * p.epi_scale * sd;
-  }
-  w[at] = v;
+// ---- slab reduction: out[m][k-row] = Σ_slabs, written in PyTorch layout
+
+// The sum `v` of k-row kk over all slabs, output row m → its place in PyTorch layout: k-row kk = channel c of segment s →
+// w[seg.out][m·out_sm + c·out_sc + out_off].  epi(v, at, c, sm) is the value stored (the plain sum, or RandomLayer's epilogue).
+// P: WwParams or WwRedEntry.  The four fields of segment si come from ww_dst(p, si), the ONE compare chain the scatter had before
+// the two scatters became one, spelled per argument struct (below, and next to WwRedEntry).  PUT BACK: with four ww_pick chains
+// per element the tail of a reduce workgroup — the latency of the whole launch — cost the res_skip launch 1-2 µs of 58
+// (profiles/wn_wgrad_refactor.txt), and the same chain written inside this template, over `x` as an array reference, made the
+// compiler copy the argument struct to scratch.
+__device__ __forceinline__ void ww_dst(const WwParams& p, int si, int& out, int& off, int& sc, int& sm) {
+  out = p.x[0].o.out; off = p.x[0].o.out_off; sc = p.x[0].o.out_sc; sm = p.x[0].o.out_sm;
+  if (si == 1) { out = p.x[1].o.out; off = p.x[1].o.out_off; sc = p.x[1].o.out_sc; sm = p.x[1].o.out_sm; }
+  if (si == 2) { out = p.x[2].o.out; off = p.x[2].o.out_off; sc = p.x[2].o.out_sc; sm = p.x[2].o.out_sm; }
+  if (si == 3) { out = p.x[3].o.out; off = p.x[3].o.out_off; sc = p.x[3].o.out_sc; sm = p.x[3].o.out_sm; }
+}
+template <class P, class Epi>
+__device__ __forceinline__ void ww_scatter(const P& p, int m, int kk, float v, Epi epi) {
+  const WwRow r = ww_k_row(p.x, p.n_x, kk);
+  int out, off, sc, sm;
+  ww_dst(p, r.si, out, off, sc, sm);
+  float* dst = out == 0 ? p.w[0] : p.w[1];
+  const long long at = (long long)m * sm + (long long)r.c * sc + off;
+  dst[at] = epi(v, at, r.c, sm);
 }
 
-__global__ __launch_bounds__(256) void wn_wgrad_reduce_kernel(WwParams p) {
-  __shared__ float4 part[4][64];
-  const int m = blockIdx.y, cx = threadIdx.x & 63, sg = threadIdx.x >> 6;
-  const int kk0 = blockIdx.x * 256 + cx * 4;
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (kk0 < p.Kcols) {
-    const long long st = (long long)WW_MROWS * p.Kcols;
-    const float* q = p.slab + (long long)m * p.Kcols + kk0;
-    int sl = sg;
-    for (; sl + 28 < p.ksplit; sl += 32) {
-      float4 v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const float4*>(q + (sl + 4 * u) * st);
-#pragma unroll
-      for (int u = 0; u < 8; ++u) { s.x += v[u].x; s.y += v[u].y; s.z += v[u].z; s.w += v[u].w; }
-    }
-    for (; sl < p.ksplit; sl += 4) {
-      const float4 v = *reinterpret_cast<const float4*>(q + sl * st);
-      s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-    }
-  }
-  part[sg][cx] = s;
-  __syncthreads();
-  if (sg == 0 && kk0 < p.Kcols) {
-    float4 t = part[0][cx];
-#pragma unroll
-    for (int g2 = 1; g2 < 4; ++g2) { const float4 o = part[g2][cx]; t.x += o.x; t.y += o.y; t.z += o.z; t.w += o.w; }
-    const float tv[4] = {t.x, t.y, t.z, t.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      if (kk0 + j < p.K_main) ww_scatter(p, m, kk0 + j, tv[j]);
-  }
-  // the leftover k-rows (VALU sums): the last column block's idle slab-group-1 threads take them
-  if (blockIdx.x == gridDim.x - 1 && sg == 1 && cx < p.n_extra && p.K_main < p.K) {
-    const float* q = p.slab_extra + (long long)m * 2 + cx;
-    float e = 0.f;
-    for (int sl = 0; sl < p.ksplit; ++sl) e += q[(long long)sl * WW_MROWS * 2];
-    ww_scatter(p, m, p.K_main + cx, e);
-  }
-}
-
-// The reductions of up to WW_MAX_RED slab sets (the in_layer and res_skip gradients of every layer of one WN) in ONE launch:
-// entry blockIdx.z of a table passed by value (a captured graph replays it as it is).  An entry holds what the reduction above
-// reads of WwParams.  Every output element is the same sum in the same order as there — per slab group sg the slabs sg, sg+4, ..
-// in turn, then groups 0..3, the leftover k-row slab after slab — so the result has the same bits; what differs is who adds:
-// the 16-byte column quads of ALL rows of an entry are dealt over the workgroups back to back (a slab's [M][Kcols] block is
-// contiguous: a wave reads 1 KiB runs), so no thread of a column block idles behind Kcols = 384 or 128, and the leftover
-// k-row's M sums get workgroups of their own behind the quads'.
-#define WW_MAX_RED 16
-struct WwRedSeg { int rows, out, out_off, out_sc, out_sm; };
-struct WwRedEntry {
-  const float* slab;        // [ksplit][256][Kcols]
-  const float* slab_extra;  // [ksplit][256][2]
-  float* w[2];
-  int ksplit, Kcols, K_main, K, n_extra, M, n_x;
-  int quad_blocks;          // workgroups of 64 column quads: ⌈M·Kcols/4 / 64⌉; the leftover sums follow, 256 per workgroup
-  WwRedSeg x[4];
-};
-struct WwRedParams { WwRedEntry e[WW_MAX_RED]; };
-
-__device__ __forceinline__ void ww_scatter_entry(const WwRedEntry& e, int m, int kk, float v) {
-  int si = 0, c = kk;
-#pragma unroll
-  for (int j = 0; j < 3; ++j)
-    if (si + 1 < e.n_x && c >= e.x[si].rows) { c -= e.x[si].rows; ++si; }
-  int out = e.x[0].out, off = e.x[0].out_off, sc = e.x[0].out_sc, sm = e.x[0].out_sm;
-  if (si == 1) { out = e.x[1].out; off = e.x[1].out_off; sc = e.x[1].out_sc; sm = e.x[1].out_sm; }
-  if (si == 2) { out = e.x[2].out; off = e.x[2].out_off; sc = e.x[2].out_sc; sm = e.x[2].out_sm; }
-  if (si == 3) { out = e.x[3].out; off = e.x[3].out_off; sc = e.x[3].out_sc; sm = e.x[3].out_sm; }
-  float* w = out == 0 ? e.w[0] : e.w[1];
-  w[(long long)m * sm + (long long)c * sc + off] = v;
-}
-
-__global__ __launch_bounds__(256) void wn_wgrad_reduce_many_kernel(WwRedParams p) {
-  __shared__ float4 part[4][64];
-  const WwRedEntry& e = p.e[blockIdx.z];
-  const int bx = blockIdx.x;
-  if (bx >= e.quad_blocks) {                               // (uniform) the leftover k-rows: one thread per (row, leftover row)
-    const int it = (bx - e.quad_blocks) * 256 + threadIdx.x;
-    if (e.K_main < e.K && it < e.M * e.n_extra) {
-      const int m = it / e.n_extra, j = it - m * e.n_extra;
-      const float* q = e.slab_extra + (long long)m * 2 + j;
-      float s = 0.f;
-      int sl = 0;
-      for (; sl + 8 <= e.ksplit; sl += 8) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = q[(long long)(sl + u) * WW_MROWS * 2];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) s += v[u];
-      }
-      for (; sl < e.ksplit; ++sl) s += q[(long long)sl * WW_MROWS * 2];
-      ww_scatter_entry(e, m, e.K_main + j, s);
-    }
-    return;
-  }
+// The slab walk of one 16-byte column quad (q: its four floats in slab 0, st: floats per slab): thread (column quad cx, slab group
+// sg) adds every fourth slab with eight loads in flight, the four groups meet in LDS and are added in the order 0..3 — a fixed
+// order, so the result is the same bits on every run.  (One thread per element walking all slabs on its own had ~6 KB in flight
+// per CU: 60 µs for 50 MB.)  store(tv) gets the four sums, on the group-0 thread of a live quad.  All 256 threads call it.
+template <class Store>
+__device__ __forceinline__ void ww_quad_sum(const float* q, long long st, int ksplit, bool live, float4 (&part)[4][64], Store store) {
   const int cx = threadIdx.x & 63, sg = threadIdx.x >> 6;
-  const int qpr = e.Kcols >> 2;                            // quads per row (Kcols is a multiple of 128)
-  const int quad = bx * 64 + cx;
-  const bool live = quad < e.M * qpr;
   float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
   if (live) {
-    const long long st = (long long)WW_MROWS * e.Kcols;
-    const float* q = e.slab + (long long)quad * 4;         // = row m·Kcols + column kk0 of slab 0
     int sl = sg;
-    for (; sl + 28 < e.ksplit; sl += 32) {
+    for (; sl + 28 < ksplit; sl += 32) {
       float4 v[8];
 #pragma unroll
       for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const float4*>(q + (sl + 4 * u) * st);
 #pragma unroll
       for (int u = 0; u < 8; ++u) { s.x += v[u].x; s.y += v[u].y; s.z += v[u].z; s.w += v[u].w; }
     }
-    for (; sl < e.ksplit; sl += 4) {
+    for (; sl < ksplit; sl += 4) {
       const float4 v = *reinterpret_cast<const float4*>(q + sl * st);
       s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
     }
@@ -591,11 +580,94 @@ __global__ __launch_bounds__(256) void wn_wgrad_reduce_many_kernel(WwRedParams p
 #pragma unroll
     for (int g2 = 1; g2 < 4; ++g2) { const float4 o = part[g2][cx]; t.x += o.x; t.y += o.y; t.z += o.z; t.w += o.w; }
     const float tv[4] = {t.x, t.y, t.z, t.w};
+    store(tv);
+  }
+}
+
+// the leftover k-row's sum (q: its element in slab 0 of [ksplit][256][2]): slab after slab, eight loads in flight
+__device__ __forceinline__ float ww_extra_sum(const float* q, int ksplit) {
+  float s = 0.f;
+  int sl = 0;
+  for (; sl + 8 <= ksplit; sl += 8) {
+    float v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = q[(long long)(sl + u) * WW_MROWS * 2];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) s += v[u];
+  }
+  for (; sl < ksplit; ++sl) s += q[(long long)sl * WW_MROWS * 2];
+  return s;
+}
+
+// One workgroup per (output row, 256 k-rows); the last column block's idle slab-group-1 threads take the leftover k-rows.
+__global__ __launch_bounds__(256) void wn_wgrad_reduce_kernel(WwParams p) {
+  __shared__ float4 part[4][64];
+  const int m = blockIdx.y, cx = threadIdx.x & 63, sg = threadIdx.x >> 6;
+  const int kk0 = blockIdx.x * 256 + cx * 4;
+  auto epi = [&](float v, long long at, int c, int sm) {
+    if (p.epi_p) {                                          // (uniform) RandomLayer: Hadamard product with the class-side map, scaled
+      float sd = 0.f;
+      for (int j = 0; j < p.epi_ncls; ++j) sd += p.epi_p[m * p.epi_ncls + j] * p.epi_r1[(long long)j * sm + c];
+      if (p.epi_raw) p.epi_raw[at] = v;
+      v = v * p.epi_scale * sd;
+    }
+    return v;
+  };
+  ww_quad_sum(p.slab + (long long)m * p.Kcols + kk0, (long long)WW_MROWS * p.Kcols, p.ksplit, kk0 < p.Kcols, part, [&](const float (&tv)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (kk0 + j < p.K_main) ww_scatter(p, m, kk0 + j, tv[j], epi);
+  });
+  if (blockIdx.x == gridDim.x - 1 && sg == 1 && cx < p.n_extra && p.K_main < p.K)
+    ww_scatter(p, m, p.K_main + cx, ww_extra_sum(p.slab_extra + (long long)m * 2 + cx, p.ksplit), epi);
+}
+
+// The reductions of up to WW_MAX_RED slab sets (the in_layer and res_skip gradients of every layer of one WN) in ONE launch:
+// entry blockIdx.z of a table passed by value (a captured graph replays it as it is).  An entry holds what the reduction above
+// reads of WwParams.  Every output element is the same sum in the same order as there (ww_quad_sum, ww_extra_sum), so the result
+// has the same bits; what differs is who adds:
+// the 16-byte column quads of ALL rows of an entry are dealt over the workgroups back to back (a slab's [M][Kcols] block is
+// contiguous: a wave reads 1 KiB runs), so no thread of a column block idles behind Kcols = 384 or 128, and the leftover
+// k-row's M sums get workgroups of their own behind the quads'.
+#define WW_MAX_RED 16
+struct WwRedEntry {
+  const float* slab;        // [ksplit][256][Kcols]
+  const float* slab_extra;  // [ksplit][256][2]
+  float* w[2];
+  int ksplit, Kcols, K_main, K, n_extra, M, n_x;
+  int quad_blocks;          // workgroups of 64 column quads: ⌈M·Kcols/4 / 64⌉; the leftover sums follow, 256 per workgroup
+  WwOut x[4];
+};
+struct WwRedParams { WwRedEntry e[WW_MAX_RED]; };
+__device__ __forceinline__ void ww_dst(const WwRedEntry& e, int si, int& out, int& off, int& sc, int& sm) {
+  // (field by field through ww_pick: an entry is picked from the table by blockIdx.z, and under the one chain of ww_dst(WwParams)
+  // the compiler copied the whole table to scratch — 2312 B, occupancy 8 -> 7; the batched launch is not latency-bound by its tail)
+  auto field = [&](int WwOut::*f) { return ww_pick(e.x, si, [f](const WwOut& o) { return o.*f; }); };
+  out = field(&WwOut::out); off = field(&WwOut::out_off); sc = field(&WwOut::out_sc); sm = field(&WwOut::out_sm);
+}
+
+__global__ __launch_bounds__(256) void wn_wgrad_reduce_many_kernel(WwRedParams p) {
+  __shared__ float4 part[4][64];
+  const WwRedEntry& e = p.e[blockIdx.z];
+  const int bx = blockIdx.x;
+  auto plain = [](float v, long long, int, int) { return v; };
+  if (bx >= e.quad_blocks) {                               // (uniform) the leftover k-rows: one thread per (row, leftover row)
+    const int it = (bx - e.quad_blocks) * 256 + threadIdx.x;
+    if (e.K_main < e.K && it < e.M * e.n_extra) {
+      const int m = it / e.n_extra, j = it - m * e.n_extra;
+      ww_scatter(e, m, e.K_main + j, ww_extra_sum(e.slab_extra + (long long)m * 2 + j, e.ksplit), plain);
+    }
+    return;
+  }
+  const int qpr = e.Kcols >> 2;                            // quads per row (Kcols is a multiple of 128)
+  const int quad = bx * 64 + (threadIdx.x & 63);
+  // (quad·4 = row m·Kcols + column kk0 of slab 0)
+  ww_quad_sum(e.slab + (long long)quad * 4, (long long)WW_MROWS * e.Kcols, e.ksplit, quad < e.M * qpr, part, [&](const float (&tv)[4]) {
     const int m = quad / qpr, kk0 = (quad - m * qpr) * 4;
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      if (kk0 + j < e.K_main) ww_scatter_entry(e, m, kk0 + j, tv[j]);
-  }
+      if (kk0 + j < e.K_main) ww_scatter(e, m, kk0 + j, tv[j], plain);
+  });
 }
 
 // ------------------------------------------------------------------------------------------------ host side
@@ -614,6 +686,37 @@ extern "C" int fst_wn_last_route(int32_t out[FST_WN_ROUTE_LEN]) {
   return g_wn_route[0] != 0 ? 0 : -1;
 }
 
+// The K split: the chip's CUs over the n_groups workgroups of a K slice, at most `clamp` slices (the tiles there are), at least `floor`.
+static int ww_ksplit(int n_groups, int clamp, int floor) {
+  int ks = fst_cu_count_or(256) / n_groups;
+  if (ks > clamp) ks = clamp;
+  if (ks < floor) ks = floor;
+  return ks;
+}
+
+// What every WwParams geometry ends with, given M, K, K_main, n_extra, xr, mul and n_groups: the staged rows, the slab row, the
+// tiles of B sequences of L samples and the K split over n_sets operand sets (every set has a workgroup of its own).
+static void ww_tiles_and_split(WwParams* p, int B, int L, int n_sets) {
+  p->RX = p->xr * (1 + p->mul) + (p->n_extra ? 8 : 0);
+  p->Kcols = p->n_groups * p->xr;
+  p->B = B; p->L = L;
+  p->tiles_per_seq = L / WW_TT;
+  p->n_tiles = B * p->tiles_per_seq;
+  p->ksplit = ww_ksplit(p->n_groups, p->n_tiles * n_sets, n_sets);
+  p->n_sets = n_sets;
+}
+
+// floats of the workspace: the slabs [ksplit][256][Kcols] and, behind them, the leftover k-row's [ksplit][256][2]
+static int64_t ww_slab_floats(const WwParams& p) { return (int64_t)p.ksplit * WW_MROWS * (p.Kcols + 2); }
+
+// refuses (in the name of the entry point `who`) a workspace smaller than that, or binds slab / slab_extra to it
+static int ww_bind_workspace(WwParams& p, float* workspace, int64_t workspace_floats, const char* who) {
+  FST_REQUIRE(workspace_floats >= ww_slab_floats(p), "%s: workspace of %lld floats is too small", who, (long long)workspace_floats);
+  p.slab = workspace;
+  p.slab_extra = workspace + (long long)p.ksplit * WW_MROWS * p.Kcols;
+  return 0;
+}
+
 // geometry shared by the size query and the launchers; kind 0 = in_layer + cond_layer, 1 = res_skip
 static int ww_geometry(int kind, int B, int L, int n, int h, int last, int n_sets, WwParams* p) {
   const int KT = kind == 0 ? 3 : 2;
@@ -626,17 +729,7 @@ static int ww_geometry(int kind, int B, int L, int n, int h, int last, int n_set
   const int kb = (p->K_main + 31) / 32;
   p->n_groups = (kb + 2 * KT - 1) / (2 * KT);
   p->mul = kind == 1;
-  p->RX = p->xr * (1 + p->mul) + (p->n_extra ? 8 : 0);
-  p->Kcols = p->n_groups * p->xr;
-  p->B = B; p->L = L;
-  p->tiles_per_seq = L / WW_TT;
-  p->n_tiles = B * p->tiles_per_seq;
-  const int cus = fst_cu_count_or(256);
-  int ks = cus / p->n_groups;
-  if (ks > p->n_tiles * n_sets) ks = p->n_tiles * n_sets;
-  if (ks < n_sets) ks = n_sets;                                    // every operand set has a workgroup of its own
-  p->ksplit = ks;
-  p->n_sets = n_sets;
+  ww_tiles_and_split(p, B, L, n_sets);
   return KT;
 }
 
@@ -655,7 +748,7 @@ extern "C" int64_t fst_wn_wgrad_workspace_floats(int kind, int B, int L, int n, 
   if (!fst_wn_wgrad_ok(kind, B, L, n, h, 4)) return -1;                        // (the workspace does not depend on the dilation)
   WwParams p;
   ww_geometry(kind, B, L, n, h, last, WW_MAX_SETS, &p);                        // (nor — above n_sets workgroups — on the set count)
-  return (int64_t)p.ksplit * WW_MROWS * (p.Kcols + 2);
+  return ww_slab_floats(p);
 }
 
 static int ww_launch(WwParams& p, int KT, void* stream, bool reduce = true) {
@@ -685,18 +778,34 @@ static int ww_launch(WwParams& p, int KT, void* stream, bool reduce = true) {
 // reads the k-row segments' output mapping only
 static void ww_in_segments(WwParams& p, int n, int h, int L, int dil, long long u0_bs) {
   p.n_dy = 1;
-  p.dy[0] = {{}, (long long)2 * n * L, 0, 2 * n, 0, 0, 0, 0, 0};
+  p.dy[0] = {{}, (long long)2 * n * L, 0, 0, {2 * n, 0, 0, 0, 0}};
   p.n_x = 4;
-  for (int tap = 0; tap < 3; ++tap) p.x[tap] = {{}, (long long)n * L, 0, n, (tap - 1) * dil, 0, tap, 3, 3 * n};
-  p.x[3] = {{}, u0_bs, 0, h, 0, 1, 0, 1, h};
+  for (int tap = 0; tap < 3; ++tap) p.x[tap] = {{}, (long long)n * L, 0, (tap - 1) * dil, {n, 0, tap, 3, 3 * n}};
+  p.x[3] = {{}, u0_bs, 0, 0, {h, 1, 0, 1, h}};
 }
 
 static void ww_rs_segments(WwParams& p, int n, int L, int last) {
   p.n_dy = last ? 1 : 2;
-  p.dy[0] = {{}, (long long)n * L, 0, n, 0, 0, 0, 0, 0};
-  p.dy[1] = {{}, (long long)n * L, 0, n, 0, 0, 0, 0, 0};
+  p.dy[0] = {{}, (long long)n * L, 0, 0, {n, 0, 0, 0, 0}};
+  p.dy[1] = {{}, (long long)n * L, 0, 0, {n, 0, 0, 0, 0}};
   p.n_x = 1;
-  p.x[0] = {{}, (long long)2 * n * L, (long long)n * L, n, 0, 0, 0, 1, n};   // t rows; the s rows n·L floats further
+  p.x[0] = {{}, (long long)2 * n * L, (long long)n * L, 0, {n, 0, 0, 1, n}};   // t rows; the s rows n·L floats further
+}
+
+// What fst_wn_wgrad_in / _rs (`who`; kind 0 / 1) share once each has cleared the route and checked its own operands and shape: the
+// set count, the workspace, the geometry (left in p with the workspace bound) and every set's pointers in the n_ops lists `ops`.
+static int ww_prologue(const char* who, int kind, const float* const* const* ops, int n_ops, int n_sets, float* workspace,
+                       int64_t workspace_floats, int B, int L, int n, int h, int last, WwParams& p, int& KT) {
+  FST_REQUIRE(n_sets >= 1 && n_sets <= WW_MAX_SETS, "%s: %d operand sets (1..%d)", who, n_sets, WW_MAX_SETS);
+  FST_REQUIRE(fst_aligned16(workspace), "%s: operands must be 16-byte aligned", who);
+  KT = ww_geometry(kind, B, L, n, h, last, n_sets, &p);
+  if (int rc = ww_bind_workspace(p, workspace, workspace_floats, who)) return rc;
+  for (int s = 0; s < n_sets; ++s)
+    for (int k = 0; k < n_ops; ++k) {
+      FST_REQUIRE(ops[k][s], "%s: null operand in set %d", who, s);
+      FST_REQUIRE(fst_aligned16(ops[k][s]), "%s: operands must be 16-byte aligned", who);
+    }
+  return 0;
 }
 
 // reduce = false (fst_wn_wgrad_in_slabs): the slabs stay in the workspace for fst_wn_wgrad_reduce_many, dw_in / dw_cond are not used
@@ -705,28 +814,23 @@ static int ww_in(const float* const* dg, const float* const* a, const float* con
                  int64_t numel_a, void* stream, bool reduce) {
   fst_wn_clear_route();
   FST_REQUIRE(dg && a && u0 && workspace && (!reduce || (dw_in && dw_cond)), "fst_wn_wgrad_in: null operand");
-  FST_REQUIRE(n_sets >= 1 && n_sets <= WW_MAX_SETS, "fst_wn_wgrad_in: %d operand sets (1..%d)", n_sets, WW_MAX_SETS);
   const int served = fst_wn_wgrad_ok(0, B, L, n, h, dil);
   FST_REQUIRE(served == 1 || (served == 2 && a_slack), "fst_wn_wgrad_in: unsupported shape B=%d L=%d n=%d h=%d dil=%d (needs L %% 32 == 0, "
               "n < 128, h <= 32, and dil %% 4 == 0 or — with 16 readable bytes either side of a — dil < 4)", B, L, n, h, dil);
   FST_REQUIRE((long long)B * n * L == (long long)numel_a, "fst_wn_wgrad_in: B*n*L does not match the element count %lld of a", (long long)numel_a);
   FST_REQUIRE(B == 1 || u0_bs >= (int64_t)h * L, "fst_wn_wgrad_in: u0 batch stride %lld < h*L", (long long)u0_bs);
-  FST_REQUIRE(u0_bs % 4 == 0 && fst_aligned16(workspace), "fst_wn_wgrad_in: operands must be 16-byte aligned");
+  FST_REQUIRE(u0_bs % 4 == 0, "fst_wn_wgrad_in: operands must be 16-byte aligned");
   WwParams p = {};
-  const int KT = ww_geometry(0, B, L, n, h, 0, n_sets, &p);
-  FST_REQUIRE(workspace_floats >= (int64_t)p.ksplit * WW_MROWS * (p.Kcols + 2), "fst_wn_wgrad_in: workspace of %lld floats is too small",
-              (long long)workspace_floats);
+  int KT;
+  const float* const* const ops[3] = {dg, a, u0};
+  if (int rc = ww_prologue("fst_wn_wgrad_in", 0, ops, 3, n_sets, workspace, workspace_floats, B, L, n, h, 0, p, KT)) return rc;
   ww_in_segments(p, n, h, L, dil, (long long)u0_bs);
   for (int s = 0; s < n_sets; ++s) {
-    FST_REQUIRE(dg[s] && a[s] && u0[s], "fst_wn_wgrad_in: null operand in set %d", s);
-    FST_REQUIRE(fst_aligned16(dg[s]) && fst_aligned16(a[s]) && fst_aligned16(u0[s]), "fst_wn_wgrad_in: operands must be 16-byte aligned");
     p.dy[0].ptr[s] = dg[s];
     for (int tap = 0; tap < 3; ++tap) p.x[tap].ptr[s] = a[s];
     p.x[3].ptr[s] = u0[s];
   }
   p.misaligned = dil % 4 != 0;
-  p.slab = workspace;
-  p.slab_extra = workspace + (long long)p.ksplit * WW_MROWS * p.Kcols;
   p.w[0] = dw_in; p.w[1] = dw_cond;
   return ww_launch(p, KT, stream, reduce);
 }
@@ -747,24 +851,18 @@ static int ww_rs(const float* const* d_a, const float* const* d_out, const float
                  int64_t workspace_floats, int last, int B, int L, int n, int64_t numel_a, void* stream, bool reduce) {
   fst_wn_clear_route();
   FST_REQUIRE(d_out && ts && (dw_rs || !reduce) && workspace && (last || d_a), "fst_wn_wgrad_rs: null operand");
-  FST_REQUIRE(n_sets >= 1 && n_sets <= WW_MAX_SETS, "fst_wn_wgrad_rs: %d operand sets (1..%d)", n_sets, WW_MAX_SETS);
   FST_REQUIRE(fst_wn_wgrad_ok(1, B, L, n, 0, 4), "fst_wn_wgrad_rs: unsupported shape B=%d L=%d n=%d (needs L %% 32 == 0, n < 128)", B, L, n);
   FST_REQUIRE((long long)B * n * L == (long long)numel_a, "fst_wn_wgrad_rs: B*n*L does not match the element count %lld", (long long)numel_a);
-  FST_REQUIRE(fst_aligned16(workspace), "fst_wn_wgrad_rs: operands must be 16-byte aligned");
   WwParams p = {};
-  const int KT = ww_geometry(1, B, L, n, 0, last, n_sets, &p);
-  FST_REQUIRE(workspace_floats >= (int64_t)p.ksplit * WW_MROWS * (p.Kcols + 2), "fst_wn_wgrad_rs: workspace of %lld floats is too small",
-              (long long)workspace_floats);
+  int KT;
+  const float* const* const ops[3] = {d_out, ts, d_a};     // (no d_a on the last layer)
+  if (int rc = ww_prologue("fst_wn_wgrad_rs", 1, ops, last ? 2 : 3, n_sets, workspace, workspace_floats, B, L, n, 0, last, p, KT)) return rc;
   ww_rs_segments(p, n, L, last);
   for (int s = 0; s < n_sets; ++s) {
-    FST_REQUIRE(d_out[s] && ts[s] && (last || d_a[s]), "fst_wn_wgrad_rs: null operand in set %d", s);
-    FST_REQUIRE(fst_aligned16(d_out[s]) && fst_aligned16(ts[s]) && (last || fst_aligned16(d_a[s])), "fst_wn_wgrad_rs: operands must be 16-byte aligned");
     if (last) p.dy[0].ptr[s] = d_out[s];
     else { p.dy[0].ptr[s] = d_a[s]; p.dy[1].ptr[s] = d_out[s]; }
     p.x[0].ptr[s] = ts[s];
   }
-  p.slab = workspace;
-  p.slab_extra = workspace + (long long)p.ksplit * WW_MROWS * p.Kcols;
   p.w[0] = dw_rs; p.w[1] = nullptr;
   return ww_launch(p, KT, stream, reduce);
 }
@@ -779,6 +877,14 @@ extern "C" int fst_wn_wgrad_rs_slabs(const float* const* d_a, const float* const
                                      float* workspace, int64_t workspace_floats, int last, int B, int L, int n, int64_t numel_a,
                                      void* stream) {
   return ww_rs(d_a, d_out, ts, n_sets, nullptr, workspace, workspace_floats, last, B, L, n, numel_a, stream, false);
+}
+
+// what the reduction reads of a WwParams whose segments, workspace and outputs are filled in
+static WwRedEntry ww_red_entry(const WwParams& p) {
+  WwRedEntry e = {p.slab, p.slab_extra, {p.w[0], p.w[1]}, p.ksplit, p.Kcols, p.K_main, p.K, p.n_extra, p.M, p.n_x,
+                  (p.M * (p.Kcols / 4) + 63) / 64, {}};
+  for (int i = 0; i < p.n_x; ++i) e.x[i] = p.x[i].o;
+  return e;
 }
 
 // One launch adds the slab sets that up to 16 fst_wn_wgrad_in_slabs / _rs_slabs calls left in their workspaces (the layers of one
@@ -803,17 +909,13 @@ extern "C" int fst_wn_wgrad_reduce_many(const int32_t* kind, const int32_t* last
     WwParams p = {};
     const int lastj = kind[j] == 1 && last[j];
     ww_geometry(kind[j], B, L, n, h, lastj, n_sets[j], &p);
-    FST_REQUIRE(workspace_floats[j] >= (int64_t)p.ksplit * WW_MROWS * (p.Kcols + 2),
-                "fst_wn_wgrad_reduce_many: workspace %d of %lld floats is too small", j, (long long)workspace_floats[j]);
+    char who[48];
+    snprintf(who, sizeof who, "fst_wn_wgrad_reduce_many: entry %d", j);
+    if (int rc = ww_bind_workspace(p, workspace[j], workspace_floats[j], who)) return rc;
     if (kind[j] == 0) ww_in_segments(p, n, h, L, 4, 0);
     else ww_rs_segments(p, n, L, lastj);
-    WwRedEntry& e = rp.e[j];
-    e.slab = workspace[j];
-    e.slab_extra = workspace[j] + (long long)p.ksplit * WW_MROWS * p.Kcols;
-    e.w[0] = dw0[j]; e.w[1] = kind[j] == 0 ? dw1[j] : nullptr;
-    e.ksplit = p.ksplit; e.Kcols = p.Kcols; e.K_main = p.K_main; e.K = p.K; e.n_extra = p.n_extra; e.M = p.M; e.n_x = p.n_x;
-    for (int i = 0; i < p.n_x; ++i) e.x[i] = {p.x[i].rows, p.x[i].out, p.x[i].out_off, p.x[i].out_sc, p.x[i].out_sm};
-    e.quad_blocks = (p.M * (p.Kcols / 4) + 63) / 64;
+    p.w[0] = dw0[j]; p.w[1] = kind[j] == 0 ? dw1[j] : nullptr;
+    const WwRedEntry& e = rp.e[j] = ww_red_entry(p);
     const unsigned blocks = (unsigned)e.quad_blocks + (unsigned)((p.K_main < p.K ? p.M * p.n_extra : 0) + 255) / 256;
     if (blocks > gx) gx = blocks;
   }
@@ -828,14 +930,19 @@ extern "C" int fst_wn_wgrad_reduce_many(const int32_t* kind, const int32_t* last
 // RandomLayer's feature-side GEMM (C_DAN.py:21: [B, 25 600] × the fixed [25 600, 1024] Gaussian, kept transposed) and its data
 // gradient ([B, 1024] × the matrix as it is) are both of this form; the 105 MB matrix is read once from HBM by the LDS-DMA ring,
 // the K split leaves partial slabs that the reduce kernel adds in a fixed order (no atomics) while applying the layer's epilogue.
+static void nt_geometry(int M, int N, int K, WwParams* p) {
+  p->M = M; p->K = N; p->K_main = N; p->n_extra = 0;
+  p->xr = 128;
+  p->n_groups = ((N + 31) / 32 + 3) / 4;
+  p->mul = 0;
+  ww_tiles_and_split(p, 1, K, 1);
+}
+
 extern "C" int64_t fst_nt_gemm_workspace_floats(int M, int N, int K) {
   if (!(M > 0 && M <= WW_MROWS && N > 0 && K > 0 && K % WW_TT == 0)) return -1;
-  const int n_groups = ((N + 31) / 32 + 3) / 4;
-  const int cus = fst_cu_count_or(256);
-  int ks = cus / n_groups;
-  if (ks > K / WW_TT) ks = K / WW_TT;
-  if (ks < 1) ks = 1;
-  return (int64_t)ks * WW_MROWS * (n_groups * 128 + 2);
+  WwParams p = {};
+  nt_geometry(M, N, K, &p);
+  return ww_slab_floats(p);
 }
 
 extern "C" int fst_nt_gemm(const float* A, const float* Bm, float* C, float* workspace, int64_t workspace_floats, int M, int N, int K,
@@ -848,29 +955,12 @@ extern "C" int fst_nt_gemm(const float* A, const float* Bm, float* C, float* wor
   FST_REQUIRE((epi_p == nullptr) == (epi_r1 == nullptr) && (epi_p == nullptr || epi_ncls > 0) && (epi_p != nullptr || epi_raw == nullptr),
               "fst_nt_gemm: the epilogue takes p [M][ncls] and r1 [ncls][N] together (and the raw product only with them)");
   WwParams p = {};
-  p.M = M; p.K = N; p.K_main = N; p.n_extra = 0;
-  p.xr = 128;
-  p.n_groups = ((N + 31) / 32 + 3) / 4;
-  p.mul = 0;
-  p.RX = p.xr;
-  p.Kcols = p.n_groups * p.xr;
-  p.B = 1; p.L = K;
-  p.tiles_per_seq = K / WW_TT;
-  p.n_tiles = p.tiles_per_seq;
-  const int cus = fst_cu_count_or(256);
-  int ks = cus / p.n_groups;
-  if (ks > p.n_tiles) ks = p.n_tiles;
-  if (ks < 1) ks = 1;
-  p.ksplit = ks;
-  p.n_sets = 1;
-  FST_REQUIRE(workspace_floats >= (int64_t)p.ksplit * WW_MROWS * (p.Kcols + 2), "fst_nt_gemm: workspace of %lld floats is too small",
-              (long long)workspace_floats);
+  nt_geometry(M, N, K, &p);
+  if (int rc = ww_bind_workspace(p, workspace, workspace_floats, "fst_nt_gemm")) return rc;
   p.n_dy = 1;
-  p.dy[0] = {{A, nullptr, nullptr}, 0, 0, M, 0, 0, 0, 0, 0};
+  p.dy[0] = {{A, nullptr, nullptr}, 0, 0, 0, {M, 0, 0, 0, 0}};
   p.n_x = 1;
-  p.x[0] = {{Bm, nullptr, nullptr}, 0, 0, N, 0, 0, 0, 1, N};              // C[m][n] at w[0][m·N + n]
-  p.slab = workspace;
-  p.slab_extra = workspace + (long long)p.ksplit * WW_MROWS * p.Kcols;
+  p.x[0] = {{Bm, nullptr, nullptr}, 0, 0, 0, {N, 0, 0, 1, N}};            // C[m][n] at w[0][m·N + n]
   p.w[0] = C; p.w[1] = nullptr;
   p.epi_p = epi_p; p.epi_r1 = epi_r1; p.epi_ncls = epi_ncls; p.epi_scale = epi_scale; p.epi_raw = epi_raw;
   // one K slice of all 256 rows whose slab [256][n_groups·128] IS the output [M][N] (the data gradient of the random layer):
@@ -904,24 +994,14 @@ static void tap_geometry(int B, int L, int M, int C, int ntaps, WwParams* p) {
   p->xr = 192;
   p->n_groups = ((p->K + 31) / 32 + 5) / 6;
   p->mul = 0;
-  p->RX = p->xr;
-  p->Kcols = p->n_groups * p->xr;
-  p->B = B; p->L = L;
-  p->tiles_per_seq = L / WW_TT;
-  p->n_tiles = B * p->tiles_per_seq;
-  const int cus = fst_cu_count_or(256);
-  int ks = cus / p->n_groups;
-  if (ks > p->n_tiles) ks = p->n_tiles;
-  if (ks < 1) ks = 1;
-  p->ksplit = ks;
-  p->n_sets = 1;
+  ww_tiles_and_split(p, B, L, 1);
 }
 
 extern "C" int64_t fst_tap_wgrad_workspace_floats(int B, int L, int M, int C, int ntaps) {
   if (!fst_tap_wgrad_ok(B, L, M, C, ntaps, 4, 0)) return -1;
   WwParams p = {};
   tap_geometry(B, L, M, C, ntaps, &p);
-  return (int64_t)p.ksplit * WW_MROWS * (p.Kcols + 2);
+  return ww_slab_floats(p);
 }
 
 extern "C" int fst_tap_wgrad(const float* dy, const float* x, float* dw, float* workspace, int64_t workspace_floats, int B, int L, int M,
@@ -937,19 +1017,16 @@ extern "C" int fst_tap_wgrad(const float* dy, const float* x, float* dw, float* 
   FST_REQUIRE(fst_aligned16(dy) && fst_aligned16(x) && fst_aligned16(workspace), "fst_tap_wgrad: operands must be 16-byte aligned");
   WwParams p = {};
   tap_geometry(B, L, M, C, ntaps, &p);
-  FST_REQUIRE(workspace_floats >= (int64_t)p.ksplit * WW_MROWS * (p.Kcols + 2), "fst_tap_wgrad: workspace of %lld floats is too small",
-              (long long)workspace_floats);
+  if (int rc = ww_bind_workspace(p, workspace, workspace_floats, "fst_tap_wgrad")) return rc;
   p.n_dy = 1;
-  p.dy[0] = {{dy, nullptr, nullptr}, (long long)M * L, 0, M, 0, 0, 0, 0, 0};
+  p.dy[0] = {{dy, nullptr, nullptr}, (long long)M * L, 0, 0, {M, 0, 0, 0, 0}};
   p.n_x = ntaps;
   p.misaligned = 0;
   for (int tap = 0; tap < ntaps; ++tap) {
     const int sh = tap * dil - pad_left;
-    p.x[tap] = {{x, nullptr, nullptr}, (long long)C * L, 0, C, sh, 0, tap, ntaps, C * ntaps};    // dW[m][c][tap] at m·C·ntaps + c·ntaps + tap
+    p.x[tap] = {{x, nullptr, nullptr}, (long long)C * L, 0, sh, {C, 0, tap, ntaps, C * ntaps}};    // dW[m][c][tap] at m·C·ntaps + c·ntaps + tap
     if (sh % 4 != 0) p.misaligned = 1;
   }
-  p.slab = workspace;
-  p.slab_extra = workspace + (long long)p.ksplit * WW_MROWS * p.Kcols;
   p.w[0] = dw; p.w[1] = nullptr;
   return ww_launch(p, 3, stream);
 }
@@ -1014,14 +1091,14 @@ __global__ __launch_bounds__(512, 2) void tz_wgrad_kernel(TzParams p) {
   const int g = blockIdx.y, L = p.L;
   const char* const zero16 = reinterpret_cast<const char*>(ww_zero16);
 
-  // ---- LDS-DMA sources.  dy: instruction i = wave + 8k fills LDS rows 8i .. 8i+7 of the slot (lane → row, piece: ww_dma_row)
+  // ---- LDS-DMA sources.  dy: instruction i = wave + 8k fills LDS rows 8i .. 8i+7 of the slot (lane → row, piece: ww_dma_lane)
   const int m_base = blockIdx.z * 128;
   const int M_here = p.m_halves > 1 ? min(128, p.M - m_base) : p.M;
   const float* dsrc[NDW];
 #pragma unroll
   for (int k = 0; k < NDW; ++k) {
-    const int r = ww_dma_row(wave_s + 8 * k, lane), q = (lane ^ r) & 7;
-    dsrc[k] = p.dy + ((long long)(m_base + (r < M_here ? r : 0)) * L + 4 * q);
+    const WwDmaLane m = ww_dma_lane(wave_s + 8 * k, lane);
+    dsrc[k] = p.dy + ((long long)(m_base + (m.r < M_here ? m.r : 0)) * L + 4 * m.q);
   }
   // the window of channel CW·g + wave (waves < CW): piece `lane` (< 40) of the 160 samples from t0 − P4
   const bool has_x = wave_s < CW;                          // wave-uniform
@@ -1053,27 +1130,22 @@ __global__ __launch_bounds__(512, 2) void tz_wgrad_kernel(TzParams p) {
   };
 
   f32x16 acc[2][3];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  zero_acc(acc);
 
-  const int tile_begin = (int)(((long long)blockIdx.x * p.n_tiles) / p.ksplit);
-  const int tile_end = (int)(((long long)(blockIdx.x + 1) * p.n_tiles) / p.ksplit);
+  int tile_begin, tile_end;
+  ww_tile_range(blockIdx.x, p.ksplit, p.n_tiles, tile_begin, tile_end);
   const int m_blocks = (M_here + 31) >> 5;
   const int k_blocks = (p.K + 31) >> 5;                    // live 32-shift blocks (<= 3)
   const bool ch_live = CW * g + wk < p.C;
 
-  // ---- per-lane LDS offsets.  A fragments as in wn_wgrad_kernel: row block·32 + l31 (LDS row l31 ^ ((l31 >> 3) & 1)), unit
-  // 2·ks + half: hi = first piece, lo = second; the block index and the slot are immediates / one scalar
-  const int row_l = (l31 ^ ((l31 >> 3) & 1)) << 7, sw = l31 & 7;
+  // ---- per-lane LDS offsets.  A fragments as in wn_wgrad_kernel (ww_frag_lane): hi = first piece, lo = second of the lane's
+  // unit; the block index and the slot are immediates / one scalar
+  const WwFragLane fl = ww_frag_lane(l31, half);
   unsigned a_lane[2][2];
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-    for (int j = 0; j < 2; ++j) a_lane[ks][j] = ((wm * 2 * 32) << 7) + row_l + ((((4 * ks + 2 * half + j) ^ sw) & 7) << 4);
+    for (int j = 0; j < 2; ++j) a_lane[ks][j] = ((wm * 2 * 32) << 7) + fl.row + fl.piece[ks][j];
   // B fragments: shift s = 32·sb + l31 at samples 16·ks + 8·half + 0..7 → window offset o = off0 + s + 16·ks + 8·half: copy o & 7
   // (the same for every ks, sb), unit o >> 3
   const int o0 = p.off0 + l31 + 8 * half;
@@ -1239,11 +1311,8 @@ __global__ __launch_bounds__(512, 2) void tz_wgrad_kernel(TzParams p) {
   for (int i = 0; i < 2; ++i) {
     if (wm * 2 + i >= m_blocks) break;
 #pragma unroll
-    for (int sb = 0; sb < 3; ++sb) {
-      float* dst = slab + (long long)(m_base + (wm * 2 + i) * 32 + 4 * half) * p.Kcols + g * (CW * 96) + wk * 96 + sb * 32 + l31;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) dst[(long long)((r & 3) + 8 * (r >> 2)) * p.Kcols] = acc[i][sb][r];
-    }
+    for (int sb = 0; sb < 3; ++sb)
+      ww_store_tile(slab + (long long)(m_base + (wm * 2 + i) * 32 + 4 * half) * p.Kcols + g * (CW * 96) + wk * 96 + sb * 32 + l31, p.Kcols, acc[i][sb]);
   }
 }
 
@@ -1274,11 +1343,7 @@ static int tz_geometry(int B, int L, int M, int C, int K, int pad, TzParams* p) 
   p->Kcols = p->n_groups * TZ_CW * 96;
   p->tiles_per_seq = L / WW_TT;
   p->n_tiles = B * p->tiles_per_seq;
-  const int cus = fst_cu_count_or(256);
-  int ks = cus / (p->n_groups * p->m_halves);
-  if (ks > p->n_tiles) ks = p->n_tiles;
-  if (ks < 1) ks = 1;
-  p->ksplit = ks;
+  p->ksplit = ww_ksplit(p->n_groups * p->m_halves, p->n_tiles, 1);
   return MP;
 }
 

@@ -1042,16 +1042,36 @@ def _sets(x) -> list:
     return list(x) if isinstance(x, (list, tuple)) else [x]
 
 
+def _wgrad_sets(who: str, *operands) -> List[list]:
+    """The operands of ``wn_wgrad_in`` / ``wn_wgrad_rs`` as equally long lists of 1..3 operand sets (one tensor = one set)."""
+    sets = [_sets(o) for o in operands]
+    if not (1 <= len(sets[0]) <= WN_WGRAD_MAX_SETS and all(len(s) == len(sets[0]) for s in sets)):
+        raise ValueError(f"{who}: {'/'.join(str(len(s)) for s in sets)} operand sets (1..{WN_WGRAD_MAX_SETS}, equally many)")
+    return sets
+
+
+def _wn_wgrad_launch(kind: int, last: bool, ns: int, B: int, L: int, n: int, h: int, device, targets: tuple, slabs: Optional[list],
+                     launch, timer: tuple) -> None:
+    """One weight-gradient product of ``wn_wgrad_in`` / ``wn_wgrad_rs`` on a fresh workspace, inside the timer bracket:
+    ``launch(lib, ws_ptr, ws_n, keep_slabs)`` issues it; with ``slabs`` the slab set and its ``targets`` are appended to the list."""
+    lib = _lib.load()
+    ws_n = lib.fst_wn_wgrad_workspace_floats(kind, B, L, n, h, int(last))
+    ws = torch.empty(ws_n, device=device, dtype=torch.float32)
+    t0 = KERNEL_TIMER.begin() if KERNEL_TIMER is not None else None
+    launch(lib, ptr(ws), ws_n, slabs is not None)
+    if slabs is not None:
+        slabs.append((kind, bool(last), ns, ws) + targets)
+    if t0 is not None:
+        KERNEL_TIMER.end(timer[0], t0, timer[1], timer[2])
+
+
 def wn_wgrad_in(dg, a, u0, dw_in: Tensor, dw_cond: Tensor, n: int, h: int, dil: int, slabs: Optional[list] = None) -> None:
     """dw_in [2n, n, 3] = Σ dg ⊗ a(t + (τ−1)·dil),  dw_cond [2n, h, 1] = Σ dg ⊗ u0 — written in place (fst_wn_wgrad_in).
     ``dg``, ``a``, ``u0``: one tensor each, or equally long lists of up to 3 same-shaped operand sets whose gradients are summed
     by the one launch (the applications of a WN in a train step).
     ``slabs``: the product only (fst_wn_wgrad_in_slabs) — its slab set is appended to the list, and the targets are written when
     ``wn_wgrad_reduce_many`` is called on it."""
-    lib = _lib.load()
-    dgs, as_, u0s = _sets(dg), _sets(a), _sets(u0)
-    if not (1 <= len(dgs) <= WN_WGRAD_MAX_SETS and len(as_) == len(dgs) and len(u0s) == len(dgs)):
-        raise ValueError(f"wn_wgrad_in: {len(dgs)}/{len(as_)}/{len(u0s)} operand sets (1..{WN_WGRAD_MAX_SETS}, equally many)")
+    dgs, as_, u0s = _wgrad_sets("wn_wgrad_in", dg, a, u0)
     B, _, L = dgs[0].shape
     u0_bs, _ = _ncl(u0s[0], "u0")
     numel = _same_numel(*as_)
@@ -1065,29 +1085,24 @@ def wn_wgrad_in(dg, a, u0, dw_in: Tensor, dw_cond: Tensor, n: int, h: int, dil: 
     for t, sh in ((dw_in, (2 * n, n, 3)), (dw_cond, (2 * n, h, 1))):
         if tuple(t.shape) != sh or not t.is_contiguous() or t.dtype != torch.float32:
             raise ValueError(f"wn_wgrad_in: gradient target of shape {tuple(t.shape)}, expected contiguous {sh}")
-    ws_n = lib.fst_wn_wgrad_workspace_floats(0, B, L, n, h, 0)
-    ws = torch.empty(ws_n, device=dgs[0].device, dtype=torch.float32)
     ns = len(dgs)
-    t0 = KERNEL_TIMER.begin() if KERNEL_TIMER is not None else None
-    if slabs is not None:
-        check(lib.fst_wn_wgrad_in_slabs(_ptr_sets(dgs), _ptr_sets(as_), _ptr_sets(u0s), ns, u0_bs, ptr(ws), ws_n, B, L, n, h, dil,
-                                        int(slack), numel, stream_ptr()), "fst_wn_wgrad_in_slabs")
-        slabs.append((0, False, ns, ws, dw_in, dw_cond))
-    else:
-        check(lib.fst_wn_wgrad_in(_ptr_sets(dgs), _ptr_sets(as_), _ptr_sets(u0s), ns, u0_bs, ptr(dw_in), ptr(dw_cond), ptr(ws), ws_n,
-                                  B, L, n, h, dil, int(slack), numel, stream_ptr()), "fst_wn_wgrad_in")
-    if t0 is not None:
-        KERNEL_TIMER.end("wn_wgrad_kernel<2, 3> bf3", t0, 2.0 * ns * B * L * 2 * n * (3 * n + h), 4.0 * ns * B * L * (2 * n + n + h))
+
+    def launch(lib, ws, ws_n, keep_slabs):
+        sets = (_ptr_sets(dgs), _ptr_sets(as_), _ptr_sets(u0s), ns, u0_bs)
+        shape = (B, L, n, h, dil, int(slack), numel, stream_ptr())
+        if keep_slabs:
+            check(lib.fst_wn_wgrad_in_slabs(*sets, ws, ws_n, *shape), "fst_wn_wgrad_in_slabs")
+        else:
+            check(lib.fst_wn_wgrad_in(*sets, ptr(dw_in), ptr(dw_cond), ws, ws_n, *shape), "fst_wn_wgrad_in")
+
+    _wn_wgrad_launch(0, False, ns, B, L, n, h, dgs[0].device, (dw_in, dw_cond), slabs, launch,
+                     ("wn_wgrad_kernel<2, 3> bf3", 2.0 * ns * B * L * 2 * n * (3 * n + h), 4.0 * ns * B * L * (2 * n + n + h)))
 
 
 def wn_wgrad_rs(d_a, d_out, ts, dw_rs: Tensor, last: bool, n: int, slabs: Optional[list] = None) -> None:
     """dw_rs [2n | n, n, 1] = Σ [d_a ; d_out] ⊗ (t·s), acts = t·s re-formed from the saved gate halves ts [B, 2n, L] (fst_wn_wgrad_rs).
     One tensor each or lists of up to 3 operand sets, and ``slabs``, as ``wn_wgrad_in``; ``d_a`` is None exactly on the last layer."""
-    lib = _lib.load()
-    d_outs, tss = _sets(d_out), _sets(ts)
-    d_as = [None] * len(d_outs) if d_a is None else _sets(d_a)
-    if not (1 <= len(d_outs) <= WN_WGRAD_MAX_SETS and len(tss) == len(d_outs) and len(d_as) == len(d_outs)):
-        raise ValueError(f"wn_wgrad_rs: {len(d_as)}/{len(d_outs)}/{len(tss)} operand sets (1..{WN_WGRAD_MAX_SETS}, equally many)")
+    d_as, d_outs, tss = _wgrad_sets("wn_wgrad_rs", [None] * len(_sets(d_out)) if d_a is None else d_a, d_out, ts)
     B, _, L = d_outs[0].shape
     numel = _same_numel(*d_outs, *[t for t in d_as if t is not None])
     M = n if last else 2 * n
@@ -1096,19 +1111,18 @@ def wn_wgrad_rs(d_a, d_out, ts, dw_rs: Tensor, last: bool, n: int, slabs: Option
             raise ValueError("wn_wgrad_rs: ts must be contiguous [B, 2n, L]; d_a is None exactly on the last layer")
     if tuple(dw_rs.shape) != (M, n, 1) or not dw_rs.is_contiguous() or dw_rs.dtype != torch.float32:
         raise ValueError(f"wn_wgrad_rs: gradient target of shape {tuple(dw_rs.shape)}, expected contiguous {(M, n, 1)}")
-    ws_n = lib.fst_wn_wgrad_workspace_floats(1, B, L, n, 0, int(last))
-    ws = torch.empty(ws_n, device=d_outs[0].device, dtype=torch.float32)
     ns = len(d_outs)
-    t0 = KERNEL_TIMER.begin() if KERNEL_TIMER is not None else None
-    if slabs is not None:
-        check(lib.fst_wn_wgrad_rs_slabs(None if last else _ptr_sets(d_as), _ptr_sets(d_outs), _ptr_sets(tss), ns, ptr(ws), ws_n,
-                                        int(last), B, L, n, numel, stream_ptr()), "fst_wn_wgrad_rs_slabs")
-        slabs.append((1, bool(last), ns, ws, dw_rs, None))
-    else:
-        check(lib.fst_wn_wgrad_rs(None if last else _ptr_sets(d_as), _ptr_sets(d_outs), _ptr_sets(tss), ns, ptr(dw_rs), ptr(ws), ws_n,
-                                  int(last), B, L, n, numel, stream_ptr()), "fst_wn_wgrad_rs")
-    if t0 is not None:
-        KERNEL_TIMER.end("wn_wgrad_kernel<2, 2> bf3", t0, 2.0 * ns * B * L * M * n, 4.0 * ns * B * L * (M + 2 * n))
+
+    def launch(lib, ws, ws_n, keep_slabs):
+        sets = (None if last else _ptr_sets(d_as), _ptr_sets(d_outs), _ptr_sets(tss), ns)
+        shape = (int(last), B, L, n, numel, stream_ptr())
+        if keep_slabs:
+            check(lib.fst_wn_wgrad_rs_slabs(*sets, ws, ws_n, *shape), "fst_wn_wgrad_rs_slabs")
+        else:
+            check(lib.fst_wn_wgrad_rs(*sets, ptr(dw_rs), ws, ws_n, *shape), "fst_wn_wgrad_rs")
+
+    _wn_wgrad_launch(1, last, ns, B, L, n, 0, d_outs[0].device, (dw_rs, None), slabs, launch,
+                     ("wn_wgrad_kernel<2, 2> bf3", 2.0 * ns * B * L * M * n, 4.0 * ns * B * L * (M + 2 * n)))
 
 
 WN_WGRAD_MAX_REDUCE = 16     # (WW_MAX_RED of csrc/wn_wgrad.hip)
@@ -1129,42 +1143,34 @@ def wn_wgrad_reduce_many(slabs: list, B: int, L: int, n: int, h: int) -> None:
     del slabs[:]
 
 
-def dense_tap_wgrad(dy: Tensor, x: Tensor, dw: Tensor, M: int, C: int, K: int, pad_left: int) -> None:
-    """dw [M, C, K] = Σ_{b,t} dy[b, m, t]·x[b, c, t + k − pad_left] for every tap k < K <= 96 — written in place (fst_dense_tap_wgrad)."""
+def _tap_wgrad(who: str, taps_name: str, timer_key: str, dy: Tensor, x: Tensor, dw: Tensor, M: int, C: int, taps: int, *geometry) -> None:
+    """``tap_wgrad`` / ``dense_tap_wgrad`` (``who``): dw [M, C, taps] from dy [B, M, L] and x [B, C, L] on a fresh workspace —
+    ``fst_<who>(dy, x, dw, ws, ws_n, B, L, M, C, taps, *geometry, numel_dy, numel_x, stream)``."""
     lib = _lib.load()
     B, _, L = dy.shape
     if tuple(dy.shape) != (B, M, L) or tuple(x.shape) != (B, C, L) or not (dy.is_contiguous() and x.is_contiguous()):
-        raise ValueError(f"dense_tap_wgrad: dy {tuple(dy.shape)} / x {tuple(x.shape)} must be contiguous [B, {M}, L] / [B, {C}, L]")
-    if tuple(dw.shape) != (M, C, K) or not dw.is_contiguous() or dw.dtype != torch.float32:
-        raise ValueError(f"dense_tap_wgrad: gradient target of shape {tuple(dw.shape)}, expected contiguous {(M, C, K)}")
-    ws_n = lib.fst_dense_tap_wgrad_workspace_floats(B, L, M, C, K)
+        raise ValueError(f"{who}: dy {tuple(dy.shape)} / x {tuple(x.shape)} must be contiguous [B, {M}, L] / [B, {C}, L]")
+    if tuple(dw.shape) != (M, C, taps) or not dw.is_contiguous() or dw.dtype != torch.float32:
+        raise ValueError(f"{who}: gradient target of shape {tuple(dw.shape)}, expected contiguous {(M, C, taps)}")
+    ws_n = getattr(lib, f"fst_{who}_workspace_floats")(B, L, M, C, taps)
     if ws_n <= 0:
-        raise ValueError(f"dense_tap_wgrad: unsupported shape B={B} L={L} M={M} C={C} K={K}")
+        raise ValueError(f"{who}: unsupported shape B={B} L={L} M={M} C={C} {taps_name}={taps}")
     ws = torch.empty(ws_n, device=dy.device, dtype=torch.float32)
     t0 = KERNEL_TIMER.begin() if KERNEL_TIMER is not None else None
-    check(lib.fst_dense_tap_wgrad(ptr(dy), ptr(x), ptr(dw), ptr(ws), ws_n, B, L, M, C, K, pad_left, dy.numel(), x.numel(), stream_ptr()),
-          "fst_dense_tap_wgrad")
+    check(getattr(lib, f"fst_{who}")(ptr(dy), ptr(x), ptr(dw), ptr(ws), ws_n, B, L, M, C, taps, *geometry, dy.numel(), x.numel(),
+                                     stream_ptr()), f"fst_{who}")
     if t0 is not None:
-        KERNEL_TIMER.end(f"tz_wgrad_kernel M={M} C={C} bf3", t0, 2.0 * B * L * M * C * K, 4.0 * B * L * (M + C))
+        KERNEL_TIMER.end(timer_key, t0, 2.0 * B * L * M * C * taps, 4.0 * B * L * (M + C))
+
+
+def dense_tap_wgrad(dy: Tensor, x: Tensor, dw: Tensor, M: int, C: int, K: int, pad_left: int) -> None:
+    """dw [M, C, K] = Σ_{b,t} dy[b, m, t]·x[b, c, t + k − pad_left] for every tap k < K <= 96 — written in place (fst_dense_tap_wgrad)."""
+    _tap_wgrad("dense_tap_wgrad", "K", f"tz_wgrad_kernel M={M} C={C} bf3", dy, x, dw, M, C, K, pad_left)
 
 
 def tap_wgrad(dy: Tensor, x: Tensor, dw: Tensor, M: int, C: int, ntaps: int, dil: int, pad_left: int) -> None:
     """dw [M, C, ntaps] = Σ_{b,t} dy[b, m, t]·x[b, c, t + τ·dil − pad_left] — written in place (fst_tap_wgrad: time-as-k kernel)."""
-    lib = _lib.load()
-    B, _, L = dy.shape
-    if tuple(dy.shape) != (B, M, L) or tuple(x.shape) != (B, C, L) or not (dy.is_contiguous() and x.is_contiguous()):
-        raise ValueError(f"tap_wgrad: dy {tuple(dy.shape)} / x {tuple(x.shape)} must be contiguous [B, {M}, L] / [B, {C}, L]")
-    if tuple(dw.shape) != (M, C, ntaps) or not dw.is_contiguous() or dw.dtype != torch.float32:
-        raise ValueError(f"tap_wgrad: gradient target of shape {tuple(dw.shape)}, expected contiguous {(M, C, ntaps)}")
-    ws_n = lib.fst_tap_wgrad_workspace_floats(B, L, M, C, ntaps)
-    if ws_n <= 0:
-        raise ValueError(f"tap_wgrad: unsupported shape B={B} L={L} M={M} C={C} ntaps={ntaps}")
-    ws = torch.empty(ws_n, device=dy.device, dtype=torch.float32)
-    t0 = KERNEL_TIMER.begin() if KERNEL_TIMER is not None else None
-    check(lib.fst_tap_wgrad(ptr(dy), ptr(x), ptr(dw), ptr(ws), ws_n, B, L, M, C, ntaps, dil, pad_left, int(has_slack(x)), dy.numel(),
-                            x.numel(), stream_ptr()), "fst_tap_wgrad")
-    if t0 is not None:
-        KERNEL_TIMER.end("tap_wgrad (wn_wgrad_kernel<2, 3>) bf3", t0, 2.0 * B * L * M * C * ntaps, 4.0 * B * L * (M + C))
+    _tap_wgrad("tap_wgrad", "ntaps", "tap_wgrad (wn_wgrad_kernel<2, 3>) bf3", dy, x, dw, M, C, ntaps, dil, pad_left, int(has_slack(x)))
 
 
 def _ptr_sets(ts: Sequence[Tensor]):
