@@ -8,6 +8,10 @@
 //   fst_guard_copy_multi   a multi-tensor copy in 4-byte words that runs unconditionally (verdict == NULL: the SAVE of state that
 //                          cannot be guarded at its writer) or only when (*verdict != 0) == when (the ROLL-BACK).
 //   (the optimiser updates behind the verdict word are in optim.hip, beside the update bodies they share)
+//   fst_sumsq_multi        the same walk over the same tensors, adding x*x instead of counting: per-group L2 norms of the gradients,
+//                          and from them and a device vector of limits the factors that clip each group and then the whole.
+//   fst_scale_multi        x *= coef[group] in place, the factors read from device memory when the kernel runs: a replayed
+//                          hipGraph clips by what its own scan found, and a workgroup whose factor is 1.0f touches nothing.
 //
 // House style of optim.hip: the pointer tuples ride BY VALUE in the kernel arguments, at most 64 per launch, so a captured launch
 // carries them; no float atomics and no zero fill: every workgroup of the scan writes its own slot with a plain store (and plain
@@ -169,6 +173,188 @@ extern "C" int fst_guard_copy_multi(void* const* dst_host, const void* const* sr
     bx = bx < 1 ? 1 : (bx > NF_SLOTS ? NF_SLOTS : bx);
     hipLaunchKernelGGL(guard_copy_multi_kernel, dim3((unsigned)bx, (unsigned)a.n), dim3(256), 0, (hipStream_t)stream, a,
                        (const int*)verdict_dev, when);
+    FST_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+// ---- gradient norms and clipping: the scan's walk with x*x in place of the count, and the scale that applies what it decided.
+// The slot array has the scan's layout in fp32: per tensor NF_REC words, its group id (as a float: exact below 32), then the
+// partial sums of its up to NF_SLOTS workgroups.  No float atomics: a thread adds its elements in one fma chain in index order, a
+// wave adds its lanes in a xor butterfly (commutative adds: every lane ends with the same word), lane 0 of wave 0 adds the four
+// wave sums as (0 + 1) + (2 + 3); the finaliser adds in fp64 in a fixed order.  Same inputs, same words.
+#define GC_GROUPS 32                // groups; norms and limits carry one more word, the total
+
+__global__ __launch_bounds__(256) void sumsq_multi_kernel(NonfiniteArgs a, float* __restrict__ slots) {
+  const int t = blockIdx.y;
+  if (t >= a.n) return;
+  const float* __restrict__ x = a.x[t];
+  const int n = a.numel[t];
+  int head = (int)(((16u - (unsigned)((uintptr_t)x & 15u)) & 15u) >> 2);
+  head = head < n ? head : n;
+  const int nv = (n - head) >> 2;
+  const int tail0 = head + 4 * nv;
+  const float4* __restrict__ xv = (const float4*)(x + head);
+  float s = 0.0f;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < nv; i += gridDim.x * 256) {
+    const float4 q = xv[i];
+    s = __builtin_fmaf(q.x, q.x, s); s = __builtin_fmaf(q.y, q.y, s); s = __builtin_fmaf(q.z, q.z, s); s = __builtin_fmaf(q.w, q.w, s);
+  }
+  if (blockIdx.x == 0) {
+    if ((int)threadIdx.x < head) s = __builtin_fmaf(x[threadIdx.x], x[threadIdx.x], s);
+    if ((int)threadIdx.x < n - tail0) s = __builtin_fmaf(x[tail0 + threadIdx.x], x[tail0 + threadIdx.x], s);
+  }
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  __shared__ float wave_sum[4];
+  if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float* rec = slots + (size_t)(a.base + t) * NF_REC;
+    if (blockIdx.x == 0) rec[0] = (float)a.group[t];
+    rec[1 + blockIdx.x] = (wave_sum[0] + wave_sum[1]) + (wave_sum[2] + wave_sum[3]);
+    for (int k = blockIdx.x + gridDim.x; k < NF_SLOTS; k += gridDim.x) rec[1 + k] = 0.0f;   // slots no workgroup of this launch owns
+  }
+}
+
+// one workgroup.  A tensor's slots are added in slot order and a group's tensors in tensor order, all in fp64 (256 tensors at a
+// time: one thread per tensor, then one thread per group).  Thread 0 then does the arithmetic of optim.clip_coefficients on the
+// fp32 norms it reports, in fp64, and rounds the product once.
+__global__ __launch_bounds__(256) void sumsq_finalize_kernel(const float* __restrict__ slots, int n_tensors,
+                                                             const float* __restrict__ limits, float* __restrict__ norms,
+                                                             float* __restrict__ coef) {
+  __shared__ double tsum[256];
+  __shared__ int tgroup[256];
+  __shared__ double gsum[GC_GROUPS];
+  __shared__ double cg[GC_GROUPS];
+  double acc = 0.0;                                                  // threads 0..31: the group's sum of squares
+  for (int base = 0; base < n_tensors; base += 256) {
+    const int i = base + (int)threadIdx.x;
+    if (i < n_tensors) {
+      const float* rec = slots + (size_t)i * NF_REC;
+      double s = 0.0;
+      for (int k = 0; k < NF_SLOTS; ++k) s += (double)rec[1 + k];
+      tsum[threadIdx.x] = s;
+      tgroup[threadIdx.x] = (int)rec[0] & (GC_GROUPS - 1);
+    }
+    __syncthreads();
+    if (threadIdx.x < GC_GROUPS) {
+      const int m = n_tensors - base < 256 ? n_tensors - base : 256;
+      for (int j = 0; j < m; ++j)
+        if (tgroup[j] == (int)threadIdx.x) acc += tsum[j];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < GC_GROUPS) gsum[threadIdx.x] = acc;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double all = 0.0;
+  int bad = 0;
+  for (int g = 0; g < GC_GROUPS; ++g) {
+    all += gsum[g];
+    const float ng = (float)sqrt(gsum[g]);
+    norms[g] = ng;
+    bad |= nonfinite_bits(__float_as_uint(ng));
+  }
+  const float total = (float)sqrt(all);
+  norms[GC_GROUPS] = total;
+  bad |= nonfinite_bits(__float_as_uint(total));
+  double rest = 0.0;                                                 // what the per-group caps leave, squared
+  for (int g = 0; g < GC_GROUPS; ++g) {
+    const double ng = (double)norms[g];
+    cg[g] = fmin(1.0, (double)limits[g] / (ng + 1e-6));
+    rest += (cg[g] * ng) * (cg[g] * ng);
+  }
+  const double c = fmin(1.0, (double)limits[GC_GROUPS] / (sqrt(rest) + 1e-6));
+  for (int g = 0; g < GC_GROUPS; ++g) coef[g] = bad ? 1.0f : (float)(cg[g] * c);
+}
+
+static int check_group_tensors(const char* who, const void* const* x_host, const int64_t* numel_host, const int32_t* group_host, int n_tensors) {
+  FST_REQUIRE(n_tensors >= 0 && n_tensors < (1 << 24) && (n_tensors == 0 || (x_host && numel_host && group_host)), "%s: bad arguments", who);
+  for (int i = 0; i < n_tensors; ++i) {                              // all of them before the first launch
+    FST_REQUIRE(x_host[i] && ((uintptr_t)x_host[i] & 3) == 0 && numel_host[i] > 0 && numel_host[i] < (1LL << 31),
+                "%s: tensor %d: null or misaligned pointer, or bad element count", who, i);
+    FST_REQUIRE(group_host[i] >= 0 && group_host[i] < GC_GROUPS, "%s: tensor %d: group %d is not in 0..31", who, i, group_host[i]);
+  }
+  return 0;
+}
+
+// workgroups per tensor of a launch: one 16-byte access per thread for its largest tensor, within NF_SLOTS (grid-stride beyond)
+static int group_launch_bx(const int64_t* numel_host, int n) {
+  long long most = 0;
+  for (int i = 0; i < n; ++i) most = most > numel_host[i] ? most : numel_host[i];
+  const int bx = (int)((most + 1023) / 1024);
+  return bx < 1 ? 1 : (bx > NF_SLOTS ? NF_SLOTS : bx);
+}
+
+extern "C" int64_t fst_sumsq_slots(int n_tensors) { return fst_nonfinite_slots(n_tensors); }
+
+extern "C" int fst_sumsq_multi(const float* const* x_host, const int64_t* numel_host, const int32_t* group_host, int n_tensors,
+                               float* slots_dev, int64_t slots_len, const float* limits_dev, float* norms_dev, float* coef_dev,
+                               void* stream) {
+  if (check_group_tensors("fst_sumsq_multi", (const void* const*)x_host, numel_host, group_host, n_tensors)) return -1;
+  FST_REQUIRE(limits_dev && norms_dev && coef_dev && (n_tensors == 0 || slots_dev) &&
+              (((uintptr_t)limits_dev | (uintptr_t)norms_dev | (uintptr_t)coef_dev | (uintptr_t)slots_dev) & 3) == 0,
+              "fst_sumsq_multi: null or misaligned limits, norms, coefficients or slots");
+  FST_REQUIRE(slots_len >= fst_sumsq_slots(n_tensors), "fst_sumsq_multi: %lld slots, %lld needed", (long long)slots_len,
+              (long long)fst_sumsq_slots(n_tensors));
+  for (int base = 0; base < n_tensors; base += NF_MAX_T) {
+    NonfiniteArgs a;
+    a.n = n_tensors - base < NF_MAX_T ? n_tensors - base : NF_MAX_T;
+    a.base = base;
+    for (int i = 0; i < a.n; ++i) { a.x[i] = x_host[base + i]; a.numel[i] = (int)numel_host[base + i]; a.group[i] = group_host[base + i]; }
+    hipLaunchKernelGGL(sumsq_multi_kernel, dim3((unsigned)group_launch_bx(numel_host + base, a.n), (unsigned)a.n), dim3(256), 0,
+                       (hipStream_t)stream, a, slots_dev);
+    FST_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(sumsq_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)slots_dev, n_tensors, limits_dev,
+                     norms_dev, coef_dev);
+  FST_LAUNCH_CHECK();
+  return 0;
+}
+
+struct ScaleArgs {
+  float* x[NF_MAX_T];
+  int numel[NF_MAX_T];
+  int group[NF_MAX_T];
+  int n;
+};
+static_assert(sizeof(ScaleArgs) + sizeof(const float*) <= 4096, "kernel arguments: 4 KB at most");
+
+// the scan's geometry, writing: coef[group] is one uniform load per workgroup, and a workgroup whose factor is exactly 1.0f
+// returns before its first load of x — an unclipped step keeps its gradients' bits and pays no memory pass here
+__global__ __launch_bounds__(256) void scale_multi_kernel(ScaleArgs a, const float* __restrict__ coef) {
+  const int t = blockIdx.y;
+  if (t >= a.n) return;
+  const float c = coef[a.group[t]];
+  if (c == 1.0f) return;
+  float* __restrict__ x = a.x[t];
+  const int n = a.numel[t];
+  int head = (int)(((16u - (unsigned)((uintptr_t)x & 15u)) & 15u) >> 2);
+  head = head < n ? head : n;
+  const int nv = (n - head) >> 2;
+  const int tail0 = head + 4 * nv;
+  float4* __restrict__ xv = (float4*)(x + head);
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < nv; i += gridDim.x * 256) {
+    float4 q = xv[i];
+    q.x *= c; q.y *= c; q.z *= c; q.w *= c;
+    xv[i] = q;
+  }
+  if (blockIdx.x == 0) {
+    if ((int)threadIdx.x < head) x[threadIdx.x] *= c;
+    if ((int)threadIdx.x < n - tail0) x[tail0 + threadIdx.x] *= c;
+  }
+}
+
+extern "C" int fst_scale_multi(float* const* x_host, const int64_t* numel_host, const int32_t* group_host, int n_tensors,
+                               const float* coef_dev, void* stream) {
+  if (check_group_tensors("fst_scale_multi", (const void* const*)x_host, numel_host, group_host, n_tensors)) return -1;
+  FST_REQUIRE(coef_dev && ((uintptr_t)coef_dev & 3) == 0, "fst_scale_multi: null or misaligned coefficients");
+  for (int base = 0; base < n_tensors; base += NF_MAX_T) {
+    ScaleArgs a;
+    a.n = n_tensors - base < NF_MAX_T ? n_tensors - base : NF_MAX_T;
+    for (int i = 0; i < a.n; ++i) { a.x[i] = x_host[base + i]; a.numel[i] = (int)numel_host[base + i]; a.group[i] = group_host[base + i]; }
+    hipLaunchKernelGGL(scale_multi_kernel, dim3((unsigned)group_launch_bx(numel_host + base, a.n), (unsigned)a.n), dim3(256), 0,
+                       (hipStream_t)stream, a, coef_dev);
     FST_LAUNCH_CHECK();
   }
   return 0;

@@ -21,6 +21,11 @@ Anomaly guard.  ``count_nonfinite`` counts NaN / inf elements of many tensors pe
 ``AnomalyGuard``, leaves its verdict there; ``rmsprop_step_many(opts, guard=...)`` and ``SharedStepAdam.step(guard=...)`` then
 launch the same updates behind that verdict word (``fst_*_multi_guard``): a step with a non-finite gradient writes nothing, and
 nothing waits for the host.
+
+Gradient norms and clipping.  ``sumsq_norms`` takes the L2 norms of many tensors per group on the device and leaves, next to them,
+the factors that cap each group and then the whole (``clip_coefficients`` is their definition; ``GradClip`` holds the device
+words); ``scale_by_group`` multiplies the tensors by those factors, read when the kernels run: what
+``torch.nn.utils.clip_grad_norm_`` does with a host decision, usable inside a replayed graph.
 """
 from __future__ import annotations
 
@@ -355,3 +360,139 @@ def guard_copy(dst: Sequence[torch.Tensor], src: Sequence[torch.Tensor], guard: 
                                                 _i64_array([d.numel() * d.element_size() // 4 for d, _ in pairs]), len(pairs),
                                                 None if guard is None else guard.verdict.data_ptr(), int(bool(when)),
                                                 _lib.stream_ptr()), "fst_guard_copy_multi")
+
+
+# ---- gradient norms and clipping: per-group L2 norms and the factors that cap them, decided and applied on the device
+def clip_coefficients(norms, limits):
+    """The factors ``fst_sumsq_multi``'s finaliser derives from 32 per-group L2 norms and 33 limits (``limits[32]`` caps the norm
+    over all groups; ``inf`` = no limit), in fp64 — the definition of the clipping, and what the CPU tests compare with torch:
+
+        c_g = min(1, limits[g] / (norms[g] + 1e-6))                            each group by its own cap, as clip_grad_norm_ would
+        c   = min(1, limits[32] / (sqrt(Σ_g (c_g·norms[g])²) + 1e-6))          then the whole by what the group caps left of it
+        coef[g] = c_g · c
+
+    The constant and the clamp are ``torch.nn.utils.clip_grad_norm_``'s.  One deliberate difference: if any norm (or their total)
+    is not finite, every factor is 1.0 where torch would multiply every gradient by NaN — the gradients are left alone, the norms
+    are reported as they came out, and the anomaly guard or the user decides about the step.  ``norms``: 32 values, or 33 of
+    which the last (the total before clipping, as the kernel reports it) only takes part in that test.  Returns a float64 tensor
+    of 32 factors; the kernel rounds the same product to fp32."""
+    norms = torch.as_tensor(norms, dtype=torch.float64).reshape(-1)
+    limits = torch.as_tensor(limits, dtype=torch.float64).reshape(-1)
+    if norms.numel() not in (MAX_GROUPS, MAX_GROUPS + 1) or limits.numel() != MAX_GROUPS + 1:
+        raise ValueError(f"clip_coefficients: {norms.numel()} norms and {limits.numel()} limits; {MAX_GROUPS} (or {MAX_GROUPS + 1}) and "
+                         f"{MAX_GROUPS + 1} wanted")
+    n = norms[:MAX_GROUPS].tolist()
+    total = float(torch.sqrt(sum(v * v for v in norms[:MAX_GROUPS])))
+    if not all(np.isfinite(v) for v in n + norms[MAX_GROUPS:].tolist() + [total]):
+        return torch.ones(MAX_GROUPS, dtype=torch.float64)
+    lim = limits.tolist()
+    c_g = [min(1.0, float(np.float64(lim[g]) / np.float64(n[g] + 1e-6))) for g in range(MAX_GROUPS)]
+    rest = 0.0
+    for g in range(MAX_GROUPS):
+        rest += (c_g[g] * n[g]) * (c_g[g] * n[g])
+    c = min(1.0, float(np.float64(lim[MAX_GROUPS]) / np.float64(float(np.sqrt(rest)) + 1e-6)))
+    return torch.tensor([c_g[g] * c for g in range(MAX_GROUPS)], dtype=torch.float64)
+
+
+class GradClip:
+    """The device words of the gradient clipping: ``limits`` (fp32[33]: a cap per group and, last, the cap on the norm over all
+    groups; ``inf`` = none), ``norms`` (fp32[33], the L2 norms of the last ``sumsq_norms``, last the total, before clipping),
+    ``coef`` (fp32[32], the factors of the last ``sumsq_norms``, 1 where nothing is clipped) and the scan's slot array.
+    ``limits_host`` is what ``limits`` holds, known without reading it back; ``set_limits`` changes both with one stream-ordered
+    copy, which a graph replayed afterwards sees."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.limits_host = [float("inf")] * (MAX_GROUPS + 1)
+        self.limits = torch.full((MAX_GROUPS + 1,), float("inf"), dtype=torch.float32, device=device)
+        self.norms = torch.zeros(MAX_GROUPS + 1, dtype=torch.float32, device=device)
+        self.coef = torch.ones(MAX_GROUPS, dtype=torch.float32, device=device)
+        self._slots = None                                                    # scratch of the scan, grown outside captures
+
+    def slots(self, n_words: int) -> torch.Tensor:
+        if self._slots is None or self._slots.numel() < n_words:
+            if _capturing(self.limits):
+                raise RuntimeError("GradClip: the scan's slot array would have to grow inside a stream capture; run one eager step "
+                                   "of the same tensors first")
+            self._slots = torch.empty(max(n_words, 1), dtype=torch.float32, device=self.device)
+        return self._slots
+
+    def set_limits(self, limits: Sequence[float]) -> bool:
+        """``limits``: 33 caps (``inf`` = none; negative or NaN values are refused).  Copies them to the device if they differ from
+        what it holds, on the current stream and without waiting for it.  Returns whether anything changed."""
+        new = [_f32(v) for v in limits]
+        if len(new) != MAX_GROUPS + 1:
+            raise ValueError(f"GradClip.set_limits: {len(new)} limits, {MAX_GROUPS + 1} wanted")
+        if any(not v >= 0.0 for v in new):
+            raise ValueError("GradClip.set_limits: a limit must be a non-negative number or inf")
+        if new == self.limits_host:
+            return False
+        host = torch.tensor(new, dtype=torch.float32)
+        if self.limits.is_cuda:
+            host = host.pin_memory()                                          # a pageable source would make the copy wait for the device
+        self.limits.copy_(host, non_blocking=True)
+        self.limits_host = new
+        return True
+
+
+def _group_tensors(who: str, tensors, groups):
+    from . import _lib
+    if len(tensors) != len(groups):
+        raise ValueError(f"{who}: {len(tensors)} tensors, {len(groups)} group ids")
+    for i, (t, g) in enumerate(zip(tensors, groups)):
+        if not 0 <= int(g) < MAX_GROUPS:
+            raise ValueError(f"{who}: tensor {i}: group {g} is not in range({MAX_GROUPS})")
+        _lib.require_gpu_tensor(t, f"{who}: tensor {i}")                       # no CPU fallback: a missing GPU is an error
+    return [(t, int(g)) for t, g in zip(tensors, groups) if t.numel() > 0]
+
+
+def _words(who: str, name: str, t: torch.Tensor, n: int) -> torch.Tensor:
+    from . import _lib
+    _lib.require_gpu_tensor(t, f"{who}: {name}")
+    if t.numel() < n or not t.is_contiguous():
+        raise ValueError(f"{who}: {name} must be a contiguous float32 tensor of {n} elements, got {tuple(t.shape)} {t.dtype}")
+    return t
+
+
+@torch.no_grad()
+def sumsq_norms(tensors: Sequence[torch.Tensor], groups: Sequence[int], limits: torch.Tensor, out_norms: torch.Tensor,
+                out_coef: torch.Tensor, slots: Optional[torch.Tensor] = None) -> None:
+    """L2 norms of the fp32 GPU ``tensors`` per group (``groups[i]`` in 0..31) into ``out_norms`` (fp32[33], last the norm over all
+    groups) and the clipping factors of ``clip_coefficients(out_norms, limits)`` into ``out_coef`` (fp32[32]); ``limits`` is
+    fp32[33] on the device.  One ``fst_sumsq_multi`` launch per 64 tensors plus a finalising one, nothing waits for the device,
+    the tensors are only read and must be contiguous (a copy could not be scaled afterwards).  ``slots``: fp32 scratch of
+    ``fst_sumsq_slots(len(tensors))`` words (allocated here if None — not under capture).  Deterministic: the same values give the
+    same words.  A non-finite norm makes every factor 1.0 (see ``clip_coefficients``)."""
+    keep = _group_tensors("sumsq_norms", tensors, groups)
+    for name, t, n in (("limits", limits, MAX_GROUPS + 1), ("out_norms", out_norms, MAX_GROUPS + 1), ("out_coef", out_coef, MAX_GROUPS)):
+        _words("sumsq_norms", name, t, n)
+    if any(not t.is_contiguous() for t, _ in keep):
+        raise ValueError("sumsq_norms: the tensors must be contiguous")
+    from . import _lib
+    lib = _lib.load()
+    n_slots = int(lib.fst_sumsq_slots(len(keep)))
+    if slots is None:
+        slots = torch.empty(max(n_slots, 1), dtype=torch.float32, device=out_norms.device)
+    _words("sumsq_norms", "slots", slots, n_slots)
+    xs = [t for t, _ in keep]
+    _lib.check(lib.fst_sumsq_multi(_ptr_array(xs), _i64_array([x.numel() for x in xs]), (ctypes.c_int32 * len(xs))(*[g for _, g in keep]),
+                                   len(xs), slots.data_ptr(), slots.numel(), limits.data_ptr(), out_norms.data_ptr(),
+                                   out_coef.data_ptr(), _lib.stream_ptr()), "fst_sumsq_multi")
+
+
+@torch.no_grad()
+def scale_by_group(tensors: Sequence[torch.Tensor], groups: Sequence[int], coef: torch.Tensor) -> None:
+    """``tensors[i] *= coef[groups[i]]`` in place (fp32 GPU tensors, contiguous; ``coef`` fp32[32] on the device, read when the
+    kernels run): one ``fst_scale_multi`` launch per 64 tensors.  A tensor whose factor is exactly 1.0 is neither read nor
+    written: it keeps its bits, NaN payloads and −0 included."""
+    keep = _group_tensors("scale_by_group", tensors, groups)
+    _words("scale_by_group", "coef", coef, MAX_GROUPS)
+    if any(not t.is_contiguous() for t, _ in keep):
+        raise ValueError("scale_by_group: the tensors must be contiguous (a copy would be scaled in their place)")
+    if not keep:
+        return
+    from . import _lib
+    xs = [t for t, _ in keep]
+    _lib.check(_lib.load().fst_scale_multi(_ptr_array(xs), _i64_array([x.numel() for x in xs]),
+                                           (ctypes.c_int32 * len(xs))(*[g for _, g in keep]), len(xs), coef.data_ptr(),
+                                           _lib.stream_ptr()), "fst_scale_multi")

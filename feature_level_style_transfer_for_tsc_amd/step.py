@@ -19,6 +19,10 @@ on a trainer's optimisers and ``end_epoch`` steps the ones the reference steps. 
 Anomaly guard (``JointTrainer.enable_anomaly_guard()``): instead of the reference's ``torch.autograd.set_detect_anomaly(True)``
 (train_and_test.py:24), which cannot run under capture, a step whose update would consume a NaN or an inf is made a no-op on the
 trainer's state, decided on the device, in eager and in replayed steps alike.
+
+Gradient norms and clipping (``JointTrainer.enable_grad_clip()``): per-module L2 norms of the gradients the optimisers are about
+to read in every report, and caps per module and on the whole that scale those gradients in place — what
+``torch.nn.utils.clip_grad_norm_`` does with a host decision — computed and applied on the device, under graph replay too.
 """
 from __future__ import annotations
 
@@ -35,7 +39,8 @@ from .cdan import CDAN, RandomLayer
 from .cpc import CPC
 from . import dist as _dist
 from .dist import GradBucket
-from .optim import AnomalyGuard, FusedRMSprop, SharedStepAdam, count_nonfinite, guard_copy, push_lr, rmsprop_step_many
+from .optim import (MAX_GROUPS, AnomalyGuard, FusedRMSprop, GradClip, SharedStepAdam, count_nonfinite, guard_copy, push_lr,
+                    rmsprop_step_many, scale_by_group, sumsq_norms)
 from .os_cnn import OS_CNN, OS_CNN_res, build_layer_with_layer_parameter
 from .structure import generate_layer_parameter_list, layer_parameter_list_input_change, out_channels
 from .waveglow import WaveGlow, WaveGlowLoss
@@ -43,6 +48,7 @@ from .widgets import (AdversarialNetworkforCDAN, DimensionUnification, FeatureDi
                       ProbTransfer, wgan_loss)
 
 MAX_KERNEL_SIZE = 89                                                          # train_and_test.py:40
+_KEEP = object()                                                              # set_grad_clip: "leave this limit as it is"
 
 
 def specs_for(length: int, in_channel: int):
@@ -231,11 +237,12 @@ class JointTrainer:
     ANOMALY_GROUPS = MODULES + ("gradnorm", "losses", "buffers")
 
     def __init__(self, cfg: JointConfig, device, bucket: Optional[GradBucket] = None, fe_t_spec=None, clf_spec=None,
-                 fe_s_spec=None, sync: str = "ddp", device_hparams: bool = False, anomaly_guard: bool = False):
+                 fe_s_spec=None, sync: str = "ddp", device_hparams: bool = False, anomaly_guard: bool = False, grad_clip=None):
         """``sync`` (with a bucket): "ddp" = per-rank batch statistics (SURVEY §8e mode A); "global" = every
         batch-coupled quantity over the samples of all ranks (mode B, eager only) — N ranks reproduce the
         single-process step on the concatenated batch.  ``device_hparams``: ``enable_device_hparams()`` at once;
-        ``anomaly_guard``: ``enable_anomaly_guard()`` at once."""
+        ``anomaly_guard``: ``enable_anomaly_guard()`` at once.  ``grad_clip``: ``enable_grad_clip()`` at once — True for norms
+        only, a number for ``max_norm``, or a dict of its keyword arguments."""
         if sync not in ("ddp", "global"):
             raise ValueError(f"sync must be 'ddp' or 'global', got {sync!r}")
         self.cfg, self.device, self.bucket, self.sync = cfg, device, bucket, sync
@@ -291,6 +298,11 @@ class JointTrainer:
         self._guard_live = None                                               # ... (live, shadow) lists of the step's save
         self._guard_fwd = ()                                                  # ... fp32 buffers the forward writes, of that save
         self._guard_losses = ()                                               # ... loss scalars of a phase step, for the counts
+        self.grad_clip = False
+        self._clip: Optional[GradClip] = None                                 # grad_clip: limits, norms and factors on the device
+        self._clip_max: Optional[float] = None                                # ... the cap on the norm over all modules (None: none)
+        self._clip_per: Dict[str, float] = {}                                 # ... the caps per module
+        self._clip_masks: Dict[Tuple[str, ...], torch.Tensor] = {}            # ... which report entries a step's modules fill
         for mod in self.m.values():
             mod.train()
         # GradNorm differentiates the shared OS_blocks only: their convs keep weight gradients in partial passes
@@ -301,6 +313,13 @@ class JointTrainer:
             self.enable_device_hparams()
         if anomaly_guard:
             self.enable_anomaly_guard()
+        if grad_clip is not None and grad_clip is not False:
+            if grad_clip is True:
+                self.enable_grad_clip()
+            elif isinstance(grad_clip, dict):
+                self.enable_grad_clip(**grad_clip)
+            else:
+                self.enable_grad_clip(max_norm=grad_clip)
 
     # ------------------------------------------------------------------ anomaly guard: skip non-finite steps on the device
     def enable_anomaly_guard(self) -> None:
@@ -410,6 +429,89 @@ class JointTrainer:
 
     def _guard_report(self) -> Dict[str, torch.Tensor]:
         return {"skipped": self._guard.verdict[0].clone(), "anomaly": self._guard.counts[: len(self.ANOMALY_GROUPS)].clone()}
+
+    # ------------------------------------------------------------------ gradient norms and clipping on the device
+    def enable_grad_clip(self, max_norm: Optional[float] = None, per_module: Optional[Dict[str, float]] = None) -> None:
+        """From now on every step measures the L2 norm of the gradients per module and, where a limit is set, scales them in
+        place before the optimisers read them — on the device, with no host decision, in ``step``, ``capture`` / ``replay``,
+        ``phase_step`` and ``capture_phase`` / ``replay_phase``.  ``max_norm`` caps the norm over all modules the step updates,
+        ``per_module`` ({name in ``MODULES``: cap}) a module's own; None = no limit, so ``enable_grad_clip()`` alone only reports.
+        A module's cap is applied first, as ``torch.nn.utils.clip_grad_norm_(module.parameters(), cap)`` would, then ``max_norm``
+        to what the module caps leave (``optim.clip_coefficients`` is the arithmetic).
+
+        Groups are ``MODULES`` in order; only the modules the step updates take part (all of them in the joint step,
+        ``PHASES[phase]`` in a phase step) and of those the parameters that have a ``.grad``.  The GradNorm weights' gradients are
+        neither counted nor clipped.  The norms are taken after ``on_grads_ready`` — after the data-parallel all-reduce and the Q3
+        doubling: those of the gradients the optimisers consume, the same on every rank — and before the anomaly guard's scan,
+        which therefore sees the clipped gradients.  Unlike torch, a non-finite norm leaves every gradient alone (all factors 1):
+        the norms are reported as they came out and the anomaly guard, if on, skips the step.
+
+        Every report gains ``"grad_l2"`` (fp32 [len(MODULES) + 1]: per module, 0 for one the step does not update; last the norm
+        over all of them, before clipping) and ``"clip_coef"`` (fp32 [len(MODULES)]: the factor applied, exactly 1 where nothing was
+        clipped — those gradients keep their bits).  With no limit set the step computes the bits of the step without the mode.
+        ``set_grad_clip`` changes the limits at any time, under resident captures too.  Idempotent (a second call with arguments
+        sets those limits); raises while a joint or phase capture is resident, whose launches lack the two kernels."""
+        limits = self._clip_limits(max_norm, dict(per_module or {}))
+        if not self.grad_clip:
+            if self._graphs is not None or self._phase:
+                raise RuntimeError("enable_grad_clip(): a capture is resident; enable the mode before capture() / capture_phase()")
+            self._clip = GradClip(self.device)
+            for mods in (self.MODULES,) + tuple(self.PHASES.values()):
+                self._clip_masks[tuple(mods)] = torch.tensor([k in mods for k in self.MODULES], device=self.device)
+            self.grad_clip = True
+        elif max_norm is None and per_module is None:
+            return
+        self._clip_max, self._clip_per = max_norm, dict(per_module or {})
+        self._clip.set_limits(limits)
+
+    def set_grad_clip(self, max_norm=_KEEP, per_module=_KEEP) -> bool:
+        """Change the limits of ``enable_grad_clip`` (an argument left out keeps its current value, None removes the limit;
+        ``per_module`` replaces the whole mapping).  Legal while captures are resident: the host copy is updated and one
+        stream-ordered copy goes into the device limits, so a graph replayed afterwards clips by the new values with no re-capture
+        (as ``push_lr`` does for learning rates).  Returns whether the device limits changed."""
+        if not self.grad_clip:
+            raise RuntimeError("set_grad_clip(): call enable_grad_clip() first")
+        max_norm = self._clip_max if max_norm is _KEEP else max_norm
+        per_module = self._clip_per if per_module is _KEEP else dict(per_module or {})
+        limits = self._clip_limits(max_norm, per_module)
+        self._clip_max, self._clip_per = max_norm, dict(per_module)
+        return self._clip.set_limits(limits)
+
+    def _clip_limits(self, max_norm, per_module) -> List[float]:
+        """The 33 limits of the device vector: group g = MODULES[g], the last one the cap on the whole; inf = none."""
+        def cap(v, what):
+            if v is None:
+                return float("inf")
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not float(v) >= 0.0:
+                raise ValueError(f"grad clip: {what} must be a non-negative number or None, got {v!r}")
+            return float(v)
+        limits = [float("inf")] * (MAX_GROUPS + 1)
+        for k, v in per_module.items():
+            if k not in self.MODULES:
+                raise ValueError(f"grad clip: unknown module {k!r}; one of {self.MODULES}")
+            limits[self.MODULES.index(k)] = cap(v, f"the cap of {k!r}")
+        limits[MAX_GROUPS] = cap(max_norm, "max_norm")
+        return limits
+
+    def _clip_grads(self, modules) -> None:
+        """Norms of the gradients of ``modules`` (one group each), the factors their limits ask for, and the scaling: one read
+        pass, a finalising workgroup, and a second launch series that returns at once where the factor is 1."""
+        xs, gs = [], []
+        for k in modules:
+            for p in self.m[k].parameters():
+                if p.grad is not None:
+                    if not p.grad.is_contiguous():
+                        p.grad = p.grad.contiguous()
+                    xs.append(p.grad); gs.append(self.MODULES.index(k))
+        from . import _lib
+        c = self._clip
+        sumsq_norms(xs, gs, c.limits, c.norms, c.coef, c.slots(int(_lib.load().fst_sumsq_slots(len(xs)))))
+        scale_by_group(xs, gs, c.coef)
+
+    def _clip_report(self, modules) -> Dict[str, torch.Tensor]:
+        c, n = self._clip, len(self.MODULES)
+        return {"grad_l2": torch.cat([c.norms[:n], c.norms[MAX_GROUPS:]]),
+                "clip_coef": torch.where(self._clip_masks[tuple(modules)], c.coef[:n], torch.ones((), device=self.device))}
 
     # ------------------------------------------------------------------ schedules under graph replay
     def enable_device_hparams(self) -> None:
@@ -523,7 +625,7 @@ class JointTrainer:
         none of this across runs (utils.py:9-25 saves the classification modules only); a captured-graph trainer that
         cannot resume would be a gap of this build, not of the reference.  Once ``make_schedulers()`` has run, also
         "schedules": the eleven schedulers' state, CPC's learning rate (the RMSprops' are in their ``param_groups``), the epoch of
-        the last step and its loss coefficients."""
+        the last step and its loss coefficients.  With ``enable_grad_clip()`` on, also "grad_clip": its limits."""
         cpu = lambda t: t.detach().cpu().clone()
         cpc = self.opt_cpc
         noise = self.m["noise"]
@@ -554,6 +656,7 @@ class JointTrainer:
                {"schedules": {"schedulers": {k: s.state_dict() for k, s in self.schedulers.items()}, "epoch": self._sched_epoch,
                               "cpc_lr": [g["lr"] for g in cpc.param_groups],       # "opts" carry theirs in param_groups
                               "coefficients": None if self._sched_epoch is None else loss_coefficients(self._sched_epoch)}}),
+            **({"grad_clip": {"max_norm": self._clip_max, "per_module": dict(self._clip_per)}} if self.grad_clip else {}),
         }
 
     def load_state_dict(self, sd: dict) -> None:
@@ -603,6 +706,10 @@ class JointTrainer:
             if sd["schedules"]["epoch"] is not None:
                 self._set_epoch(sd["schedules"]["epoch"])
         push_lr(self._scheduled_opts())
+        if "grad_clip" in sd:                                                 # a checkpoint without the entry leaves the mode as it is
+            if not self.grad_clip:
+                self.enable_grad_clip()
+            self.set_grad_clip(max_norm=sd["grad_clip"]["max_norm"], per_module=sd["grad_clip"]["per_module"])
 
     def save_state(self, path: str) -> None:
         torch.save(self.state_dict(), path)
@@ -700,6 +807,8 @@ class JointTrainer:
         if self.bucket is not None:
             self.bucket.all_reduce(self.parameters())
         self._phase_update(phase)
+        if self._clip is not None:
+            report.update(self._clip_report(self.PHASES[phase]))
         if self._guard is not None:
             report.update(self._guard_report())
         return report
@@ -726,6 +835,8 @@ class JointTrainer:
         """Second half (after the gradient all-reduce of a data-parallel step): the phase's optimisers."""
         if self.on_grads_ready is not None:
             self.on_grads_ready()
+        if self._clip is not None:
+            self._clip_grads(self.PHASES[phase])
         if self._guard is not None:
             self._guard_scan(self.PHASES[phase], (), self._guard_losses)
             self._guard_losses = ()
@@ -782,13 +893,18 @@ class JointTrainer:
         main.wait_stream(side)
         torch.cuda.synchronize()
         # static report: the graphs' own outputs live in the shared pool, where a later capture may reuse what this one frees
-        keys = [k for k in keys if k not in ("skipped", "anomaly")]            # anomaly guard: static tensors of their own
+        keys = [k for k in keys if k not in ("skipped", "anomaly", "grad_l2", "clip_coef")]   # static tensors of their own
         out = torch.zeros(len(keys), device=dev)
         g_rep = {} if self._guard is None else {"skipped": torch.zeros((), dtype=torch.int32, device=dev),
                                                 "anomaly": torch.zeros(len(self.ANOMALY_GROUPS), dtype=torch.int32, device=dev)}
+        if self._clip is not None:
+            g_rep.update(grad_l2=torch.zeros(len(self.MODULES) + 1, device=dev), clip_coef=torch.ones(len(self.MODULES), device=dev))
 
         def update():
             self._phase_update(phase)
+            if self._clip is not None:
+                for k, v in self._clip_report(self.PHASES[phase]).items():
+                    g_rep[k].copy_(v)
             if self._guard is not None:
                 g_rep["skipped"].copy_(self._guard.verdict[0])
                 g_rep["anomaly"].copy_(self._guard.counts[: len(self.ANOMALY_GROUPS)])
@@ -970,6 +1086,8 @@ class JointTrainer:
             w.grad.copy_(g)
         if self.on_grads_ready is not None:
             self.on_grads_ready()
+        if self._clip is not None:
+            self._clip_grads(self.MODULES)
         if guard is not None:
             self._guard_scan(self.MODULES, (scal, self.w_t.grad, self.w_s.grad), [mid["report"][k] for k in mid["loss_keys"]])
             if first and int(guard.verdict) != 0:                             # the one host read: only a COMPLETED step sets them
@@ -995,6 +1113,8 @@ class JointTrainer:
         report = dict(mid["report"])
         report.update({"w_t": self.w_t.detach().clone(), "w_s": self.w_s.detach().clone(),
                        "norms_t": nt.detach(), "norms_s": ns.detach()})
+        if self._clip is not None:
+            report.update(self._clip_report(self.MODULES))
         if guard is not None:
             report.update(self._guard_report())
         return report

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FST_ABI_VERSION 21
+#define FST_ABI_VERSION 22
 
 int fst_version(void);
 const char* fst_last_error(void);
@@ -643,6 +643,30 @@ int fst_adam_multi_guard(float* const* p_host, const float* const* g_host, float
                          float beta2, float eps, const int32_t* verdict_dev, void* stream);
 int fst_guard_copy_multi(void* const* dst_host, const void* const* src_host, const int64_t* words_host, int n_tensors,
                          const int32_t* verdict_dev, int when, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Gradient norms and clipping on the device (ABI v22), so that a replayed hipGraph can report and bound its gradients (what
+ * torch.nn.utils.clip_grad_norm_ does with a host decision).  Tensors, groups, launch geometry, refusals and the slot discipline
+ * are nonfinite_multi's: fp32 tensors with 4-byte aligned pointers and 0 < element count < 2^31, group_host[i] in 0..31, at most 64
+ * tensors per launch, every entry validated on the host before the first launch.
+ * sumsq_multi only reads the tensors.  slots_dev is fp32 scratch of at least sumsq_slots(n_tensors) words that every call
+ * rewrites: per tensor a record of 65 words, its group id as a float and the partial sums of x*x of its up to 64 workgroups
+ * (one fp32 fma chain per thread, a fixed-order reduction per workgroup, no float atomics).  A finalising launch of one workgroup
+ * adds a tensor's slots in slot order and a group's tensors in call order in fp64 and writes
+ *   norms_dev[g]  = (float)sqrt(sum_g) for g in 0..31, norms_dev[32] = (float)sqrt(sum over all groups)      (fp32[33])
+ *   coef_dev[g]   = c_g * c                                                                                  (fp32[32])
+ * with c_g = min(1, limits_dev[g] / (norms_dev[g] + 1e-6)), c = min(1, limits_dev[32] / (sqrt(sum_g (c_g norms_dev[g])^2) + 1e-6)),
+ * computed in fp64 from the fp32 norms and rounded once; limits_dev is fp32[33], +inf = no limit.  If any of the 33 norms is not
+ * finite every coefficient is 1.0f (the norms are reported as they came out).  The same inputs give the same words on every run.
+ * n_tensors == 0 writes zero norms and unit coefficients.
+ * scale_multi multiplies tensor i in place by coef_dev[group_host[i]], read when the kernel RUNS; a workgroup whose coefficient is
+ * exactly 1.0f returns before it loads anything, so those tensors keep their bits.  Nothing outside [x, x + numel) is touched.
+ * ------------------------------------------------------------------------------------------- */
+int64_t fst_sumsq_slots(int n_tensors);
+int fst_sumsq_multi(const float* const* x_host, const int64_t* numel_host, const int32_t* group_host, int n_tensors,
+                    float* slots_dev, int64_t slots_len, const float* limits_dev, float* norms_dev, float* coef_dev, void* stream);
+int fst_scale_multi(float* const* x_host, const int64_t* numel_host, const int32_t* group_host, int n_tensors,
+                    const float* coef_dev, void* stream);
 
 #ifdef __cplusplus
 }
