@@ -12,6 +12,10 @@
 //                          and from them and a device vector of limits the factors that clip each group and then the whole.
 //   fst_scale_multi        x *= coef[group] in place, the factors read from device memory when the kernel runs: a replayed
 //                          hipGraph clips by what its own scan found, and a workgroup whose factor is 1.0f touches nothing.
+//   fst_ema_multi          avg = fma(w[group], live − avg, avg) over pairs of tensors: an exponential moving average of the weights
+//                          whose per-group weight a one-workgroup prologue derives, when it runs, from a device decay, a warm-up
+//                          count, the call's mask of active groups and the guard's verdict; w == 0 touches nothing.
+//   fst_swap_multi         exchanges pairs of tensors in place (the averages into the modules' storage for evaluation, and back).
 //
 // House style of optim.hip: the pointer tuples ride BY VALUE in the kernel arguments, at most 64 per launch, so a captured launch
 // carries them; no float atomics and no zero fill: every workgroup of the scan writes its own slot with a plain store (and plain
@@ -355,6 +359,165 @@ extern "C" int fst_scale_multi(float* const* x_host, const int64_t* numel_host, 
     for (int i = 0; i < a.n; ++i) { a.x[i] = x_host[base + i]; a.numel[i] = (int)numel_host[base + i]; a.group[i] = group_host[base + i]; }
     hipLaunchKernelGGL(scale_multi_kernel, dim3((unsigned)group_launch_bx(numel_host + base, a.n), (unsigned)a.n), dim3(256), 0,
                        (hipStream_t)stream, a, coef_dev);
+    FST_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+// ---- weight averaging (EMA) and the in-place exchange that puts the averages into the modules' own storage.  Both walk PAIRS of
+// tensors, tensor t of a launch on grid row t, in the scale's geometry.  The walk is written once (pair_walk) and instantiated for
+// 16-byte and for 4-byte units: a pair whose two pointers are both 16-byte aligned goes in quads and hands the up to three
+// elements behind its last quad to the dword walk; any other pair (a view that starts off a boundary, or two views that start
+// differently) goes in dwords altogether.  Nothing outside [a, a + numel) and [b, b + numel) is touched.
+#define EMA_GROUPS GC_GROUPS
+#define EMA_DECAY 0                 // the state block, in 4-byte words: decay (fp32)
+#define EMA_WARMUP 1                //   warm-up flag (int32)
+#define EMA_COUNT 2                 //   count[32] (int32): completed updates per group
+#define EMA_W (2 + EMA_GROUPS)      //   w[32] (fp32): the weight of this step
+#define EMA_WORDS (2 + 2 * EMA_GROUPS)
+
+struct PairArgs {
+  float* a[NF_MAX_T];
+  float* b[NF_MAX_T];
+  int numel[NF_MAX_T];
+  int group[NF_MAX_T];
+  int n;
+};
+static_assert(sizeof(PairArgs) + sizeof(const float*) <= 4096, "kernel arguments: 4 KB at most");
+
+template <int N>
+struct alignas(4 * N) Pack {
+  float v[N];
+};
+
+// units [0, units) of N floats each, starting at element `first` of both tensors.  The index is unsigned: units < 2^31 and the
+// stride is at most 64 * 256, so the last increment stays below 2^32 where a signed index would overflow
+template <int N, class Op>
+__device__ __forceinline__ void pair_walk(float* __restrict__ a, float* __restrict__ b, int first, int units, Op op) {
+  Pack<N>* __restrict__ av = (Pack<N>*)(a + first);
+  Pack<N>* __restrict__ bv = (Pack<N>*)(b + first);
+  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < (unsigned)units; i += gridDim.x * 256u) {
+    Pack<N> x = av[i], y = bv[i];
+#pragma unroll
+    for (int k = 0; k < N; ++k) op(x.v[k], y.v[k]);
+    av[i] = x;
+    if (Op::writes_b) bv[i] = y;
+  }
+}
+
+template <class Op>
+__device__ __forceinline__ void pair_tensor(float* a, float* b, int n, Op op) {
+  int done = 0;
+  if ((((uintptr_t)a | (uintptr_t)b) & 15u) == 0) {
+    pair_walk<4>(a, b, 0, n >> 2, op);
+    done = n & ~3;
+  }
+  pair_walk<1>(a, b, done, n - done, op);
+}
+
+// avg = fma(w, live − avg, avg): one IEEE subtraction and one fused multiply-add, never reshaped (contraction is off and the fma
+// is spelled out).  w == 1 takes the live value itself: decay 0 means "the average IS the iterate", bit for bit, which
+// (live − avg) + avg only is where the subtraction happens to be exact.
+struct EmaOp {
+  static constexpr bool writes_b = false;
+  float w;
+  __device__ __forceinline__ void operator()(float& avg, float& live) const {
+#pragma clang fp contract(off)
+    const float d = live - avg;
+    avg = w == 1.0f ? live : __builtin_fmaf(w, d, avg);
+  }
+};
+
+struct SwapOp {
+  static constexpr bool writes_b = true;
+  __device__ __forceinline__ void operator()(float& x, float& y) const { const float t = x; x = y; y = t; }
+};
+
+// one workgroup, threads 0..31 a group each: the weight of THIS step from words read when the kernel runs.  A group of the mask
+// takes w = 1 − d_t, d_t = decay or, warming up, min(decay, (1 + count) / (10 + count)), and counts the update; a group outside
+// the mask, or any group of a step the anomaly guard skips (verdict != 0), takes w = 0 and keeps its count.
+__global__ __launch_bounds__(64) void ema_weights_kernel(uint32_t active_mask, float* __restrict__ state, const int* __restrict__ verdict) {
+#pragma clang fp contract(off)
+  const int g = threadIdx.x;
+  if (g >= EMA_GROUPS) return;
+  int* count = (int*)state + EMA_COUNT;
+  float w = 0.0f;
+  if (((active_mask >> g) & 1u) && !(verdict && verdict[0] != 0)) {
+    const int c = count[g];
+    float d = state[EMA_DECAY];
+    if (((const int*)state)[EMA_WARMUP] != 0) d = fminf(d, (1.0f + (float)c) / (10.0f + (float)c));
+    w = 1.0f - d;
+    count[g] = c + 1;
+  }
+  state[EMA_W + g] = w;
+}
+
+// w[group] is one uniform load per workgroup; a workgroup whose weight is exactly 0 returns before its first load of either
+// tensor: an inactive module and a skipped step keep their averages' bits (NaN payloads included) and pay no memory pass
+__global__ __launch_bounds__(256) void ema_multi_kernel(PairArgs a, const float* __restrict__ w_words) {
+  const int t = blockIdx.y;
+  if (t >= a.n) return;
+  const float w = w_words[a.group[t]];
+  if (w == 0.0f) return;
+  pair_tensor(a.a[t], a.b[t], a.numel[t], EmaOp{w});
+}
+
+__global__ __launch_bounds__(256) void swap_multi_kernel(PairArgs a) {
+  const int t = blockIdx.y;
+  if (t >= a.n) return;
+  pair_tensor(a.a[t], a.b[t], a.numel[t], SwapOp{});
+}
+
+// every pair of a call before its first launch: the entries of check_group_tensors on both sides (group_host == NULL: no groups),
+// and two ranges that do not overlap (the walk holds both pointers restrict; an average is never its own iterate)
+static int check_pairs(const char* who, float* const* a_host, float* const* b_host, const int64_t* numel_host, const int32_t* group_host,
+                       int n_tensors) {
+  FST_REQUIRE(n_tensors >= 0 && n_tensors < (1 << 24) && (n_tensors == 0 || (a_host && b_host && numel_host)), "%s: bad arguments", who);
+  for (int i = 0; i < n_tensors; ++i) {
+    FST_REQUIRE(a_host[i] && b_host[i] && (((uintptr_t)a_host[i] | (uintptr_t)b_host[i]) & 3) == 0 && numel_host[i] > 0 &&
+                numel_host[i] < (1LL << 31), "%s: tensor %d: null or misaligned pointer, or bad element count", who, i);
+    FST_REQUIRE(!group_host || (group_host[i] >= 0 && group_host[i] < EMA_GROUPS), "%s: tensor %d: group %d is not in 0..31", who, i,
+                group_host ? group_host[i] : 0);
+    const uintptr_t a = (uintptr_t)a_host[i], b = (uintptr_t)b_host[i], bytes = (uintptr_t)numel_host[i] * 4;
+    FST_REQUIRE(a + bytes <= b || b + bytes <= a, "%s: tensor %d: the two tensors overlap", who, i);
+  }
+  return 0;
+}
+
+static void fill_pairs(PairArgs& a, float* const* a_host, float* const* b_host, const int64_t* numel_host, const int32_t* group_host,
+                       int base, int n_tensors) {
+  a.n = n_tensors - base < NF_MAX_T ? n_tensors - base : NF_MAX_T;
+  for (int i = 0; i < a.n; ++i) {
+    a.a[i] = a_host[base + i]; a.b[i] = b_host[base + i]; a.numel[i] = (int)numel_host[base + i];
+    a.group[i] = group_host ? group_host[base + i] : 0;
+  }
+}
+
+extern "C" int fst_ema_multi(float* const* avg_host, const float* const* live_host, const int64_t* numel_host, const int32_t* group_host,
+                             int n_tensors, int32_t active_mask, void* state_dev, const int32_t* verdict_dev, void* stream) {
+  FST_REQUIRE(n_tensors == 0 || group_host, "fst_ema_multi: bad arguments");
+  if (check_pairs("fst_ema_multi", avg_host, (float* const*)live_host, numel_host, group_host, n_tensors)) return -1;
+  FST_REQUIRE(state_dev && (((uintptr_t)state_dev | (uintptr_t)verdict_dev) & 3) == 0, "fst_ema_multi: null or misaligned state or verdict word");
+  float* state = (float*)state_dev;
+  hipLaunchKernelGGL(ema_weights_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (uint32_t)active_mask, state, (const int*)verdict_dev);
+  FST_LAUNCH_CHECK();
+  for (int base = 0; base < n_tensors; base += NF_MAX_T) {
+    PairArgs a;
+    fill_pairs(a, avg_host, (float* const*)live_host, numel_host, group_host, base, n_tensors);
+    hipLaunchKernelGGL(ema_multi_kernel, dim3((unsigned)group_launch_bx(numel_host + base, a.n), (unsigned)a.n), dim3(256), 0,
+                       (hipStream_t)stream, a, (const float*)(state + EMA_W));
+    FST_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+extern "C" int fst_swap_multi(float* const* a_host, float* const* b_host, const int64_t* numel_host, int n_tensors, void* stream) {
+  if (check_pairs("fst_swap_multi", a_host, b_host, numel_host, nullptr, n_tensors)) return -1;
+  for (int base = 0; base < n_tensors; base += NF_MAX_T) {
+    PairArgs a;
+    fill_pairs(a, a_host, b_host, numel_host, nullptr, base, n_tensors);
+    hipLaunchKernelGGL(swap_multi_kernel, dim3((unsigned)group_launch_bx(numel_host + base, a.n), (unsigned)a.n), dim3(256), 0,
+                       (hipStream_t)stream, a);
     FST_LAUNCH_CHECK();
   }
   return 0;

@@ -26,6 +26,10 @@ Gradient norms and clipping.  ``sumsq_norms`` takes the L2 norms of many tensors
 the factors that cap each group and then the whole (``clip_coefficients`` is their definition; ``GradClip`` holds the device
 words); ``scale_by_group`` multiplies the tensors by those factors, read when the kernels run: what
 ``torch.nn.utils.clip_grad_norm_`` does with a host decision, usable inside a replayed graph.
+
+Weight averaging.  ``ema_update`` keeps an exponential moving average of many tensors per group, its weight derived on the device
+from the words of a ``WeightAverage`` (decay, warm-up, update counts) when the kernels run; ``swap_tensors`` exchanges two lists of
+tensors in place — the averages into the modules' own storage for evaluation, and back.
 """
 from __future__ import annotations
 
@@ -496,3 +500,136 @@ def scale_by_group(tensors: Sequence[torch.Tensor], groups: Sequence[int], coef:
     _lib.check(_lib.load().fst_scale_multi(_ptr_array(xs), _i64_array([x.numel() for x in xs]),
                                            (ctypes.c_int32 * len(xs))(*[g for _, g in keep]), len(xs), coef.data_ptr(),
                                            _lib.stream_ptr()), "fst_scale_multi")
+
+
+# ---- weight averaging: an exponential moving average of the weights, kept and steered on the device
+class WeightAverage:
+    """The device words of the weight averaging, one block of 66 4-byte words (``fst_ema_multi``'s ``state_dev``): ``decay``
+    (fp32), ``warmup`` (int32 flag), ``count`` (int32[32], completed updates per group) and ``w`` (fp32[32], the weight the last
+    ``ema_update`` applied per group, 0 for a group it left alone) are views of ``words``.  ``decay_host`` / ``warmup_host`` are what
+    the first two hold, known without reading them back; ``set_decay`` changes both sides with one stream-ordered copy, which a
+    graph replayed afterwards sees."""
+
+    def __init__(self, device, decay: float = 0.999, warmup: bool = True):
+        self.device = torch.device(device)
+        self.decay_host, self.warmup_host = self._checked(decay), bool(warmup)
+        self.words = torch.zeros(2 + 2 * MAX_GROUPS, dtype=torch.int32, device=device)
+        self.decay = self.words[0:1].view(torch.float32)
+        self.warmup = self.words[1:2]
+        self.count = self.words[2: 2 + MAX_GROUPS]
+        self.w = self.words[2 + MAX_GROUPS:].view(torch.float32)
+        self.words[:2].copy_(self._head())
+
+    @staticmethod
+    def _checked(decay) -> float:
+        if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0.0 <= float(decay) <= 1.0:
+            raise ValueError(f"weight average: decay must be a number in [0, 1], got {decay!r}")
+        return _f32(decay)
+
+    def _head(self) -> torch.Tensor:
+        return torch.cat([torch.tensor([self.decay_host], dtype=torch.float32).view(torch.int32),
+                          torch.tensor([int(self.warmup_host)], dtype=torch.int32)])
+
+    def set_decay(self, decay: Optional[float] = None, warmup: Optional[bool] = None) -> bool:
+        """``decay`` in [0, 1] and / or the warm-up flag (None keeps the current one).  Copies them to the device if they differ
+        from what it holds, on the current stream and without waiting for it.  Returns whether anything changed."""
+        new = (self.decay_host if decay is None else self._checked(decay), self.warmup_host if warmup is None else bool(warmup))
+        if new == (self.decay_host, self.warmup_host):
+            return False
+        self.decay_host, self.warmup_host = new
+        host = self._head()
+        if self.words.is_cuda:
+            host = host.pin_memory()                                          # a pageable source would make the copy wait for the device
+        self.words[:2].copy_(host, non_blocking=True)
+        return True
+
+
+def _pairs(who: str, a: Sequence[torch.Tensor], b: Sequence[torch.Tensor]):
+    if len(a) != len(b):
+        raise ValueError(f"{who}: {len(a)} and {len(b)} tensors")
+    for i, (x, y) in enumerate(zip(a, b)):
+        if x.dtype != torch.float32 or y.dtype != torch.float32:
+            raise TypeError(f"{who}: pair {i} must be float32, got {x.dtype} and {y.dtype}")
+        if x.shape != y.shape or x.device != y.device:
+            raise ValueError(f"{who}: pair {i}: {tuple(x.shape)} on {x.device} and {tuple(y.shape)} on {y.device}")
+        if not (x.is_contiguous() and y.is_contiguous()):
+            raise ValueError(f"{who}: pair {i} must be contiguous (a copy would be written in its place)")
+
+
+def _active_mask(who: str, active) -> int:
+    if isinstance(active, int) and not isinstance(active, bool):
+        if not 0 <= active < 1 << MAX_GROUPS:
+            raise ValueError(f"{who}: the mask of active groups must fit {MAX_GROUPS} bits, got {active}")
+        return active
+    mask = 0
+    for g in active:
+        if not 0 <= int(g) < MAX_GROUPS:
+            raise ValueError(f"{who}: active group {g} is not in range({MAX_GROUPS})")
+        mask |= 1 << int(g)
+    return mask
+
+
+@torch.no_grad()
+def ema_update(avg: Sequence[torch.Tensor], live: Sequence[torch.Tensor], groups: Sequence[int], state: WeightAverage, active,
+               guard: Optional[AnomalyGuard] = None) -> None:
+    """One update of the averages: ``avg[i] = fma(w, live[i] − avg[i], avg[i])`` with ``w = state.w[groups[i]]``, which this call
+    first sets on the device, from the words as they are when the kernels run: for a group of ``active`` (group ids, or a bit mask)
+    ``w = 1 − d``, ``d = state.decay`` or, warming up, ``min(decay, (1 + count) / (10 + count))`` — the warm-up of
+    ``tf.train.ExponentialMovingAverage(num_updates=)`` — and ``state.count`` advances; every other group, and every group when ``guard.verdict`` is non-zero,
+    takes ``w = 0`` and keeps averages and count bit for bit.  fp32 tensors, contiguous, same shapes; ``live`` is only read.  One
+    ``fst_ema_multi`` launch per 64 pairs behind a one-workgroup prologue; nothing waits for the device.  On CPU tensors the same
+    words and ``torch.lerp`` (host-logic tests): the same quantity, not the same bits — for ``w`` ≥ 0.5 lerp evaluates
+    ``live − (live − avg)·(1 − w)``, and below it may or may not fuse the multiply-add; the kernel's formula is the definition."""
+    _pairs("ema_update", avg, live)
+    if len(groups) != len(avg):
+        raise ValueError(f"ema_update: {len(avg)} tensors, {len(groups)} group ids")
+    for i, g in enumerate(groups):
+        if not 0 <= int(g) < MAX_GROUPS:
+            raise ValueError(f"ema_update: tensor {i}: group {g} is not in range({MAX_GROUPS})")
+    mask = _active_mask("ema_update", active)
+    keep = [(a, l, int(g)) for a, l, g in zip(avg, live, groups) if a.numel() > 0]
+    if state.device.type != "cuda":
+        skip = guard is not None and int(guard.verdict.item()) != 0
+        d, warm = state.decay.clone(), bool(int(state.warmup))
+        for g in range(MAX_GROUPS):
+            if skip or not (mask >> g) & 1:
+                state.w[g] = 0.0
+                continue
+            c = state.count[g].to(torch.float32)
+            state.w[g] = (1.0 - (torch.minimum(d, (1.0 + c) / (10.0 + c)) if warm else d))[0]
+            state.count[g] += 1
+        for a, l, g in keep:
+            w = float(state.w[g])
+            if w == 1.0:
+                a.copy_(l)
+            elif w != 0.0:
+                a.lerp_(l, w)
+        return
+    from . import _lib
+    for i, (a, l, _) in enumerate(keep):
+        _lib.require_gpu_tensor(a, f"ema_update: avg {i}"); _lib.require_gpu_tensor(l, f"ema_update: live {i}")
+    _lib.check(_lib.load().fst_ema_multi(_ptr_array([a for a, _, _ in keep]), _ptr_array([l for _, l, _ in keep]),
+                                         _i64_array([a.numel() for a, _, _ in keep]), (ctypes.c_int32 * len(keep))(*[g for _, _, g in keep]),
+                                         len(keep), mask - (1 << 32) if mask >> 31 else mask, state.words.data_ptr(), None if guard is None else guard.verdict.data_ptr(),
+                                         _lib.stream_ptr()), "fst_ema_multi")
+
+
+@torch.no_grad()
+def swap_tensors(a: Sequence[torch.Tensor], b: Sequence[torch.Tensor]) -> None:
+    """Exchange ``a[i]`` and ``b[i]`` in place, element for element (fp32, contiguous, same shapes): one ``fst_swap_multi`` launch
+    per 64 pairs.  Twice is the identity on every bit.  No version counter moves: whatever was derived from either tensor before
+    (a packed weight image, a folded BatchNorm) is stale afterwards."""
+    _pairs("swap_tensors", a, b)
+    keep = [(x, y) for x, y in zip(a, b) if x.numel() > 0]
+    if not keep:
+        return
+    if not keep[0][0].is_cuda:
+        for x, y in keep:
+            t = x.clone()
+            x.copy_(y); y.copy_(t)
+        return
+    from . import _lib
+    for i, (x, y) in enumerate(keep):
+        _lib.require_gpu_tensor(x, f"swap_tensors: a {i}"); _lib.require_gpu_tensor(y, f"swap_tensors: b {i}")
+    _lib.check(_lib.load().fst_swap_multi(_ptr_array([x for x, _ in keep]), _ptr_array([y for _, y in keep]),
+                                          _i64_array([x.numel() for x, _ in keep]), len(keep), _lib.stream_ptr()), "fst_swap_multi")

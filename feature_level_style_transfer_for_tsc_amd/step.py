@@ -39,8 +39,8 @@ from .cdan import CDAN, RandomLayer
 from .cpc import CPC
 from . import dist as _dist
 from .dist import GradBucket
-from .optim import (MAX_GROUPS, AnomalyGuard, FusedRMSprop, GradClip, SharedStepAdam, count_nonfinite, guard_copy, push_lr,
-                    rmsprop_step_many, scale_by_group, sumsq_norms)
+from .optim import (MAX_GROUPS, AnomalyGuard, FusedRMSprop, GradClip, SharedStepAdam, WeightAverage, count_nonfinite, ema_update,
+                    guard_copy, push_lr, rmsprop_step_many, scale_by_group, sumsq_norms, swap_tensors)
 from .os_cnn import OS_CNN, OS_CNN_res, build_layer_with_layer_parameter
 from .structure import generate_layer_parameter_list, layer_parameter_list_input_change, out_channels
 from .waveglow import WaveGlow, WaveGlowLoss
@@ -135,13 +135,148 @@ def step_schedulers(schedulers: Dict[str, object], kind: str, report: Dict[str, 
 _CAPTURE_MODE = "thread_local"
 
 
-class ClassifierTrainer:
+class _WeightAveraging:
+    """Weight averaging of the two trainers.  A trainer supplies ``_ema_modules()`` ({group name: module}, in group order),
+    ``_ema_resident()`` (is a capture resident?) and ``device``; it calls ``_ema_update`` as the last thing of a step and
+    ``_ema_no_step`` as the first."""
+    weight_average: Optional[WeightAverage] = None                            # the device words; None while the mode is off
+    _ema_avg: Dict[str, Dict[str, torch.Tensor]] = {}                         # module -> state_dict name -> the average
+    _ema_live: Dict[str, Dict[str, torch.Tensor]] = {}                        # ... -> the live tensor (addresses never change)
+    _ema_inside = False                                                       # inside averaged_weights()
+
+    def _ema_resident(self) -> bool:
+        raise NotImplementedError
+
+    def _ema_modules(self) -> Dict[str, nn.Module]:
+        raise NotImplementedError
+
+    def enable_weight_average(self, decay: float = 0.999, warmup: bool = True) -> None:
+        """From now on every step ends by moving an exponential moving average of the weights towards the weights it has just
+        written: for every module a copy of each parameter and of each fp32 buffer of its ``state_dict()`` (BatchNorm running
+        statistics are averaged like parameters, as timm's ``ModelEma`` does; integer buffers are not averaged),
+        ``avg ← avg + w·(live − avg)`` with ``w = 1 − decay``, or while ``warmup`` lasts ``1 − min(decay, (1 + n) / (10 + n))``
+        after ``n`` updates of that module.  Decided and applied on the device with no host read, alike in eager and in captured
+        steps; only the modules a step's optimisers stepped are averaged, and a step the anomaly guard skips leaves averages
+        and counts as they were.  The averages only read the weights: the training trajectory is that of the mode off, bit for
+        bit.  ``averaged_weights()`` puts them to use; ``set_weight_average`` steers the decay, under resident captures too.
+        Idempotent (a second call changes nothing, its arguments included); raises while a capture is resident, whose launches lack the update."""
+        if self.weight_average is not None:
+            return
+        state = WeightAverage(self.device, decay, warmup)                     # (refuses a bad decay before anything changes)
+        if self._ema_resident():
+            raise RuntimeError("enable_weight_average(): a capture is resident; enable the mode before capturing")
+        # the live tensors are listed once: every loader of this package writes them in place, and the exchange of
+        # averaged_weights() depends on their addresses staying what they are anyway
+        self._ema_live = {k: {n: t for n, t in mod.state_dict().items() if t.dtype == torch.float32}
+                          for k, mod in self._ema_modules().items()}
+        self._ema_avg = {k: {n: t.detach().clone(memory_format=torch.contiguous_format) for n, t in d.items()}
+                         for k, d in self._ema_live.items()}
+        self.weight_average = state
+
+    def set_weight_average(self, decay: Optional[float] = None, warmup: Optional[bool] = None) -> bool:
+        """Change the decay and / or the warm-up flag (an argument left out keeps its value).  Legal while captures are
+        resident: one stream-ordered copy into the device words, which a graph replayed afterwards reads — no re-capture.
+        Returns whether the device words changed."""
+        if self.weight_average is None:
+            raise RuntimeError("set_weight_average(): call enable_weight_average() first")
+        return self.weight_average.set_decay(decay, warmup)
+
+    def _ema_pairs(self, names):
+        """(averages, live tensors, group ids) of the modules ``names``, in a fixed order."""
+        order = list(self._ema_avg)
+        avg, live, groups = [], [], []
+        for k in names:
+            for n, a in self._ema_avg[k].items():
+                avg.append(a); live.append(self._ema_live[k][n]); groups.append(order.index(k))
+        return avg, live, groups
+
+    def _ema_update(self, names, guard: Optional[AnomalyGuard] = None) -> None:
+        if self.weight_average is None:
+            return
+        avg, live, groups = self._ema_pairs(names)
+        ema_update(avg, live, groups, self.weight_average, sorted(set(groups)), guard)
+
+    def _ema_no_step(self, what: str) -> None:
+        if self._ema_inside:
+            raise RuntimeError(f"{what}: inside averaged_weights() the modules hold the averages and the averages' tensors the live "
+                               "weights; leave the context first")
+
+    def _ema_report(self) -> Dict[str, torch.Tensor]:
+        n = len(self._ema_avg)
+        return {"ema_weight": self.weight_average.w[:n].clone(), "ema_steps": self.weight_average.count[:n].clone()}
+
+    def _ema_caches(self) -> list:
+        """Objects whose attribute ``W_inverse`` caches something derived from the weights outside any ``ops.pack_cache()``."""
+        return []
+
+    def averaged_weights(self):
+        """Context manager: inside it the modules hold the AVERAGED weights and fp32 buffers — one in-place exchange with the
+        averages on entry, the same exchange on exit, after which every live bit is what it was.  The addresses do not change,
+        so captured graphs stay valid, and ``eval_accuracy``, ``collect_logits`` and the ``save_*_classification_modules``
+        functions work on the averaged model unchanged: a checkpoint saved inside is a reference-format ``.tar`` of it.  The
+        modules' train / eval mode is the caller's business, as in ``eval_accuracy``.  The flow's cached 1x1 inverses (quirk Q2)
+        are set aside on entry and put back on exit; what is cached inside belongs to the averaged weights and is dropped.
+        Raises inside an open ``ops.pack_cache()`` scope (the exchange moves no version counter: a packed image or a BatchNorm
+        fold made before it would be stale) and when nested; inside it the trainer's step, replay and capture methods and its
+        state methods (``snapshot`` / ``restore`` / ``state_dict`` / ``load_state_dict``) raise: they would train on, or save
+        and load, the two sets exchanged."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def scope():
+            if self.weight_average is None:
+                raise RuntimeError("averaged_weights(): call enable_weight_average() first")
+            if self._ema_inside:
+                raise RuntimeError("averaged_weights(): already inside; the context does not nest")
+            if ops._PACK_CACHE is not None:
+                raise RuntimeError("averaged_weights(): inside an ops.pack_cache() scope, whose packed weights and BatchNorm folds "
+                                   "would be stale after the exchange; enter it outside")
+            avg, live, _ = self._ema_pairs(list(self._ema_avg))
+            swap_tensors(avg, live)                                           # (refuses before it exchanges anything)
+            caches = self._ema_caches()
+            aside = [c.__dict__.pop("W_inverse", None) for c in caches]
+            self._ema_inside = True
+            try:
+                yield self
+            finally:
+                try:
+                    swap_tensors(avg, live)
+                finally:
+                    self._ema_inside = False
+                    for c, w in zip(caches, aside):
+                        c.__dict__.pop("W_inverse", None)
+                        if w is not None:
+                            c.W_inverse = w
+        return scope()
+
+    def _ema_state_dict(self) -> dict:
+        st = self.weight_average
+        return {"decay": st.decay_host, "warmup": st.warmup_host, "counts": st.count.cpu().tolist(),
+                "tensors": {k: {n: t.detach().cpu().clone() for n, t in d.items()} for k, d in self._ema_avg.items()}}
+
+    def _ema_load_state_dict(self, sd: dict) -> None:
+        """In place: a resident capture keeps valid addresses."""
+        if self.weight_average is None:
+            self.enable_weight_average(sd["decay"], sd["warmup"])
+        self.weight_average.set_decay(sd["decay"], sd["warmup"])
+        with torch.no_grad():
+            self.weight_average.count.copy_(torch.tensor(sd["counts"], dtype=torch.int32))
+            for k, d in self._ema_avg.items():
+                if set(d) != set(sd["tensors"][k]):
+                    raise KeyError(f"weight average of {k!r}: the checkpoint's tensors are not this module's")
+                for n, t in d.items():
+                    t.copy_(sd["tensors"][k][n])
+
+
+class ClassifierTrainer(_WeightAveraging):
     """S1 of the reference.  The anomaly guard (``JointTrainer.enable_anomaly_guard``) is not offered here: a non-finite batch
-    reaches this trainer's parameters as it does in the reference."""
+    reaches this trainer's parameters as it does in the reference.  Weight averaging (``enable_weight_average``) is, over the
+    groups "fe" and "clf"; its device words are ``weight_average``."""
 
     def __init__(self, length: int, in_channel: int, n_class: int, device, bucket: Optional[GradBucket] = None,
-                 sync: str = "ddp", device_hparams: bool = False):
-        self.sync = sync
+                 sync: str = "ddp", device_hparams: bool = False, weight_average=None):
+        """``weight_average``: ``enable_weight_average()`` at once — True, a decay, or a dict of its keyword arguments."""
+        self.sync, self.device = sync, device
         fe_spec, clf_spec = specs_for(length, in_channel)
         self.fe = OS_CNN_res(fe_spec).to(device)
         self.clf = OS_CNN(clf_spec, n_class).to(device)
@@ -154,6 +289,13 @@ class ClassifierTrainer:
         self.device_hparams = False
         if device_hparams:
             self.enable_device_hparams()
+        _enable_weight_average(self, weight_average)
+
+    def _ema_modules(self) -> Dict[str, nn.Module]:
+        return {"fe": self.fe, "clf": self.clf}
+
+    def _ema_resident(self) -> bool:
+        return self._graph is not None
 
     def enable_device_hparams(self) -> None:
         """Keep both learning rates in device tensors (``optim.push_lr``): ``replay`` then trains at the current ``group["lr"]`` of
@@ -170,6 +312,7 @@ class ClassifierTrainer:
         return list(self.fe.parameters()) + list(self.clf.parameters())
 
     def step(self, x: torch.Tensor, y: torch.Tensor):
+        self._ema_no_step("step()")
         with _dist.global_batch(self.bucket if self.sync == "global" else None):
             with ops.pack_cache():
                 logits, _ = self.clf(self.fe(x))
@@ -179,11 +322,13 @@ class ClassifierTrainer:
             self.bucket.all_reduce(self.parameters())
         rmsprop_step_many([self.opt_fe, self.opt_clf])
         self.opt_fe.zero_grad(set_to_none=True); self.opt_clf.zero_grad(set_to_none=True)
+        self._ema_update(("fe", "clf"))
         return loss.detach(), logits.detach()
 
     # ---- single GPU: the whole step as one hipGraph (the eager step is launch-bound: ~300 launches for ~2 ms of GPU work)
     def capture(self, x: torch.Tensor, y: torch.Tensor, warmup: int = 3):
         """Capture one step.  The learning rates are baked into the graph unless ``enable_device_hparams()`` ran before."""
+        self._ema_no_step("capture()")
         if self.bucket is not None:
             raise RuntimeError("ClassifierTrainer.capture(): single-GPU only (the DP step has an eager all-reduce)")
         self._g_x, self._g_y = x.clone(), y.clone()
@@ -201,6 +346,7 @@ class ClassifierTrainer:
     def replay(self, x: torch.Tensor, y: torch.Tensor):
         """One captured step on a new batch of the captured shape; returns (loss, logits) in static buffers.  With
         ``device_hparams`` it runs at the optimisers' current ``group["lr"]``, otherwise at the captured rates."""
+        self._ema_no_step("replay()")
         if self._graph is None:
             raise RuntimeError("call capture() first")
         self._g_x.copy_(x); self._g_y.copy_(y)
@@ -208,6 +354,18 @@ class ClassifierTrainer:
             push_lr((self.opt_fe, self.opt_clf))
         self._graph.replay()
         return self._g_out
+
+
+def _enable_weight_average(trainer, arg) -> None:
+    """The constructors' ``weight_average=``: None / False, True, a decay, or a dict of enable_weight_average's arguments."""
+    if arg is None or arg is False:
+        return
+    if arg is True:
+        trainer.enable_weight_average()
+    elif isinstance(arg, dict):
+        trainer.enable_weight_average(**arg)
+    else:
+        trainer.enable_weight_average(decay=arg)
 
 
 @dataclass
@@ -227,7 +385,7 @@ class JointConfig:
     nf_end_std: float = 0.0       # >0: draw WN.end (zero-init in the reference) so the flow is non-degenerate
 
 
-class JointTrainer:
+class JointTrainer(_WeightAveraging):
     MODULES = ("fe_t", "clf_t", "fe_s", "dimunif", "clf_s", "probtransfer", "nf", "noise", "ad_net", "fd_s", "cpc")
     LRS = {"fe_t": 0.001, "clf_t": 0.003, "fe_s": 0.001, "dimunif": 0.001, "clf_s": 0.003, "probtransfer": 0.001,
            "nf": 0.001, "noise": 0.005, "ad_net": 0.001, "fd_s": 0.001}       # train_and_test.py:97-106
@@ -237,12 +395,14 @@ class JointTrainer:
     ANOMALY_GROUPS = MODULES + ("gradnorm", "losses", "buffers")
 
     def __init__(self, cfg: JointConfig, device, bucket: Optional[GradBucket] = None, fe_t_spec=None, clf_spec=None,
-                 fe_s_spec=None, sync: str = "ddp", device_hparams: bool = False, anomaly_guard: bool = False, grad_clip=None):
+                 fe_s_spec=None, sync: str = "ddp", device_hparams: bool = False, anomaly_guard: bool = False, grad_clip=None,
+                 weight_average=None):
         """``sync`` (with a bucket): "ddp" = per-rank batch statistics (SURVEY §8e mode A); "global" = every
         batch-coupled quantity over the samples of all ranks (mode B, eager only) — N ranks reproduce the
         single-process step on the concatenated batch.  ``device_hparams``: ``enable_device_hparams()`` at once;
         ``anomaly_guard``: ``enable_anomaly_guard()`` at once.  ``grad_clip``: ``enable_grad_clip()`` at once — True for norms
-        only, a number for ``max_norm``, or a dict of its keyword arguments."""
+        only, a number for ``max_norm``, or a dict of its keyword arguments.  ``weight_average``: ``enable_weight_average()`` at
+        once — True, a decay, or a dict of its keyword arguments."""
         if sync not in ("ddp", "global"):
             raise ValueError(f"sync must be 'ddp' or 'global', got {sync!r}")
         self.cfg, self.device, self.bucket, self.sync = cfg, device, bucket, sync
@@ -320,6 +480,17 @@ class JointTrainer:
                 self.enable_grad_clip(**grad_clip)
             else:
                 self.enable_grad_clip(max_norm=grad_clip)
+        _enable_weight_average(self, weight_average)
+
+    # ------------------------------------------------------------------ weight averaging (the methods are _WeightAveraging's)
+    def _ema_modules(self) -> Dict[str, nn.Module]:
+        return {k: self.m[k] for k in self.MODULES}
+
+    def _ema_resident(self) -> bool:
+        return self._graphs is not None or bool(self._phase)
+
+    def _ema_caches(self) -> list:
+        return list(self.m["nf"].convinv)                                     # Invertible1x1Conv.W_inverse (Q2)
 
     # ------------------------------------------------------------------ anomaly guard: skip non-finite steps on the device
     def enable_anomaly_guard(self) -> None:
@@ -593,11 +764,17 @@ class JointTrainer:
         out["noise.target_avg"], out["noise.source_avg"] = self.m["noise"].target_avg, self.m["noise"].source_avg
         if self.init_t is not None:
             out["init_t"], out["init_s"] = self.init_t, self.init_s
+        if self.weight_average is not None:
+            for k, d in self._ema_avg.items():
+                for n, t in d.items():
+                    out[f"ema.{k}.{n}"] = t
+            out["ema.count"] = self.weight_average.count
         return out
 
     def snapshot(self):
         """Copy of every tensor the step mutates (parameters, BN buffers, optimiser moments, GradNorm weights,
         NoiseTransfer sums) plus the host-side counters."""
+        self._ema_no_step("snapshot()")
         host = {"noise": (self.m["noise"].time, self.m["noise"].cal_num_target, self.m["noise"].cal_num_source),
                 "ad": self.m["ad_net"].iter_num, "fd": self.m["fd_s"].iter_num}
         return {"t": {k: v.detach().clone() for k, v in self._state_tensors().items()}, "host": host}
@@ -605,6 +782,7 @@ class JointTrainer:
     def restore(self, snap, new_to_zero: bool = False) -> None:
         """``new_to_zero``: also return state created since the snapshot (moments an optimiser makes on its first step) to its
         initial value, zero — the trainer then computes what it would have computed had that state never been created."""
+        self._ema_no_step("restore()")
         cur = self._state_tensors()
         with torch.no_grad():
             for k, v in snap["t"].items():
@@ -625,7 +803,9 @@ class JointTrainer:
         none of this across runs (utils.py:9-25 saves the classification modules only); a captured-graph trainer that
         cannot resume would be a gap of this build, not of the reference.  Once ``make_schedulers()`` has run, also
         "schedules": the eleven schedulers' state, CPC's learning rate (the RMSprops' are in their ``param_groups``), the epoch of
-        the last step and its loss coefficients.  With ``enable_grad_clip()`` on, also "grad_clip": its limits."""
+        the last step and its loss coefficients.  With ``enable_grad_clip()`` on, also "grad_clip": its limits; with
+        ``enable_weight_average()`` on, also "weight_average": decay, warm-up flag, update counts and the averaged tensors."""
+        self._ema_no_step("state_dict()")
         cpu = lambda t: t.detach().cpu().clone()
         cpc = self.opt_cpc
         noise = self.m["noise"]
@@ -657,6 +837,7 @@ class JointTrainer:
                               "cpc_lr": [g["lr"] for g in cpc.param_groups],       # "opts" carry theirs in param_groups
                               "coefficients": None if self._sched_epoch is None else loss_coefficients(self._sched_epoch)}}),
             **({"grad_clip": {"max_norm": self._clip_max, "per_module": dict(self._clip_per)}} if self.grad_clip else {}),
+            **({"weight_average": self._ema_state_dict()} if self.weight_average is not None else {}),
         }
 
     def load_state_dict(self, sd: dict) -> None:
@@ -668,6 +849,7 @@ class JointTrainer:
         which is called here if it has not run; a checkpoint without the entry leaves them alone.  The RMSprop moments are NOT restored in place
         (``Optimizer.load_state_dict`` replaces the tensors), so a resident phase graph would update dead moments:
         every phase capture is dropped here and ``replay_phase`` raises until ``capture_phase`` has run again."""
+        self._ema_no_step("load_state_dict()")
         self.release_phase()
         dev = self.device
         for k in self.MODULES:
@@ -710,6 +892,8 @@ class JointTrainer:
             if not self.grad_clip:
                 self.enable_grad_clip()
             self.set_grad_clip(max_norm=sd["grad_clip"]["max_norm"], per_module=sd["grad_clip"]["per_module"])
+        if "weight_average" in sd:                                            # likewise; restored in place
+            self._ema_load_state_dict(sd["weight_average"])
 
     def save_state(self, path: str) -> None:
         torch.save(self.state_dict(), path)
@@ -803,12 +987,15 @@ class JointTrainer:
     def phase_step(self, phase: str, x_t, y_t, x_s, y_s, t_samples=(None, None)):
         """One batch of a pre-training phase: forward, backward, the phase's optimisers, zero_grad (eager; ``capture_phase`` /
         ``replay_phase`` issue the same launches as one hipGraph)."""
+        self._ema_no_step("phase_step()")
         report = self._phase_fwd_bwd(phase, x_t, y_t, x_s, y_s, t_samples)
         if self.bucket is not None:
             self.bucket.all_reduce(self.parameters())
         self._phase_update(phase)
         if self._clip is not None:
             report.update(self._clip_report(self.PHASES[phase]))
+        if self.weight_average is not None:
+            report.update(self._ema_report())
         if self._guard is not None:
             report.update(self._guard_report())
         return report
@@ -832,7 +1019,7 @@ class JointTrainer:
         return report
 
     def _phase_update(self, phase: str) -> None:
-        """Second half (after the gradient all-reduce of a data-parallel step): the phase's optimisers."""
+        """Second half (after the gradient all-reduce of a data-parallel step): the phase's optimisers, then the weight average."""
         if self.on_grads_ready is not None:
             self.on_grads_ready()
         if self._clip is not None:
@@ -844,10 +1031,11 @@ class JointTrainer:
             if "cpc" in self.PHASES[phase]:
                 self.opt_cpc.step(guard=self._guard)
             self._guard_rollback()
-            return
-        rmsprop_step_many([self.opts[k] for k in self.PHASES[phase] if k != "cpc"])
-        if "cpc" in self.PHASES[phase]:
-            self.opt_cpc.step()
+        else:
+            rmsprop_step_many([self.opts[k] for k in self.PHASES[phase] if k != "cpc"])
+            if "cpc" in self.PHASES[phase]:
+                self.opt_cpc.step()
+        self._ema_update(self.PHASES[phase], self._guard)                     # the last thing a step does
 
     # ------------------------------------------------------------------ hipGraph for the phases: capture once each, replay per batch
     def capture_phase(self, phase: str, x_t, y_t, x_s, y_s, warmup: int = 2):
@@ -865,6 +1053,7 @@ class JointTrainer:
         ``enable_device_hparams()`` ran before: then every ``replay_phase`` runs at their current ``group["lr"]``.
         ``on_grads_ready`` is called inside the captured region, as in ``capture``: it fires ONCE, at capture time (on the gradient
         tensors the graph will write), not per replay and not during the warm-up."""
+        self._ema_no_step("capture_phase()")
         if phase not in self.PHASES:
             raise ValueError(f"unknown phase {phase!r}; one of {sorted(self.PHASES)}")
         if self.sync == "global" and self.bucket is not None and self.bucket.world > 1:
@@ -893,12 +1082,15 @@ class JointTrainer:
         main.wait_stream(side)
         torch.cuda.synchronize()
         # static report: the graphs' own outputs live in the shared pool, where a later capture may reuse what this one frees
-        keys = [k for k in keys if k not in ("skipped", "anomaly", "grad_l2", "clip_coef")]   # static tensors of their own
+        keys = [k for k in keys if k not in ("skipped", "anomaly", "grad_l2", "clip_coef", "ema_weight", "ema_steps")]   # static tensors of their own
         out = torch.zeros(len(keys), device=dev)
         g_rep = {} if self._guard is None else {"skipped": torch.zeros((), dtype=torch.int32, device=dev),
                                                 "anomaly": torch.zeros(len(self.ANOMALY_GROUPS), dtype=torch.int32, device=dev)}
         if self._clip is not None:
             g_rep.update(grad_l2=torch.zeros(len(self.MODULES) + 1, device=dev), clip_coef=torch.ones(len(self.MODULES), device=dev))
+        if self.weight_average is not None:
+            g_rep.update(ema_weight=torch.zeros(len(self.MODULES), device=dev),
+                         ema_steps=torch.zeros(len(self.MODULES), dtype=torch.int32, device=dev))
 
         def update():
             self._phase_update(phase)
@@ -908,6 +1100,9 @@ class JointTrainer:
             if self._guard is not None:
                 g_rep["skipped"].copy_(self._guard.verdict[0])
                 g_rep["anomaly"].copy_(self._guard.counts[: len(self.ANOMALY_GROUPS)])
+            if self.weight_average is not None:
+                g_rep["ema_weight"].copy_(self.weight_average.w[: len(self.MODULES)])
+                g_rep["ema_steps"].copy_(self.weight_average.count[: len(self.MODULES)])
 
         def fwd_bwd():
             rep = self._phase_fwd_bwd(phase, *args)
@@ -940,6 +1135,7 @@ class JointTrainer:
         """One batch of a captured phase on a new batch of the captured shapes; returns the phase's static report (the keys of
         ``phase_step``: its losses and "total"), valid until this phase's next replay.  Nothing here waits for the device.
         ``.grad`` is left alone: the gradients are in the tensors the capture kept."""
+        self._ema_no_step("replay_phase()")
         rec = self._phase.get(phase)
         if rec is None:
             if phase not in self.PHASES:
@@ -979,6 +1175,7 @@ class JointTrainer:
     # ------------------------------------------------------------------ one optimisation step (:645-766)
     def step(self, x_t, y_t, x_s, y_s, epoch: int = 0, t_samples=(None, None)):
         """Eager step.  ``t_samples``: the two CPC start indices (drawn like the reference if None)."""
+        self._ema_no_step("step()")
         self._set_epoch(epoch)
         ratios = self.m["noise"].advance(x_t.size(0), x_s.size(0))
         return self._step_body(x_t, y_t, x_s, y_s, epoch, t_samples, ratios)
@@ -1110,11 +1307,14 @@ class JointTrainer:
                 p.clamp_(-0.01, 0.01)
         if guard is not None:
             self._guard_rollback()
+        self._ema_update(self.MODULES, guard)                                 # the last thing a step does
         report = dict(mid["report"])
         report.update({"w_t": self.w_t.detach().clone(), "w_s": self.w_s.detach().clone(),
                        "norms_t": nt.detach(), "norms_s": ns.detach()})
         if self._clip is not None:
             report.update(self._clip_report(self.MODULES))
+        if self.weight_average is not None:
+            report.update(self._ema_report())
         if guard is not None:
             report.update(self._guard_report())
         return report
@@ -1132,6 +1332,7 @@ class JointTrainer:
         GradNorm-weight Adams' rates stay baked).
         Single GPU: one graph.  Data parallel: three graphs (A1 forward + backward, A2 GradNorm's partial passes, B update)
         with the eager RCCL collectives between them, the gradient all-reduce overlapping A2 on a side stream."""
+        self._ema_no_step("capture()")
         if self.sync == "global" and self.bucket is not None and self.bucket.world > 1:
             raise RuntimeError("sync='global' (mode B) puts collectives inside autograd: run it eagerly with step()")
         dev = self.device
@@ -1196,6 +1397,7 @@ class JointTrainer:
         """One step through the captured graph(s); returns the (static) report tensors.  With ``device_hparams`` the step runs at
         the optimisers' current ``group["lr"]`` and, when ``epoch`` is given, at ``loss_coefficients(epoch)``; without it, at the
         captured values, and an ``epoch`` other than the captured one raises."""
+        self._ema_no_step("replay()")
         if self._graphs is None:
             raise RuntimeError("call capture() first")
         if self.device_hparams:

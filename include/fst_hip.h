@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FST_ABI_VERSION 22
+#define FST_ABI_VERSION 23
 
 int fst_version(void);
 const char* fst_last_error(void);
@@ -667,6 +667,25 @@ int fst_sumsq_multi(const float* const* x_host, const int64_t* numel_host, const
                     float* slots_dev, int64_t slots_len, const float* limits_dev, float* norms_dev, float* coef_dev, void* stream);
 int fst_scale_multi(float* const* x_host, const int64_t* numel_host, const int32_t* group_host, int n_tensors,
                     const float* coef_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Weight averaging on the device (ABI v23): an exponential moving average of parameters and fp32 buffers that a replayed
+ * hipGraph keeps up to date (what timm's ModelEma and torch.optim.swa_utils.AveragedModel do from the host).  Pairs of fp32
+ * tensors with 4-byte aligned pointers that do not overlap, 0 < element count < 2^31, group_host[i] in 0..31, at most 64 pairs per
+ * launch, every entry validated on the host before the first launch: a refused call has written nothing.
+ * state_dev is a block of 66 4-byte words: [0] decay (fp32), [1] warm-up flag (int32), [2..33] count[32] (int32, completed updates
+ * per group), [34..65] w[32] (fp32).  ema_multi first launches one workgroup that, from the words as they are when it RUNS, writes
+ *   w[g] = 1 - d,  d = warm-up ? min(decay, (1 + count[g]) / (10 + count[g])) : decay,  then count[g] += 1
+ * for every group g of active_mask (bit g; group 31 is the sign bit), in fp32, and w[g] = 0 with count[g] unchanged for every other group -- and for every
+ * group if verdict_dev (optional, the anomaly guard's word) is non-zero.  Then avg[i] = fma(w[g], live[i] - avg[i], avg[i]) per
+ * element, the subtraction and the fma each rounded once; w == 1 stores live[i] itself.  A workgroup whose w is exactly 0 returns
+ * before it loads anything: those averages keep their bits.  live is only read.  n_tensors == 0 runs the prologue alone.
+ * swap_multi exchanges a[i] and b[i] element for element; twice is the identity on every bit.
+ * Pairs whose two pointers are 16-byte aligned move in 16-byte accesses, all others in 4-byte ones.
+ * ------------------------------------------------------------------------------------------- */
+int fst_ema_multi(float* const* avg_host, const float* const* live_host, const int64_t* numel_host, const int32_t* group_host,
+                  int n_tensors, int32_t active_mask, void* state_dev, const int32_t* verdict_dev, void* stream);
+int fst_swap_multi(float* const* a_host, float* const* b_host, const int64_t* numel_host, int n_tensors, void* stream);
 
 #ifdef __cplusplus
 }
