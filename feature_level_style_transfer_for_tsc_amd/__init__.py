@@ -14,8 +14,8 @@ from .cpc import CPC
 from .widgets import (AdversarialNetworkforCDAN, DimensionUnification, FeatureDiscriminatorforSource, NoiseTransfer,
                       ProbTransfer, wgan_loss)
 from .step import ClassifierTrainer, JointConfig, JointTrainer, specs_for
-from .optim import (AnomalyGuard, GradClip, WeightAverage, clip_coefficients, count_nonfinite, ema_update, scale_by_group, sumsq_norms,
-                    swap_tensors)
+from .optim import (AnomalyGuard, GradAccumulation, GradClip, WeightAverage, accumulate, clip_coefficients, count_nonfinite, ema_update,
+                    scale_by_group, sumsq_norms, swap_tensors)
 from .dist import GradBucket, shard_batch
 from .data import DeviceLoader, TestData, TrainData, load_ts, parse_ts
 from .voting import collect_logits, multi_source_vote, multi_source_voting, precision_weights, vote_scores

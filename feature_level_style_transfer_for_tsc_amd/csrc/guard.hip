@@ -16,6 +16,8 @@
 //                          whose per-group weight a one-workgroup prologue derives, when it runs, from a device decay, a warm-up
 //                          count, the call's mask of active groups and the guard's verdict; w == 0 touches nothing.
 //   fst_swap_multi         exchanges pairs of tensors in place (the averages into the modules' storage for evaluation, and back).
+//   fst_accum_multi        folds gradients into fp32 accumulators over a window of k calls whose position j is a device word:
+//                          acc = g when the window opens, acc += g after, and g = acc / k in place on the call that closes it.
 //
 // House style of optim.hip: the pointer tuples ride BY VALUE in the kernel arguments, at most 64 per launch, so a captured launch
 // carries them; no float atomics and no zero fill: every workgroup of the scan writes its own slot with a plain store (and plain
@@ -397,11 +399,13 @@ __device__ __forceinline__ void pair_walk(float* __restrict__ a, float* __restri
   Pack<N>* __restrict__ av = (Pack<N>*)(a + first);
   Pack<N>* __restrict__ bv = (Pack<N>*)(b + first);
   for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < (unsigned)units; i += gridDim.x * 256u) {
-    Pack<N> x = av[i], y = bv[i];
+    Pack<N> y = bv[i];
+    Pack<N> x = y;
+    if (Op::reads_a) x = av[i];
 #pragma unroll
     for (int k = 0; k < N; ++k) op(x.v[k], y.v[k]);
     av[i] = x;
-    if (Op::writes_b) bv[i] = y;
+    if (op.writes_b) bv[i] = y;
   }
 }
 
@@ -419,7 +423,7 @@ __device__ __forceinline__ void pair_tensor(float* a, float* b, int n, Op op) {
 // is spelled out).  w == 1 takes the live value itself: decay 0 means "the average IS the iterate", bit for bit, which
 // (live − avg) + avg only is where the subtraction happens to be exact.
 struct EmaOp {
-  static constexpr bool writes_b = false;
+  static constexpr bool reads_a = true, writes_b = false;
   float w;
   __device__ __forceinline__ void operator()(float& avg, float& live) const {
 #pragma clang fp contract(off)
@@ -429,7 +433,7 @@ struct EmaOp {
 };
 
 struct SwapOp {
-  static constexpr bool writes_b = true;
+  static constexpr bool reads_a = true, writes_b = true;
   __device__ __forceinline__ void operator()(float& x, float& y) const { const float t = x; x = y; y = t; }
 };
 
@@ -518,6 +522,68 @@ extern "C" int fst_swap_multi(float* const* a_host, float* const* b_host, const 
     fill_pairs(a, a_host, b_host, numel_host, nullptr, base, n_tensors);
     hipLaunchKernelGGL(swap_multi_kernel, dim3((unsigned)group_launch_bx(numel_host + base, a.n), (unsigned)a.n), dim3(256), 0,
                        (hipStream_t)stream, a);
+    FST_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+// ---- gradient accumulation: a window of k calls folds k gradients into one mean, the position in the window a device word, so
+// that ONE captured launch series serves every position.  The state block, in 4-byte words: k (int32), j (int32, folds done in
+// the open window), inv_k (fp32, the host's float32(1 / k)), windows (int32, closed windows), four reserved words.
+#define ACC_K 0
+#define ACC_J 1
+#define ACC_INV_K 2
+#define ACC_WINDOWS 3
+
+// acc = g (the window opens: acc is not read, so it never needs a zero fill) or acc + g, one IEEE addition; on the closing call
+// then g = acc * inv_k, one IEEE multiplication (contraction is off: never an fma of the two).  NaN and inf go the way IEEE sends them.
+template <bool READS_ACC>
+struct AccumOp {
+  static constexpr bool reads_a = READS_ACC;   // false on the call that opens a window
+  bool writes_b;                               // the call that closes it
+  float inv_k;
+  __device__ __forceinline__ void operator()(float& acc, float& g) const {
+#pragma clang fp contract(off)
+    acc = READS_ACC ? acc + g : g;
+    if (writes_b) g = acc * inv_k;
+  }
+};
+
+// k and j are uniform loads per workgroup, taken when the kernel RUNS; with k == 1 (every call opens and closes a window: the mean
+// of one gradient is the gradient) a workgroup returns before its first load of either tensor
+__global__ __launch_bounds__(256) void accum_multi_kernel(PairArgs a, const int* __restrict__ state) {
+  const int t = blockIdx.y;
+  if (t >= a.n) return;
+  const int k = state[ACC_K], j = state[ACC_J];
+  if (k <= 1) return;
+  const bool closing = j + 1 >= k;
+  const float inv_k = ((const float*)state)[ACC_INV_K];
+  if (j == 0) pair_tensor(a.a[t], a.b[t], a.numel[t], AccumOp<false>{closing, inv_k});
+  else pair_tensor(a.a[t], a.b[t], a.numel[t], AccumOp<true>{closing, inv_k});
+}
+
+// one workgroup, stream-ordered behind the folds of a call: the window moves on, written by lane 0 with ordinary stores
+__global__ __launch_bounds__(64) void accum_advance_kernel(int* __restrict__ state) {
+  if (threadIdx.x != 0) return;
+  const int k = state[ACC_K], j = state[ACC_J];
+  const int closing = j + 1 >= k;
+  state[ACC_J] = closing ? 0 : j + 1;
+  state[ACC_WINDOWS] += closing;
+}
+
+extern "C" int fst_accum_multi(float* const* acc_host, float* const* g_host, const int64_t* numel_host, int n_tensors, void* state_dev,
+                               int advance, void* stream) {
+  if (check_pairs("fst_accum_multi", acc_host, g_host, numel_host, nullptr, n_tensors)) return -1;
+  FST_REQUIRE(state_dev && ((uintptr_t)state_dev & 15) == 0, "fst_accum_multi: null state block, or one off a 16-byte boundary");
+  for (int base = 0; base < n_tensors; base += NF_MAX_T) {
+    PairArgs a;
+    fill_pairs(a, acc_host, g_host, numel_host, nullptr, base, n_tensors);
+    hipLaunchKernelGGL(accum_multi_kernel, dim3((unsigned)group_launch_bx(numel_host + base, a.n), (unsigned)a.n), dim3(256), 0,
+                       (hipStream_t)stream, a, (const int*)state_dev);
+    FST_LAUNCH_CHECK();
+  }
+  if (advance) {
+    hipLaunchKernelGGL(accum_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (int*)state_dev);
     FST_LAUNCH_CHECK();
   }
   return 0;

@@ -30,6 +30,10 @@ words); ``scale_by_group`` multiplies the tensors by those factors, read when th
 Weight averaging.  ``ema_update`` keeps an exponential moving average of many tensors per group, its weight derived on the device
 from the words of a ``WeightAverage`` (decay, warm-up, update counts) when the kernels run; ``swap_tensors`` exchanges two lists of
 tensors in place — the averages into the modules' own storage for evaluation, and back.
+
+Gradient accumulation.  ``accumulate`` folds gradients into fp32 accumulators over a window of k calls and leaves their mean in
+the gradient tensors on the call that closes it; the position in the window is a word of a ``GradAccumulation`` that the kernels
+read when they run, so one captured launch series serves every position.
 """
 from __future__ import annotations
 
@@ -633,3 +637,99 @@ def swap_tensors(a: Sequence[torch.Tensor], b: Sequence[torch.Tensor]) -> None:
         _lib.require_gpu_tensor(x, f"swap_tensors: a {i}"); _lib.require_gpu_tensor(y, f"swap_tensors: b {i}")
     _lib.check(_lib.load().fst_swap_multi(_ptr_array([x for x, _ in keep]), _ptr_array([y for _, y in keep]),
                                           _i64_array([x.numel() for x, _ in keep]), len(keep), _lib.stream_ptr()), "fst_swap_multi")
+
+
+# ---- gradient accumulation: one optimiser step over a window of k calls, the position in the window a device word
+class GradAccumulation:
+    """The device words of the gradient accumulation, one 16-byte aligned block of eight 4-byte words (``fst_accum_multi``'s
+    ``state_dev``): ``k`` (int32, calls per window), ``j`` (int32, folds done in the open window), ``inv_k`` (fp32,
+    ``float32(1 / k)``) and ``windows`` (int32, closed windows) are views of ``words``; four words are reserved.  ``steps_host`` is
+    what ``k`` holds and ``pending`` what ``j`` holds once the stream has run what was issued, both known without reading them
+    back: ``accumulate(..., advance=True)`` moves ``pending`` with the launch it issues, and whoever replays a captured such launch
+    calls ``advance_host()`` beside it.  ``set_steps`` changes ``k`` and ``inv_k`` with one stream-ordered copy, which a graph replayed
+    afterwards reads."""
+
+    def __init__(self, device, steps: int = 1):
+        self.device = torch.device(device)
+        self.steps_host, self.pending = self._checked(steps), 0
+        self.words = torch.zeros(8, dtype=torch.int32, device=device)
+        if self.words.data_ptr() % 16:
+            raise RuntimeError("GradAccumulation: the allocator returned a block off a 16-byte boundary")
+        self.k, self.j, self.windows = self.words[0:1], self.words[1:2], self.words[3:4]
+        self.inv_k = self.words[2:3].view(torch.float32)
+        self.words[:3].copy_(self._head())
+
+    @staticmethod
+    def _checked(steps) -> int:
+        if isinstance(steps, bool) or not isinstance(steps, int) or not 1 <= steps < 1 << 24:
+            raise ValueError(f"gradient accumulation: steps must be an integer in 1..2^24 - 1, got {steps!r}")
+        return steps
+
+    def _head(self) -> torch.Tensor:
+        """k, j = 0 and inv_k: the first three words between two windows."""
+        inv = torch.tensor([np.float32(1.0) / np.float32(self.steps_host)], dtype=torch.float32)
+        return torch.cat([torch.tensor([self.steps_host, 0], dtype=torch.int32), inv.view(torch.int32)])
+
+    def set_steps(self, steps: int) -> bool:
+        """Calls per window from now on.  Between windows only (``pending == 0``, where ``j`` is 0 as well: the one copy carries
+        ``k``, that 0 and ``inv_k`` from pinned memory, on the current stream and without waiting for it).  Returns whether
+        anything changed."""
+        steps = self._checked(steps)
+        if self.pending != 0:
+            raise RuntimeError(f"gradient accumulation: a window is open ({self.pending} of {self.steps_host} calls done); change "
+                               "the number of steps between windows")
+        if steps == self.steps_host:
+            return False
+        self.steps_host = steps
+        host = self._head()
+        if self.words.is_cuda:
+            host = host.pin_memory()                                          # a pageable source would make the copy wait for the device
+        self.words[:3].copy_(host, non_blocking=True)
+        return True
+
+    @property
+    def closing_next(self) -> bool:
+        """Will the next advancing call close its window?"""
+        return self.pending + 1 >= self.steps_host
+
+    def advance_host(self) -> None:
+        self.pending = 0 if self.closing_next else self.pending + 1
+
+
+@torch.no_grad()
+def accumulate(acc: Sequence[torch.Tensor], grads: Sequence[torch.Tensor], state: GradAccumulation, advance: bool = True) -> None:
+    """Fold ``grads[i]`` into ``acc[i]`` (fp32, contiguous, same shapes) at the window position the device words of ``state`` hold
+    when the kernels run: ``acc = g`` on a window's first call (``acc`` is not read), ``acc += g`` on the others, and on the call
+    that closes the window also ``g = acc · inv_k`` in place; on every other call ``g`` is only read, and with ``k == 1`` nothing
+    is touched.  ``advance``: move the window on behind the folds (``j`` and ``state.pending``); several calls with
+    ``advance=False`` and a last one with ``advance=True`` all fold at the same position.  One ``fst_accum_multi`` launch per 64
+    pairs; nothing waits for the device.  On CPU tensors the same recurrence in plain torch fp32 — every operation is one IEEE
+    addition or multiplication, so the bits are the kernel's."""
+    _pairs("accumulate", acc, grads)
+    keep = [(a, g) for a, g in zip(acc, grads) if a.numel() > 0]
+    if any(a.device != state.words.device for a, _ in keep):
+        raise ValueError(f"accumulate: the tensors must live on the state's device, {state.words.device}")
+    if state.device.type != "cuda":
+        k, j = int(state.k), int(state.j)
+        first, closing = j == 0, j + 1 >= k
+        if k > 1:
+            for a, g in keep:
+                if first:
+                    a.copy_(g)
+                else:
+                    a.add_(g)
+                if closing:
+                    torch.mul(a, state.inv_k[0], out=g)
+        if advance:
+            state.j.fill_(0 if closing else j + 1)
+            state.windows.add_(int(closing))
+            state.advance_host()
+        return
+    from . import _lib
+    for i, (a, g) in enumerate(keep):
+        _lib.require_gpu_tensor(a, f"accumulate: acc {i}"); _lib.require_gpu_tensor(g, f"accumulate: grad {i}")
+    _lib.check(_lib.load().fst_accum_multi(_ptr_array([a for a, _ in keep]), _ptr_array([g for _, g in keep]),
+                                           _i64_array([a.numel() for a, _ in keep]), len(keep), state.words.data_ptr(),
+                                           int(bool(advance)), _lib.stream_ptr()), "fst_accum_multi")
+    if advance and not _capturing(state.words):                               # a captured launch has not run: its replayer counts
+        state.advance_host()

@@ -23,6 +23,10 @@ trainer's state, decided on the device, in eager and in replayed steps alike.
 Gradient norms and clipping (``JointTrainer.enable_grad_clip()``): per-module L2 norms of the gradients the optimisers are about
 to read in every report, and caps per module and on the whole that scale those gradients in place — what
 ``torch.nn.utils.clip_grad_norm_`` does with a host decision — computed and applied on the device, under graph replay too.
+
+Gradient accumulation (``enable_grad_accumulation(steps)``, both trainers): one optimiser step over ``steps`` consecutive calls,
+each on its own micro-batch; the gradients, GradNorm's ten scalars and the loss scalars are folded into fp32 accumulators at a
+window position kept on the device, and everything behind the backward runs on the call that closes the window, on their means.
 """
 from __future__ import annotations
 
@@ -39,8 +43,8 @@ from .cdan import CDAN, RandomLayer
 from .cpc import CPC
 from . import dist as _dist
 from .dist import GradBucket
-from .optim import (MAX_GROUPS, AnomalyGuard, FusedRMSprop, GradClip, SharedStepAdam, WeightAverage, count_nonfinite, ema_update,
-                    guard_copy, push_lr, rmsprop_step_many, scale_by_group, sumsq_norms, swap_tensors)
+from .optim import (MAX_GROUPS, _capturing, AnomalyGuard, FusedRMSprop, GradAccumulation, GradClip, SharedStepAdam, WeightAverage, accumulate,
+                    count_nonfinite, ema_update, guard_copy, push_lr, rmsprop_step_many, scale_by_group, sumsq_norms, swap_tensors)
 from .os_cnn import OS_CNN, OS_CNN_res, build_layer_with_layer_parameter
 from .structure import generate_layer_parameter_list, layer_parameter_list_input_change, out_channels
 from .waveglow import WaveGlow, WaveGlowLoss
@@ -268,14 +272,84 @@ class _WeightAveraging:
                     t.copy_(sd["tensors"][k][n])
 
 
-class ClassifierTrainer(_WeightAveraging):
+class _GradAccumulating:
+    """Gradient accumulation of the two trainers: one optimiser step over a WINDOW of ``steps`` consecutive calls, each on its own
+    micro-batch.  A trainer supplies ``_ema_resident()`` (is a capture resident?) and ``device``; it calls ``_accum_fold`` behind a
+    micro-step's backward and runs its update only on the call that closes a window."""
+    grad_accumulation: Optional[GradAccumulation] = None                      # the device words; None while the mode is off
+    _accum: Dict[nn.Parameter, torch.Tensor] = {}                             # parameter -> its fp32 accumulator (addresses never change)
+
+    def enable_grad_accumulation(self, steps: int = 1) -> None:
+        """From now on ``steps`` consecutive calls of ``step`` / ``replay`` / ``phase_step`` form a window.  Every call runs its own
+        forward and backward unchanged — batch-coupled quantities (BatchNorm moments, CPC negatives, NoiseTransfer means, CDAN
+        sums) are per micro-batch, and what is stateful (BatchNorm running statistics, ``NoiseTransfer.advance``, the GRL counters)
+        advances per call — and then folds each gradient into a persistent fp32 accumulator: ``acc = g`` on a window's first
+        call, ``acc += g`` after; the call that closes the window writes ``g = acc · float32(1 / steps)`` back into the gradient
+        tensors and alone runs what follows the backward: the data-parallel all-reduce, ``on_grads_ready``, clip, guard,
+        GradNorm's weight update, the optimisers, the WGAN clamps, the roll-back and the weight average.  A call that does not
+        close a window changes no parameter, no optimiser moment, no GradNorm weight and no average.  The position in the window
+        is a device word (``optim.GradAccumulation``), so one captured micro-step serves every position; ``accum_pending`` is
+        its host mirror.  ``steps == 1`` computes the bits of the mode off.  ``set_grad_accumulation`` steers ``steps`` between
+        windows, under resident captures too.  Idempotent (a second call changes nothing, its argument included); raises while
+        a capture is resident, whose launches are the one-graph layout."""
+        if self.grad_accumulation is not None:
+            return
+        state = GradAccumulation(self.device, steps)                          # (refuses a bad count before anything changes)
+        if self._ema_resident():
+            raise RuntimeError("enable_grad_accumulation(): a capture is resident; enable the mode before capturing")
+        self._accum = {}
+        self.grad_accumulation = state
+
+    def set_grad_accumulation(self, steps: int) -> bool:
+        """Calls per window from now on; between windows only.  Legal while captures are resident: one stream-ordered copy into
+        the device words, which a graph replayed afterwards reads — no re-capture.  Returns whether the device words changed."""
+        if self.grad_accumulation is None:
+            raise RuntimeError("set_grad_accumulation(): call enable_grad_accumulation() first")
+        return self.grad_accumulation.set_steps(steps)
+
+    @property
+    def accum_pending(self) -> int:
+        """Calls done in the open window (0 between windows, and with the mode off)."""
+        return 0 if self.grad_accumulation is None else self.grad_accumulation.pending
+
+    def _accum_closed(self, what: str) -> None:
+        if self.accum_pending:
+            raise RuntimeError(f"{what}: a gradient-accumulation window is open ({self.accum_pending} of "
+                               f"{self.grad_accumulation.steps_host} calls done); close it first")
+
+    def _accum_fold(self, params, advance: bool) -> None:
+        """Fold the gradients of ``params`` at the window's current position; the accumulators are made at a parameter's first fold."""
+        acc, grads = [], []
+        for p in params:
+            if p.grad is None:
+                continue
+            if not p.grad.is_contiguous():
+                p.grad = p.grad.contiguous()
+            a = self._accum.get(p)
+            if a is None:
+                if _capturing(p.grad):
+                    raise RuntimeError("gradient accumulation: a gradient has no accumulator yet; run one eager window before capturing")
+                a = self._accum[p] = torch.empty_like(p.grad, memory_format=torch.contiguous_format)
+            acc.append(a); grads.append(p.grad)
+        accumulate(acc, grads, self.grad_accumulation, advance)
+
+
+def _enable_grad_accumulation(trainer, arg) -> None:
+    """The constructors' ``grad_accumulation=``: None / False, or the number of steps."""
+    if arg is None or arg is False:
+        return
+    trainer.enable_grad_accumulation(1 if arg is True else arg)
+
+
+class ClassifierTrainer(_WeightAveraging, _GradAccumulating):
     """S1 of the reference.  The anomaly guard (``JointTrainer.enable_anomaly_guard``) is not offered here: a non-finite batch
     reaches this trainer's parameters as it does in the reference.  Weight averaging (``enable_weight_average``) is, over the
-    groups "fe" and "clf"; its device words are ``weight_average``."""
+    groups "fe" and "clf"; its device words are ``weight_average``.  Gradient accumulation (``enable_grad_accumulation``) too."""
 
     def __init__(self, length: int, in_channel: int, n_class: int, device, bucket: Optional[GradBucket] = None,
-                 sync: str = "ddp", device_hparams: bool = False, weight_average=None):
-        """``weight_average``: ``enable_weight_average()`` at once — True, a decay, or a dict of its keyword arguments."""
+                 sync: str = "ddp", device_hparams: bool = False, weight_average=None, grad_accumulation=None):
+        """``weight_average``: ``enable_weight_average()`` at once — True, a decay, or a dict of its keyword arguments.
+        ``grad_accumulation``: ``enable_grad_accumulation()`` at once, with that many steps."""
         self.sync, self.device = sync, device
         fe_spec, clf_spec = specs_for(length, in_channel)
         self.fe = OS_CNN_res(fe_spec).to(device)
@@ -286,10 +360,12 @@ class ClassifierTrainer(_WeightAveraging):
         self.bucket = bucket
         self.fe.train(); self.clf.train()
         self._graph = None
+        self._graph_update = None                                             # gradient accumulation: the update's own graph
         self.device_hparams = False
         if device_hparams:
             self.enable_device_hparams()
         _enable_weight_average(self, weight_average)
+        _enable_grad_accumulation(self, grad_accumulation)
 
     def _ema_modules(self) -> Dict[str, nn.Module]:
         return {"fe": self.fe, "clf": self.clf}
@@ -312,25 +388,51 @@ class ClassifierTrainer(_WeightAveraging):
         return list(self.fe.parameters()) + list(self.clf.parameters())
 
     def step(self, x: torch.Tensor, y: torch.Tensor):
+        """One batch; with gradient accumulation one micro-batch, whose call updates only if it closes its window.  Returns
+        (loss, logits) of this call's batch."""
         self._ema_no_step("step()")
+        acc = self.grad_accumulation
+        closing = acc is None or acc.closing_next
+        loss, logits = self._fwd_bwd(x, y)
+        if acc is not None:
+            self._accum_fold(self.parameters(), advance=True)
+        if closing:
+            self._update()
+        return loss.detach(), logits.detach()
+
+    def _fwd_bwd(self, x: torch.Tensor, y: torch.Tensor):
+        """First half of a step: forward and backward.  With gradient accumulation the gradients of the call before are dropped
+        here, not behind the update: they stay alive for the update of a captured window, which is a graph of its own."""
+        if self.grad_accumulation is not None:
+            self.opt_fe.zero_grad(set_to_none=True); self.opt_clf.zero_grad(set_to_none=True)
         with _dist.global_batch(self.bucket if self.sync == "global" else None):
             with ops.pack_cache():
                 logits, _ = self.clf(self.fe(x))
                 loss = F.cross_entropy(logits, y)
                 loss.backward()
+        return loss, logits
+
+    def _update(self) -> None:
+        """Second half: the gradient all-reduce, both optimisers, then the weight average."""
         if self.bucket is not None:
             self.bucket.all_reduce(self.parameters())
         rmsprop_step_many([self.opt_fe, self.opt_clf])
-        self.opt_fe.zero_grad(set_to_none=True); self.opt_clf.zero_grad(set_to_none=True)
+        if self.grad_accumulation is None:
+            self.opt_fe.zero_grad(set_to_none=True); self.opt_clf.zero_grad(set_to_none=True)
         self._ema_update(("fe", "clf"))
-        return loss.detach(), logits.detach()
 
     # ---- single GPU: the whole step as one hipGraph (the eager step is launch-bound: ~300 launches for ~2 ms of GPU work)
     def capture(self, x: torch.Tensor, y: torch.Tensor, warmup: int = 3):
-        """Capture one step.  The learning rates are baked into the graph unless ``enable_device_hparams()`` ran before."""
+        """Capture one step.  The learning rates are baked into the graph unless ``enable_device_hparams()`` ran before.  With
+        gradient accumulation two graphs sharing a pool, the micro-step (forward, backward, fold) and the update, and a warm-up
+        of whole windows, so that the capture starts with the window closed."""
         self._ema_no_step("capture()")
         if self.bucket is not None:
             raise RuntimeError("ClassifierTrainer.capture(): single-GPU only (the DP step has an eager all-reduce)")
+        self._accum_closed("capture()")
+        acc = self.grad_accumulation
+        if acc is not None:
+            warmup = -(-warmup // acc.steps_host) * acc.steps_host
         self._g_x, self._g_y = x.clone(), y.clone()
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -340,12 +442,23 @@ class ClassifierTrainer(_WeightAveraging):
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self._graph = torch.cuda.CUDAGraph()
+        self._graph_update = None
+        if acc is None:
+            with torch.cuda.graph(self._graph, capture_error_mode=_CAPTURE_MODE):
+                self._g_out = self.step(self._g_x, self._g_y)
+            return
         with torch.cuda.graph(self._graph, capture_error_mode=_CAPTURE_MODE):
-            self._g_out = self.step(self._g_x, self._g_y)
+            loss, logits = self._fwd_bwd(self._g_x, self._g_y)
+            self._accum_fold(self.parameters(), advance=True)
+            self._g_out = (loss.detach(), logits.detach())
+        self._graph_update = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self._graph_update, pool=self._graph.pool(), capture_error_mode=_CAPTURE_MODE):
+            self._update()
 
     def replay(self, x: torch.Tensor, y: torch.Tensor):
         """One captured step on a new batch of the captured shape; returns (loss, logits) in static buffers.  With
-        ``device_hparams`` it runs at the optimisers' current ``group["lr"]``, otherwise at the captured rates."""
+        ``device_hparams`` it runs at the optimisers' current ``group["lr"]``, otherwise at the captured rates.  With gradient
+        accumulation the micro-step graph, and the update graph behind it on the call that closes a window."""
         self._ema_no_step("replay()")
         if self._graph is None:
             raise RuntimeError("call capture() first")
@@ -353,6 +466,11 @@ class ClassifierTrainer(_WeightAveraging):
         if self.device_hparams:
             push_lr((self.opt_fe, self.opt_clf))
         self._graph.replay()
+        if self._graph_update is not None:
+            closing = self.grad_accumulation.closing_next
+            self.grad_accumulation.advance_host()
+            if closing:
+                self._graph_update.replay()
         return self._g_out
 
 
@@ -366,6 +484,13 @@ def _enable_weight_average(trainer, arg) -> None:
         trainer.enable_weight_average(**arg)
     else:
         trainer.enable_weight_average(decay=arg)
+
+
+class _WindowOpens:
+    """``guard_copy``'s predicate word of a save under gradient accumulation: the window's position ``j`` in the place of a verdict."""
+
+    def __init__(self, acc: GradAccumulation):
+        self.verdict = acc.j
 
 
 @dataclass
@@ -385,7 +510,7 @@ class JointConfig:
     nf_end_std: float = 0.0       # >0: draw WN.end (zero-init in the reference) so the flow is non-degenerate
 
 
-class JointTrainer(_WeightAveraging):
+class JointTrainer(_WeightAveraging, _GradAccumulating):
     MODULES = ("fe_t", "clf_t", "fe_s", "dimunif", "clf_s", "probtransfer", "nf", "noise", "ad_net", "fd_s", "cpc")
     LRS = {"fe_t": 0.001, "clf_t": 0.003, "fe_s": 0.001, "dimunif": 0.001, "clf_s": 0.003, "probtransfer": 0.001,
            "nf": 0.001, "noise": 0.005, "ad_net": 0.001, "fd_s": 0.001}       # train_and_test.py:97-106
@@ -396,13 +521,14 @@ class JointTrainer(_WeightAveraging):
 
     def __init__(self, cfg: JointConfig, device, bucket: Optional[GradBucket] = None, fe_t_spec=None, clf_spec=None,
                  fe_s_spec=None, sync: str = "ddp", device_hparams: bool = False, anomaly_guard: bool = False, grad_clip=None,
-                 weight_average=None):
+                 weight_average=None, grad_accumulation=None):
         """``sync`` (with a bucket): "ddp" = per-rank batch statistics (SURVEY §8e mode A); "global" = every
         batch-coupled quantity over the samples of all ranks (mode B, eager only) — N ranks reproduce the
         single-process step on the concatenated batch.  ``device_hparams``: ``enable_device_hparams()`` at once;
         ``anomaly_guard``: ``enable_anomaly_guard()`` at once.  ``grad_clip``: ``enable_grad_clip()`` at once — True for norms
         only, a number for ``max_norm``, or a dict of its keyword arguments.  ``weight_average``: ``enable_weight_average()`` at
-        once — True, a decay, or a dict of its keyword arguments."""
+        once — True, a decay, or a dict of its keyword arguments.  ``grad_accumulation``: ``enable_grad_accumulation()`` at once,
+        with that many steps."""
         if sync not in ("ddp", "global"):
             raise ValueError(f"sync must be 'ddp' or 'global', got {sync!r}")
         self.cfg, self.device, self.bucket, self.sync = cfg, device, bucket, sync
@@ -458,6 +584,7 @@ class JointTrainer(_WeightAveraging):
         self._guard_live = None                                               # ... (live, shadow) lists of the step's save
         self._guard_fwd = ()                                                  # ... fp32 buffers the forward writes, of that save
         self._guard_losses = ()                                               # ... loss scalars of a phase step, for the counts
+        self._accum_scalars = None                                            # gradient accumulation: accumulators of the 10 GradNorm scalars and the 9 losses
         self.grad_clip = False
         self._clip: Optional[GradClip] = None                                 # grad_clip: limits, norms and factors on the device
         self._clip_max: Optional[float] = None                                # ... the cap on the norm over all modules (None: none)
@@ -481,6 +608,7 @@ class JointTrainer(_WeightAveraging):
             else:
                 self.enable_grad_clip(max_norm=grad_clip)
         _enable_weight_average(self, weight_average)
+        _enable_grad_accumulation(self, grad_accumulation)
 
     # ------------------------------------------------------------------ weight averaging (the methods are _WeightAveraging's)
     def _ema_modules(self) -> Dict[str, nn.Module]:
@@ -541,7 +669,13 @@ class JointTrainer(_WeightAveraging):
         return None if self._guard is None else self._guard.skipped
 
     def _guard_save(self) -> None:
-        """Start of a guarded step: copy the state that is not guarded at its writer into its shadows."""
+        """Start of a guarded step: copy the state that is not guarded at its writer into its shadows.  With gradient
+        accumulation only the call that opens a window saves: eagerly a host decision, under capture the copy's own predicate
+        on the window's position word, so that a skipped window is rolled back to before its first micro-step."""
+        acc = self.grad_accumulation
+        capturing = acc is not None and _capturing(acc.words)
+        if acc is not None and not capturing and acc.pending != 0:
+            return
         live: List[torch.Tensor] = []
         names: List[str] = []
         fwd = []                                                              # fp32 state the forward pass writes
@@ -572,7 +706,10 @@ class JointTrainer(_WeightAveraging):
                     raise RuntimeError(f"anomaly guard: no shadow buffer for {n} yet; run one eager step before capturing")
                 sh = self._shadow[n] = torch.empty_like(t, memory_format=torch.contiguous_format)
             shadow.append(sh)
-        guard_copy(shadow, live)
+        if acc is not None and capturing:
+            guard_copy(shadow, live, _WindowOpens(acc), when=False)           # copies where j == 0 when the kernel runs
+        else:
+            guard_copy(shadow, live)
         self._guard_live = (live, shadow)
 
     def _guard_scan(self, modules, gradnorm, losses) -> None:
@@ -775,6 +912,7 @@ class JointTrainer(_WeightAveraging):
         """Copy of every tensor the step mutates (parameters, BN buffers, optimiser moments, GradNorm weights,
         NoiseTransfer sums) plus the host-side counters."""
         self._ema_no_step("snapshot()")
+        self._accum_closed("snapshot()")
         host = {"noise": (self.m["noise"].time, self.m["noise"].cal_num_target, self.m["noise"].cal_num_source),
                 "ad": self.m["ad_net"].iter_num, "fd": self.m["fd_s"].iter_num}
         return {"t": {k: v.detach().clone() for k, v in self._state_tensors().items()}, "host": host}
@@ -804,8 +942,11 @@ class JointTrainer(_WeightAveraging):
         cannot resume would be a gap of this build, not of the reference.  Once ``make_schedulers()`` has run, also
         "schedules": the eleven schedulers' state, CPC's learning rate (the RMSprops' are in their ``param_groups``), the epoch of
         the last step and its loss coefficients.  With ``enable_grad_clip()`` on, also "grad_clip": its limits; with
-        ``enable_weight_average()`` on, also "weight_average": decay, warm-up flag, update counts and the averaged tensors."""
+        ``enable_weight_average()`` on, also "weight_average": decay, warm-up flag, update counts and the averaged tensors; with
+        ``enable_grad_accumulation()`` on, also "grad_accumulation": its steps.  Raises while an accumulation window is open:
+        half a window is no state a run could resume from."""
         self._ema_no_step("state_dict()")
+        self._accum_closed("state_dict()")
         cpu = lambda t: t.detach().cpu().clone()
         cpc = self.opt_cpc
         noise = self.m["noise"]
@@ -838,6 +979,7 @@ class JointTrainer(_WeightAveraging):
                               "coefficients": None if self._sched_epoch is None else loss_coefficients(self._sched_epoch)}}),
             **({"grad_clip": {"max_norm": self._clip_max, "per_module": dict(self._clip_per)}} if self.grad_clip else {}),
             **({"weight_average": self._ema_state_dict()} if self.weight_average is not None else {}),
+            **({"grad_accumulation": {"steps": self.grad_accumulation.steps_host}} if self.grad_accumulation is not None else {}),
         }
 
     def load_state_dict(self, sd: dict) -> None:
@@ -850,6 +992,7 @@ class JointTrainer(_WeightAveraging):
         (``Optimizer.load_state_dict`` replaces the tensors), so a resident phase graph would update dead moments:
         every phase capture is dropped here and ``replay_phase`` raises until ``capture_phase`` has run again."""
         self._ema_no_step("load_state_dict()")
+        self._accum_closed("load_state_dict()")
         self.release_phase()
         dev = self.device
         for k in self.MODULES:
@@ -894,8 +1037,13 @@ class JointTrainer(_WeightAveraging):
             self.set_grad_clip(max_norm=sd["grad_clip"]["max_norm"], per_module=sd["grad_clip"]["per_module"])
         if "weight_average" in sd:                                            # likewise; restored in place
             self._ema_load_state_dict(sd["weight_average"])
+        if "grad_accumulation" in sd:                                         # likewise; under a resident capture a copy into its words
+            if self.grad_accumulation is None:
+                self.enable_grad_accumulation(sd["grad_accumulation"]["steps"])
+            self.set_grad_accumulation(sd["grad_accumulation"]["steps"])
 
     def save_state(self, path: str) -> None:
+        self._accum_closed("save_state()")
         torch.save(self.state_dict(), path)
 
     def load_state(self, path: str) -> None:
@@ -986,9 +1134,18 @@ class JointTrainer(_WeightAveraging):
 
     def phase_step(self, phase: str, x_t, y_t, x_s, y_s, t_samples=(None, None)):
         """One batch of a pre-training phase: forward, backward, the phase's optimisers, zero_grad (eager; ``capture_phase`` /
-        ``replay_phase`` issue the same launches as one hipGraph)."""
+        ``replay_phase`` issue the same launches as one hipGraph).  With gradient accumulation one micro-batch of a window: the
+        report is this call's own plus "accum_index", and the update, with what it adds to the report, runs on the call that
+        closes the window.  Captured phases do not accumulate: ``capture_phase`` / ``replay_phase`` raise at more than one step."""
         self._ema_no_step("phase_step()")
+        acc = self.grad_accumulation
+        closing = acc is None or acc.closing_next
         report = self._phase_fwd_bwd(phase, x_t, y_t, x_s, y_s, t_samples)
+        if acc is not None:                                                   # a micro-step of a window: only its last call updates
+            self._accum_fold(self.parameters(), advance=True)
+            report["accum_index"] = acc.j[0].clone()
+            if not closing:
+                return report
         if self.bucket is not None:
             self.bucket.all_reduce(self.parameters())
         self._phase_update(phase)
@@ -1060,6 +1217,7 @@ class JointTrainer(_WeightAveraging):
             raise RuntimeError("sync='global' (mode B) puts collectives inside autograd: run it eagerly with phase_step()")
         if warmup < 1:
             raise ValueError("capture_phase(): at least one warm-up step (it creates the optimiser moments the graph updates)")
+        self._accum_phase_graphs("capture_phase()")
         self.release_phase(phase)
         dev = self.device
         gi = {"x_t": x_t.clone(), "y_t": y_t.clone(), "x_s": x_s.clone(), "y_s": y_s.clone(),
@@ -1082,7 +1240,8 @@ class JointTrainer(_WeightAveraging):
         main.wait_stream(side)
         torch.cuda.synchronize()
         # static report: the graphs' own outputs live in the shared pool, where a later capture may reuse what this one frees
-        keys = [k for k in keys if k not in ("skipped", "anomaly", "grad_l2", "clip_coef", "ema_weight", "ema_steps")]   # static tensors of their own
+        keys = [k for k in keys if k not in ("skipped", "anomaly", "grad_l2", "clip_coef", "ema_weight", "ema_steps",   # static tensors of their own
+                                          "accum_index")]                                # (the eager warm-up's; a captured phase is a whole step)
         out = torch.zeros(len(keys), device=dev)
         g_rep = {} if self._guard is None else {"skipped": torch.zeros((), dtype=torch.int32, device=dev),
                                                 "anomaly": torch.zeros(len(self.ANOMALY_GROUPS), dtype=torch.int32, device=dev)}
@@ -1136,6 +1295,7 @@ class JointTrainer(_WeightAveraging):
         ``phase_step``: its losses and "total"), valid until this phase's next replay.  Nothing here waits for the device.
         ``.grad`` is left alone: the gradients are in the tensors the capture kept."""
         self._ema_no_step("replay_phase()")
+        self._accum_phase_graphs("replay_phase()")
         rec = self._phase.get(phase)
         if rec is None:
             if phase not in self.PHASES:
@@ -1159,6 +1319,13 @@ class JointTrainer(_WeightAveraging):
             self.bucket.all_reduce_grads(rec["grads"])
             rec["graphs"][1].replay()
         return rec["report"]
+
+    def _accum_phase_graphs(self, what: str) -> None:
+        """A captured phase is one whole step per replay: the phase graphs have no micro-step / update split."""
+        self._accum_closed(what)
+        if self.grad_accumulation is not None and self.grad_accumulation.steps_host > 1:
+            raise RuntimeError(f"{what}: captured phases do not accumulate gradients ({self.grad_accumulation.steps_host} steps per "
+                               "window are set); run the phase eagerly with phase_step()")
 
     def release_phase(self, phase: Optional[str] = None) -> None:
         """Drop the capture of ``phase`` (of every phase if None); a phase that is not captured is left as it is."""
@@ -1186,12 +1353,24 @@ class JointTrainer(_WeightAveraging):
         A1 = forward + the full backward;  [the gradient bucket's all-reduce starts on a side stream]
         A2 = GradNorm's partial backward passes (they never touch ``.grad``: they overlap the all-reduce);
         [wait for the bucket; average the 10 GradNorm scalars]  B = GradNorm weight update + optimisers."""
+        acc = self.grad_accumulation
+        closing = acc is None or acc.closing_next                             # the collectives and B: on the call that closes a window
         with _dist.global_batch(self.bucket if self.sync == "global" else None), self._step_scope():
             state = self._step_part_a1(x_t, y_t, x_s, y_s, epoch, t_samples, noise_ratios)
-            self._reduce_begin()
+            if closing:
+                self._reduce_begin()
             mid = self._step_part_a2(state)
+        if not closing:
+            return self._micro_report(mid)
         self._reduce_end(mid)
         return self._step_part_b(mid)
+
+    @staticmethod
+    def _micro_report(mid):
+        """What a call that does not close its window returns: this micro-batch's losses and aux entries, and the position."""
+        report = dict(mid["report"])
+        report["accum_index"] = mid["accum_index"]
+        return report
 
     def _step_scope(self):
         """One scope for forward and every backward pass of a step: weights packed once, the flow's weight-norm fold and the
@@ -1219,6 +1398,8 @@ class JointTrainer(_WeightAveraging):
                 o.zero_grad(set_to_none=True)
             self.opt_cpc.zero_grad(set_to_none=True)
             total.backward(retain_graph=True)
+        if self.grad_accumulation is not None:                                # every .grad of the step is final here: A2 never touches one
+            self._accum_fold(self.parameters(), advance=False)
         return {"L": L, "aux": aux, "lt": lt, "ls": ls}
 
     def _step_part_a2(self, state):
@@ -1247,7 +1428,19 @@ class JointTrainer(_WeightAveraging):
         report.update({k: v.detach() for k, v in aux.items()})
         # scalars that must be identical on every rank: loss values and gradient-norm bases (10 floats)
         scal = torch.cat([lt.detach(), ls.detach(), base_t, base_s]).contiguous()
-        return {"report": report, "scal": scal, "loss_keys": tuple(L)}
+        mid = {"report": report, "scal": scal, "loss_keys": tuple(L)}
+        acc = self.grad_accumulation
+        if acc is not None:
+            # the ten scalars and the nine losses are averaged over the window as the gradients are, at the same position: this
+            # fold is the one that moves the window on
+            losses = torch.stack([L[k].detach().float() for k in L]).contiguous()
+            if self._accum_scalars is None:
+                if _capturing(scal):
+                    raise RuntimeError("gradient accumulation: run one eager window before capturing")
+                self._accum_scalars = (torch.empty_like(scal), torch.empty_like(losses))
+            accumulate(self._accum_scalars, (scal, losses), acc, advance=True)
+            mid["window_losses"], mid["accum_index"] = losses, acc.j[0].clone()
+        return mid
 
     def _step_part_a(self, x_t, y_t, x_s, y_s, epoch, t_samples, noise_ratios):
         with self._step_scope():
@@ -1286,7 +1479,8 @@ class JointTrainer(_WeightAveraging):
         if self._clip is not None:
             self._clip_grads(self.MODULES)
         if guard is not None:
-            self._guard_scan(self.MODULES, (scal, self.w_t.grad, self.w_s.grad), [mid["report"][k] for k in mid["loss_keys"]])
+            losses = [mid["window_losses"]] if "window_losses" in mid else [mid["report"][k] for k in mid["loss_keys"]]
+            self._guard_scan(self.MODULES, (scal, self.w_t.grad, self.w_s.grad), losses)
             if first and int(guard.verdict) != 0:                             # the one host read: only a COMPLETED step sets them
                 self.init_t = self.init_s = None
         self.opt_w_t.step(); self.opt_w_s.step()
@@ -1317,6 +1511,8 @@ class JointTrainer(_WeightAveraging):
             report.update(self._ema_report())
         if guard is not None:
             report.update(self._guard_report())
+        if "window_losses" in mid:
+            report.update({"accum_index": mid["accum_index"], "window_losses": mid["window_losses"]})
         return report
 
     # ------------------------------------------------------------------ hipGraph: capture once, replay per step
@@ -1331,8 +1527,16 @@ class JointTrainer(_WeightAveraging):
         ``group["lr"]`` and ``replay(..., epoch=)`` at that epoch's coefficients, with no re-capture (the GRL coefficients and the
         GradNorm-weight Adams' rates stay baked).
         Single GPU: one graph.  Data parallel: three graphs (A1 forward + backward, A2 GradNorm's partial passes, B update)
-        with the eager RCCL collectives between them, the gradient all-reduce overlapping A2 on a side stream."""
+        with the eager RCCL collectives between them, the gradient all-reduce overlapping A2 on a side stream.
+        With gradient accumulation, single GPU: two graphs sharing a pool — the micro-step (A1, the fold of the gradients, A2, the
+        fold of the scalars, which moves the window on) and the update (B) — of which ``replay`` launches the first on every call
+        and the second on the calls that close a window; data parallel: the three graphs, the folds at the end of A1 and of A2.
+        The warm-up then runs whole windows (``warmup`` rounded up), so that the capture starts with the window closed."""
         self._ema_no_step("capture()")
+        self._accum_closed("capture()")
+        acc = self.grad_accumulation
+        if acc is not None:
+            warmup = -(-warmup // acc.steps_host) * acc.steps_host
         if self.sync == "global" and self.bucket is not None and self.bucket.world > 1:
             raise RuntimeError("sync='global' (mode B) puts collectives inside autograd: run it eagerly with step()")
         dev = self.device
@@ -1355,10 +1559,19 @@ class JointTrainer(_WeightAveraging):
             raise RuntimeError("capture(): the anomaly guard skipped every warm-up step (non-finite gradients), so the GradNorm "
                                "reference losses init_t / init_s do not exist yet; capture on a batch the step completes on")
         self._replay_inputs(x_t, y_t, x_s, y_s, (0, 0))
-        if self.bucket is None:
+        if self.bucket is None and acc is None:
             self._graphs = [torch.cuda.CUDAGraph()]
             with torch.cuda.graph(self._graphs[0], capture_error_mode=_CAPTURE_MODE):
                 self._g_out = self._graph_body()
+        elif self.bucket is None:
+            gm, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+            gi = self._g_in
+            with torch.cuda.graph(gm, capture_error_mode=_CAPTURE_MODE):
+                self._g_mid = self._step_part_a(gi["x_t"], gi["y_t"], gi["x_s"], gi["y_s"], self._g_epoch, (gi["t"][0], gi["t"][1]),
+                                                (gi["r"][0], gi["r"][1]))
+            with torch.cuda.graph(gb, pool=gm.pool(), capture_error_mode=_CAPTURE_MODE):
+                self._g_out = self._step_part_b(self._g_mid)
+            self._graphs = [gm, gb]
         else:
             ga1, ga2, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
             gi = self._g_in
@@ -1375,6 +1588,8 @@ class JointTrainer(_WeightAveraging):
             with torch.cuda.graph(gb, pool=pool, capture_error_mode=_CAPTURE_MODE):
                 self._g_out = self._step_part_b(self._g_mid)
             self._graphs = [ga1, ga2, gb]
+        if acc is not None:
+            self._g_micro = self._micro_report(self._g_mid)
         return self
 
     def _graph_body(self):
@@ -1396,7 +1611,9 @@ class JointTrainer(_WeightAveraging):
     def replay(self, x_t, y_t, x_s, y_s, t_samples, epoch: Optional[int] = None):
         """One step through the captured graph(s); returns the (static) report tensors.  With ``device_hparams`` the step runs at
         the optimisers' current ``group["lr"]`` and, when ``epoch`` is given, at ``loss_coefficients(epoch)``; without it, at the
-        captured values, and an ``epoch`` other than the captured one raises."""
+        captured values, and an ``epoch`` other than the captured one raises.  With gradient accumulation a call that does not
+        close its window returns the micro-step's report (this batch's losses and aux entries, "accum_index") and launches no
+        update; the closing call returns the whole report, with "window_losses"."""
         self._ema_no_step("replay()")
         if self._graphs is None:
             raise RuntimeError("call capture() first")
@@ -1408,10 +1625,19 @@ class JointTrainer(_WeightAveraging):
             raise ValueError(f"replay(epoch={epoch}): the graph was captured at epoch {self._g_epoch} and its loss coefficients "
                              "are baked in; re-capture, or enable_device_hparams() before capturing")
         self._replay_inputs(x_t, y_t, x_s, y_s, t_samples)
+        acc = self.grad_accumulation
+        closing = acc is None or acc.closing_next
         self._graphs[0].replay()
         if len(self._graphs) == 3:
-            self._reduce_begin()                                              # the bucket's all-reduce, on its side stream ...
+            if closing:
+                self._reduce_begin()                                          # the bucket's all-reduce, on its side stream ...
             self._graphs[1].replay()                                          # ... under GradNorm's partial backward passes
+        if acc is not None:
+            acc.advance_host()                                                # the captured fold of the scalars moved the window on
+            if not closing:
+                return self._g_micro
+        if len(self._graphs) == 3:
             self._reduce_end(self._g_mid)
-            self._graphs[2].replay()
+        if len(self._graphs) > 1:
+            self._graphs[-1].replay()
         return self._g_out

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FST_ABI_VERSION 23
+#define FST_ABI_VERSION 24
 
 int fst_version(void);
 const char* fst_last_error(void);
@@ -686,6 +686,24 @@ int fst_scale_multi(float* const* x_host, const int64_t* numel_host, const int32
 int fst_ema_multi(float* const* avg_host, const float* const* live_host, const int64_t* numel_host, const int32_t* group_host,
                   int n_tensors, int32_t active_mask, void* state_dev, const int32_t* verdict_dev, void* stream);
 int fst_swap_multi(float* const* a_host, float* const* b_host, const int64_t* numel_host, int n_tensors, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Gradient accumulation on the device (ABI v24): one optimiser step over a WINDOW of k calls, each on its own micro-batch, whose
+ * position in the window is a device word, so that one captured launch series serves every position.  Pairs (acc, g) as for
+ * ema_multi: fp32, 4-byte aligned pointers that do not overlap, 0 < element count < 2^31, at most 64 pairs per launch, every entry
+ * and the state pointer validated on the host before the first launch: a refused call has written nothing.
+ * state_dev is a 16-byte aligned block of eight 4-byte words: [0] k (int32 >= 1), [1] j (int32, folds done in the open window,
+ * 0 <= j < k), [2] inv_k (fp32, written by the host together with k: float32(1 / k)), [3] windows (int32, closed windows),
+ * [4..7] reserved, zero.  From the words as they are when a kernel RUNS, first = (j == 0) and closing = (j + 1 >= k):
+ *   first: acc = g (acc is not read: no zero fill is ever needed);  otherwise acc = acc + g, one fp32 addition rounded once;
+ *   closing: then g = acc * inv_k in place, one fp32 multiplication rounded once;  on every other call g is only read.
+ * With k == 1 a workgroup returns before it loads anything: g and acc keep every bit.  NaN and inf are not special-cased.
+ * With advance != 0 a one-workgroup launch behind the folds sets j = closing ? 0 : j + 1 and windows += closing; n_tensors == 0
+ * with advance runs that launch alone.  Calls with advance == 0 followed by one with advance != 0 all see the same j.
+ * Pairs whose two pointers are 16-byte aligned move in 16-byte accesses, all others in 4-byte ones.
+ * ------------------------------------------------------------------------------------------- */
+int fst_accum_multi(float* const* acc_host, float* const* g_host, const int64_t* numel_host, int n_tensors, void* state_dev,
+                    int advance, void* stream);
 
 #ifdef __cplusplus
 }
