@@ -17,7 +17,8 @@ from .step import ClassifierTrainer, JointConfig, JointTrainer, specs_for
 from .optim import (AnomalyGuard, GradAccumulation, GradClip, WeightAverage, accumulate, clip_coefficients, count_nonfinite, ema_update,
                     scale_by_group, sumsq_norms, swap_tensors)
 from .dist import GradBucket, shard_batch
-from .data import DeviceLoader, TestData, TrainData, load_ts, parse_ts
+from .data import DeviceDataset, DeviceLoader, EpochFeeder, TestData, TrainData, load_ts, parse_ts
+from .ops import feed_batch
 from .voting import collect_logits, multi_source_vote, multi_source_voting, precision_weights, vote_scores
 from .checkpoint import (eval_accuracy, load_source_classification_modules, load_target_classification_modules,
                          save_source_classification_modules, save_target_classification_modules)

@@ -13,6 +13,10 @@ parser has no reference-generated vectors: "parity unpinned" for ``load_ts``); t
 
 ``DeviceLoader`` is the H2D side: batches are cast to float32, staged in pinned memory and copied on a side stream one
 batch ahead, so the step never waits for the host at B=256.
+
+``DeviceDataset`` / ``EpochFeeder`` take the host out of the per-step path altogether: the set is uploaded once, an epoch's
+permutations, CPC indices and ratios are planned once and uploaded with one copy, and every batch is gathered on the device
+(``ops.feed_batch``, csrc/feed.hip) at a plan position kept in a device word.
 """
 from __future__ import annotations
 
@@ -192,3 +196,203 @@ class DeviceLoader:
                 xd.record_stream(torch.cuda.current_stream(self.device))
                 yd.record_stream(torch.cuda.current_stream(self.device))
             yield xd, yd
+
+
+class DeviceDataset:
+    """A whole data set resident on the device: ``x`` [N, C, L] of any float dtype as ONE contiguous fp32 tensor (the reference's
+    ``.float()``, train_and_test.py:151, applied once at upload as ``DeviceLoader`` applies it) and ``y`` as int64.  The
+    reference's sets are a few MB to a few hundred MB: nothing forces them across PCIe once per step."""
+
+    def __init__(self, x: torch.Tensor, y: torch.Tensor, device):
+        if x.size(0) != y.size(0):
+            raise ValueError(f"{x.size(0)} series but {y.size(0)} labels")
+        if x.size(0) < 1:
+            raise ValueError("an empty data set")
+        self.device = torch.device(device)
+        self.x = x.to(torch.float32).contiguous().to(self.device)
+        self.y = y.to(torch.int64).contiguous().to(self.device)
+
+    def __len__(self) -> int:
+        return self.x.size(0)
+
+    def batches(self, batch_size: int) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
+        """Contiguous views in data-set order, the last partial one included: evaluation over a resident set copies nothing."""
+        if batch_size < 1:
+            raise ValueError(f"batch_size {batch_size}")
+        for i in range(0, len(self), batch_size):
+            yield self.x[i: i + batch_size], self.y[i: i + batch_size]
+
+
+class EpochFeeder:
+    """Plans a whole epoch on the host, uploads the plan once and then serves every step's batch from device memory
+    (``ops.feed_batch``), the plan's current row a device word: per step the host issues one launch pair and touches no tensor.
+
+    ``target`` / ``source``: ``DeviceDataset``s (``source=None``: a target-only feeder, for ``ClassifierTrainer``).  ``batch_size``:
+    one int or ``(B_t, B_s)``.  ``begin_epoch`` draws from ``generator`` (the global CPU generator if None) in this fixed order:
+    ``randperm(N_t)``; ``randperm(N_s)`` if there is a source; ``randint(cpc_timestep // 2, (rounds, 2))`` if ``cpc_timestep`` (the
+    CPC module's ``timestep``, L_t // 2) is given.  With ``shuffle=False`` the orders are ``arange`` and only the CPC indices are
+    drawn.  ``rounds = min(N_t // (world·B_t), N_s // (world·B_s))``: full batches only (graph shapes are static), the tail of a
+    permutation dropped as ``DeviceLoader(drop_last=True)`` drops it, the number of rounds the reference's ``min``
+    (train_and_test.py:538).  Rank ``r`` of ``world`` takes slice ``[r·B, (r+1)·B)`` of every global batch of ``world·B``.
+    For the same generator state the batches of an epoch are bit-equal to ``DeviceLoader(x, y, B, device, generator,
+    drop_last=True)``'s."""
+
+    SCALARS = 4                                                               # columns of the scalar table: t_t, t_s (int32), r_t, r_s (fp32)
+
+    def __init__(self, target: DeviceDataset, source: Optional[DeviceDataset] = None, batch_size=1,
+                 generator: Optional[torch.Generator] = None, shuffle: bool = True, cpc_timestep: Optional[int] = None,
+                 rank: int = 0, world: int = 1):
+        sizes = tuple(batch_size) if isinstance(batch_size, (tuple, list)) else (batch_size, batch_size)
+        if len(sizes) != 2 or any(isinstance(b, bool) or not isinstance(b, int) or b < 1 for b in sizes):
+            raise ValueError(f"batch_size must be a positive int or a pair of them, got {batch_size!r}")
+        if not 0 <= rank < world:
+            raise ValueError(f"rank {rank} of world {world}")
+        if source is not None and source.device != target.device:
+            raise ValueError(f"the target set lives on {target.device}, the source set on {source.device}")
+        if cpc_timestep is not None and cpc_timestep < 1:
+            raise ValueError(f"cpc_timestep {cpc_timestep}")
+        self.target, self.source, self.device = target, source, target.device
+        self.batch = sizes if source is not None else sizes[:1]
+        self.generator, self.shuffle, self.cpc_timestep, self.rank, self.world = generator, shuffle, cpc_timestep, rank, world
+        self.sets = (target,) if source is None else (target, source)
+        self.rounds = min(len(d) // (world * b) for d, b in zip(self.sets, self.batch))
+        self.epoch = 0                                                        # epochs begun
+        self.cursor = 0                                                       # host mirror of the device cursor
+        self.steps = 0                                                        # rows of the current plan (0: no epoch begun)
+        self.state = torch.zeros(8, dtype=torch.int32, device=self.device)    # fst_feed_batch's state block
+        if self.state.data_ptr() % 16:
+            raise RuntimeError("EpochFeeder: the allocator returned a block off a 16-byte boundary")
+        self._host: Optional[torch.Tensor] = None                             # the current plan's tables, int32, as uploaded
+        self._plan: Optional[torch.Tensor] = None                             # ... on the device
+        self._sink = torch.zeros(self.SCALARS, dtype=torch.int32, device=self.device)   # scalars nobody asked for
+        self._calls: Dict[tuple, object] = {}
+
+    def _gen(self) -> torch.Generator:
+        return torch.default_generator if self.generator is None else self.generator
+
+    def _words(self) -> int:
+        return self.rounds * (sum(self.batch) + self.SCALARS)
+
+    def _upload(self, host: torch.Tensor, head: torch.Tensor) -> None:
+        """The tables in one host-to-device copy, the state words in a second one of 32 bytes; neither waits for the device."""
+        if self.device.type == "cuda":
+            host, head = host.pin_memory(), head.pin_memory()
+        self._host = host
+        if self._plan is None or self._plan.numel() != host.numel():
+            self._plan = torch.empty(host.numel(), dtype=torch.int32, device=self.device)
+            self._calls = {}
+        self._plan.copy_(host, non_blocking=True)
+        self.state[: head.numel()].copy_(head, non_blocking=True)
+
+    def _tables(self):
+        """Views of the device plan: one index table per data set, then the scalars."""
+        out, at = [], 0
+        for b in self.batch:
+            out.append(self._plan[at: at + self.rounds * b].view(self.rounds, b))
+            at += self.rounds * b
+        return out, self._plan[at:].view(self.rounds, self.SCALARS)
+
+    def begin_epoch(self, ratios=None) -> int:
+        """Plan and upload the next epoch; returns its number of rounds.  ``ratios``: optional ``[rounds, 2]`` NoiseTransfer
+        accumulation ratios, rounded to float32 here.  Resets the cursor; the counters ``fed``, ``overrun`` and ``bad_index`` run on."""
+        gen, R, W = self._gen(), self.rounds, self.world
+        parts = []
+        for d, b in zip(self.sets, self.batch):
+            order = torch.randperm(len(d), generator=gen) if self.shuffle else torch.arange(len(d))
+            parts.append(order[: R * W * b].view(R, W, b)[:, self.rank].to(torch.int32).reshape(-1))
+        scal = torch.zeros(R, self.SCALARS, dtype=torch.int32)
+        if self.cpc_timestep is not None:
+            scal[:, :2] = torch.randint(max(1, self.cpc_timestep // 2), (R, 2), generator=gen).to(torch.int32)
+        r32 = torch.ones(R, 2, dtype=torch.float32)
+        if ratios is not None:
+            r32 = torch.as_tensor(ratios, dtype=torch.float64).reshape(-1, 2).to(torch.float32)
+            if r32.size(0) != R:
+                raise ValueError(f"begin_epoch(): {r32.size(0)} rows of ratios for {R} rounds")
+        scal[:, 2:] = r32.contiguous().view(torch.int32)
+        self.epoch += 1
+        self.cursor, self.steps = 0, R
+        self._upload(torch.cat(parts + [scal.reshape(-1)]), torch.tensor([0, R], dtype=torch.int32))
+        return R
+
+    def _need_epoch(self, what: str) -> None:
+        if self._plan is None:
+            raise RuntimeError(f"{what}: no epoch is planned; call begin_epoch() first")
+
+    def feed(self, *dst: torch.Tensor, t: Optional[torch.Tensor] = None, r: Optional[torch.Tensor] = None) -> None:
+        """Serve the current round into ``dst`` — (x_t, y_t) or (x_t, y_t, x_s, y_s), device tensors of the batch shapes — and the
+        round's scalars into ``t`` (int32 [2]: the CPC start indices) and ``r`` (fp32 [2]: the ratios) where given; then move on.
+        Two launches on the current stream.  Raises ``StopIteration`` before any launch once the epoch is over."""
+        self._need_epoch("feed()")
+        if self.cursor >= self.steps:
+            raise StopIteration
+        key = tuple(d.data_ptr() for d in dst) + (None if t is None else t.data_ptr(), None if r is None else r.data_ptr())
+        call = self._calls.get(key)
+        if call is None:
+            from . import ops
+            if len(dst) != 2 * len(self.sets):
+                raise ValueError(f"feed(): {len(dst)} destinations for {len(self.sets)} data sets (x and y each)")
+            for name, v, dt in (("t", t, torch.int32), ("r", r, torch.float32)):
+                if v is not None and (v.dtype != dt or v.numel() != 2 or not v.is_contiguous()):
+                    raise ValueError(f"feed(): {name} must be two contiguous {dt} words")
+            index, scal = self._tables()
+            streams = []
+            for i, d in enumerate(self.sets):
+                streams += [(d.x, dst[2 * i], index[i]), (d.y, dst[2 * i + 1], index[i])]
+            words = [self._sink[k: k + 1] for k in range(self.SCALARS)]
+            if t is not None:
+                words[0], words[1] = t.view(-1)[0:1], t.view(-1)[1:2]
+            if r is not None:
+                words[2], words[3] = r.view(-1)[0:1], r.view(-1)[1:2]
+            call = self._calls[key] = ops.FeedCall(streams, [(scal, w) for w in words], self.state)
+        call()
+        self.cursor += 1
+
+    def peek(self):
+        """Row 0 of the current plan as fresh tensors, nothing moved: (x_t, y_t[, x_s, y_s], t int32 [2], r fp32 [2]) — the batch to
+        hand to ``capture(...)``."""
+        self._need_epoch("peek()")
+        if self.steps < 1:
+            raise RuntimeError("peek(): the plan has no rounds")
+        index, scal = self._tables()
+        out = []
+        for d, idx in zip(self.sets, index):
+            rows = idx[0].long()
+            out += [d.x.index_select(0, rows), d.y.index_select(0, rows)]
+        return (*out, scal[0, :2].clone(), scal[0, 2:].view(torch.float32).clone())
+
+    def counters(self) -> torch.Tensor:
+        """The state block on the device (``ops.FEED_CURSOR`` ... ``ops.FEED_BAD_INDEX``); no host read."""
+        return self.state
+
+    def check(self) -> None:
+        """Read the state block once (this waits for the device: for the end of an epoch) and raise if a call ran past the plan's
+        end or a row's index fell outside its data set."""
+        from . import ops
+        words = self.state.cpu()
+        over, bad = int(words[ops.FEED_OVERRUN]), int(words[ops.FEED_BAD_INDEX])
+        if over or bad:
+            raise RuntimeError(f"EpochFeeder: {over} calls past the end of a plan, {bad} rows with an index outside their data set")
+
+    def state_dict(self) -> dict:
+        """Generator state, epoch number, cursor and the current plan's tables: a run resumed mid-epoch feeds the same remaining
+        batches.  Reads the counters back (waits for the device)."""
+        return {"generator": self._gen().get_state().clone(), "epoch": self.epoch, "cursor": self.cursor, "steps": self.steps,
+                "batch": tuple(self.batch), "rank": self.rank, "world": self.world,
+                "table": None if self._host is None else self._host.clone(), "counters": self.state.cpu().clone()}
+
+    def load_state_dict(self, sd: dict) -> None:
+        if tuple(sd["batch"]) != tuple(self.batch) or (sd["rank"], sd["world"]) != (self.rank, self.world):
+            raise ValueError(f"EpochFeeder: the checkpoint was planned for batch {tuple(sd['batch'])}, rank {sd['rank']} of "
+                             f"{sd['world']}; this feeder has batch {tuple(self.batch)}, rank {self.rank} of {self.world}")
+        if sd["table"] is not None and (sd["steps"] != self.rounds or sd["table"].numel() != self._words()):
+            raise ValueError("EpochFeeder: the checkpoint's plan does not fit this feeder's data sets")
+        self._gen().set_state(sd["generator"])
+        self.epoch, self.cursor, self.steps = sd["epoch"], sd["cursor"], sd["steps"]
+        head = sd["counters"].to(torch.int32).clone()
+        head[0], head[1] = self.cursor, self.steps
+        if sd["table"] is None:
+            self._host = self._plan = None
+            self._calls = {}
+            self.state.copy_(head)
+        else:
+            self._upload(sd["table"].to(torch.int32).clone(), head)

@@ -1,7 +1,8 @@
 """Autograd-visible ops of the hot path, each a thin host wrapper over the C ABI (include/fst_hip.h).
 
 Everything here launches hand-written gfx950 kernels on torch's current HIP stream; torch supplies
-device memory and the autograd graph only.  No op has a CPU implementation.
+device memory and the autograd graph only.  No op has a CPU implementation (``feed_batch``, a copy by index with host
+bookkeeping, is the exception: its CPU branch gives the kernel's bits and state words).
 """
 from __future__ import annotations
 
@@ -2549,3 +2550,97 @@ def _fixed_matmul(x: Tensor, R: Tensor, M: int, K: int, N: int) -> Tensor:
     conv_gemm(plan, a, R.view(1, K, N), None, None, 1, N, M, y, nb=1, ksplit=ksplit,
               flags=EPI_ATOMIC if ksplit > 1 else 0, bf3=bf3)
     return y.view(M, N)
+
+
+# ---- device-resident datasets: a step's batch gathered on the device by a plan whose current row is a device word (csrc/feed.hip)
+FEED_CURSOR, FEED_STEPS, FEED_FED, FEED_OVERRUN, FEED_BAD_INDEX = range(5)      # words of fst_feed_batch's state block
+FEED_MAX_STREAMS = FEED_MAX_SCALARS = 8
+
+
+def _feed_words(t: Tensor, rows: int) -> Tensor:
+    """``t`` [rows, ...] as int32 words [rows, row_words] over the same storage."""
+    return t.reshape(rows, -1).view(torch.int32)
+
+
+class FeedCall:
+    """One validated ``fst_feed_batch`` call, kept so that issuing it again costs no more than the call itself (the tensors it names
+    are held, so the addresses stay valid).  See ``feed_batch`` for the arguments."""
+
+    def __init__(self, streams: Sequence[Tuple[Tensor, Tensor, Tensor]], scalars: Sequence[Tuple[Tensor, Tensor]], state: Tensor):
+        if len(streams) > FEED_MAX_STREAMS or len(scalars) > FEED_MAX_SCALARS:
+            raise ValueError(f"feed_batch: {len(streams)} streams and {len(scalars)} scalars; at most {FEED_MAX_STREAMS} and {FEED_MAX_SCALARS}")
+        if state.dtype != torch.int32 or state.numel() != 8 or not state.is_contiguous() or state.data_ptr() % 16:
+            raise ValueError("feed_batch: the state block is eight contiguous int32 words on a 16-byte boundary")
+        dev = state.device
+        self.streams, self.scalars, self.state = list(streams), list(scalars), state
+        self.geom = []
+        for s, (src, dst, index) in enumerate(self.streams):
+            if not (src.device == dst.device == index.device == dev):
+                raise ValueError(f"feed_batch: stream {s}: every tensor must live on the state's device, {dev}")
+            if src.dim() < 1 or dst.dim() != src.dim() or src.shape[1:] != dst.shape[1:] or src.dtype != dst.dtype:
+                raise ValueError(f"feed_batch: stream {s}: source {tuple(src.shape)} {src.dtype}, destination {tuple(dst.shape)} {dst.dtype}")
+            if src.element_size() not in (4, 8) or not (src.is_contiguous() and dst.is_contiguous() and index.is_contiguous()):
+                raise ValueError(f"feed_batch: stream {s}: contiguous tensors of 4- or 8-byte elements only")
+            n_rows, batch = src.size(0), dst.size(0)
+            if n_rows < 1 or batch < 1 or src[0].numel() < 1:
+                raise ValueError(f"feed_batch: stream {s}: empty source, destination or row")
+            if index.dtype != torch.int32 or index.dim() != 2 or index.size(1) != batch:
+                raise ValueError(f"feed_batch: stream {s}: the index table must be int32 [steps, {batch}], got {tuple(index.shape)} {index.dtype}")
+            row_words = src[0].numel() * src.element_size() // 4
+            if max(n_rows, batch, row_words, row_words * batch) >= 1 << 31:
+                raise ValueError(f"feed_batch: stream {s}: row_words {row_words}, n_rows {n_rows}, batch {batch} (each, and row_words * batch, below 2^31)")
+            self.geom.append((row_words, n_rows, batch))
+        for k, (table, dst) in enumerate(self.scalars):
+            if table.device != dev or dst.device != dev:
+                raise ValueError(f"feed_batch: scalar {k}: every tensor must live on the state's device, {dev}")
+            if table.dim() != 2 or table.size(1) != len(self.scalars) or table.element_size() != 4 or not table.is_contiguous():
+                raise ValueError(f"feed_batch: scalar {k}: the table must be contiguous 4-byte words [steps, {len(self.scalars)}]")
+            if dst.numel() != 1 or dst.element_size() != 4:
+                raise ValueError(f"feed_batch: scalar {k}: the destination is one 4-byte word")
+        self._args = None
+        if dev.type == "cuda":
+            P, I64 = ctypes.c_void_p, ctypes.c_int64
+            n, ns = len(self.streams), len(self.scalars)
+            self._args = ((P * n)(*[t[0].data_ptr() for t in self.streams]), (P * n)(*[t[1].data_ptr() for t in self.streams]),
+                          (P * n)(*[t[2].data_ptr() for t in self.streams]), (I64 * n)(*[g[0] for g in self.geom]),
+                          (I64 * n)(*[g[1] for g in self.geom]), (I64 * n)(*[g[2] for g in self.geom]), n,
+                          (P * ns)(*[t[0].data_ptr() for t in self.scalars]), (P * ns)(*[t[1].data_ptr() for t in self.scalars]), ns,
+                          state.data_ptr())
+            self._fn = _lib.load().fst_feed_batch
+
+    def __call__(self) -> None:
+        if self._args is not None:
+            check(self._fn(*self._args, stream_ptr()), "fst_feed_batch")
+            return
+        st = self.state
+        cursor, steps = int(st[FEED_CURSOR]), int(st[FEED_STEPS])
+        if cursor < 0 or cursor >= steps:
+            st[FEED_OVERRUN] += 1
+            return
+        bad = 0
+        for (src, dst, index), (_, n_rows, batch) in zip(self.streams, self.geom):
+            idx = index[cursor].long()
+            ok = (idx >= 0) & (idx < n_rows)
+            bad += int((~ok).sum())
+            rows = torch.nonzero(ok).flatten()
+            _feed_words(dst, batch)[rows] = torch.index_select(_feed_words(src, n_rows), 0, idx[rows])
+        for k, (table, dst) in enumerate(self.scalars):
+            dst.view(-1).view(torch.int32)[0] = table.view(torch.int32)[cursor, k]
+        st[FEED_BAD_INDEX] += bad
+        st[FEED_FED] += 1
+        st[FEED_CURSOR] = cursor + 1
+
+
+@torch.no_grad()
+def feed_batch(streams: Sequence[Tuple[Tensor, Tensor, Tensor]], scalars: Sequence[Tuple[Tensor, Tensor]], state: Tensor) -> None:
+    """Serve the current row of an epoch plan from device memory and move the plan's cursor on (``fst_feed_batch``: two launches on
+    the current stream, nothing waits for the device).  ``streams``: up to 8 triples (source [n_rows, ...], destination
+    [batch, ...] of the same dtype and trailing shape, index table int32 [steps, batch]) of contiguous tensors with 4- or 8-byte
+    elements; ``scalars``: up to 8 pairs (table of 4-byte words [steps, len(scalars)], destination of one 4-byte word) — scalar
+    ``k`` becomes ``table[cursor, k]``; ``state``: eight int32 words on a 16-byte boundary, indexed by ``FEED_CURSOR`` ...
+    ``FEED_BAD_INDEX``.  With ``cursor`` in ``0..steps-1`` destination row ``b`` of a stream becomes source row
+    ``index[cursor, b]``, bit for bit; a row whose index is outside ``0..n_rows-1`` is left unwritten and counted in
+    ``bad_index``; then ``fed`` and ``cursor`` move on.  Otherwise nothing is written but ``overrun += 1``.  The words are read when
+    the kernels run, so consecutive calls serve consecutive rows with no host action between them.  On CPU tensors the same in
+    plain torch (``index_select`` on int32 views and host bookkeeping of the five words): the same destination bits and state."""
+    FeedCall(streams, scalars, state)()

@@ -334,6 +334,59 @@ class _GradAccumulating:
         accumulate(acc, grads, self.grad_accumulation, advance)
 
 
+class _Fed:
+    """Device-resident input of the two trainers: an attached ``data.EpochFeeder`` plans an epoch once and the ``*_fed`` methods
+    draw every batch from device memory — into the captures' own static inputs, or into buffers kept here for the eager steps.
+    A fed method creates no tensor on the host, issues no host-to-device copy and waits for nothing: the feed is one launch pair
+    in front of what the unfed method issues, and is never captured."""
+    feeder = None
+    _fed_kind: Optional[str] = None                                           # what begin_epoch planned ("joint", a phase, "classifier")
+    _fed_buf: Optional[dict] = None                                           # the eager steps' batch, CPC indices and ratios
+
+    def attach_feeder(self, feeder) -> None:
+        """Use ``feeder`` from now on (None: detach).  An epoch has to be begun (``begin_epoch``) before the first fed call."""
+        if feeder is not None and torch.device(feeder.device).type != torch.device(self.device).type:
+            raise ValueError(f"attach_feeder(): the feeder lives on {feeder.device}, the trainer on {self.device}")
+        self.feeder, self._fed_kind, self._fed_buf = feeder, None, None
+
+    def _fed_begin(self, kind: str, ratios=None) -> int:
+        if self.feeder is None:
+            raise RuntimeError("begin_epoch(): call attach_feeder() first")
+        rounds = self.feeder.begin_epoch(ratios)
+        self._fed_kind = kind
+        return rounds
+
+    def _fed_check(self, kind: str, what: str) -> None:
+        if self.feeder is None:
+            raise RuntimeError(f"{what}: call attach_feeder() and begin_epoch() first")
+        if self._fed_kind is None:
+            raise RuntimeError(f"{what}: no epoch is planned; call begin_epoch() first")
+        if kind != self._fed_kind:
+            raise RuntimeError(f"{what}: the epoch was begun for {self._fed_kind!r}, not for {kind!r}")
+
+    def _fed_eager(self) -> dict:
+        """Feed the current round into the buffers the trainer keeps for its eager steps (made at the first call)."""
+        f = self.feeder
+        if self._fed_buf is None:
+            batch = []
+            for d, b in zip(f.sets, f.batch):
+                batch += [torch.empty((b,) + tuple(d.x.shape[1:]), dtype=torch.float32, device=f.device),
+                          torch.empty((b,) + tuple(d.y.shape[1:]), dtype=torch.int64, device=f.device)]
+            self._fed_buf = {"batch": batch, "t": torch.zeros(2, dtype=torch.int32, device=f.device), "r": torch.ones(2, device=f.device)}
+        b = self._fed_buf
+        f.feed(*b["batch"], t=b["t"], r=b["r"])
+        return b
+
+    def _fed_state_dict(self) -> dict:
+        return {} if self.feeder is None else {"feeder": {"kind": self._fed_kind, **self.feeder.state_dict()}}
+
+    def _fed_load_state_dict(self, sd: dict) -> None:
+        """A "feeder" entry goes into the attached feeder; without one attached, or without the entry, nothing happens."""
+        if "feeder" in sd and self.feeder is not None:
+            self.feeder.load_state_dict(sd["feeder"])
+            self._fed_kind = sd["feeder"]["kind"]
+
+
 def _enable_grad_accumulation(trainer, arg) -> None:
     """The constructors' ``grad_accumulation=``: None / False, or the number of steps."""
     if arg is None or arg is False:
@@ -341,7 +394,7 @@ def _enable_grad_accumulation(trainer, arg) -> None:
     trainer.enable_grad_accumulation(1 if arg is True else arg)
 
 
-class ClassifierTrainer(_WeightAveraging, _GradAccumulating):
+class ClassifierTrainer(_WeightAveraging, _GradAccumulating, _Fed):
     """S1 of the reference.  The anomaly guard (``JointTrainer.enable_anomaly_guard``) is not offered here: a non-finite batch
     reaches this trainer's parameters as it does in the reference.  Weight averaging (``enable_weight_average``) is, over the
     groups "fe" and "clf"; its device words are ``weight_average``.  Gradient accumulation (``enable_grad_accumulation``) too."""
@@ -463,6 +516,10 @@ class ClassifierTrainer(_WeightAveraging, _GradAccumulating):
         if self._graph is None:
             raise RuntimeError("call capture() first")
         self._g_x.copy_(x); self._g_y.copy_(y)
+        return self._replay_graphs()
+
+    def _replay_graphs(self):
+        """What a replay does once the static inputs hold the batch."""
         if self.device_hparams:
             push_lr((self.opt_fe, self.opt_clf))
         self._graph.replay()
@@ -472,6 +529,28 @@ class ClassifierTrainer(_WeightAveraging, _GradAccumulating):
             if closing:
                 self._graph_update.replay()
         return self._g_out
+
+    # ---- device-resident input (the methods of _Fed): a target-only EpochFeeder
+    def begin_epoch(self) -> int:
+        """Plan and upload the attached feeder's next epoch; returns its number of rounds."""
+        if self.feeder is not None and len(self.feeder.sets) != 1:
+            raise ValueError("ClassifierTrainer.begin_epoch(): a target-only feeder (source=None) is needed")
+        return self._fed_begin("classifier")
+
+    def step_fed(self):
+        """``step`` on the feeder's current round, drawn into buffers this trainer keeps.  ``StopIteration`` once the epoch is over."""
+        self._ema_no_step("step_fed()")
+        self._fed_check("classifier", "step_fed()")
+        return self.step(*self._fed_eager()["batch"])
+
+    def replay_fed(self):
+        """``replay`` on the feeder's current round, drawn straight into the capture's static inputs."""
+        self._ema_no_step("replay_fed()")
+        if self._graph is None:
+            raise RuntimeError("call capture() first")
+        self._fed_check("classifier", "replay_fed()")
+        self.feeder.feed(self._g_x, self._g_y)
+        return self._replay_graphs()
 
 
 def _enable_weight_average(trainer, arg) -> None:
@@ -510,7 +589,7 @@ class JointConfig:
     nf_end_std: float = 0.0       # >0: draw WN.end (zero-init in the reference) so the flow is non-degenerate
 
 
-class JointTrainer(_WeightAveraging, _GradAccumulating):
+class JointTrainer(_WeightAveraging, _GradAccumulating, _Fed):
     MODULES = ("fe_t", "clf_t", "fe_s", "dimunif", "clf_s", "probtransfer", "nf", "noise", "ad_net", "fd_s", "cpc")
     LRS = {"fe_t": 0.001, "clf_t": 0.003, "fe_s": 0.001, "dimunif": 0.001, "clf_s": 0.003, "probtransfer": 0.001,
            "nf": 0.001, "noise": 0.005, "ad_net": 0.001, "fd_s": 0.001}       # train_and_test.py:97-106
@@ -943,8 +1022,10 @@ class JointTrainer(_WeightAveraging, _GradAccumulating):
         "schedules": the eleven schedulers' state, CPC's learning rate (the RMSprops' are in their ``param_groups``), the epoch of
         the last step and its loss coefficients.  With ``enable_grad_clip()`` on, also "grad_clip": its limits; with
         ``enable_weight_average()`` on, also "weight_average": decay, warm-up flag, update counts and the averaged tensors; with
-        ``enable_grad_accumulation()`` on, also "grad_accumulation": its steps.  Raises while an accumulation window is open:
-        half a window is no state a run could resume from."""
+        ``enable_grad_accumulation()`` on, also "grad_accumulation": its steps; with a feeder attached (``attach_feeder``), also
+        "feeder": the epoch's kind and the feeder's generator state, epoch, cursor and plan, which ``load_state_dict`` puts into
+        the feeder attached then (without one the entry is ignored).  Raises while an accumulation window is open: half a window
+        is no state a run could resume from."""
         self._ema_no_step("state_dict()")
         self._accum_closed("state_dict()")
         cpu = lambda t: t.detach().cpu().clone()
@@ -980,6 +1061,7 @@ class JointTrainer(_WeightAveraging, _GradAccumulating):
             **({"grad_clip": {"max_norm": self._clip_max, "per_module": dict(self._clip_per)}} if self.grad_clip else {}),
             **({"weight_average": self._ema_state_dict()} if self.weight_average is not None else {}),
             **({"grad_accumulation": {"steps": self.grad_accumulation.steps_host}} if self.grad_accumulation is not None else {}),
+            **self._fed_state_dict(),                                         # "feeder", while one is attached: its plan and position
         }
 
     def load_state_dict(self, sd: dict) -> None:
@@ -1041,6 +1123,7 @@ class JointTrainer(_WeightAveraging, _GradAccumulating):
             if self.grad_accumulation is None:
                 self.enable_grad_accumulation(sd["grad_accumulation"]["steps"])
             self.set_grad_accumulation(sd["grad_accumulation"]["steps"])
+        self._fed_load_state_dict(sd)
 
     def save_state(self, path: str) -> None:
         self._accum_closed("save_state()")
@@ -1294,14 +1377,7 @@ class JointTrainer(_WeightAveraging, _GradAccumulating):
         """One batch of a captured phase on a new batch of the captured shapes; returns the phase's static report (the keys of
         ``phase_step``: its losses and "total"), valid until this phase's next replay.  Nothing here waits for the device.
         ``.grad`` is left alone: the gradients are in the tensors the capture kept."""
-        self._ema_no_step("replay_phase()")
-        self._accum_phase_graphs("replay_phase()")
-        rec = self._phase.get(phase)
-        if rec is None:
-            if phase not in self.PHASES:
-                raise ValueError(f"unknown phase {phase!r}; one of {sorted(self.PHASES)}")
-            raise RuntimeError(f"phase {phase!r} is not captured: call capture_phase({phase!r}, ...) first "
-                               "(load_state_dict drops every phase capture)")
+        rec = self._replay_phase_begin(phase, "replay_phase()")
         gi = rec["in"]
         batch = (("x_t", x_t), ("y_t", y_t), ("x_s", x_s), ("y_s", y_s))
         for k, v in batch:
@@ -1312,6 +1388,22 @@ class JointTrainer(_WeightAveraging, _GradAccumulating):
             if v is not gi[k]:
                 gi[k].copy_(v, non_blocking=True)
         gi["t"].copy_(torch.tensor([int(t_samples[0]), int(t_samples[1])], dtype=torch.int32), non_blocking=True)
+        return self._replay_phase_graphs(rec)
+
+    def _replay_phase_begin(self, phase: str, what: str) -> dict:
+        """The checks of a phase replay; returns the phase's capture record."""
+        self._ema_no_step(what)
+        self._accum_phase_graphs(what)
+        rec = self._phase.get(phase)
+        if rec is None:
+            if phase not in self.PHASES:
+                raise ValueError(f"unknown phase {phase!r}; one of {sorted(self.PHASES)}")
+            raise RuntimeError(f"phase {phase!r} is not captured: call capture_phase({phase!r}, ...) first "
+                               "(load_state_dict drops every phase capture)")
+        return rec
+
+    def _replay_phase_graphs(self, rec: dict):
+        """What a phase replay does once the static inputs hold the batch and the CPC indices."""
         if self.device_hparams:
             push_lr(self._scheduled_opts())
         rec["graphs"][0].replay()
@@ -1319,6 +1411,59 @@ class JointTrainer(_WeightAveraging, _GradAccumulating):
             self.bucket.all_reduce_grads(rec["grads"])
             rec["graphs"][1].replay()
         return rec["report"]
+
+    # ------------------------------------------------------------------ device-resident input (the methods of _Fed)
+    def begin_epoch(self, kind: str = "joint") -> int:
+        """Plan and upload the attached feeder's next epoch for ``kind`` — "joint" or a phase name — and return its number of
+        rounds.  For a joint epoch the NoiseTransfer ratios of every round are planned here (``NoiseTransfer.planned_ratios``:
+        ``advance``'s own arithmetic from a copy of its counters) and ride in the plan; the counters themselves still move one
+        ``advance`` per fed joint step, so a checkpoint taken mid-epoch stays right.  The plan assumes that until the epoch is over
+        every joint step is a fed one."""
+        if kind != "joint" and kind not in self.PHASES:
+            raise ValueError(f"unknown kind {kind!r}; 'joint' or one of {sorted(self.PHASES)}")
+        f = self.feeder
+        if f is not None and len(f.sets) != 2:
+            raise ValueError("JointTrainer.begin_epoch(): a feeder with a source set is needed")
+        ratios = None
+        if kind == "joint" and f is not None:
+            ratios = self.m["noise"].planned_ratios(f.rounds, f.batch[0], f.batch[1])
+        return self._fed_begin(kind, ratios)
+
+    def step_fed(self, epoch: int = 0):
+        """``step`` on the feeder's current round: the batch, the CPC start indices and the ratios drawn into device buffers this
+        trainer keeps, the indices and ratios passed on as 0-d device tensors.  ``StopIteration`` once the epoch is over."""
+        self._ema_no_step("step_fed()")
+        self._fed_check("joint", "step_fed()")
+        b = self._fed_eager()
+        x_t, y_t, x_s, y_s = b["batch"]
+        self._set_epoch(epoch)
+        self.m["noise"].advance(x_t.size(0), x_s.size(0))                     # the counters; this round's ratios are in the plan
+        return self._step_body(x_t, y_t, x_s, y_s, epoch, (b["t"][0], b["t"][1]), (b["r"][0], b["r"][1]))
+
+    def replay_fed(self, epoch: Optional[int] = None):
+        """``replay`` on the feeder's current round, drawn straight into the capture's static inputs (batch, CPC indices, ratios);
+        everything behind the inputs is ``replay``'s, the three-graph data-parallel path included."""
+        self._fed_check("joint", "replay_fed()")
+        self._replay_begin("replay_fed()", epoch)
+        gi = self._g_in
+        self.feeder.feed(gi["x_t"], gi["y_t"], gi["x_s"], gi["y_s"], t=gi["t"], r=gi["r"])
+        self.m["noise"].advance(gi["x_t"].size(0), gi["x_s"].size(0))
+        return self._replay_graphs()
+
+    def phase_step_fed(self, phase: str):
+        """``phase_step`` on the feeder's current round.  A phase that uses one side only still consumes the round's other side."""
+        self._ema_no_step("phase_step_fed()")
+        self._fed_check(phase, "phase_step_fed()")
+        b = self._fed_eager()
+        return self.phase_step(phase, *b["batch"], (b["t"][0], b["t"][1]))
+
+    def replay_phase_fed(self, phase: str):
+        """``replay_phase`` on the feeder's current round, drawn straight into the phase capture's static inputs."""
+        self._fed_check(phase, "replay_phase_fed()")
+        rec = self._replay_phase_begin(phase, "replay_phase_fed()")
+        gi = rec["in"]
+        self.feeder.feed(gi["x_t"], gi["y_t"], gi["x_s"], gi["y_s"], t=gi["t"])
+        return self._replay_phase_graphs(rec)
 
     def _accum_phase_graphs(self, what: str) -> None:
         """A captured phase is one whole step per replay: the phase graphs have no micro-step / update split."""
@@ -1614,7 +1759,13 @@ class JointTrainer(_WeightAveraging, _GradAccumulating):
         captured values, and an ``epoch`` other than the captured one raises.  With gradient accumulation a call that does not
         close its window returns the micro-step's report (this batch's losses and aux entries, "accum_index") and launches no
         update; the closing call returns the whole report, with "window_losses"."""
-        self._ema_no_step("replay()")
+        self._replay_begin("replay()", epoch)
+        self._replay_inputs(x_t, y_t, x_s, y_s, t_samples)
+        return self._replay_graphs()
+
+    def _replay_begin(self, what: str, epoch: Optional[int]) -> None:
+        """The checks of a replay, and with ``device_hparams`` the epoch's coefficients and the learning rates."""
+        self._ema_no_step(what)
         if self._graphs is None:
             raise RuntimeError("call capture() first")
         if self.device_hparams:
@@ -1622,9 +1773,11 @@ class JointTrainer(_WeightAveraging, _GradAccumulating):
                 self._set_epoch(epoch)
             push_lr(self._scheduled_opts())
         elif epoch is not None and epoch != self._g_epoch:
-            raise ValueError(f"replay(epoch={epoch}): the graph was captured at epoch {self._g_epoch} and its loss coefficients "
+            raise ValueError(f"{what[:-1]}epoch={epoch}): the graph was captured at epoch {self._g_epoch} and its loss coefficients "
                              "are baked in; re-capture, or enable_device_hparams() before capturing")
-        self._replay_inputs(x_t, y_t, x_s, y_s, t_samples)
+
+    def _replay_graphs(self):
+        """What a replay does once the static inputs hold the batch, the CPC indices and the ratios."""
         acc = self.grad_accumulation
         closing = acc is None or acc.closing_next
         self._graphs[0].replay()

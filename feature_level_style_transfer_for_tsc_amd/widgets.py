@@ -162,6 +162,18 @@ class NoiseTransfer(nn.Module):
         self.cal_num_source += batch_source
         return ratios
 
+    def planned_ratios(self, rounds: int, batch_target: int, batch_source: int):
+        """What the next ``rounds`` calls of ``advance(batch_target, batch_source)`` WILL return, computed from a copy of the counters
+        with ``advance``'s own Python float arithmetic (so each ratio rounds to the same float32); the counters do not move."""
+        time, n_t, n_s = self.time, self.cal_num_target, self.cal_num_source
+        out = []
+        for _ in range(rounds):
+            time += 1
+            out.append((1.0, 1.0) if time == 1 else (batch_target / n_t, batch_source / n_s))
+            n_t += batch_target
+            n_s += batch_source
+        return out
+
     def forward(self, target_noise_batch, source_noise_batch, ratios=None):
         """``ratios``: optional pair of 0-d DEVICE tensors holding this call's accumulation ratios; a captured
         hipGraph passes static buffers that the host refreshes (via ``advance``) before every replay."""

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FST_ABI_VERSION 24
+#define FST_ABI_VERSION 25
 
 int fst_version(void);
 const char* fst_last_error(void);
@@ -704,6 +704,30 @@ int fst_swap_multi(float* const* a_host, float* const* b_host, const int64_t* nu
  * ------------------------------------------------------------------------------------------- */
 int fst_accum_multi(float* const* acc_host, float* const* g_host, const int64_t* numel_host, int n_tensors, void* state_dev,
                     int advance, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Device-resident datasets (ABI v25): the batch of a step gathered on the device from a data set and an epoch plan that were
+ * uploaded once, the plan's current row a device word, so that one launch pair serves every row and nothing crosses from the host
+ * per step.  Up to 8 streams (x_t, y_t, x_s, y_s, ...), stream s being a source of n_rows[s] rows of row_words[s] 4-byte words,
+ * a destination of batch[s] such rows and a device index table int32 [steps][batch[s]] (an int64 label is a row of 2 words); up to
+ * 8 scalars, scalar k being a device table of 4-byte words [steps][n_scalars] and a destination word.  Every pointer non-null and
+ * 4-byte aligned, 0 < row_words, n_rows, batch, row_words * batch < 2^31, no destination overlapping its source or the state
+ * block, every entry validated on the host before the first launch: a refused call has written nothing.
+ * state_dev is a 16-byte aligned block of eight int32 words: [0] cursor (current plan row), [1] steps (rows in the plan), [2] fed
+ * (rows served), [3] overrun (calls that found cursor >= steps), [4] bad_index (rows whose index fell outside 0..n_rows-1),
+ * [5..7] reserved, zero.  Two launches per call, both reading cursor and steps when they RUN.  If 0 <= cursor < steps:
+ *   dst_s[b] = src_s[index_s[cursor * batch_s + b]] for every stream s and row b, moved as 32-bit integers (every bit pattern
+ *   survives); a row whose index is outside 0..n_rows_s-1 is left unwritten and its index is never dereferenced;
+ *   scalar_dst_k[0] = table_k[cursor * n_scalars + k];
+ *   then a one-workgroup launch adds the row's count of such indices to bad_index, fed += 1, cursor += 1 (plain stores, one lane).
+ * Otherwise no destination word is written, overrun += 1 and the cursor stays.
+ * A stream whose row_words is a multiple of 4 and whose two base pointers are 16-byte aligned moves in 16-byte accesses, every
+ * other in 4-byte ones.  A stream's batch is one flat range of such units over at most 2048 workgroups of the launch: a long row
+ * spreads over several workgroups, short rows share one.
+ * ------------------------------------------------------------------------------------------- */
+int fst_feed_batch(const void* const* src_host, void* const* dst_host, const int32_t* const* index_host,
+                   const int64_t* row_words_host, const int64_t* n_rows_host, const int64_t* batch_host, int n_streams,
+                   const void* const* table_host, void* const* scalar_dst_host, int n_scalars, void* state_dev, void* stream);
 
 #ifdef __cplusplus
 }
