@@ -17,6 +17,9 @@ batch ahead, so the step never waits for the host at B=256.
 ``DeviceDataset`` / ``EpochFeeder`` take the host out of the per-step path altogether: the set is uploaded once, an epoch's
 permutations, CPC indices and ratios are planned once and uploaded with one copy, and every batch is gathered on the device
 (``ops.feed_batch``, csrc/feed.hip) at a plan position kept in a device word.
+
+``EvalPlan`` is the evaluation's counterpart: one sequential plan over a resident set, built once, whose last batch is padded to
+the static shape and comes with its count of valid rows (``evaluate.Evaluator`` serves its captured passes from it).
 """
 from __future__ import annotations
 
@@ -396,3 +399,73 @@ class EpochFeeder:
             self.state.copy_(head)
         else:
             self._upload(sd["table"].to(torch.int32).clone(), head)
+
+
+class EvalPlan:
+    """A sequential plan over ONE ``DeviceDataset`` for evaluation, built and uploaded once at construction (one host-to-device
+    copy), not per epoch: ``rounds = ceil(N / B)`` rows of ``B`` indices holding ``arange(N)``, the last row padded with index
+    ``N - 1`` (a valid index: ``bad_index`` stays 0, and the padding rows hold finite data), and one scalar column with each round's
+    count of valid rows.  ``feed`` serves the current round through the unchanged ``ops.FeedCall`` (``fst_feed_batch``): ``x`` and
+    ``y`` into the caller's static inputs, the count into the word that ``ops.eval_fold`` reads.  ``rewind`` resets the cursor from
+    a resident device word: a device-to-device copy of four bytes that a captured graph can hold.  The host keeps no mirror of the
+    cursor, so a call past the end is not refused here but counted in ``overrun`` on the device (``check``).
+
+    ``rank`` / ``world`` slicing is out of scope: a data-parallel user evaluates on rank 0."""
+
+    def __init__(self, data: DeviceDataset, batch_size: int):
+        if isinstance(batch_size, bool) or not isinstance(batch_size, int) or batch_size < 1:
+            raise ValueError(f"batch_size must be a positive int, got {batch_size!r}")
+        N, B = len(data), batch_size
+        self.data, self.device, self.batch, self.n = data, data.device, B, N
+        self.rounds = R = (N + B - 1) // B
+        if R * B >= 1 << 31:
+            raise ValueError(f"EvalPlan: {R} rounds of {B} rows exceed int32 indices")
+        host = torch.zeros(16 + R * B + R, dtype=torch.int32)
+        host[1] = R                                                           # ops.FEED_STEPS; words 0..7: fst_feed_batch's state block
+        host[16: 16 + R * B] = torch.arange(R * B, dtype=torch.int32).clamp_(max=N - 1)      # (words 8..15: the cursor's home, zero)
+        host[16 + R * B:] = (N - torch.arange(R, dtype=torch.int64) * B).clamp_(max=B).to(torch.int32)
+        if self.device.type == "cuda":
+            host = host.pin_memory()
+        self._host = host
+        self._words = torch.empty(host.numel(), dtype=torch.int32, device=self.device)
+        self._words.copy_(host, non_blocking=True)
+        self.state = self._words[:8]
+        if self.state.data_ptr() % 16:
+            raise RuntimeError("EvalPlan: the allocator returned a block off a 16-byte boundary")
+        self._home = self._words[8:9]
+        self.index = self._words[16: 16 + R * B].view(R, B)
+        self.valid = self._words[16 + R * B:].view(R, 1)
+        self._calls: Dict[tuple, object] = {}
+
+    def __len__(self) -> int:
+        return self.rounds
+
+    def rewind(self) -> None:
+        """Back to round 0; the counters ``fed``, ``overrun`` and ``bad_index`` run on.  One four-byte copy within device memory."""
+        self.state[:1].copy_(self._home)
+
+    def feed(self, x: torch.Tensor, y: torch.Tensor, valid: torch.Tensor) -> None:
+        """Serve the current round into ``x`` [B, ...], ``y`` [B] and the round's count of valid rows into ``valid`` (one int32 word);
+        then move on.  Two launches on the current stream."""
+        key = (x.data_ptr(), y.data_ptr(), valid.data_ptr())
+        call = self._calls.get(key)
+        if call is None:
+            from . import ops
+            if valid.dtype != torch.int32 or valid.numel() != 1:
+                raise ValueError("EvalPlan.feed(): valid must be one int32 word")
+            call = self._calls[key] = ops.FeedCall([(self.data.x, x, self.index), (self.data.y, y, self.index)],
+                                                   [(self.valid, valid.view(-1))], self.state)
+        call()
+
+    def counters(self) -> torch.Tensor:
+        """The state block on the device (``ops.FEED_CURSOR`` ... ``ops.FEED_BAD_INDEX``); no host read."""
+        return self.state
+
+    def check(self) -> None:
+        """Read the state block once (this waits for the device) and raise if a call ran past the plan's end or an index fell
+        outside the data set."""
+        from . import ops
+        words = self.state.cpu()
+        over, bad = int(words[ops.FEED_OVERRUN]), int(words[ops.FEED_BAD_INDEX])
+        if over or bad:
+            raise RuntimeError(f"EvalPlan: {over} calls past the end of the plan, {bad} rows with an index outside the data set")

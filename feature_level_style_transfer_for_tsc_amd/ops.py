@@ -2644,3 +2644,182 @@ def feed_batch(streams: Sequence[Tuple[Tensor, Tensor, Tensor]], scalars: Sequen
     the kernels run, so consecutive calls serve consecutive rows with no host action between them.  On CPU tensors the same in
     plain torch (``index_select`` on int32 views and host bookkeeping of the five words): the same destination bits and state."""
     FeedCall(streams, scalars, state)()
+
+
+# ---- evaluation on the device: a pass folded batch by batch into device words, and closed on the device (csrc/eval.hip)
+EVAL_SEEN, EVAL_HITS, EVAL_BATCHES, EVAL_BAD_LABEL, EVAL_NONFINITE, EVAL_OVERFLOW = range(6)          # words of fst_eval_fold's state block
+EVAL_IMPROVED, EVAL_PASSES, EVAL_BEST_HITS, EVAL_BEST_PASS, EVAL_BEST_LOSS, EVAL_INCOMPLETE = 0, 1, 2, 3, 4, 6   # ... of the best block
+EVAL_MAX_C = 4096
+
+
+def eval_best_block(device) -> Tensor:
+    """A fresh best block of ``fst_eval_finish``: eight int32 words, ``best_hits`` = -1 and ``best_loss`` (fp64, words 4..5) = +inf."""
+    host = torch.zeros(8, dtype=torch.int32)
+    host[EVAL_BEST_HITS] = -1
+    host[EVAL_BEST_LOSS: EVAL_BEST_LOSS + 2].view(torch.float64)[0] = float("inf")
+    return host.to(device)
+
+
+def eval_best_loss(best: Tensor) -> Tensor:
+    """The fp64 ``best_loss`` word of a best block, as a view."""
+    return best[EVAL_BEST_LOSS: EVAL_BEST_LOSS + 2].view(torch.float64)
+
+
+def eval_scratch(B: int, device) -> Tensor:
+    """``fst_eval_fold``'s scratch for batches of ``B`` rows: B fp64 words and B int32 words, as one fp64 tensor."""
+    return torch.empty(B + (B + 1) // 2, dtype=torch.float64, device=device)
+
+
+def _eval_block(who: str, name: str, t: Tensor, dtype, numel: int, align: int) -> None:
+    if t.dtype != dtype or t.numel() != numel or not t.is_contiguous() or t.data_ptr() % align:
+        raise ValueError(f"{who}: {name} must be {numel} contiguous {dtype} word(s) on a {align}-byte boundary")
+
+
+class EvalFoldCall:
+    """One validated ``fst_eval_fold`` call, kept so that issuing it again costs no more than the call itself (the tensors it names
+    are held).  See ``eval_fold`` for the arguments."""
+
+    def __init__(self, logits: Tensor, labels: Tensor, valid: Tensor, state: Tensor, loss: Tensor, confusion: Tensor,
+                 pred_out: Optional[Tensor] = None, logits_out: Optional[Tensor] = None, capacity: Optional[int] = None,
+                 scratch: Optional[Tensor] = None):
+        who = "eval_fold"
+        if logits.dim() != 2 or logits.dtype != torch.float32 or logits.size(0) < 1 or logits.size(1) < 1 or \
+                (logits.size(1) > 1 and logits.stride(1) != 1) or (logits.size(0) > 1 and logits.stride(0) < logits.size(1)):
+            raise ValueError(f"{who}: logits must be fp32 [B, C] with unit column stride and a row stride of at least C, got "
+                             f"{tuple(logits.shape)} {logits.dtype} strides {tuple(logits.stride())}")
+        B, C = logits.shape
+        ld = logits.stride(0) if B > 1 else max(C, logits.stride(0))
+        if not 1 <= C <= EVAL_MAX_C:
+            raise ValueError(f"{who}: {C} classes; 1..{EVAL_MAX_C}")
+        if labels.dtype != torch.int64 or labels.shape != (B,) or not labels.is_contiguous():
+            raise ValueError(f"{who}: labels must be contiguous int64 [{B}], got {tuple(labels.shape)} {labels.dtype}")
+        _eval_block(who, "valid", valid, torch.int32, 1, 4)
+        _eval_block(who, "state", state, torch.int32, 8, 16)
+        _eval_block(who, "loss", loss, torch.float64, 1, 8)
+        _eval_block(who, "confusion", confusion, torch.int32, C * C, 4)
+        for name, t, dt, cols in (("pred_out", pred_out, torch.int64, None), ("logits_out", logits_out, torch.float32, C)):
+            if t is None:
+                continue
+            if t.dtype != dt or not t.is_contiguous() or t.dim() != (1 if cols is None else 2) or t.size(0) < 1 or \
+                    (cols is not None and t.size(1) != cols):
+                raise ValueError(f"{who}: {name} must be contiguous {dt} [capacity{'' if cols is None else f', {cols}'}], got {tuple(t.shape)} {t.dtype}")
+            if capacity is None:
+                capacity = t.size(0)
+            if t.size(0) < capacity:
+                raise ValueError(f"{who}: {name} holds {t.size(0)} rows, the capacity is {capacity}")
+        if capacity is None or capacity < 1:
+            raise ValueError(f"{who}: a capacity of at least 1 is needed (given, or the rows of pred_out / logits_out)")
+        dev = state.device
+        for name, t in (("logits", logits), ("labels", labels), ("valid", valid), ("loss", loss), ("confusion", confusion),
+                        ("pred_out", pred_out), ("logits_out", logits_out), ("scratch", scratch)):
+            if t is not None and t.device != dev:
+                raise ValueError(f"{who}: {name} lives on {t.device}, the state on {dev}")
+        self.logits, self.labels, self.valid, self.state, self.loss, self.confusion = logits, labels, valid, state, loss, confusion
+        self.pred_out, self.logits_out, self.B, self.C, self.capacity = pred_out, logits_out, B, C, int(capacity)
+        self._args = None
+        if dev.type == "cuda":
+            if scratch is None:
+                scratch = eval_scratch(B, dev)
+            if scratch.dtype != torch.float64 or not scratch.is_contiguous() or scratch.numel() < B + (B + 1) // 2:
+                raise ValueError(f"{who}: the scratch must be {B + (B + 1) // 2} contiguous fp64 words (ops.eval_scratch)")
+            self.scratch = scratch
+            self._args = (logits.data_ptr(), ld, labels.data_ptr(), B, C, valid.data_ptr(), state.data_ptr(), loss.data_ptr(),
+                          confusion.data_ptr(), ptr(pred_out), ptr(logits_out), self.capacity, scratch.data_ptr())
+            self._fn = _lib.load().fst_eval_fold
+
+    def __call__(self) -> None:
+        if self._args is not None:
+            check(self._fn(*self._args, stream_ptr()), "fst_eval_fold")
+            return
+        st, B, C = self.state, self.B, self.C
+        valid = min(max(int(self.valid.view(-1)[0]), 0), B)
+        seen = int(st[EVAL_SEEN])
+        if seen < 0 or seen + valid > self.capacity:
+            st[EVAL_OVERFLOW] += 1
+            return
+        x, y = self.logits[:valid], self.labels[:valid]
+        pred = torch.argmax(x, dim=1)
+        xd = x.double()
+        z = xd - xd.max(dim=1, keepdim=True).values                          # (max propagates a NaN, as the kernel's argmax value does)
+        ok = (y >= 0) & (y < C)
+        picked = z.gather(1, y.clamp(0, C - 1).view(-1, 1)).view(-1)
+        nll = -(picked - torch.log(torch.exp(z).sum(dim=1)))
+        total = float(self.loss.view(-1)[0])
+        for v, k in zip(nll.tolist(), ok.tolist()):                          # one chain of fp64 additions in row order
+            if k:
+                total += v
+        self.loss.view(-1)[0] = total
+        self.confusion.view(-1).index_add_(0, (y * C + pred)[ok], torch.ones(int(ok.sum()), dtype=torch.int32))
+        if self.pred_out is not None:
+            self.pred_out[seen: seen + valid] = pred
+        if self.logits_out is not None:
+            self.logits_out[seen: seen + valid].view(torch.int32).copy_(x.contiguous().view(torch.int32))
+        st[EVAL_HITS] += int(((pred == y) & ok).sum())
+        st[EVAL_BAD_LABEL] += int((~ok).sum())
+        st[EVAL_NONFINITE] += int((~torch.isfinite(x)).any(dim=1).sum())
+        st[EVAL_BATCHES] += 1
+        st[EVAL_SEEN] = seen + valid
+
+
+@torch.no_grad()
+def eval_fold(logits: Tensor, labels: Tensor, valid: Tensor, state: Tensor, loss: Tensor, confusion: Tensor,
+              pred_out: Optional[Tensor] = None, logits_out: Optional[Tensor] = None, capacity: Optional[int] = None,
+              scratch: Optional[Tensor] = None) -> None:
+    """Fold one batch into a running evaluation (``fst_eval_fold``: two launches on the current stream, nothing waits for the
+    device).  ``logits`` fp32 [B, C] (rows may be strided), ``labels`` int64 [B], ``valid`` one int32 word (rows ``0..valid-1``
+    count, clamped to ``0..B``; the others are never read), ``state`` eight int32 words on a 16-byte boundary indexed by
+    ``EVAL_SEEN`` ... ``EVAL_OVERFLOW``, ``loss`` one fp64 word, ``confusion`` int32 [C, C] (row = label, column = prediction),
+    ``pred_out`` int64 [capacity] and ``logits_out`` fp32 [capacity, C] (either optional), written at rows ``seen..seen+valid-1``.
+    Per valid row: the prediction is ``torch.argmax``'s on the CPU (first maximum, a NaN beats every number); the loss term is
+    ``F.cross_entropy(row.double(), label)``, added to ``loss`` in row order; a label outside ``0..C-1`` is counted in
+    ``bad_label`` and enters neither hits nor confusion nor loss; a row with a NaN or an inf is counted in ``nonfinite``.  A call
+    that finds ``seen + valid > capacity`` writes nothing but ``overflow += 1``.  All words are read when the kernels run.  On CPU
+    tensors the same in plain torch (``torch.argmax``, fp64 log-softmax, a Python chain of additions): the executable
+    specification — equal predictions, confusion, stored logits and state words, a loss equal up to the order of a row's sum."""
+    EvalFoldCall(logits, labels, valid, state, loss, confusion, pred_out, logits_out, capacity, scratch)()
+
+
+class EvalFinishCall:
+    """One validated ``fst_eval_finish`` call; see ``eval_finish``."""
+
+    def __init__(self, state: Tensor, loss: Tensor, expect_rows: int, best: Tensor, mode: int = 0):
+        who = "eval_finish"
+        _eval_block(who, "state", state, torch.int32, 8, 16)
+        _eval_block(who, "loss", loss, torch.float64, 1, 8)
+        _eval_block(who, "best", best, torch.int32, 8, 16)
+        if mode not in (0, 1) or not 0 <= int(expect_rows) < 1 << 31:
+            raise ValueError(f"{who}: mode {mode!r} (0: accuracy, 1: loss), expect_rows {expect_rows!r} (0..2^31 - 1)")
+        if not (state.device == loss.device == best.device):
+            raise ValueError(f"{who}: every tensor must live on one device")
+        self.state, self.loss, self.best, self.expect_rows, self.mode = state, loss, best, int(expect_rows), int(mode)
+        self._args = None
+        if state.device.type == "cuda":
+            self._args = (state.data_ptr(), loss.data_ptr(), self.expect_rows, best.data_ptr(), self.mode)
+            self._fn = _lib.load().fst_eval_finish
+
+    def __call__(self) -> None:
+        if self._args is not None:
+            check(self._fn(*self._args, stream_ptr()), "fst_eval_finish")
+            return
+        st, best = self.state, self.best
+        hits, loss = int(st[EVAL_HITS]), float(self.loss.view(-1)[0])
+        complete = int(st[EVAL_SEEN]) == self.expect_rows and int(st[EVAL_OVERFLOW]) == 0 and int(st[EVAL_BAD_LABEL]) == 0
+        better = hits > int(best[EVAL_BEST_HITS]) if self.mode == 0 else loss < float(eval_best_loss(best)[0])
+        passes = int(best[EVAL_PASSES]) + 1
+        if not complete:
+            best[EVAL_INCOMPLETE] += 1
+        if complete and better:
+            best[EVAL_BEST_HITS], best[EVAL_BEST_PASS] = hits, passes
+            eval_best_loss(best)[0] = loss
+        best[EVAL_IMPROVED] = int(complete and better)
+        best[EVAL_PASSES] = passes
+
+
+@torch.no_grad()
+def eval_finish(state: Tensor, loss: Tensor, expect_rows: int, best: Tensor, mode: int = 0) -> None:
+    """Close a pass (``fst_eval_finish``: one launch).  ``best``: eight 4-byte words on a 16-byte boundary (``eval_best_block``),
+    indexed by ``EVAL_IMPROVED`` ... ``EVAL_INCOMPLETE``, ``best_loss`` an fp64 at words 4..5 (``eval_best_loss``).  The pass is
+    complete if ``seen == expect_rows`` and ``overflow == bad_label == 0``; ``improved`` = complete and (``mode`` 0: ``hits >
+    best_hits``; 1: ``loss < best_loss``, which a NaN never is); where it improved the best words take this pass's values
+    (``best_pass`` = the pass's number counted from 1); an incomplete pass is counted; ``passes += 1``.  The same on CPU tensors."""
+    EvalFinishCall(state, loss, expect_rows, best, mode)()

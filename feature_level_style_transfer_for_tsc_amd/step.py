@@ -552,6 +552,11 @@ class ClassifierTrainer(_WeightAveraging, _GradAccumulating, _Fed):
         self.feeder.feed(self._g_x, self._g_y)
         return self._replay_graphs()
 
+    def make_evaluator(self, data, batch_size: int, **kw):
+        """An ``evaluate.Evaluator`` of (``fe``, ``clf``) over the resident ``data``; ``kw`` are its other arguments."""
+        from .evaluate import Evaluator
+        return Evaluator(self.fe, self.clf, data, batch_size, **kw)
+
 
 def _enable_weight_average(trainer, arg) -> None:
     """The constructors' ``weight_average=``: None / False, True, a decay, or a dict of enable_weight_average's arguments."""
@@ -1464,6 +1469,16 @@ class JointTrainer(_WeightAveraging, _GradAccumulating, _Fed):
         gi = rec["in"]
         self.feeder.feed(gi["x_t"], gi["y_t"], gi["x_s"], gi["y_s"], t=gi["t"])
         return self._replay_phase_graphs(rec)
+
+    def make_evaluator(self, side: str, data, batch_size: int, **kw):
+        """An ``evaluate.Evaluator`` over the resident ``data``: ``side="target"`` evaluates (``fe_t``, ``clf_t``), ``side="source"``
+        (``fe_s``, ``clf_s``) through ``dimunif``; ``kw`` are its other arguments."""
+        from .evaluate import Evaluator
+        if side == "target":
+            return Evaluator(self.m["fe_t"], self.m["clf_t"], data, batch_size, **kw)
+        if side == "source":
+            return Evaluator(self.m["fe_s"], self.m["clf_s"], data, batch_size, feature_trans=self.m["dimunif"], **kw)
+        raise ValueError(f"make_evaluator(): side must be 'target' or 'source', got {side!r}")
 
     def _accum_phase_graphs(self, what: str) -> None:
         """A captured phase is one whole step per replay: the phase graphs have no micro-step / update split."""

@@ -27,6 +27,21 @@ def precision_weights(train_logits: torch.Tensor, train_labels: torch.Tensor) ->
 
 
 @torch.no_grad()
+def precision_weights_from_confusion(confusion: torch.Tensor) -> torch.Tensor:
+    """[K, C, C] train-set confusion matrices (row = label, column = prediction: ``Evaluator``'s) -> [K, C] weights: the
+    precision of class c is ``cm[c, c] / cm[:, c].sum()``, then ``precision_weights``' rules (0 for a class never predicted,
+    divided by the mean over models, 0/0 -> 0) in its float64.  Equal to ``precision_weights(train_logits, labels)`` exactly:
+    both are ratios of the same integers."""
+    if confusion.dim() != 3 or confusion.size(1) != confusion.size(2):
+        raise ValueError(f"precision_weights_from_confusion: [K, C, C] expected, got {tuple(confusion.shape)}")
+    cm = confusion.to(torch.float64)
+    predicted = cm.sum(dim=1)                                                      # [K, C]: column sums
+    correct = torch.diagonal(cm, dim1=1, dim2=2)
+    w = torch.where(predicted > 0, correct / predicted.clamp(min=1), torch.zeros_like(predicted))
+    return torch.nan_to_num(w / w.mean(dim=0, keepdim=True), nan=0.0, posinf=0.0, neginf=0.0)
+
+
+@torch.no_grad()
 def vote_scores(test_logits: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:
     """[K, M, C] logits + [K, C] weights -> [M, C] summed scores (:406-422)."""
     p = torch.softmax(test_logits.float(), dim=2)

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FST_ABI_VERSION 25
+#define FST_ABI_VERSION 26
 
 int fst_version(void);
 const char* fst_last_error(void);
@@ -728,6 +728,46 @@ int fst_accum_multi(float* const* acc_host, float* const* g_host, const int64_t*
 int fst_feed_batch(const void* const* src_host, void* const* dst_host, const int32_t* const* index_host,
                    const int64_t* row_words_host, const int64_t* n_rows_host, const int64_t* batch_host, int n_streams,
                    const void* const* table_host, void* const* scalar_dst_host, int n_scalars, void* state_dev, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Evaluation on the device (ABI v26): a pass over a data set folded batch by batch into device words, and closed by a launch that
+ * decides on the device whether the pass is the best so far.  Every argument is validated on the host before the first launch: a
+ * refused call has written nothing.  Every word that steers a kernel is read when the kernel RUNS.  No float atomics.
+ *
+ * eval_fold folds one batch.  logits: fp32 [B][ld], ld >= C; labels: int64 [B]; valid_dev: one int32 word, clamped to 0..B: rows
+ * 0..valid-1 count, the others are padding and are never read (neither their logits nor their labels).
+ * state_dev is a 16-byte aligned block of eight int32 words: [0] seen (rows folded in this pass; also where this batch's outputs
+ * go), [1] hits, [2] batches, [3] bad_label (labels outside 0..C-1), [4] nonfinite (rows holding a NaN or an inf), [5] overflow
+ * (calls that found seen + valid > capacity), [6..7] reserved, zero.  loss_dev: one fp64 word.  confusion_dev: int32 [C][C],
+ * row = label, column = prediction.  pred_out: int64 [capacity] and logits_out: fp32 [capacity][C], either may be NULL; both are
+ * written at rows seen..seen+valid-1 (the logits moved as 32-bit integers: every bit pattern survives).  scratch: B fp64 words
+ * followed by B int32 words, 8-byte aligned, contents of no meaning between calls.
+ * If seen + valid > capacity the call writes nothing but overflow += 1.  Otherwise, per valid row:
+ *   pred = the first index of the row's maximum as torch.argmax finds it on the CPU: a NaN beats every number and the first NaN
+ *          wins; -0.0 == +0.0 is a tie that the lower index takes;
+ *   nll  = -((x[label] - m) - log(sum_c exp(x[c] - m))), m the row's maximum, evaluated in fp64 from the fp32 logits: what
+ *          F.cross_entropy(row.double(), label) evaluates; a NaN or an inf in the row so makes it NaN;
+ *   a label outside 0..C-1 is counted in bad_label, its prediction (and logits) still stored, and it enters neither hits nor the
+ *   confusion matrix nor the loss; otherwise confusion[label][pred] += 1 (integer atomic), hits += (pred == label);
+ *   a row holding a NaN or an inf is counted in nonfinite and folded like any other.
+ * A one-workgroup launch behind the rows then adds the rows' nll to loss_dev as ONE chain of fp64 additions in row order,
+ * starting from the word's value (the loss of a pass does not depend on how the pass is cut into batches), and moves seen, hits,
+ * batches and the counters on with plain stores from one lane.  One wave per row, four rows per 256-thread workgroup.
+ * 1 <= B < 2^31, 1 <= C <= 4096, C <= ld < 2^31, 1 <= capacity < 2^31; pointers 4-byte aligned, those to int64 / fp64 data and the
+ * scratch 8-byte, the state block 16-byte; no output (state, loss, confusion, pred_out, logits_out, scratch) overlaps an input
+ * (logits, labels, valid) or another output.
+ *
+ * eval_finish closes a pass: one workgroup.  best_dev is a 16-byte aligned block of eight 4-byte words: [0] improved (int32,
+ * written by every call), [1] passes, [2] best_hits (int32, initially -1), [3] best_pass (the value of passes, counted from 1, of
+ * the best pass), [4..5] best_loss (fp64, initially +inf), [6] incomplete, [7] reserved.  The pass is complete if seen ==
+ * expect_rows and overflow == 0 and bad_label == 0.  improved = complete and (mode == 0 ? hits > best_hits : loss < best_loss): a
+ * tie does not improve and a NaN loss never does.  Where it improved, best_hits, best_loss and best_pass take this pass's values;
+ * an incomplete pass adds one to incomplete; passes += 1 always.
+ * ------------------------------------------------------------------------------------------- */
+int fst_eval_fold(const float* logits, int64_t ld, const int64_t* labels, int64_t B, int C, const void* valid_dev, void* state_dev,
+                  void* loss_dev, void* confusion_dev, int64_t* pred_out, float* logits_out, int64_t capacity, void* scratch,
+                  void* stream);
+int fst_eval_finish(const void* state_dev, const void* loss_dev, int64_t expect_rows, void* best_dev, int mode, void* stream);
 
 #ifdef __cplusplus
 }
