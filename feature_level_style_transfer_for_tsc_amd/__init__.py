@@ -18,10 +18,10 @@ from .optim import (AnomalyGuard, GradAccumulation, GradClip, WeightAverage, acc
                     scale_by_group, sumsq_norms, swap_tensors)
 from .dist import GradBucket, shard_batch
 from .data import DeviceDataset, DeviceLoader, EpochFeeder, EvalPlan, TestData, TrainData, load_ts, parse_ts
-from .ops import eval_finish, eval_fold, feed_batch
+from .ops import eval_finish, eval_fold, feed_batch, vote_fold, vote_weights
 from .voting import (collect_logits, multi_source_vote, multi_source_voting, precision_weights,
                      precision_weights_from_confusion, vote_scores)
-from .evaluate import Evaluator
+from .evaluate import Evaluator, VotingEvaluator, make_voter
 from .checkpoint import (eval_accuracy, load_source_classification_modules, load_target_classification_modules,
                          save_source_classification_modules, save_target_classification_modules)
 

@@ -12,7 +12,7 @@ from typing import Optional
 
 import torch
 
-ABI_VERSION = 26
+ABI_VERSION = 27
 _LIB_NAME = "libfst_hip.so"
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FST_HIP_LIB", os.path.join(_HERE, _LIB_NAME))     # override: diagnostic builds only
@@ -76,6 +76,8 @@ _SIGNATURES = {
     "fst_feed_batch": (c_int, [_P, _P, _P, _P, _P, _P, c_int, _P, _P, c_int, _P, c_void_p]),
     "fst_eval_fold": (c_int, [_P, c_int64, _P, c_int64, c_int, _P, _P, _P, _P, _P, _P, c_int64, _P, c_void_p]),
     "fst_eval_finish": (c_int, [_P, _P, c_int64, _P, c_int, c_void_p]),
+    "fst_vote_weights": (c_int, [_P, c_int, c_int, c_float, _P, _P, c_void_p]),
+    "fst_vote_fold": (c_int, [_P, c_int, c_int64, _P, c_int64, c_int, _P, _P, _P, _P, _P, _P, _P, c_float, c_int64, _P, c_void_p]),
     "fst_wn_stack_fwd_ok": (c_int, [c_int, c_int, c_int, c_int]),
     "fst_wn_stack_fwd": (c_int, [_P, _P, _P, c_int64, _P, _P, _P, c_int64, _P, c_int, c_int, c_int, c_int, c_int, c_int64, c_void_p]),
     "fst_wn_stack_infer": (c_int, [_P, _P, _P, c_int64, _P, _P, c_int64, _P, c_int, c_int, c_int, c_int, c_int, c_int64, c_void_p]),

@@ -11,17 +11,7 @@
 // the host before the first launch, every word that steers a kernel (valid, seen, the counters) is read when the kernel RUNS, no
 // float atomics (the confusion cells take integer atomicAdd: integer addition commutes), and the state words are written by
 // plain stores from one lane.
-#include "fst_common.h"
-
-#define EVAL_MAX_C 4096
-
-// the state block, in int32 words (two more are reserved)
-#define EVAL_SEEN 0                 // rows folded in this pass; where this batch's outputs go
-#define EVAL_HITS 1
-#define EVAL_BATCHES 2
-#define EVAL_BAD_LABEL 3            // labels outside 0..C-1
-#define EVAL_NONFINITE 4            // rows holding a NaN or an inf
-#define EVAL_OVERFLOW 5             // calls that found seen + valid > capacity
+#include "eval_words.h"            // EVAL_MAX_C, the state block, a row's word, eval_beats, eval_disjoint: shared with vote.hip
 
 // the best block, in 4-byte words
 #define EVAL_IMPROVED 0
@@ -30,12 +20,6 @@
 #define EVAL_BEST_PASS 3
 #define EVAL_BEST_LOSS 4            // fp64: words 4 and 5
 #define EVAL_INCOMPLETE 6
-
-// a row's word in the scratch: the prediction in the low bits (C <= 4096), the row's flags above it
-#define EVAL_ROW_PRED_MASK 0xFFFF
-#define EVAL_ROW_HIT (1 << 28)
-#define EVAL_ROW_NONFINITE (1 << 29)
-#define EVAL_ROW_BAD_LABEL (1 << 30)
 
 struct EvalArgs {
   const float* logits;
@@ -55,14 +39,6 @@ struct EvalArgs {
 __device__ __forceinline__ int eval_valid(const EvalArgs& a) {
   const int v = a.valid[0];
   return v < 0 ? 0 : (v > a.B ? a.B : v);
-}
-
-// torch.argmax on the CPU: the first index of the maximum, a NaN beats every number and the first NaN wins, -0.0 == +0.0 is a tie
-// for the lower index.  (v, i) against (w, j): does (w, j) take the place of (v, i)?
-__device__ __forceinline__ bool eval_beats(float v, int i, float w, int j) {
-  const bool vn = v != v, wn = w != w;
-  if (vn || wn) return wn && (!vn || j < i);
-  return w > v || (w == v && j < i);
 }
 
 // grid ceil(B / 4) x 256 threads: wave w of a workgroup takes row 4 * blockIdx.x + w, its lanes stride over the C logits.
@@ -176,12 +152,6 @@ __global__ __launch_bounds__(64) void eval_finish_kernel(const int* __restrict__
   }
   best[EVAL_IMPROVED] = complete && better;
   best[EVAL_PASSES] = passes;
-}
-
-static bool eval_disjoint(const void* p, uint64_t p_bytes, const void* q, uint64_t q_bytes) {
-  if (!p || !q) return true;
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return a + p_bytes <= b || b + q_bytes <= a;
 }
 
 extern "C" int fst_eval_fold(const float* logits, int64_t ld, const int64_t* labels, int64_t B, int C, const void* valid_dev,

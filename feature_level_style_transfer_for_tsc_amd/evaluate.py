@@ -11,6 +11,10 @@ trip either.
 
 Every batch, the last partial one included, runs at the static shape ``[B, ...]``: the tail is padded with the set's last row and
 ``eval_fold`` reads only the valid rows.  Eager and replayed passes so issue the same kernels on the same inputs.
+
+``VotingEvaluator`` (``make_voter``) is the multi-source vote of multi_source_voting.py:265-429 in the same manner: a weighing pass
+over the train set (K forwards and K ``eval_fold`` calls per batch, then ``ops.vote_weights``) and a vote pass over the test set
+(K forwards and one ``ops.vote_fold`` per batch, csrc/vote.hip), eager or as captured graphs.
 """
 from __future__ import annotations
 
@@ -24,10 +28,23 @@ from . import ops
 from .data import DeviceDataset, EvalPlan
 from .optim import guard_copy, swap_tensors
 
-__all__ = ["Evaluator"]
+__all__ = ["Evaluator", "VotingEvaluator", "make_voter"]
 
 _CAPTURE_MODE = "thread_local"
 _METRICS = {"accuracy": 0, "loss": 1}
+
+
+def _read_once(tensors: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """Several device tensors in ONE device-to-host copy (as bytes, widest elements first so every view stays aligned)."""
+    order = sorted(tensors, key=lambda k: -tensors[k].element_size())
+    flat = torch.cat([tensors[k].contiguous().view(-1).view(torch.uint8) for k in order]).cpu()
+    out, at = {}, 0
+    for k in order:
+        t = tensors[k]
+        n = t.numel() * t.element_size()
+        out[k] = flat[at: at + n].view(t.dtype).view(t.shape)
+        at += n
+    return out
 
 
 class _Improved:
@@ -225,16 +242,7 @@ class Evaluator:
         return out
 
     def _read(self, tensors: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-        """Several device tensors in ONE device-to-host copy (as bytes, widest elements first so every view stays aligned)."""
-        order = sorted(tensors, key=lambda k: -tensors[k].element_size())
-        flat = torch.cat([tensors[k].contiguous().view(-1).view(torch.uint8) for k in order]).cpu()
-        out, at = {}, 0
-        for k in order:
-            t = tensors[k]
-            n = t.numel() * t.element_size()
-            out[k] = flat[at: at + n].view(t.dtype).view(t.shape)
-            at += n
-        return out
+        return _read_once(tensors)
 
     def result(self) -> dict:
         """The last pass with ONE host read (this waits for the device): Python numbers for the words (``loss`` the mean), CPU
@@ -351,3 +359,310 @@ class Evaluator:
             self.best.copy_(sd["best"].to(torch.int32))
             for k, t in self._shadow.items():
                 t.copy_(sd["shadow"][k])
+
+
+class VotingEvaluator:
+    """The multi-source vote of multi_source_voting.py:265-429 as passes that stay on the device.  ``members``: K (1..16) target-side
+    pipelines, each ``(fe, clf)`` or ``(fe, clf, feature_trans)``; ``train_data`` and ``test_data``: resident ``DeviceDataset``s of
+    one series shape.  A *weighing* pass over ``train_data`` folds every member's predictions into its own confusion matrix
+    (K unchanged ``ops.eval_fold`` calls per batch, the batch fed once) and ends in ``ops.vote_weights``: per-class precision
+    weights relative to the mean over the members, and ``scale = base ** weights``.  A *vote* pass over ``test_data`` runs the K
+    forwards on each batch and folds them with one ``ops.vote_fold`` (csrc/vote.hip): every member's softmax sharpened by its
+    confidence, ``p (1 + sharpen exp(-H(p)))``, scaled per class, summed and argmax-ed, in fp64.  ``base=1, sharpen=2`` is the
+    entropy-only vote.  ``keep_scores``: also keep every row's summed scores, fp64 ``[N, C]``.
+
+    ``run()`` is eager; ``capture()`` / ``replay()`` run the same passes as hipGraphs (a prepare and a batch graph per pass, as
+    ``Evaluator.capture``) with no host tensor, no copy and no wait.  Every batch runs at the static shape ``[B, ...]``."""
+
+    def __init__(self, members, train_data: DeviceDataset, test_data: DeviceDataset, batch_size: int, n_class: Optional[int] = None,
+                 sharpen: float = 120.0, base: float = 9.0, keep_scores: bool = False):
+        members = [tuple(m) for m in members]
+        if not 1 <= len(members) <= ops.VOTE_MAX_K:
+            raise ValueError(f"VotingEvaluator: {len(members)} members; 1..{ops.VOTE_MAX_K}")
+        if any(len(m) not in (2, 3) for m in members):
+            raise ValueError("VotingEvaluator: a member is (fe, clf) or (fe, clf, feature_trans)")
+        self.members = [(m[0], m[1], m[2] if len(m) == 3 else None) for m in members]
+        widths = [clf.hidden.out_features if isinstance(getattr(clf, "hidden", None), nn.Linear) else None for _, clf, _ in self.members]
+        if n_class is None:
+            if widths[0] is None:
+                raise ValueError("VotingEvaluator: n_class is needed (member 0's classifier has no Linear `hidden` to read it from)")
+            n_class = widths[0]
+        if isinstance(n_class, bool) or not isinstance(n_class, int) or not 1 <= n_class <= ops.EVAL_MAX_C:
+            raise ValueError(f"VotingEvaluator: n_class must be in 1..{ops.EVAL_MAX_C}, got {n_class!r}")
+        for k, w in enumerate(widths):
+            if w is not None and w != n_class:
+                raise ValueError(f"VotingEvaluator: member {k}'s classifier has {w} classes, n_class is {n_class}")
+        if train_data.device != test_data.device or train_data.x.shape[1:] != test_data.x.shape[1:]:
+            raise ValueError(f"VotingEvaluator: the two data sets must live on one device and hold one series shape, got "
+                             f"{tuple(train_data.x.shape[1:])} on {train_data.device} and {tuple(test_data.x.shape[1:])} on {test_data.device}")
+        self.sharpen, self.base = ops._vote_f32(sharpen), ops._vote_f32(base)           # as the library receives them
+        if not (self.base > 0.0 and self.base < float("inf")) or not (0.0 <= self.sharpen < float("inf")):
+            raise ValueError(f"VotingEvaluator: base must be positive and finite and sharpen finite and not negative, got {base!r}, {sharpen!r}")
+        self.train_data, self.test_data, self.device = train_data, test_data, test_data.device
+        self.n_class, self.keep_scores, self.batch = n_class, bool(keep_scores), batch_size
+        self.train_plan, self.test_plan = EvalPlan(train_data, batch_size), EvalPlan(test_data, batch_size)
+        self.n_train, self.n = len(train_data), len(test_data)
+        dev, B, C, K = self.device, batch_size, n_class, len(self.members)
+        self.K = K
+        # the static inputs of every batch of either pass, eager or captured
+        self._x = torch.zeros((B,) + tuple(test_data.x.shape[1:]), dtype=torch.float32, device=dev)
+        self._y = torch.zeros(B, dtype=torch.int64, device=dev)
+        self._valid = torch.zeros(1, dtype=torch.int32, device=dev)
+        # the words of a vote pass as ONE block, zeroed by one fill: state (8 int32), member_hits (16), confusion (C x C)
+        self._pass = torch.zeros(24 + C * C, dtype=torch.int32, device=dev)
+        # ... and of a weighing pass: per member state (8), loss (fp64), confusion (C x C), each on a 16-byte boundary
+        stride = (10 + C * C + 3) // 4 * 4
+        self._weigh_pass = torch.zeros(K * stride, dtype=torch.int32, device=dev)
+        if self._pass.data_ptr() % 16 or self._weigh_pass.data_ptr() % 16:
+            raise RuntimeError("VotingEvaluator: the allocator returned a block off a 16-byte boundary")
+        self.state, self.member_hits, self.confusion = self._pass[:8], self._pass[8: 8 + K], self._pass[24:].view(C, C)
+        blocks = [self._weigh_pass[k * stride: k * stride + 10 + C * C] for k in range(K)]
+        self._member_state = [b[:8] for b in blocks]
+        self._member_loss = [b[8:10].view(torch.float64) for b in blocks]
+        self.member_confusion = [b[10:].view(C, C) for b in blocks]
+        self.weights = torch.zeros(K, C, dtype=torch.float64, device=dev)
+        self.scale = torch.ones(K, C, dtype=torch.float64, device=dev)
+        self.predictions = torch.zeros(self.n, dtype=torch.int64, device=dev)
+        self.scores = torch.zeros(self.n, C, dtype=torch.float64, device=dev) if keep_scores else None
+        on_gpu = dev.type == "cuda"
+        self._scratch = ops.eval_scratch(B, dev) if on_gpu else None
+        self._vote_scratch = ops.vote_scratch(B, dev) if on_gpu else None
+        self._weights_call = ops.VoteWeightsCall(self.member_confusion, self.weights, self.scale, self.base)
+        self._weighted = False                                                # weights are in place: weigh() or set_weights()
+        self._weighed_here = False                                            # ... by a weighing pass of this object
+        self._graphs = None                                                   # (weigh prepare, weigh batch, vote prepare, vote batch)
+        self._caches = None                                                   # the two capture-time pack caches, kept alive here
+        self._held = None
+
+    # ------------------------------------------------------------------ the passes
+    def _modules(self):
+        seen, out = set(), []
+        for member in self.members:
+            for m in member:
+                if m is not None and id(m) not in seen:
+                    seen.add(id(m))
+                    out.append(m)
+        return out
+
+    @contextlib.contextmanager
+    def _eval_mode(self):
+        mods = self._modules()
+        modes = [m.training for m in mods]
+        for m in mods:
+            m.eval()
+        try:
+            with torch.no_grad():
+                yield
+        finally:
+            for m, mode in zip(mods, modes):
+                m.train(mode)
+
+    def _forward(self, k: int) -> torch.Tensor:
+        fe, clf, trans = self.members[k]
+        f = fe(self._x)
+        if trans is not None:
+            f = trans(f)
+        out = clf(f)
+        logits = out[0] if isinstance(out, (tuple, list)) else out
+        if logits.dim() != 2 or logits.shape != (self.batch, self.n_class) or logits.dtype != torch.float32:
+            raise ValueError(f"VotingEvaluator: member {k}'s classifier returned {tuple(logits.shape)} {logits.dtype}; fp32 "
+                             f"[{self.batch}, {self.n_class}] expected")
+        return logits
+
+    def _weigh_begin(self) -> None:
+        self.train_plan.rewind()
+        self._weigh_pass.zero_()
+
+    def _weigh_round(self):
+        """Feed once, K forwards, K ``eval_fold`` calls; returns what a graph that captured the round must keep alive."""
+        self.train_plan.feed(self._x, self._y, self._valid)
+        held = []
+        for k in range(self.K):
+            logits = self._forward(k)
+            call = ops.EvalFoldCall(logits, self._y, self._valid, self._member_state[k], self._member_loss[k], self.member_confusion[k],
+                                    capacity=self.n_train, scratch=self._scratch)
+            call()
+            held.append((logits, call))
+        return held
+
+    def _vote_begin(self) -> None:
+        self.test_plan.rewind()
+        self._pass.zero_()
+
+    def _vote_round(self):
+        """Feed once, K forwards, one ``vote_fold``."""
+        self.test_plan.feed(self._x, self._y, self._valid)
+        logits = [self._forward(k) for k in range(self.K)]
+        call = ops.VoteFoldCall(logits, self.scale, self._y, self._valid, self.state, self.member_hits, self.confusion, self.predictions,
+                                self.scores, sharpen=self.sharpen, capacity=self.n, scratch=self._vote_scratch)
+        call()
+        return logits, call
+
+    def _need_weights(self, what: str) -> None:
+        if not self._weighted:
+            raise RuntimeError(f"{what}: no weights yet; call weigh() or set_weights() first, or pass weigh=True")
+
+    def weigh(self) -> torch.Tensor:
+        """One eager weighing pass over ``train_data`` and ``ops.vote_weights``; returns ``weights`` (the resident tensor)."""
+        with self._eval_mode(), ops.pack_cache():
+            self._weigh_begin()
+            for _ in range(self.train_plan.rounds):
+                self._weigh_round()
+        self._weights_call()
+        self._weighted = self._weighed_here = True
+        return self.weights
+
+    @torch.no_grad()
+    def set_weights(self, w) -> None:
+        """Weights computed elsewhere, ``[K, C]``, in the place of a weighing pass: written into ``weights`` and, as ``base ** w``,
+        into ``scale``, in place."""
+        w = torch.as_tensor(w, dtype=torch.float64)
+        if w.shape != self.weights.shape:
+            raise ValueError(f"set_weights(): [{self.K}, {self.n_class}] expected, got {tuple(w.shape)}")
+        self.weights.copy_(w)
+        torch.pow(torch.tensor(self.base, dtype=torch.float64, device=self.device), self.weights, out=self.scale)
+        self._weighted = True
+
+    def run(self, weigh: bool = False) -> Dict[str, torch.Tensor]:
+        """One eager vote pass over ``test_data`` (after a weighing pass with ``weigh=True``): the modules in eval mode (their modes
+        restored afterwards), under ``torch.no_grad()`` and one ``ops.pack_cache()``.  Returns ``report()``: no host read."""
+        if weigh:
+            self.weigh()
+        self._need_weights("run()")
+        with self._eval_mode(), ops.pack_cache():
+            self._vote_begin()
+            for _ in range(self.test_plan.rounds):
+                self._vote_round()
+        return self.report()
+
+    def capture(self, warmup: int = 1) -> None:
+        """Capture both passes as hipGraphs sharing one pool, each as ``Evaluator.capture`` does: a *prepare* graph (rewind, zero the
+        pass's words, round 0, whose forwards fold the BatchNorms and pack the weights) and a *batch* graph for every later round.
+        Each pass is captured under a pack cache of its own, so either prepare graph recomputes the folds and images it is served
+        by from the live parameter storage: replaying the vote pass alone evaluates the weights as they are then."""
+        if self.device.type != "cuda":
+            raise RuntimeError("VotingEvaluator.capture(): a GPU is needed")
+        if ops._PACK_CACHE is not None:
+            raise RuntimeError("VotingEvaluator.capture(): inside an ops.pack_cache() scope; capture outside it")
+        passes = ((self._weigh_begin, self._weigh_round), (self._vote_begin, self._vote_round))
+        with self._eval_mode():
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for begin, one_round in passes:
+                    for _ in range(max(1, warmup)):
+                        with ops.pack_cache():
+                            begin()
+                            one_round()
+                    begin()
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            graphs, caches, held, pool = [], [], [], None
+            for begin, one_round in passes:
+                prepare, batch = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+                with ops.pack_cache():
+                    caches.append(ops._PACK_CACHE)
+                    with torch.cuda.graph(prepare, pool=pool, capture_error_mode=_CAPTURE_MODE):
+                        begin()
+                        held.append(one_round())
+                    pool = prepare.pool()
+                    with torch.cuda.graph(batch, pool=pool, capture_error_mode=_CAPTURE_MODE):
+                        held.append(one_round())
+                graphs += [prepare, batch]
+        self._graphs, self._caches, self._held = tuple(graphs), caches, held
+
+    def replay(self, weigh: bool = False, report: bool = True) -> Optional[Dict[str, torch.Tensor]]:
+        """The captured vote pass (after the captured weighing pass and ``vote_weights`` with ``weigh=True``): launches only — no
+        host tensor, no host-to-device copy, no wait.  Returns ``report()``, or nothing with ``report=False``."""
+        if self._graphs is None:
+            raise RuntimeError("call capture() first")
+        weigh_prepare, weigh_batch, vote_prepare, vote_batch = self._graphs
+        if weigh:
+            weigh_prepare.replay()
+            for _ in range(self.train_plan.rounds - 1):
+                weigh_batch.replay()
+            self._weights_call()
+            self._weighted = self._weighed_here = True
+        self._need_weights("replay()")
+        vote_prepare.replay()
+        for _ in range(self.test_plan.rounds - 1):
+            vote_batch.replay()
+        return self.report() if report else None
+
+    def release(self) -> None:
+        """Drop the captured graphs and what they kept alive."""
+        self._graphs = self._caches = self._held = None
+
+    # ------------------------------------------------------------------ what a pass leaves
+    def report(self) -> Dict[str, torch.Tensor]:
+        """The last vote pass as fresh DEVICE tensors (copies within device memory; no host read): ``seen``, ``hits``, ``accuracy``
+        (fp64), ``confusion`` [C, C], ``predictions`` [N], ``labels`` (the resident ``test_data.y`` itself), ``member_hits`` [K],
+        ``member_accuracy`` (fp64 [K]), ``weights`` and ``scale`` (fp64 [K, C]), ``scores`` (fp64 [N, C]) with ``keep_scores``; the
+        counters ``batches``, ``bad_label``, ``nonfinite``, ``overflow``."""
+        st, member_hits = self.state.clone(), self.member_hits.clone()
+        hits = st[ops.EVAL_HITS]
+        out = {"seen": st[ops.EVAL_SEEN], "hits": hits, "accuracy": hits.to(torch.float64) / self.n, "confusion": self.confusion.clone(),
+               "predictions": self.predictions.clone(), "labels": self.test_data.y, "member_hits": member_hits,
+               "member_accuracy": member_hits.to(torch.float64) / self.n, "weights": self.weights.clone(), "scale": self.scale.clone(),
+               "batches": st[ops.EVAL_BATCHES], "bad_label": st[ops.EVAL_BAD_LABEL], "nonfinite": st[ops.EVAL_NONFINITE],
+               "overflow": st[ops.EVAL_OVERFLOW]}
+        if self.scores is not None:
+            out["scores"] = self.scores.clone()
+        return out
+
+    def result(self) -> dict:
+        """The last vote pass with ONE host read (this waits for the device): Python numbers for the words, CPU tensors for
+        ``confusion``, ``predictions``, ``member_hits``, ``member_accuracy``, ``weights``, ``scale`` and, with ``keep_scores``,
+        ``scores``; ``feed`` holds the test plan's counters."""
+        parts = {"pass": self._pass, "feed": self.test_plan.state, "predictions": self.predictions, "weights": self.weights,
+                 "scale": self.scale}
+        if self.scores is not None:
+            parts["scores"] = self.scores
+        h = _read_once(parts)
+        C, K = self.n_class, self.K
+        st, member_hits = h["pass"][:8].tolist(), h["pass"][8: 8 + K].clone()
+        out = {"seen": st[ops.EVAL_SEEN], "hits": st[ops.EVAL_HITS], "accuracy": st[ops.EVAL_HITS] / self.n,
+               "confusion": h["pass"][24:].view(C, C).clone(), "predictions": h["predictions"].clone(), "member_hits": member_hits,
+               "member_accuracy": member_hits.to(torch.float64) / self.n, "weights": h["weights"].clone(), "scale": h["scale"].clone(),
+               "batches": st[ops.EVAL_BATCHES], "bad_label": st[ops.EVAL_BAD_LABEL], "nonfinite": st[ops.EVAL_NONFINITE],
+               "overflow": st[ops.EVAL_OVERFLOW],
+               "feed": {"overrun": int(h["feed"][ops.FEED_OVERRUN]), "bad_index": int(h["feed"][ops.FEED_BAD_INDEX])}}
+        if self.scores is not None:
+            out["scores"] = h["scores"].clone()
+        return out
+
+    def check(self) -> None:
+        """One host read; raises if the last vote pass (or, where this object weighed, the last weighing pass) overflowed its
+        capacity, met a label outside ``0..C-1`` or did not see every row, or if a plan was fed past its end or held an index
+        outside its data set."""
+        parts = {"state": self.state, "feed": self.test_plan.state, "train_feed": self.train_plan.state}
+        parts.update({f"member {k}": s for k, s in enumerate(self._member_state)})
+        h = {k: v.tolist() for k, v in _read_once(parts).items()}
+        found = {}
+        blocks = [("", h["state"], self.n)]
+        if self._weighed_here:
+            blocks += [(f"member {k} ", h[f"member {k}"], self.n_train) for k in range(self.K)]
+        for who, st, rows in blocks:
+            found[who + "overflow"], found[who + "bad_label"] = st[ops.EVAL_OVERFLOW], st[ops.EVAL_BAD_LABEL]
+            found[who + "rows missing"] = rows - st[ops.EVAL_SEEN]
+        for who, feed in (("", h["feed"]), ("train ", h["train_feed"])):
+            found[who + "overrun"], found[who + "bad_index"] = feed[ops.FEED_OVERRUN], feed[ops.FEED_BAD_INDEX]
+        if any(found.values()):
+            raise RuntimeError("VotingEvaluator: " + ", ".join(f"{k} = {v}" for k, v in found.items() if v))
+
+
+def make_voter(trainers, train_data: DeviceDataset, test_data: DeviceDataset, batch_size: int, **kw) -> VotingEvaluator:
+    """A ``VotingEvaluator`` over K trained pipelines: each entry a ``JointTrainer`` (its target side, ``fe_t`` and ``clf_t``), a
+    ``ClassifierTrainer`` (``fe`` and ``clf``) or a ``(fe, clf[, feature_trans])`` tuple; ``kw`` are ``VotingEvaluator``'s other
+    arguments."""
+    members = []
+    for k, t in enumerate(trainers):
+        if isinstance(t, (tuple, list)):
+            members.append(tuple(t))
+        elif isinstance(getattr(t, "m", None), dict) and "fe_t" in t.m and "clf_t" in t.m:
+            members.append((t.m["fe_t"], t.m["clf_t"]))
+        elif hasattr(t, "fe") and hasattr(t, "clf"):
+            members.append((t.fe, t.clf))
+        else:
+            raise ValueError(f"make_voter(): entry {k} is neither a trainer nor a (fe, clf) tuple: {type(t).__name__}")
+    return VotingEvaluator(members, train_data, test_data, batch_size, **kw)

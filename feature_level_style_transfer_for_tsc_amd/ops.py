@@ -2823,3 +2823,214 @@ def eval_finish(state: Tensor, loss: Tensor, expect_rows: int, best: Tensor, mod
     best_hits``; 1: ``loss < best_loss``, which a NaN never is); where it improved the best words take this pass's values
     (``best_pass`` = the pass's number counted from 1); an incomplete pass is counted; ``passes += 1``.  The same on CPU tensors."""
     EvalFinishCall(state, loss, expect_rows, best, mode)()
+
+
+# ---- multi-source voting on the device: weights from confusion matrices, a vote folded batch by batch (csrc/vote.hip)
+VOTE_MAX_K = 16
+
+
+def vote_scratch(B: int, device) -> Tensor:
+    """``fst_vote_fold``'s scratch for batches of ``B`` rows: 2 B int32 words."""
+    return torch.empty(2 * B, dtype=torch.int32, device=device)
+
+
+def _vote_f32(v: float) -> float:
+    """``v`` as the fp32 value the library receives (``base`` and ``sharpen`` cross the ABI as fp32 and are widened there)."""
+    return float(torch.tensor(float(v), dtype=torch.float32))
+
+
+def _vote_members(who: str, members: Sequence[Tensor]) -> int:
+    K = len(members)
+    if not 1 <= K <= VOTE_MAX_K:
+        raise ValueError(f"{who}: {K} members; 1..{VOTE_MAX_K}")
+    return K
+
+
+class VoteWeightsCall:
+    """One validated ``fst_vote_weights`` call, kept so that issuing it again costs no more than the call itself (the tensors it
+    names are held).  See ``vote_weights`` for the arguments."""
+
+    def __init__(self, confusions: Sequence[Tensor], weights_out: Tensor, scale_out: Tensor, base: float = 9.0):
+        who = "vote_weights"
+        confusions = list(confusions)
+        K = _vote_members(who, confusions)
+        first = confusions[0]
+        if first.dim() != 2 or first.size(0) != first.size(1) or not 1 <= first.size(0) <= EVAL_MAX_C:
+            raise ValueError(f"{who}: a confusion matrix is int32 [C, C] with C in 1..{EVAL_MAX_C}, got {tuple(first.shape)}")
+        C = first.size(0)
+        for k, cm in enumerate(confusions):
+            if cm.dtype != torch.int32 or cm.shape != (C, C) or not cm.is_contiguous():
+                raise ValueError(f"{who}: the confusion matrix of member {k} must be contiguous int32 [{C}, {C}], got {tuple(cm.shape)} {cm.dtype}")
+        base = _vote_f32(base)
+        if not (0.0 < base < math.inf):
+            raise ValueError(f"{who}: base must be positive and finite, got {base!r}")
+        dev = weights_out.device
+        for name, t in (("weights_out", weights_out), ("scale_out", scale_out)):
+            if t.dtype != torch.float64 or t.shape != (K, C) or not t.is_contiguous() or t.data_ptr() % 8:
+                raise ValueError(f"{who}: {name} must be contiguous fp64 [{K}, {C}], got {tuple(t.shape)} {t.dtype}")
+        for name, t in [("scale_out", scale_out)] + [(f"the confusion matrix of member {k}", cm) for k, cm in enumerate(confusions)]:
+            if t.device != dev:
+                raise ValueError(f"{who}: {name} lives on {t.device}, weights_out on {dev}")
+        self.confusions, self.weights_out, self.scale_out, self.base, self.K, self.C = confusions, weights_out, scale_out, base, K, C
+        self._args = None
+        if dev.type == "cuda":
+            self._table = _ptr_table(confusions)
+            self._args = (self._table, K, C, base, weights_out.data_ptr(), scale_out.data_ptr())
+            self._fn = _lib.load().fst_vote_weights
+        else:
+            self._base = torch.tensor(base, dtype=torch.float64)
+
+    def __call__(self) -> None:
+        if self._args is not None:
+            check(self._fn(*self._args, stream_ptr()), "fst_vote_weights")
+            return
+        cm = torch.stack(self.confusions)                                     # [K, C, C]
+        predicted = cm.sum(dim=1, dtype=torch.int64)                          # column sums, as integers
+        correct = torch.diagonal(cm, dim1=1, dim2=2).to(torch.float64)
+        prec = torch.where(predicted > 0, correct / predicted.clamp(min=1).to(torch.float64), torch.zeros_like(correct))
+        total = torch.zeros(self.C, dtype=torch.float64)
+        for k in range(self.K):                                               # k ascending
+            total = total + prec[k]
+        w = prec / (total / self.K)
+        w = torch.where(torch.isfinite(w), w, torch.zeros_like(w))
+        self.weights_out.copy_(w)
+        self.scale_out.copy_(torch.pow(self._base, w))
+
+
+@torch.no_grad()
+def vote_weights(confusions: Sequence[Tensor], weights_out: Tensor, scale_out: Tensor, base: float = 9.0) -> None:
+    """The voting weights of K models from their train-set confusion matrices (``fst_vote_weights``: one launch on the current
+    stream).  ``confusions``: K (1..16) int32 [C, C] tensors, row = label, column = prediction (``eval_fold``'s), read when the
+    kernel runs; ``weights_out`` and ``scale_out``: fp64 [K, C].  The precision of class c for model k is ``cm_k[c, c] /
+    cm_k[:, c].sum()`` (0 for a class it never predicts); the weight is that over the mean over the models (summed with k
+    ascending; 0 / 0 -> 0), ``voting.precision_weights_from_confusion``'s arithmetic in fp64; ``scale_out = base ** weights_out``.
+    On CPU tensors the same in plain torch fp64: the executable specification."""
+    VoteWeightsCall(confusions, weights_out, scale_out, base)()
+
+
+class VoteFoldCall:
+    """One validated ``fst_vote_fold`` call, kept so that issuing it again costs no more than the call itself (the tensors it names
+    are held).  See ``vote_fold`` for the arguments."""
+
+    def __init__(self, logits: Sequence[Tensor], scale: Tensor, labels: Tensor, valid: Tensor, state: Tensor, member_hits: Tensor,
+                 confusion: Tensor, pred_out: Tensor, scores_out: Optional[Tensor] = None, sharpen: float = 120.0,
+                 capacity: Optional[int] = None, scratch: Optional[Tensor] = None):
+        who = "vote_fold"
+        logits = list(logits)
+        K = _vote_members(who, logits)
+        B, C, ld = None, None, None
+        for k, x in enumerate(logits):
+            if x.dim() != 2 or x.dtype != torch.float32 or x.size(0) < 1 or x.size(1) < 1 or (x.size(1) > 1 and x.stride(1) != 1) or \
+                    (x.size(0) > 1 and x.stride(0) < x.size(1)):
+                raise ValueError(f"{who}: the logits of member {k} must be fp32 [B, C] with unit column stride and a row stride of at "
+                                 f"least C, got {tuple(x.shape)} {x.dtype} strides {tuple(x.stride())}")
+            if k == 0:
+                B, C = x.shape
+                ld = x.stride(0) if B > 1 else max(C, x.stride(0))
+            elif x.shape != (B, C) or (B > 1 and x.stride(0) != ld):
+                raise ValueError(f"{who}: the logits of member {k} are {tuple(x.shape)} with row stride {x.stride(0)}; member 0's are "
+                                 f"[{B}, {C}] with {ld}")
+        if not 1 <= C <= EVAL_MAX_C:
+            raise ValueError(f"{who}: {C} classes; 1..{EVAL_MAX_C}")
+        if scale.dtype != torch.float64 or scale.shape != (K, C) or not scale.is_contiguous() or scale.data_ptr() % 8:
+            raise ValueError(f"{who}: scale must be contiguous fp64 [{K}, {C}], got {tuple(scale.shape)} {scale.dtype}")
+        if labels.dtype != torch.int64 or labels.shape != (B,) or not labels.is_contiguous():
+            raise ValueError(f"{who}: labels must be contiguous int64 [{B}], got {tuple(labels.shape)} {labels.dtype}")
+        _eval_block(who, "valid", valid, torch.int32, 1, 4)
+        _eval_block(who, "state", state, torch.int32, 8, 16)
+        _eval_block(who, "member_hits", member_hits, torch.int32, K, 4)
+        _eval_block(who, "confusion", confusion, torch.int32, C * C, 4)
+        for name, t, dt, cols in (("pred_out", pred_out, torch.int64, None), ("scores_out", scores_out, torch.float64, C)):
+            if t is None:
+                if cols is None:
+                    raise ValueError(f"{who}: pred_out is needed")
+                continue
+            if t.dtype != dt or not t.is_contiguous() or t.dim() != (1 if cols is None else 2) or t.size(0) < 1 or \
+                    (cols is not None and t.size(1) != cols):
+                raise ValueError(f"{who}: {name} must be contiguous {dt} [capacity{'' if cols is None else f', {cols}'}], got {tuple(t.shape)} {t.dtype}")
+            if capacity is None:
+                capacity = t.size(0)
+            if t.size(0) < capacity:
+                raise ValueError(f"{who}: {name} holds {t.size(0)} rows, the capacity is {capacity}")
+        if capacity < 1:
+            raise ValueError(f"{who}: a capacity of at least 1 is needed")
+        sharpen = _vote_f32(sharpen)
+        if not (0.0 <= sharpen < math.inf):
+            raise ValueError(f"{who}: sharpen must be finite and not negative, got {sharpen!r}")
+        dev = state.device
+        for name, t in [(f"the logits of member {k}", x) for k, x in enumerate(logits)] + \
+                [("scale", scale), ("labels", labels), ("valid", valid), ("member_hits", member_hits), ("confusion", confusion),
+                 ("pred_out", pred_out), ("scores_out", scores_out), ("scratch", scratch)]:
+            if t is not None and t.device != dev:
+                raise ValueError(f"{who}: {name} lives on {t.device}, the state on {dev}")
+        self.logits, self.scale, self.labels, self.valid, self.state = logits, scale, labels, valid, state
+        self.member_hits, self.confusion, self.pred_out, self.scores_out = member_hits, confusion, pred_out, scores_out
+        self.K, self.B, self.C, self.sharpen, self.capacity = K, B, C, sharpen, int(capacity)
+        self._args = None
+        if dev.type == "cuda":
+            if scratch is None:
+                scratch = vote_scratch(B, dev)
+            if scratch.dtype != torch.int32 or not scratch.is_contiguous() or scratch.numel() < 2 * B:
+                raise ValueError(f"{who}: the scratch must be {2 * B} contiguous int32 words (ops.vote_scratch)")
+            self.scratch = scratch
+            self._table = _ptr_table(logits)
+            self._args = (self._table, K, ld, labels.data_ptr(), B, C, scale.data_ptr(), valid.data_ptr(), state.data_ptr(),
+                          member_hits.data_ptr(), confusion.data_ptr(), pred_out.data_ptr(), ptr(scores_out), sharpen, self.capacity,
+                          scratch.data_ptr())
+            self._fn = _lib.load().fst_vote_fold
+
+    def __call__(self) -> None:
+        if self._args is not None:
+            check(self._fn(*self._args, stream_ptr()), "fst_vote_fold")
+            return
+        st, B, C = self.state, self.B, self.C
+        valid = min(max(int(self.valid.view(-1)[0]), 0), B)
+        seen = int(st[EVAL_SEEN])
+        if seen < 0 or seen + valid > self.capacity:
+            st[EVAL_OVERFLOW] += 1
+            return
+        y = self.labels[:valid]
+        ok = (y >= 0) & (y < C)
+        score = torch.zeros(valid, C, dtype=torch.float64)
+        odd = torch.zeros(valid, dtype=torch.bool)
+        for k, logits in enumerate(self.logits):                              # k ascending
+            x = logits[:valid]
+            self.member_hits[k] += int(((torch.argmax(x, dim=1) == y) & ok).sum())
+            odd |= (~torch.isfinite(x)).any(dim=1)
+            xd = x.double()
+            z = xd - xd.max(dim=1, keepdim=True).values                      # (max propagates a NaN, as the kernel's argmax value does)
+            e = torch.exp(z)
+            s = e.sum(dim=1, keepdim=True)
+            t = torch.where(e == 0, torch.zeros_like(e), e * z).sum(dim=1, keepdim=True)
+            f = 1.0 + self.sharpen * torch.exp(-(torch.log(s) - t / s))
+            score = score + e / s * f * self.scale[k].view(1, C)
+        pred = torch.argmax(score, dim=1)
+        self.confusion.view(-1).index_add_(0, (y * C + pred)[ok], torch.ones(int(ok.sum()), dtype=torch.int32))
+        self.pred_out[seen: seen + valid] = pred
+        if self.scores_out is not None:
+            self.scores_out[seen: seen + valid] = score
+        st[EVAL_HITS] += int(((pred == y) & ok).sum())
+        st[EVAL_BAD_LABEL] += int((~ok).sum())
+        st[EVAL_NONFINITE] += int(odd.sum())
+        st[EVAL_BATCHES] += 1
+        st[EVAL_SEEN] = seen + valid
+
+
+@torch.no_grad()
+def vote_fold(logits: Sequence[Tensor], scale: Tensor, labels: Tensor, valid: Tensor, state: Tensor, member_hits: Tensor,
+              confusion: Tensor, pred_out: Tensor, scores_out: Optional[Tensor] = None, sharpen: float = 120.0,
+              capacity: Optional[int] = None, scratch: Optional[Tensor] = None) -> None:
+    """Fold one batch of K models' logits into a running vote (``fst_vote_fold``: two launches on the current stream, nothing waits
+    for the device).  ``logits``: K (1..16) fp32 [B, C] tensors with one common row stride; ``scale`` fp64 [K, C]
+    (``vote_weights``); ``labels`` int64 [B]; ``valid`` one int32 word (rows ``0..valid-1`` count, clamped to ``0..B``; the others
+    are never read); ``state`` eight int32 words on a 16-byte boundary, ``eval_fold``'s (``EVAL_SEEN`` ... ``EVAL_OVERFLOW``);
+    ``member_hits`` int32 [K]; ``confusion`` int32 [C, C] of the voted prediction; ``pred_out`` int64 [capacity] and ``scores_out``
+    fp64 [capacity, C] (optional), written at rows ``seen..seen+valid-1``.  Per valid row, in fp64 from the fp32 logits: each
+    member's softmax around its maximum, its entropy ``H = log s - T / s`` (``s = sum e``, ``T = sum e (x - m)``, a term with ``e ==
+    0`` counting as 0), ``f = 1 + sharpen exp(-H)``; ``score = sum_k p_k f_k scale[k]`` with k ascending; the voted prediction is
+    ``torch.argmax``'s on the CPU of the scores (first maximum, a NaN beats every number), member k's own is that of its logits.  A
+    label outside ``0..C-1`` is counted in ``bad_label`` and enters neither hits nor member hits nor confusion; a row with a NaN or
+    an inf in any member is counted once in ``nonfinite``.  A call that finds ``seen + valid > capacity`` writes nothing but
+    ``overflow += 1``.  All words are read when the kernels run.  On CPU tensors the same in plain torch fp64: the executable
+    specification — equal predictions, confusion, hits and state words, scores equal up to the order of a row's sums."""
+    VoteFoldCall(logits, scale, labels, valid, state, member_hits, confusion, pred_out, scores_out, sharpen, capacity, scratch)()

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FST_ABI_VERSION 26
+#define FST_ABI_VERSION 27
 
 int fst_version(void);
 const char* fst_last_error(void);
@@ -768,6 +768,49 @@ int fst_eval_fold(const float* logits, int64_t ld, const int64_t* labels, int64_
                   void* loss_dev, void* confusion_dev, int64_t* pred_out, float* logits_out, int64_t capacity, void* scratch,
                   void* stream);
 int fst_eval_finish(const void* state_dev, const void* loss_dev, int64_t expect_rows, void* best_dev, int mode, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Multi-source voting on the device (ABI v27; multi_source_voting.py:265-429): K <= 16 target-side models vote on a test set, batch
+ * by batch, into device words, as eval_fold folds one model's pass.  Every argument is validated on the host before the first
+ * launch: a refused call has written nothing.  Every word that steers a kernel is read when the kernel RUNS.  No float atomics.
+ * All arithmetic is fp64 (base and sharpen arrive as fp32 and are widened).  1 <= K <= 16, 1 <= C <= 4096.
+ *
+ * vote_weights: one launch, one thread per class.  confusion_host: a host array of K device pointers to int32 [C][C], row = label,
+ * column = prediction (eval_fold's), read when the kernel runs.  weights_out, scale_out: fp64 [K][C], 8-byte aligned, overlapping
+ * neither each other nor a matrix.  base > 0 and finite.  Per class c:
+ *   predicted_k = sum_r cm_k[r][c] (an integer sum);  prec_k = predicted_k > 0 ? cm_k[c][c] / predicted_k : 0;
+ *   mean = (sum_k prec_k) / K, summed with k ascending;  w_k = prec_k / mean, a quotient that is not finite (0 / 0) becoming 0;
+ *   weights_out[k][c] = w_k;  scale_out[k][c] = pow(base, w_k).
+ * (voting.precision_weights_from_confusion's arithmetic.)
+ *
+ * vote_fold folds one batch: two launches.  logits_host: a host array of K device pointers to fp32 [B][ld], ld >= C common to all;
+ * scale: fp64 [K][C]; labels: int64 [B]; valid_dev: one int32 word, clamped to 0..B: rows 0..valid-1 count, the others are padding
+ * and are never read.  state_dev: eval_fold's block of eight int32 words, the same meanings ([0] seen ... [5] overflow).
+ * member_hits_dev: int32 [K].  confusion_dev: int32 [C][C] of the VOTED prediction.  pred_out: int64 [capacity]; scores_out: fp64
+ * [capacity][C], may be NULL; both written at rows seen..seen+valid-1.  scratch: 2 B int32 words, contents of no meaning between
+ * calls.  sharpen >= 0 and finite.  If seen + valid > capacity the call writes nothing but overflow += 1.  Otherwise, per valid
+ * row and for each member k (x = its fp32 logits, widened):
+ *   m_k = max_c x_c (a NaN in the row is the maximum);  e_c = exp(x_c - m_k);  s_k = sum_c e_c;
+ *   T_k = sum_c e_c * (x_c - m_k), a term with e_c == 0 counting as 0 (a -inf logit has probability 0 and makes no NaN);
+ *   H_k = log(s_k) - T_k / s_k  (= -sum p log p: two non-negative terms, no cancellation);  f_k = 1 + sharpen * exp(-H_k);
+ * then score_c = sum_k e_kc / s_k * f_k * scale[k][c], summed with k ascending; the voted prediction is the argmax of the scores by
+ * eval_fold's rule (first maximum; a NaN beats every number and the first NaN wins; -0.0 == +0.0 ties to the lower index);
+ * member k's own prediction is that argmax of its fp32 logits.  A label outside 0..C-1 is counted in bad_label, the row's
+ * prediction (and scores) still stored, and it enters neither hits nor member_hits nor the confusion matrix; otherwise
+ * confusion[label][pred] += 1 (integer atomic), hits += (pred == label), member_hits[k] += (member k's prediction == label).  A row
+ * holding a NaN or an inf in any member is counted once in nonfinite and folded like any other.
+ * One wave per row, four rows per 256-thread workgroup, the classes strided over the lanes and every sum over classes closed by
+ * a butterfly, so a row's bits do not depend on the batch it arrives in.  A one-workgroup launch behind the rows adds the rows'
+ * counters in a fixed order and moves seen, hits, batches, the counters and member_hits on with plain stores from one lane.
+ * 1 <= B < 2^31, C <= ld < 2^31, 1 <= capacity < 2^31; pointers 4-byte aligned, those to int64 / fp64 data 8-byte, the state block
+ * 16-byte; no output (state, member_hits, confusion, pred_out, scores_out, scratch) overlaps an input (the logits, labels, scale,
+ * valid) or another output.
+ * ------------------------------------------------------------------------------------------- */
+int fst_vote_weights(const void* const* confusion_host, int K, int C, float base, double* weights_out, double* scale_out,
+                     void* stream);
+int fst_vote_fold(const float* const* logits_host, int K, int64_t ld, const int64_t* labels, int64_t B, int C, const double* scale,
+                  const void* valid_dev, void* state_dev, void* member_hits_dev, void* confusion_dev, int64_t* pred_out,
+                  double* scores_out, float sharpen, int64_t capacity, void* scratch, void* stream);
 
 #ifdef __cplusplus
 }
