@@ -24,14 +24,22 @@ from typing import Dict, Optional, Sequence, Union
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import _capture, ops
 from .data import DeviceDataset, EvalPlan
-from .optim import guard_copy, swap_tensors
+from .optim import exchanged, guard_copy
 
 __all__ = ["Evaluator", "VotingEvaluator", "make_voter"]
 
-_CAPTURE_MODE = "thread_local"
 _METRICS = {"accuracy": 0, "loss": 1}
+# report() / result(): the name of every counter of a pass's state block and of a plan's feed block -> its word
+_STATE_WORDS = {"seen": ops.EVAL_SEEN, "hits": ops.EVAL_HITS, "batches": ops.EVAL_BATCHES, "bad_label": ops.EVAL_BAD_LABEL,
+                "nonfinite": ops.EVAL_NONFINITE, "overflow": ops.EVAL_OVERFLOW}
+_FEED_WORDS = {"overrun": ops.FEED_OVERRUN, "bad_index": ops.FEED_BAD_INDEX}
+
+
+def _named(words, table: Dict[str, int]) -> dict:
+    """The entries of ``table`` out of a block of words: a tensor (0-d views) or the list read from one (Python numbers)."""
+    return {k: words[i] for k, i in table.items()}
 
 
 def _read_once(tensors: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -54,53 +62,53 @@ class _Improved:
         self.verdict = best[ops.EVAL_IMPROVED: ops.EVAL_IMPROVED + 1]
 
 
-class Evaluator:
-    """Evaluate ``classification_module(feature_trans(feature_extraction_module(x)))`` over ``data`` in batches of ``batch_size``.
+def _n_class(who: str, n_class: Optional[int], clf: nn.Module, whose: str) -> int:
+    """The number of classes: given, or the width of ``clf.hidden``."""
+    if n_class is None:
+        hidden = getattr(clf, "hidden", None)
+        if not isinstance(hidden, nn.Linear):
+            raise ValueError(f"{who}: n_class is needed ({whose} classifier has no Linear `hidden` to read it from)")
+        n_class = hidden.out_features
+    if isinstance(n_class, bool) or not isinstance(n_class, int) or not 1 <= n_class <= ops.EVAL_MAX_C:
+        raise ValueError(f"{who}: n_class must be in 1..{ops.EVAL_MAX_C}, got {n_class!r}")
+    return n_class
 
-    ``n_class``: the number of classes (default: ``classification_module.hidden.out_features``).  ``feature_trans``: the source
-    side's DimensionUnification.  ``keep_logits``: also keep every row's logits, ``[N, C]``, on the device.  The classifier may
-    return the logits or a tuple whose first entry they are.  ``accuracy`` and the mean ``loss`` divide by ``len(data)``."""
 
-    def __init__(self, feature_extraction_module: nn.Module, classification_module: nn.Module, data: DeviceDataset, batch_size: int,
-                 n_class: Optional[int] = None, feature_trans: Optional[nn.Module] = None, keep_logits: bool = False):
-        if n_class is None:
-            hidden = getattr(classification_module, "hidden", None)
-            if not isinstance(hidden, nn.Linear):
-                raise ValueError("Evaluator: n_class is needed (the classifier has no Linear `hidden` to read it from)")
-            n_class = hidden.out_features
-        if isinstance(n_class, bool) or not isinstance(n_class, int) or not 1 <= n_class <= ops.EVAL_MAX_C:
-            raise ValueError(f"Evaluator: n_class must be in 1..{ops.EVAL_MAX_C}, got {n_class!r}")
-        self.fe, self.clf, self.feature_trans = feature_extraction_module, classification_module, feature_trans
-        self.data, self.device, self.n_class, self.keep_logits = data, data.device, n_class, bool(keep_logits)
-        self.plan = EvalPlan(data, batch_size)
-        self.batch, self.rounds, self.n = batch_size, self.plan.rounds, len(data)
-        dev, B, C, N = self.device, batch_size, n_class, self.n
-        # the static inputs of every batch, eager or captured
+def _logits(fe, trans, clf, x: torch.Tensor, batch: int, n_class: int, who: str) -> torch.Tensor:
+    """``clf(trans(fe(x)))``, or its first entry: fp32 ``[batch, n_class]``; ``who`` names the classifier in the message."""
+    f = fe(x)
+    if trans is not None:
+        f = trans(f)
+    out = clf(f)
+    logits = out[0] if isinstance(out, (tuple, list)) else out
+    if logits.dim() != 2 or logits.shape != (batch, n_class) or logits.dtype != torch.float32:
+        raise ValueError(f"{who} classifier returned {tuple(logits.shape)} {logits.dtype}; fp32 [{batch}, {n_class}] expected")
+    return logits
+
+
+def _replay_pass(prepare, batch, rounds: int) -> None:
+    """A captured pass: *prepare* once (round 0 with it), *batch* ``rounds - 1`` times."""
+    prepare.replay()
+    for _ in range(rounds - 1):
+        batch.replay()
+
+
+class _Passes:
+    """What ``Evaluator`` and ``VotingEvaluator`` share: the static inputs of a batch, the modules' eval mode, and the capture of
+    a pass — (begin, round) — as a (prepare, batch) pair of hipGraphs.  An owner supplies ``_modules()``, ``device`` and ``batch``."""
+    _graphs = None                                                            # (prepare, batch) of every captured pass, in a row
+    _caches = None                                                            # the capture-time pack caches, kept alive here
+    _held = None                                                              # what the captured rounds returned: logits and calls, likewise
+
+    def _static_inputs(self, data: DeviceDataset, *blocks: torch.Tensor) -> None:
+        """The static inputs of every batch, eager or captured; ``blocks``: the words of the passes, which the kernels take
+        in 16-byte pieces."""
+        dev, B = data.device, self.batch
         self._x = torch.zeros((B,) + tuple(data.x.shape[1:]), dtype=torch.float32, device=dev)
         self._y = torch.zeros(B, dtype=torch.int64, device=dev)
         self._valid = torch.zeros(1, dtype=torch.int32, device=dev)
-        # the words of a pass as ONE block, zeroed by one fill: state (8 int32), loss (fp64), confusion (C x C int32)
-        self._pass = torch.zeros(10 + C * C, dtype=torch.int32, device=dev)
-        if self._pass.data_ptr() % 16:
-            raise RuntimeError("Evaluator: the allocator returned a block off a 16-byte boundary")
-        self.state, self.loss, self.confusion = self._pass[:8], self._pass[8:10].view(torch.float64), self._pass[10:].view(C, C)
-        self.predictions = torch.zeros(N, dtype=torch.int64, device=dev)
-        self.logits = torch.zeros(N, C, dtype=torch.float32, device=dev) if keep_logits else None
-        self.best = ops.eval_best_block(dev)
-        self._scratch = ops.eval_scratch(B, dev) if dev.type == "cuda" else None
-        self.metric = "accuracy"
-        self._finish_call = ops.EvalFinishCall(self.state, self.loss, N, self.best, 0)
-        self._improved = _Improved(self.best)
-        self._live: Dict[str, torch.Tensor] = {}                              # track_best: name -> live tensor
-        self._shadow: Dict[str, torch.Tensor] = {}                            # ... -> the copy of the best pass
-        self._tracked: Sequence[nn.Module] = ()
-        self._inside = False                                                  # inside best_weights()
-        self._graphs = None                                                   # (prepare, batch) once captured
-        self._cache: Optional[dict] = None                                    # the capture-time pack cache, kept alive here
-
-    # ------------------------------------------------------------------ the pass
-    def _modules(self):
-        return [m for m in (self.fe, self.feature_trans, self.clf) if m is not None]
+        if any(b.data_ptr() % 16 for b in blocks):
+            raise RuntimeError(f"{type(self).__name__}: the allocator returned a block off a 16-byte boundary")
 
     @contextlib.contextmanager
     def _eval_mode(self):
@@ -115,15 +123,78 @@ class Evaluator:
             for m, mode in zip(mods, modes):
                 m.train(mode)
 
-    def _forward(self) -> torch.Tensor:
-        f = self.fe(self._x)
-        if self.feature_trans is not None:
-            f = self.feature_trans(f)
-        out = self.clf(f)
-        logits = out[0] if isinstance(out, (tuple, list)) else out
-        if logits.dim() != 2 or logits.shape != (self.batch, self.n_class) or logits.dtype != torch.float32:
-            raise ValueError(f"Evaluator: the classifier returned {tuple(logits.shape)} {logits.dtype}; fp32 [{self.batch}, {self.n_class}] expected")
-        return logits
+    def _capture_passes(self, passes, warmup: int) -> None:
+        """Capture every (begin, round) of ``passes`` as two hipGraphs, all in one pool.  *prepare*: ``begin`` — rewind the plan,
+        zero the pass's words — and round 0, whose forwards do what the first forward of a pass does once: the BatchNorm folds
+        and the weight packing.  *batch*: every later round, served by the folds and images of *prepare*.  Each pass is captured
+        under a pack cache of its own, whose objects are kept alive here, so a replay of *prepare* recomputes them in place from
+        the live parameter storage; the global ``ops.pack_cache()`` scope is left before this returns."""
+        who = type(self).__name__
+        if self.device.type != "cuda":
+            raise RuntimeError(f"{who}.capture(): a GPU is needed")
+        if ops._PACK_CACHE is not None:
+            raise RuntimeError(f"{who}.capture(): inside an ops.pack_cache() scope; capture outside it")
+        with self._eval_mode():
+            with _capture.warmup_stream(self.device):
+                for begin, one_round in passes:
+                    for _ in range(max(1, warmup)):
+                        with ops.pack_cache():
+                            begin()
+                            one_round()
+                    begin()
+            graphs, caches, held, pool = [], [], [], None
+            for begin, one_round in passes:
+                prepare, batch = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
+                with ops.pack_cache():
+                    caches.append(ops._PACK_CACHE)
+                    with _capture.graph(prepare, pool):
+                        begin()
+                        held.append(one_round())
+                    pool = prepare.pool()
+                    with _capture.graph(batch, pool):
+                        held.append(one_round())
+                graphs += [prepare, batch]
+        self._graphs, self._caches, self._held = tuple(graphs), caches, held
+
+    def release(self) -> None:
+        """Drop the captured graphs and what they kept alive."""
+        self._graphs = self._caches = self._held = None
+
+
+class Evaluator(_Passes):
+    """Evaluate ``classification_module(feature_trans(feature_extraction_module(x)))`` over ``data`` in batches of ``batch_size``.
+
+    ``n_class``: the number of classes (default: ``classification_module.hidden.out_features``).  ``feature_trans``: the source
+    side's DimensionUnification.  ``keep_logits``: also keep every row's logits, ``[N, C]``, on the device.  The classifier may
+    return the logits or a tuple whose first entry they are.  ``accuracy`` and the mean ``loss`` divide by ``len(data)``."""
+
+    def __init__(self, feature_extraction_module: nn.Module, classification_module: nn.Module, data: DeviceDataset, batch_size: int,
+                 n_class: Optional[int] = None, feature_trans: Optional[nn.Module] = None, keep_logits: bool = False):
+        n_class = _n_class("Evaluator", n_class, classification_module, "the")
+        self.fe, self.clf, self.feature_trans = feature_extraction_module, classification_module, feature_trans
+        self.data, self.device, self.n_class, self.keep_logits = data, data.device, n_class, bool(keep_logits)
+        self.plan = EvalPlan(data, batch_size)
+        self.batch, self.rounds, self.n = batch_size, self.plan.rounds, len(data)
+        dev, B, C, N = self.device, batch_size, n_class, self.n
+        # the words of a pass as ONE block, zeroed by one fill: state (8 int32), loss (fp64), confusion (C x C int32)
+        self._pass = torch.zeros(10 + C * C, dtype=torch.int32, device=dev)
+        self._static_inputs(data, self._pass)
+        self.state, self.loss, self.confusion = self._pass[:8], self._pass[8:10].view(torch.float64), self._pass[10:].view(C, C)
+        self.predictions = torch.zeros(N, dtype=torch.int64, device=dev)
+        self.logits = torch.zeros(N, C, dtype=torch.float32, device=dev) if keep_logits else None
+        self.best = ops.eval_best_block(dev)
+        self._scratch = ops.eval_scratch(B, dev) if dev.type == "cuda" else None
+        self.metric = "accuracy"
+        self._finish_call = ops.EvalFinishCall(self.state, self.loss, N, self.best, 0)
+        self._improved = _Improved(self.best)
+        self._live: Dict[str, torch.Tensor] = {}                              # track_best: name -> live tensor
+        self._shadow: Dict[str, torch.Tensor] = {}                            # ... -> the copy of the best pass
+        self._tracked: Sequence[nn.Module] = ()
+        self._inside = False                                                  # inside best_weights()
+
+    # ------------------------------------------------------------------ the pass
+    def _modules(self):
+        return [m for m in (self.fe, self.feature_trans, self.clf) if m is not None]
 
     def _fold_call(self, logits: torch.Tensor) -> ops.EvalFoldCall:
         return ops.EvalFoldCall(logits, self._y, self._valid, self.state, self.loss, self.confusion, self.predictions, self.logits,
@@ -133,9 +204,13 @@ class Evaluator:
         self.plan.rewind()
         self._pass.zero_()
 
-    def _round(self) -> None:
+    def _round(self):
+        """Feed, forward, ``eval_fold``; returns what a graph that captured the round must keep alive: the logits and the call."""
         self.plan.feed(self._x, self._y, self._valid)
-        self._fold_call(self._forward())()
+        logits = _logits(self.fe, self.feature_trans, self.clf, self._x, self.batch, self.n_class, "Evaluator: the")
+        call = self._fold_call(logits)
+        call()
+        return logits, call
 
     def _finish(self) -> None:
         self._finish_call()
@@ -161,47 +236,12 @@ class Evaluator:
         return self.report()
 
     def capture(self, warmup: int = 1) -> None:
-        """Capture the pass as two hipGraphs sharing a pool.  *prepare*: rewind the plan, zero the pass's words and run round 0 —
-        feed, forward, ``eval_fold`` —, whose forward does what the first forward of a pass does once: the BatchNorm folds and the
-        weight packing.  *batch*: feed + forward + ``eval_fold`` of every later round, served by the folds and images of
-        *prepare*.  Those are recomputed in place by every replay of *prepare* from the live parameter storage, so a replay
-        evaluates the weights as they are then.  (A *prepare* that only folded and packed would need a forward whose logits nobody
-        reads: one batch's time per pass.)  The objects of the capture-time pack cache are kept alive here; the global
-        ``ops.pack_cache()`` scope is left before this returns."""
+        """Capture the pass as two hipGraphs sharing a pool (``_capture_passes``): *prepare* — rewind the plan, zero the pass's
+        words and run round 0 — and *batch*, every later round.  Every replay of *prepare* recomputes the BatchNorm folds and the
+        packed weights from the live parameter storage, so a replay evaluates the weights as they are then.  (A *prepare* that
+        only folded and packed would need a forward whose logits nobody reads: one batch's time per pass.)"""
         self._no_pass("capture()")
-        if self.device.type != "cuda":
-            raise RuntimeError("Evaluator.capture(): a GPU is needed")
-        if ops._PACK_CACHE is not None:
-            raise RuntimeError("Evaluator.capture(): inside an ops.pack_cache() scope; capture outside it")
-        with self._eval_mode():
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(max(1, warmup)):
-                    with ops.pack_cache():
-                        self._begin()
-                        self._round()
-                self._begin()
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            cache = ops.pack_cache()
-            prepare, batch = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-            with cache:
-                self._cache = ops._PACK_CACHE
-                with torch.cuda.graph(prepare, capture_error_mode=_CAPTURE_MODE):
-                    self._begin()
-                    self._g_first = self._captured_round()
-                with torch.cuda.graph(batch, pool=prepare.pool(), capture_error_mode=_CAPTURE_MODE):
-                    self._g_next = self._captured_round()
-        self._graphs = (prepare, batch)
-
-    def _captured_round(self):
-        """A round inside a stream capture; returns what must stay alive as long as the graph: the logits and the fold's call."""
-        self.plan.feed(self._x, self._y, self._valid)
-        logits = self._forward()
-        call = self._fold_call(logits)
-        call()
-        return logits, call
+        self._capture_passes([(self._begin, self._round)], warmup)
 
     def replay(self, report: bool = True) -> Optional[Dict[str, torch.Tensor]]:
         """One captured pass: *prepare* once (round 0 with it), *batch* ``rounds - 1`` times, then ``eval_finish`` (and the best-weights save, if
@@ -210,17 +250,9 @@ class Evaluator:
         self._no_pass("replay()")
         if self._graphs is None:
             raise RuntimeError("call capture() first")
-        prepare, batch = self._graphs
-        prepare.replay()
-        for _ in range(self.rounds - 1):
-            batch.replay()
+        _replay_pass(*self._graphs, self.rounds)
         self._finish()
         return self.report() if report else None
-
-    def release(self) -> None:
-        """Drop the captured graphs and what they kept alive."""
-        self._graphs = self._cache = None
-        self._g_first = self._g_next = None
 
     # ------------------------------------------------------------------ what a pass leaves
     def report(self) -> Dict[str, torch.Tensor]:
@@ -230,13 +262,12 @@ class Evaluator:
         ``best_pass``, ``passes``; the counters ``batches``, ``bad_label``, ``nonfinite``, ``overflow``, ``incomplete``."""
         st, best = self.state.clone(), self.best.clone()
         hits, best_hits = st[ops.EVAL_HITS], best[ops.EVAL_BEST_HITS]
-        out = {"seen": st[ops.EVAL_SEEN], "hits": hits, "accuracy": hits.to(torch.float64) / self.n,
+        out = {**_named(st, _STATE_WORDS), "accuracy": hits.to(torch.float64) / self.n,
                "loss": self.loss[0] / self.n, "confusion": self.confusion.clone(), "predictions": self.predictions.clone(),
                "labels": self.data.y, "improved": best[ops.EVAL_IMPROVED],
                "best_accuracy": torch.where(best_hits >= 0, best_hits.to(torch.float64) / self.n, float("nan")),
                "best_loss": ops.eval_best_loss(best)[0] / self.n, "best_pass": best[ops.EVAL_BEST_PASS], "passes": best[ops.EVAL_PASSES],
-               "batches": st[ops.EVAL_BATCHES], "bad_label": st[ops.EVAL_BAD_LABEL], "nonfinite": st[ops.EVAL_NONFINITE],
-               "overflow": st[ops.EVAL_OVERFLOW], "incomplete": best[ops.EVAL_INCOMPLETE]}
+               "incomplete": best[ops.EVAL_INCOMPLETE]}
         if self.logits is not None:
             out["logits"] = self.logits.clone()
         return out
@@ -254,14 +285,12 @@ class Evaluator:
         h = self._read(parts)
         st, best = h["state"].tolist(), h["best"].tolist()
         best_loss = float(ops.eval_best_loss(h["best"])[0])
-        out = {"seen": st[ops.EVAL_SEEN], "hits": st[ops.EVAL_HITS], "accuracy": st[ops.EVAL_HITS] / self.n,
+        out = {**_named(st, _STATE_WORDS), "accuracy": st[ops.EVAL_HITS] / self.n,
                "loss": float(h["loss"][0]) / self.n, "confusion": h["confusion"].clone(), "predictions": h["predictions"].clone(),
                "improved": bool(best[ops.EVAL_IMPROVED]),
                "best_accuracy": best[ops.EVAL_BEST_HITS] / self.n if best[ops.EVAL_BEST_HITS] >= 0 else float("nan"),
                "best_loss": best_loss / self.n, "best_pass": best[ops.EVAL_BEST_PASS], "passes": best[ops.EVAL_PASSES],
-               "batches": st[ops.EVAL_BATCHES], "bad_label": st[ops.EVAL_BAD_LABEL], "nonfinite": st[ops.EVAL_NONFINITE],
-               "overflow": st[ops.EVAL_OVERFLOW], "incomplete": best[ops.EVAL_INCOMPLETE],
-               "feed": {"overrun": int(h["feed"][ops.FEED_OVERRUN]), "bad_index": int(h["feed"][ops.FEED_BAD_INDEX])}}
+               "incomplete": best[ops.EVAL_INCOMPLETE], "feed": _named(h["feed"].tolist(), _FEED_WORDS)}
         if self.logits is not None:
             out["logits"] = h["logits"].clone()
         return out
@@ -272,7 +301,7 @@ class Evaluator:
         h = self._read({"state": self.state, "best": self.best, "feed": self.plan.state})
         st, best, feed = h["state"].tolist(), h["best"].tolist(), h["feed"].tolist()
         found = {"overflow": st[ops.EVAL_OVERFLOW], "bad_label": st[ops.EVAL_BAD_LABEL], "incomplete": best[ops.EVAL_INCOMPLETE],
-                 "overrun": feed[ops.FEED_OVERRUN], "bad_index": feed[ops.FEED_BAD_INDEX]}
+                 **_named(feed, _FEED_WORDS)}
         if any(found.values()):
             raise RuntimeError("Evaluator: " + ", ".join(f"{k} = {v}" for k, v in found.items() if v))
 
@@ -302,43 +331,20 @@ class Evaluator:
         self.best.copy_(ops.eval_best_block(self.device))
         self._finish_call = ops.EvalFinishCall(self.state, self.loss, self.n, self.best, _METRICS[metric])
 
-    def _caches(self) -> list:
-        """Submodules that cache something derived from the weights in an attribute ``W_inverse`` outside any ``ops.pack_cache()``."""
-        return [s for m in self._tracked for s in m.modules()]
-
+    @contextlib.contextmanager
     def best_weights(self):
         """Context manager: inside it the tracked modules hold the weights of the BEST pass — one in-place exchange with the shadow
         on entry, the same exchange on exit, after which every live bit is what it was.  The addresses do not change, so captured
         graphs stay valid.  Cached ``W_inverse`` attributes of the tracked modules are set aside on entry and put back on exit.
         Raises inside an open ``ops.pack_cache()`` scope (a packed image or a BatchNorm fold made before the exchange would be
         stale) and when nested; inside it ``run``, ``replay``, ``capture`` and ``track_best`` raise."""
-        @contextlib.contextmanager
-        def scope():
-            if not self._shadow:
-                raise RuntimeError("best_weights(): call track_best() first")
-            if self._inside:
-                raise RuntimeError("best_weights(): already inside; the context does not nest")
-            if ops._PACK_CACHE is not None:
-                raise RuntimeError("best_weights(): inside an ops.pack_cache() scope, whose packed weights and BatchNorm folds would "
-                                   "be stale after the exchange; enter it outside")
-            names = list(self._shadow)
-            shadow, live = [self._shadow[k] for k in names], [self._live[k] for k in names]
-            swap_tensors(shadow, live)                                        # (refuses before it exchanges anything)
-            caches = self._caches()
-            aside = [c.__dict__.pop("W_inverse", None) for c in caches]
-            self._inside = True
-            try:
-                yield self
-            finally:
-                try:
-                    swap_tensors(shadow, live)
-                finally:
-                    self._inside = False
-                    for c, w in zip(caches, aside):
-                        c.__dict__.pop("W_inverse", None)
-                        if w is not None:
-                            c.W_inverse = w
-        return scope()
+        if not self._shadow:
+            raise RuntimeError("best_weights(): call track_best() first")
+        names = list(self._shadow)
+        # the submodules may cache something derived from the weights in an attribute ``W_inverse`` outside any ``ops.pack_cache()``
+        caches = [s for m in self._tracked for s in m.modules()]
+        with exchanged([self._shadow[k] for k in names], [self._live[k] for k in names], caches, self, "_inside", "best_weights()"):
+            yield self
 
     def state_dict(self) -> dict:
         """The best words and the shadows (CPU copies; waits for the device)."""
@@ -361,7 +367,7 @@ class Evaluator:
                 t.copy_(sd["shadow"][k])
 
 
-class VotingEvaluator:
+class VotingEvaluator(_Passes):
     """The multi-source vote of multi_source_voting.py:265-429 as passes that stay on the device.  ``members``: K (1..16) target-side
     pipelines, each ``(fe, clf)`` or ``(fe, clf, feature_trans)``; ``train_data`` and ``test_data``: resident ``DeviceDataset``s of
     one series shape.  A *weighing* pass over ``train_data`` folds every member's predictions into its own confusion matrix
@@ -382,15 +388,10 @@ class VotingEvaluator:
         if any(len(m) not in (2, 3) for m in members):
             raise ValueError("VotingEvaluator: a member is (fe, clf) or (fe, clf, feature_trans)")
         self.members = [(m[0], m[1], m[2] if len(m) == 3 else None) for m in members]
-        widths = [clf.hidden.out_features if isinstance(getattr(clf, "hidden", None), nn.Linear) else None for _, clf, _ in self.members]
-        if n_class is None:
-            if widths[0] is None:
-                raise ValueError("VotingEvaluator: n_class is needed (member 0's classifier has no Linear `hidden` to read it from)")
-            n_class = widths[0]
-        if isinstance(n_class, bool) or not isinstance(n_class, int) or not 1 <= n_class <= ops.EVAL_MAX_C:
-            raise ValueError(f"VotingEvaluator: n_class must be in 1..{ops.EVAL_MAX_C}, got {n_class!r}")
-        for k, w in enumerate(widths):
-            if w is not None and w != n_class:
+        n_class = _n_class("VotingEvaluator", n_class, self.members[0][1], "member 0's")
+        for k, (_, clf, _) in enumerate(self.members):
+            w = clf.hidden.out_features if isinstance(getattr(clf, "hidden", None), nn.Linear) else n_class
+            if w != n_class:
                 raise ValueError(f"VotingEvaluator: member {k}'s classifier has {w} classes, n_class is {n_class}")
         if train_data.device != test_data.device or train_data.x.shape[1:] != test_data.x.shape[1:]:
             raise ValueError(f"VotingEvaluator: the two data sets must live on one device and hold one series shape, got "
@@ -404,17 +405,12 @@ class VotingEvaluator:
         self.n_train, self.n = len(train_data), len(test_data)
         dev, B, C, K = self.device, batch_size, n_class, len(self.members)
         self.K = K
-        # the static inputs of every batch of either pass, eager or captured
-        self._x = torch.zeros((B,) + tuple(test_data.x.shape[1:]), dtype=torch.float32, device=dev)
-        self._y = torch.zeros(B, dtype=torch.int64, device=dev)
-        self._valid = torch.zeros(1, dtype=torch.int32, device=dev)
         # the words of a vote pass as ONE block, zeroed by one fill: state (8 int32), member_hits (16), confusion (C x C)
         self._pass = torch.zeros(24 + C * C, dtype=torch.int32, device=dev)
         # ... and of a weighing pass: per member state (8), loss (fp64), confusion (C x C), each on a 16-byte boundary
         stride = (10 + C * C + 3) // 4 * 4
         self._weigh_pass = torch.zeros(K * stride, dtype=torch.int32, device=dev)
-        if self._pass.data_ptr() % 16 or self._weigh_pass.data_ptr() % 16:
-            raise RuntimeError("VotingEvaluator: the allocator returned a block off a 16-byte boundary")
+        self._static_inputs(test_data, self._pass, self._weigh_pass)          # of every batch of either pass
         self.state, self.member_hits, self.confusion = self._pass[:8], self._pass[8: 8 + K], self._pass[24:].view(C, C)
         blocks = [self._weigh_pass[k * stride: k * stride + 10 + C * C] for k in range(K)]
         self._member_state = [b[:8] for b in blocks]
@@ -430,9 +426,6 @@ class VotingEvaluator:
         self._weights_call = ops.VoteWeightsCall(self.member_confusion, self.weights, self.scale, self.base)
         self._weighted = False                                                # weights are in place: weigh() or set_weights()
         self._weighed_here = False                                            # ... by a weighing pass of this object
-        self._graphs = None                                                   # (weigh prepare, weigh batch, vote prepare, vote batch)
-        self._caches = None                                                   # the two capture-time pack caches, kept alive here
-        self._held = None
 
     # ------------------------------------------------------------------ the passes
     def _modules(self):
@@ -444,30 +437,9 @@ class VotingEvaluator:
                     out.append(m)
         return out
 
-    @contextlib.contextmanager
-    def _eval_mode(self):
-        mods = self._modules()
-        modes = [m.training for m in mods]
-        for m in mods:
-            m.eval()
-        try:
-            with torch.no_grad():
-                yield
-        finally:
-            for m, mode in zip(mods, modes):
-                m.train(mode)
-
     def _forward(self, k: int) -> torch.Tensor:
         fe, clf, trans = self.members[k]
-        f = fe(self._x)
-        if trans is not None:
-            f = trans(f)
-        out = clf(f)
-        logits = out[0] if isinstance(out, (tuple, list)) else out
-        if logits.dim() != 2 or logits.shape != (self.batch, self.n_class) or logits.dtype != torch.float32:
-            raise ValueError(f"VotingEvaluator: member {k}'s classifier returned {tuple(logits.shape)} {logits.dtype}; fp32 "
-                             f"[{self.batch}, {self.n_class}] expected")
-        return logits
+        return _logits(fe, trans, clf, self._x, self.batch, self.n_class, f"VotingEvaluator: member {k}'s")
 
     def _weigh_begin(self) -> None:
         self.train_plan.rewind()
@@ -540,58 +512,20 @@ class VotingEvaluator:
         pass's words, round 0, whose forwards fold the BatchNorms and pack the weights) and a *batch* graph for every later round.
         Each pass is captured under a pack cache of its own, so either prepare graph recomputes the folds and images it is served
         by from the live parameter storage: replaying the vote pass alone evaluates the weights as they are then."""
-        if self.device.type != "cuda":
-            raise RuntimeError("VotingEvaluator.capture(): a GPU is needed")
-        if ops._PACK_CACHE is not None:
-            raise RuntimeError("VotingEvaluator.capture(): inside an ops.pack_cache() scope; capture outside it")
-        passes = ((self._weigh_begin, self._weigh_round), (self._vote_begin, self._vote_round))
-        with self._eval_mode():
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for begin, one_round in passes:
-                    for _ in range(max(1, warmup)):
-                        with ops.pack_cache():
-                            begin()
-                            one_round()
-                    begin()
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            graphs, caches, held, pool = [], [], [], None
-            for begin, one_round in passes:
-                prepare, batch = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-                with ops.pack_cache():
-                    caches.append(ops._PACK_CACHE)
-                    with torch.cuda.graph(prepare, pool=pool, capture_error_mode=_CAPTURE_MODE):
-                        begin()
-                        held.append(one_round())
-                    pool = prepare.pool()
-                    with torch.cuda.graph(batch, pool=pool, capture_error_mode=_CAPTURE_MODE):
-                        held.append(one_round())
-                graphs += [prepare, batch]
-        self._graphs, self._caches, self._held = tuple(graphs), caches, held
+        self._capture_passes([(self._weigh_begin, self._weigh_round), (self._vote_begin, self._vote_round)], warmup)
 
     def replay(self, weigh: bool = False, report: bool = True) -> Optional[Dict[str, torch.Tensor]]:
         """The captured vote pass (after the captured weighing pass and ``vote_weights`` with ``weigh=True``): launches only — no
         host tensor, no host-to-device copy, no wait.  Returns ``report()``, or nothing with ``report=False``."""
         if self._graphs is None:
             raise RuntimeError("call capture() first")
-        weigh_prepare, weigh_batch, vote_prepare, vote_batch = self._graphs
         if weigh:
-            weigh_prepare.replay()
-            for _ in range(self.train_plan.rounds - 1):
-                weigh_batch.replay()
+            _replay_pass(*self._graphs[:2], self.train_plan.rounds)
             self._weights_call()
             self._weighted = self._weighed_here = True
         self._need_weights("replay()")
-        vote_prepare.replay()
-        for _ in range(self.test_plan.rounds - 1):
-            vote_batch.replay()
+        _replay_pass(*self._graphs[2:], self.test_plan.rounds)
         return self.report() if report else None
-
-    def release(self) -> None:
-        """Drop the captured graphs and what they kept alive."""
-        self._graphs = self._caches = self._held = None
 
     # ------------------------------------------------------------------ what a pass leaves
     def report(self) -> Dict[str, torch.Tensor]:
@@ -601,11 +535,9 @@ class VotingEvaluator:
         counters ``batches``, ``bad_label``, ``nonfinite``, ``overflow``."""
         st, member_hits = self.state.clone(), self.member_hits.clone()
         hits = st[ops.EVAL_HITS]
-        out = {"seen": st[ops.EVAL_SEEN], "hits": hits, "accuracy": hits.to(torch.float64) / self.n, "confusion": self.confusion.clone(),
+        out = {**_named(st, _STATE_WORDS), "accuracy": hits.to(torch.float64) / self.n, "confusion": self.confusion.clone(),
                "predictions": self.predictions.clone(), "labels": self.test_data.y, "member_hits": member_hits,
-               "member_accuracy": member_hits.to(torch.float64) / self.n, "weights": self.weights.clone(), "scale": self.scale.clone(),
-               "batches": st[ops.EVAL_BATCHES], "bad_label": st[ops.EVAL_BAD_LABEL], "nonfinite": st[ops.EVAL_NONFINITE],
-               "overflow": st[ops.EVAL_OVERFLOW]}
+               "member_accuracy": member_hits.to(torch.float64) / self.n, "weights": self.weights.clone(), "scale": self.scale.clone()}
         if self.scores is not None:
             out["scores"] = self.scores.clone()
         return out
@@ -621,12 +553,10 @@ class VotingEvaluator:
         h = _read_once(parts)
         C, K = self.n_class, self.K
         st, member_hits = h["pass"][:8].tolist(), h["pass"][8: 8 + K].clone()
-        out = {"seen": st[ops.EVAL_SEEN], "hits": st[ops.EVAL_HITS], "accuracy": st[ops.EVAL_HITS] / self.n,
+        out = {**_named(st, _STATE_WORDS), "accuracy": st[ops.EVAL_HITS] / self.n,
                "confusion": h["pass"][24:].view(C, C).clone(), "predictions": h["predictions"].clone(), "member_hits": member_hits,
                "member_accuracy": member_hits.to(torch.float64) / self.n, "weights": h["weights"].clone(), "scale": h["scale"].clone(),
-               "batches": st[ops.EVAL_BATCHES], "bad_label": st[ops.EVAL_BAD_LABEL], "nonfinite": st[ops.EVAL_NONFINITE],
-               "overflow": st[ops.EVAL_OVERFLOW],
-               "feed": {"overrun": int(h["feed"][ops.FEED_OVERRUN]), "bad_index": int(h["feed"][ops.FEED_BAD_INDEX])}}
+               "feed": _named(h["feed"].tolist(), _FEED_WORDS)}
         if self.scores is not None:
             out["scores"] = h["scores"].clone()
         return out

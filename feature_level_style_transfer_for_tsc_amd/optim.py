@@ -37,6 +37,7 @@ read when they run, so one captured launch series serves every position.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 from typing import Iterable, List, Optional, Sequence
 
@@ -63,6 +64,13 @@ class _DeviceLR:
         self.lr_on_device = True
 
 
+def push_words(dst: torch.Tensor, host: torch.Tensor) -> None:
+    """Copy the host tensor into the device words ``dst`` on the current stream, without waiting for the device."""
+    if dst.is_cuda:
+        host = host.pin_memory()                     # a pageable source would make the copy wait for the device
+    dst.copy_(host, non_blocking=True)
+
+
 def push_lr(optimisers) -> int:
     """Write every ``group["lr"]`` whose fp32 value differs from the one last pushed into its optimiser's ``lr_dev``, on the
     current stream and without waiting for the device (the device reads the new values in stream order: a graph replayed
@@ -74,10 +82,7 @@ def push_lr(optimisers) -> int:
         new = [_f32(g["lr"]) for g in o.param_groups]
         n = sum(a != b for a, b in zip(new, o._lr_pushed))
         if n:
-            host = torch.tensor(new, dtype=torch.float32)
-            if o.lr_dev.is_cuda:
-                host = host.pin_memory()             # a pageable source would make the copy wait for the device
-            o.lr_dev.copy_(host, non_blocking=True)
+            push_words(o.lr_dev, torch.tensor(new, dtype=torch.float32))
             o._lr_pushed = new
             changed += n
     return changed
@@ -85,6 +90,16 @@ def push_lr(optimisers) -> int:
 
 def _capturing(t: torch.Tensor) -> bool:
     return t.is_cuda and torch.cuda.is_current_stream_capturing()
+
+
+def _scan_slots(owner, n_words: int, like: torch.Tensor) -> torch.Tensor:
+    """``owner._slots``, the scratch of a scan, grown to ``n_words`` words of the dtype and device of ``like`` — outside captures only."""
+    if owner._slots is None or owner._slots.numel() < n_words:
+        if _capturing(like):
+            raise RuntimeError(f"{type(owner).__name__}: the scan's slot array would have to grow inside a stream capture; run one "
+                               "eager step of the same tensors first")
+        owner._slots = torch.empty(max(n_words, 1), dtype=like.dtype, device=like.device)
+    return owner._slots
 
 
 class SharedStepAdam(_DeviceLR, torch.optim.Optimizer):
@@ -289,12 +304,7 @@ class AnomalyGuard:
         self._slots = None                                                    # scratch of the scan, grown outside captures
 
     def slots(self, n_words: int) -> torch.Tensor:
-        if self._slots is None or self._slots.numel() < n_words:
-            if _capturing(self.verdict):
-                raise RuntimeError("AnomalyGuard: the scan's slot array would have to grow inside a stream capture; run one eager "
-                                   "step of the same tensors first")
-            self._slots = torch.empty(max(n_words, 1), dtype=torch.int32, device=self.device)
-        return self._slots
+        return _scan_slots(self, n_words, self.verdict)
 
 
 @torch.no_grad()
@@ -418,12 +428,7 @@ class GradClip:
         self._slots = None                                                    # scratch of the scan, grown outside captures
 
     def slots(self, n_words: int) -> torch.Tensor:
-        if self._slots is None or self._slots.numel() < n_words:
-            if _capturing(self.limits):
-                raise RuntimeError("GradClip: the scan's slot array would have to grow inside a stream capture; run one eager step "
-                                   "of the same tensors first")
-            self._slots = torch.empty(max(n_words, 1), dtype=torch.float32, device=self.device)
-        return self._slots
+        return _scan_slots(self, n_words, self.limits)
 
     def set_limits(self, limits: Sequence[float]) -> bool:
         """``limits``: 33 caps (``inf`` = none; negative or NaN values are refused).  Copies them to the device if they differ from
@@ -435,10 +440,7 @@ class GradClip:
             raise ValueError("GradClip.set_limits: a limit must be a non-negative number or inf")
         if new == self.limits_host:
             return False
-        host = torch.tensor(new, dtype=torch.float32)
-        if self.limits.is_cuda:
-            host = host.pin_memory()                                          # a pageable source would make the copy wait for the device
-        self.limits.copy_(host, non_blocking=True)
+        push_words(self.limits, torch.tensor(new, dtype=torch.float32))
         self.limits_host = new
         return True
 
@@ -541,10 +543,7 @@ class WeightAverage:
         if new == (self.decay_host, self.warmup_host):
             return False
         self.decay_host, self.warmup_host = new
-        host = self._head()
-        if self.words.is_cuda:
-            host = host.pin_memory()                                          # a pageable source would make the copy wait for the device
-        self.words[:2].copy_(host, non_blocking=True)
+        push_words(self.words[:2], self._head())
         return True
 
 
@@ -639,6 +638,34 @@ def swap_tensors(a: Sequence[torch.Tensor], b: Sequence[torch.Tensor]) -> None:
                                           _i64_array([x.numel() for x, _ in keep]), len(keep), _lib.stream_ptr()), "fst_swap_multi")
 
 
+@contextlib.contextmanager
+def exchanged(a: Sequence[torch.Tensor], b: Sequence[torch.Tensor], caches, owner, flag: str, who: str):
+    """The scope of ``averaged_weights()`` and ``best_weights()``: ``swap_tensors(a, b)`` on entry and again on exit, the
+    ``W_inverse`` attributes that the objects ``caches`` hold (derived from the weights outside any ``ops.pack_cache()``) set aside
+    meanwhile — what is cached inside belongs to the exchanged weights and is dropped — and ``owner.<flag>`` true inside.
+    Refuses when nested and inside an open ``ops.pack_cache()`` scope; ``who`` names the caller in the messages."""
+    from . import ops
+    if getattr(owner, flag):
+        raise RuntimeError(f"{who}: already inside; the context does not nest")
+    if ops._PACK_CACHE is not None:
+        raise RuntimeError(f"{who}: inside an ops.pack_cache() scope, whose packed weights and BatchNorm folds would be stale "
+                           "after the exchange; enter it outside")
+    swap_tensors(a, b)                                                        # (refuses before it exchanges anything)
+    aside = [c.__dict__.pop("W_inverse", None) for c in caches]
+    setattr(owner, flag, True)
+    try:
+        yield owner
+    finally:
+        try:
+            swap_tensors(a, b)
+        finally:
+            setattr(owner, flag, False)
+            for c, w in zip(caches, aside):
+                c.__dict__.pop("W_inverse", None)
+                if w is not None:
+                    c.W_inverse = w
+
+
 # ---- gradient accumulation: one optimiser step over a window of k calls, the position in the window a device word
 class GradAccumulation:
     """The device words of the gradient accumulation, one 16-byte aligned block of eight 4-byte words (``fst_accum_multi``'s
@@ -681,10 +708,7 @@ class GradAccumulation:
         if steps == self.steps_host:
             return False
         self.steps_host = steps
-        host = self._head()
-        if self.words.is_cuda:
-            host = host.pin_memory()                                          # a pageable source would make the copy wait for the device
-        self.words[:3].copy_(host, non_blocking=True)
+        push_words(self.words[:3], self._head())
         return True
 
     @property

@@ -12,8 +12,8 @@ Differences from the reference are mechanical, not numerical:
     every other conv skips its weight-gradient kernels (``ops.partial_backward``).
 Data parallelism: ``dist.GradBucket`` all-reduces one flat fp32 gradient bucket over RCCL.
 
-Schedules (train_and_test.py:118-134, :665-672): ``make_schedulers`` builds the reference's eleven learning-rate schedulers
-on a trainer's optimisers and ``end_epoch`` steps the ones the reference steps.  A captured step follows them only after
+Schedules (schedules.py): ``JointTrainer.make_schedulers`` builds the reference's eleven learning-rate schedulers on the trainer's
+optimisers and ``end_epoch`` steps the ones the reference steps.  A captured step follows them only after
 ``enable_device_hparams()``, which moves the learning rates and the four epoch coefficients into device tensors.
 
 Anomaly guard (``JointTrainer.enable_anomaly_guard()``): instead of the reference's ``torch.autograd.set_detect_anomaly(True)``
@@ -24,13 +24,10 @@ Gradient norms and clipping (``JointTrainer.enable_grad_clip()``): per-module L2
 to read in every report, and caps per module and on the whole that scale those gradients in place — what
 ``torch.nn.utils.clip_grad_norm_`` does with a host decision — computed and applied on the device, under graph replay too.
 
-Gradient accumulation (``enable_grad_accumulation(steps)``, both trainers): one optimiser step over ``steps`` consecutive calls,
-each on its own micro-batch; the gradients, GradNorm's ten scalars and the loss scalars are folded into fp32 accumulators at a
-window position kept on the device, and everything behind the backward runs on the call that closes the window, on their means.
+Weight averaging, gradient accumulation and device-resident input, which both trainers offer, are the mixins of modes.py.
 """
 from __future__ import annotations
 
-import warnings
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
@@ -38,14 +35,17 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import _capture, ops
 from .cdan import CDAN, RandomLayer
 from .cpc import CPC
 from . import dist as _dist
 from .dist import GradBucket
-from .optim import (MAX_GROUPS, _capturing, AnomalyGuard, FusedRMSprop, GradAccumulation, GradClip, SharedStepAdam, WeightAverage, accumulate,
-                    count_nonfinite, ema_update, guard_copy, push_lr, rmsprop_step_many, scale_by_group, sumsq_norms, swap_tensors)
+from .modes import _enable_from_arg, _Fed, _GradAccumulating, _WeightAveraging, _WindowOpens
+from .optim import (MAX_GROUPS, _capturing, AnomalyGuard, FusedRMSprop, GradClip, SharedStepAdam, accumulate, count_nonfinite, guard_copy,
+                    push_lr, push_words, rmsprop_step_many, scale_by_group, sumsq_norms)
 from .os_cnn import OS_CNN, OS_CNN_res, build_layer_with_layer_parameter
+from .schedules import (EPOCH_SCHEDULERS, PLATEAU, PLATEAU_METRIC, STEP_LR, loss_coefficients, make_schedulers,  # noqa: F401 (re-exported)
+                        step_schedulers)
 from .structure import generate_layer_parameter_list, layer_parameter_list_input_change, out_channels
 from .waveglow import WaveGlow, WaveGlowLoss
 from .widgets import (AdversarialNetworkforCDAN, DimensionUnification, FeatureDiscriminatorforSource, NoiseTransfer,
@@ -61,337 +61,6 @@ def specs_for(length: int, in_channel: int):
     rf = min(int(length / 4), MAX_KERNEL_SIZE)
     fe = generate_layer_parameter_list(1, rf, budgets, in_channel)
     return fe, layer_parameter_list_input_change(fe, out_channels(fe[-1]))
-
-
-def loss_coefficients(epoch: int) -> Tuple[float, float, float, float]:
-    """(cdan, fd_s, sl_t, sl_s) coefficients by epoch (train_and_test.py:665-672)."""
-    if epoch < 12:
-        return 3, 3, 2, 2
-    if epoch < 24:
-        return 2, 3, 1.8, 1.5
-    if epoch < 50:
-        return 1.5, 2, 1.8, 1.8
-    return 1.5, 1.5, 2.5, 2.5
-
-
-# ---- the reference's learning-rate schedules (train_and_test.py:118-134), on a device-free footing so the table can be tested
-STEP_LR = {"fe_t": (25, 0.8), "clf_t": (25, 0.8), "fe_s": (25, 0.8), "dimunif": (25, 0.8), "clf_s": (25, 0.8),
-           "cpc": (25, 0.7), "noise": (55, 0.6)}                               # name -> (step_size, gamma)
-PLATEAU = ("probtransfer", "nf", "ad_net", "fd_s")                             # ReduceLROnPlateau('min', factor=0.7, min_lr=1e-4)
-EPOCH_SCHEDULERS = {                                                           # kind of epoch -> schedulers stepped after it
-    "target_pretrain": ("fe_t", "clf_t", "cpc"),                               # :172-174
-    "source_pretrain": ("fe_s", "dimunif", "clf_s"),                           # :211-213
-    "ssl_with_ce": ("fe_t", "clf_t", "cpc", "fe_s", "dimunif", "clf_s"),       # :275-280
-    "ssl": ("fe_t", "cpc", "fe_s", "dimunif"),                                 # :343-348
-    "nf_with_ce": ("fe_t", "clf_t", "fe_s", "dimunif", "clf_s", "cpc", "nf"),  # :436-442
-    "nf": ("fe_t", "fe_s", "dimunif", "nf"),                                   # :491-494
-    "joint": ("fe_t", "clf_t", "cpc", "fe_s", "dimunif", "clf_s", "probtransfer", "nf", "noise", "ad_net", "fd_s"),  # :767-777
-}
-# The metric a plateau scheduler is given: a key of the epoch's LAST batch report, or None for the constant 0.0 (quirk Q8: the
-# reference zeroes cdan_loss.data and feature_discriminator_s_loss.data in place at :739-740 before :776-777 read them)
-PLATEAU_METRIC = {
-    "nf_with_ce": {"nf": "total"},                                             # :420, :442
-    "nf": {"nf": "total"},                                                     # :481, :494
-    "joint": {"probtransfer": "ce_s2t2s", "nf": "nf_t", "ad_net": None, "fd_s": None},   # :773-777
-}
-
-
-def make_schedulers(opts: Dict[str, torch.optim.Optimizer]) -> Dict[str, object]:
-    """The reference's scheduler for every optimiser of ``opts`` it schedules ({module name: optimiser}, "cpc" for CPC's Adam):
-    stock ``torch.optim.lr_scheduler`` objects, {name: scheduler}."""
-    sch = torch.optim.lr_scheduler
-    out = {}
-    for k, o in opts.items():
-        if k in STEP_LR:
-            out[k] = sch.StepLR(o, step_size=STEP_LR[k][0], gamma=STEP_LR[k][1])
-        elif k in PLATEAU:
-            out[k] = sch.ReduceLROnPlateau(o, "min", factor=0.7, min_lr=0.0001)
-    return out
-
-
-def step_schedulers(schedulers: Dict[str, object], kind: str, report: Dict[str, torch.Tensor], bucket=None) -> None:
-    """Step the schedulers the reference steps after an epoch of ``kind`` (a phase name or "joint"); ``report`` is the epoch's
-    last batch report.  With a ``GradBucket`` the plateau metrics are averaged over the ranks first, so that every rank's
-    schedulers take the same decisions."""
-    if kind not in EPOCH_SCHEDULERS:
-        raise ValueError(f"unknown kind of epoch {kind!r}; one of {sorted(EPOCH_SCHEDULERS)}")
-    metric_of = PLATEAU_METRIC.get(kind, {})
-    keys = [k for k in EPOCH_SCHEDULERS[kind] if metric_of.get(k) is not None]
-    values = {}
-    if keys:
-        vals = torch.stack([report[metric_of[k]].detach().float().reshape(()) for k in keys])
-        if bucket is not None:
-            vals = bucket.mean_scalars(vals)
-        values = dict(zip(keys, vals.tolist()))
-    with warnings.catch_warnings():
-        # torch warns when a scheduler steps before its optimiser's step() was ever called: the trainers step the optimisers
-        # through rmsprop_step_many and graph replays, never through step()
-        warnings.filterwarnings("ignore", message="Detected call of `lr_scheduler.step\\(\\)` before", category=UserWarning)
-        for k in EPOCH_SCHEDULERS[kind]:
-            if k in PLATEAU:
-                schedulers[k].step(values.get(k, 0.0))
-            else:
-                schedulers[k].step()
-
-
-# hipGraph capture must not be invalidated by other threads' HIP calls: with an RCCL communicator alive, PyTorch's
-# watchdog thread polls events while the step is being captured ("global" mode would then abort the capture).
-_CAPTURE_MODE = "thread_local"
-
-
-class _WeightAveraging:
-    """Weight averaging of the two trainers.  A trainer supplies ``_ema_modules()`` ({group name: module}, in group order),
-    ``_ema_resident()`` (is a capture resident?) and ``device``; it calls ``_ema_update`` as the last thing of a step and
-    ``_ema_no_step`` as the first."""
-    weight_average: Optional[WeightAverage] = None                            # the device words; None while the mode is off
-    _ema_avg: Dict[str, Dict[str, torch.Tensor]] = {}                         # module -> state_dict name -> the average
-    _ema_live: Dict[str, Dict[str, torch.Tensor]] = {}                        # ... -> the live tensor (addresses never change)
-    _ema_inside = False                                                       # inside averaged_weights()
-
-    def _ema_resident(self) -> bool:
-        raise NotImplementedError
-
-    def _ema_modules(self) -> Dict[str, nn.Module]:
-        raise NotImplementedError
-
-    def enable_weight_average(self, decay: float = 0.999, warmup: bool = True) -> None:
-        """From now on every step ends by moving an exponential moving average of the weights towards the weights it has just
-        written: for every module a copy of each parameter and of each fp32 buffer of its ``state_dict()`` (BatchNorm running
-        statistics are averaged like parameters, as timm's ``ModelEma`` does; integer buffers are not averaged),
-        ``avg ← avg + w·(live − avg)`` with ``w = 1 − decay``, or while ``warmup`` lasts ``1 − min(decay, (1 + n) / (10 + n))``
-        after ``n`` updates of that module.  Decided and applied on the device with no host read, alike in eager and in captured
-        steps; only the modules a step's optimisers stepped are averaged, and a step the anomaly guard skips leaves averages
-        and counts as they were.  The averages only read the weights: the training trajectory is that of the mode off, bit for
-        bit.  ``averaged_weights()`` puts them to use; ``set_weight_average`` steers the decay, under resident captures too.
-        Idempotent (a second call changes nothing, its arguments included); raises while a capture is resident, whose launches lack the update."""
-        if self.weight_average is not None:
-            return
-        state = WeightAverage(self.device, decay, warmup)                     # (refuses a bad decay before anything changes)
-        if self._ema_resident():
-            raise RuntimeError("enable_weight_average(): a capture is resident; enable the mode before capturing")
-        # the live tensors are listed once: every loader of this package writes them in place, and the exchange of
-        # averaged_weights() depends on their addresses staying what they are anyway
-        self._ema_live = {k: {n: t for n, t in mod.state_dict().items() if t.dtype == torch.float32}
-                          for k, mod in self._ema_modules().items()}
-        self._ema_avg = {k: {n: t.detach().clone(memory_format=torch.contiguous_format) for n, t in d.items()}
-                         for k, d in self._ema_live.items()}
-        self.weight_average = state
-
-    def set_weight_average(self, decay: Optional[float] = None, warmup: Optional[bool] = None) -> bool:
-        """Change the decay and / or the warm-up flag (an argument left out keeps its value).  Legal while captures are
-        resident: one stream-ordered copy into the device words, which a graph replayed afterwards reads — no re-capture.
-        Returns whether the device words changed."""
-        if self.weight_average is None:
-            raise RuntimeError("set_weight_average(): call enable_weight_average() first")
-        return self.weight_average.set_decay(decay, warmup)
-
-    def _ema_pairs(self, names):
-        """(averages, live tensors, group ids) of the modules ``names``, in a fixed order."""
-        order = list(self._ema_avg)
-        avg, live, groups = [], [], []
-        for k in names:
-            for n, a in self._ema_avg[k].items():
-                avg.append(a); live.append(self._ema_live[k][n]); groups.append(order.index(k))
-        return avg, live, groups
-
-    def _ema_update(self, names, guard: Optional[AnomalyGuard] = None) -> None:
-        if self.weight_average is None:
-            return
-        avg, live, groups = self._ema_pairs(names)
-        ema_update(avg, live, groups, self.weight_average, sorted(set(groups)), guard)
-
-    def _ema_no_step(self, what: str) -> None:
-        if self._ema_inside:
-            raise RuntimeError(f"{what}: inside averaged_weights() the modules hold the averages and the averages' tensors the live "
-                               "weights; leave the context first")
-
-    def _ema_report(self) -> Dict[str, torch.Tensor]:
-        n = len(self._ema_avg)
-        return {"ema_weight": self.weight_average.w[:n].clone(), "ema_steps": self.weight_average.count[:n].clone()}
-
-    def _ema_caches(self) -> list:
-        """Objects whose attribute ``W_inverse`` caches something derived from the weights outside any ``ops.pack_cache()``."""
-        return []
-
-    def averaged_weights(self):
-        """Context manager: inside it the modules hold the AVERAGED weights and fp32 buffers — one in-place exchange with the
-        averages on entry, the same exchange on exit, after which every live bit is what it was.  The addresses do not change,
-        so captured graphs stay valid, and ``eval_accuracy``, ``collect_logits`` and the ``save_*_classification_modules``
-        functions work on the averaged model unchanged: a checkpoint saved inside is a reference-format ``.tar`` of it.  The
-        modules' train / eval mode is the caller's business, as in ``eval_accuracy``.  The flow's cached 1x1 inverses (quirk Q2)
-        are set aside on entry and put back on exit; what is cached inside belongs to the averaged weights and is dropped.
-        Raises inside an open ``ops.pack_cache()`` scope (the exchange moves no version counter: a packed image or a BatchNorm
-        fold made before it would be stale) and when nested; inside it the trainer's step, replay and capture methods and its
-        state methods (``snapshot`` / ``restore`` / ``state_dict`` / ``load_state_dict``) raise: they would train on, or save
-        and load, the two sets exchanged."""
-        import contextlib
-
-        @contextlib.contextmanager
-        def scope():
-            if self.weight_average is None:
-                raise RuntimeError("averaged_weights(): call enable_weight_average() first")
-            if self._ema_inside:
-                raise RuntimeError("averaged_weights(): already inside; the context does not nest")
-            if ops._PACK_CACHE is not None:
-                raise RuntimeError("averaged_weights(): inside an ops.pack_cache() scope, whose packed weights and BatchNorm folds "
-                                   "would be stale after the exchange; enter it outside")
-            avg, live, _ = self._ema_pairs(list(self._ema_avg))
-            swap_tensors(avg, live)                                           # (refuses before it exchanges anything)
-            caches = self._ema_caches()
-            aside = [c.__dict__.pop("W_inverse", None) for c in caches]
-            self._ema_inside = True
-            try:
-                yield self
-            finally:
-                try:
-                    swap_tensors(avg, live)
-                finally:
-                    self._ema_inside = False
-                    for c, w in zip(caches, aside):
-                        c.__dict__.pop("W_inverse", None)
-                        if w is not None:
-                            c.W_inverse = w
-        return scope()
-
-    def _ema_state_dict(self) -> dict:
-        st = self.weight_average
-        return {"decay": st.decay_host, "warmup": st.warmup_host, "counts": st.count.cpu().tolist(),
-                "tensors": {k: {n: t.detach().cpu().clone() for n, t in d.items()} for k, d in self._ema_avg.items()}}
-
-    def _ema_load_state_dict(self, sd: dict) -> None:
-        """In place: a resident capture keeps valid addresses."""
-        if self.weight_average is None:
-            self.enable_weight_average(sd["decay"], sd["warmup"])
-        self.weight_average.set_decay(sd["decay"], sd["warmup"])
-        with torch.no_grad():
-            self.weight_average.count.copy_(torch.tensor(sd["counts"], dtype=torch.int32))
-            for k, d in self._ema_avg.items():
-                if set(d) != set(sd["tensors"][k]):
-                    raise KeyError(f"weight average of {k!r}: the checkpoint's tensors are not this module's")
-                for n, t in d.items():
-                    t.copy_(sd["tensors"][k][n])
-
-
-class _GradAccumulating:
-    """Gradient accumulation of the two trainers: one optimiser step over a WINDOW of ``steps`` consecutive calls, each on its own
-    micro-batch.  A trainer supplies ``_ema_resident()`` (is a capture resident?) and ``device``; it calls ``_accum_fold`` behind a
-    micro-step's backward and runs its update only on the call that closes a window."""
-    grad_accumulation: Optional[GradAccumulation] = None                      # the device words; None while the mode is off
-    _accum: Dict[nn.Parameter, torch.Tensor] = {}                             # parameter -> its fp32 accumulator (addresses never change)
-
-    def enable_grad_accumulation(self, steps: int = 1) -> None:
-        """From now on ``steps`` consecutive calls of ``step`` / ``replay`` / ``phase_step`` form a window.  Every call runs its own
-        forward and backward unchanged — batch-coupled quantities (BatchNorm moments, CPC negatives, NoiseTransfer means, CDAN
-        sums) are per micro-batch, and what is stateful (BatchNorm running statistics, ``NoiseTransfer.advance``, the GRL counters)
-        advances per call — and then folds each gradient into a persistent fp32 accumulator: ``acc = g`` on a window's first
-        call, ``acc += g`` after; the call that closes the window writes ``g = acc · float32(1 / steps)`` back into the gradient
-        tensors and alone runs what follows the backward: the data-parallel all-reduce, ``on_grads_ready``, clip, guard,
-        GradNorm's weight update, the optimisers, the WGAN clamps, the roll-back and the weight average.  A call that does not
-        close a window changes no parameter, no optimiser moment, no GradNorm weight and no average.  The position in the window
-        is a device word (``optim.GradAccumulation``), so one captured micro-step serves every position; ``accum_pending`` is
-        its host mirror.  ``steps == 1`` computes the bits of the mode off.  ``set_grad_accumulation`` steers ``steps`` between
-        windows, under resident captures too.  Idempotent (a second call changes nothing, its argument included); raises while
-        a capture is resident, whose launches are the one-graph layout."""
-        if self.grad_accumulation is not None:
-            return
-        state = GradAccumulation(self.device, steps)                          # (refuses a bad count before anything changes)
-        if self._ema_resident():
-            raise RuntimeError("enable_grad_accumulation(): a capture is resident; enable the mode before capturing")
-        self._accum = {}
-        self.grad_accumulation = state
-
-    def set_grad_accumulation(self, steps: int) -> bool:
-        """Calls per window from now on; between windows only.  Legal while captures are resident: one stream-ordered copy into
-        the device words, which a graph replayed afterwards reads — no re-capture.  Returns whether the device words changed."""
-        if self.grad_accumulation is None:
-            raise RuntimeError("set_grad_accumulation(): call enable_grad_accumulation() first")
-        return self.grad_accumulation.set_steps(steps)
-
-    @property
-    def accum_pending(self) -> int:
-        """Calls done in the open window (0 between windows, and with the mode off)."""
-        return 0 if self.grad_accumulation is None else self.grad_accumulation.pending
-
-    def _accum_closed(self, what: str) -> None:
-        if self.accum_pending:
-            raise RuntimeError(f"{what}: a gradient-accumulation window is open ({self.accum_pending} of "
-                               f"{self.grad_accumulation.steps_host} calls done); close it first")
-
-    def _accum_fold(self, params, advance: bool) -> None:
-        """Fold the gradients of ``params`` at the window's current position; the accumulators are made at a parameter's first fold."""
-        acc, grads = [], []
-        for p in params:
-            if p.grad is None:
-                continue
-            if not p.grad.is_contiguous():
-                p.grad = p.grad.contiguous()
-            a = self._accum.get(p)
-            if a is None:
-                if _capturing(p.grad):
-                    raise RuntimeError("gradient accumulation: a gradient has no accumulator yet; run one eager window before capturing")
-                a = self._accum[p] = torch.empty_like(p.grad, memory_format=torch.contiguous_format)
-            acc.append(a); grads.append(p.grad)
-        accumulate(acc, grads, self.grad_accumulation, advance)
-
-
-class _Fed:
-    """Device-resident input of the two trainers: an attached ``data.EpochFeeder`` plans an epoch once and the ``*_fed`` methods
-    draw every batch from device memory — into the captures' own static inputs, or into buffers kept here for the eager steps.
-    A fed method creates no tensor on the host, issues no host-to-device copy and waits for nothing: the feed is one launch pair
-    in front of what the unfed method issues, and is never captured."""
-    feeder = None
-    _fed_kind: Optional[str] = None                                           # what begin_epoch planned ("joint", a phase, "classifier")
-    _fed_buf: Optional[dict] = None                                           # the eager steps' batch, CPC indices and ratios
-
-    def attach_feeder(self, feeder) -> None:
-        """Use ``feeder`` from now on (None: detach).  An epoch has to be begun (``begin_epoch``) before the first fed call."""
-        if feeder is not None and torch.device(feeder.device).type != torch.device(self.device).type:
-            raise ValueError(f"attach_feeder(): the feeder lives on {feeder.device}, the trainer on {self.device}")
-        self.feeder, self._fed_kind, self._fed_buf = feeder, None, None
-
-    def _fed_begin(self, kind: str, ratios=None) -> int:
-        if self.feeder is None:
-            raise RuntimeError("begin_epoch(): call attach_feeder() first")
-        rounds = self.feeder.begin_epoch(ratios)
-        self._fed_kind = kind
-        return rounds
-
-    def _fed_check(self, kind: str, what: str) -> None:
-        if self.feeder is None:
-            raise RuntimeError(f"{what}: call attach_feeder() and begin_epoch() first")
-        if self._fed_kind is None:
-            raise RuntimeError(f"{what}: no epoch is planned; call begin_epoch() first")
-        if kind != self._fed_kind:
-            raise RuntimeError(f"{what}: the epoch was begun for {self._fed_kind!r}, not for {kind!r}")
-
-    def _fed_eager(self) -> dict:
-        """Feed the current round into the buffers the trainer keeps for its eager steps (made at the first call)."""
-        f = self.feeder
-        if self._fed_buf is None:
-            batch = []
-            for d, b in zip(f.sets, f.batch):
-                batch += [torch.empty((b,) + tuple(d.x.shape[1:]), dtype=torch.float32, device=f.device),
-                          torch.empty((b,) + tuple(d.y.shape[1:]), dtype=torch.int64, device=f.device)]
-            self._fed_buf = {"batch": batch, "t": torch.zeros(2, dtype=torch.int32, device=f.device), "r": torch.ones(2, device=f.device)}
-        b = self._fed_buf
-        f.feed(*b["batch"], t=b["t"], r=b["r"])
-        return b
-
-    def _fed_state_dict(self) -> dict:
-        return {} if self.feeder is None else {"feeder": {"kind": self._fed_kind, **self.feeder.state_dict()}}
-
-    def _fed_load_state_dict(self, sd: dict) -> None:
-        """A "feeder" entry goes into the attached feeder; without one attached, or without the entry, nothing happens."""
-        if "feeder" in sd and self.feeder is not None:
-            self.feeder.load_state_dict(sd["feeder"])
-            self._fed_kind = sd["feeder"]["kind"]
-
-
-def _enable_grad_accumulation(trainer, arg) -> None:
-    """The constructors' ``grad_accumulation=``: None / False, or the number of steps."""
-    if arg is None or arg is False:
-        return
-    trainer.enable_grad_accumulation(1 if arg is True else arg)
 
 
 class ClassifierTrainer(_WeightAveraging, _GradAccumulating, _Fed):
@@ -417,13 +86,13 @@ class ClassifierTrainer(_WeightAveraging, _GradAccumulating, _Fed):
         self.device_hparams = False
         if device_hparams:
             self.enable_device_hparams()
-        _enable_weight_average(self, weight_average)
-        _enable_grad_accumulation(self, grad_accumulation)
+        _enable_from_arg(self.enable_weight_average, weight_average, "decay")
+        _enable_from_arg(self.enable_grad_accumulation, grad_accumulation, "steps")
 
     def _ema_modules(self) -> Dict[str, nn.Module]:
         return {"fe": self.fe, "clf": self.clf}
 
-    def _ema_resident(self) -> bool:
+    def _capture_resident(self) -> bool:
         return self._graph is not None
 
     def enable_device_hparams(self) -> None:
@@ -432,8 +101,7 @@ class ClassifierTrainer(_WeightAveraging, _GradAccumulating, _Fed):
         Idempotent; before ``capture`` only (a resident graph holds the launches that take the rates by value)."""
         if self.device_hparams:
             return
-        if self._graph is not None:
-            raise RuntimeError("enable_device_hparams(): a capture is resident; enable the mode before capture()")
+        self._refuse_resident("enable_device_hparams()")
         self.opt_fe.enable_lr_on_device(); self.opt_clf.enable_lr_on_device()
         self.device_hparams = True
 
@@ -444,10 +112,9 @@ class ClassifierTrainer(_WeightAveraging, _GradAccumulating, _Fed):
         """One batch; with gradient accumulation one micro-batch, whose call updates only if it closes its window.  Returns
         (loss, logits) of this call's batch."""
         self._ema_no_step("step()")
-        acc = self.grad_accumulation
-        closing = acc is None or acc.closing_next
+        closing = self._closing
         loss, logits = self._fwd_bwd(x, y)
-        if acc is not None:
+        if self.grad_accumulation is not None:
             self._accum_fold(self.parameters(), advance=True)
         if closing:
             self._update()
@@ -487,25 +154,21 @@ class ClassifierTrainer(_WeightAveraging, _GradAccumulating, _Fed):
         if acc is not None:
             warmup = -(-warmup // acc.steps_host) * acc.steps_host
         self._g_x, self._g_y = x.clone(), y.clone()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
+        with _capture.warmup_stream(self.device):
             for _ in range(warmup):
                 self.step(self._g_x, self._g_y)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
         self._graph = torch.cuda.CUDAGraph()
         self._graph_update = None
         if acc is None:
-            with torch.cuda.graph(self._graph, capture_error_mode=_CAPTURE_MODE):
+            with _capture.graph(self._graph):
                 self._g_out = self.step(self._g_x, self._g_y)
             return
-        with torch.cuda.graph(self._graph, capture_error_mode=_CAPTURE_MODE):
+        with _capture.graph(self._graph):
             loss, logits = self._fwd_bwd(self._g_x, self._g_y)
             self._accum_fold(self.parameters(), advance=True)
             self._g_out = (loss.detach(), logits.detach())
         self._graph_update = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self._graph_update, pool=self._graph.pool(), capture_error_mode=_CAPTURE_MODE):
+        with _capture.graph(self._graph_update, self._graph.pool()):
             self._update()
 
     def replay(self, x: torch.Tensor, y: torch.Tensor):
@@ -524,7 +187,7 @@ class ClassifierTrainer(_WeightAveraging, _GradAccumulating, _Fed):
             push_lr((self.opt_fe, self.opt_clf))
         self._graph.replay()
         if self._graph_update is not None:
-            closing = self.grad_accumulation.closing_next
+            closing = self._closing
             self.grad_accumulation.advance_host()
             if closing:
                 self._graph_update.replay()
@@ -556,25 +219,6 @@ class ClassifierTrainer(_WeightAveraging, _GradAccumulating, _Fed):
         """An ``evaluate.Evaluator`` of (``fe``, ``clf``) over the resident ``data``; ``kw`` are its other arguments."""
         from .evaluate import Evaluator
         return Evaluator(self.fe, self.clf, data, batch_size, **kw)
-
-
-def _enable_weight_average(trainer, arg) -> None:
-    """The constructors' ``weight_average=``: None / False, True, a decay, or a dict of enable_weight_average's arguments."""
-    if arg is None or arg is False:
-        return
-    if arg is True:
-        trainer.enable_weight_average()
-    elif isinstance(arg, dict):
-        trainer.enable_weight_average(**arg)
-    else:
-        trainer.enable_weight_average(decay=arg)
-
-
-class _WindowOpens:
-    """``guard_copy``'s predicate word of a save under gradient accumulation: the window's position ``j`` in the place of a verdict."""
-
-    def __init__(self, acc: GradAccumulation):
-        self.verdict = acc.j
 
 
 @dataclass
@@ -684,21 +328,15 @@ class JointTrainer(_WeightAveraging, _GradAccumulating, _Fed):
             self.enable_device_hparams()
         if anomaly_guard:
             self.enable_anomaly_guard()
-        if grad_clip is not None and grad_clip is not False:
-            if grad_clip is True:
-                self.enable_grad_clip()
-            elif isinstance(grad_clip, dict):
-                self.enable_grad_clip(**grad_clip)
-            else:
-                self.enable_grad_clip(max_norm=grad_clip)
-        _enable_weight_average(self, weight_average)
-        _enable_grad_accumulation(self, grad_accumulation)
+        _enable_from_arg(self.enable_grad_clip, grad_clip, "max_norm")
+        _enable_from_arg(self.enable_weight_average, weight_average, "decay")
+        _enable_from_arg(self.enable_grad_accumulation, grad_accumulation, "steps")
 
     # ------------------------------------------------------------------ weight averaging (the methods are _WeightAveraging's)
     def _ema_modules(self) -> Dict[str, nn.Module]:
         return {k: self.m[k] for k in self.MODULES}
 
-    def _ema_resident(self) -> bool:
+    def _capture_resident(self) -> bool:
         return self._graphs is not None or bool(self._phase)
 
     def _ema_caches(self) -> list:
@@ -734,8 +372,7 @@ class JointTrainer(_WeightAveraging, _GradAccumulating, _Fed):
         capture is resident, whose launches are the unguarded ones."""
         if self.anomaly_guard:
             return
-        if self._graphs is not None or self._phase:
-            raise RuntimeError("enable_anomaly_guard(): a capture is resident; enable the mode before capture() / capture_phase()")
+        self._refuse_resident("enable_anomaly_guard()")
         self._guard = AnomalyGuard(self.device)
         # the GradNorm-weight Adams create their state on their first step; a skipped first step must leave none behind, so it
         # exists from now on, with the values torch would create (capturable: a float32 device step counter)
@@ -819,8 +456,19 @@ class JointTrainer(_WeightAveraging, _GradAccumulating, _Fed):
         live, shadow = self._guard_live
         guard_copy(live, shadow, self._guard, when=True)
 
-    def _guard_report(self) -> Dict[str, torch.Tensor]:
-        return {"skipped": self._guard.verdict[0].clone(), "anomaly": self._guard.counts[: len(self.ANOMALY_GROUPS)].clone()}
+    def _mode_report(self, modules, live: bool = False) -> Dict[str, torch.Tensor]:
+        """What the enabled modes add to the report of a step over ``modules``: fresh tensors, or with ``live`` the views of the
+        device words themselves where an entry is one — ``capture_phase`` copies those into static tensors of its own, and a
+        clone would be one more launch in its graph."""
+        out = {}
+        if self._clip is not None:
+            out.update(self._clip_report(modules))
+        if self.weight_average is not None:
+            out.update(self._ema_report(live))
+        if self._guard is not None:
+            words = {"skipped": self._guard.verdict[0], "anomaly": self._guard.counts[: len(self.ANOMALY_GROUPS)]}
+            out.update(words if live else {k: v.clone() for k, v in words.items()})
+        return out
 
     # ------------------------------------------------------------------ gradient norms and clipping on the device
     def enable_grad_clip(self, max_norm: Optional[float] = None, per_module: Optional[Dict[str, float]] = None) -> None:
@@ -845,8 +493,7 @@ class JointTrainer(_WeightAveraging, _GradAccumulating, _Fed):
         sets those limits); raises while a joint or phase capture is resident, whose launches lack the two kernels."""
         limits = self._clip_limits(max_norm, dict(per_module or {}))
         if not self.grad_clip:
-            if self._graphs is not None or self._phase:
-                raise RuntimeError("enable_grad_clip(): a capture is resident; enable the mode before capture() / capture_phase()")
+            self._refuse_resident("enable_grad_clip()")
             self._clip = GradClip(self.device)
             for mods in (self.MODULES,) + tuple(self.PHASES.values()):
                 self._clip_masks[tuple(mods)] = torch.tensor([k in mods for k in self.MODULES], device=self.device)
@@ -914,8 +561,7 @@ class JointTrainer(_WeightAveraging, _GradAccumulating, _Fed):
         while a joint or phase capture is resident, whose launches take the values by value."""
         if self.device_hparams:
             return
-        if self._graphs is not None or self._phase:
-            raise RuntimeError("enable_device_hparams(): a capture is resident; enable the mode before capture() / capture_phase()")
+        self._refuse_resident("enable_device_hparams()")
         for o in self._scheduled_opts():
             o.enable_lr_on_device()
         self._coef_host = tuple(float(v) for v in loss_coefficients(0))
@@ -933,8 +579,7 @@ class JointTrainer(_WeightAveraging, _GradAccumulating, _Fed):
             return
         want = tuple(float(v) for v in loss_coefficients(epoch))
         if want != self._coef_host:
-            host = torch.tensor(want, dtype=torch.float32)
-            self._coef.copy_(host.pin_memory() if self._coef.is_cuda else host, non_blocking=True)
+            push_words(self._coef, torch.tensor(want, dtype=torch.float32))
             self._coef_host = want
 
     def make_schedulers(self) -> Dict[str, object]:
@@ -1226,8 +871,7 @@ class JointTrainer(_WeightAveraging, _GradAccumulating, _Fed):
         report is this call's own plus "accum_index", and the update, with what it adds to the report, runs on the call that
         closes the window.  Captured phases do not accumulate: ``capture_phase`` / ``replay_phase`` raise at more than one step."""
         self._ema_no_step("phase_step()")
-        acc = self.grad_accumulation
-        closing = acc is None or acc.closing_next
+        acc, closing = self.grad_accumulation, self._closing
         report = self._phase_fwd_bwd(phase, x_t, y_t, x_s, y_s, t_samples)
         if acc is not None:                                                   # a micro-step of a window: only its last call updates
             self._accum_fold(self.parameters(), advance=True)
@@ -1237,12 +881,7 @@ class JointTrainer(_WeightAveraging, _GradAccumulating, _Fed):
         if self.bucket is not None:
             self.bucket.all_reduce(self.parameters())
         self._phase_update(phase)
-        if self._clip is not None:
-            report.update(self._clip_report(self.PHASES[phase]))
-        if self.weight_average is not None:
-            report.update(self._ema_report())
-        if self._guard is not None:
-            report.update(self._guard_report())
+        report.update(self._mode_report(self.PHASES[phase]))
         return report
 
     def _phase_fwd_bwd(self, phase: str, x_t, y_t, x_s, y_s, t_samples):
@@ -1272,14 +911,11 @@ class JointTrainer(_WeightAveraging, _GradAccumulating, _Fed):
         if self._guard is not None:
             self._guard_scan(self.PHASES[phase], (), self._guard_losses)
             self._guard_losses = ()
-            rmsprop_step_many([self.opts[k] for k in self.PHASES[phase] if k != "cpc"], self._guard)
-            if "cpc" in self.PHASES[phase]:
-                self.opt_cpc.step(guard=self._guard)
+        rmsprop_step_many([self.opts[k] for k in self.PHASES[phase] if k != "cpc"], self._guard)
+        if "cpc" in self.PHASES[phase]:
+            self.opt_cpc.step(guard=self._guard)
+        if self._guard is not None:
             self._guard_rollback()
-        else:
-            rmsprop_step_many([self.opts[k] for k in self.PHASES[phase] if k != "cpc"])
-            if "cpc" in self.PHASES[phase]:
-                self.opt_cpc.step()
         self._ema_update(self.PHASES[phase], self._guard)                     # the last thing a step does
 
     # ------------------------------------------------------------------ hipGraph for the phases: capture once each, replay per batch
@@ -1310,46 +946,28 @@ class JointTrainer(_WeightAveraging, _GradAccumulating, _Fed):
         dev = self.device
         gi = {"x_t": x_t.clone(), "y_t": y_t.clone(), "x_s": x_s.clone(), "y_s": y_s.clone(),
               "t": torch.zeros(2, dtype=torch.int32, device=dev)}
-        args = (gi["x_t"], gi["y_t"], gi["x_s"], gi["y_s"], (gi["t"][0], gi["t"][1]))
+        args = self._static_args(gi)
         params = self.parameters()
         grads_before = [p.grad for p in params]
         snap, hook = self.snapshot(), self.on_grads_ready
         self.on_grads_ready = None
-        main = torch.cuda.current_stream()
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(main)
         try:
-            with torch.cuda.stream(side):                                     # eager warm-up on a side stream
+            with _capture.warmup_stream(dev):                                 # eager warm-up on a side stream
                 for _ in range(warmup):
                     keys = sorted(self.phase_step(phase, *args))
                 self.restore(snap, new_to_zero=True)
         finally:
             self.on_grads_ready = hook
-        main.wait_stream(side)
-        torch.cuda.synchronize()
-        # static report: the graphs' own outputs live in the shared pool, where a later capture may reuse what this one frees
-        keys = [k for k in keys if k not in ("skipped", "anomaly", "grad_l2", "clip_coef", "ema_weight", "ema_steps",   # static tensors of their own
-                                          "accum_index")]                                # (the eager warm-up's; a captured phase is a whole step)
+        # static report: the graphs' own outputs live in the shared pool, where a later capture may reuse what this one frees;
+        # the modes' entries get static tensors of their own, shaped like the entries themselves
+        g_rep = {k: torch.zeros_like(v) for k, v in self._mode_report(self.PHASES[phase], live=True).items()}
+        keys = [k for k in keys if k not in g_rep and k != "accum_index"]     # (the eager warm-up's; a captured phase is a whole step)
         out = torch.zeros(len(keys), device=dev)
-        g_rep = {} if self._guard is None else {"skipped": torch.zeros((), dtype=torch.int32, device=dev),
-                                                "anomaly": torch.zeros(len(self.ANOMALY_GROUPS), dtype=torch.int32, device=dev)}
-        if self._clip is not None:
-            g_rep.update(grad_l2=torch.zeros(len(self.MODULES) + 1, device=dev), clip_coef=torch.ones(len(self.MODULES), device=dev))
-        if self.weight_average is not None:
-            g_rep.update(ema_weight=torch.zeros(len(self.MODULES), device=dev),
-                         ema_steps=torch.zeros(len(self.MODULES), dtype=torch.int32, device=dev))
 
         def update():
             self._phase_update(phase)
-            if self._clip is not None:
-                for k, v in self._clip_report(self.PHASES[phase]).items():
-                    g_rep[k].copy_(v)
-            if self._guard is not None:
-                g_rep["skipped"].copy_(self._guard.verdict[0])
-                g_rep["anomaly"].copy_(self._guard.counts[: len(self.ANOMALY_GROUPS)])
-            if self.weight_average is not None:
-                g_rep["ema_weight"].copy_(self.weight_average.w[: len(self.MODULES)])
-                g_rep["ema_steps"].copy_(self.weight_average.count[: len(self.MODULES)])
+            for k, v in self._mode_report(self.PHASES[phase], live=True).items():
+                g_rep[k].copy_(v)
 
         def fwd_bwd():
             rep = self._phase_fwd_bwd(phase, *args)
@@ -1360,15 +978,15 @@ class JointTrainer(_WeightAveraging, _GradAccumulating, _Fed):
         try:
             if self.bucket is None:
                 graphs = [torch.cuda.CUDAGraph()]
-                with torch.cuda.graph(graphs[0], pool=self._phase_pool, capture_error_mode=_CAPTURE_MODE):
+                with _capture.graph(graphs[0], self._phase_pool):
                     fwd_bwd()
                     update()
             else:
                 graphs = [torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()]
-                with torch.cuda.graph(graphs[0], pool=self._phase_pool, capture_error_mode=_CAPTURE_MODE):
+                with _capture.graph(graphs[0], self._phase_pool):
                     fwd_bwd()
                 self.bucket.all_reduce(params)                                # eager, between the graphs
-                with torch.cuda.graph(graphs[1], pool=self._phase_pool, capture_error_mode=_CAPTURE_MODE):
+                with _capture.graph(graphs[1], self._phase_pool):
                     update()
             # the gradient tensors the graph writes stay allocated as long as the graph does
             grads = [p.grad for p in params if p.grad is not None]
@@ -1513,8 +1131,7 @@ class JointTrainer(_WeightAveraging, _GradAccumulating, _Fed):
         A1 = forward + the full backward;  [the gradient bucket's all-reduce starts on a side stream]
         A2 = GradNorm's partial backward passes (they never touch ``.grad``: they overlap the all-reduce);
         [wait for the bucket; average the 10 GradNorm scalars]  B = GradNorm weight update + optimisers."""
-        acc = self.grad_accumulation
-        closing = acc is None or acc.closing_next                             # the collectives and B: on the call that closes a window
+        closing = self._closing                                               # the collectives and B: on the call that closes a window
         with _dist.global_batch(self.bucket if self.sync == "global" else None), self._step_scope():
             state = self._step_part_a1(x_t, y_t, x_s, y_s, epoch, t_samples, noise_ratios)
             if closing:
@@ -1545,45 +1162,43 @@ class JointTrainer(_WeightAveraging, _GradAccumulating, _Fed):
     def _step_part_a1(self, x_t, y_t, x_s, y_s, epoch, t_samples, noise_ratios):
         if self._guard is not None:
             self._guard_save()
-        if True:
-            L, aux = self.forward_losses(x_t, y_t, x_s, y_s, t_samples, noise_ratios)
-            lt = torch.stack([L["nf_t"], L["ce_t"]])
-            ls = torch.stack([L["nf_s"], L["ce_s"], L["ce_s2t2s"]])
-            # device_hparams: 0-dim views of the coefficient tensor (_set_epoch wrote the epoch's values) — same fp32 products
-            a, b, c, d = loss_coefficients(epoch) if self._coef is None else self._coef.unbind(0)
-            # Q3: first backward + second backward (weights zeroed) == Σ wᵢ∇Lᵢ + 2·(a∇cdan + b∇fd + c∇sl_t + d∇sl_s)
-            total = torch.sum(self.w_t.detach() * lt) + torch.sum(self.w_s.detach() * ls) \
-                + 2.0 * (a * L["cdan"] + b * L["fd_s"] + c * L["sl_t"] + d * L["sl_s"])
-            for o in self.opts.values():
-                o.zero_grad(set_to_none=True)
-            self.opt_cpc.zero_grad(set_to_none=True)
-            total.backward(retain_graph=True)
+        L, aux = self.forward_losses(x_t, y_t, x_s, y_s, t_samples, noise_ratios)
+        lt = torch.stack([L["nf_t"], L["ce_t"]])
+        ls = torch.stack([L["nf_s"], L["ce_s"], L["ce_s2t2s"]])
+        # device_hparams: 0-dim views of the coefficient tensor (_set_epoch wrote the epoch's values) — same fp32 products
+        a, b, c, d = loss_coefficients(epoch) if self._coef is None else self._coef.unbind(0)
+        # Q3: first backward + second backward (weights zeroed) == Σ wᵢ∇Lᵢ + 2·(a∇cdan + b∇fd + c∇sl_t + d∇sl_s)
+        total = torch.sum(self.w_t.detach() * lt) + torch.sum(self.w_s.detach() * ls) \
+            + 2.0 * (a * L["cdan"] + b * L["fd_s"] + c * L["sl_t"] + d * L["sl_s"])
+        for o in self.opts.values():
+            o.zero_grad(set_to_none=True)
+        self.opt_cpc.zero_grad(set_to_none=True)
+        total.backward(retain_graph=True)
         if self.grad_accumulation is not None:                                # every .grad of the step is final here: A2 never touches one
             self._accum_fold(self.parameters(), advance=False)
         return {"L": L, "aux": aux, "lt": lt, "ls": ls}
 
     def _step_part_a2(self, state):
         L, aux, lt, ls = state["L"], state["aux"], state["lt"], state["ls"]
-        if True:
-            # GradNorm (:682-690): per-loss gradient norms over the 12 shared tensors
-            sh_t = list(self.m["fe_t"].return_last_layer().parameters())
-            sh_s = list(self.m["fe_s"].return_last_layer().parameters())
-            # Differentiate the loss tensors themselves, not lt[i] / ls[i]: a select of the stacked vector sends a ZERO
-            # cotangent down every other loss's graph (autograd does not prune zeros), i.e. 8 WaveGlow backward
-            # traversals per step where 4 carry anything (ce_t / ce_s never touch the flow).  Same values, half the work.
-            with ops.partial_backward():
-                g_t = [torch.autograd.grad(L[k], sh_t, retain_graph=True) for k in ("nf_t", "ce_t")]
-                g_s = [torch.autograd.grad(L[k], sh_s, retain_graph=(k != "ce_s2t2s")) for k in ("nf_s", "ce_s", "ce_s2t2s")]
-            if _dist.global_batch_active():
-                # mode B: the norms are those of the GLOBAL per-loss gradients (mean over ranks), not means of norms
-                flat = torch.cat([g.reshape(-1) for gs in g_t + g_s for g in gs])
-                flat = flat / _dist.sum_over_ranks_(flat)
-                it = iter(torch.split(flat, [g.numel() for gs in g_t + g_s for g in gs]))
-                g_t = [[next(it).view_as(g) for g in gs] for gs in g_t]
-                g_s = [[next(it).view_as(g) for g in gs] for gs in g_s]
-            # Σ_θ ‖∂L_i/∂θ‖₂ per loss (:685-690): all 5 × 12 norms as ONE multi-tensor launch (60 separate reductions before)
-            norms = torch.stack(torch._foreach_norm([g for gs in g_t + g_s for g in gs])).view(len(g_t) + len(g_s), -1).sum(dim=1)
-            base_t, base_s = norms[: len(g_t)], norms[len(g_t):]
+        # GradNorm (:682-690): per-loss gradient norms over the 12 shared tensors
+        sh_t = list(self.m["fe_t"].return_last_layer().parameters())
+        sh_s = list(self.m["fe_s"].return_last_layer().parameters())
+        # Differentiate the loss tensors themselves, not lt[i] / ls[i]: a select of the stacked vector sends a ZERO
+        # cotangent down every other loss's graph (autograd does not prune zeros), i.e. 8 WaveGlow backward
+        # traversals per step where 4 carry anything (ce_t / ce_s never touch the flow).  Same values, half the work.
+        with ops.partial_backward():
+            g_t = [torch.autograd.grad(L[k], sh_t, retain_graph=True) for k in ("nf_t", "ce_t")]
+            g_s = [torch.autograd.grad(L[k], sh_s, retain_graph=(k != "ce_s2t2s")) for k in ("nf_s", "ce_s", "ce_s2t2s")]
+        if _dist.global_batch_active():
+            # mode B: the norms are those of the GLOBAL per-loss gradients (mean over ranks), not means of norms
+            flat = torch.cat([g.reshape(-1) for gs in g_t + g_s for g in gs])
+            flat = flat / _dist.sum_over_ranks_(flat)
+            it = iter(torch.split(flat, [g.numel() for gs in g_t + g_s for g in gs]))
+            g_t = [[next(it).view_as(g) for g in gs] for gs in g_t]
+            g_s = [[next(it).view_as(g) for g in gs] for gs in g_s]
+        # Σ_θ ‖∂L_i/∂θ‖₂ per loss (:685-690): all 5 × 12 norms as ONE multi-tensor launch (60 separate reductions before)
+        norms = torch.stack(torch._foreach_norm([g for gs in g_t + g_s for g in gs])).view(len(g_t) + len(g_s), -1).sum(dim=1)
+        base_t, base_s = norms[: len(g_t)], norms[len(g_t):]
         report = {k: v.detach() for k, v in L.items()}
         report.update({k: v.detach() for k, v in aux.items()})
         # scalars that must be identical on every rank: loss values and gradient-norm bases (10 floats)
@@ -1644,12 +1259,8 @@ class JointTrainer(_WeightAveraging, _GradAccumulating, _Fed):
             if first and int(guard.verdict) != 0:                             # the one host read: only a COMPLETED step sets them
                 self.init_t = self.init_s = None
         self.opt_w_t.step(); self.opt_w_s.step()
-        if guard is not None:
-            rmsprop_step_many(list(self.opts.values()), guard)
-            self.opt_cpc.step(guard=guard)
-        else:
-            rmsprop_step_many(list(self.opts.values()))
-            self.opt_cpc.step()
+        rmsprop_step_many(list(self.opts.values()), guard)
+        self.opt_cpc.step(guard=guard)
         with torch.no_grad():                                                 # :756-766
             self.w_t.clamp_(min=0.0)
             self.w_t.mul_(7 / torch.sum(self.w_t))
@@ -1665,12 +1276,7 @@ class JointTrainer(_WeightAveraging, _GradAccumulating, _Fed):
         report = dict(mid["report"])
         report.update({"w_t": self.w_t.detach().clone(), "w_s": self.w_s.detach().clone(),
                        "norms_t": nt.detach(), "norms_s": ns.detach()})
-        if self._clip is not None:
-            report.update(self._clip_report(self.MODULES))
-        if self.weight_average is not None:
-            report.update(self._ema_report())
-        if guard is not None:
-            report.update(self._guard_report())
+        report.update(self._mode_report(self.MODULES))
         if "window_losses" in mid:
             report.update({"accum_index": mid["accum_index"], "window_losses": mid["window_losses"]})
         return report
@@ -1705,14 +1311,10 @@ class JointTrainer(_WeightAveraging, _GradAccumulating, _Fed):
         self._g_epoch = epoch
         self._set_epoch(epoch)
         T_half = max(1, (self.cfg.L_t // 2) // 2)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):                                         # eager warm-up on a side stream
+        with _capture.warmup_stream(dev):                                     # eager warm-up on a side stream
             for _ in range(warmup):
                 self._replay_inputs(x_t, y_t, x_s, y_s, (int(torch.randint(T_half, (1,))), int(torch.randint(T_half, (1,)))))
                 self._graph_body()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
         if self.m["ad_net"].iter_num < self.m["ad_net"].max_iter or self.m["fd_s"].iter_num < self.m["fd_s"].max_iter:
             raise RuntimeError("capture(): GRL call counters not saturated yet; increase warmup")
         if self._guard is not None and self.init_t is None:
@@ -1721,31 +1323,27 @@ class JointTrainer(_WeightAveraging, _GradAccumulating, _Fed):
         self._replay_inputs(x_t, y_t, x_s, y_s, (0, 0))
         if self.bucket is None and acc is None:
             self._graphs = [torch.cuda.CUDAGraph()]
-            with torch.cuda.graph(self._graphs[0], capture_error_mode=_CAPTURE_MODE):
+            with _capture.graph(self._graphs[0]):
                 self._g_out = self._graph_body()
         elif self.bucket is None:
             gm, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-            gi = self._g_in
-            with torch.cuda.graph(gm, capture_error_mode=_CAPTURE_MODE):
-                self._g_mid = self._step_part_a(gi["x_t"], gi["y_t"], gi["x_s"], gi["y_s"], self._g_epoch, (gi["t"][0], gi["t"][1]),
-                                                (gi["r"][0], gi["r"][1]))
-            with torch.cuda.graph(gb, pool=gm.pool(), capture_error_mode=_CAPTURE_MODE):
+            with _capture.graph(gm):
+                self._g_mid = self._step_part_a(*self._static_args(self._g_in, self._g_epoch))
+            with _capture.graph(gb, gm.pool()):
                 self._g_out = self._step_part_b(self._g_mid)
             self._graphs = [gm, gb]
         else:
             ga1, ga2, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-            gi = self._g_in
             with self._step_scope():                                          # packed weights of A1 are reused by A2
-                with torch.cuda.graph(ga1, capture_error_mode=_CAPTURE_MODE):
-                    state = self._step_part_a1(gi["x_t"], gi["y_t"], gi["x_s"], gi["y_s"], self._g_epoch, (gi["t"][0], gi["t"][1]),
-                                               (gi["r"][0], gi["r"][1]))
+                with _capture.graph(ga1):
+                    state = self._step_part_a1(*self._static_args(self._g_in, self._g_epoch))
                 pool = ga1.pool()
                 self._reduce_begin()                                          # eager, on the bucket's side stream
-                with torch.cuda.graph(ga2, pool=pool, capture_error_mode=_CAPTURE_MODE):
+                with _capture.graph(ga2, pool):
                     self._g_mid = self._step_part_a2(state)
                 del state                                                     # the autograd graph of the captured step
             self._reduce_end(self._g_mid)                                     # eager; also fixes the bucket's buffer
-            with torch.cuda.graph(gb, pool=pool, capture_error_mode=_CAPTURE_MODE):
+            with _capture.graph(gb, pool):
                 self._g_out = self._step_part_b(self._g_mid)
             self._graphs = [ga1, ga2, gb]
         if acc is not None:
@@ -1753,9 +1351,14 @@ class JointTrainer(_WeightAveraging, _GradAccumulating, _Fed):
         return self
 
     def _graph_body(self):
-        gi = self._g_in
-        return self._step_body(gi["x_t"], gi["y_t"], gi["x_s"], gi["y_s"], self._g_epoch, (gi["t"][0], gi["t"][1]),
-                               (gi["r"][0], gi["r"][1]))
+        return self._step_body(*self._static_args(self._g_in, self._g_epoch))
+
+    @staticmethod
+    def _static_args(gi: dict, *epoch):
+        """The arguments of a step out of a capture's static inputs ``gi``: the batch, ``epoch`` if the step takes one, the two CPC
+        indices and, where the capture holds them, NoiseTransfer's two ratios, as 0-d views."""
+        pairs = [(gi[k][0], gi[k][1]) for k in ("t", "r") if k in gi]
+        return (gi["x_t"], gi["y_t"], gi["x_s"], gi["y_s"], *epoch, *pairs)
 
     def _replay_inputs(self, x_t, y_t, x_s, y_s, t_samples):
         gi = self._g_in
@@ -1793,8 +1396,7 @@ class JointTrainer(_WeightAveraging, _GradAccumulating, _Fed):
 
     def _replay_graphs(self):
         """What a replay does once the static inputs hold the batch, the CPC indices and the ratios."""
-        acc = self.grad_accumulation
-        closing = acc is None or acc.closing_next
+        acc, closing = self.grad_accumulation, self._closing
         self._graphs[0].replay()
         if len(self._graphs) == 3:
             if closing:

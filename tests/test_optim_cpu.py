@@ -49,3 +49,32 @@ def test_fused_rmsprop_host_logic_matches_torch_rmsprop():
     fresh = FusedRMSprop([torch.nn.Parameter(p.detach().clone()) for p in b1], lr=0.001)
     fresh.load_state_dict(sd)
     assert torch.equal(fresh.state[fresh.param_groups[0]["params"][0]]["square_avg"], mine[0].state[b1[0]]["square_avg"])
+
+
+def test_push_words_writes_a_slice_in_place():
+    from feature_level_style_transfer_for_tsc_amd.optim import push_words
+    words = torch.zeros(4, dtype=torch.int32)
+    push_words(words[:2], torch.tensor([7, 9], dtype=torch.int32))
+    assert words.tolist() == [7, 9, 0, 0]
+
+
+def test_exchanged_swaps_back_and_restores_flag_and_caches_even_when_the_body_raises():
+    import pytest
+    from types import SimpleNamespace
+    from feature_level_style_transfer_for_tsc_amd import ops
+    from feature_level_style_transfer_for_tsc_amd.optim import exchanged
+    a, b = [torch.tensor([1.0, 2.0])], [torch.tensor([3.0, 4.0])]
+    owner, cache = SimpleNamespace(inside=False), SimpleNamespace(W_inverse="live")
+    with pytest.raises(KeyError):
+        with exchanged(a, b, [cache], owner, "inside", "scope()") as got:
+            assert got is owner and owner.inside and not hasattr(cache, "W_inverse")
+            assert a[0].tolist() == [3.0, 4.0] and b[0].tolist() == [1.0, 2.0]
+            cache.W_inverse = "of the exchanged weights"
+            with pytest.raises(RuntimeError, match=r"scope\(\).*nest"):
+                exchanged(a, b, [cache], owner, "inside", "scope()").__enter__()
+            raise KeyError("body")
+    assert not owner.inside and cache.W_inverse == "live" and a[0].tolist() == [1.0, 2.0] and b[0].tolist() == [3.0, 4.0]
+    with ops.pack_cache():
+        with pytest.raises(RuntimeError, match=r"scope\(\).*pack_cache"):
+            exchanged(a, b, [], owner, "inside", "scope()").__enter__()
+    assert a[0].tolist() == [1.0, 2.0] and not owner.inside
