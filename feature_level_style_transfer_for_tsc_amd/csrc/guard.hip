@@ -20,59 +20,88 @@
 //                          acc = g when the window opens, acc += g after, and g = acc / k in place on the call that closes it.
 //
 // House style of optim.hip: the pointer tuples ride BY VALUE in the kernel arguments, at most 64 per launch, so a captured launch
-// carries them; no float atomics and no zero fill: every workgroup of the scan writes its own slot with a plain store (and plain
-// zeros into the slots of its tensor that no workgroup of this launch owns), the finalising launch adds the slots.  The counts are
-// integers, so their sum does not depend on the order of the additions: the finaliser's LDS integer adds give the same words on
-// every run.  The scan only reads its inputs.
-#include "fst_common.h"
+// carries them (the chunks of a call, the grid of a launch and the test of an entry are fst_multi.h's); no float atomics and no
+// zero fill: every workgroup of a scan writes its own slot with a plain store (and plain zeros into the slots of its tensor that
+// no workgroup of this launch owns), the finalising launch adds the slots.  The counts are integers, so their sum does not depend
+// on the order of the additions: the finaliser's LDS integer adds give the same words on every run.  A scan only reads its inputs.
+//
+// Written once each: the walk over ONE tensor in 16-byte quads with its odd ends (quad_walk: the count, the sum of squares and the
+// scale are its three element functors), a scan's record in the slot array (slot_record), the walk over a PAIR of tensors
+// (pair_tensor: the average, the exchange and the accumulation), and the two argument structs with their checks and fills
+// (GroupArgs, PairArgs).
+#include "fst_multi.h"
 
-#define NF_MAX_T 64                 // tensors per launch
-#define NF_SLOTS 64                 // workgroups (and slots) per tensor at most
-#define NF_REC (NF_SLOTS + 1)       // a tensor's record in the slot array: its group id, then its NF_SLOTS counts
+#define NF_REC (FST_MULTI_WG + 1)   // a tensor's record in the slot array: its group id, then the words of its FST_MULTI_WG workgroups
+#define GC_GROUPS 32                // groups; norms and limits carry one more word, the total
 
-struct NonfiniteArgs {
-  const float* x[NF_MAX_T];
-  int numel[NF_MAX_T];
-  int group[NF_MAX_T];
+struct GroupArgs {
+  float* x[FST_MULTI_T];
+  int numel[FST_MULTI_T];
+  int group[FST_MULTI_T];
   int n, base;                      // tensors of this launch; index of its first tensor in the call (its record in the slot array)
 };
-static_assert(sizeof(NonfiniteArgs) + sizeof(int*) <= 4096, "kernel arguments: 4 KB at most");
+static_assert(sizeof(GroupArgs) + sizeof(void*) <= 4096, "kernel arguments: 4 KB at most");
 
 // NaN and ±inf are the values whose exponent bits are all ones; a test on the bits cannot be folded away by fast-math rules
 __device__ __forceinline__ int nonfinite_bits(uint32_t b) { return (b & 0x7f800000u) == 0x7f800000u; }
 
-// grid (bx, n): up to NF_SLOTS workgroups per tensor, grid-stride beyond.  16-byte loads over the aligned middle of the tensor;
-// the up to three elements in front of the first 16-byte boundary and the up to three after the last full quad go to workgroup 0.
-__global__ __launch_bounds__(256) void nonfinite_multi_kernel(NonfiniteArgs a, int* __restrict__ slots) {
-  const int t = blockIdx.y;
-  if (t >= a.n) return;
-  const uint32_t* __restrict__ x = (const uint32_t*)a.x[t];
-  const int n = a.numel[t];
+// One workgroup's share of x[0, n) on a grid of up to FST_MULTI_WG workgroups per tensor, grid-stride beyond: 16-byte accesses
+// over the aligned middle of the tensor; the up to three elements in front of the first 16-byte boundary and the up to three after
+// the last full quad go to workgroup 0.  A thread hands op its elements in this order: its quads in index order, each as
+// .x .y .z .w, then its head element, then its tail element (a sum that op keeps depends on it).  Op::writes: op changes the
+// element, which is stored back; otherwise x is only read.
+template <class Op>
+__device__ __forceinline__ void quad_walk(float* __restrict__ x, int n, Op& op) {
   int head = (int)(((16u - (unsigned)((uintptr_t)x & 15u)) & 15u) >> 2);
   head = head < n ? head : n;
   const int nv = (n - head) >> 2;
   const int tail0 = head + 4 * nv;
-  const uint4* __restrict__ xv = (const uint4*)(x + head);
-  int c = 0;
+  float4* __restrict__ xv = (float4*)(x + head);
   for (int i = blockIdx.x * 256 + threadIdx.x; i < nv; i += gridDim.x * 256) {
-    const uint4 q = xv[i];
-    c += nonfinite_bits(q.x) + nonfinite_bits(q.y) + nonfinite_bits(q.z) + nonfinite_bits(q.w);
+    float4 q = xv[i];
+    op(q.x); op(q.y); op(q.z); op(q.w);
+    if (Op::writes) xv[i] = q;
   }
   if (blockIdx.x == 0) {
-    if ((int)threadIdx.x < head) c += nonfinite_bits(x[threadIdx.x]);
-    if ((int)threadIdx.x < n - tail0) c += nonfinite_bits(x[tail0 + threadIdx.x]);
+    if ((int)threadIdx.x < head) {
+      float e = x[threadIdx.x];
+      op(e);
+      if (Op::writes) x[threadIdx.x] = e;
+    }
+    if ((int)threadIdx.x < n - tail0) {
+      float e = x[tail0 + threadIdx.x];
+      op(e);
+      if (Op::writes) x[tail0 + threadIdx.x] = e;
+    }
   }
+}
+
+struct CountOp {
+  static constexpr bool writes = false;
+  int c;
+  __device__ __forceinline__ void operator()(float e) { c += nonfinite_bits(__float_as_uint(e)); }
+};
+
+// thread 0 of a scan's workgroup: the tensor's group id (workgroup 0), the workgroup's own slot, and plain zeros into the slots
+// that no workgroup of this launch owns
+template <class W>
+__device__ __forceinline__ void slot_record(W* __restrict__ rec, int group, W total) {
+  if (blockIdx.x == 0) rec[0] = (W)group;
+  rec[1 + blockIdx.x] = total;
+  for (int s = blockIdx.x + gridDim.x; s < FST_MULTI_WG; s += gridDim.x) rec[1 + s] = (W)0;
+}
+
+__global__ __launch_bounds__(256) void nonfinite_multi_kernel(GroupArgs a, int* __restrict__ slots) {
+  const int t = blockIdx.y;
+  if (t >= a.n) return;
+  CountOp op{0};
+  quad_walk(a.x[t], a.numel[t], op);
   __shared__ int total;
   if (threadIdx.x == 0) total = 0;
   __syncthreads();
-  if (c) atomicAdd(&total, c);                                      // LDS, integer
+  if (op.c) atomicAdd(&total, op.c);                                // LDS, integer
   __syncthreads();
-  if (threadIdx.x == 0) {
-    int* rec = slots + (size_t)(a.base + t) * NF_REC;
-    if (blockIdx.x == 0) rec[0] = a.group[t];
-    rec[1 + blockIdx.x] = total;
-    for (int s = blockIdx.x + gridDim.x; s < NF_SLOTS; s += gridDim.x) rec[1 + s] = 0;   // slots no workgroup of this launch owns
-  }
+  if (threadIdx.x == 0) slot_record(slots + (size_t)(a.base + t) * NF_REC, a.group[t], total);
 }
 
 // one workgroup: counts[32] = per-group sums of every slot, then the three words (each may be NULL: not written)
@@ -82,9 +111,9 @@ __global__ __launch_bounds__(256) void nonfinite_finalize_kernel(const int* __re
   __shared__ int cnt[32];
   if (threadIdx.x < 32) cnt[threadIdx.x] = 0;
   __syncthreads();
-  for (int i = threadIdx.x; i < n_tensors * NF_SLOTS; i += 256) {
-    const int* rec = slots + (size_t)(i / NF_SLOTS) * NF_REC;
-    const int c = rec[1 + i % NF_SLOTS];
+  for (int i = threadIdx.x; i < n_tensors * FST_MULTI_WG; i += 256) {
+    const int* rec = slots + (size_t)(i / FST_MULTI_WG) * NF_REC;
+    const int c = rec[1 + i % FST_MULTI_WG];
     if (c) atomicAdd(&cnt[rec[0] & 31], c);                         // LDS, integer: the sum is the same in any order
   }
   __syncthreads();
@@ -98,6 +127,21 @@ __global__ __launch_bounds__(256) void nonfinite_finalize_kernel(const int* __re
   }
 }
 
+// every (tensor, count, group) entry of a call before its first launch
+static int check_group_tensors(const char* who, const void* const* x_host, const int64_t* numel_host, const int32_t* group_host, int n_tensors) {
+  FST_REQUIRE(n_tensors >= 0 && n_tensors < (1 << 24) && (n_tensors == 0 || (x_host && numel_host && group_host)), "%s: bad arguments", who);
+  for (int i = 0; i < n_tensors; ++i) {
+    FST_REQUIRE(fst_multi_entry_ok({x_host[i]}, numel_host[i], 4), "%s: tensor %d: null or misaligned pointer, or bad element count", who, i);
+    FST_REQUIRE(group_host[i] >= 0 && group_host[i] < GC_GROUPS, "%s: tensor %d: group %d is not in 0..31", who, i, group_host[i]);
+  }
+  return 0;
+}
+
+static void fill_group(GroupArgs& a, const void* const* x_host, const int64_t* numel_host, const int32_t* group_host, int base, int n) {
+  a.n = n; a.base = base;
+  for (int i = 0; i < n; ++i) { a.x[i] = (float*)x_host[base + i]; a.numel[i] = (int)numel_host[base + i]; a.group[i] = group_host[base + i]; }
+}
+
 extern "C" int64_t fst_nonfinite_slots(int n_tensors) { return n_tensors < 0 ? -1 : (int64_t)n_tensors * NF_REC; }
 
 extern "C" int fst_nonfinite_multi(const float* const* x_host, const int64_t* numel_host, const int32_t* group_host, int n_tensors,
@@ -107,25 +151,14 @@ extern "C" int fst_nonfinite_multi(const float* const* x_host, const int64_t* nu
               "fst_nonfinite_multi: bad arguments");
   FST_REQUIRE(slots_len >= fst_nonfinite_slots(n_tensors), "fst_nonfinite_multi: %lld slots, %lld needed", (long long)slots_len,
               (long long)fst_nonfinite_slots(n_tensors));
-  for (int i = 0; i < n_tensors; ++i) {                              // all of them before the first launch
-    FST_REQUIRE(x_host[i] && ((uintptr_t)x_host[i] & 3) == 0 && numel_host[i] > 0 && numel_host[i] < (1LL << 31),
-                "fst_nonfinite_multi: tensor %d: null or misaligned pointer, or bad element count", i);
-    FST_REQUIRE(group_host[i] >= 0 && group_host[i] < 32, "fst_nonfinite_multi: tensor %d: group %d is not in 0..31", i, group_host[i]);
-  }
-  for (int base = 0; base < n_tensors; base += NF_MAX_T) {
-    NonfiniteArgs a;
-    a.n = n_tensors - base < NF_MAX_T ? n_tensors - base : NF_MAX_T;
-    a.base = base;
-    long long most = 0;
-    for (int i = 0; i < a.n; ++i) {
-      a.x[i] = x_host[base + i]; a.numel[i] = (int)numel_host[base + i]; a.group[i] = group_host[base + i];
-      most = most > numel_host[base + i] ? most : numel_host[base + i];
-    }
-    int bx = (int)((most + 1023) / 1024);                            // one 16-byte load per thread for the largest tensor ...
-    bx = bx < 1 ? 1 : (bx > NF_SLOTS ? NF_SLOTS : bx);               // ... within 64 workgroups per tensor (grid-stride beyond)
-    hipLaunchKernelGGL(nonfinite_multi_kernel, dim3((unsigned)bx, (unsigned)a.n), dim3(256), 0, (hipStream_t)stream, a, (int*)slots_dev);
-    FST_LAUNCH_CHECK();
-  }
+  if (check_group_tensors("fst_nonfinite_multi", (const void* const*)x_host, numel_host, group_host, n_tensors)) return -1;
+  if (int rc = fst_multi_chunks(n_tensors, [&](int base, int n) {
+        GroupArgs a;
+        fill_group(a, (const void* const*)x_host, numel_host, group_host, base, n);
+        hipLaunchKernelGGL(nonfinite_multi_kernel, fst_multi_grid(numel_host + base, n), dim3(256), 0, (hipStream_t)stream, a, (int*)slots_dev);
+        FST_LAUNCH_CHECK();
+        return 0;
+      })) return rc;
   hipLaunchKernelGGL(nonfinite_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const int*)slots_dev, n_tensors,
                      (unsigned)verdict_mask, (int*)counts_dev, (int*)verdict_dev, ok_dev, (int*)skipped_dev);
   FST_LAUNCH_CHECK();
@@ -133,9 +166,9 @@ extern "C" int fst_nonfinite_multi(const float* const* x_host, const int64_t* nu
 }
 
 struct GuardCopyArgs {
-  uint32_t* dst[NF_MAX_T];
-  const uint32_t* src[NF_MAX_T];
-  int words[NF_MAX_T];
+  uint32_t* dst[FST_MULTI_T];
+  const uint32_t* src[FST_MULTI_T];
+  int words[FST_MULTI_T];
   int n;
 };
 static_assert(sizeof(GuardCopyArgs) + sizeof(const int*) + sizeof(int) <= 4096, "kernel arguments: 4 KB at most");
@@ -162,64 +195,46 @@ extern "C" int fst_guard_copy_multi(void* const* dst_host, const void* const* sr
                                     const int32_t* verdict_dev, int when, void* stream) {
   FST_REQUIRE(n_tensors >= 0 && (n_tensors == 0 || (dst_host && src_host && words_host)) && (when == 0 || when == 1),
               "fst_guard_copy_multi: bad arguments");
-  for (int i = 0; i < n_tensors; ++i) {                              // all of them before the first launch
-    FST_REQUIRE(dst_host[i] && src_host[i] && dst_host[i] != src_host[i] && (((uintptr_t)dst_host[i] | (uintptr_t)src_host[i]) & 3) == 0 &&
-                words_host[i] > 0 && words_host[i] < (1LL << 31),
+  for (int i = 0; i < n_tensors; ++i) {                              // all of them before the first launch; they may overlap
+    FST_REQUIRE(fst_multi_entry_ok({dst_host[i], src_host[i]}, words_host[i], 4) && dst_host[i] != src_host[i],
                 "fst_guard_copy_multi: tensor %d: null, equal or misaligned pointers, or bad word count", i);
   }
-  for (int base = 0; base < n_tensors; base += NF_MAX_T) {
+  return fst_multi_chunks(n_tensors, [&](int base, int n) {
     GuardCopyArgs a;
-    a.n = n_tensors - base < NF_MAX_T ? n_tensors - base : NF_MAX_T;
-    long long most = 0;
-    for (int i = 0; i < a.n; ++i) {
+    a.n = n;
+    for (int i = 0; i < n; ++i) {
       a.dst[i] = (uint32_t*)dst_host[base + i]; a.src[i] = (const uint32_t*)src_host[base + i]; a.words[i] = (int)words_host[base + i];
-      most = most > words_host[base + i] ? most : words_host[base + i];
     }
-    int bx = (int)((most + 1023) / 1024);
-    bx = bx < 1 ? 1 : (bx > NF_SLOTS ? NF_SLOTS : bx);
-    hipLaunchKernelGGL(guard_copy_multi_kernel, dim3((unsigned)bx, (unsigned)a.n), dim3(256), 0, (hipStream_t)stream, a,
+    hipLaunchKernelGGL(guard_copy_multi_kernel, fst_multi_grid(words_host + base, n), dim3(256), 0, (hipStream_t)stream, a,
                        (const int*)verdict_dev, when);
     FST_LAUNCH_CHECK();
-  }
-  return 0;
+    return 0;
+  });
 }
 
 // ---- gradient norms and clipping: the scan's walk with x*x in place of the count, and the scale that applies what it decided.
 // The slot array has the scan's layout in fp32: per tensor NF_REC words, its group id (as a float: exact below 32), then the
-// partial sums of its up to NF_SLOTS workgroups.  No float atomics: a thread adds its elements in one fma chain in index order, a
+// partial sums of its up to FST_MULTI_WG workgroups.  No float atomics: a thread adds its elements in one fma chain in index order, a
 // wave adds its lanes in a xor butterfly (commutative adds: every lane ends with the same word), lane 0 of wave 0 adds the four
 // wave sums as (0 + 1) + (2 + 3); the finaliser adds in fp64 in a fixed order.  Same inputs, same words.
-#define GC_GROUPS 32                // groups; norms and limits carry one more word, the total
+struct SumsqOp {
+  static constexpr bool writes = false;
+  float s;
+  __device__ __forceinline__ void operator()(float e) { s = __builtin_fmaf(e, e, s); }
+};
 
-__global__ __launch_bounds__(256) void sumsq_multi_kernel(NonfiniteArgs a, float* __restrict__ slots) {
+__global__ __launch_bounds__(256) void sumsq_multi_kernel(GroupArgs a, float* __restrict__ slots) {
   const int t = blockIdx.y;
   if (t >= a.n) return;
-  const float* __restrict__ x = a.x[t];
-  const int n = a.numel[t];
-  int head = (int)(((16u - (unsigned)((uintptr_t)x & 15u)) & 15u) >> 2);
-  head = head < n ? head : n;
-  const int nv = (n - head) >> 2;
-  const int tail0 = head + 4 * nv;
-  const float4* __restrict__ xv = (const float4*)(x + head);
-  float s = 0.0f;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < nv; i += gridDim.x * 256) {
-    const float4 q = xv[i];
-    s = __builtin_fmaf(q.x, q.x, s); s = __builtin_fmaf(q.y, q.y, s); s = __builtin_fmaf(q.z, q.z, s); s = __builtin_fmaf(q.w, q.w, s);
-  }
-  if (blockIdx.x == 0) {
-    if ((int)threadIdx.x < head) s = __builtin_fmaf(x[threadIdx.x], x[threadIdx.x], s);
-    if ((int)threadIdx.x < n - tail0) s = __builtin_fmaf(x[tail0 + threadIdx.x], x[tail0 + threadIdx.x], s);
-  }
+  SumsqOp op{0.0f};
+  quad_walk(a.x[t], a.numel[t], op);
+  float s = op.s;
   for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
   __shared__ float wave_sum[4];
   if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = s;
   __syncthreads();
-  if (threadIdx.x == 0) {
-    float* rec = slots + (size_t)(a.base + t) * NF_REC;
-    if (blockIdx.x == 0) rec[0] = (float)a.group[t];
-    rec[1 + blockIdx.x] = (wave_sum[0] + wave_sum[1]) + (wave_sum[2] + wave_sum[3]);
-    for (int k = blockIdx.x + gridDim.x; k < NF_SLOTS; k += gridDim.x) rec[1 + k] = 0.0f;   // slots no workgroup of this launch owns
-  }
+  if (threadIdx.x == 0)
+    slot_record(slots + (size_t)(a.base + t) * NF_REC, a.group[t], (wave_sum[0] + wave_sum[1]) + (wave_sum[2] + wave_sum[3]));
 }
 
 // one workgroup.  A tensor's slots are added in slot order and a group's tensors in tensor order, all in fp64 (256 tensors at a
@@ -238,7 +253,7 @@ __global__ __launch_bounds__(256) void sumsq_finalize_kernel(const float* __rest
     if (i < n_tensors) {
       const float* rec = slots + (size_t)i * NF_REC;
       double s = 0.0;
-      for (int k = 0; k < NF_SLOTS; ++k) s += (double)rec[1 + k];
+      for (int k = 0; k < FST_MULTI_WG; ++k) s += (double)rec[1 + k];
       tsum[threadIdx.x] = s;
       tgroup[threadIdx.x] = (int)rec[0] & (GC_GROUPS - 1);
     }
@@ -274,24 +289,6 @@ __global__ __launch_bounds__(256) void sumsq_finalize_kernel(const float* __rest
   for (int g = 0; g < GC_GROUPS; ++g) coef[g] = bad ? 1.0f : (float)(cg[g] * c);
 }
 
-static int check_group_tensors(const char* who, const void* const* x_host, const int64_t* numel_host, const int32_t* group_host, int n_tensors) {
-  FST_REQUIRE(n_tensors >= 0 && n_tensors < (1 << 24) && (n_tensors == 0 || (x_host && numel_host && group_host)), "%s: bad arguments", who);
-  for (int i = 0; i < n_tensors; ++i) {                              // all of them before the first launch
-    FST_REQUIRE(x_host[i] && ((uintptr_t)x_host[i] & 3) == 0 && numel_host[i] > 0 && numel_host[i] < (1LL << 31),
-                "%s: tensor %d: null or misaligned pointer, or bad element count", who, i);
-    FST_REQUIRE(group_host[i] >= 0 && group_host[i] < GC_GROUPS, "%s: tensor %d: group %d is not in 0..31", who, i, group_host[i]);
-  }
-  return 0;
-}
-
-// workgroups per tensor of a launch: one 16-byte access per thread for its largest tensor, within NF_SLOTS (grid-stride beyond)
-static int group_launch_bx(const int64_t* numel_host, int n) {
-  long long most = 0;
-  for (int i = 0; i < n; ++i) most = most > numel_host[i] ? most : numel_host[i];
-  const int bx = (int)((most + 1023) / 1024);
-  return bx < 1 ? 1 : (bx > NF_SLOTS ? NF_SLOTS : bx);
-}
-
 extern "C" int64_t fst_sumsq_slots(int n_tensors) { return fst_nonfinite_slots(n_tensors); }
 
 extern "C" int fst_sumsq_multi(const float* const* x_host, const int64_t* numel_host, const int32_t* group_host, int n_tensors,
@@ -303,67 +300,46 @@ extern "C" int fst_sumsq_multi(const float* const* x_host, const int64_t* numel_
               "fst_sumsq_multi: null or misaligned limits, norms, coefficients or slots");
   FST_REQUIRE(slots_len >= fst_sumsq_slots(n_tensors), "fst_sumsq_multi: %lld slots, %lld needed", (long long)slots_len,
               (long long)fst_sumsq_slots(n_tensors));
-  for (int base = 0; base < n_tensors; base += NF_MAX_T) {
-    NonfiniteArgs a;
-    a.n = n_tensors - base < NF_MAX_T ? n_tensors - base : NF_MAX_T;
-    a.base = base;
-    for (int i = 0; i < a.n; ++i) { a.x[i] = x_host[base + i]; a.numel[i] = (int)numel_host[base + i]; a.group[i] = group_host[base + i]; }
-    hipLaunchKernelGGL(sumsq_multi_kernel, dim3((unsigned)group_launch_bx(numel_host + base, a.n), (unsigned)a.n), dim3(256), 0,
-                       (hipStream_t)stream, a, slots_dev);
-    FST_LAUNCH_CHECK();
-  }
+  if (int rc = fst_multi_chunks(n_tensors, [&](int base, int n) {
+        GroupArgs a;
+        fill_group(a, (const void* const*)x_host, numel_host, group_host, base, n);
+        hipLaunchKernelGGL(sumsq_multi_kernel, fst_multi_grid(numel_host + base, n), dim3(256), 0, (hipStream_t)stream, a, slots_dev);
+        FST_LAUNCH_CHECK();
+        return 0;
+      })) return rc;
   hipLaunchKernelGGL(sumsq_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)slots_dev, n_tensors, limits_dev,
                      norms_dev, coef_dev);
   FST_LAUNCH_CHECK();
   return 0;
 }
 
-struct ScaleArgs {
-  float* x[NF_MAX_T];
-  int numel[NF_MAX_T];
-  int group[NF_MAX_T];
-  int n;
+struct ScaleOp {
+  static constexpr bool writes = true;
+  float c;
+  __device__ __forceinline__ void operator()(float& e) const { e *= c; }
 };
-static_assert(sizeof(ScaleArgs) + sizeof(const float*) <= 4096, "kernel arguments: 4 KB at most");
 
 // the scan's geometry, writing: coef[group] is one uniform load per workgroup, and a workgroup whose factor is exactly 1.0f
 // returns before its first load of x — an unclipped step keeps its gradients' bits and pays no memory pass here
-__global__ __launch_bounds__(256) void scale_multi_kernel(ScaleArgs a, const float* __restrict__ coef) {
+__global__ __launch_bounds__(256) void scale_multi_kernel(GroupArgs a, const float* __restrict__ coef) {
   const int t = blockIdx.y;
   if (t >= a.n) return;
-  const float c = coef[a.group[t]];
-  if (c == 1.0f) return;
-  float* __restrict__ x = a.x[t];
-  const int n = a.numel[t];
-  int head = (int)(((16u - (unsigned)((uintptr_t)x & 15u)) & 15u) >> 2);
-  head = head < n ? head : n;
-  const int nv = (n - head) >> 2;
-  const int tail0 = head + 4 * nv;
-  float4* __restrict__ xv = (float4*)(x + head);
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < nv; i += gridDim.x * 256) {
-    float4 q = xv[i];
-    q.x *= c; q.y *= c; q.z *= c; q.w *= c;
-    xv[i] = q;
-  }
-  if (blockIdx.x == 0) {
-    if ((int)threadIdx.x < head) x[threadIdx.x] *= c;
-    if ((int)threadIdx.x < n - tail0) x[tail0 + threadIdx.x] *= c;
-  }
+  ScaleOp op{coef[a.group[t]]};
+  if (op.c == 1.0f) return;
+  quad_walk(a.x[t], a.numel[t], op);
 }
 
 extern "C" int fst_scale_multi(float* const* x_host, const int64_t* numel_host, const int32_t* group_host, int n_tensors,
                                const float* coef_dev, void* stream) {
   if (check_group_tensors("fst_scale_multi", (const void* const*)x_host, numel_host, group_host, n_tensors)) return -1;
   FST_REQUIRE(coef_dev && ((uintptr_t)coef_dev & 3) == 0, "fst_scale_multi: null or misaligned coefficients");
-  for (int base = 0; base < n_tensors; base += NF_MAX_T) {
-    ScaleArgs a;
-    a.n = n_tensors - base < NF_MAX_T ? n_tensors - base : NF_MAX_T;
-    for (int i = 0; i < a.n; ++i) { a.x[i] = x_host[base + i]; a.numel[i] = (int)numel_host[base + i]; a.group[i] = group_host[base + i]; }
-    hipLaunchKernelGGL(scale_multi_kernel, dim3((unsigned)group_launch_bx(numel_host + base, a.n), (unsigned)a.n), dim3(256), 0,
-                       (hipStream_t)stream, a, coef_dev);
+  return fst_multi_chunks(n_tensors, [&](int base, int n) {
+    GroupArgs a;
+    fill_group(a, (const void* const*)x_host, numel_host, group_host, base, n);
+    hipLaunchKernelGGL(scale_multi_kernel, fst_multi_grid(numel_host + base, n), dim3(256), 0, (hipStream_t)stream, a, coef_dev);
     FST_LAUNCH_CHECK();
-  }
-  return 0;
+    return 0;
+  });
 }
 
 // ---- weight averaging (EMA) and the in-place exchange that puts the averages into the modules' own storage.  Both walk PAIRS of
@@ -379,10 +355,10 @@ extern "C" int fst_scale_multi(float* const* x_host, const int64_t* numel_host, 
 #define EMA_WORDS (2 + 2 * EMA_GROUPS)
 
 struct PairArgs {
-  float* a[NF_MAX_T];
-  float* b[NF_MAX_T];
-  int numel[NF_MAX_T];
-  int group[NF_MAX_T];
+  float* a[FST_MULTI_T];
+  float* b[FST_MULTI_T];
+  int numel[FST_MULTI_T];
+  int group[FST_MULTI_T];
   int n;
 };
 static_assert(sizeof(PairArgs) + sizeof(const float*) <= 4096, "kernel arguments: 4 KB at most");
@@ -478,8 +454,8 @@ static int check_pairs(const char* who, float* const* a_host, float* const* b_ho
                        int n_tensors) {
   FST_REQUIRE(n_tensors >= 0 && n_tensors < (1 << 24) && (n_tensors == 0 || (a_host && b_host && numel_host)), "%s: bad arguments", who);
   for (int i = 0; i < n_tensors; ++i) {
-    FST_REQUIRE(a_host[i] && b_host[i] && (((uintptr_t)a_host[i] | (uintptr_t)b_host[i]) & 3) == 0 && numel_host[i] > 0 &&
-                numel_host[i] < (1LL << 31), "%s: tensor %d: null or misaligned pointer, or bad element count", who, i);
+    FST_REQUIRE(fst_multi_entry_ok({a_host[i], b_host[i]}, numel_host[i], 4), "%s: tensor %d: null or misaligned pointer, or bad element count",
+                who, i);
     FST_REQUIRE(!group_host || (group_host[i] >= 0 && group_host[i] < EMA_GROUPS), "%s: tensor %d: group %d is not in 0..31", who, i,
                 group_host ? group_host[i] : 0);
     const uintptr_t a = (uintptr_t)a_host[i], b = (uintptr_t)b_host[i], bytes = (uintptr_t)numel_host[i] * 4;
@@ -489,9 +465,9 @@ static int check_pairs(const char* who, float* const* a_host, float* const* b_ho
 }
 
 static void fill_pairs(PairArgs& a, float* const* a_host, float* const* b_host, const int64_t* numel_host, const int32_t* group_host,
-                       int base, int n_tensors) {
-  a.n = n_tensors - base < NF_MAX_T ? n_tensors - base : NF_MAX_T;
-  for (int i = 0; i < a.n; ++i) {
+                       int base, int n) {
+  a.n = n;
+  for (int i = 0; i < n; ++i) {
     a.a[i] = a_host[base + i]; a.b[i] = b_host[base + i]; a.numel[i] = (int)numel_host[base + i];
     a.group[i] = group_host ? group_host[base + i] : 0;
   }
@@ -505,26 +481,25 @@ extern "C" int fst_ema_multi(float* const* avg_host, const float* const* live_ho
   float* state = (float*)state_dev;
   hipLaunchKernelGGL(ema_weights_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (uint32_t)active_mask, state, (const int*)verdict_dev);
   FST_LAUNCH_CHECK();
-  for (int base = 0; base < n_tensors; base += NF_MAX_T) {
+  return fst_multi_chunks(n_tensors, [&](int base, int n) {
     PairArgs a;
-    fill_pairs(a, avg_host, (float* const*)live_host, numel_host, group_host, base, n_tensors);
-    hipLaunchKernelGGL(ema_multi_kernel, dim3((unsigned)group_launch_bx(numel_host + base, a.n), (unsigned)a.n), dim3(256), 0,
-                       (hipStream_t)stream, a, (const float*)(state + EMA_W));
+    fill_pairs(a, avg_host, (float* const*)live_host, numel_host, group_host, base, n);
+    hipLaunchKernelGGL(ema_multi_kernel, fst_multi_grid(numel_host + base, n), dim3(256), 0, (hipStream_t)stream, a,
+                       (const float*)(state + EMA_W));
     FST_LAUNCH_CHECK();
-  }
-  return 0;
+    return 0;
+  });
 }
 
 extern "C" int fst_swap_multi(float* const* a_host, float* const* b_host, const int64_t* numel_host, int n_tensors, void* stream) {
   if (check_pairs("fst_swap_multi", a_host, b_host, numel_host, nullptr, n_tensors)) return -1;
-  for (int base = 0; base < n_tensors; base += NF_MAX_T) {
+  return fst_multi_chunks(n_tensors, [&](int base, int n) {
     PairArgs a;
-    fill_pairs(a, a_host, b_host, numel_host, nullptr, base, n_tensors);
-    hipLaunchKernelGGL(swap_multi_kernel, dim3((unsigned)group_launch_bx(numel_host + base, a.n), (unsigned)a.n), dim3(256), 0,
-                       (hipStream_t)stream, a);
+    fill_pairs(a, a_host, b_host, numel_host, nullptr, base, n);
+    hipLaunchKernelGGL(swap_multi_kernel, fst_multi_grid(numel_host + base, n), dim3(256), 0, (hipStream_t)stream, a);
     FST_LAUNCH_CHECK();
-  }
-  return 0;
+    return 0;
+  });
 }
 
 // ---- gradient accumulation: a window of k calls folds k gradients into one mean, the position in the window a device word, so
@@ -575,13 +550,14 @@ extern "C" int fst_accum_multi(float* const* acc_host, float* const* g_host, con
                                int advance, void* stream) {
   if (check_pairs("fst_accum_multi", acc_host, g_host, numel_host, nullptr, n_tensors)) return -1;
   FST_REQUIRE(state_dev && ((uintptr_t)state_dev & 15) == 0, "fst_accum_multi: null state block, or one off a 16-byte boundary");
-  for (int base = 0; base < n_tensors; base += NF_MAX_T) {
-    PairArgs a;
-    fill_pairs(a, acc_host, g_host, numel_host, nullptr, base, n_tensors);
-    hipLaunchKernelGGL(accum_multi_kernel, dim3((unsigned)group_launch_bx(numel_host + base, a.n), (unsigned)a.n), dim3(256), 0,
-                       (hipStream_t)stream, a, (const int*)state_dev);
-    FST_LAUNCH_CHECK();
-  }
+  if (int rc = fst_multi_chunks(n_tensors, [&](int base, int n) {
+        PairArgs a;
+        fill_pairs(a, acc_host, g_host, numel_host, nullptr, base, n);
+        hipLaunchKernelGGL(accum_multi_kernel, fst_multi_grid(numel_host + base, n), dim3(256), 0, (hipStream_t)stream, a,
+                           (const int*)state_dev);
+        FST_LAUNCH_CHECK();
+        return 0;
+      })) return rc;
   if (advance) {
     hipLaunchKernelGGL(accum_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (int*)state_dev);
     FST_LAUNCH_CHECK();

@@ -130,38 +130,28 @@ class SharedStepAdam(_DeviceLR, torch.optim.Optimizer):
             ps = [p for p in group["params"] if p.grad is not None]
             if not ps:
                 continue
-            if ps[0].is_cuda:
-                # one single-pass multi-tensor launch per 64 tensors (csrc/optim.hip) instead of eleven foreach passes
-                from . import _lib
-                lib = _lib.load()
-                t = group["step"]
-                t += 1 if guard is None else guard.ok
-                grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in ps]
-                m = [self.state[p]["exp_avg"] for p in ps]
-                v = [self.state[p]["exp_avg_sq"] for p in ps]
-                b1, b2 = group["betas"]
-                if guard is not None:
-                    _lib.check(lib.fst_adam_multi_guard(_ptr_array(ps), _ptr_array(grads), _ptr_array(m), _ptr_array(v),
-                                                        _i64_array([p.numel() for p in ps]), len(ps), t.data_ptr(), group["lr"],
-                                                        self.lr_dev[gi].data_ptr() if self.lr_on_device else None, b1, b2,
-                                                        group["eps"], guard.verdict.data_ptr(), _lib.stream_ptr()),
-                               "fst_adam_multi_guard")
-                    continue
-                if self.lr_on_device:
-                    _lib.check(lib.fst_adam_multi_dev(_ptr_array(ps), _ptr_array(grads), _ptr_array(m), _ptr_array(v),
-                                                      _i64_array([p.numel() for p in ps]), len(ps), t.data_ptr(),
-                                                      self.lr_dev[gi].data_ptr(), b1, b2, group["eps"], _lib.stream_ptr()),
-                               "fst_adam_multi_dev")
-                    continue
-                _lib.check(lib.fst_adam_multi(_ptr_array(ps), _ptr_array(grads), _ptr_array(m), _ptr_array(v),
-                                              _i64_array([p.numel() for p in ps]), len(ps), t.data_ptr(), group["lr"], b1, b2,
-                                              group["eps"], _lib.stream_ptr()), "fst_adam_multi")
-                continue
-            grads = [p.grad for p in ps]
             m = [self.state[p]["exp_avg"] for p in ps]
             v = [self.state[p]["exp_avg_sq"] for p in ps]
             b1, b2 = group["betas"]
             t = group["step"]
+            if ps[0].is_cuda:
+                # one single-pass multi-tensor launch per 64 tensors (csrc/optim.hip) instead of eleven foreach passes
+                from . import _lib
+                lib = _lib.load()
+                t += 1 if guard is None else guard.ok
+                grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in ps]
+                lr_dev = self.lr_dev[gi].data_ptr() if self.lr_on_device else None
+                if guard is not None:                                           # either rate form: lr_dev is None or not
+                    name, rate, verdict = "fst_adam_multi_guard", (group["lr"], lr_dev), (guard.verdict.data_ptr(),)
+                elif self.lr_on_device:
+                    name, rate, verdict = "fst_adam_multi_dev", (lr_dev,), ()
+                else:
+                    name, rate, verdict = "fst_adam_multi", (group["lr"],), ()
+                _lib.check(getattr(lib, name)(_ptr_array(ps), _ptr_array(grads), _ptr_array(m), _ptr_array(v),
+                                              _i64_array([p.numel() for p in ps]), len(ps), t.data_ptr(), *rate, b1, b2, group["eps"],
+                                              *verdict, _lib.stream_ptr()), name)
+                continue
+            grads = [p.grad for p in ps]
             if guard is not None:                                               # CPU: the unguarded arithmetic on copies, kept where ok
                 old = [t.clone()] + [x.detach().clone() for x in list(ps) + m + v]
             t += 1
@@ -191,6 +181,15 @@ def _ptr_array(tensors: Sequence[torch.Tensor]):
 
 def _i64_array(values: Sequence[int]):
     return (ctypes.c_int64 * len(values))(*values)
+
+
+def _i32_array(values: Sequence[int]):
+    return (ctypes.c_int32 * len(values))(*values)
+
+
+def _mask_i32(mask: int) -> int:
+    """A mask of 32 group bits as the int32 the C ABI takes it in."""
+    return mask - (1 << 32) if mask >> 31 else mask
 
 
 class FusedRMSprop(_DeviceLR, torch.optim.Optimizer):
@@ -271,18 +270,13 @@ def _rmsprop_launch(opts: Sequence[FusedRMSprop], on_device: bool, guard: Option
     from . import _lib
     lib = _lib.load()
     assert all(p.is_contiguous() for p in ps)
-    if guard is not None:
-        _lib.check(lib.fst_rmsprop_multi_guard(_ptr_array(ps), _ptr_array(grads), _ptr_array(vs), _i64_array([p.numel() for p in ps]),
-                                               None if on_device else (ctypes.c_float * len(lrs))(*lrs),
-                                               _ptr_array(lrs) if on_device else None, len(ps), alpha, eps,
-                                               guard.verdict.data_ptr(), _lib.stream_ptr()), "fst_rmsprop_multi_guard")
-        return
-    if on_device:
-        _lib.check(lib.fst_rmsprop_multi_dev(_ptr_array(ps), _ptr_array(grads), _ptr_array(vs), _i64_array([p.numel() for p in ps]),
-                                             _ptr_array(lrs), len(ps), alpha, eps, _lib.stream_ptr()), "fst_rmsprop_multi_dev")
-        return
-    _lib.check(lib.fst_rmsprop_multi(_ptr_array(ps), _ptr_array(grads), _ptr_array(vs), _i64_array([p.numel() for p in ps]),
-                                     (ctypes.c_float * len(lrs))(*lrs), len(ps), alpha, eps, _lib.stream_ptr()), "fst_rmsprop_multi")
+    rates = _ptr_array(lrs) if on_device else (ctypes.c_float * len(lrs))(*lrs)
+    if guard is not None:                                                     # either rate form: by value, or by address
+        name, rate, verdict = "fst_rmsprop_multi_guard", ((None, rates) if on_device else (rates, None)), (guard.verdict.data_ptr(),)
+    else:
+        name, rate, verdict = ("fst_rmsprop_multi_dev" if on_device else "fst_rmsprop_multi"), (rates,), ()
+    _lib.check(getattr(lib, name)(_ptr_array(ps), _ptr_array(grads), _ptr_array(vs), _i64_array([p.numel() for p in ps]), *rate,
+                                  len(ps), alpha, eps, *verdict, _lib.stream_ptr()), name)
 
 
 # ---- anomaly guard: a device-side verdict on the values a step's update consumes
@@ -350,8 +344,8 @@ def count_nonfinite(tensors: Sequence[torch.Tensor], groups: Sequence[int], n_gr
     else:
         counts, slots = guard.counts, guard.slots(n_slots)
         words = (guard.verdict.data_ptr(), guard.ok.data_ptr(), guard.skipped.data_ptr())
-    _lib.check(lib.fst_nonfinite_multi(_ptr_array(xs), _i64_array([x.numel() for x in xs]), (ctypes.c_int32 * len(xs))(*[g for _, g in keep]),
-                                       len(xs), mask - (1 << 32) if mask >> 31 else mask, slots.data_ptr(), slots.numel(), counts.data_ptr(), *words, _lib.stream_ptr()),
+    _lib.check(lib.fst_nonfinite_multi(_ptr_array(xs), _i64_array([x.numel() for x in xs]), _i32_array([g for _, g in keep]), len(xs),
+                                       _mask_i32(mask), slots.data_ptr(), slots.numel(), counts.data_ptr(), *words, _lib.stream_ptr()),
                "fst_nonfinite_multi")
     return counts[:n_groups]
 
@@ -485,8 +479,7 @@ def sumsq_norms(tensors: Sequence[torch.Tensor], groups: Sequence[int], limits: 
         slots = torch.empty(max(n_slots, 1), dtype=torch.float32, device=out_norms.device)
     _words("sumsq_norms", "slots", slots, n_slots)
     xs = [t for t, _ in keep]
-    _lib.check(lib.fst_sumsq_multi(_ptr_array(xs), _i64_array([x.numel() for x in xs]), (ctypes.c_int32 * len(xs))(*[g for _, g in keep]),
-                                   len(xs), slots.data_ptr(), slots.numel(), limits.data_ptr(), out_norms.data_ptr(),
+    _lib.check(lib.fst_sumsq_multi(_ptr_array(xs), _i64_array([x.numel() for x in xs]), _i32_array([g for _, g in keep]), len(xs), slots.data_ptr(), slots.numel(), limits.data_ptr(), out_norms.data_ptr(),
                                    out_coef.data_ptr(), _lib.stream_ptr()), "fst_sumsq_multi")
 
 
@@ -503,9 +496,8 @@ def scale_by_group(tensors: Sequence[torch.Tensor], groups: Sequence[int], coef:
         return
     from . import _lib
     xs = [t for t, _ in keep]
-    _lib.check(_lib.load().fst_scale_multi(_ptr_array(xs), _i64_array([x.numel() for x in xs]),
-                                           (ctypes.c_int32 * len(xs))(*[g for _, g in keep]), len(xs), coef.data_ptr(),
-                                           _lib.stream_ptr()), "fst_scale_multi")
+    _lib.check(_lib.load().fst_scale_multi(_ptr_array(xs), _i64_array([x.numel() for x in xs]), _i32_array([g for _, g in keep]),
+                                           len(xs), coef.data_ptr(), _lib.stream_ptr()), "fst_scale_multi")
 
 
 # ---- weight averaging: an exponential moving average of the weights, kept and steered on the device
@@ -612,8 +604,8 @@ def ema_update(avg: Sequence[torch.Tensor], live: Sequence[torch.Tensor], groups
     for i, (a, l, _) in enumerate(keep):
         _lib.require_gpu_tensor(a, f"ema_update: avg {i}"); _lib.require_gpu_tensor(l, f"ema_update: live {i}")
     _lib.check(_lib.load().fst_ema_multi(_ptr_array([a for a, _, _ in keep]), _ptr_array([l for _, l, _ in keep]),
-                                         _i64_array([a.numel() for a, _, _ in keep]), (ctypes.c_int32 * len(keep))(*[g for _, _, g in keep]),
-                                         len(keep), mask - (1 << 32) if mask >> 31 else mask, state.words.data_ptr(), None if guard is None else guard.verdict.data_ptr(),
+                                         _i64_array([a.numel() for a, _, _ in keep]), _i32_array([g for _, _, g in keep]), len(keep),
+                                         _mask_i32(mask), state.words.data_ptr(), None if guard is None else guard.verdict.data_ptr(),
                                          _lib.stream_ptr()), "fst_ema_multi")
 
 
