@@ -56,10 +56,84 @@ __host__ __device__ __forceinline__ void wn_stage_chunk_tap(int k, int CH, int& 
 }
 
 // ------------------------------------------------------------------------------------------------
-// weight image
+// weight images: four formats (forward here; backward, projected backward and data gradient beside their kernels), each a run of
+// 2 KiB blocks = 64 lanes × 8 bf16 hi then 64 lanes × 8 bf16 lo, the A fragments of the 32x32x16 bf16 MFMA (lane l: row l&31 of
+// the block, k = 8·(l>>5) + j), then 16 B of zeros (forward: and 16 B of ones) that the consumers' LDS-DMA reads for whatever lies
+// outside a tensor.  Where an image ends — its size, its pack grid, its tail and every consumer's zero16 — is one function per format:
+// ------------------------------------------------------------------------------------------------
+__host__ __device__ static inline int wn_ch(int n) { return (n + 15) / 16; }
+__host__ __device__ static inline int wn_ch2(int h) { return (h + 1 + 15) / 16; }
+__host__ __device__ static inline int wn_fwd_stages(int CH, int CH2) { return 3 * CH + CH2 + 8; }                         // of 8 blocks
+__host__ __device__ static inline int wn_bwd_stages(int CH, int last) { return (last ? 1 : 2) * CH; }                     // of 4 blocks
+__host__ __device__ static inline int wn_bwd_proj_stages(int CH, int CHO, int last) { return (last ? 0 : CH) + CHO; }     // of 4 blocks
+__host__ __device__ static inline int wn_dgrad_chunks(int n) { return (2 * n + 15) / 16; }                                // of 13 blocks
+
+// one block of an image: lane `lane`'s eight values as four hi and four lo bf16 pairs
+__device__ __forceinline__ void wn_store_frag(uint4* img, long long block, int lane, const float (&v)[8]) {
+  unsigned hi[4], lo[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) split_bf16_pair(v[2 * j], v[2 * j + 1], hi[j], lo[j]);
+  uint4* dst = img + block * 128 + lane;
+  dst[0] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
+  dst[64] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+}
+// the constants behind an image's n_blocks blocks, written by workgroup 0 of its pack
+template <bool ONES>
+__device__ __forceinline__ void wn_store_tail(uint4* img, long long n_blocks, int bx, int lane) {
+  if (bx == 0 && lane < (ONES ? 2 : 1)) {
+    const unsigned w = lane ? 0x3f800000u : 0u;
+    img[n_blocks * 128 + lane] = make_uint4(w, w, w, w);
+  }
+}
+
+// The arguments of a pack kernel: layer blockIdx.y of up to WS_MAXL layers, NSRC source tensors each; a format's scalars ride beside
+// the table.  ML = the table's capacity: WS_MAXL for a stack entry point, 1 for a per-layer one (the same kernel, instantiated for a
+// table of one: a per-layer call measured 0.2-0.4 us dearer with 568 bytes of arguments than with 64).
+template <int NSRC, int ML = WS_MAXL>
+struct WnPackTable {
+  const float* src[NSRC][ML];
+  uint4* img[ML];
+  int nl, last_layer;   // the layer packed as `last` (a stack's top layer: nl - 1), or -1 for none
+};
+static_assert(sizeof(WnPackTable<6>) + 64 <= 4096, "kernel arguments: the largest pack table and its scalars");
+
+// who; kernel; src[j][i] = source j of layer i; image_bytes against `expected`; blocks[l]: workgroups of a layer packed with
+// last = l.  The grid is (the most blocks of any layer, nl): a kernel leaves early in a layer with fewer.  mid(): the entry point's
+// own tests that sit between the layer count and the image size.
+template <int NSRC, int ML, class Mid, class... S>
+static int wn_pack_launch(const char* who, void (*kernel)(WnPackTable<NSRC, ML>, S...), const float* const* const (&src)[NSRC],
+                          int nl, int last_layer, void* const* images, int64_t image_bytes, int64_t expected, const int (&blocks)[2],
+                          Mid mid, void* stream, S... scalars) {
+  constexpr bool stack = ML > 1;                     // the entry point takes tables, and its messages say so
+  bool tables = images != nullptr;
+  for (int j = 0; j < NSRC; ++j) tables = tables && src[j];
+  FST_REQUIRE(tables, "%s: null table", who);
+  FST_REQUIRE(nl >= 1 && nl <= ML, "%s: %d layers (1..%d)", who, nl, ML);
+  if (int rc = mid()) return rc;
+  FST_REQUIRE(image_bytes == expected, "%s: %s %lld bytes, expected %lld", who, stack ? "images are" : "image is",
+              (long long)image_bytes, (long long)expected);
+  WnPackTable<NSRC, ML> t = {};
+  int grid_x = 0;
+  for (int i = 0; i < nl; ++i) {
+    bool operands = images[i] != nullptr;
+    for (int j = 0; j < NSRC; ++j) operands = operands && src[j][i];
+    FST_REQUIRE(operands, "%s: null operand in layer %d", who, i);
+    FST_REQUIRE(fst_aligned16(images[i]), "%s: %s must be 16-byte aligned", who, stack ? "images" : "image");
+    for (int j = 0; j < NSRC; ++j) t.src[j][i] = src[j][i];
+    t.img[i] = static_cast<uint4*>(images[i]);
+    grid_x = blocks[i == last_layer] > grid_x ? blocks[i == last_layer] : grid_x;
+  }
+  t.nl = nl; t.last_layer = last_layer;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid_x, (unsigned)nl), dim3(64), 0, (hipStream_t)stream, t, scalars...);
+  FST_LAUNCH_CHECK();
+  return 0;
+}
+static inline int wn_no_tests() { return 0; }
+
+// ------------------------------------------------------------------------------------------------
+// forward weight image
 //   [S1 stages of GEMM 1][8 k-steps of GEMM 2][16 B of zeros][16 B of ones]
-// one stage / k-step = 8 row blocks × (64 lanes × 8 bf16 hi, 64 lanes × 8 bf16 lo) = 16 KiB, the A fragments of
-// the 32x32x16 bf16 MFMA (lane l: row l&31 of the block, k = 8·(l>>5) + j).
+// one stage / k-step = 8 row blocks = 16 KiB.
 //   GEMM 1  stage k < 3·CH = (chunk c < CH = ⌈n/16⌉, tap) in wn_stage_chunk_tap order: channels 16c.. of `a` at tap `tap`;
 //           then CH2 = ⌈(h+1)/16⌉ stages
 //           of the conditioning input (zero shift) whose channel h is the constant-one row carrying b_in + b_cond.
@@ -68,21 +142,14 @@ __host__ __device__ __forceinline__ void wn_stage_chunk_tap(int k, int CH, int& 
 //           (the order in which an accumulator tile delivers its rows as a B operand); k = n carries b_rs.
 //           rows: blocks 0-3 = residual rows (→ a_next), blocks 4-7 = skip rows (→ out); last layer: only skip rows.
 // ------------------------------------------------------------------------------------------------
-struct WnPackParams {
-  const float* in_w;    // [2n][n][3]
-  const float* cond_w;  // [2n][h]
-  const float* in_b;    // [2n]
-  const float* cond_b;  // [2n]
-  const float* rs_w;    // [2n][n]  (last: [n][n])
-  const float* rs_b;    // [2n]     (last: [n])
-  int n, h, last, CH, CH2;
-  uint4* img;
-};
-
-// workgroup bx of one layer's pack (64 lanes): row block bx & 7 of stage bx >> 3
-__device__ __forceinline__ void wn_pack_body(const WnPackParams& p, int bx) {
+// sources: in_w [2n][n][3], cond_w [2n][h], in_b [2n], cond_b [2n], rs_w [2n][n] (last: [n][n]), rs_b [2n] (last: [n]).
+// Workgroup blockIdx.x of layer blockIdx.y (64 lanes): row block bx & 7 of stage bx >> 3.
+template <int ML>
+__global__ __launch_bounds__(64) void wn_pack_kernel(WnPackTable<6, ML> t, int n, int h) {
+  const int i = blockIdx.y, bx = blockIdx.x, last = i == t.last_layer;
+  const float *in_w = t.src[0][i], *cond_w = t.src[1][i], *in_b = t.src[2][i], *cond_b = t.src[3][i], *rs_w = t.src[4][i], *rs_b = t.src[5][i];
   const int lane = threadIdx.x, blk = bx & 7, st = bx >> 3;
-  const int S1 = 3 * p.CH + p.CH2, n = p.n, h = p.h;
+  const int CH = wn_ch(n), CH2 = wn_ch2(h), S1 = 3 * CH + CH2;
   const int hh = lane >> 5, rowb = (blk & 3) * 32 + (lane & 31);
   const bool row_ok = rowb < n;
   float v[8];
@@ -92,15 +159,15 @@ __device__ __forceinline__ void wn_pack_body(const WnPackParams& p, int bx) {
     for (int j = 0; j < 8; ++j) {
       float w = 0.f;
       if (row_ok) {
-        if (st < 3 * p.CH) {
+        if (st < 3 * CH) {
           int cc, tap;
-          wn_stage_chunk_tap(st, p.CH, cc, tap);
+          wn_stage_chunk_tap(st, CH, cc, tap);
           const int c = cc * 16 + 8 * hh + j;
-          if (c < n) w = p.in_w[((long long)row * n + c) * 3 + tap];
+          if (c < n) w = in_w[((long long)row * n + c) * 3 + tap];
         } else {
-          const int c = (st - 3 * p.CH) * 16 + 8 * hh + j;
-          if (c < h) w = p.cond_w[(long long)row * h + c];
-          else if (c == h) w = p.in_b[row] + p.cond_b[row];
+          const int c = (st - 3 * CH) * 16 + 8 * hh + j;
+          if (c < h) w = cond_w[(long long)row * h + c];
+          else if (c == h) w = in_b[row] + cond_b[row];
         }
       }
       v[j] = w;
@@ -108,59 +175,26 @@ __device__ __forceinline__ void wn_pack_body(const WnPackParams& p, int bx) {
   } else {
     const int ks = st - S1, kb = ks >> 1, s = ks & 1;
     const bool skip = blk >= 4;
-    const bool live = row_ok && (!p.last || skip);
-    const int row = (skip && !p.last ? n : 0) + rowb;
+    const bool live = row_ok && (!last || skip);
+    const int row = (skip && !last ? n : 0) + rowb;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int k = kb * 32 + 16 * s + 8 * (j >> 2) + 4 * hh + (j & 3);
       float w = 0.f;
       if (live) {
-        if (k < n) w = p.rs_w[(long long)row * n + k];
-        else if (k == n) w = p.rs_b[row];
+        if (k < n) w = rs_w[(long long)row * n + k];
+        else if (k == n) w = rs_b[row];
       }
       v[j] = w;
     }
   }
-  unsigned hi[4], lo[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) split_bf16_pair(v[2 * j], v[2 * j + 1], hi[j], lo[j]);
-  uint4* dst = p.img + ((long long)st * 8 + blk) * 128 + lane;
-  dst[0] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
-  dst[64] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
-  if (bx == 0 && lane < 2) {
-    const unsigned one = lane ? 0x3f800000u : 0u;
-    p.img[(long long)(S1 + 8) * 8 * 128 + lane] = make_uint4(one, one, one, one);
-  }
+  wn_store_frag(t.img[i], bx, lane, v);
+  wn_store_tail<true>(t.img[i], wn_fwd_stages(CH, CH2) * 8, bx, lane);
 }
-
-__global__ __launch_bounds__(64) void wn_pack_kernel(WnPackParams p) { wn_pack_body(p, blockIdx.x); }
-
-// Every layer of a WN stack in one launch: layer blockIdx.y of tables in the kernel arguments, the per-layer body unchanged
-// (the images are the per-layer launches' byte for byte).  The top layer (nl - 1) is the `last` one.
-struct WnPackStackParams {
-  const float* in_w[WS_MAXL];
-  const float* cond_w[WS_MAXL];
-  const float* in_b[WS_MAXL];
-  const float* cond_b[WS_MAXL];
-  const float* rs_w[WS_MAXL];
-  const float* rs_b[WS_MAXL];
-  uint4* img[WS_MAXL];
-  int n, h, nl, CH, CH2;
-};
-
-__global__ __launch_bounds__(64) void wn_pack_stack_kernel(WnPackStackParams s) {
-  const int i = blockIdx.y;
-  const WnPackParams p = {s.in_w[i], s.cond_w[i], s.in_b[i], s.cond_b[i], s.rs_w[i], s.rs_b[i], s.n, s.h, i == s.nl - 1 ? 1 : 0,
-                          s.CH, s.CH2, s.img[i]};
-  wn_pack_body(p, blockIdx.x);
-}
-
-static inline int wn_ch(int n) { return (n + 15) / 16; }
-static inline int wn_ch2(int h) { return (h + 1 + 15) / 16; }
 
 extern "C" int64_t fst_wn_image_bytes(int n, int h) {
   if (n <= 0 || h <= 0) return -1;
-  return (int64_t)(3 * wn_ch(n) + wn_ch2(h) + 8) * WN_A_BYTES + 32;
+  return (int64_t)wn_fwd_stages(wn_ch(n), wn_ch2(h)) * WN_A_BYTES + 32;
 }
 
 extern "C" int fst_wn_pack(const float* in_w, const float* cond_w, const float* in_b, const float* cond_b,
@@ -169,37 +203,22 @@ extern "C" int fst_wn_pack(const float* in_w, const float* cond_w, const float* 
   FST_REQUIRE(in_w && cond_w && in_b && cond_b && rs_w && rs_b && image, "fst_wn_pack: null operand");
   FST_REQUIRE(ntaps == 3, "fst_wn_pack: the fused WN kernels are 3-tap (in_w [2n][n][3]); got %d taps", ntaps);
   FST_REQUIRE(n > 0 && n < 128 && h > 0, "fst_wn_pack: needs 0 < n < 128 (one spare K row carries the bias), h > 0; n=%d h=%d", n, h);
-  FST_REQUIRE(image_bytes == fst_wn_image_bytes(n, h), "fst_wn_pack: image is %lld bytes, expected %lld",
-              (long long)image_bytes, (long long)fst_wn_image_bytes(n, h));
-  FST_REQUIRE(fst_aligned16(image), "fst_wn_pack: image must be 16-byte aligned");
-  WnPackParams p = {in_w, cond_w, in_b, cond_b, rs_w, rs_b, n, h, last ? 1 : 0, wn_ch(n), wn_ch2(h), static_cast<uint4*>(image)};
-  const int stages = 3 * p.CH + p.CH2 + 8;
-  hipLaunchKernelGGL(wn_pack_kernel, dim3((unsigned)(stages * 8)), dim3(64), 0, (hipStream_t)stream, p);
-  FST_LAUNCH_CHECK();
-  return 0;
+  const int blocks = wn_fwd_stages(wn_ch(n), wn_ch2(h)) * 8;
+  return wn_pack_launch("fst_wn_pack", wn_pack_kernel<1>, {&in_w, &cond_w, &in_b, &cond_b, &rs_w, &rs_b}, 1, last ? 0 : -1, &image,
+                        image_bytes, fst_wn_image_bytes(n, h), {blocks, blocks}, wn_no_tests, stream, n, h);
 }
 
 extern "C" int fst_wn_pack_stack(const float* const* in_w, const float* const* cond_w, const float* const* in_b,
                                  const float* const* cond_b, const float* const* rs_w, const float* const* rs_b, int nl, int n, int h,
                                  int ntaps, void* const* images, int64_t image_bytes, void* stream) {
-  FST_REQUIRE(in_w && cond_w && in_b && cond_b && rs_w && rs_b && images, "fst_wn_pack_stack: null table");
-  FST_REQUIRE(nl >= 1 && nl <= WS_MAXL, "fst_wn_pack_stack: %d layers (1..%d)", nl, WS_MAXL);
-  FST_REQUIRE(ntaps == 3, "fst_wn_pack_stack: the fused WN kernels are 3-tap (in_w [2n][n][3]); got %d taps", ntaps);
-  FST_REQUIRE(n > 0 && n < 128 && h > 0, "fst_wn_pack_stack: needs 0 < n < 128 (one spare K row carries the bias), h > 0; n=%d h=%d", n, h);
-  FST_REQUIRE(image_bytes == fst_wn_image_bytes(n, h), "fst_wn_pack_stack: images are %lld bytes, expected %lld",
-              (long long)image_bytes, (long long)fst_wn_image_bytes(n, h));
-  WnPackStackParams s = {};
-  for (int i = 0; i < nl; ++i) {
-    FST_REQUIRE(in_w[i] && cond_w[i] && in_b[i] && cond_b[i] && rs_w[i] && rs_b[i] && images[i], "fst_wn_pack_stack: null operand in layer %d", i);
-    FST_REQUIRE(fst_aligned16(images[i]), "fst_wn_pack_stack: images must be 16-byte aligned");
-    s.in_w[i] = in_w[i]; s.cond_w[i] = cond_w[i]; s.in_b[i] = in_b[i]; s.cond_b[i] = cond_b[i]; s.rs_w[i] = rs_w[i]; s.rs_b[i] = rs_b[i];
-    s.img[i] = static_cast<uint4*>(images[i]);
-  }
-  s.n = n; s.h = h; s.nl = nl; s.CH = wn_ch(n); s.CH2 = wn_ch2(h);
-  const int stages = 3 * s.CH + s.CH2 + 8;
-  hipLaunchKernelGGL(wn_pack_stack_kernel, dim3((unsigned)(stages * 8), (unsigned)nl), dim3(64), 0, (hipStream_t)stream, s);
-  FST_LAUNCH_CHECK();
-  return 0;
+  const int blocks = wn_fwd_stages(wn_ch(n), wn_ch2(h)) * 8;
+  const auto mid = [&]() -> int {
+    FST_REQUIRE(ntaps == 3, "fst_wn_pack_stack: the fused WN kernels are 3-tap (in_w [2n][n][3]); got %d taps", ntaps);
+    FST_REQUIRE(n > 0 && n < 128 && h > 0, "fst_wn_pack_stack: needs 0 < n < 128 (one spare K row carries the bias), h > 0; n=%d h=%d", n, h);
+    return 0;
+  };
+  return wn_pack_launch("fst_wn_pack_stack", wn_pack_kernel<WS_MAXL>, {in_w, cond_w, in_b, cond_b, rs_w, rs_b}, nl, nl - 1, images,
+                        image_bytes, fst_wn_image_bytes(n, h), {blocks, blocks}, mid, stream, n, h);
 }
 
 #ifdef FST_STAMPS
@@ -420,7 +439,8 @@ __device__ __forceinline__ void wn_fwd_tile(WnFwdArgs& p, const int b, const int
   const int wave_n0 = wave_s * 32;
   const int L = p.L, n = p.n, h = p.h, CH = p.CH;
   const int S1 = 3 * CH + p.CH2;
-  const char* const zero16 = p.img + (long long)(S1 + 8) * WN_A_BYTES;
+  const char* const zero16 = p.img + (long long)(S1 + 8) * WN_A_BYTES;     // S1 + 8 = wn_fwd_stages(CH, CH2), spelt out: the
+                                                                          // call reorders this kernel's scalar code (ten to eighty instructions)
   const char* const ones16 = zero16 + 16;
   const float* const ab = p.a + (long long)b * p.a_bs;
   const float* const ub = p.u0 + (long long)b * p.u0_bs;
@@ -914,88 +934,52 @@ constexpr int WN_BWD_OCC = 2;                        // workgroups per CU the re
 #define WN_BW_SLOT (WN_BW_A + 2 * WN_BW_GS)
 #define WN_BW_LDS (3 * WN_BW_SLOT)
 
-struct WnPackBwdParams {
-  const float* rs_w;   // [2n][n] (last: [n][n])
-  int n, last, CH;
-  uint4* img;
-  int acc_order;       // the d_a stages in the k-order in which a 32x32 accumulator tile delivers its rows as a B operand
-};
-
-// workgroup bx of the n_blocks = 4·S3 of one layer's pack
-__device__ __forceinline__ void wn_pack_bwd_body(const WnPackBwdParams& p, int bx, int n_blocks) {
+// Workgroup bx of a layer's d_a / d_out stages: row block bx & 3 of stage bx >> 2, from rs_w [2n][n] (last: [n][n]).  acc_order:
+// the d_a stages in the k-order in which a 32x32 accumulator tile delivers its rows as a B operand.
+__device__ __forceinline__ void wn_pack_bwd_body(uint4* img, const float* rs_w, int n, int last, int acc_order, int bx) {
   const int lane = threadIdx.x, blk = bx & 3, st = bx >> 2;
-  const int n = p.n, hh = lane >> 5, m = blk * 32 + (lane & 31);
-  const int src = p.last ? 0 : st / p.CH, c = st - src * p.CH;
+  const int CH = wn_ch(n), hh = lane >> 5, m = blk * 32 + (lane & 31);
+  const int src = last ? 0 : st / CH, c = st - src * CH;
   float v[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     // acc_order (fst_wn_stack_bwd keeps d_a in its accumulators and multiplies straight out of them): element j of lane half
     // hh multiplies row 16c + 8(j>>2) + 4hh + (j&3) — registers 8s..8s+7 of the tile of row block c>>1, s = c&1
-    const bool perm = p.acc_order && !p.last && src == 0;
+    const bool perm = acc_order && !last && src == 0;
     const int ch = 16 * c + (perm ? 8 * (j >> 2) + 4 * hh + (j & 3) : 8 * hh + j);
-    v[j] = (m < n && ch < n) ? p.rs_w[(long long)(src * n + ch) * n + m] : 0.f;
+    v[j] = (m < n && ch < n) ? rs_w[(long long)(src * n + ch) * n + m] : 0.f;
   }
-  unsigned hi[4], lo[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) split_bf16_pair(v[2 * j], v[2 * j + 1], hi[j], lo[j]);
-  uint4* dst = p.img + ((long long)st * 4 + blk) * 128 + lane;
-  dst[0] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
-  dst[64] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
-  if (bx == 0 && lane == 0) p.img[(long long)n_blocks * 128] = make_uint4(0u, 0u, 0u, 0u);
+  wn_store_frag(img, bx, lane, v);
 }
 
-__global__ __launch_bounds__(64) void wn_pack_bwd_kernel(WnPackBwdParams p) { wn_pack_bwd_body(p, blockIdx.x, gridDim.x); }
-
-// every layer of a stack, layer blockIdx.y (the top layer is the `last` one: half the stages, its other workgroups leave)
-struct WnPackBwdStackParams {
-  const float* rs_w[WS_MAXL];
-  uint4* img[WS_MAXL];
-  int n, nl, CH, acc_order;
-};
-
-__global__ __launch_bounds__(64) void wn_pack_bwd_stack_kernel(WnPackBwdStackParams s) {
-  const int i = blockIdx.y, last = i == s.nl - 1 ? 1 : 0, n_blocks = (last ? 1 : 2) * s.CH * 4;
-  if ((int)blockIdx.x >= n_blocks) return;
-  const WnPackBwdParams p = {s.rs_w[i], s.n, last, s.CH, s.img[i], s.acc_order};
-  wn_pack_bwd_body(p, blockIdx.x, n_blocks);
+// source: rs_w.  Layer blockIdx.y; the `last` layer has half the stages, its other workgroups leave.
+template <int ML>
+__global__ __launch_bounds__(64) void wn_pack_bwd_kernel(WnPackTable<1, ML> t, int n, int acc_order) {
+  const int i = blockIdx.y, bx = blockIdx.x, last = i == t.last_layer, n_blocks = wn_bwd_stages(wn_ch(n), last) * 4;
+  if (bx >= n_blocks) return;
+  wn_pack_bwd_body(t.img[i], t.src[0][i], n, last, acc_order, bx);
+  wn_store_tail<false>(t.img[i], n_blocks, bx, threadIdx.x);
 }
 
 extern "C" int64_t fst_wn_bwd_image_bytes(int n, int last) {
   if (n <= 0) return -1;
-  return (int64_t)(last ? 1 : 2) * wn_ch(n) * WN_BW_A + 16;
+  return (int64_t)wn_bwd_stages(wn_ch(n), last) * WN_BW_A + 16;
 }
 
 extern "C" int fst_wn_pack_bwd(const float* rs_w, int n, int last, int acc_order, void* image, int64_t image_bytes, void* stream) {
   FST_REQUIRE(rs_w && image && n > 0 && n <= 128, "fst_wn_pack_bwd: bad arguments (n=%d, needs n <= 128)", n);
-  FST_REQUIRE(image_bytes == fst_wn_bwd_image_bytes(n, last), "fst_wn_pack_bwd: image is %lld bytes, expected %lld",
-              (long long)image_bytes, (long long)fst_wn_bwd_image_bytes(n, last));
-  FST_REQUIRE(fst_aligned16(image), "fst_wn_pack_bwd: image must be 16-byte aligned");
-  WnPackBwdParams p = {rs_w, n, last ? 1 : 0, wn_ch(n), static_cast<uint4*>(image), acc_order ? 1 : 0};
-  const int stages = (last ? 1 : 2) * p.CH;
-  hipLaunchKernelGGL(wn_pack_bwd_kernel, dim3((unsigned)(stages * 4)), dim3(64), 0, (hipStream_t)stream, p);
-  FST_LAUNCH_CHECK();
-  return 0;
+  return wn_pack_launch("fst_wn_pack_bwd", wn_pack_bwd_kernel<1>, {&rs_w}, 1, last ? 0 : -1, &image, image_bytes,
+                        fst_wn_bwd_image_bytes(n, last), {wn_bwd_stages(wn_ch(n), 0) * 4, wn_bwd_stages(wn_ch(n), 1) * 4}, wn_no_tests,
+                        stream, n, acc_order ? 1 : 0);
 }
 
 // images[i] of fst_wn_bwd_image_bytes(n, i == nl - 1) bytes: image_bytes is that of the layers below the top one
 extern "C" int fst_wn_pack_bwd_stack(const float* const* rs_w, int nl, int n, int acc_order, void* const* images, int64_t image_bytes,
                                      void* stream) {
   FST_REQUIRE(rs_w && images && n > 0 && n <= 128, "fst_wn_pack_bwd_stack: bad arguments (n=%d, needs n <= 128)", n);
-  FST_REQUIRE(nl >= 1 && nl <= WS_MAXL, "fst_wn_pack_bwd_stack: %d layers (1..%d)", nl, WS_MAXL);
-  FST_REQUIRE(image_bytes == fst_wn_bwd_image_bytes(n, 0), "fst_wn_pack_bwd_stack: images are %lld bytes, expected %lld",
-              (long long)image_bytes, (long long)fst_wn_bwd_image_bytes(n, 0));
-  WnPackBwdStackParams s = {};
-  for (int i = 0; i < nl; ++i) {
-    FST_REQUIRE(rs_w[i] && images[i], "fst_wn_pack_bwd_stack: null operand in layer %d", i);
-    FST_REQUIRE(fst_aligned16(images[i]), "fst_wn_pack_bwd_stack: images must be 16-byte aligned");
-    s.rs_w[i] = rs_w[i];
-    s.img[i] = static_cast<uint4*>(images[i]);
-  }
-  s.n = n; s.nl = nl; s.CH = wn_ch(n); s.acc_order = acc_order ? 1 : 0;
-  const int stages = (nl > 1 ? 2 : 1) * s.CH;
-  hipLaunchKernelGGL(wn_pack_bwd_stack_kernel, dim3((unsigned)(stages * 4), (unsigned)nl), dim3(64), 0, (hipStream_t)stream, s);
-  FST_LAUNCH_CHECK();
-  return 0;
+  return wn_pack_launch("fst_wn_pack_bwd_stack", wn_pack_bwd_kernel<WS_MAXL>, {rs_w}, nl, nl - 1, images, image_bytes,
+                        fst_wn_bwd_image_bytes(n, 0), {wn_bwd_stages(wn_ch(n), 0) * 4, wn_bwd_stages(wn_ch(n), 1) * 4}, wn_no_tests,
+                        stream, n, acc_order ? 1 : 0);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1005,30 +989,24 @@ extern "C" int fst_wn_pack_bwd_stack(const float* const* rs_w, int nl, int n, in
 // skip stages only), then 16 B of zeros.  Skip stage c: lane l holds F_i[16c + 8(l>>5) + j][blk·32 + (l&31)], F_i = W_end·W_skip,i
 // ([2h][n]; rows >= 2h and columns >= n are zero) — every element one fp32 fmaf chain over k = 0..n-1, then the hi/lo split.
 // ------------------------------------------------------------------------------------------------
-struct WnPackBwdProjParams {
-  const float* rs_w[WS_MAXL];
-  uint4* img[WS_MAXL];
-  const float* end_w;  // [2h][n]
-  int n, h2, nl, CH, CHO;
-};
-
-__global__ __launch_bounds__(64) void wn_pack_bwd_proj_stack_kernel(WnPackBwdProjParams s) {
-  const int i = blockIdx.y, last = i == s.nl - 1 ? 1 : 0, n_da = last ? 0 : s.CH, n_blocks = (n_da + s.CHO) * 4;
-  const int bx = blockIdx.x;
+// source: rs_w; end_w [2h][n] is the stack's
+__global__ __launch_bounds__(64) void wn_pack_bwd_proj_kernel(WnPackTable<1> t, const float* end_w, int n, int h2) {
+  const int i = blockIdx.y, bx = blockIdx.x, lane = threadIdx.x, last = i == t.last_layer;
+  const int n_da = last ? 0 : wn_ch(n), n_blocks = wn_bwd_proj_stages(wn_ch(n), wn_ch(h2), last) * 4;
   if (bx >= n_blocks) return;
+  wn_store_tail<false>(t.img[i], n_blocks, bx, lane);
   if ((bx >> 2) < n_da) {                              // a d_a stage: what fst_wn_pack_bwd (acc_order = 1) writes there
-    const WnPackBwdParams p = {s.rs_w[i], s.n, 0, s.CH, s.img[i], 1};
-    wn_pack_bwd_body(p, bx, n_blocks);
+    wn_pack_bwd_body(t.img[i], t.src[0][i], n, 0, 1, bx);
     return;
   }
-  const int lane = threadIdx.x, blk = bx & 3, c = (bx >> 2) - n_da;
-  const int n = s.n, m = blk * 32 + (lane & 31), hh = lane >> 5;
-  const float* const w_skip = s.rs_w[i] + (long long)(last ? 0 : n) * n;       // [n][n]: skip channel k, acts channel m
+  const int blk = bx & 3, c = (bx >> 2) - n_da;
+  const int m = blk * 32 + (lane & 31), hh = lane >> 5;
+  const float* const w_skip = t.src[0][i] + (long long)(last ? 0 : n) * n;     // [n][n]: skip channel k, acts channel m
   // the stage's 16 rows of W_end, rows >= h2 as zeros: every lane then runs the same chain of independent loads
   __shared__ float e_rows[16 * 128];
   for (int x = lane; x < 16 * n; x += 64) {
     const int r = x / n, k = x - r * n;
-    e_rows[r * 128 + k] = 16 * c + r < s.h2 ? s.end_w[(long long)(16 * c + r) * n + k] : 0.f;
+    e_rows[r * 128 + k] = 16 * c + r < h2 ? end_w[(long long)(16 * c + r) * n + k] : 0.f;
   }
   __syncthreads();
   float v[8];
@@ -1044,19 +1022,13 @@ __global__ __launch_bounds__(64) void wn_pack_bwd_proj_stack_kernel(WnPackBwdPro
   }
 #pragma unroll
   for (int j = 0; j < 8; ++j)
-    if (16 * c + 8 * hh + j >= s.h2) v[j] = 0.f;         // dead rows are zeros whatever the weights hold
-  unsigned hi[4], lo[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) split_bf16_pair(v[2 * j], v[2 * j + 1], hi[j], lo[j]);
-  uint4* dst = s.img[i] + ((long long)(bx >> 2) * 4 + blk) * 128 + lane;
-  dst[0] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
-  dst[64] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
-  if (bx == 0 && lane == 0) s.img[i][(long long)n_blocks * 128] = make_uint4(0u, 0u, 0u, 0u);
+    if (16 * c + 8 * hh + j >= h2) v[j] = 0.f;           // dead rows are zeros whatever the weights hold
+  wn_store_frag(t.img[i], bx, lane, v);
 }
 
 extern "C" int64_t fst_wn_bwd_proj_image_bytes(int n, int h2, int last) {
   if (n <= 0 || h2 <= 0) return -1;
-  return (int64_t)((last ? 0 : wn_ch(n)) + wn_ch(h2)) * WN_BW_A + 16;
+  return (int64_t)wn_bwd_proj_stages(wn_ch(n), wn_ch(h2), last) * WN_BW_A + 16;
 }
 
 // images[i] of fst_wn_bwd_proj_image_bytes(n, h2, i == nl - 1) bytes: image_bytes is that of the layers below the top one
@@ -1064,21 +1036,10 @@ extern "C" int fst_wn_pack_bwd_proj_stack(const float* const* rs_w, const float*
                                           int64_t image_bytes, void* stream) {
   FST_REQUIRE(rs_w && end_w && images && n > 0 && n <= 128 && h2 > 0 && h2 <= 64,
               "fst_wn_pack_bwd_proj_stack: bad arguments (n=%d, h2=%d; needs n <= 128, h2 <= 64)", n, h2);
-  FST_REQUIRE(nl >= 1 && nl <= WS_MAXL, "fst_wn_pack_bwd_proj_stack: %d layers (1..%d)", nl, WS_MAXL);
-  FST_REQUIRE(image_bytes == fst_wn_bwd_proj_image_bytes(n, h2, 0), "fst_wn_pack_bwd_proj_stack: images are %lld bytes, expected %lld",
-              (long long)image_bytes, (long long)fst_wn_bwd_proj_image_bytes(n, h2, 0));
-  WnPackBwdProjParams s = {};
-  for (int i = 0; i < nl; ++i) {
-    FST_REQUIRE(rs_w[i] && images[i], "fst_wn_pack_bwd_proj_stack: null operand in layer %d", i);
-    FST_REQUIRE(fst_aligned16(images[i]), "fst_wn_pack_bwd_proj_stack: images must be 16-byte aligned");
-    s.rs_w[i] = rs_w[i];
-    s.img[i] = static_cast<uint4*>(images[i]);
-  }
-  s.end_w = end_w; s.n = n; s.h2 = h2; s.nl = nl; s.CH = wn_ch(n); s.CHO = wn_ch(h2);
-  const int stages = (nl > 1 ? s.CH : 0) + s.CHO;
-  hipLaunchKernelGGL(wn_pack_bwd_proj_stack_kernel, dim3((unsigned)(stages * 4), (unsigned)nl), dim3(64), 0, (hipStream_t)stream, s);
-  FST_LAUNCH_CHECK();
-  return 0;
+  const int CH = wn_ch(n), CHO = wn_ch(h2);
+  return wn_pack_launch("fst_wn_pack_bwd_proj_stack", wn_pack_bwd_proj_kernel, {rs_w}, nl, nl - 1, images, image_bytes,
+                        fst_wn_bwd_proj_image_bytes(n, h2, 0), {wn_bwd_proj_stages(CH, CHO, 0) * 4, wn_bwd_proj_stages(CH, CHO, 1) * 4},
+                        wn_no_tests, stream, end_w, n, h2);
 }
 
 struct WnBwdParams {
@@ -1126,7 +1087,7 @@ __global__ __launch_bounds__(256, WN_BWD_OCC) void wn_layer_bwd_kernel(WnBwdPara
   const int t0 = (wg - b * p.tiles_per_seq) * WN_TN;
   const int wave_n0 = wave_s * 32;
   const int L = p.L, n = p.n, CH = p.CH;
-  const int S3 = (p.last ? 1 : 2) * CH;
+  const int S3 = wn_bwd_stages(CH, p.last);
   const char* const zero16 = p.img + (long long)S3 * WN_BW_A;
   const float* const ts_b = p.ts + (long long)b * (2 * n) * L;
   const int tcol = t0 + wave_n0;
@@ -1271,17 +1232,13 @@ extern "C" int fst_wn_layer_bwd(const float* d_a, const float* d_out, const floa
 #define DG_A_BLOCKS 13
 #define DG_A_BYTES (DG_A_BLOCKS * 2048)
 
-struct WnPackDgradParams {
-  const float* in_w;    // [2n][n][3]
-  const float* cond_w;  // [2n][h]
-  int n, h, CHK;
-  uint4* img;
-};
-
-// workgroup bx of the n_blocks = 13·CHK of one layer's pack
-__device__ __forceinline__ void wn_pack_dgrad_body(const WnPackDgradParams& p, int bx, int n_blocks) {
+// sources: in_w [2n][n][3], cond_w [2n][h].  Workgroup blockIdx.x of the 13·CHK of layer blockIdx.y.
+template <int ML>
+__global__ __launch_bounds__(64) void wn_pack_dgrad_kernel(WnPackTable<2, ML> t, int n, int h) {
+  const int i = blockIdx.y, bx = blockIdx.x;
+  const float *in_w = t.src[0][i], *cond_w = t.src[1][i];
   const int lane = threadIdx.x, ab = bx % DG_A_BLOCKS, c = bx / DG_A_BLOCKS;
-  const int n = p.n, h = p.h, hh = lane >> 5, l31 = lane & 31;
+  const int hh = lane >> 5, l31 = lane & 31;
   // block ab of the chunk -> (tap, row block)
   int tap, blk;
   if (ab < 4) { tap = 0; blk = ab; } else if (ab < 9) { tap = 1; blk = ab - 4; } else { tap = 2; blk = ab - 9; }
@@ -1293,74 +1250,41 @@ __device__ __forceinline__ void wn_pack_dgrad_body(const WnPackDgradParams& p, i
     if (k < 2 * n) {
       if (blk < 4) {
         const int m = blk * 32 + l31;
-        if (m < n) w = p.in_w[((long long)k * n + m) * 3 + tap];
+        if (m < n) w = in_w[((long long)k * n + m) * 3 + tap];
       } else {
-        if (l31 < h) w = p.cond_w[(long long)k * h + l31];
+        if (l31 < h) w = cond_w[(long long)k * h + l31];
       }
     }
     v[j] = w;
   }
-  unsigned hi[4], lo[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) split_bf16_pair(v[2 * j], v[2 * j + 1], hi[j], lo[j]);
-  uint4* dst = p.img + (long long)bx * 128 + lane;
-  dst[0] = make_uint4(hi[0], hi[1], hi[2], hi[3]);
-  dst[64] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
-  if (bx == 0 && lane == 0) p.img[(long long)n_blocks * 128] = make_uint4(0u, 0u, 0u, 0u);
-}
-
-__global__ __launch_bounds__(64) void wn_pack_dgrad_kernel(WnPackDgradParams p) { wn_pack_dgrad_body(p, blockIdx.x, gridDim.x); }
-
-// every layer of a stack, layer blockIdx.y
-struct WnPackDgradStackParams {
-  const float* in_w[WS_MAXL];
-  const float* cond_w[WS_MAXL];
-  uint4* img[WS_MAXL];
-  int n, h, CHK;
-};
-
-__global__ __launch_bounds__(64) void wn_pack_dgrad_stack_kernel(WnPackDgradStackParams s) {
-  const int i = blockIdx.y;
-  const WnPackDgradParams p = {s.in_w[i], s.cond_w[i], s.n, s.h, s.CHK, s.img[i]};
-  wn_pack_dgrad_body(p, blockIdx.x, gridDim.x);
+  wn_store_frag(t.img[i], bx, lane, v);
+  wn_store_tail<false>(t.img[i], wn_dgrad_chunks(n) * DG_A_BLOCKS, bx, lane);
 }
 
 extern "C" int64_t fst_wn_dgrad_image_bytes(int n) {
   if (n <= 0) return -1;
-  return (int64_t)((2 * n + 15) / 16) * DG_A_BYTES + 16;
+  return (int64_t)wn_dgrad_chunks(n) * DG_A_BYTES + 16;
 }
 
 extern "C" int fst_wn_pack_dgrad(const float* in_w, const float* cond_w, int n, int h, int ntaps, void* image, int64_t image_bytes,
                                  void* stream) {
   FST_REQUIRE(in_w && cond_w && image && n > 0 && n <= 128 && h > 0 && h <= 32, "fst_wn_pack_dgrad: needs n <= 128, h <= 32 (n=%d h=%d)", n, h);
   FST_REQUIRE(ntaps == 3, "fst_wn_pack_dgrad: the fused WN kernels are 3-tap (in_w [2n][n][3]); got %d taps", ntaps);
-  FST_REQUIRE(image_bytes == fst_wn_dgrad_image_bytes(n), "fst_wn_pack_dgrad: image is %lld bytes, expected %lld",
-              (long long)image_bytes, (long long)fst_wn_dgrad_image_bytes(n));
-  FST_REQUIRE(fst_aligned16(image), "fst_wn_pack_dgrad: image must be 16-byte aligned");
-  WnPackDgradParams p = {in_w, cond_w, n, h, (2 * n + 15) / 16, static_cast<uint4*>(image)};
-  hipLaunchKernelGGL(wn_pack_dgrad_kernel, dim3((unsigned)(p.CHK * DG_A_BLOCKS)), dim3(64), 0, (hipStream_t)stream, p);
-  FST_LAUNCH_CHECK();
-  return 0;
+  const int blocks = wn_dgrad_chunks(n) * DG_A_BLOCKS;
+  return wn_pack_launch("fst_wn_pack_dgrad", wn_pack_dgrad_kernel<1>, {&in_w, &cond_w}, 1, -1, &image, image_bytes,
+                        fst_wn_dgrad_image_bytes(n), {blocks, blocks}, wn_no_tests, stream, n, h);
 }
 
 extern "C" int fst_wn_pack_dgrad_stack(const float* const* in_w, const float* const* cond_w, int nl, int n, int h, int ntaps,
                                        void* const* images, int64_t image_bytes, void* stream) {
   FST_REQUIRE(in_w && cond_w && images && n > 0 && n <= 128 && h > 0 && h <= 32, "fst_wn_pack_dgrad_stack: needs n <= 128, h <= 32 (n=%d h=%d)", n, h);
-  FST_REQUIRE(nl >= 1 && nl <= WS_MAXL, "fst_wn_pack_dgrad_stack: %d layers (1..%d)", nl, WS_MAXL);
-  FST_REQUIRE(ntaps == 3, "fst_wn_pack_dgrad_stack: the fused WN kernels are 3-tap (in_w [2n][n][3]); got %d taps", ntaps);
-  FST_REQUIRE(image_bytes == fst_wn_dgrad_image_bytes(n), "fst_wn_pack_dgrad_stack: images are %lld bytes, expected %lld",
-              (long long)image_bytes, (long long)fst_wn_dgrad_image_bytes(n));
-  WnPackDgradStackParams s = {};
-  for (int i = 0; i < nl; ++i) {
-    FST_REQUIRE(in_w[i] && cond_w[i] && images[i], "fst_wn_pack_dgrad_stack: null operand in layer %d", i);
-    FST_REQUIRE(fst_aligned16(images[i]), "fst_wn_pack_dgrad_stack: images must be 16-byte aligned");
-    s.in_w[i] = in_w[i]; s.cond_w[i] = cond_w[i];
-    s.img[i] = static_cast<uint4*>(images[i]);
-  }
-  s.n = n; s.h = h; s.CHK = (2 * n + 15) / 16;
-  hipLaunchKernelGGL(wn_pack_dgrad_stack_kernel, dim3((unsigned)(s.CHK * DG_A_BLOCKS), (unsigned)nl), dim3(64), 0, (hipStream_t)stream, s);
-  FST_LAUNCH_CHECK();
-  return 0;
+  const int blocks = wn_dgrad_chunks(n) * DG_A_BLOCKS;
+  const auto mid = [&]() -> int {
+    FST_REQUIRE(ntaps == 3, "fst_wn_pack_dgrad_stack: the fused WN kernels are 3-tap (in_w [2n][n][3]); got %d taps", ntaps);
+    return 0;
+  };
+  return wn_pack_launch("fst_wn_pack_dgrad_stack", wn_pack_dgrad_kernel<WS_MAXL>, {in_w, cond_w}, nl, nl - 1, images, image_bytes,
+                        fst_wn_dgrad_image_bytes(n), {blocks, blocks}, mid, stream, n, h);
 }
 
 // One data-gradient stage into the ring slot at sl, as 1-KiB LDS-DMA pieces dealt round the eight waves: the 13 weight blocks of
@@ -1369,8 +1293,7 @@ extern "C" int fst_wn_pack_dgrad_stack(const float* const* in_w, const float* co
 __device__ __forceinline__ void wn_dgrad_issue(char* sl, const char* img, const float* dg_b, int c, int t0, int n, int L, int dil,
                                                int nblkw, int gsw, int wave_s, int lane) {
   const char* asrc = img + (long long)c * DG_A_BYTES;
-  // 16 bytes of zeros behind the last chunk: (2n + 15) / 16 is the CHK of both launchers and of wn_pack_dgrad_kernel's grid
-  const char* const zero16 = img + (long long)((2 * n + 15) / 16) * DG_A_BYTES;
+  const char* const zero16 = img + (long long)wn_dgrad_chunks(n) * DG_A_BYTES;   // 16 bytes of zeros behind the last chunk
   const float* xb = dg_b + (long long)(16 * c) * L;
   const int c_count = min(16, 2 * n - 16 * c);
   const int w4 = (t0 - dil) & ~3;                        // 16-byte aligned start of the window (first column any tap needs)
@@ -1571,7 +1494,7 @@ extern "C" int fst_wn_layer_dgrad(const float* dg, const void* image, int64_t im
   WnDgradParams p;
   p.dg = dg; p.img = static_cast<const char*>(image); p.d_a = d_a; p.d_a_new = d_a_new; p.d_u0 = d_u0; p.d_u0_bs = d_u0_bs;
   p.row_sums = row_sums;
-  p.B = B; p.L = L; p.n = n; p.h = h; p.dil = dil; p.CHK = (2 * n + 15) / 16;
+  p.B = B; p.L = L; p.n = n; p.h = h; p.dil = dil; p.CHK = wn_dgrad_chunks(n);
   p.tiles_per_seq = (L + DG_TN - 1) / DG_TN;
   p.n_wg = B * p.tiles_per_seq;
   FST_REQUIRE(row_sums == nullptr || row_sums_rows == p.n_wg, "fst_wn_layer_dgrad: row_sums has %lld rows, the launch has %d "
@@ -1693,7 +1616,7 @@ __global__ __launch_bounds__(512, 2) void wn_stack_bwd_kernel(WnStackParams p_by
 
   // layer i's W_rsᵀ image ([d_a stages][skip stages]; the top layer: skip stages only): one 1-KiB piece per wave and stage
   auto issue_res = [&](int i) {
-    const int S3 = (i == p.nl - 1 ? 0 : CH) + p.SCH;
+    const int S3 = wn_bwd_proj_stages(CH, p.SCH, i == p.nl - 1);
     const char* const img = p.img_b[i];
     for (int c = 0; c < S3; ++c)
       lds_dma16(img + (long long)c * WN_BW_A + wave_s * 1024 + lane * 16, ldsb + c * WN_BW_A + wave_s * 1024);
@@ -1940,7 +1863,7 @@ static int wn_stack_bwd_launch(const char* who, const float* const* ts, const vo
   FST_REQUIRE(fst_aligned16(skip) && fst_aligned16(d_u0), "%s: %s / d_u0 must be 16-byte aligned", who, skip_rows == n ? "d_out" : "d_o");
   FST_REQUIRE(lds_bytes <= 160 * 1024, "%s: %zu bytes of LDS", who, lds_bytes);
   p.d_out = skip; p.d_u0 = d_u0; p.d_u0_bs = d_u0_bs;
-  p.nl = nl; p.B = B; p.L = L; p.n = n; p.h = h; p.CH = wn_ch(n); p.CHK = (2 * n + 15) / 16;
+  p.nl = nl; p.B = B; p.L = L; p.n = n; p.h = h; p.CH = wn_ch(n); p.CHK = wn_dgrad_chunks(n);
   p.SR = skip_rows; p.SCH = wn_ch(skip_rows);
   FST_REQUIRE((size_t)(p.CH + p.SCH) * WN_BW_A <= WS_LDS_A, "%s: a weight image of %d stages does not fit its LDS", who, p.CH + p.SCH);
   if (int rc = fst_allow_full_lds((const void*)wn_stack_bwd_kernel, who)) return rc;
