@@ -21,6 +21,7 @@ from .data import DeviceDataset, DeviceLoader, EpochFeeder, EvalPlan, TestData, 
 from .ops import eval_finish, eval_fold, feed_batch, vote_fold, vote_weights
 from .voting import (collect_logits, multi_source_vote, multi_source_voting, precision_weights,
                      precision_weights_from_confusion, vote_scores)
+from .monitor import TransferMonitor, mmd2, mmd2_reference
 from .evaluate import Evaluator, VotingEvaluator, make_voter
 from .checkpoint import (eval_accuracy, load_source_classification_modules, load_target_classification_modules,
                          save_source_classification_modules, save_target_classification_modules)

@@ -12,7 +12,7 @@ from typing import Optional
 
 import torch
 
-ABI_VERSION = 27
+ABI_VERSION = 28
 _LIB_NAME = "libfst_hip.so"
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FST_HIP_LIB", os.path.join(_HERE, _LIB_NAME))     # override: diagnostic builds only
@@ -150,6 +150,11 @@ _SIGNATURES = {
     "fst_cpc_nce_fwd": (c_int, [_P, c_int64, c_int64, c_int64, _I32P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_void_p]),
     "fst_cpc_nce_bwd": (c_int, [_P, c_int64, c_int64, c_int64, _I32P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P,
                                 c_void_p]),
+    "fst_mmd_gram_splits": (c_int, [c_int, c_int]),
+    "fst_mmd_gram_workspace_floats": (c_int64, [c_int, c_int]),
+    "fst_mmd_centre": (c_int, [_P, c_int64, c_int, c_int, _P, c_void_p]),
+    "fst_mmd_gram": (c_int, [_P, _I32P, _P, c_int, c_int, _P, _P, _P, c_int64, c_void_p]),
+    "fst_mmd_fold": (c_int, [_P, _I32P, c_int, _I32P, c_int, c_int, c_float, _P, _P, _P, _P, _P, _P, c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

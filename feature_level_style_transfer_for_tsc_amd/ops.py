@@ -3034,3 +3034,117 @@ def vote_fold(logits: Sequence[Tensor], scale: Tensor, labels: Tensor, valid: Te
     ``overflow += 1``.  All words are read when the kernels run.  On CPU tensors the same in plain torch fp64: the executable
     specification — equal predictions, confusion, hits and state words, scores equal up to the order of a row's sums."""
     VoteFoldCall(logits, scale, labels, valid, state, member_hits, confusion, pred_out, scores_out, sharpen, capacity, scratch)()
+
+
+# ---- transfer monitor: pooled Gram of up to four row sets, and its fold into MMD² per pair of sets (csrc/mmd.hip, monitor.py)
+MMD_MAX_SETS, MMD_MAX_ROWS, MMD_MAX_PAIRS, MMD_MAX_KERNELS = 4, 1024, 8, 16           # FST_MMD_* of include/fst_hip.h
+
+
+def _mmd_sets(who: str, sets: Sequence[Tensor]):
+    """The checks ``mmd_centre`` and ``mmd_gram`` share: fp32 [n_s, D] matrices on one GPU with unit column stride, rows that do not
+    overlap and a 16-byte aligned start.  Returns (rows per set, row stride per set, D)."""
+    if not 1 <= len(sets) <= MMD_MAX_SETS:
+        raise ValueError(f"{who}: {len(sets)} sets; 1..{MMD_MAX_SETS}")
+    D = sets[0].size(1) if sets[0].dim() == 2 else -1
+    rows, lds = [], []
+    for i, t in enumerate(sets):
+        _lib.require_gpu_tensor(t, f"{who}: set {i}")
+        if t.dim() != 2 or t.size(0) < 1 or t.size(1) != D or D < 1 or (D > 1 and t.stride(1) != 1) or \
+                (t.size(0) > 1 and t.stride(0) < D) or t.data_ptr() % 16 or t.device != sets[0].device:
+            raise ValueError(f"{who}: set {i} must be a 16-byte aligned fp32 [n, {D}] matrix with unit column stride and a row stride of "
+                             f"at least {D} on {sets[0].device}, got {tuple(t.shape)} strides {tuple(t.stride())}")
+        rows.append(t.size(0))
+        lds.append(t.stride(0) if t.size(0) > 1 else max(D, t.stride(0)))
+    if sum(rows) > MMD_MAX_ROWS:
+        raise ValueError(f"{who}: {sum(rows)} rows in all; at most {MMD_MAX_ROWS}")
+    return rows, lds, D
+
+
+@torch.no_grad()
+def mmd_centre(x: Tensor) -> Tensor:
+    """The column mean of one row set, fp32 [D] (``fst_mmd_centre``: one launch, a fixed order of additions)."""
+    (n,), (ld,), D = _mmd_sets("mmd_centre", [x])
+    c = torch.empty(D, device=x.device, dtype=torch.float32)
+    t0 = KERNEL_TIMER.begin() if KERNEL_TIMER is not None else None
+    check(_lib.load().fst_mmd_centre(ptr(x), ld, n, D, ptr(c), stream_ptr()), "fst_mmd_centre")
+    if t0 is not None:
+        KERNEL_TIMER.end("mmd_centre_kernel", t0, float(n) * D, 4.0 * (n + 1) * D)
+    return c
+
+
+def mmd_gram_splits(R: int, D: int) -> int:
+    """How many slabs ``mmd_gram`` cuts ``D`` columns into (it depends on ``D`` alone)."""
+    return int(_lib.load().fst_mmd_gram_splits(int(R), int(D)))
+
+
+@torch.no_grad()
+def mmd_gram(sets: Sequence[Tensor], centre: Optional[Tensor] = None) -> Tensor:
+    """G [R, R] = Zc·Zcᵀ in fp32 for the pooled rows Z = [sets[0]; sets[1]; ...] (up to four fp32 [n_s, D] matrices anywhere in
+    memory, R = Σ n_s <= 1024) minus ``centre`` (fp32 [D], subtracted in fp32 before the bf16 split; None: nothing is subtracted).
+    ``fst_mmd_gram``: split-bf16 products over the upper-triangular tiles only, K slabs added in a fixed order; G equals its transpose
+    bit for bit, two calls give equal bits, and the bits of G[i, j] depend on rows i and j only."""
+    lib = _lib.load()
+    rows, lds, D = _mmd_sets("mmd_gram", sets)
+    if MATH != "bf16x3":
+        raise ValueError(f"mmd_gram is a split-bf16 kernel (FST_MATH={MATH}); monitor.pooled_gram composes the exact-f32 Gram")
+    if centre is not None:
+        _lib.require_gpu_tensor(centre, "mmd_gram: centre")
+        if centre.shape != (D,) or not centre.is_contiguous() or centre.device != sets[0].device:
+            raise ValueError(f"mmd_gram: the centre must be a contiguous fp32 [{D}] vector on {sets[0].device}, got {tuple(centre.shape)}")
+    R, n = sum(rows), len(sets)
+    G = torch.empty(R, R, device=sets[0].device, dtype=torch.float32)
+    ws_n = int(lib.fst_mmd_gram_workspace_floats(R, D))
+    ws = torch.empty(ws_n, device=G.device, dtype=torch.float32)
+    t0 = KERNEL_TIMER.begin() if KERNEL_TIMER is not None else None
+    check(lib.fst_mmd_gram((ctypes.c_void_p * n)(*[t.data_ptr() for t in sets]), (ctypes.c_int32 * n)(*rows), (ctypes.c_int64 * n)(*lds), n, D,
+                           ptr(centre), ptr(G), ptr(ws), ws_n, stream_ptr()), "fst_mmd_gram")
+    if t0 is not None:
+        KERNEL_TIMER.end("mmd_gram_kernel bf3", t0, 2.0 * R * R * D, 4.0 * (R * D + R * R))
+    return G
+
+
+def _mmd_words(who: str, name: str, t: Optional[Tensor], dtype, numel: int, dev) -> None:
+    if t is None:
+        return
+    if t.dtype != dtype or t.numel() != numel or not t.is_contiguous() or t.device != dev:
+        raise ValueError(f"{who}: {name} must be {numel} contiguous {dtype} word(s) on {dev}")
+
+
+@torch.no_grad()
+def mmd_fold(G: Tensor, rows: Sequence[int], pairs: Sequence[Tuple[int, int]], kernels: int, mul: float, out: Tensor, sums: Tensor,
+             count: Tensor, nonfinite: Tensor, bandwidth: Optional[Tensor] = None, live: Optional[Tensor] = None) -> None:
+    """MMD² per pair of row sets from their pooled Gram (``fst_mmd_fold``: one launch, one workgroup per pair, all in fp64; the
+    arithmetic is ``monitor.mmd2_from_gram``'s).  ``G`` fp32 [R, R] as ``mmd_gram`` wrote it for sets of ``rows`` rows; ``pairs``: up
+    to 8 (a, b) of set indices; ``out`` fp64 [len(pairs), 5] = mmd2, bandwidth, mean d² within a, within b, between.  ``bandwidth``:
+    one fp64 device word that replaces the mean-distance bandwidth while it is positive; ``live``: one int32 device word, 0 = report
+    only; ``mul`` crosses the ABI as fp32.  Otherwise a pair whose mmd2 is finite adds its five numbers to ``sums`` (fp64, the shape of ``out``) and 1 to its ``count``
+    (int32 [len(pairs)]); one whose mmd2 is not adds 1 to the int32 word ``nonfinite``.  Every word is read when the kernel runs."""
+    who = "mmd_fold"
+    _lib.require_gpu_tensor(G, f"{who}: G")
+    rows, pairs = [int(r) for r in rows], [(int(a), int(b)) for a, b in pairs]
+    R, n, P = sum(rows), len(rows), len(pairs)
+    if not 1 <= n <= MMD_MAX_SETS or min(rows) < 1 or R > MMD_MAX_ROWS or G.shape != (R, R) or not G.is_contiguous():
+        raise ValueError(f"{who}: G must be a contiguous fp32 [{R}, {R}] matrix for 1..{MMD_MAX_SETS} sets of {rows} rows "
+                         f"(at most {MMD_MAX_ROWS} in all), got {tuple(G.shape)}")
+    if not 1 <= P <= MMD_MAX_PAIRS:
+        raise ValueError(f"{who}: {P} pairs; 1..{MMD_MAX_PAIRS}")
+    for a, b in pairs:
+        if not (0 <= a < n and 0 <= b < n and a != b) or rows[a] < 2 or rows[b] < 2:
+            raise ValueError(f"{who}: pair ({a}, {b}) of {n} sets of {rows} rows: two different sets of at least 2 rows each")
+    if isinstance(kernels, bool) or not isinstance(kernels, int) or not 1 <= kernels <= MMD_MAX_KERNELS or \
+            not isinstance(mul, (int, float)) or not 0.0 < float(mul) <= 1e30:
+        raise ValueError(f"{who}: kernels {kernels!r} (1..{MMD_MAX_KERNELS}), mul {mul!r} (0 < mul <= 1e30)")
+    dev = G.device
+    _mmd_words(who, "out", out, torch.float64, 5 * P, dev)
+    _mmd_words(who, "sums", sums, torch.float64, 5 * P, dev)
+    _mmd_words(who, "count", count, torch.int32, P, dev)
+    _mmd_words(who, "nonfinite", nonfinite, torch.int32, 1, dev)
+    _mmd_words(who, "bandwidth", bandwidth, torch.float64, 1, dev)
+    _mmd_words(who, "live", live, torch.int32, 1, dev)
+    t0 = KERNEL_TIMER.begin() if KERNEL_TIMER is not None else None
+    check(_lib.load().fst_mmd_fold(ptr(G), (ctypes.c_int32 * n)(*rows), n, (ctypes.c_int32 * (2 * P))(*[v for p in pairs for v in p]), P,
+                                   kernels, float(mul), ptr(bandwidth), ptr(live), ptr(out), ptr(sums), ptr(count), ptr(nonfinite),
+                                   stream_ptr()), "fst_mmd_fold")
+    if t0 is not None:
+        N2 = sum((rows[a] + rows[b]) ** 2 for a, b in pairs)
+        KERNEL_TIMER.end("mmd_fold_kernel", t0, float(kernels) * N2, 8.0 * N2)

@@ -24,6 +24,10 @@ Gradient norms and clipping (``JointTrainer.enable_grad_clip()``): per-module L2
 to read in every report, and caps per module and on the whole that scale those gradients in place — what
 ``torch.nn.utils.clip_grad_norm_`` does with a host decision — computed and applied on the device, under graph replay too.
 
+Transfer monitor (``JointTrainer.enable_transfer_monitor()``, monitor.py): in place of the feature dumps for t-SNE plots (:564-621,
+:792-797), the multi-kernel MMD² between the target, source-to-target and source feature sets and between the source, t2s and
+s2t2s hidden vectors in every report, computed on the device, under graph replay too; ``aux`` still hands out the raw tensors.
+
 Weight averaging, gradient accumulation and device-resident input, which both trainers offer, are the mixins of modes.py.
 """
 from __future__ import annotations
@@ -41,6 +45,7 @@ from .cpc import CPC
 from . import dist as _dist
 from .dist import GradBucket
 from .modes import _enable_from_arg, _Fed, _GradAccumulating, _WeightAveraging, _WindowOpens
+from .monitor import _TransferMonitoring
 from .optim import (MAX_GROUPS, _capturing, AnomalyGuard, FusedRMSprop, GradClip, SharedStepAdam, accumulate, count_nonfinite, guard_copy,
                     push_lr, push_words, rmsprop_step_many, scale_by_group, sumsq_norms)
 from .os_cnn import OS_CNN, OS_CNN_res, build_layer_with_layer_parameter
@@ -238,7 +243,7 @@ class JointConfig:
     nf_end_std: float = 0.0       # >0: draw WN.end (zero-init in the reference) so the flow is non-degenerate
 
 
-class JointTrainer(_WeightAveraging, _GradAccumulating, _Fed):
+class JointTrainer(_WeightAveraging, _GradAccumulating, _Fed, _TransferMonitoring):
     MODULES = ("fe_t", "clf_t", "fe_s", "dimunif", "clf_s", "probtransfer", "nf", "noise", "ad_net", "fd_s", "cpc")
     LRS = {"fe_t": 0.001, "clf_t": 0.003, "fe_s": 0.001, "dimunif": 0.001, "clf_s": 0.003, "probtransfer": 0.001,
            "nf": 0.001, "noise": 0.005, "ad_net": 0.001, "fd_s": 0.001}       # train_and_test.py:97-106
@@ -246,17 +251,19 @@ class JointTrainer(_WeightAveraging, _GradAccumulating, _Fed):
     # gradients; "losses" = the step's loss scalars (per rank under data parallelism: reported, never part of the verdict);
     # "buffers" = the BatchNorm running statistics and NoiseTransfer sums the forward pass wrote (decide without a GradBucket only)
     ANOMALY_GROUPS = MODULES + ("gradnorm", "losses", "buffers")
+    TRANSFER_AUX = ("feat_s", "pool_s", "tr_t", "tr_s2t")                       # aux entries that reach a report with the transfer monitor on only
 
     def __init__(self, cfg: JointConfig, device, bucket: Optional[GradBucket] = None, fe_t_spec=None, clf_spec=None,
                  fe_s_spec=None, sync: str = "ddp", device_hparams: bool = False, anomaly_guard: bool = False, grad_clip=None,
-                 weight_average=None, grad_accumulation=None):
+                 weight_average=None, grad_accumulation=None, transfer_monitor=None):
         """``sync`` (with a bucket): "ddp" = per-rank batch statistics (SURVEY §8e mode A); "global" = every
         batch-coupled quantity over the samples of all ranks (mode B, eager only) — N ranks reproduce the
         single-process step on the concatenated batch.  ``device_hparams``: ``enable_device_hparams()`` at once;
         ``anomaly_guard``: ``enable_anomaly_guard()`` at once.  ``grad_clip``: ``enable_grad_clip()`` at once — True for norms
         only, a number for ``max_norm``, or a dict of its keyword arguments.  ``weight_average``: ``enable_weight_average()`` at
         once — True, a decay, or a dict of its keyword arguments.  ``grad_accumulation``: ``enable_grad_accumulation()`` at once,
-        with that many steps."""
+        with that many steps.  ``transfer_monitor``: ``enable_transfer_monitor()`` at once — True, a number of kernels, or a dict of
+        its keyword arguments."""
         if sync not in ("ddp", "global"):
             raise ValueError(f"sync must be 'ddp' or 'global', got {sync!r}")
         self.cfg, self.device, self.bucket, self.sync = cfg, device, bucket, sync
@@ -331,6 +338,7 @@ class JointTrainer(_WeightAveraging, _GradAccumulating, _Fed):
         _enable_from_arg(self.enable_grad_clip, grad_clip, "max_norm")
         _enable_from_arg(self.enable_weight_average, weight_average, "decay")
         _enable_from_arg(self.enable_grad_accumulation, grad_accumulation, "steps")
+        _enable_from_arg(self.enable_transfer_monitor, transfer_monitor, "kernels")
 
     # ------------------------------------------------------------------ weight averaging (the methods are _WeightAveraging's)
     def _ema_modules(self) -> Dict[str, nn.Module]:
@@ -672,7 +680,8 @@ class JointTrainer(_WeightAveraging, _GradAccumulating, _Fed):
         "schedules": the eleven schedulers' state, CPC's learning rate (the RMSprops' are in their ``param_groups``), the epoch of
         the last step and its loss coefficients.  With ``enable_grad_clip()`` on, also "grad_clip": its limits; with
         ``enable_weight_average()`` on, also "weight_average": decay, warm-up flag, update counts and the averaged tensors; with
-        ``enable_grad_accumulation()`` on, also "grad_accumulation": its steps; with a feeder attached (``attach_feeder``), also
+        ``enable_grad_accumulation()`` on, also "grad_accumulation": its steps; with ``enable_transfer_monitor()`` on, also
+        "transfer_monitor": its settings, running sums and counts; with a feeder attached (``attach_feeder``), also
         "feeder": the epoch's kind and the feeder's generator state, epoch, cursor and plan, which ``load_state_dict`` puts into
         the feeder attached then (without one the entry is ignored).  Raises while an accumulation window is open: half a window
         is no state a run could resume from."""
@@ -711,6 +720,7 @@ class JointTrainer(_WeightAveraging, _GradAccumulating, _Fed):
             **({"grad_clip": {"max_norm": self._clip_max, "per_module": dict(self._clip_per)}} if self.grad_clip else {}),
             **({"weight_average": self._ema_state_dict()} if self.weight_average is not None else {}),
             **({"grad_accumulation": {"steps": self.grad_accumulation.steps_host}} if self.grad_accumulation is not None else {}),
+            **({"transfer_monitor": self.transfer_monitor.state_dict()} if self.transfer_monitor is not None else {}),
             **self._fed_state_dict(),                                         # "feeder", while one is attached: its plan and position
         }
 
@@ -773,6 +783,8 @@ class JointTrainer(_WeightAveraging, _GradAccumulating, _Fed):
             if self.grad_accumulation is None:
                 self.enable_grad_accumulation(sd["grad_accumulation"]["steps"])
             self.set_grad_accumulation(sd["grad_accumulation"]["steps"])
+        if "transfer_monitor" in sd:                                          # likewise; sums, counts and bandwidth restored in place
+            self._transfer_load_state_dict(sd["transfer_monitor"])
         self._fed_load_state_dict(sd)
 
     def save_state(self, path: str) -> None:
@@ -818,7 +830,10 @@ class JointTrainer(_WeightAveraging, _GradAccumulating, _Fed):
             t.record_stream(self._side)
         losses = {"nf_t": nf_t, "nf_s": nf_s, "ce_t": ce_t, "sl_t": sl_t, "ce_s": ce_s, "sl_s": sl_s, "cdan": cdan,
                   "ce_s2t2s": ce_s2t2s, "fd_s": fd}
-        aux = {"logit_t": logit_t, "logit_s": logit_s, "logit_s2t": logit_s2t, "feat_t": feat_t, "feat_s2t": feat_s2t}
+        # with the two feature tensors, the tensors the reference dumps for its t-SNE plots (:564-581, :604-621): what the
+        # transfer monitor measures
+        aux = {"logit_t": logit_t, "logit_s": logit_s, "logit_s2t": logit_s2t, "feat_t": feat_t, "feat_s2t": feat_s2t, "feat_s": feat_s,
+               "pool_s": pool_s, "tr_t": tr_t, "tr_s2t": tr_s2t}
         return losses, aux
 
     # ------------------------------------------------------------------ pre-training phases (train_and_test.py:141-494)
@@ -1200,7 +1215,11 @@ class JointTrainer(_WeightAveraging, _GradAccumulating, _Fed):
         norms = torch.stack(torch._foreach_norm([g for gs in g_t + g_s for g in gs])).view(len(g_t) + len(g_s), -1).sum(dim=1)
         base_t, base_s = norms[: len(g_t)], norms[len(g_t):]
         report = {k: v.detach() for k, v in L.items()}
-        report.update({k: v.detach() for k, v in aux.items()})
+        # (with the transfer monitor off a report holds the entries it always held: the monitor's four extra tensors stay in aux)
+        mine = () if self.transfer_monitor is not None else self.TRANSFER_AUX
+        report.update({k: v.detach() for k, v in aux.items() if k not in mine})
+        if self.transfer_monitor is not None:                                 # this batch's MMD² for the four pairs; reads only
+            report["transfer"] = self._transfer_measure(report)
         # scalars that must be identical on every rank: loss values and gradient-norm bases (10 floats)
         scal = torch.cat([lt.detach(), ls.detach(), base_t, base_s]).contiguous()
         mid = {"report": report, "scal": scal, "loss_keys": tuple(L)}

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define FST_ABI_VERSION 27
+#define FST_ABI_VERSION 28
 
 int fst_version(void);
 const char* fst_last_error(void);
@@ -811,6 +811,46 @@ int fst_vote_weights(const void* const* confusion_host, int K, int C, float base
 int fst_vote_fold(const float* const* logits_host, int K, int64_t ld, const int64_t* labels, int64_t B, int C, const double* scale,
                   const void* valid_dev, void* state_dev, void* member_hits_dev, void* confusion_dev, int64_t* pred_out,
                   double* scores_out, float sharpen, int64_t capacity, void* scratch, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Transfer monitor (ABI v28; csrc/mmd.hip, monitor.py): the multi-kernel maximum mean discrepancy between feature sets — what the
+ * reference's t-SNE dumps show by eye (train_and_test.py:564-621, :792-797).  Every argument is validated on the host before the
+ * first launch: a refused call has written nothing.  Every device word is read when its kernel RUNS.  No float atomics, no zero
+ * fill: same inputs, same bits.
+ *
+ * mmd_centre: centre[k] = the mean of column k over the n rows of one set x [n][ld], ld >= D (one launch; four row quarters per
+ * column, each summed in row order, joined as (0 + 1) + (2 + 3)).  Pointers 4-byte aligned.
+ *
+ * mmd_gram: x_host / rows_host / ld_host are host arrays of n_sets <= 4 entries: device pointers to fp32 row sets X_s [rows_s][ld_s],
+ * 16-byte aligned, ld_s >= D, anywhere in memory; R = sum rows_s <= 1024; 1 <= D <= 2^28.  centre: fp32 [D] or NULL.  Writes the
+ * contiguous G [R][R] = Zc·Zc^T of the pooled rows Z = [X_0; X_1; ...] minus the centre (subtracted in fp32 while a row is staged),
+ * in split-bf16 on the matrix cores.  Only the upper-triangular 128 x 128 tiles are computed; the reduce writes G_ij and G_ji from
+ * one sum, so G equals its transpose bit for bit.  K is cut into slabs of 8192 columns (mmd_gram_splits; the cut depends on D
+ * alone), partial tiles go to `workspace` (mmd_gram_workspace_floats(R, D) floats, 16-byte aligned) and are added in slab order.
+ * The bits of G_ij depend on rows i and j only: not on the other sets of the call, nor on the rows' place in the pool.  Columns
+ * past D in the last 32-column stage enter as zeros and are not read.  No output overlaps an input.
+ *
+ * mmd_fold: G as mmd_gram wrote it for the sets rows_host [n_sets]; pairs_host: n_pairs <= 8 pairs (a, b) of set indices, a != b,
+ * both sets of at least 2 rows.  One workgroup per pair, all in fp64: with x = set a (n rows), y = set b (m rows), N = n + m,
+ *   d2_ij = max(G_ii + G_jj - 2 G_ij, 0) (a NaN stays one), d2_ii = 0;   bw = sum_{i != j} d2_ij / (N^2 - N), replaced by
+ *   *bandwidth_override_dev when that word (fp64, may be NULL) is positive;   k_ij = sum_{q < kernels} exp(-d2_ij / (bw mul^(q - kernels/2)));
+ *   mmd2 = sum_{i != j in x} k / (n (n - 1)) + sum_{i != j in y} k / (m (m - 1)) - 2 sum_{i in x, j in y} k / (n m);  bw == 0: mmd2 = 0.
+ * out [n_pairs][5] (fp64) = mmd2, bw, mean d2 within x, within y, between.  Unless *live_dev (int32, may be NULL) is 0: a pair whose
+ * mmd2 is finite adds its five numbers to sum [n_pairs][5] and 1 to count [n_pairs] (int32); one whose mmd2 is not adds 1 to the
+ * int32 word *nonfinite and leaves the sums alone.  1 <= kernels <= 16, 0 < mul <= 1e30 (it arrives as fp32 and is widened).
+ * ------------------------------------------------------------------------------------------- */
+#define FST_MMD_MAX_SETS 4
+#define FST_MMD_MAX_ROWS 1024
+#define FST_MMD_MAX_PAIRS 8
+#define FST_MMD_MAX_KERNELS 16
+int fst_mmd_gram_splits(int R, int D);
+int64_t fst_mmd_gram_workspace_floats(int R, int D);
+int fst_mmd_centre(const float* x, int64_t ld, int n, int D, float* centre, void* stream);
+int fst_mmd_gram(const float* const* x_host, const int32_t* rows_host, const int64_t* ld_host, int n_sets, int D, const float* centre,
+                 float* G, float* workspace, int64_t workspace_floats, void* stream);
+int fst_mmd_fold(const float* G, const int32_t* rows_host, int n_sets, const int32_t* pairs_host, int n_pairs, int kernels, float mul,
+                 const double* bandwidth_override_dev, const int32_t* live_dev, double* out, double* sum, int32_t* count,
+                 int32_t* nonfinite, void* stream);
 
 #ifdef __cplusplus
 }
